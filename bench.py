@@ -9,7 +9,12 @@ The 64 events are laid out disjointly on a T_v = 8192 video so that all 64x128 f
 (--overlap uses SURVEY 8-d's T_v = 160 one-video layout instead, where events share rows).
 metric = decoder timesteps/s = (iterations x S x n_gpus) / wall time; every rank works on its own video (weak scaling).
 
-usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--overlap] [--no-cpu] [--no-roofline]
+A plain run sets up, warms up, times exactly K steps back to back (ms_per_step = their wall time / K) and prints the result line.
+--full adds everything else measured after the headline: the native_f32 figure, the roofline passes, the gradient-exchange pass of
+several ranks, configs 2 and 5 and the CPU baseline (each still switched off by its --no-* option).
+--dump-outputs DIR writes what the last timed step handed its caller (DIR/<name>.npy, float32, at most 64 MB; see dump_outputs).
+
+usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--overlap] [--full] [--no-cpu] [--no-roofline] [--dump-outputs DIR]
 """
 import argparse
 import ctypes as C
@@ -92,7 +97,7 @@ class Workload(object):
             from echr_amd import models as EM
             from echr_amd.misc.utils import TAPModelCriterion
             torch.manual_seed(0)
-            tap_model = EM.setup_tap(opt).to(dev)
+            self.tap_model = tap_model = EM.setup_tap(opt).to(dev)
             tap_model.train()
             tap_arena = None if args.no_arena else tap_model.build_arena()
             tap_optim = ClampAdam(tap_model.parameters(), lr=opt.lr, arena=tap_arena)
@@ -185,16 +190,18 @@ class Workload(object):
         return '%d/%d' % (int(live.sum()), mk.size)
 
 
-def timed_regions(iteration, steps, regions, fence, world, dev, use_dist):
-    """`regions` back-to-back timed regions of exactly `steps` iterations, each bracketed by barrier + torch.cuda.synchronize() on both sides
-    and reduced with MAX over ranks; returns the per-region wall times [s], the host issue time of the first region and the last loss."""
+def timed_regions(iteration, sizes, fence, world, dev, use_dist, collect=True):
+    """Back-to-back timed regions of exactly sizes[r] iterations, each bracketed by barrier + torch.cuda.synchronize() on both sides
+    and reduced with MAX over ranks; returns the per-region wall times [s], the host issue time of the first region and the last loss.
+    collect=False: the caller ran gc.collect() before its warm-up (a collection here idles the GPU right before the first region)."""
     out, t_issue, loss = [], None, None
     import gc
-    gc.collect()
+    if collect:
+        gc.collect()
     if os.environ.get('ECHR_BENCH_GC') != '1':
         gc.disable()          # like timeit: a generation-2 collection of the interpreter (~40 ms with torch loaded) is not part of an iteration
     try:
-        for r in range(regions):
+        for steps in sizes:
             fence()
             t0 = time.perf_counter()
             for _ in range(steps):
@@ -213,11 +220,50 @@ def timed_regions(iteration, steps, regions, fence, world, dev, use_dist):
     return out, t_issue, loss
 
 
-def region_stats(times, steps, world):
-    ms = sorted(1e3 * t / steps for t in times)
+def region_stats(times, sizes, world):
+    ms = sorted(1e3 * t / s for t, s in zip(times, sizes))
     med = float(np.median(ms))
     return dict(ms_per_step=round(med, 3), value=round(1e3 * S_STEPS * world / med, 1),
-                regions=dict(n=len(ms), steps_each=steps, ms_per_step_min=round(ms[0], 3), ms_per_step_median=round(med, 3), ms_per_step_max=round(ms[-1], 3)))
+                regions=dict(n=len(ms), steps_each=list(sizes), ms_per_step_min=round(ms[0], 3), ms_per_step_median=round(med, 3), ms_per_step_max=round(ms[-1], 3)))
+
+
+DUMP_MAX_BYTES = 64 << 20        # everything one --dump-outputs writes
+DUMP_MAX_ELEMS = 1 << 19         # per tensor (2 MB); halved for every tensor while the total would exceed DUMP_MAX_BYTES
+# d loss / d b_alpha is exactly zero (the attention softmax is shift invariant), so the trained value of this bias is fp32 rounding noise
+# that Adam scales to steps of up to lr either way: it differs from run to run of the (order-dependent) default path by far more than
+# rounding, and no output depends on it.  It is not written.
+DUMP_SKIP = ('lm_model.core.attention.alpha_net.bias',)
+
+
+def dump_outputs(wl, loss, out_dir):
+    """What the timed path handed its caller in the last timed step: `loss` (the returned 0-d tensor) and, for the training
+    configurations, every parameter after that step's update (`param.<name>`, the proposal encoder's as `param.tap.<name>` for --c5),
+    except DUMP_SKIP.  Called behind the timed steps' closing fence (torch.cuda.synchronize()), so updates the library deferred to its
+    helper streams are included.  Tensors above the per-tensor cap are written as a fixed sample of that many elements (sorted indices
+    from a RandomState seeded by the tensor's name), so that two builds of the project can be compared element for element."""
+    import zlib
+    tensors = [('loss', loss.detach().float())]
+    if wl.kind != 'fwd':
+        models = [('', wl.model)] + ([('tap.', wl.tap_model)] if wl.kind == 'c5' else [])
+        tensors += [('param.' + prefix + name, p.detach().reshape(-1)) for prefix, model in models for name, p in model.named_parameters()
+                    if prefix + name not in DUMP_SKIP]
+    cap = DUMP_MAX_ELEMS
+    while cap > 1 and 4 * sum(min(t.numel(), cap) for _, t in tensors) > DUMP_MAX_BYTES:
+        cap //= 2
+    arrays = {}
+    for name, t in tensors:
+        if t.numel() > cap:
+            rs = np.random.RandomState(zlib.crc32(name[len('param.'):].encode()))
+            idx = np.sort(rs.choice(t.numel(), cap, replace=False))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        arrays[name] = t.float().cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError('--dump-outputs: %d tensors need %d bytes even at one element each' % (len(arrays), total))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+    return total
 
 
 # kernel classes of libechr_hip.so (echr_prof_read kinds) -> (name, rocprof kernel symbol, bound)
@@ -345,6 +391,9 @@ def gpu_leg(args, rank, world, local_rank):
         _lib.check(_lib.load().echr_streams_init(), 'streams_init')
     use_dist = dist.is_available() and dist.is_initialized()
     kind = 'c5' if args.c5 else ('fwd' if args.mode == 'fwd' else 'train')
+    # the dropout stream's seed comes from torch.initial_seed() (rank-mixed with several ranks): fixed, so that the same arguments
+    # give the same inputs and dropout masks in every run (--dump-outputs)
+    torch.manual_seed(0)
     wl = Workload(args, kind, rank, dev, use_dist)
 
     def fence():
@@ -357,13 +406,17 @@ def gpu_leg(args, rank, world, local_rank):
             print('[bench] ' + msg, file=sys.stderr, flush=True)
 
     say('model ready; warm-up')
+    import gc
+    gc.collect()          # before the warm-up, not between it and the timed steps: the GPU idles while it runs (+0.5 ms on the first steps)
     for i in range(args.warmup):
         wl.iteration()
         torch.cuda.synchronize()
         say('warm-up %d done' % i)
-    times, t_issue, loss = timed_regions(wl.iteration, args.steps, args.regions, fence, world, dev, use_dist)
-    head = region_stats(times, args.steps, world)
-    say('host issue time %.3f ms per step; timed regions (ms per step): %s' % (1e3 * t_issue / args.steps, ' '.join('%.3f' % (1e3 * t / args.steps) for t in times)))
+    times, t_issue, loss = timed_regions(wl.iteration, [args.steps], fence, world, dev, use_dist, collect=False)      # the --steps timed steps
+    head = region_stats(times, [args.steps], world)
+    say('host issue time %.3f ms per step; timed steps %.3f ms per step' % (1e3 * t_issue / args.steps, 1e3 * times[0] / args.steps))
+    if args.dump_outputs and rank == 0:
+        say('outputs of the last timed step: %.1f MB in %s' % (dump_outputs(wl, loss, args.dump_outputs) / 1e6, args.dump_outputs))
     if os.environ.get('ECHR_HOST_PROBE') == '1':          # diagnostic: host time of one iteration issued into an empty queue
         ts = []
         for _ in range(10):
@@ -374,14 +427,15 @@ def gpu_leg(args, rank, world, local_rank):
 
     # second timed figure with every large projection on the NATIVE fp32 MFMA path (no fp16-pair / bf16-plane emulation)
     native = None
-    if not args.no_native and kind == 'train':
+    if args.full and not args.no_native and kind == 'train':
         lib = _lib.load()
         for k in (b'gemm_h2', b'persist_h2', b'gemm_bf16x3'):
             lib.echr_config_set(k, 0)
         for _ in range(2):
             wl.iteration()
-        tn, _, _ = timed_regions(wl.iteration, args.steps, min(args.regions, 3), fence, world, dev, use_dist)
-        st = region_stats(tn, args.steps, world)
+        sn = [args.steps] * min(args.regions, 3)
+        tn, _, _ = timed_regions(wl.iteration, sn, fence, world, dev, use_dist)
+        st = region_stats(tn, sn, world)
         native = dict(value=st['value'], unit='timesteps/s', ms_per_step=st['ms_per_step'], regions=st['regions'],
                       note='same workload with gemm_h2=0, gemm_bf16x3=0, persist_h2=0: every product on v_mfma_f32_* (exact fp32 MFMA)')
         if not args.no_roofline:
@@ -394,13 +448,13 @@ def gpu_leg(args, rank, world, local_rank):
         fence()
 
     roof = None
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         roof = roofline_pass(wl, args, rank, fence)
 
     # several ranks: how much of the gradient exchange the backward tail did NOT hide (HIP events around the caller's stream's wait for the
     # last collective, fused.DataParallelStep), per step, in a pass of its own behind the timed regions; MAX over ranks like the timing
     exchange = None
-    if wl.dp is not None and use_dist:
+    if args.full and wl.dp is not None and use_dist:
         wl.dp.measure = True
         for _ in range(max(3, min(args.steps, 10))):
             wl.iteration()
@@ -416,14 +470,15 @@ def gpu_leg(args, rank, world, local_rank):
     # the other single-GPU configurations of BASELINE.json in the same process: config 2 (forward + criterion only, same one-call entry) and
     # config 5 (SST proposal encoder + caption path, joint iteration) -- each with its own timed regions and its dominant kernel's roofline
     others = None
-    if kind == 'train' and world == 1 and not args.no_others and not args.overlap:
+    if args.full and kind == 'train' and world == 1 and not args.no_others and not args.overlap:
         others = {}
         for name, k2 in (('c2', 'fwd'), ('c5', 'c5')):
             w2 = Workload(args, k2, rank, dev, use_dist)
             for _ in range(max(3, args.warmup // 2)):
                 w2.iteration()
-            t2, _, l2 = timed_regions(w2.iteration, args.steps, args.regions, fence, world, dev, use_dist)
-            st = region_stats(t2, args.steps, world)
+            s2 = [args.steps] * args.regions
+            t2, _, l2 = timed_regions(w2.iteration, s2, fence, world, dev, use_dist)
+            st = region_stats(t2, s2, world)
             rf = None if args.no_roofline else roofline_pass(w2, args, rank, fence, brief=True)
             others[name] = dict(metric='caption-decoder timesteps/sec (%s)' % ('fwd only' if k2 == 'fwd' else 'SST + decoder, joint fwd+bwd'),
                                 value=st['value'], unit='timesteps/s', ms_per_step=st['ms_per_step'], regions=st['regions'],
@@ -561,8 +616,11 @@ def self_launch(args):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
-    ap.add_argument('--steps', type=int, default=100)       # 0.2 s of timed work: one host hiccup no longer moves the average
+    ap.add_argument('--steps', type=int, default=100, help='timed steps of the headline (one back-to-back region)')
     ap.add_argument('--warmup', type=int, default=10)
+    ap.add_argument('--full', action='store_true', help='after the headline also measure native_f32, the roofline passes, the exchange pass '
+                    'of several ranks, configs 2 and 5 (other_configs) and the CPU baseline (each unless its --no-* option is given)')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write the loss and the updated parameters of the last timed step as DIR/<name>.npy')
     ap.add_argument('--overlap', action='store_true', help='SURVEY 8-d one-video layout (T_v=160, events share rows)')
     ap.add_argument('--mode', choices=['train', 'fwd'], default='train',
                     help="'train' = fwd+bwd+clamp+Adam (BASELINE config 3, the headline metric); 'fwd' = forward + loss only (config 2)")
@@ -571,12 +629,15 @@ def main():
     ap.add_argument('--no-arena', action='store_true', help='per-tensor gradients/optimiser instead of the flat arena')
     ap.add_argument('--fused', choices=['auto', 'on', 'off'], default=os.environ.get('ECHR_BENCH_FUSED', 'auto'),
                     help='one echr_train_step call per iteration (auto = on, for every world size) or the autograd path (off)')
-    ap.add_argument('--regions', type=int, default=5, help='back-to-back timed regions of --steps iterations each; ms_per_step = their median')
+    ap.add_argument('--regions', type=int, default=5, help='--full: back-to-back timed regions of --steps iterations each behind native_f32 '
+                    '(at most 3) and other_configs; their ms_per_step = the regions\' median')
     ap.add_argument('--no-others', action='store_true', help='skip the config-2 / config-5 lines measured after the headline (other_configs)')
     ap.add_argument('--no-cpu', action='store_true')
     ap.add_argument('--no-roofline', action='store_true')
     ap.add_argument('--no-native', action='store_true', help='skip the second timed figure on the native fp32 MFMA path')
     args = ap.parse_args()
+    if args.steps < 1 or args.regions < 1:
+        ap.error('--steps and --regions must be at least 1')
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         # `python bench.py --gpus N` without an outer launcher: start the N ranks ourselves (one process per GPU) BEFORE anything in this
         # process touches the GPU -- the child is torch.distributed.run, this process only relays its output and exit code
@@ -675,7 +736,7 @@ def main():
             out['config']['other_configs'] = res['others']
         if res['roof'] is not None:
             out['roofline'] = res['roof']
-        if world == 1 and not args.no_cpu and args.mode == 'train':
+        if args.full and world == 1 and not args.no_cpu and args.mode == 'train':
             out['cpu_baseline'] = cpu_leg(args)
         print(json.dumps(out), flush=True)
     if dist.is_available() and dist.is_initialized():

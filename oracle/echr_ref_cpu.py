@@ -67,6 +67,7 @@ def tsrm_forward(P, feats, soi, n_head=16, drop_mask=None, prefix='fusion_model.
     if use_posit:                                                  # :38-43, :105-116
         pos = position_embedding(position_matrix(soi), P[prefix + 'enc_attn.pair_pos_fc1.weight'].shape[1])
         pos = torch.tensor(pos, dtype=torch.float32)               # :41 (float64 -> float32)
+        pos = pos.to(P[prefix + 'enc_attn.pair_pos_fc1.weight'].dtype)      # (no-op on fp32 parameters; float64 ones: tests' exact-arithmetic runs)
         p1 = F.linear(pos.view(-1, pos.shape[2]), P[prefix + 'enc_attn.pair_pos_fc1.weight'],
                       P[prefix + 'enc_attn.pair_pos_fc1.bias'])    # :110
         gate = F.linear(torch.tanh(p1), P[prefix + 'enc_attn.pair_pos_fc2.weight'],

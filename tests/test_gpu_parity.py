@@ -2107,8 +2107,8 @@ def test_bench_two_rank_rehearsal_on_one_gpu(fused):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, ECHR_BENCH_BACKEND='gloo', ECHR_BENCH_ONE_GPU='1')
     env.pop('WORLD_SIZE', None)
-    r = subprocess.run([_sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '4', '--warmup', '2', '--no-cpu', '--no-native',
-                        '--no-roofline', '--fused', fused], env=env, cwd=root, capture_output=True, text=True, timeout=900)
+    r = subprocess.run([_sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '4', '--warmup', '2', '--full', '--no-cpu',
+                        '--no-native', '--no-roofline', '--fused', fused], env=env, cwd=root, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
     assert len(lines) == 1, r.stdout

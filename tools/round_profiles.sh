@@ -49,10 +49,10 @@ cd $root
 { echo "# in-kernel phase stamps of the persistent recurrences (tools/persist_stamps.py), commit $commit"; echo "## c3 forward"; timeout -k 10 200 python3 tools/persist_stamps.py 2>/dev/null | grep -v amdgpu;
   echo "## c3 reverse"; timeout -k 10 200 python3 tools/persist_stamps.py bwd 2>/dev/null | grep -v amdgpu; echo "## c5 (BIG) forward"; timeout -k 10 200 python3 tools/persist_stamps.py c5 2>/dev/null | grep -v amdgpu;
   echo "## c5 (BIG) reverse"; timeout -k 10 200 python3 tools/persist_stamps.py c5 bwd 2>/dev/null | grep -v amdgpu; } > $out/${tag}_persist_stamps.txt
-timeout -k 10 400 python3 bench.py > $out/${tag}_bench_final.json 2> $out/bench.err; echo bench_exit=$?
-timeout -k 10 400 python3 bench.py --c5 > $out/${tag}_bench_c5.json 2> $out/bench5.err; echo bench5_exit=$?
+timeout -k 10 400 python3 bench.py --full > $out/${tag}_bench_final.json 2> $out/bench.err; echo bench_exit=$?
+timeout -k 10 400 python3 bench.py --full --c5 > $out/${tag}_bench_c5.json 2> $out/bench5.err; echo bench5_exit=$?
 # BASELINE config 2 (forward + criterion only, train-mode dropout): bench line and kernel stats
-timeout -k 10 300 python3 bench.py --mode fwd --no-cpu > $out/${tag}_bench_c2.json 2> $out/bench2.err; echo bench2_exit=$?
+timeout -k 10 300 python3 bench.py --full --mode fwd --no-cpu > $out/${tag}_bench_c2.json 2> $out/bench2.err; echo bench2_exit=$?
 cd /tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof2 -- python3 $root/bench.py --mode fwd --steps 12 --warmup 3 --regions 1 --no-others --no-cpu --no-roofline --no-native > $out/prof2.log 2>&1
 python3 $root/tools/prof_summary.py $out/prof2 15 30 > $out/${tag}_rocprof_kernel_stats_c2.txt; rm -rf $out/prof2
