@@ -1,7 +1,8 @@
 """CaptionGenerator -- drop-in for the reference's CaptionGenerator.py (:7-167) on MI355X.
 
 Same constructor side effects on `opt` (video/event/clip_context_dim, :56-84), same `forward`
-signature and live modes ('train' -> log-probs [N,S,V+1]; 'eval' -> (seq, logp)), same sub-module
+signature and live modes ('train' -> log-probs [N,S,V+1]; 'eval' -> (seq, logp); 'train_rl' -> (gen_result, sample_logprobs,
+greedy_res), self-critical training), same sub-module
 names (`fusion_model`, `lm_model`) and state_dict keys.  The three context levels are built without
 python loops over events: index lists are uploaded once as int32 (start, length, anchor) vectors and
 every kernel addresses the video features through them.
@@ -48,9 +49,12 @@ class CaptionGenerator(nn.Module):
         self.lm_model._drop_seed = int(seed)
         self.lm_model._drop_calls = int(calls)
 
-    def forward(self, tap_feats, c3d_feats, lda_feats, lm_labels, ind_select_list, soi_select_list, mode='train'):
-        if mode not in ('train', 'eval'):
-            raise NotImplementedError("mode=%r: only 'train' and 'eval' are live in the reference as shipped (SURVEY section 2 row 12)" % (mode,))
+    def forward(self, tap_feats, c3d_feats, lda_feats, lm_labels, ind_select_list, soi_select_list, mode='train', gen_result=None):
+        """`gen_result` (mode='train_rl' only, optional): score these captions [N,T] instead of drawing them (tests, replayed samples)."""
+        if mode not in ('train', 'eval', 'train_rl'):
+            raise NotImplementedError("mode=%r: 'train', 'eval' and 'train_rl' are the reference's live modes (SURVEY section 2 row 12)" % (mode,))
+        if gen_result is not None and mode != 'train_rl':
+            raise ValueError("gen_result is taken by mode='train_rl' only")
         self._require_live_decoder()
         if not c3d_feats.is_cuda:
             raise EF.L.EchrHipError('CaptionGenerator runs on the GPU only: move the module and its inputs with .cuda()')
@@ -71,7 +75,29 @@ class CaptionGenerator(nn.Module):
             raise
         if mode == 'train':
             return self.lm_model(video, event, clip, clip_mask, lm_labels, drop=drop, prepared=prepared)
+        if mode == 'train_rl':
+            return self._train_rl(video, event, clip, clip_mask, drop, gen_result)
         return self.lm_model.sample(video, event, clip, clip_mask)
+
+    def _train_rl(self, video, event, clip, clip_mask, drop, gen_result):
+        """Self-critical training (CaptionGenerator.py:32-37): a multinomial sample under the iteration's dropout state, the greedy baseline in
+        eval mode without a graph, both on the same event context; `sample_logprobs` is the teacher-forced recompute of the sample under the
+        SAME dropout state gathered at its tokens, so the gradient reaches the decoder, `event` and the encoder as mode='train' does."""
+        lm = self.lm_model
+        if gen_result is None:
+            gen_result, _ = lm.sample_train(video, event.detach(), clip, clip_mask, drop)
+        else:
+            gen_result = torch.as_tensor(gen_result).to(device=event.device, dtype=torch.int64)
+        was_training = lm.training
+        lm.eval()
+        try:
+            with torch.no_grad():
+                greedy_res, _ = lm.sample(video, event.detach(), clip, clip_mask)
+        finally:
+            lm.train(was_training)
+        if isinstance(gen_result, list) or gen_result.numel() == 0:
+            return [], [], greedy_res                  # every row drew <eos> first (OldModel.sample returns [] then, :186-187)
+        return gen_result, lm.sequence_logprobs(video, event, clip, clip_mask, gen_result, drop=drop), greedy_res
 
     def change_context_dim(self):
         opt = self.opt

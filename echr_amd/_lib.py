@@ -138,6 +138,11 @@ SYMBOLS = [
     ('echr_sampler_ws_floats', i64, [C.POINTER(DecArgs)]),
     ('echr_sampler_table_floats', i64, [C.POINTER(DecArgs)]),
     ('echr_decoder_sample', i32, [C.POINTER(SampleArgs), C.c_void_p]),
+    ('echr_decoder_sample_train', i32, [C.POINTER(SampleArgs), C.POINTER(Dropout), C.c_void_p]),
+    ('echr_gather_tokens_fwd', i32, [c_f, c_f, c_f, i32, i32, i32, i32, C.c_void_p]),
+    ('echr_gather_tokens_bwd', i32, [c_f, c_f, c_f, i32, i32, i32, i32, C.c_void_p]),
+    ('echr_reward_loss_fwd', i32, [c_f, c_f, c_f, c_f, i32, i32, C.c_void_p]),
+    ('echr_reward_loss_bwd', i32, [c_f, c_f, c_f, c_f, c_f, i32, i32, C.c_void_p]),
     ('echr_config_set', i32, [C.c_char_p, i32]),
     ('echr_stream_join', i32, [C.c_void_p]),
     ('echr_streams_init', i32, []),
@@ -164,6 +169,8 @@ SYMBOLS = [
     ('echr_train_step_ws_floats', i64, [C.POINTER(TrainStepArgs)]),
     ('echr_train_step', i32, [C.POINTER(TrainStepArgs), C.c_void_p]),
     ('echr_train_step_prepare', i32, [C.POINTER(TrainStepArgs), C.c_void_p]),
+    ('echr_train_step_rw_ws_floats', i64, [C.POINTER(TrainStepArgs)]),
+    ('echr_train_step_rw', i32, [C.POINTER(TrainStepArgs), c_f, C.c_void_p]),
     ('echr_handover_wait', i32, [i32, C.c_void_p]),
     ('echr_clamp', i32, [c_f, i64, f32, C.c_void_p]),
     ('echr_clamp_adam', i32, [c_f, c_f, c_f, c_f, i64, i32, C.c_double, C.c_double, C.c_double, C.c_double, f32, C.c_void_p]),

@@ -518,10 +518,13 @@ int logsoftmax_rows(float* X, long ld, int N, int S, int t0, int nt, int cols, h
 __device__ __forceinline__ int load_index(const void* p, long i, int is64) {
     return is64 ? (int)reinterpret_cast<const long long*>(p)[i] : reinterpret_cast<const int*>(p)[i];
 }
+// RW: RewardCriterion (misc/utils.py:48-59) in the fused-criterion form -- signed weight rw = reward * mask over the plain sum(mask)
+template <bool RW>
 __global__ __launch_bounds__(256) void logsoftmax_bwd_kernel(const float* __restrict__ logp, const float* __restrict__ G,
                                                              const void* __restrict__ target, int tgt64, const float* __restrict__ mask,
                                                              const float* __restrict__ g_loss, const float* __restrict__ mask_sum,
-                                                             float* __restrict__ out, long ldo, int N, int S, int V1) {
+                                                             float* __restrict__ out, long ldo, int N, int S, int V1,
+                                                             const float* __restrict__ rw) {
     __shared__ float red[4];
     const int row = blockIdx.x;             // time-major row = t*N + n
     const int t = row / N, n = row % N;
@@ -534,7 +537,7 @@ __global__ __launch_bounds__(256) void logsoftmax_bwd_kernel(const float* __rest
         for (int j = threadIdx.x; j < V1; j += 256) o[j] = G[src + j] - expf(logp[src + j]) * s;
     } else {
         // loss = -sum(logp[target]*mask)/(sum(mask)+1e-6)  =>  g[target] = -mask/(den) * g_loss, other entries 0
-        const float gv = -mask[n * S + t] / (mask_sum[0] + 1e-6f) * g_loss[0];
+        const float gv = RW ? -rw[n * S + t] / mask_sum[0] * g_loss[0] : -mask[n * S + t] / (mask_sum[0] + 1e-6f) * g_loss[0];
         const int tg = load_index(target, n * S + t, tgt64);
         for (int j = threadIdx.x; j < V1; j += 256) o[j] = (j == tg ? gv : 0.f) - expf(logp[src + j]) * gv;
     }
@@ -567,10 +570,11 @@ __global__ __launch_bounds__(256) void logsoftmax_bwd_reg_kernel(const float* __
     }
 }
 int logsoftmax_bwd(const float* logp, const float* G, const void* target, int tgt64, const float* mask, const float* g_loss,
-                   const float* mask_sum, float* out, long ldo, int N, int S, int V1, hipStream_t st) {
+                   const float* mask_sum, float* out, long ldo, int N, int S, int V1, hipStream_t st, const float* rw) {
     if (G && ldo <= 256 * 20 && ldo > 256 * 8) hipLaunchKernelGGL(logsoftmax_bwd_reg_kernel<20>, dim3(N * S), dim3(256), 0, st, logp, G, out, ldo, N, S, V1);
     else if (G && ldo <= 256 * 8) hipLaunchKernelGGL(logsoftmax_bwd_reg_kernel<8>, dim3(N * S), dim3(256), 0, st, logp, G, out, ldo, N, S, V1);
-    else hipLaunchKernelGGL(logsoftmax_bwd_kernel, dim3(N * S), dim3(256), 0, st, logp, G, target, tgt64, mask, g_loss, mask_sum, out, ldo, N, S, V1);
+    else if (rw && !G) hipLaunchKernelGGL(logsoftmax_bwd_kernel<true>, dim3(N * S), dim3(256), 0, st, logp, G, target, tgt64, mask, g_loss, mask_sum, out, ldo, N, S, V1, rw);
+    else hipLaunchKernelGGL(logsoftmax_bwd_kernel<false>, dim3(N * S), dim3(256), 0, st, logp, G, target, tgt64, mask, g_loss, mask_sum, out, ldo, N, S, V1, nullptr);
     return check_launch("logsoftmax_bwd");
 }
 
@@ -578,11 +582,13 @@ int logsoftmax_bwd(const float* logp, const float* G, const void* target, int tg
 // written): block = row (n, t) of the [N,S,ld] logits held in registers -> lse; d logits row (time-major t*N+n, leading dimension ldo, zero
 // padded) = (onehot(target) - softmax) * gv with gv = -mask[n,t] / (sum(mask) + 1e-6) * g_loss (misc/utils.py:66-75 and its backward);
 // row_loss[t*N+n] = -logp[target] * mask[n,t].  Every block sums the N*S mask entries itself (same fixed order everywhere).
-template <int EPT>
+// RW (RewardCriterion, misc/utils.py:48-59, self-critical training): the signed per-position weight rw[n,t] = reward * mask replaces the mask
+// in the numerator, the denominator is the plain sum(mask): gv = -rw[n,t] / sum(mask) * g_loss, row_loss = -logp[target] * rw[n,t]
+template <int EPT, bool RW>
 __global__ __launch_bounds__(256) void logsoftmax_nll_dlg_kernel(const float* __restrict__ X, long ld, const void* __restrict__ target, int tgt64,
                                                                  const float* __restrict__ mask, const float* __restrict__ g_loss, float* __restrict__ out,
                                                                  long ldo, float* __restrict__ row_loss, float* __restrict__ msum_out, int N, int S, int V1,
-                                                                 const int* __restrict__ act) {
+                                                                 const int* __restrict__ act, const float* __restrict__ rw) {
     __shared__ float red[4];
     // act != nullptr: block i handles the compacted row i = time-major row act[i] (only rows whose mask is non-zero exist: the logits arrive
     // as [n_active, ld], d logits / row_loss leave in the same compact order)
@@ -601,7 +607,7 @@ __global__ __launch_bounds__(256) void logsoftmax_nll_dlg_kernel(const float* __
     float ms = 0.f;
     for (int i = threadIdx.x; i < N * S; i += 256) ms += mask[i];
     const int tg = min(max(load_index(target, n * S + t, tgt64), 0), V1 - 1);
-    const float mk = mask[n * S + t];
+    const float mk = RW ? rw[n * S + t] : mask[n * S + t];
     m = block_max(m, red);
     float s = 0.f;
 #pragma unroll
@@ -609,7 +615,7 @@ __global__ __launch_bounds__(256) void logsoftmax_nll_dlg_kernel(const float* __
     s = block_sum(s, red);
     ms = block_sum(ms, red);
     const float lse = m + logf(s);
-    const float gv = -mk / (ms + 1e-6f) * g_loss[0];
+    const float gv = RW ? -mk / ms * g_loss[0] : -mk / (ms + 1e-6f) * g_loss[0];
     float* o = out + (long)row * ldo;
 #pragma unroll
     for (int i = 0; i < EPT; ++i) {
@@ -622,31 +628,40 @@ __global__ __launch_bounds__(256) void logsoftmax_nll_dlg_kernel(const float* __
     }
     if (row == 0 && threadIdx.x == 0) msum_out[0] = ms;
 }
-// loss[0] = sum(row_loss) / (msum + 1e-6), loss[1] = msum: one block, fixed order
+// loss[0] = sum(row_loss) / (msum + 1e-6) (RW: / msum), loss[1] = msum: one block, fixed order
+template <bool RW>
 __global__ __launch_bounds__(256) void nll_rows_sum_kernel(const float* __restrict__ row_loss, int NS, const float* __restrict__ msum, float* __restrict__ loss) {
     __shared__ float red[4];
     float s = 0.f;
     for (int i = threadIdx.x; i < NS; i += 256) s += row_loss[i];
     s = block_sum(s, red);
-    if (threadIdx.x == 0) { loss[0] = s / (msum[0] + 1e-6f); loss[1] = msum[0]; }
+    if (threadIdx.x == 0) { loss[0] = RW ? s / msum[0] : s / (msum[0] + 1e-6f); loss[1] = msum[0]; }
 }
 bool logsoftmax_nll_dlg_ok(int V1, long ldo) { return ldo <= 256 * 40; }
 int logsoftmax_nll_dlg(const float* X, long ld, const void* target, int tgt64, const float* mask, const float* g_loss, float* out, long ldo,
-                       float* row_loss, float* msum_out, int N, int S, int V1, hipStream_t st, const int* act, int n_active) {
+                       float* row_loss, float* msum_out, int N, int S, int V1, hipStream_t st, const int* act, int n_active, const float* rw) {
     const int rows = act ? n_active : N * S;
-    if (ldo <= 256 * 8) hipLaunchKernelGGL(logsoftmax_nll_dlg_kernel<8>, dim3(rows), dim3(256), 0, st, X, ld, target, tgt64, mask, g_loss, out, ldo, row_loss, msum_out, N, S, V1, act);
-    else if (ldo <= 256 * 20) hipLaunchKernelGGL(logsoftmax_nll_dlg_kernel<20>, dim3(rows), dim3(256), 0, st, X, ld, target, tgt64, mask, g_loss, out, ldo, row_loss, msum_out, N, S, V1, act);
-    else hipLaunchKernelGGL(logsoftmax_nll_dlg_kernel<40>, dim3(rows), dim3(256), 0, st, X, ld, target, tgt64, mask, g_loss, out, ldo, row_loss, msum_out, N, S, V1, act);
+#define ECHR_NLL_DLG(EPT) \
+    if (rw) hipLaunchKernelGGL((logsoftmax_nll_dlg_kernel<EPT, true>), dim3(rows), dim3(256), 0, st, X, ld, target, tgt64, mask, g_loss, out, ldo, row_loss, msum_out, N, S, V1, act, rw); \
+    else hipLaunchKernelGGL((logsoftmax_nll_dlg_kernel<EPT, false>), dim3(rows), dim3(256), 0, st, X, ld, target, tgt64, mask, g_loss, out, ldo, row_loss, msum_out, N, S, V1, act, nullptr)
+    if (ldo <= 256 * 8) { ECHR_NLL_DLG(8); }
+    else if (ldo <= 256 * 20) { ECHR_NLL_DLG(20); }
+    else { ECHR_NLL_DLG(40); }
+#undef ECHR_NLL_DLG
     return check_launch("logsoftmax_nll_dlg");
 }
-int nll_rows_sum(const float* row_loss, int NS, const float* msum, float* loss, hipStream_t st) {
-    hipLaunchKernelGGL(nll_rows_sum_kernel, dim3(1), dim3(256), 0, st, row_loss, NS, msum, loss);
+int nll_rows_sum(const float* row_loss, int NS, const float* msum, float* loss, hipStream_t st, bool rw) {
+    if (rw) hipLaunchKernelGGL(nll_rows_sum_kernel<true>, dim3(1), dim3(256), 0, st, row_loss, NS, msum, loss);
+    else hipLaunchKernelGGL(nll_rows_sum_kernel<false>, dim3(1), dim3(256), 0, st, row_loss, NS, msum, loss);
     return check_launch("nll_rows_sum");
 }
 
-// masked NLL (misc/utils.py:66-75): out[0] = loss, out[1] = sum(mask)
+// masked NLL (misc/utils.py:66-75): out[0] = loss, out[1] = sum(mask).  RW: RewardCriterion's numerator weight rw = reward * mask
+// (misc/utils.py:48-59) and the plain sum(mask) as the denominator
+template <bool RW>
 __global__ __launch_bounds__(256) void nll_loss_kernel(const float* __restrict__ logp, const void* __restrict__ target, int tgt64,
-                                                       const float* __restrict__ mask, float* __restrict__ out, int NS, int V1) {
+                                                       const float* __restrict__ mask, float* __restrict__ out, int NS, int V1,
+                                                       const float* __restrict__ rw) {
     __shared__ float red[4];
     float s = 0.f, ms = 0.f;
     // four rows per round: targets and masks first, then the four gathered log-probs in flight together (the gather depends on its target:
@@ -663,11 +678,55 @@ __global__ __launch_bounds__(256) void nll_loss_kernel(const float* __restrict__
 #pragma unroll
         for (int u = 0; u < 4; ++u) { const int i = i0 + 256 * u; lv[u] = i < NS ? logp[(long)i * V1 + tg[u]] : 0.f; }
 #pragma unroll
-        for (int u = 0; u < 4; ++u) if (i0 + 256 * u < NS) { s -= lv[u] * mk[u]; ms += mk[u]; }
+        for (int u = 0; u < 4; ++u) if (i0 + 256 * u < NS) { s -= lv[u] * (RW ? rw[i0 + 256 * u] : mk[u]); ms += mk[u]; }
     }
     s = block_sum(s, red);
     ms = block_sum(ms, red);
-    if (threadIdx.x == 0) { out[0] = s / (ms + 1e-6f); out[1] = ms; }
+    if (threadIdx.x == 0) { out[0] = RW ? s / ms : s / (ms + 1e-6f); out[1] = ms; }
+}
+
+// ---- self-critical training on gathered log-probs (the module path: CaptionGenerator.forward(mode='train_rl') + RewardCriterion) ----
+// out[n, t] = logp[n, t, seq[n, t]] over log-probs [N, S, V1], t < T <= S
+__global__ __launch_bounds__(256) void gather_tokens_kernel(const float* __restrict__ logp, const long long* __restrict__ seq,
+                                                            float* __restrict__ out, int N, int S, int T, int V1) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= N * T) return;
+    const int n = i / T, t = i % T;
+    const int tk = (int)min(max(seq[i], 0LL), (long long)(V1 - 1));
+    out[i] = logp[((long)n * S + t) * V1 + tk];
+}
+// its backward, g_logp [N, S, V1] fully written: g_out at (n, t, seq[n, t]) for t < T, zero elsewhere.  Block = one (n, t) row
+__global__ __launch_bounds__(256) void gather_tokens_bwd_kernel(const float* __restrict__ g_out, const long long* __restrict__ seq,
+                                                                float* __restrict__ g_logp, int N, int S, int T, int V1) {
+    const int row = blockIdx.x;          // n * S + t
+    const int n = row / S, t = row % S;
+    const int tk = t < T ? (int)min(max(seq[(long)n * T + t], 0LL), (long long)(V1 - 1)) : -1;
+    const float g = t < T ? g_out[(long)n * T + t] : 0.f;
+    float* o = g_logp + (long)row * V1;
+    for (int j = threadIdx.x; j < V1; j += 256) o[j] = j == tk ? g : 0.f;
+}
+// RewardCriterion (misc/utils.py:48-59): mask[n, 0] = 1, mask[n, t] = (seq[n, t-1] > 0); out[0] = sum(-input * reward * mask) / sum(mask)
+// (no epsilon, unlike LanguageModelCriterion), out[1] = sum(mask).  One block, one fixed order of additions
+__device__ __forceinline__ float reward_mask(const long long* seq, int n, int t, int T) { return t == 0 ? 1.f : (seq[(long)n * T + t - 1] > 0 ? 1.f : 0.f); }
+__global__ __launch_bounds__(256) void reward_loss_kernel(const float* __restrict__ in, const long long* __restrict__ seq, const float* __restrict__ reward,
+                                                          float* __restrict__ out, int N, int T) {
+    __shared__ float red[4];
+    float s = 0.f, ms = 0.f;
+    for (int i = threadIdx.x; i < N * T; i += 256) {
+        const float mk = reward_mask(seq, i / T, i % T, T);
+        s -= in[i] * reward[i] * mk;
+        ms += mk;
+    }
+    s = block_sum(s, red);
+    ms = block_sum(ms, red);
+    if (threadIdx.x == 0) { out[0] = s / ms; out[1] = ms; }
+}
+__global__ __launch_bounds__(256) void reward_loss_bwd_kernel(const long long* __restrict__ seq, const float* __restrict__ reward,
+                                                              const float* __restrict__ fwd_out, const float* __restrict__ g_loss,
+                                                              float* __restrict__ g_in, int N, int T) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= N * T) return;
+    g_in[i] = -reward[i] * reward_mask(seq, i / T, i % T, T) / fwd_out[1] * g_loss[0];
 }
 
 // backward of the masked NLL as ONE pass: g_logp[n,s,:] = 0 except g_logp[n,s,target] = -mask / (sum(mask) + 1e-6) * g_loss
@@ -1149,8 +1208,39 @@ extern "C" int echr_event_pool_gather_bwd(const float* d_ech, const int32_t* ind
 
 static int nll_fwd(const float* logp, const void* target, int tgt64, const float* mask, float* loss, int32_t N, int32_t S, int32_t V1, void* stream) {
     ECHR_REQUIRE(logp && target && mask && loss && N > 0 && S > 0 && V1 > 0, "nll_loss_fwd: bad arguments");
-    hipLaunchKernelGGL(nll_loss_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, logp, target, tgt64, mask, loss, N * S, V1);
+    hipLaunchKernelGGL(nll_loss_kernel<false>, dim3(1), dim3(256), 0, (hipStream_t)stream, logp, target, tgt64, mask, loss, N * S, V1, nullptr);
     return check_launch("nll_loss_fwd");
+}
+namespace echr {
+int nll_loss_rw(const float* logp, const void* target, int tgt64, const float* mask, const float* rw, float* loss, int N, int S, int V1, hipStream_t st) {
+    ECHR_REQUIRE(logp && target && mask && rw && loss && N > 0 && S > 0 && V1 > 0, "nll_loss_rw: bad arguments");
+    hipLaunchKernelGGL(nll_loss_kernel<true>, dim3(1), dim3(256), 0, st, logp, target, tgt64, mask, loss, N * S, V1, rw);
+    return check_launch("nll_loss_rw");
+}
+}  // namespace echr
+extern "C" int echr_gather_tokens_fwd(const float* logp, const int64_t* seq, float* out, int32_t N, int32_t S, int32_t T, int32_t V1, void* stream) {
+    ECHR_REQUIRE(logp && seq && out && N > 0 && T > 0 && T <= S && V1 > 0, "gather_tokens_fwd: bad arguments");
+    hipLaunchKernelGGL(gather_tokens_kernel, dim3((N * T + 255) / 256), dim3(256), 0, (hipStream_t)stream, logp, reinterpret_cast<const long long*>(seq),
+                       out, N, S, T, V1);
+    return check_launch("gather_tokens_fwd");
+}
+extern "C" int echr_gather_tokens_bwd(const float* g_out, const int64_t* seq, float* g_logp, int32_t N, int32_t S, int32_t T, int32_t V1, void* stream) {
+    ECHR_REQUIRE(g_out && seq && g_logp && N > 0 && T > 0 && T <= S && V1 > 0, "gather_tokens_bwd: bad arguments");
+    hipLaunchKernelGGL(gather_tokens_bwd_kernel, dim3(N * S), dim3(256), 0, (hipStream_t)stream, g_out, reinterpret_cast<const long long*>(seq),
+                       g_logp, N, S, T, V1);
+    return check_launch("gather_tokens_bwd");
+}
+extern "C" int echr_reward_loss_fwd(const float* input, const int64_t* seq, const float* reward, float* out, int32_t N, int32_t T, void* stream) {
+    ECHR_REQUIRE(input && seq && reward && out && N > 0 && T > 0, "reward_loss_fwd: bad arguments");
+    hipLaunchKernelGGL(reward_loss_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, input, reinterpret_cast<const long long*>(seq), reward, out, N, T);
+    return check_launch("reward_loss_fwd");
+}
+extern "C" int echr_reward_loss_bwd(const int64_t* seq, const float* reward, const float* fwd_out, const float* g_loss, float* g_input,
+                                    int32_t N, int32_t T, void* stream) {
+    ECHR_REQUIRE(seq && reward && fwd_out && g_loss && g_input && N > 0 && T > 0, "reward_loss_bwd: bad arguments");
+    hipLaunchKernelGGL(reward_loss_bwd_kernel, dim3((N * T + 255) / 256), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const long long*>(seq),
+                       reward, fwd_out, g_loss, g_input, N, T);
+    return check_launch("reward_loss_bwd");
 }
 extern "C" int echr_nll_loss_fwd(const float* logp, const int32_t* target, const float* mask, float* loss, int32_t N, int32_t S,
                                  int32_t V1, void* stream) { return nll_fwd(logp, target, 0, mask, loss, N, S, V1, stream); }

@@ -1387,20 +1387,23 @@ extern "C" int echr_decoder_fwd_prepare_cancel(void* stream) {
     return 0;
 }
 
-static int decoder_fwd_impl(const echr_dec_args* a, const echr_dropout* drop, void* stream, const echr_dec_grads* fz, bool* fused_out, bool* compact_out);
-extern "C" int echr_decoder_fwd(const echr_dec_args* a, const echr_dropout* drop, void* stream) { return decoder_fwd_impl(a, drop, stream, nullptr, nullptr, nullptr); }
+static int decoder_fwd_impl(const echr_dec_args* a, const echr_dropout* drop, void* stream, const echr_dec_grads* fz, bool* fused_out, bool* compact_out,
+                            const float* rw);
+extern "C" int echr_decoder_fwd(const echr_dec_args* a, const echr_dropout* drop, void* stream) { return decoder_fwd_impl(a, drop, stream, nullptr, nullptr, nullptr, nullptr); }
 namespace echr {
-int decoder_fwd_fused(const echr_dec_args* a, const echr_dec_grads* g, const echr_dropout* drop, void* stream, bool* fused, bool* compact) {
-    return decoder_fwd_impl(a, drop, stream, g, fused, compact);
+int decoder_fwd_fused(const echr_dec_args* a, const echr_dec_grads* g, const echr_dropout* drop, void* stream, bool* fused, bool* compact, const float* rw) {
+    return decoder_fwd_impl(a, drop, stream, g, fused, compact, rw);
 }
-int decoder_fused_loss(const echr_dec_args* a, const echr_dec_grads* g, float* loss, hipStream_t st) {
+int decoder_fused_loss(const echr_dec_args* a, const echr_dec_grads* g, float* loss, hipStream_t st, bool rw) {
     const DecWsBwd b = carve_ws_bwd(a, g->ws_bwd);
-    return nll_rows_sum(b.ROWL, (g->active_rows && g->n_active > 0) ? g->n_active : a->S * a->N, b.MSUM, loss, st);
+    return nll_rows_sum(b.ROWL, (g->active_rows && g->n_active > 0) ? g->n_active : a->S * a->N, b.MSUM, loss, st, rw);
 }
 }  // namespace echr
 // fz != nullptr: the criterion is fused behind the logits product (echr_train_step) -- the logits are turned into d logits in ws_bwd and
 // per-row loss terms by ONE pass instead of log-softmax, NLL and log-softmax backward passes; the log-probs are never materialised
-static int decoder_fwd_impl(const echr_dec_args* a, const echr_dropout* drop, void* stream, const echr_dec_grads* fz, bool* fused_out, bool* compact_out) {
+// rw (with fz): RewardCriterion's signed weight [N,S] (echr_train_step_rw) in place of the NLL's mask in the fused criterion pass
+static int decoder_fwd_impl(const echr_dec_args* a, const echr_dropout* drop, void* stream, const echr_dec_grads* fz, bool* fused_out, bool* compact_out,
+                            const float* rw) {
     if (fused_out) *fused_out = false;
     if (compact_out) *compact_out = false;
     RC(persist_check_async());
@@ -1467,7 +1470,7 @@ static int decoder_fwd_impl(const echr_dec_args* a, const echr_dropout* drop, vo
                 if (fused_out) *fused_out = true;
                 if (compact_out) *compact_out = true;
                 return logsoftmax_nll_dlg(a->logp, a->V1, fz->nll_target, fz->nll_target_i64, fz->nll_mask, fz->g_loss, b.DLG, b.ldg, b.ROWL, b.MSUM, N, S, a->V1, q,
-                                          fz->active_rows, fz->n_active);
+                                          fz->active_rows, fz->n_active, rw);
             }
         }
         echr_gemm_desc d = desc_nt(w.OUTD + (long)t0 * N * 3 * H, 3 * H, a->w_logit, 3 * H, a->logp + (long)t0 * a->V1, a->V1,
@@ -1485,7 +1488,8 @@ static int decoder_fwd_impl(const echr_dec_args* a, const echr_dropout* drop, vo
             const DecWsBwd b = carve_ws_bwd(a, fz->ws_bwd);
             if (logsoftmax_nll_dlg_ok(a->V1, b.ldg)) {
                 if (fused_out) *fused_out = true;
-                return logsoftmax_nll_dlg(a->logp, a->V1, fz->nll_target, fz->nll_target_i64, fz->nll_mask, fz->g_loss, b.DLG, b.ldg, b.ROWL, b.MSUM, N, S, a->V1, q);
+                return logsoftmax_nll_dlg(a->logp, a->V1, fz->nll_target, fz->nll_target_i64, fz->nll_mask, fz->g_loss, b.DLG, b.ldg, b.ROWL, b.MSUM, N, S, a->V1, q,
+                                          nullptr, 0, rw);
             }
         }
         return logsoftmax_rows(a->logp, a->V1, N, S, t0, t1 - t0, a->V1, q);
@@ -1532,18 +1536,21 @@ static int logit_grads(const echr_dec_args* a, const echr_dec_grads* g, const De
 }
 
 extern "C" int echr_decoder_bwd(const echr_dec_args* a, const echr_dec_grads* g, const echr_dropout* drop, void* stream) {
+    return echr::decoder_bwd_checked(a, g, drop, stream, nullptr);
+}
+int echr::decoder_bwd_checked(const echr_dec_args* a, const echr_dec_grads* g, const echr_dropout* drop, void* stream, const float* rw) {
     RC(persist_check_async());
     RC(join_tail((hipStream_t)stream));
     RC(check_dims(a, "decoder_bwd"));
     ECHR_REQUIRE(g && a->ws && g->ws_bwd && a->logp, "decoder_bwd: missing buffers");
     ECHR_REQUIRE(g->dlg_ready || g->g_logp || (g->nll_target && g->nll_mask && g->g_loss), "decoder_bwd: need g_logp or the fused NLL inputs");
-    return decoder_bwd_parts(a, g, drop, stream, 0);
+    return decoder_bwd_parts(a, g, drop, stream, 0, rw);
 }
 
 // part 0: the whole call.  echr_train_step's joint mode (d tap_feats wanted early, step.hip) issues it in two pieces: 1 = what runs on the
 // caller's stream (late fusion, reverse recurrence, d event), 2 = what runs on the library's helper streams (every other gradient) -- forked
 // from the caller's stream where the second call is made, i.e. behind the event encoder's backward.  Pieces need async_tail = 2.
-int echr::decoder_bwd_parts(const echr_dec_args* a, const echr_dec_grads* g, const echr_dropout* drop, void* stream, int part) {
+int echr::decoder_bwd_parts(const echr_dec_args* a, const echr_dec_grads* g, const echr_dropout* drop, void* stream, int part, const float* rw) {
     if (prep().fill_pending) {
         prep().fill_pending = false;
         if (hipStreamWaitEvent((hipStream_t)stream, prep().fill_done, 0) != hipSuccess) { set_error("decoder_bwd: stream wait failed"); return -5; }
@@ -1582,7 +1589,8 @@ int echr::decoder_bwd_parts(const echr_dec_args* a, const echr_dec_grads* g, con
     if (do_a) {
     if (!g->dlg_ready) {          // (echr_train_step formed d logits in the pass that read the logits)
         if (!g->g_logp && !g->nll_msum) RC(colsum(g->nll_mask, 1, N * S, 1, b.MSUM, false, st));
-        RC(logsoftmax_bwd(a->logp, g->g_logp, g->nll_target, g->nll_target_i64, g->nll_mask, g->g_loss, g->nll_msum ? g->nll_msum : b.MSUM, b.DLG, b.ldg, N, S, V1, st));
+        RC(logsoftmax_bwd(a->logp, g->g_logp, g->nll_target, g->nll_target_i64, g->nll_mask, g->g_loss, g->nll_msum ? g->nll_msum : b.MSUM, b.DLG, b.ldg, N, S, V1, st,
+                           rw));
     }
     // scratch that is accumulated into, and the transposed recurrent weights (every d h / d ATT product of the reverse recurrence
     // then has the same NT form as forward): two launches, independent of everything above
@@ -2144,7 +2152,16 @@ extern "C" int64_t echr_sampler_table_floats(const echr_dec_args* a) {
     return sample_uses_persistent(a) ? carve_tables(a, nullptr).total : 0;
 }
 
-extern "C" int echr_decoder_sample(const echr_sample_args* sa, void* stream) {
+// drop != nullptr: echr_decoder_sample_train -- the launch-per-step chain with the caller's training-mode dropout masks, keyed like
+// echr_decoder_fwd's step t: (element, t, site, drop->offset)
+static int decoder_sample_impl(const echr_sample_args* sa, const echr_dropout* drop, void* stream);
+extern "C" int echr_decoder_sample(const echr_sample_args* sa, void* stream) { return decoder_sample_impl(sa, nullptr, stream); }
+extern "C" int echr_decoder_sample_train(const echr_sample_args* sa, const echr_dropout* drop, void* stream) {
+    ECHR_REQUIRE(sa && drop, "decoder_sample_train: null args");
+    ECHR_REQUIRE(sa->multinomial, "decoder_sample_train: the training-mode decode is the multinomial one (multinomial = 1)");
+    return decoder_sample_impl(sa, drop, stream);
+}
+static int decoder_sample_impl(const echr_sample_args* sa, const echr_dropout* drop, void* stream) {
     ECHR_REQUIRE(sa, "decoder_sample: null args");
     RC(persist_check_async());
     DeterministicScope det;                    // `seq` is an index output: bitwise reproducible logits (no atomic split-K anywhere below)
@@ -2157,8 +2174,8 @@ extern "C" int echr_decoder_sample(const echr_sample_args* sa, void* stream) {
     const int N = a.N, H = a.H, E = a.E;
     DecWs w = carve_ws(&a, a.ws);
     SampWs s = carve_samp(&a, sa->ws_sample);
-    const DropCfg off = make_drop(nullptr, 0.f);
-    const bool persistent = !sa->multinomial && sample_uses_persistent(&a);
+    const DropCfg dh = make_drop(drop, drop ? drop->p_h : 0.f), dout = make_drop(drop, drop ? drop->p_out : 0.f);          // (nullptr: identity)
+    const bool persistent = !sa->multinomial && !drop && sample_uses_persistent(&a);
     {
         // one fill launch: the launch-per-step form starts from zero state / <bos> = 0 and zero outputs; the persistent form writes every
         // output element itself and only needs the unfinished counters cleared
@@ -2220,11 +2237,11 @@ extern "C" int echr_decoder_sample(const echr_sample_args* sa, void* stream) {
                 RC(h2_pack_multi(pj, t > 0 ? 4 : 1, st));
             }
             RC(input_gates(&a, w, s.XT, t, 1, st, false, true, true));
-            RC(step_fwd_big(&a, w, s, t, off, off, st));
+            RC(step_fwd_big(&a, w, s, t, dh, dout, st));
         } else {
             // few events: no embedding gather, no input-gate GEMM -- the token-side products are jobs of the step's first grouped launch
             // (rows gathered from the embedding table by token id), the time-invariant addends are read by the gate kernel
-            RC(step_fwd(&a, w, t, off, off, st, 0, false, s.IT));
+            RC(step_fwd(&a, w, t, dh, dout, st, 0, false, s.IT));
         }
         bool slab_form = false;
         if (big) {

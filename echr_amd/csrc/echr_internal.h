@@ -102,7 +102,10 @@ int tsrm_position_early(const echr_tsrm_args* a, hipStream_t from);          // 
 void tsrm_bwd_defer_join(bool on);          // echr_train_step: the position branch's stream is joined by echr_stream_join, not inside echr_tsrm_bwd
 int tsrm_bwd_parts(const echr_tsrm_args* a, const echr_tsrm_grads* g, const echr_dropout* drop, void* stream, int part);
 int decoder_bwd_scratch_ahead(const echr_dec_args* a, const echr_dec_grads* g);
-int decoder_bwd_parts(const echr_dec_args* a, const echr_dec_grads* g, const echr_dropout* drop, void* stream, int part);
+// rw (optional): RewardCriterion's signed weight [N,S] for the criterion gradient formed here (the non-fused d logits; echr_train_step_rw)
+int decoder_bwd_parts(const echr_dec_args* a, const echr_dec_grads* g, const echr_dropout* drop, void* stream, int part, const float* rw = nullptr);
+// echr_decoder_bwd with that weight: the entry checks, then the whole backward pass
+int decoder_bwd_checked(const echr_dec_args* a, const echr_dec_grads* g, const echr_dropout* drop, void* stream, const float* rw);
 void handover_close();                   // stop recording; the recorded events stay valid for echr_handover_wait
 void handover_request(bool on, echr_handover_fn cb = nullptr, void* user = nullptr);          // the next decoder backward records the data-parallel hand-over events (decoder.hip)
 int join_tail(hipStream_t st);          // make st wait for an asynchronous decoder-backward tail (decoder.hip); no-op when none is pending
@@ -183,16 +186,22 @@ int vec_mat(const float* x, const float* W, long ldw, float* out, int M, int N, 
 int embed_scatter_add(const float* dX, const int* tok, float* gW, int rows, int E, int V1, hipStream_t st, const int* rowmap = nullptr);
 int logsoftmax_rows(float* X, long ld, int N, int S, int t0, int nt, int cols, hipStream_t st);
 int logsoftmax_bwd(const float* logp, const float* G, const void* target, int tgt64, const float* mask, const float* g_loss,
-                   const float* mask_sum, float* out, long ldo, int N, int S, int V1, hipStream_t st);
+                   const float* mask_sum, float* out, long ldo, int N, int S, int V1, hipStream_t st, const float* rw = nullptr);
 // log-softmax + masked NLL + d logits in one pass over the logits (echr_train_step); rows_sum turns the per-row terms into (loss, sum(mask))
 bool logsoftmax_nll_dlg_ok(int V1, long ldo);
 int logsoftmax_nll_dlg(const float* X, long ld, const void* target, int tgt64, const float* mask, const float* g_loss, float* out, long ldo,
-                       float* row_loss, float* msum_out, int N, int S, int V1, hipStream_t st, const int* act = nullptr, int n_active = 0);
-int nll_rows_sum(const float* row_loss, int NS, const float* msum, float* loss, hipStream_t st);
+                       float* row_loss, float* msum_out, int N, int S, int V1, hipStream_t st, const int* act = nullptr, int n_active = 0,
+                       const float* rw = nullptr);
+int nll_rows_sum(const float* row_loss, int NS, const float* msum, float* loss, hipStream_t st, bool rw = false);
+// RewardCriterion's loss from log-probs [N,S,V1]: out = (sum(-logp[target] * rw) / sum(mask), sum(mask))
+int nll_loss_rw(const float* logp, const void* target, int tgt64, const float* mask, const float* rw, float* loss, int N, int S, int V1, hipStream_t st);
+
 // echr_decoder_fwd with the criterion fused behind the logits product: g carries nll_target / nll_mask / g_loss / ws_bwd; d logits land in ws_bwd
 // (echr_dec_grads.dlg_ready = 1 for the echr_decoder_bwd that follows); returns through *fused whether the fused form applied
-int decoder_fwd_fused(const echr_dec_args* a, const echr_dec_grads* g, const echr_dropout* drop, void* stream, bool* fused, bool* compact);
-int decoder_fused_loss(const echr_dec_args* a, const echr_dec_grads* g, float* loss, hipStream_t st);
+// rw (optional): echr_train_step_rw's signed criterion weight [N,S] (RewardCriterion) in place of the NLL's mask in the numerator
+int decoder_fwd_fused(const echr_dec_args* a, const echr_dec_grads* g, const echr_dropout* drop, void* stream, bool* fused, bool* compact,
+                      const float* rw = nullptr);
+int decoder_fused_loss(const echr_dec_args* a, const echr_dec_grads* g, float* loss, hipStream_t st, bool rw = false);
 int sample_step(const float* logits, long ld, int N, int V1, int t, int seq_len, int* it_next, int* unfinished, long long* seq,
                 float* seq_logp, int* n_unfinished, float temperature, unsigned long long seed, hipStream_t st);
 // slabs != nullptr: logits rows are formed here from four k-slice slabs (+ bias) in a fixed order and written to `logits`

@@ -28,13 +28,15 @@ static inline int init_feats_width(const echr_train_step_args* a) {
     return (a->init_use_v ? a->dec.Dv : 0) + (a->init_use_e ? a->dec.De : 0) + (a->init_use_c ? a->dec.D : 0);
 }
 
-static StepWs carve_step(const echr_train_step_args* a) {
+// rw: echr_train_step_rw -- the index region holds the criterion weights [N,S] too (host_nll = 1)
+static StepWs carve_step(const echr_train_step_args* a, bool rw = false) {
     StepWs w;
     long off = 0;
     auto take = [&](long n) { long o = off; off += up64(n); return o; };
     const echr_tsrm_args& t = a->tsrm;
     const echr_dec_args& d = a->dec;
-    w.idx = take((long)(3 + 4 * d.S) * d.N);              // int32: ev_start | ev_len | ind | tokens [S,N] | active rows [<= S*N] | targets [N,S] | mask fp32 [N,S]
+    w.idx = take((long)(3 + (rw ? 5 : 4) * d.S) * d.N);  // int32: ev_start | ev_len | ind | tokens [S,N] | active rows [<= S*N] | targets [N,S] | mask fp32 [N,S]
+                                                          // (| weights fp32 [N,S] with rw)
     w.ech = take((long)t.N * t.Din);
     w.tsrm_ws = take(echr_tsrm_ws_floats(t.N, t.Din, t.Df, t.Do, t.G));
     w.event = take((long)t.N * t.Do);
@@ -172,11 +174,12 @@ static void step_timing_end() {
 }
 
 // joint mode: the helper streams' work of one call
-struct JointPending { echr_dec_args d; echr_dec_grads g; echr_tsrm_args t; echr_tsrm_grads tg; echr_dropout drop; echr_train_step_args args; };
+struct JointPending { echr_dec_args d; echr_dec_grads g; echr_tsrm_args t; echr_tsrm_grads tg; echr_dropout drop; echr_train_step_args args;
+                      const float* crit_w; };          // (crit_w: echr_train_step_rw's criterion weight, nullptr for the NLL)
 // every parameter gradient (decoder: helper streams forked from `src`; event encoder: behind them on the prepare stream), then clamp + Adam on
 // the tail stream, published for echr_stream_join
 static int joint_finish(JointPending& jp, hipStream_t src) {
-    RC(decoder_bwd_parts(&jp.d, &jp.g, &jp.drop, src, 2));
+    RC(decoder_bwd_parts(&jp.d, &jp.g, &jp.drop, src, 2, jp.crit_w));
     hipStream_t s2 = aux2_stream();
     RC(tsrm_bwd_parts(&jp.t, &jp.tg, &jp.drop, s2, 2));
     hipStream_t ts = helpers_merge_to_tail();
@@ -200,8 +203,8 @@ static echr_dec_args step_dec_args(const echr_train_step_args* a, const StepWs& 
     d.h0 = a->w_init ? a->ws + L.h0 : nullptr;
     return d;
 }
-static size_t step_index_count(const echr_train_step_args* a) {
-    return (size_t)(3 + a->dec.S) * a->dec.N + (size_t)a->n_active + (a->host_nll ? 2 * (size_t)a->dec.S * a->dec.N : 0);
+static size_t step_index_count(const echr_train_step_args* a, bool rw = false) {
+    return (size_t)(3 + a->dec.S) * a->dec.N + (size_t)a->n_active + (a->host_nll ? (rw ? 3 : 2) * (size_t)a->dec.S * a->dec.N : 0);
 }
 
 // Optional first half of echr_train_step for the joint 'tap_cg' iteration (train.py:300-313): everything of the call that does not read
@@ -235,7 +238,21 @@ extern "C" int echr_train_step_prepare(const echr_train_step_args* a, void* stre
     return rc;
 }
 
-extern "C" int echr_train_step(const echr_train_step_args* a, void* stream) {
+static int train_step_impl(const echr_train_step_args* a, void* stream, bool rw, const float* rw_dev);
+extern "C" int echr_train_step(const echr_train_step_args* a, void* stream) { return train_step_impl(a, stream, false, nullptr); }
+extern "C" int64_t echr_train_step_rw_ws_floats(const echr_train_step_args* a) { return a ? carve_step(a, true).total : -1; }
+// Self-critical training (RewardCriterion, misc/utils.py:48-59): the same iteration with the criterion's numerator weighted by the signed
+// rw[n,t] = reward * mask.  Stage-ahead needs no extra guard here: the decodes a caller runs between two calls (the sampled and the greedy pass,
+// the event context they read) use workspaces of their own and never this call's `ws`, index ring or gradient arena, and they are queued on
+// the caller's stream behind the update they read the parameters of; the next call's staging is the only work that runs beside that update,
+// and everything else of it is ordered behind the caller's stream's position at its entry, i.e. behind those decodes.
+extern "C" int echr_train_step_rw(const echr_train_step_args* a, const float* weight, void* stream) {
+    ECHR_REQUIRE(a && (a->host_nll || weight), "train_step_rw: the criterion weights are missing (device `weight`, or host_index with host_nll = 1)");
+    ECHR_REQUIRE(!(a->host_nll && weight), "train_step_rw: host_nll = 1 carries the weights in host_index: pass weight = NULL");
+    ECHR_REQUIRE(!a->prepared, "train_step_rw: echr_train_step_prepare does not take the weights (prepared must be 0)");
+    return train_step_impl(a, stream, true, a->host_nll ? nullptr : weight);
+}
+static int train_step_impl(const echr_train_step_args* a, void* stream, bool rw, const float* rw_dev) {
     ECHR_REQUIRE(a && a->ws && a->host_index && a->loss && a->g_loss && a->flat_g && (a->tap || a->event_parts == 1), "train_step: missing buffers");
     ECHR_REQUIRE(!a->prepared || a->overlap_encoder, "train_step: prepared = 1 needs overlap_encoder = 1");
     const int parts = a->event_parts ? a->event_parts : 3;
@@ -248,8 +265,9 @@ extern "C" int echr_train_step(const echr_train_step_args* a, void* stream) {
     ECHR_REQUIRE(!a->do_step || (a->flat_p && a->adam_m && a->adam_v && a->adam_step >= 1), "train_step: optimiser state missing");
     hipStream_t st = (hipStream_t)stream;
     RC(join_tail(st));          // (a deferred update of the previous call: it reads the index region this call is about to restage)
-    const StepWs L = carve_step(a);
-    ECHR_REQUIRE(a->ws_floats >= L.total, "train_step: workspace holds %lld floats, %ld needed (echr_train_step_ws_floats)", (long long)a->ws_floats, L.total);
+    const StepWs L = carve_step(a, rw);
+    ECHR_REQUIRE(a->ws_floats >= L.total, "train_step: workspace holds %lld floats, %ld needed (echr_train_step%s_ws_floats)", (long long)a->ws_floats, L.total,
+                 rw ? "_rw" : "");
     float* ws = a->ws;
     const int N = a->dec.N, S = a->dec.S;
     step_mark(0, st);
@@ -262,7 +280,7 @@ extern "C" int echr_train_step(const echr_train_step_args* a, void* stream) {
     if (ahead) {
         hipStream_t ts = tail_stream_raw();
         if (hipStreamWaitEvent(ts, sa.pre, 0) != hipSuccess) { set_error("train_step: stream wait failed"); return -5; }
-        RC(stage_indices(a->host_index, idx, sizeof(int32_t) * step_index_count(a), ts));
+        RC(stage_indices(a->host_index, idx, sizeof(int32_t) * step_index_count(a, rw), ts));
         // the caller's stream: behind the staging copy (its own position is already behind the update).  The prepare stream: behind the
         // caller's stream's position AT ENTRY -- the update, and whatever the caller queued since (this call's inputs: an upload of the next
         // video's features, the proposal encoder's forward; a write to the parameters) -- since the staging event it forks from no longer
@@ -270,15 +288,17 @@ extern "C" int echr_train_step(const echr_train_step_args* a, void* stream) {
         if (hipEventRecord(sa.post, st) != hipSuccess) { set_error("train_step: event record failed"); return -5; }
         RC(prep_stream_wait(sa.post));
         if (hipStreamWaitEvent(st, ring_last(), 0) != hipSuccess) { set_error("train_step: stream wait failed"); return -5; }
-    } else if (!a->prepared) RC(stage_indices(a->host_index, idx, sizeof(int32_t) * step_index_count(a), st));
+    } else if (!a->prepared) RC(stage_indices(a->host_index, idx, sizeof(int32_t) * step_index_count(a, rw), st));
     const int32_t *ev_start = idx, *ev_len = idx + N, *ind = idx + 2 * N, *active = idx + (3 + S) * N;          // (tokens at idx + 3 N: step_dec_args)
     const void* nll_target = a->nll_target;
     const float* nll_mask = a->nll_mask;
     int nll_i64 = a->nll_target_i64;
-    if (a->host_nll) {          // targets / mask came with the index vectors
+    const float* crit_w = rw_dev;
+    if (a->host_nll) {          // targets / mask (/ weights) came with the index vectors
         nll_target = active + a->n_active;
         nll_mask = reinterpret_cast<const float*>(active + a->n_active + (size_t)S * N);
         nll_i64 = 0;
+        if (rw) crit_w = reinterpret_cast<const float*>(active + a->n_active + 2 * (size_t)S * N);
     }
     ECHR_REQUIRE(nll_target && nll_mask, "train_step: criterion targets / mask missing");
 
@@ -333,8 +353,9 @@ extern "C" int echr_train_step(const echr_train_step_args* a, void* stream) {
     // this stream waits for the helper stream anyway).  forward_only: the plain log-softmax + criterion, loss[0] = loss, loss[1] = sum(mask)
     bool fused_nll = false, compact = false;
     if (a->forward_only) RC(echr_decoder_fwd(&d, &a->drop, stream));
-    else RC(decoder_fwd_fused(&d, &g, &a->drop, stream, &fused_nll, &compact));
-    if (!fused_nll) {
+    else RC(decoder_fwd_fused(&d, &g, &a->drop, stream, &fused_nll, &compact, crit_w));          // (crit_w nullptr: LanguageModelCriterion)
+    if (!fused_nll && crit_w) RC(nll_loss_rw(d.logp, nll_target, nll_i64, nll_mask, crit_w, a->loss, N, S, d.V1, st));
+    else if (!fused_nll) {
         if (nll_i64) RC(echr_nll_loss_fwd_i64(d.logp, static_cast<const int64_t*>(nll_target), nll_mask, a->loss, N, S, d.V1, stream));
         else RC(echr_nll_loss_fwd(d.logp, static_cast<const int32_t*>(nll_target), nll_mask, a->loss, N, S, d.V1, stream));
     }
@@ -355,22 +376,22 @@ extern "C" int echr_train_step(const echr_train_step_args* a, void* stream) {
         // queues next.  echr_stream_join (and the next echr_train_step / decoder call) waits for them.
         echr_tsrm_grads tg = a->tsrm_g;
         tg.g_ech = ws + L.g_ech; tg.g_out = ws + L.g_event; tg.ws_bwd = ws + L.tsrm_ws_bwd; tg.zeroed = 1;
-        RC(decoder_bwd_parts(&d, &g, &a->drop, stream, 1));
+        RC(decoder_bwd_parts(&d, &g, &a->drop, stream, 1, crit_w));
         RC(tsrm_bwd_parts(&t, &tg, &a->drop, stream, 1));
         if (De_tap > 0) RC(echr_event_pool_gather_bwd(ws + L.g_ech, ind, a->g_tap, N, De_c3d, De_tap, stream));
-        RC(decoder_fused_loss(&d, &g, a->loss, st));
+        RC(decoder_fused_loss(&d, &g, a->loss, st, crit_w != nullptr));
         // the caller's hook: the proposal encoder's backward (+ update) goes onto `stream` HERE, right behind g_tap; the helper streams fork
         // behind it (joint_finish), so the chip-filling tail never shares CUs with that 64-workgroup latency chain
         if (a->mid_cb) a->mid_cb(stream, a->mid_user);
         JointPending jp;
-        jp.d = d; jp.g = g; jp.t = t; jp.tg = tg; jp.drop = a->drop; jp.args = *a;
+        jp.d = d; jp.g = g; jp.t = t; jp.tg = tg; jp.drop = a->drop; jp.args = *a; jp.crit_w = crit_w;
         // (issuing the helper work only after the caller has queued the proposal encoder's backward -- a second entry point, tried -- is worse:
         // 3.21 vs 3.00 ms on c5.  The host needs ~0.5 ms to get from here to that launch anyway, the helpers fill exactly that gap, and a
         // persistent recurrence that shares its CUs with GEMM workgroups from its first step on loses more than the gap is worth)
         return joint_finish(jp, st);
     }
     handover_request(a->handover && !a->do_step, a->handover_cb, a->handover_user);
-    rc = echr_decoder_bwd(&d, &g, &a->drop, stream);
+    rc = decoder_bwd_checked(&d, &g, &a->drop, stream, crit_w);
     handover_close();          // (the events stay valid for echr_handover_wait; later backward passes do not re-record them)
     RC(rc);
     step_mark(2, st);
@@ -391,7 +412,7 @@ extern "C" int echr_train_step(const echr_train_step_args* a, void* stream) {
     tsrm_bwd_defer_join(false);
     RC(rc);
     if (a->g_tap && De_tap > 0) RC(echr_event_pool_gather_bwd(ws + L.g_ech, ind, a->g_tap, N, De_c3d, De_tap, stream));
-    if (fused_nll) RC(decoder_fused_loss(&d, &g, a->loss, st));
+    if (fused_nll) RC(decoder_fused_loss(&d, &g, a->loss, st, crit_w != nullptr));
     step_mark(3, st);
     RC(echr_stream_join(stream));          // the decoder backward's asynchronous tail: every gradient is final in `stream` order now
     if (vh) {

@@ -444,7 +444,7 @@ class DecoderFunction(torch.autograd.Function):
 
 
 def greedy_sample(video, event, c3d, ev_start, ev_len, A, seq_length, params, debug=None, multinomial=False, temperature=1.0, seed=0,
-                  table_cache=None, h0=None):
+                  table_cache=None, h0=None, drop=None):
     """OldModel.sample (OldModel_NEW.py:139-187) with every step on device; one host sync at the end.  Greedy arg-max by default
     (sample_max = 1); multinomial=True draws each token from softmax(logp / temperature) (:160-168) with the library's Philox stream
     keyed by `seed`.
@@ -453,7 +453,12 @@ def greedy_sample(video, event, c3d, ev_start, ev_len, A, seq_length, params, de
     logit-weight image) are kept in it and reused while the parameters are unchanged (data pointers, torch version counters and the
     library's own PARAM_EPOCH).
 
+    `drop` (a training-mode DropState, multinomial only): the sampled pass of self-critical training -- the decoder's dropout is active
+    with the masks echr_decoder_fwd draws for the same state at the same step (echr_decoder_sample_train).
+
     Returns (seq int64 [N,T], logp fp32 [N,T]) with T <= seq_length, or ([], []) when nothing was generated."""
+    if drop is not None and not multinomial:
+        raise ValueError('a dropout state is taken by the multinomial decode only (the greedy baseline runs in eval mode)')
     lib = L.load()
     video, event, c3d = _f32c(video), _f32c(event), _f32c(c3d)
     ps = [_f32c(p) for p in params]
@@ -481,7 +486,11 @@ def greedy_sample(video, event, c3d, ev_start, ev_len, A, seq_length, params, de
     sa = L.SampleArgs(a, seq_length, L.ptr(seq, torch.int64), L.ptr(slp), L.ptr(nun, torch.int32), L.ptr(wss),
                       1 if multinomial else 0, float(temperature), int(seed) & 0xFFFFFFFFFFFFFFFF,
                       L.ptr(tables) if tables is not None else None, valid)
-    L.check(lib.echr_decoder_sample(C.byref(sa), L.stream_ptr()), 'decoder_sample')
+    if drop is not None:
+        dc = drop.c()
+        L.check(lib.echr_decoder_sample_train(C.byref(sa), C.byref(dc), L.stream_ptr()), 'decoder_sample_train')
+    else:
+        L.check(lib.echr_decoder_sample(C.byref(sa), L.stream_ptr()), 'decoder_sample')
     counts = nun.cpu().numpy()                 # the only device->host sync of the whole decode
     L.check(lib.echr_check_async(), 'decoder_sample')
     if tables is not None:
@@ -554,6 +563,62 @@ def _nll_target(target, S):
     if t.dtype not in (torch.int64, torch.int32):
         t = t.to(torch.int64)
     return t.contiguous()
+
+
+class GatherTokens(torch.autograd.Function):
+    """Teacher-forced log-probs [N,S,V1] gathered at the tokens seq [N,T] (T <= S): the `sampleLogprobs = logprobs.gather(1, it)` of
+    OldModel.sample (OldModel_NEW.py:168) recomputed from a teacher-forced pass (echr_gather_tokens_fwd / _bwd)."""
+
+    @staticmethod
+    def forward(ctx, logp, seq):
+        lib = L.load()
+        N, S, V1 = logp.shape
+        T = seq.shape[1]
+        if seq.shape[0] != N or T > S:
+            raise ValueError('seq %s does not fit log-probs %s' % (tuple(seq.shape), tuple(logp.shape)))
+        logp = _f32c(logp)
+        sq = seq.to(device=logp.device, dtype=torch.int64).contiguous()
+        out = torch.empty(N, T, device=logp.device, dtype=torch.float32)
+        L.check(lib.echr_gather_tokens_fwd(L.ptr(logp), L.ptr(sq, torch.int64), L.ptr(out), N, S, T, V1, L.stream_ptr()), 'gather_tokens_fwd')
+        ctx.save_for_backward(sq)
+        ctx.shape = (N, S, T, V1)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        (sq,) = ctx.saved_tensors
+        N, S, T, V1 = ctx.shape
+        g_logp = torch.empty(N, S, V1, device=sq.device, dtype=torch.float32)
+        L.check(L.load().echr_gather_tokens_bwd(L.ptr(_f32c(g)), L.ptr(sq, torch.int64), L.ptr(g_logp), N, S, T, V1, L.stream_ptr()),
+                'gather_tokens_bwd')
+        return g_logp, None
+
+
+class RewardLoss(torch.autograd.Function):
+    """RewardCriterion.forward (misc/utils.py:48-59) on device: sum(-input * reward * mask) / sum(mask), mask = [1 | seq > 0][:, :-1]."""
+
+    @staticmethod
+    def forward(ctx, input, seq, reward):
+        lib = L.load()
+        N, T = input.shape
+        x = _f32c(input)
+        sq = seq.to(device=x.device, dtype=torch.int64).contiguous()
+        rw = _f32c(reward.to(device=x.device, dtype=torch.float32))
+        if tuple(sq.shape) != (N, T) or tuple(rw.shape) != (N, T):
+            raise ValueError('RewardCriterion: input %s, seq %s and reward %s must all be [N, T]' % (tuple(input.shape), tuple(seq.shape), tuple(reward.shape)))
+        out = torch.empty(2, device=x.device, dtype=torch.float32)
+        L.check(lib.echr_reward_loss_fwd(L.ptr(x), L.ptr(sq, torch.int64), L.ptr(rw), L.ptr(out), N, T, L.stream_ptr()), 'reward_loss_fwd')
+        ctx.save_for_backward(sq, rw, out)
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        sq, rw, out = ctx.saved_tensors
+        N, T = sq.shape
+        g_in = torch.empty(N, T, device=sq.device, dtype=torch.float32)
+        L.check(L.load().echr_reward_loss_bwd(L.ptr(sq, torch.int64), L.ptr(rw), L.ptr(out), L.ptr(_f32c(g).reshape(1)), L.ptr(g_in), N, T,
+                                              L.stream_ptr()), 'reward_loss_bwd')
+        return g_in, None, None
 
 
 class MaskedNLL(torch.autograd.Function):

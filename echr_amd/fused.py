@@ -229,7 +229,9 @@ class FusedTrainStep(object):
             a.vh_offset, a.tap_rows = -1, 0
 
     def _setup(self, tap_feats, c3d_feats, lda_feats, lm_labels, ind_select_list, soi_select_list, targets, masks, step, forward_only,
-               tap_grad, defer_update):
+               tap_grad, defer_update, drop=None, weights=None):
+        """(`drop`: the iteration's dropout state when the caller already drew it -- SelfCriticalStep's sampled pass used it; `weights`:
+        host [N, >= S] criterion weights of echr_train_step_rw, travelling with the index vectors)"""
         a, m, ar, lib = self.a, self.model, self.arena, self.lib
         if getattr(self, '_pending_deferred', False):
             # a deferred update may still be reading the previous call's inputs (c3d, the staged indices) on the library's streams: order this
@@ -275,6 +277,8 @@ class FusedTrainStep(object):
         # reach the loss (misc/utils.py:66-75 multiplies by the mask), so training forms logits, d logits and the logit-layer products on the
         # active rows only (ECHR_MASKED_ROWS=0: all rows).  On the device: used in place, all rows.
         host_nll = not (isinstance(targets, torch.Tensor) and targets.is_cuda) and not (isinstance(masks, torch.Tensor) and masks.is_cuda)
+        if weights is not None and not host_nll:
+            raise ValueError('criterion weights travel with host targets / masks')
         act = None
         if host_nll:
             tg_h = np.ascontiguousarray(np.asarray(targets)[:, :S], dtype=np.int32)
@@ -290,7 +294,8 @@ class FusedTrainStep(object):
                 if act.size == 0 or act.size == N * S:
                     act = None
         n_act = 0 if act is None else int(act.size)
-        host = np.empty((3 + S) * N + n_act + (2 * N * S if host_nll else 0), dtype=np.int32)
+        n_w = 0 if weights is None else N * S
+        host = np.empty((3 + S) * N + n_act + (2 * N * S if host_nll else 0) + n_w, dtype=np.int32)
         host[:N], host[N:2 * N], host[2 * N:3 * N] = soi[:, 0], lens, ind
         host[3 * N:(3 + S) * N] = labels[:, :S].T.reshape(-1)
         o = (3 + S) * N
@@ -298,7 +303,12 @@ class FusedTrainStep(object):
             host[o:o + n_act] = act
         if host_nll:
             host[o + n_act:o + n_act + N * S] = tg_h.reshape(-1)
-            host[o + n_act + N * S:] = mk_h.reshape(-1).view(np.int32)
+            host[o + n_act + N * S:o + n_act + 2 * N * S] = mk_h.reshape(-1).view(np.int32)
+            if n_w:
+                w_h = np.ascontiguousarray(np.asarray(weights)[:, :S], dtype=np.float32)
+                if w_h.shape != (N, S):
+                    raise ValueError('weights must be [N, >= S] (got %s)' % (tuple(np.asarray(weights).shape),))
+                host[o + n_act + 2 * N * S:] = w_h.reshape(-1).view(np.int32)
             tgt = msk = None
         else:
             tgt = EF._nll_target(targets if targets.is_cuda else EF.upload(targets, self.dev), S)
@@ -323,10 +333,11 @@ class FusedTrainStep(object):
         else:
             a.nll_target, a.nll_target_i64, a.nll_mask = tgt.data_ptr(), 1 if tgt.dtype == torch.int64 else 0, msk.data_ptr()
         self.last_active_rows = n_act
-        drop = m.lm_model.next_drop_state(m.fusion_model.enc_attn.dropout.p)
-        drop.training = m.training
+        if drop is None:
+            drop = m.lm_model.next_drop_state(m.fusion_model.enc_attn.dropout.p)
+            drop.training = m.training
         a.drop = drop.c()
-        need = lib.echr_train_step_ws_floats(C.byref(a))
+        need = (lib.echr_train_step_ws_floats if weights is None else lib.echr_train_step_rw_ws_floats)(C.byref(a))
         if self.ws is None or self.ws.numel() < need:
             self.join()                        # (a deferred update may still be reading the old workspace on the helper streams)
             self.ws = None                     # (released in stream order by the caching allocator)
@@ -377,6 +388,90 @@ class FusedTrainStep(object):
                     p.grad = ar.grad_view(i)
             ar._zeroed = [(0, ar.total)]
         return slot[0]
+
+
+class SelfCriticalStep(object):
+    """One self-critical training iteration (CaptionGenerator.py:32-37 + RewardCriterion, misc/utils.py:48-59; train.py:241-245, 303-308
+    past --self_critical_after) on the one-call path of `fused` (a FusedTrainStep):
+
+      event context in training mode under the iteration's dropout state -> sampled decode with the decoder's dropout active under the
+      same state (echr_decoder_sample_train) -> greedy baseline (eval mode, persistent decoder) -> ONE host sync -> reward_fn on the host
+      -> echr_train_step_rw on the teacher-forced tokens [0 | gen_result | 0] with the same dropout state: the encoder is recomputed, the
+      criterion weight is reward * mask, then clamp + Adam as FusedTrainStep does (applied-update counting included).
+
+    `reward_fn(gen_result, greedy_res)` receives int64 host tensors [N,T] / [N,T'] and returns the reward [N,T] or [N] (one value per
+    caption, broadcast over its steps), e.g. CIDEr(gen) - CIDEr(greedy) on the decoded strings.  The recomputed event context equals the
+    sampling one within fp32 rounding (bitwise under echr_amd.set_deterministic(True)): the same kernels on the same inputs and masks."""
+
+    def __init__(self, fused, reward_fn=None):
+        if not isinstance(fused, FusedTrainStep):
+            raise TypeError('SelfCriticalStep wraps a FusedTrainStep')
+        self.fused, self.reward_fn = fused, reward_fn
+
+    def __call__(self, tap_feats, c3d_feats, lda_feats, ind_select_list, soi_select_list, gen_result=None, reward=None, step=True):
+        """Returns (loss 0-d device tensor, gen_result [N,T] int64 host, greedy_res [N,T'] int64 host, reward [N,T] fp32 host).
+        `gen_result` (optional): score these captions instead of drawing them (tests pin the sample this way); `reward` (optional): use
+        it instead of calling reward_fn.  step=False stops after the backward pass (gradients as `.grad` views, as FusedTrainStep)."""
+        f = self.fused
+        m = f.model
+        lm = m.lm_model
+        L.check(f.lib.echr_check_async(), 'self_critical_step (asynchronous failure of an earlier call)')
+        if getattr(f, '_pending_deferred', False):
+            f.join()
+            f._pending_deferred = False
+        drop = lm.next_drop_state(m.fusion_model.enc_attn.dropout.p)
+        drop.training = m.training
+        with torch.no_grad():
+            ev = EF.event_index_tensors(soi_select_list, ind_select_list, c3d_feats.device, min(c3d_feats.shape[0], tap_feats.shape[0]))
+            video = m.get_video_context(tap_feats, c3d_feats, lda_feats, ind_select_list, soi_select_list)
+            clip, clip_mask = m.get_clip_context(tap_feats, c3d_feats, lda_feats, ind_select_list, soi_select_list, _ev=ev)
+            event = m.get_event_context(tap_feats, c3d_feats, lda_feats, ind_select_list, soi_select_list, _ev=ev, _drop=drop)
+            self.last_event = event          # the event context the decodes read (inspection: the step recomputes it)
+            if gen_result is None:
+                gen, _ = lm.sample_train(video, event, clip, clip_mask, drop)
+            else:
+                gen = torch.as_tensor(gen_result).to(dtype=torch.int64)
+            was_training = lm.training
+            lm.eval()
+            try:
+                greedy, _ = lm.sample(video, event, clip, clip_mask)
+            finally:
+                lm.train(was_training)
+        # the one host sync of the iteration (the greedy decode's own counter read has already drained the stream)
+        gen_h = gen.cpu() if isinstance(gen, torch.Tensor) else torch.zeros(len(soi_select_list), 0, dtype=torch.int64)
+        greedy_h = greedy.cpu() if isinstance(greedy, torch.Tensor) else torch.zeros(len(soi_select_list), 0, dtype=torch.int64)
+        N, T = gen_h.shape
+        if T == 0:
+            raise ValueError('every caption drew <eos> at its first step: nothing to train on (OldModel.sample returns [] then)')
+        if reward is None:
+            if self.reward_fn is None:
+                raise ValueError('SelfCriticalStep needs reward_fn or an explicit reward')
+            reward = self.reward_fn(gen_h, greedy_h)
+        r = np.asarray(reward.cpu() if isinstance(reward, torch.Tensor) else reward, dtype=np.float32)
+        if r.ndim == 1:
+            r = np.repeat(r[:, None], T, 1)
+        if r.shape != (N, T):
+            raise ValueError('reward must be [N, T] or [N] (got %s for gen_result %s)' % (r.shape, (N, T)))
+        g = gen_h.numpy()
+        labels = np.zeros((N, T + 2), dtype=np.int64)
+        labels[:, 1:T + 1] = g
+        # RewardCriterion's mask [1 | seq > 0][:, :-1] over the T sampled positions; the teacher-forced pass has one step more (its target is
+        # the trailing 0), which gets mask and weight 0
+        mask = np.zeros((N, T + 1), dtype=np.float32)
+        mask[:, 0] = 1.0
+        mask[:, 1:T] = g[:, :T - 1] > 0
+        w = np.zeros((N, T + 1), dtype=np.float32)
+        w[:, :T] = r * mask[:, :T]
+        a, lib = f.a, f.lib
+        if getattr(f, '_prepared', False):
+            raise RuntimeError('prepare() must be followed by a call with prepared=True')
+        slot, st = f._setup(tap_feats, c3d_feats, lda_feats, labels, ind_select_list, soi_select_list, labels[:, 1:], mask, step, False, None,
+                            False, drop=drop, weights=w)
+        a.prepared = a.handover = 0
+        a.handover_cb = a.handover_user = a.mid_cb = a.mid_user = None
+        f._pending_deferred = False
+        L.check(lib.echr_train_step_rw(C.byref(a), None, L.stream_ptr()), 'train_step_rw')
+        return f._finish(slot, st, False), gen_h, greedy_h, torch.from_numpy(r)
 
 
 class JointTrainStep(object):

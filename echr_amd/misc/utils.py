@@ -33,6 +33,24 @@ class LanguageModelCriterion(nn.Module):
         return EF.MaskedNLL.apply(input, target.to(input.device), mask.to(input.device), node)
 
 
+class RewardCriterion(nn.Module):
+    """Self-critical policy-gradient loss (misc/utils.py:48-59): sum(-input * reward * mask) / sum(mask) with mask = [1 | seq > 0][:, :-1]
+    (the step that emitted <eos> counts; no epsilon, unlike LanguageModelCriterion).  input: sample_logprobs [N,T]; seq: gen_result [N,T];
+    reward [N,T] (or [N], one value per caption), signed.  Device tensors run through echr_reward_loss_fwd / _bwd; host tensors (rewards
+    computed and kept on the host, unit checks) are reduced on the host with the same formula."""
+
+    def forward(self, input, seq, reward):
+        reward = torch.as_tensor(reward, dtype=torch.float32)
+        seq = torch.as_tensor(seq)
+        if reward.dim() == 1:
+            reward = reward[:, None].expand(seq.shape[0], seq.shape[1])
+        if not input.is_cuda:
+            mask = (seq > 0).float()
+            mask = torch.cat([mask.new_ones(mask.size(0), 1), mask[:, :-1]], 1).reshape(-1)
+            return torch.sum(-input.reshape(-1) * reward.reshape(-1).to(input.dtype) * mask.to(input.dtype)) / torch.sum(mask)
+        return EF.RewardLoss.apply(input, seq.to(input.device), reward.to(input.device).contiguous())
+
+
 class TAPModelCriterion(nn.Module):
     """Weighted BCE of the proposal head (misc/utils.py:78-99), evaluated by echr_tap_bce_fwd/bwd."""
 

@@ -232,18 +232,44 @@ class OldModel(nn.Module):
             raise NotImplementedError('beam search (beam_size > 1) is not on the HIP path')
         cv = self._clip_view(clip, clip_mask)
         multinomial = opt.get('sample_max', 1) != 1
-        seed = 0
-        if multinomial:
-            if self._drop_seed is None:
-                self.next_drop_state()                     # derives the (rank-mixed) seed once
-            self._sample_calls = getattr(self, '_sample_calls', 0) + 1
-            seed = (self._drop_seed * 0x9E3779B97F4A7C15 + self._sample_calls) & 0xFFFFFFFFFFFFFFFF
+        seed = self._sample_seed() if multinomial else 0
         with torch.no_grad():
             if '_sample_tables' not in self.__dict__:
                 self._sample_tables = {}          # decoding operands derived from the parameters alone, reused across calls (EF.greedy_sample)
             return EF.greedy_sample(video, event, cv.feats, cv.ev_start, cv.ev_len, cv.max_len, self.seq_length,
                                     self.native_params(), multinomial=multinomial, temperature=float(opt.get('temperature', 1.0)),
                                     seed=seed, table_cache=self._sample_tables, h0=self._initial_state(video, event, cv))
+
+
+    def _sample_seed(self):
+        """Seed of the next multinomial decode: one per call, derived from the (rank-mixed) dropout seed."""
+        if self._drop_seed is None:
+            self.next_drop_state()                         # derives the (rank-mixed) seed once
+        self._sample_calls = getattr(self, '_sample_calls', 0) + 1
+        return (self._drop_seed * 0x9E3779B97F4A7C15 + self._sample_calls) & 0xFFFFFFFFFFFFFFFF
+
+    def sample_train(self, video, event, clip, clip_mask, drop, temperature=1.0, seed=None):
+        """The sampled pass of self-critical training (CaptionGenerator.py:33 -> sample(..., {'sample_max': 0}) in training mode,
+        OldModel_NEW.py:139-187): a multinomial draw per step with the decoder's dropout active under `drop`, the masks that forward() draws
+        for the same state at the same step (echr_decoder_sample_train).  Returns (gen_result int64 [N,T], log-probs at the drawn tokens
+        [N,T]) without a graph, or ([], []); score the tokens with sequence_logprobs() for the gradient."""
+        cv = self._clip_view(clip, clip_mask)
+        seed = self._sample_seed() if seed is None else int(seed)
+        with torch.no_grad():
+            return EF.greedy_sample(video, event, cv.feats, cv.ev_start, cv.ev_len, cv.max_len, self.seq_length, self.native_params(),
+                                    multinomial=True, temperature=float(temperature), seed=seed, h0=self._initial_state(video, event, cv),
+                                    drop=drop)
+
+    def sequence_logprobs(self, video, event, clip, clip_mask, seq, drop=None):
+        """Log-probs [N,T] of the given captions seq [N,T] (zero after a row's <eos>): the teacher-forced forward() on [0 | seq | 0] under
+        `drop`, gathered at seq -- with the drop state of the sampled pass these are its `sampleLogprobs` up to each row's <eos>, and the
+        gradient flows through the decoder into `event` like forward()'s (the sampling loop keeps no graph)."""
+        seq = torch.as_tensor(seq)
+        N, T = seq.shape
+        labels = torch.zeros(N, T + 2, dtype=torch.int64, device=seq.device)
+        labels[:, 1:T + 1] = seq
+        logp = self.forward(video, event, clip, clip_mask, labels, drop=drop)
+        return EF.GatherTokens.apply(logp, seq)
 
 
 class Attention(nn.Module):

@@ -167,6 +167,11 @@ CASES = {
     # that the mean over the PADDED frame slots differs from a mean over each event's own rows
     'init': dict(opt=dict(CG_init_feats_type='VEC', CG_vocab_size=300, CG_seq_length=7), video=dict(N=12, A=40, L=9, seed=68)),
     'initc': dict(opt=dict(CG_init_feats_type='C', CG_vocab_size=300, CG_seq_length=7), video=dict(N=12, A=40, L=9, seed=69)),
+    # self-critical training with captions that end at different steps (tests/golden/case_scst_eos.npz): the 'tiny' widths with more events
+    # and steps; tools/make_golden_scst.py picks the reference's draw seed whose rows finish at three or more different steps
+    'tiny_eos': dict(opt=dict(video_dim=20, hidden_dim=24, lda_dim=12, d_feats=32, d_o=32, n_head=4, CG_rnn_size=32,
+                              CG_input_encoding_size=16, CG_att_hid_size=24, CG_vocab_size=30, CG_seq_length=6),
+                     video=dict(N=8, A=7, L=8, seed=13)),
     # EXACTLY the layout bench.py times (BASELINE config 3): 64 disjoint 128-segment events on a T_v = 8192 video
     'c3bench': dict(opt=dict(CG_vocab_size=5000, CG_seq_length=19), video=dict(N=64, A=128, L=21, seed=1234, disjoint=True)),
 }

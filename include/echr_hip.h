@@ -376,6 +376,23 @@ typedef struct {
 int64_t echr_sampler_ws_floats(const echr_dec_args* a);
 int64_t echr_sampler_table_floats(const echr_dec_args* a);      /* 0 when the persistent decoder does not apply to these shapes / settings */
 int echr_decoder_sample(const echr_sample_args* a, void* stream);
+/* The sampled pass of self-critical training (CaptionGenerator.py:32-37 -> OldModel.sample with sample_max = 0 while the model is in
+ * training mode, OldModel_NEW.py:139-187): the multinomial decode (a->multinomial must be 1) with the decoder's dropout ACTIVE, its masks
+ * those of echr_decoder_fwd's step t under the same `drop` (keyed by element, step t, site, drop->offset), so a teacher-forced
+ * echr_decoder_fwd on the tokens [0 | seq | 0] with the same `drop` reproduces seq_logp at every position up to a row's <eos>.  Always
+ * the launch-per-step chain (the persistent decoder has neither draws nor dropout); its own ws / ws_sample, like echr_decoder_sample. */
+int echr_decoder_sample_train(const echr_sample_args* a, const echr_dropout* drop, void* stream);
+
+/* Self-critical training on gathered log-probs (the module path; the one-call path is echr_train_step_rw).
+ * echr_gather_tokens_fwd: out [N,T] = logp [N,S,V1] at (n, t, seq[n,t]), t < T <= S; _bwd writes g_logp [N,S,V1] in full (zero but there).
+ * echr_reward_loss_fwd: RewardCriterion (misc/utils.py:48-59), mask[n,0] = 1, mask[n,t] = (seq[n,t-1] > 0):
+ *   out[0] = sum(-input * reward * mask) / sum(mask) (no epsilon), out[1] = sum(mask); input / reward [N,T], seq int64 [N,T].
+ * echr_reward_loss_bwd: g_input [N,T] = -reward * mask / fwd_out[1] * g_loss[0]. */
+int echr_gather_tokens_fwd(const float* logp, const int64_t* seq, float* out, int32_t N, int32_t S, int32_t T, int32_t V1, void* stream);
+int echr_gather_tokens_bwd(const float* g_out, const int64_t* seq, float* g_logp, int32_t N, int32_t S, int32_t T, int32_t V1, void* stream);
+int echr_reward_loss_fwd(const float* input, const int64_t* seq, const float* reward, float* out, int32_t N, int32_t T, void* stream);
+int echr_reward_loss_bwd(const int64_t* seq, const float* reward, const float* fwd_out, const float* g_loss, float* g_input,
+                         int32_t N, int32_t T, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * SST proposal encoder.  Replaces models/sst_model.py:31-40 (nn.LSTM over one video + Linear + sigmoid)
@@ -553,6 +570,16 @@ int64_t echr_train_step_ws_floats(const echr_train_step_args* a);
  * changes for the caller: host_index is copied inside the call, and `ws` must stay untouched between calls as it always had to (it holds the
  * saved activations until the call's last kernel).  ECHR_STAGE_AHEAD=0 in the environment switches it off. */
 int echr_train_step(const echr_train_step_args* a, void* stream);
+/* Self-critical training step (RewardCriterion, misc/utils.py:48-59): echr_train_step with the criterion
+ *   loss = sum(-logp[target] * w) / sum(mask),   w[n,t] = reward[n,t] * mask[n,t]   (signed; no epsilon in the denominator)
+ * for the teacher-forced tokens [0 | gen_result | 0].  Rows with a non-zero mask are the active rows, whatever their reward.
+ * `weight`: device [N,S] fp32 with host_nll = 0; with host_nll = 1 host_index carries it behind the mask (| weights fp32 [N*S]) and
+ * `weight` must be NULL (both at once is an error).
+ * Workspace: echr_train_step_rw_ws_floats (the index region holds the weights too).  prepared must be 0.  Every other field, the
+ * applied-update counting and stage-ahead behave as in echr_train_step: the sampled / greedy decodes a caller runs between two calls use
+ * workspaces of their own and are ordered on the caller's stream, so they need no extra guard. */
+int64_t echr_train_step_rw_ws_floats(const echr_train_step_args* a);
+int echr_train_step_rw(const echr_train_step_args* a, const float* weight, void* stream);
 /* Optional first half for the joint 'tap_cg' iteration (train.py:300-313): stages the index vectors and starts everything of the call that
  * does not read tap_feats (the decoder's event-independent part, the gradient-arena fill) on the library's prepare stream, so that it runs
  * beside the proposal encoder's forward the caller queues next.  Takes the arguments of the following echr_train_step (tap, g_tap, loss
