@@ -49,12 +49,19 @@ class CaptionGenerator(nn.Module):
         self.lm_model._drop_seed = int(seed)
         self.lm_model._drop_calls = int(calls)
 
-    def forward(self, tap_feats, c3d_feats, lda_feats, lm_labels, ind_select_list, soi_select_list, mode='train', gen_result=None):
-        """`gen_result` (mode='train_rl' only, optional): score these captions [N,T] instead of drawing them (tests, replayed samples)."""
+    def forward(self, tap_feats, c3d_feats, lda_feats, lm_labels, ind_select_list, soi_select_list, mode='train', gen_result=None,
+                beam_size=1, return_score=False):
+        """`gen_result` (mode='train_rl' only, optional): score these captions [N,T] instead of drawing them (tests, replayed samples).
+        `beam_size` (mode='eval' only): > 1 decodes by beam search (OldModel.sample with opt beam_size); `return_score` (with beam_size > 1)
+        appends each caption's score, the sum of its token log-probs (<eos> included)."""
         if mode not in ('train', 'eval', 'train_rl'):
             raise NotImplementedError("mode=%r: 'train', 'eval' and 'train_rl' are the reference's live modes (SURVEY section 2 row 12)" % (mode,))
         if gen_result is not None and mode != 'train_rl':
             raise ValueError("gen_result is taken by mode='train_rl' only")
+        if beam_size != 1 and mode != 'eval':
+            raise ValueError("beam_size is taken by mode='eval' only")
+        if return_score and (mode != 'eval' or beam_size == 1):
+            raise ValueError("return_score is taken by mode='eval' with beam_size > 1 only")
         self._require_live_decoder()
         if not c3d_feats.is_cuda:
             raise EF.L.EchrHipError('CaptionGenerator runs on the GPU only: move the module and its inputs with .cuda()')
@@ -77,6 +84,8 @@ class CaptionGenerator(nn.Module):
             return self.lm_model(video, event, clip, clip_mask, lm_labels, drop=drop, prepared=prepared)
         if mode == 'train_rl':
             return self._train_rl(video, event, clip, clip_mask, drop, gen_result)
+        if beam_size != 1:
+            return self.lm_model.sample(video, event, clip, clip_mask, {'beam_size': beam_size, 'return_score': return_score})
         return self.lm_model.sample(video, event, clip, clip_mask)
 
     def _train_rl(self, video, event, clip, clip_mask, drop, gen_result):

@@ -88,6 +88,11 @@ class SampleArgs(C.Structure):
                 ('tables', c_f), ('tables_valid', i32)]
 
 
+class BeamArgs(C.Structure):
+    _fields_ = [('dec', DecArgs), ('beam_size', i32), ('seq_len', i32), ('seq', c_f), ('seq_logp', c_f), ('score', c_f), ('words', c_f),
+                ('ws_beam', c_f)]
+
+
 HANDOVER_FN = C.CFUNCTYPE(None, i32, C.c_void_p, C.c_void_p)          # echr_handover_fn
 MID_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p)                    # echr_mid_fn
 
@@ -139,6 +144,8 @@ SYMBOLS = [
     ('echr_sampler_table_floats', i64, [C.POINTER(DecArgs)]),
     ('echr_decoder_sample', i32, [C.POINTER(SampleArgs), C.c_void_p]),
     ('echr_decoder_sample_train', i32, [C.POINTER(SampleArgs), C.POINTER(Dropout), C.c_void_p]),
+    ('echr_beam_ws_floats', i64, [C.POINTER(BeamArgs)]),
+    ('echr_decoder_beam', i32, [C.POINTER(BeamArgs), C.c_void_p]),
     ('echr_gather_tokens_fwd', i32, [c_f, c_f, c_f, i32, i32, i32, i32, C.c_void_p]),
     ('echr_gather_tokens_bwd', i32, [c_f, c_f, c_f, i32, i32, i32, i32, C.c_void_p]),
     ('echr_reward_loss_fwd', i32, [c_f, c_f, c_f, c_f, i32, i32, C.c_void_p]),
@@ -179,7 +186,8 @@ SYMBOLS = [
 
 ABI_STRUCTS = {'echr_gemm_desc': GemmDesc, 'echr_dropout': Dropout, 'echr_tsrm_args': TsrmArgs, 'echr_tsrm_grads': TsrmGrads,
                'echr_dec_args': DecArgs, 'echr_dec_grads': DecGrads, 'echr_sample_args': SampleArgs, 'echr_sst_args': SstArgs,
-               'echr_sst_grads': SstGrads, 'echr_train_step_args': TrainStepArgs, 'echr_init_state_args': InitStateArgs, 'echr_init_state_grads': InitStateGrads}
+               'echr_sst_grads': SstGrads, 'echr_train_step_args': TrainStepArgs, 'echr_init_state_args': InitStateArgs, 'echr_init_state_grads': InitStateGrads,
+               'echr_beam_args': BeamArgs}
 
 ABI_VERSION = 3          # include/echr_hip.h ECHR_ABI_VERSION
 _lib = None

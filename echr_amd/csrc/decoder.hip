@@ -2045,7 +2045,7 @@ static SampTables carve_tables(const echr_dec_args* a, float* base) {
 constexpr int SAMP_SLAB_ROWS = 192;
 constexpr int SAMP_SLABS = 4;
 static inline int samp_slabs(const echr_dec_args* a) { (void)a; return SAMP_SLABS; }
-static SampWs carve_samp(const echr_dec_args* a, float* base) {
+static SampWs carve_samp(const echr_dec_args* a, float* base, bool persist_bufs = true) {
     SampWs s;
     long off = 0;
     auto take = [&](long n) { float* p = base ? base + off : nullptr; off += rup(n, 64); return p; };
@@ -2056,7 +2056,7 @@ static SampWs carve_samp(const echr_dec_args* a, float* base) {
     s.SLABS = take(a->N < SAMP_SLAB_ROWS ? (long)((samp_slabs(a) + 3) / 4 * 4) * a->N * a->V1 : 64);
     // persistent decoding (csrc/persist.hip, PersistS): token-side gate tables, the packed embedding they are made from, the logit-weight
     // image and the launch's exchange buffers
-    const bool ps = persist_sample_shape_ok(a);          // by shape only: the carving must not depend on switches that can change between calls
+    const bool ps = persist_bufs && persist_sample_shape_ok(a);          // by shape only: the carving must not depend on switches that can change between calls
     s.TABLES = take(ps ? carve_tables(a, nullptr).total : 64);
     const long groups = (a->N + 63) / 64;          // the persistent decoder runs one launch per group of 64 events, each on its own workspaces
     s.PSWS = take(ps ? groups * persist_sample_ws_floats(a->S, a->V1) : 64);
@@ -2089,7 +2089,7 @@ static int step_fwd_big(const echr_dec_args* a, const DecWs& w, const SampWs& s,
     const long gs = (long)N * 4 * H, qs = (long)N * Ha;
     (void)hprev;
     float* qt = w.QACC + (long)t * qs;          // this step's q: its own zero-filled slab (the caller cleared QACC once), so the product accumulates
-    if (t > 0) {          // (h(-1) = 0: nothing to add at the first step; q = 0 then, the score kernel adds b_h2a)
+    if (t > 0 || a->h0) {          // (h(-1) = 0 without echr_dec_args.h0: nothing to add at the first step; q = 0 then, the score kernel adds b_h2a)
         echr_gemm_desc g4[4];          // the caller packed h(t-1) of the three streams with the step's token embeddings
         for (int k = 0; k < 3; ++k) g4[k] = desc_h2(s.PK_H[k], s.PK_WHH[k], w.GATES[k] + (long)t * gs, 4 * H, N, 4 * H, H);
         g4[3] = desc_h2(s.PK_H[1], s.PK_WH2A, qt, Ha, N, Ha, H);
@@ -2150,6 +2150,70 @@ extern "C" int64_t echr_sampler_ws_floats(const echr_dec_args* a) { return a ? c
 extern "C" int64_t echr_sampler_table_floats(const echr_dec_args* a) {
     if (!a) return -1;
     return sample_uses_persistent(a) ? carve_tables(a, nullptr).total : 0;
+}
+
+// The launch-per-step decode chain shared by the sampler (decoder_sample_impl) and beam search (echr_decoder_beam).  chain_setup runs
+// once per decode, chain_step once per step: the decoder timestep from IT (the tokens fed at step t) and the logits product.  `big`
+// (many rows with gemm_h2: every product an h2 GEMM over the rows) is decided by the caller once per decode.  With the slab form of the
+// logits product (few rows) the logits are left as k-slice slabs in SLABS unless `sum_slabs` asks for them in LOGITS (*slab_form says
+// which); otherwise LOGITS holds them, bias included.
+static int chain_setup(const echr_dec_args& a, const DecWs& w, const SampWs& s, bool big, hipStream_t st) {
+    const int N = a.N, H = a.H, E = a.E, L = a.S;
+    RC(precompute_static(&a, w, st, big));
+    if (big) RC(fill_zero(w.QACC, (long)L * N * a.Ha, st));          // q(t) slabs of step_fwd_big
+    if (big) {          // recurrent weights as h2 operands, once per decode
+        H2PackJob pj[5] = {pack_rows(a.w_hh[0], H, 4 * H, H, s.PK_WHH[0]), pack_rows(a.w_hh[1], H, 4 * H, H, s.PK_WHH[1]),
+                           pack_rows(a.w_hh[2], H, 4 * H, H, s.PK_WHH[2]), pack_rows(a.w_h2a, H, a.Ha, H, s.PK_WH2A),
+                           pack_rows(a.w_ih[1] + E, E + a.D, 4 * H, a.D, s.PK_WATT)};
+        RC(h2_pack_multi(pj, 5, st));
+    }
+    const int nsl = samp_slabs(&a), nsl4 = (nsl + 3) / 4 * 4;          // slabs are added four at a time: the spare ones stay zero
+    if (N < SAMP_SLAB_ROWS && nsl4 > nsl) RC(fill_zero(s.SLABS + (long)nsl * N * a.V1, (long)(nsl4 - nsl) * N * a.V1, st));
+    return 0;
+}
+static int chain_step(const echr_dec_args& a, const DecWs& w, const SampWs& s, int t, bool big, const DropCfg& dh, const DropCfg& dout,
+                      bool sum_slabs, bool* slab_form, hipStream_t st) {
+    const int N = a.N, H = a.H, E = a.E;
+    const int nsl4 = (samp_slabs(&a) + 3) / 4 * 4;
+    if (big) {
+        RC(embed_gather(a.embed, s.IT, s.XT, N, E, a.V1, st));
+        {   // the step's h2 operands in ONE pack launch: the token embeddings and the three streams' h(t-1)
+            const float* hprev = w.HS + (long)t * N * 3 * H;
+            H2PackJob pj[4] = {pack_rows(s.XT, E, N, E, w.PK_XT), pack_rows(hprev, 3 * H, N, H, s.PK_H[0]), pack_rows(hprev + H, 3 * H, N, H, s.PK_H[1]),
+                               pack_rows(hprev + 2 * H, 3 * H, N, H, s.PK_H[2])};
+            RC(h2_pack_multi(pj, (t > 0 || a.h0) ? 4 : 1, st));
+        }
+        RC(input_gates(&a, w, s.XT, t, 1, st, false, true, true));
+        RC(step_fwd_big(&a, w, s, t, dh, dout, st));
+    } else {
+        // few events: no embedding gather, no input-gate GEMM -- the token-side products are jobs of the step's first grouped launch
+        // (rows gathered from the embedding table by token id), the time-invariant addends are read by the gate kernel
+        RC(step_fwd(&a, w, t, dh, dout, st, 0, false, s.IT));
+    }
+    *slab_form = false;
+    if (big) {
+        H2PackJob pj = pack_rows(w.OUTD + (long)t * N * 3 * H, 3 * H, N, 3 * H, w.PK_OUTD);
+        RC(h2_pack_multi(&pj, 1, st));
+        echr_gemm_desc d = desc_h2(w.PK_OUTD, w.PK_WL, s.LOGITS, a.V1, N, a.V1, 3 * H);
+        d.bias = a.b_logit; d.split_k = 1;
+        RC(gemm(d, st));
+    } else if (N < SAMP_SLAB_ROWS && (3 * H) % (SAMP_SLABS * 32) == 0) {
+        const int ksl = 3 * H / SAMP_SLABS;
+        echr_gemm_desc d = desc_nt(w.OUTD + (long)t * N * 3 * H, 3 * H, a.w_logit, 3 * H, s.SLABS, a.V1, N, a.V1, ksl);
+        d.batch = SAMP_SLABS; d.bsa = ksl; d.bsb = ksl; d.bsc = (long)N * a.V1; d.split_k = 1;
+        RC(gemm(d, st));
+        *slab_form = true;
+        if (sum_slabs) {         // the multinomial / beam steps read finished logits: sum the slabs first (the greedy step folds the sum in)
+            const long n = (long)N * a.V1;
+            hipLaunchKernelGGL(slab_sum_bias_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, s.SLABS, n, nsl4, a.b_logit, s.LOGITS, n, a.V1);
+            RC(check_launch("slab_sum_bias"));
+        }
+    } else {
+        echr_gemm_desc d = desc_nt(w.OUTD + (long)t * N * 3 * H, 3 * H, a.w_logit, 3 * H, s.LOGITS, a.V1, N, a.V1, 3 * H);
+        d.bias = a.b_logit; d.split_k = 1;
+        RC(gemm(d, st));
+    }
+    return 0;
 }
 
 // drop != nullptr: echr_decoder_sample_train -- the launch-per-step chain with the caller's training-mode dropout masks, keyed like
@@ -2217,55 +2281,11 @@ static int decoder_sample_impl(const echr_sample_args* sa, const echr_dropout* d
         return 0;
     }
     const bool big = config().gemm_h2 && N >= SAMP_SLAB_ROWS;
-    RC(precompute_static(&a, w, st, big));
-    if (big) RC(fill_zero(w.QACC, (long)L * N * a.Ha, st));          // q(t) slabs of step_fwd_big
-    if (big) {          // recurrent weights as h2 operands, once per decode
-        H2PackJob pj[5] = {pack_rows(a.w_hh[0], H, 4 * H, H, s.PK_WHH[0]), pack_rows(a.w_hh[1], H, 4 * H, H, s.PK_WHH[1]),
-                           pack_rows(a.w_hh[2], H, 4 * H, H, s.PK_WHH[2]), pack_rows(a.w_h2a, H, a.Ha, H, s.PK_WH2A),
-                           pack_rows(a.w_ih[1] + E, E + a.D, 4 * H, a.D, s.PK_WATT)};
-        RC(h2_pack_multi(pj, 5, st));
-    }
-    const int nsl = samp_slabs(&a), nsl4 = (nsl + 3) / 4 * 4;          // slabs are added four at a time: the spare ones stay zero
-    if (N < SAMP_SLAB_ROWS && nsl4 > nsl) RC(fill_zero(s.SLABS + (long)nsl * N * a.V1, (long)(nsl4 - nsl) * N * a.V1, st));
+    RC(chain_setup(a, w, s, big, st));
+    const int nsl4 = (samp_slabs(&a) + 3) / 4 * 4;
     for (int t = 0; t < L; ++t) {
-        if (big) {
-            RC(embed_gather(a.embed, s.IT, s.XT, N, E, a.V1, st));
-            {   // the step's h2 operands in ONE pack launch: the token embeddings and the three streams' h(t-1)
-                const float* hprev = w.HS + (long)t * N * 3 * H;
-                H2PackJob pj[4] = {pack_rows(s.XT, E, N, E, w.PK_XT), pack_rows(hprev, 3 * H, N, H, s.PK_H[0]), pack_rows(hprev + H, 3 * H, N, H, s.PK_H[1]),
-                                   pack_rows(hprev + 2 * H, 3 * H, N, H, s.PK_H[2])};
-                RC(h2_pack_multi(pj, t > 0 ? 4 : 1, st));
-            }
-            RC(input_gates(&a, w, s.XT, t, 1, st, false, true, true));
-            RC(step_fwd_big(&a, w, s, t, dh, dout, st));
-        } else {
-            // few events: no embedding gather, no input-gate GEMM -- the token-side products are jobs of the step's first grouped launch
-            // (rows gathered from the embedding table by token id), the time-invariant addends are read by the gate kernel
-            RC(step_fwd(&a, w, t, dh, dout, st, 0, false, s.IT));
-        }
         bool slab_form = false;
-        if (big) {
-            H2PackJob pj = pack_rows(w.OUTD + (long)t * N * 3 * H, 3 * H, N, 3 * H, w.PK_OUTD);
-            RC(h2_pack_multi(&pj, 1, st));
-            echr_gemm_desc d = desc_h2(w.PK_OUTD, w.PK_WL, s.LOGITS, a.V1, N, a.V1, 3 * H);
-            d.bias = a.b_logit; d.split_k = 1;
-            RC(gemm(d, st));
-        } else if (N < SAMP_SLAB_ROWS && (3 * H) % (SAMP_SLABS * 32) == 0) {
-            const int ksl = 3 * H / SAMP_SLABS;
-            echr_gemm_desc d = desc_nt(w.OUTD + (long)t * N * 3 * H, 3 * H, a.w_logit, 3 * H, s.SLABS, a.V1, N, a.V1, ksl);
-            d.batch = SAMP_SLABS; d.bsa = ksl; d.bsb = ksl; d.bsc = (long)N * a.V1; d.split_k = 1;
-            RC(gemm(d, st));
-            slab_form = true;
-            if (sa->multinomial) {         // the multinomial step reads finished logits: sum the slabs first (the greedy step folds the sum in)
-                const long n = (long)N * a.V1;
-                hipLaunchKernelGGL(slab_sum_bias_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, s.SLABS, n, nsl4, a.b_logit, s.LOGITS, n, a.V1);
-                RC(check_launch("slab_sum_bias"));
-            }
-        } else {
-            echr_gemm_desc d = desc_nt(w.OUTD + (long)t * N * 3 * H, 3 * H, a.w_logit, 3 * H, s.LOGITS, a.V1, N, a.V1, 3 * H);
-            d.bias = a.b_logit; d.split_k = 1;
-            RC(gemm(d, st));
-        }
+        RC(chain_step(a, w, s, t, big, dh, dout, sa->multinomial != 0, &slab_form, st));
         if (sa->multinomial)
             RC(sample_step(s.LOGITS, a.V1, N, a.V1, t, L, s.IT, s.UNF, reinterpret_cast<long long*>(sa->seq), sa->seq_logp, sa->n_unfinished,
                            sa->temperature, sa->seed, st));
@@ -2274,6 +2294,68 @@ static int decoder_sample_impl(const echr_sample_args* sa, const echr_dropout* d
                            sa->n_unfinished, st, slab_form ? s.SLABS : nullptr, (long)N * a.V1, a.b_logit, nsl4));
     }
     return 0;
+}
+
+// ------------------------------------------------------------------------------------------------------
+// beam search (echr_decoder_beam): the launch-per-step chain over events * B rows, one beam_step launch per step (beam.hip)
+// ------------------------------------------------------------------------------------------------------
+struct BeamWs { SampWs s; BeamState b; long total; };
+static BeamWs carve_beam(const echr_dec_args* a, int B, float* base) {          // a->N = rows, a->S = seq_len
+    BeamWs r;
+    r.s = carve_samp(a, base, false);          // (never the persistent decoder)
+    long off = r.s.total;
+    auto take = [&](long n) { float* p = base ? base + off : nullptr; off += rup(n, 64); return p; };
+    const long N = a->N, E = N / B, L = a->S;
+    r.b.SCORE = take(N);
+    r.b.ALIVE = reinterpret_cast<int*>(take(N));
+    r.b.HTOK = reinterpret_cast<int*>(take(N * L));
+    r.b.HLP = take(N * L);
+    r.b.BTOK = reinterpret_cast<int*>(take(E * L));
+    r.b.BLP = take(E * L);
+    r.b.BSCORE = take(E);
+    r.b.BW = reinterpret_cast<int*>(take(E));
+    r.total = off;
+    return r;
+}
+extern "C" int64_t echr_beam_ws_floats(const echr_beam_args* ba) {
+    if (!ba || ba->beam_size < 1 || ba->seq_len <= 0 || ba->dec.N <= 0 || ba->dec.N % ba->beam_size) return -1;
+    echr_dec_args a = ba->dec;
+    a.S = ba->seq_len;
+    return carve_beam(&a, ba->beam_size, nullptr).total;
+}
+extern "C" int echr_decoder_beam(const echr_beam_args* ba, void* stream) {
+    ECHR_REQUIRE(ba, "decoder_beam: null args");
+    RC(persist_check_async());
+    DeterministicScope det;                    // `seq` is an index output: bitwise reproducible logits, as the sampler's
+    echr_dec_args a = ba->dec;
+    const int L = ba->seq_len, B = ba->beam_size;
+    ECHR_REQUIRE(L > 0 && ba->seq && ba->seq_logp && ba->score && ba->words && ba->ws_beam && a.ws, "decoder_beam: missing buffers");
+    ECHR_REQUIRE(B >= 1 && B <= 16 && B <= a.V1, "decoder_beam: beam_size %d outside [1, min(16, V1)]", B);
+    ECHR_REQUIRE(a.N > 0 && a.N % B == 0, "decoder_beam: dec.N = %d is not events * beam_size (%d)", a.N, B);
+    ECHR_REQUIRE(!a.rows_disjoint, "decoder_beam: the B rows of an event share its clip rows (rows_disjoint must be 0)");
+    a.S = L;                                   // workspace is carved for seq_len steps
+    RC(check_dims(&a, "decoder_beam"));
+    hipStream_t st = (hipStream_t)stream;
+    const int N = a.N, H = a.H, E = N / B;
+    DecWs w = carve_ws(&a, a.ws);
+    const BeamWs bw = carve_beam(&a, B, ba->ws_beam);
+    const DropCfg none = make_drop(nullptr, 0.f);
+    {
+        float* zp[5] = {w.HS, w.CS[0], w.CS[1], w.CS[2], reinterpret_cast<float*>(bw.s.IT)};          // zero state, <bos> = 0
+        long zn[5] = {(long)N * 3 * H, (long)N * H, (long)N * H, (long)N * H, N};
+        RC(fill_zero_multi(zp, zn, 5, st));
+    }
+    if (a.h0) RC(init_state_copy(&a, w, st));
+    const bool big = config().gemm_h2 && N >= SAMP_SLAB_ROWS;
+    RC(chain_setup(a, w, bw.s, big, st));
+    for (int t = 0; t < L; ++t) {
+        bool slab_form = false;
+        RC(chain_step(a, w, bw.s, t, big, none, none, true, &slab_form, st));
+        // the only per-row carries of the chain across steps: h / c after step t (HS[t+1], CS[k][t+1]) and the next tokens (IT)
+        const long o = (long)(t + 1) * N;
+        RC(beam_step(bw.s.LOGITS, a.V1, E, B, t, L, bw.s.IT, bw.b, w.HS + o * 3 * H, w.CS[0] + o * H, w.CS[1] + o * H, w.CS[2] + o * H, H, st));
+    }
+    return beam_finalize(bw.b, E, L, reinterpret_cast<long long*>(ba->seq), ba->seq_logp, ba->score, ba->words, st);
 }
 
 // ------------------------------------------------------------------------------------------------------

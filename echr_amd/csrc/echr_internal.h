@@ -208,5 +208,10 @@ int sample_step(const float* logits, long ld, int N, int V1, int t, int seq_len,
 int greedy_step(float* logits, long ld, int N, int V1, int t, int seq_len, int* it_next, int* unfinished,
                 long long* seq, float* seq_logp, int* n_unfinished, hipStream_t st, const float* slabs = nullptr, long slab_stride = 0,
                 const float* bias = nullptr, int nslab = 0);
+// beam search (beam.hip; driver echr_decoder_beam in decoder.hip): per-slot scores / alive flags and histories [rows, L], per-event result
+struct BeamState { float* SCORE; int* ALIVE; int* HTOK; float* HLP; int* BTOK; float* BLP; float* BSCORE; int* BW; };
+int beam_step(const float* logits, int V1, int E, int B, int t, int L, int* IT, const BeamState& bs, float* HS, float* C0, float* C1, float* C2,
+              int H, hipStream_t st);
+int beam_finalize(const BeamState& bs, int E, int L, long long* seq, float* seq_logp, float* score, int* words, hipStream_t st);
 
 }  // namespace echr

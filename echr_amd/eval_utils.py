@@ -72,13 +72,15 @@ def gettop1000_nms(pred_proposals, tap_masks, cg_gts, duration, featstamp_to_tim
 
 
 def caption_video(tap_model, cg_model, c3d_feats, lda_feats, duration, featstamp_to_time, vocab=None, tap_masks=None, cg_gts=(),
-                  topN=1000, nms_threshold=0.0, val_score_thres=0.0, flag_eval_what='tap_cg'):
+                  topN=1000, nms_threshold=0.0, val_score_thres=0.0, flag_eval_what='tap_cg', beam_size=1):
     """One video through the reference's evaluation flow (eval_utils.py:51-53,106-167 for flag_eval_what 'tap_cg' / 'tap'):
     SST -> proposal selection (greedy NMS when nms_threshold != 0, else score threshold) -> greedy captions -> the per-proposal
     records of result.json.  Everything between the two host reads (proposal count, caption lengths) stays on the GPU.
 
     Returns (vid_info, extras): vid_info is the reference's list of dicts (sentence, timestamp, sentence_confidence, proposal_score,
-    re_score, num); extras carries the tensors (tap_feats, pred_proposals, seq, ind_select_list, soi_select_list)."""
+    re_score, num); extras carries the tensors (tap_feats, pred_proposals, seq, ind_select_list, soi_select_list).
+    beam_size > 1 captions by beam search (the reference's --beam_size); sentence_confidence is then each caption's beam score (the sum
+    of its token log-probs, <eos> included)."""
     if not c3d_feats.is_cuda:
         raise L.EchrHipError('caption_video runs on the GPU: move the models and features with .cuda()')
     nfeats = c3d_feats.shape[0]
@@ -101,11 +103,18 @@ def caption_video(tap_model, cg_model, c3d_feats, lda_feats, duration, featstamp
         if flag_eval_what == 'tap':
             sents, cg_score = [0] * n, [0] * n
         else:
-            seq, cg_prob = cg_model(tap_feats, c3d_feats, lda_feats, [], ind_select_list, soi_select_list, mode='eval')
+            if beam_size != 1:
+                seq, cg_prob, beam_score = cg_model(tap_feats, c3d_feats, lda_feats, [], ind_select_list, soi_select_list, mode='eval',
+                                                    beam_size=beam_size, return_score=True)
+            else:
+                seq, cg_prob = cg_model(tap_feats, c3d_feats, lda_feats, [], ind_select_list, soi_select_list, mode='eval')
             if len(seq) == 0:
                 return [], extras
             extras['seq'], extras['cg_prob'] = seq, cg_prob
-            cg_score = cg_prob.sum(1).cpu().numpy().astype('float')
+            if beam_size != 1:
+                cg_score = beam_score.cpu().numpy().astype('float')
+            else:
+                cg_score = cg_prob.sum(1).cpu().numpy().astype('float')
             sents = utils.decode_sequence(vocab, seq) if vocab is not None else [row[row > 0].tolist() for row in seq.cpu().numpy()]
     vid_info = []
     for i, sent in enumerate(sents):

@@ -511,6 +511,50 @@ def greedy_sample(video, event, c3d, ev_start, ev_len, A, seq_length, params, de
     return seq[:, :T].contiguous(), slp[:, :T].contiguous()
 
 
+BEAM_MAX = 16          # echr_decoder_beam's largest beam
+
+
+def beam_search(video, event, c3d, ev_start, ev_len, A, seq_length, params, beam_size, h0=None):
+    """Beam search (OldModel.sample with opt beam_size, eval mode) with every step on device; one host sync at the end
+    (echr_decoder_beam).  Each event's beam_size slots are rows of one decode over N * beam_size event-major rows: event, ev_start,
+    ev_len and h0 are repeated per slot (the clip rows and their attention projection stay shared).  Per step the beam_size largest
+    s_j + logp_j[v] over the alive slots win (ties to the smaller slot, then the smaller token); <eos> or the last step finishes a
+    hypothesis, and an event keeps the finished one with the greatest score.  No length penalty.
+
+    Returns (seq int64 [N,T], logp fp32 [N,T], score fp32 [N]): T = the longest result's word count, seq its words then zeros, logp
+    its token log-probs with the <eos> one at each row's word count (when inside T) then zeros, score the sum of its log-probs (<eos>
+    included).  seq and logp are [] when T == 0.  beam_size = 1 gives the greedy decode's seq up to each row's first <eos>."""
+    lib = L.load()
+    video, event, c3d = _f32c(video), _f32c(event), _f32c(c3d)
+    ps = [_f32c(p) for p in params]
+    B = int(beam_size)
+    V1 = ps[0].shape[0]
+    if not 1 <= B <= min(BEAM_MAX, V1):
+        raise ValueError('beam_size must be in [1, %d] (and <= the vocabulary size + 1), got %d' % (min(BEAM_MAX, V1), B))
+    N = event.shape[0]
+    dev = event.device
+    rep = lambda x: x.repeat_interleave(B, dim=0).contiguous()          # event-major: row n*B + j is slot j of event n
+    ev_start_r = rep(ev_start.to(torch.int32))
+    ev_len_r = rep(ev_len.to(torch.int32))
+    h0_r = rep(_f32c(h0)) if h0 is not None else None
+    a = _dec_args(ps, c3d, ev_start_r, ev_len_r, rep(event), video, None, A, seq_length, None, None, h0=h0_r)
+    ws = torch.empty(lib.echr_decoder_ws_floats(C.byref(a)), device=dev, dtype=torch.float32)
+    a.ws = L.ptr(ws)
+    seq = torch.empty(N, seq_length, device=dev, dtype=torch.int64)
+    slp = torch.empty(N, seq_length, device=dev, dtype=torch.float32)
+    score = torch.empty(N, device=dev, dtype=torch.float32)
+    words = torch.empty(N + 1, device=dev, dtype=torch.int32)
+    ba = L.BeamArgs(a, B, seq_length, L.ptr(seq, torch.int64), L.ptr(slp), L.ptr(score), L.ptr(words, torch.int32), None)
+    wsb = torch.empty(lib.echr_beam_ws_floats(C.byref(ba)), device=dev, dtype=torch.float32)
+    ba.ws_beam = L.ptr(wsb)
+    L.check(lib.echr_decoder_beam(C.byref(ba), L.stream_ptr()), 'decoder_beam')
+    T = int(words[N].item())                   # the only device->host sync of the whole decode
+    L.check(lib.echr_check_async(), 'decoder_beam')
+    if T == 0:
+        return [], [], score
+    return seq[:, :T].contiguous(), slp[:, :T].contiguous(), score
+
+
 def decoder_step(it, video, event, c3d, ev_start, ev_len, A, state, params, drop=None):
     """OldModel.get_logprobs_state (OldModel_NEW.py:133-137): ONE timestep, state in / state out.
 

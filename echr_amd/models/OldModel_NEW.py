@@ -224,12 +224,28 @@ class OldModel(nn.Module):
             return EF.decoder_step(it, video, event, cv.feats, cv.ev_start, cv.ev_len, cv.max_len, state, self.native_params(), drop)
 
     def sample(self, video, event, clip, clip_mask, opt={}):
-        """Decoding without beam search (OldModel_NEW.py:139-187, beam_size = 1): greedy arg-max (sample_max = 1, the recipe's setting) or,
-        with sample_max = 0, a draw from softmax(logp / temperature) per step (:160-168).  The draws come from the library's
-        counter-based Philox stream (seed: set_dropout_state / torch.initial_seed, advanced once per call), not from
-        torch.multinomial's generator: same distribution, different random numbers."""
-        if opt.get('beam_size', 1) != 1:
-            raise NotImplementedError('beam search (beam_size > 1) is not on the HIP path')
+        """OldModel.sample (OldModel_NEW.py:139-187).  beam_size = 1: greedy arg-max (sample_max = 1, the recipe's setting) or, with
+        sample_max = 0, a draw from softmax(logp / temperature) per step (:160-168).  The draws come from the library's counter-based
+        Philox stream (seed: set_dropout_state / torch.initial_seed, advanced once per call), not from torch.multinomial's generator: same
+        distribution, different random numbers.
+
+        beam_size = B > 1 (the reference's `--beam_size`, whose beam branch is commented out there): beam search on device
+        (functional.beam_search), eval mode and sample_max = 1 only.  Returns (seq, logp) like the greedy decode; logp is 0 after a row's
+        <eos> where the greedy decode keeps the raw arg-max log-probs.  opt['return_score'] = True appends score [N], the sum of each
+        result's token log-probs (<eos> included)."""
+        beam = int(opt.get('beam_size', 1))
+        if beam != 1:
+            if not 1 <= beam <= min(EF.BEAM_MAX, self.vocab_size + 1):
+                raise ValueError('beam_size must be in [1, %d], got %d' % (min(EF.BEAM_MAX, self.vocab_size + 1), beam))
+            if opt.get('sample_max', 1) != 1:
+                raise ValueError('beam search decodes by score: it does not combine with sample_max = 0')
+            if self.training:
+                raise ValueError('beam search is an evaluation decode: call eval() first')
+            cv = self._clip_view(clip, clip_mask)
+            with torch.no_grad():
+                seq, logp, score = EF.beam_search(video, event, cv.feats, cv.ev_start, cv.ev_len, cv.max_len, self.seq_length,
+                                                  self.native_params(), beam, h0=self._initial_state(video, event, cv))
+            return (seq, logp, score) if opt.get('return_score', False) else (seq, logp)
         cv = self._clip_view(clip, clip_mask)
         multinomial = opt.get('sample_max', 1) != 1
         seed = self._sample_seed() if multinomial else 0

@@ -383,6 +383,28 @@ int echr_decoder_sample(const echr_sample_args* a, void* stream);
  * the launch-per-step chain (the persistent decoder has neither draws nor dropout); its own ws / ws_sample, like echr_decoder_sample. */
 int echr_decoder_sample_train(const echr_sample_args* a, const echr_dropout* drop, void* stream);
 
+/* Beam search (OldModel.sample with opt beam_size = B, 1 <= B <= min(16, V1)): seq_len decision steps on device without host syncs,
+ * eval mode, every event independently.  Per step: candidates s_j + logp_j[v] (fp32 log-softmax, no length penalty) over the event's
+ * alive slots j and every token v; the B largest win, ties to the smaller j then the smaller v; new slot k is the k-th winner and
+ * continues its parent's LSTM state.  A winner with v == 0 (<eos>), or any winner at the last step, finishes; the event's result is
+ * replaced only by a finished hypothesis with a strictly greater score (slot order within a step).  B = 1 is the greedy decode up to
+ * each row's first <eos>.  Bitwise reproducible. */
+typedef struct {
+    echr_dec_args dec;       /* N = events * beam_size rows, event-major (slot j of event n is row n*B + j): event, ev_start, ev_len and
+                                h0 repeated B times per event; rows_disjoint 0; S, tokens, logp unused; ws from echr_decoder_ws_floats
+                                with S = seq_len */
+    int32_t beam_size;
+    int32_t seq_len;
+    int64_t* seq;            /* out [N/B, seq_len]: the result's words, then zeros */
+    float* seq_logp;         /* out [N/B, seq_len]: its token log-probs, <eos> included (at position words[n] < seq_len), then zeros */
+    float* score;            /* out [N/B]: the sum of its token log-probs, <eos> included */
+    int32_t* words;          /* out [N/B + 1]: words per event (seq_len when it never emitted <eos>), then their maximum (the host's one
+                                read: the output width) */
+    float* ws_beam;          /* echr_beam_ws_floats */
+} echr_beam_args;
+int64_t echr_beam_ws_floats(const echr_beam_args* a);
+int echr_decoder_beam(const echr_beam_args* a, void* stream);
+
 /* Self-critical training on gathered log-probs (the module path; the one-call path is echr_train_step_rw).
  * echr_gather_tokens_fwd: out [N,T] = logp [N,S,V1] at (n, t, seq[n,t]), t < T <= S; _bwd writes g_logp [N,S,V1] in full (zero but there).
  * echr_reward_loss_fwd: RewardCriterion (misc/utils.py:48-59), mask[n,0] = 1, mask[n,t] = (seq[n,t-1] > 0):
