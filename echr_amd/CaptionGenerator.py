@@ -26,9 +26,18 @@ class CaptionGenerator(nn.Module):
             self.fusion_model = models.setup_fusion(opt)
         self.lm_model = models.setup_lm(opt)
         self.overlap_encoder = os.environ.get('ECHR_OVERLAP_ENCODER', '1') != '0'        # 'train' mode: run the decoder's event-independent precompute concurrently with the event encoder
-        if not any(k in opt.video_context_type for k in ('VL', 'VC', 'VH')) or opt.event_context_type not in ('ER1', 'ER2', 'ER3') or opt.clip_context_type != 'CC':
+        if not any(k in opt.video_context_type for k in ('VL', 'VC', 'VH')) or opt.event_context_type not in ('ER1', 'ER2', 'ER3') or not self.clip_parts():
             raise NotImplementedError('the HIP path implements the ECHR recipe: video_context_type from VL / VC / VH (any combination), '
-                                      'event_context_type ER1 / ER2 / ER3, clip_context_type=CC (experiments/train_ECHR.sh)')
+                                      'event_context_type ER1 / ER2 / ER3, clip_context_type CC / CH / CC+CH (experiments/train_ECHR.sh, opts.py:130)')
+        if self.clip_parts() & 2 and 'C' in opt.CG_init_feats_type:
+            raise NotImplementedError("clip_context_type with 'CH' and a CG_init_feats_type that reads the clip: the initial state's clip mean has "
+                                      "no gradient into tap_feats on the HIP path")
+
+    def clip_parts(self):
+        """Frame-level context rows as the reference tests them (`in`, CaptionGenerator.py:140-167): 1 = 'CC' (C3D rows), 2 = 'CH' (the
+        proposal encoder's states), 3 = both, C3D first ('CC+CH', also spelt 'CCCH'); 0 = neither."""
+        ct = self.opt.clip_context_type
+        return (1 if 'CC' in ct else 0) | (2 if 'CH' in ct else 0)
 
     def _require_live_decoder(self):
         if type(self.lm_model).__name__ != 'ThreestreamModel':
@@ -143,10 +152,23 @@ class CaptionGenerator(nn.Module):
         return self.fusion_model(ech, soi_select_list, ev_tensors=(ev_start, ev_len), drop=_drop)
 
     def get_clip_context(self, tap_feats, c3d_feats, lda_feats, ind_select_list, soi_select_list, _ev=None):
-        """'CC' frame-level context.  Internal callers get a zero-copy ClipView (+ None mask); external callers
-        (no `_ev`) get the reference's padded [N,A,D] tensor and [N,A] mask (CaptionGenerator.py:140-167)."""
+        """Frame-level context over the rows of 'CC' (c3d_feats), 'CH' (tap_feats) or 'CC+CH' ([c3d | tap] on the feature axis).  Internal
+        callers get a zero-copy ClipView (+ None mask) whose rows' tap columns receive their gradient through the decoder's backward
+        (echr_decoder_row_grad); external callers (no `_ev`) get the reference's padded [N,A,D] tensor and [N,A] mask (CaptionGenerator.py:140-167)."""
+        parts = self.clip_parts()
         if _ev is not None:
             ev_start, ev_len, _, A = _ev
-            return ClipView(c3d_feats, ev_start, ev_len, A, EF.rows_disjoint(soi_select_list)), None
-        ev_start, ev_len, _, A = EF.event_index_tensors(soi_select_list, ind_select_list, c3d_feats.device)
-        return ClipView(c3d_feats, ev_start, ev_len, A).materialize()
+            if parts == 1:
+                return ClipView(c3d_feats, ev_start, ev_len, A, EF.rows_disjoint(soi_select_list)), None
+            rows = tap_feats if parts == 2 else EF.clip_rows(c3d_feats, tap_feats)
+            col0 = 0 if parts == 2 else c3d_feats.shape[1]
+            return ClipView(rows, ev_start, ev_len, A, EF.rows_disjoint(soi_select_list), grad_src=tap_feats, grad_col0=col0), None
+        if parts == 1:
+            rows = c3d_feats
+        elif parts == 2:
+            rows = tap_feats
+        else:
+            T = min(c3d_feats.shape[0], tap_feats.shape[0])
+            rows = torch.cat([c3d_feats[:T], tap_feats[:T]], 1)
+        ev_start, ev_len, _, A = EF.event_index_tensors(soi_select_list, ind_select_list, rows.device)
+        return ClipView(rows, ev_start, ev_len, A).materialize()

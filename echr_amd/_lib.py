@@ -93,6 +93,10 @@ class BeamArgs(C.Structure):
                 ('ws_beam', c_f)]
 
 
+class RowGradArgs(C.Structure):
+    _fields_ = [('col0', i32), ('ncols', i32), ('out', c_f), ('ld', i64), ('ws', c_f)]
+
+
 HANDOVER_FN = C.CFUNCTYPE(None, i32, C.c_void_p, C.c_void_p)          # echr_handover_fn
 MID_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p)                    # echr_mid_fn
 
@@ -109,6 +113,10 @@ class TrainStepArgs(C.Structure):
                 ('event_parts', i32), ('w_init', c_f), ('b_init', c_f), ('g_w_init', c_f), ('g_b_init', c_f),
                 ('init_use_v', i32), ('init_use_e', i32), ('init_use_c', i32), ('vh_offset', i32), ('tap_rows', i32),
                 ('mid_cb', C.c_void_p), ('mid_user', C.c_void_p)]
+
+
+class ClipStepArgs(C.Structure):
+    _fields_ = [('clip_parts', i32), ('Dc', i32), ('c3d', c_f), ('rw', i32), ('weight', c_f)]
 
 
 # every symbol include/echr_hip.h declares: (name, restype, argtypes)
@@ -152,6 +160,9 @@ SYMBOLS = [
     ('echr_reward_loss_bwd', i32, [c_f, c_f, c_f, c_f, c_f, i32, i32, C.c_void_p]),
     ('echr_config_set', i32, [C.c_char_p, i32]),
     ('echr_stream_join', i32, [C.c_void_p]),
+    ('echr_decoder_row_grad_ws_floats', i64, [C.POINTER(DecArgs), i32]),
+    ('echr_decoder_row_grad', i32, [C.POINTER(DecArgs), C.POINTER(DecGrads), C.POINTER(RowGradArgs), C.c_void_p]),
+    ('echr_clip_rows', i32, [c_f, i32, c_f, i32, c_f, i32, C.c_void_p]),
     ('echr_streams_init', i32, []),
     ('echr_decoder_step', i32, [C.POINTER(DecArgs), c_f, c_f, c_f, c_f, C.POINTER(Dropout), C.c_void_p]),
     ('echr_tsrm_attn_fwd', i32, [C.POINTER(TsrmArgs), c_f, c_f, C.POINTER(Dropout), C.c_void_p]),
@@ -178,6 +189,8 @@ SYMBOLS = [
     ('echr_train_step_prepare', i32, [C.POINTER(TrainStepArgs), C.c_void_p]),
     ('echr_train_step_rw_ws_floats', i64, [C.POINTER(TrainStepArgs)]),
     ('echr_train_step_rw', i32, [C.POINTER(TrainStepArgs), c_f, C.c_void_p]),
+    ('echr_train_step_clip_ws_floats', i64, [C.POINTER(TrainStepArgs), C.POINTER(ClipStepArgs)]),
+    ('echr_train_step_clip', i32, [C.POINTER(TrainStepArgs), C.POINTER(ClipStepArgs), C.c_void_p]),
     ('echr_handover_wait', i32, [i32, C.c_void_p]),
     ('echr_clamp', i32, [c_f, i64, f32, C.c_void_p]),
     ('echr_clamp_adam', i32, [c_f, c_f, c_f, c_f, i64, i32, C.c_double, C.c_double, C.c_double, C.c_double, f32, C.c_void_p]),
@@ -187,7 +200,7 @@ SYMBOLS = [
 ABI_STRUCTS = {'echr_gemm_desc': GemmDesc, 'echr_dropout': Dropout, 'echr_tsrm_args': TsrmArgs, 'echr_tsrm_grads': TsrmGrads,
                'echr_dec_args': DecArgs, 'echr_dec_grads': DecGrads, 'echr_sample_args': SampleArgs, 'echr_sst_args': SstArgs,
                'echr_sst_grads': SstGrads, 'echr_train_step_args': TrainStepArgs, 'echr_init_state_args': InitStateArgs, 'echr_init_state_grads': InitStateGrads,
-               'echr_beam_args': BeamArgs}
+               'echr_beam_args': BeamArgs, 'echr_row_grad_args': RowGradArgs, 'echr_clip_step_args': ClipStepArgs}
 
 ABI_VERSION = 3          # include/echr_hip.h ECHR_ABI_VERSION
 _lib = None

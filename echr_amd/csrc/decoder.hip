@@ -999,6 +999,14 @@ static int check_dims(const echr_dec_args* a, const char* who) {
     ECHR_REQUIRE(a->H % 4 == 0 && a->E % 4 == 0, "%s: need H%%4==0 and E%%4==0 (H=%d E=%d)", who, a->H, a->E);
     return 0;
 }
+int check_dims_public(const echr_dec_args* a, const char* who) { return check_dims(a, who); }
+// what the clip-row gradient (clipctx.hip) reads from a finished echr_decoder_bwd / echr_decoder_fwd on the same workspaces
+void decoder_bwd_views(const echr_dec_args* a, const echr_dec_grads* g, const float** dg1, const float** dpall) {
+    const DecWsBwd b = carve_ws_bwd(a, g->ws_bwd);
+    *dg1 = b.DG[1];
+    *dpall = b.DPALL;
+}
+const float* decoder_fwd_wt(const echr_dec_args* a) { return carve_ws(a, a->ws).WT; }
 
 #define RC(x) do { int _rc = (x); if (_rc) return _rc; } while (0)
 

@@ -33,7 +33,7 @@ bool deterministic_gemm();
 inline bool det_mode() { return config().deterministic != 0; }
 // scratch slabs of the fixed-order variants: one lazily grown device buffer per use (`kind`), owned by the library, never shrunk; the call
 // that grows one synchronises the device (hipFree / hipMalloc).  One calling thread, like the rest of the library's static state.
-enum { DET_DQ = 0, DET_DPALL = 1, DET_ALPHA = 2, DET_REC = 3, DET_KINDS = 4 };
+enum { DET_DQ = 0, DET_DPALL = 1, DET_ALPHA = 2, DET_REC = 3, DET_ROWG = 4, DET_KINDS = 5 };
 float* det_scratch(int kind, size_t floats);
 
 // persistent (one launch for all timesteps) recurrence of the decoder, csrc/persist.hip
@@ -108,6 +108,12 @@ int decoder_bwd_parts(const echr_dec_args* a, const echr_dec_grads* g, const ech
 int decoder_bwd_checked(const echr_dec_args* a, const echr_dec_grads* g, const echr_dropout* drop, void* stream, const float* rw);
 void handover_close();                   // stop recording; the recorded events stay valid for echr_handover_wait
 void handover_request(bool on, echr_handover_fn cb = nullptr, void* user = nullptr);          // the next decoder backward records the data-parallel hand-over events (decoder.hip)
+// clip contexts 'CH' / 'CC+CH' (clipctx.hip): the decoder backward's d gates1 and d P_all, the forward's attention weights WT [S,N,A]
+void decoder_bwd_views(const echr_dec_args* a, const echr_dec_grads* g, const float** dg1, const float** dpall);
+const float* decoder_fwd_wt(const echr_dec_args* a);
+int check_dims_public(const echr_dec_args* a, const char* who);
+int row_grad(const echr_dec_args* a, const echr_dec_grads* g, const echr_row_grad_args* r, hipStream_t st);
+int clip_rows(const float* c3d, int Dc, const float* tap, int Ht, float* rows, int Tv, hipStream_t st);
 int join_tail(hipStream_t st);          // make st wait for an asynchronous decoder-backward tail (decoder.hip); no-op when none is pending
 int persist_read_stamps(unsigned long long* dst, int max_entries);
 unsigned long long* persist_stamp_buffer(int S, hipStream_t st);      // diagnostic: [4][S <= 256][16] stamps, zeroed on st (nullptr: unavailable)

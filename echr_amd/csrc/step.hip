@@ -22,14 +22,16 @@ static int async_level() {
     return lv;
 }
 
-struct StepWs { long idx, ech, tsrm_ws, event, logp, dec_ws, dec_ws_bwd, g_event, g_ech, tsrm_ws_bwd, h0, g_h0, init_feats, init_dfeats, g_video, g_video_init, total; };
+struct StepWs { long idx, ech, tsrm_ws, event, logp, dec_ws, dec_ws_bwd, g_event, g_ech, tsrm_ws_bwd, h0, g_h0, init_feats, init_dfeats, g_video, g_video_init,
+                 rows, row_grad, total; };
 
 static inline int init_feats_width(const echr_train_step_args* a) {
     return (a->init_use_v ? a->dec.Dv : 0) + (a->init_use_e ? a->dec.De : 0) + (a->init_use_c ? a->dec.D : 0);
 }
 
 // rw: echr_train_step_rw -- the index region holds the criterion weights [N,S] too (host_nll = 1)
-static StepWs carve_step(const echr_train_step_args* a, bool rw = false) {
+// x: echr_train_step_clip -- the 'CC+CH' row source [Tv, Dc + Ht] and the clip-row gradient's scratch
+static StepWs carve_step(const echr_train_step_args* a, bool rw = false, const echr_clip_step_args* x = nullptr) {
     StepWs w;
     long off = 0;
     auto take = [&](long n) { long o = off; off += up64(n); return o; };
@@ -53,6 +55,11 @@ static StepWs carve_step(const echr_train_step_args* a, bool rw = false) {
         w.h0 = take((long)d.N * h3); w.g_h0 = take((long)d.N * h3); w.init_feats = take((long)d.N * dt); w.init_dfeats = take((long)d.N * dt);
     }
     w.g_video = take(d.Dv); w.g_video_init = take(d.Dv);
+    w.rows = w.row_grad = -1;
+    if (x) {
+        if (x->clip_parts == 3) w.rows = take((long)d.Tv * d.D);
+        w.row_grad = take(echr_decoder_row_grad_ws_floats(&d, a->Ht > 0 ? a->Ht : 1));
+    }
     w.total = off;
     return w;
 }
@@ -238,8 +245,25 @@ extern "C" int echr_train_step_prepare(const echr_train_step_args* a, void* stre
     return rc;
 }
 
-static int train_step_impl(const echr_train_step_args* a, void* stream, bool rw, const float* rw_dev);
+static int train_step_impl(const echr_train_step_args* a, void* stream, bool rw, const float* rw_dev, const echr_clip_step_args* x = nullptr);
 extern "C" int echr_train_step(const echr_train_step_args* a, void* stream) { return train_step_impl(a, stream, false, nullptr); }
+// Frame-level context 'CH' / 'CC+CH' (include/echr_hip.h): the same iteration with tap_feats (or [c3d | tap]) as the attended rows and the
+// clip-row gradient added to g_tap behind the join of the backward's helper streams
+extern "C" int64_t echr_train_step_clip_ws_floats(const echr_train_step_args* a, const echr_clip_step_args* x) {
+    return (a && x) ? carve_step(a, x->rw != 0, x).total : -1;
+}
+extern "C" int echr_train_step_clip(const echr_train_step_args* a, const echr_clip_step_args* x, void* stream) {
+    ECHR_REQUIRE(a && x && (x->clip_parts == 2 || x->clip_parts == 3), "train_step_clip: clip_parts must be 2 ('CH') or 3 ('CC+CH')");
+    ECHR_REQUIRE(x->c3d && x->Dc > 0 && a->tap && a->Ht > 0, "train_step_clip: c3d / tap missing");
+    ECHR_REQUIRE(a->dec.D == (x->clip_parts == 3 ? x->Dc + a->Ht : a->Ht), "train_step_clip: dec.D = %d is not the width of the clip rows", a->dec.D);
+    ECHR_REQUIRE(!a->prepared, "train_step_clip: the clip rows are tap_feats: echr_train_step_prepare cannot run ahead of them (prepared must be 0)");
+    ECHR_REQUIRE(!(a->w_init && a->init_use_c), "train_step_clip: an initial state that reads the clip has no row gradient");
+    if (x->rw) {
+        ECHR_REQUIRE(a->host_nll || x->weight, "train_step_clip: the criterion weights are missing (device `weight`, or host_index with host_nll = 1)");
+        ECHR_REQUIRE(!(a->host_nll && x->weight), "train_step_clip: host_nll = 1 carries the weights in host_index: pass weight = NULL");
+    }
+    return train_step_impl(a, stream, x->rw != 0, (x->rw && !a->host_nll) ? x->weight : nullptr, x);
+}
 extern "C" int64_t echr_train_step_rw_ws_floats(const echr_train_step_args* a) { return a ? carve_step(a, true).total : -1; }
 // Self-critical training (RewardCriterion, misc/utils.py:48-59): the same iteration with the criterion's numerator weighted by the signed
 // rw[n,t] = reward * mask.  Stage-ahead needs no extra guard here: the decodes a caller runs between two calls (the sampled and the greedy pass,
@@ -252,12 +276,14 @@ extern "C" int echr_train_step_rw(const echr_train_step_args* a, const float* we
     ECHR_REQUIRE(!a->prepared, "train_step_rw: echr_train_step_prepare does not take the weights (prepared must be 0)");
     return train_step_impl(a, stream, true, a->host_nll ? nullptr : weight);
 }
-static int train_step_impl(const echr_train_step_args* a, void* stream, bool rw, const float* rw_dev) {
+static int train_step_impl(const echr_train_step_args* a, void* stream, bool rw, const float* rw_dev, const echr_clip_step_args* x) {
     ECHR_REQUIRE(a && a->ws && a->host_index && a->loss && a->g_loss && a->flat_g && (a->tap || a->event_parts == 1), "train_step: missing buffers");
     ECHR_REQUIRE(!a->prepared || a->overlap_encoder, "train_step: prepared = 1 needs overlap_encoder = 1");
     const int parts = a->event_parts ? a->event_parts : 3;
     ECHR_REQUIRE(parts >= 1 && parts <= 3, "train_step: event_parts must be 0..3");
-    const int De_c3d = (parts & 1) ? a->dec.D : 0, De_tap = (parts & 2) ? a->Ht : 0;          // the two halves of the event encoder's input rows
+    const int Dc = x ? x->Dc : a->dec.D;          // (the C3D features' width: the row source's one with 'CC')
+    const float* c3d = x ? x->c3d : a->dec.c3d;
+    const int De_c3d = (parts & 1) ? Dc : 0, De_tap = (parts & 2) ? a->Ht : 0;          // the two halves of the event encoder's input rows
     ECHR_REQUIRE(a->tsrm.N == a->dec.N && a->tsrm.Do == a->dec.De && a->tsrm.Din == De_c3d + De_tap, "train_step: encoder / decoder shapes disagree");
     const bool vh = a->g_tap && a->vh_offset >= 0;
     ECHR_REQUIRE(!vh || (a->vh_offset + a->Ht <= a->dec.Dv && a->tap_rows > 0), "train_step: vh_offset / tap_rows do not describe a span of dec.video");
@@ -265,10 +291,12 @@ static int train_step_impl(const echr_train_step_args* a, void* stream, bool rw,
     ECHR_REQUIRE(!a->do_step || (a->flat_p && a->adam_m && a->adam_v && a->adam_step >= 1), "train_step: optimiser state missing");
     hipStream_t st = (hipStream_t)stream;
     RC(join_tail(st));          // (a deferred update of the previous call: it reads the index region this call is about to restage)
-    const StepWs L = carve_step(a, rw);
+    const StepWs L = carve_step(a, rw, x);
     ECHR_REQUIRE(a->ws_floats >= L.total, "train_step: workspace holds %lld floats, %ld needed (echr_train_step%s_ws_floats)", (long long)a->ws_floats, L.total,
-                 rw ? "_rw" : "");
+                 x ? "_clip" : (rw ? "_rw" : ""));
     float* ws = a->ws;
+    // 'CC+CH': the row source [c3d | tap] is formed first, ahead of every fork of this call (the decoder's event-independent part reads it)
+    if (x && x->clip_parts == 3) RC(clip_rows(c3d, Dc, a->tap, a->Ht, ws + L.rows, a->dec.Tv, st));
     const int N = a->dec.N, S = a->dec.S;
     step_mark(0, st);
     int32_t* idx = reinterpret_cast<int32_t*>(ws + L.idx);
@@ -303,6 +331,7 @@ static int train_step_impl(const echr_train_step_args* a, void* stream, bool rw,
     ECHR_REQUIRE(nll_target && nll_mask, "train_step: criterion targets / mask missing");
 
     echr_dec_args d = step_dec_args(a, L, idx);
+    if (x) d.c3d = x->clip_parts == 3 ? ws + L.rows : a->tap;
     echr_tsrm_args t = a->tsrm;
     t.ech = ws + L.ech; t.ev_start = ev_start; t.ev_len = ev_len; t.ws = ws + L.tsrm_ws; t.out = ws + L.event;
     t.inference = 0; t.max_len = 0; t.max_span = 0;
@@ -324,7 +353,7 @@ static int train_step_impl(const echr_train_step_args* a, void* stream, bool rw,
             return rc2;
         }
     }
-    int rc = echr_event_pool_gather_fwd(a->dec.c3d, a->tap, ev_start, ev_len, ind, ws + L.ech, N, De_c3d, De_tap, stream);       // :106-128
+    int rc = echr_event_pool_gather_fwd(c3d, a->tap, ev_start, ev_len, ind, ws + L.ech, N, De_c3d, De_tap, stream);       // :106-128
     if (!rc) rc = echr_tsrm_fwd(&t, &a->drop, stream);                                                                       // :129
     if (rc) { (void)tsrm_position_early(nullptr, nullptr); if (a->overlap_encoder) (void)echr_decoder_fwd_prepare_cancel(stream); return rc; }
     d.event = ws + L.event; d.prepared = a->overlap_encoder ? 1 : 0;
@@ -334,7 +363,7 @@ static int train_step_impl(const echr_train_step_args* a, void* stream, bool rw,
     if (a->w_init) {
         ia.N = N; ia.Dv = a->dec.Dv; ia.De = a->dec.De; ia.D = a->dec.D; ia.H3 = 3 * a->dec.H;
         ia.use_v = a->init_use_v; ia.use_e = a->init_use_e; ia.use_c = a->init_use_c; ia.A = a->dec.A;
-        ia.video = a->dec.video; ia.event = ws + L.event; ia.c3d = a->dec.c3d; ia.ev_start = ev_start; ia.ev_len = ev_len;
+        ia.video = a->dec.video; ia.event = ws + L.event; ia.c3d = d.c3d; ia.ev_start = ev_start; ia.ev_len = ev_len;
         ia.w = a->w_init; ia.b = a->b_init; ia.feats = ws + L.init_feats; ia.h0 = ws + L.h0;
         rc = echr_init_state_fwd(&ia, stream);
         if (rc) { if (a->overlap_encoder) (void)echr_decoder_fwd_prepare_cancel(stream); return rc; }
@@ -368,7 +397,7 @@ static int train_step_impl(const echr_train_step_args* a, void* stream, bool rw,
     // backward (train.py:313): criterion gradient in fused form
     g.zero_extra = nullptr; g.zero_extra_count = 0;
     handover_request(false);          // (hand-over points of an earlier call are void from here on)
-    if (a->defer_update && a->g_tap && a->do_step && g.async_tail == 2 && fused_nll && config().gemm_h2 && helpers_available() && !vh && !a->w_init) {
+    if (a->defer_update && a->g_tap && a->do_step && g.async_tail == 2 && fused_nll && config().gemm_h2 && helpers_available() && !vh && !a->w_init && !x) {
         // Joint 'tap_cg' iteration (train.py:300-313): the proposal encoder's backward -- a 64-workgroup persistent launch that leaves three
         // quarters of the chip idle -- waits for d tap_feats alone.  The chain that leads to it (late fusion, reverse recurrence, d event,
         // the event encoder's attention backward, d ech) runs first and alone on the caller's stream; every parameter gradient and the
@@ -415,6 +444,12 @@ static int train_step_impl(const echr_train_step_args* a, void* stream, bool rw,
     if (fused_nll) RC(decoder_fused_loss(&d, &g, a->loss, st, crit_w != nullptr));
     step_mark(3, st);
     RC(echr_stream_join(stream));          // the decoder backward's asynchronous tail: every gradient is final in `stream` order now
+    if (x && a->g_tap) {
+        // 'CH' / 'CC+CH': d tap_feats gains the attended rows' gradient (the tap columns of the row source), from what the backward left
+        echr_row_grad_args r;
+        r.col0 = x->clip_parts == 3 ? Dc : 0; r.ncols = a->Ht; r.out = a->g_tap; r.ld = a->Ht; r.ws = ws + L.row_grad;
+        RC(row_grad(&d, &g, &r, st));
+    }
     if (vh) {
         // scene context 'VH' = tap.mean(0) (CaptionGenerator.py:95-99): d tap[r, :] += d video[vh span] / rows, for the decoder's d video (final
         // behind the join: it is formed in the LSTM-layer stage on a helper stream) and init_linear's

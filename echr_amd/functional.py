@@ -336,9 +336,11 @@ class DecoderFunction(torch.autograd.Function):
     """OldModel.forward with the ThreeStream core (OldModel_NEW.py:98-137, :376-401, :801-823): log-probs [N,S,V1]."""
 
     @staticmethod
-    def forward(ctx, video, event, c3d, ev_start, ev_len, tokens, A, disjoint, drop, sink, prep, h0, *params):
+    def forward(ctx, video, event, c3d, ev_start, ev_len, tokens, A, disjoint, drop, sink, prep, h0, tap=None, col0=0, *params):
+        # tap / col0 ('CH', 'CC+CH'): the rows c3d[:, col0 : col0 + tap width] are tap[:Tv]; backward returns d tap (echr_decoder_row_grad)
         lib = L.load()
         ctx.sink = sink
+        ctx.tap_meta = (tuple(tap.shape), int(col0)) if tap is not None else None
         event = _f32c(event)
         h0 = _f32c(h0) if h0 is not None else None          # [N, 3H] initial state (OldModel.init_hidden, CG_init_feats_type); None = zeros
         S, N = tokens.shape
@@ -392,6 +394,7 @@ class DecoderFunction(torch.autograd.Function):
         g_video = torch.empty_like(video) if ctx.needs_input_grad[0] else None
         h0 = ctx.h0
         g_h0 = torch.empty_like(h0) if (h0 is not None and ctx.needs_input_grad[11]) else None
+        want_tap = ctx.tap_meta is not None and ctx.needs_input_grad[12]
         a = _dec_args(ps, c3d, ev_start, ev_len, event, video, tokens, A, S, ws, logp, disjoint, train=train, h0=h0)
         wsb = torch.empty(lib.echr_decoder_ws_bwd_floats(C.byref(a)), device=event.device, dtype=torch.float32)
         gp = [L.ptr(x) for x in grads]
@@ -432,7 +435,7 @@ class DecoderFunction(torch.autograd.Function):
                 # data parallel, one-call form: the LSTM-layer gradients (and everything else part A of the backward produced) are final in
                 # stream order now; the reducer starts their all-reduce, which overlaps the asynchronous tail and the event encoder's backward
                 hook(list(ctx.sink.params[3:15]), after_recurrence=True)
-            if g.async_tail:
+            if g.async_tail and not want_tap:
                 keep = [ws, wsb, logp, c3d, tokens, ev_start, ev_len, g_logp, fused]
                 sp = L.stream_ptr()
 
@@ -440,7 +443,26 @@ class DecoderFunction(torch.autograd.Function):
                     L.check(lib.echr_stream_join(sp), 'stream_join')
                     del keep[:]
                 torch.autograd.Variable._execution_engine.queue_callback(_join)
-        return (g_video, g_event, None, None, None, None, None, None, None, None, None, g_h0) + tuple(grads)
+        g_tap = None
+        if want_tap:
+            # d rows of the tap columns (echr_decoder_row_grad): orders the asynchronous tail, whose d P_all it reads, on this stream first --
+            # every workspace read of that tail then precedes this return in stream order
+            (T, Ht), col0 = ctx.tap_meta
+            g_tap = torch.zeros(T, Ht, device=event.device, dtype=torch.float32)
+            rws = torch.empty(lib.echr_decoder_row_grad_ws_floats(C.byref(a), Ht), device=event.device, dtype=torch.float32)
+            r = L.RowGradArgs(col0, Ht, L.ptr(g_tap), Ht, L.ptr(rws))
+            L.check(lib.echr_decoder_row_grad(C.byref(a), C.byref(g), C.byref(r), L.stream_ptr()), 'decoder_row_grad')
+        return (g_video, g_event, None, None, None, None, None, None, None, None, None, g_h0, g_tap, None) + tuple(grads)
+
+
+def clip_rows(c3d, tap):
+    """The 'CC+CH' row source [T, Dc + Ht] = [c3d | tap] over T = min(rows) (echr_clip_rows; no graph: the decoder's backward returns the
+    tap columns' gradient itself)."""
+    c3d, tap = _f32c(c3d.detach()), _f32c(tap.detach())
+    T = min(c3d.shape[0], tap.shape[0])
+    rows = torch.empty(T, c3d.shape[1] + tap.shape[1], device=tap.device, dtype=torch.float32)
+    L.check(L.load().echr_clip_rows(L.ptr(c3d), c3d.shape[1], L.ptr(tap), tap.shape[1], L.ptr(rows), T, L.stream_ptr()), 'clip_rows')
+    return rows
 
 
 def greedy_sample(video, event, c3d, ev_start, ev_len, A, seq_length, params, debug=None, multinomial=False, temperature=1.0, seed=0,

@@ -47,6 +47,11 @@ class FusedTrainStep(object):
             L.check(self.lib.echr_streams_init(), 'streams_init')
         self.dev = arena.flat_p.device
         self.a = L.TrainStepArgs()
+        # frame-level context (CaptionGenerator.clip_parts): 1 = 'CC'; 2 = 'CH' / 3 = 'CC+CH' run through echr_train_step_clip, whose extension
+        # struct carries the C3D features (the decoder's row source is then tap_feats, or [c3d | tap] formed in the library's workspace)
+        self.clip = model.clip_parts()
+        self._dc = model.opt.video_dim
+        self.x = L.ClipStepArgs(self.clip, self._dc, None, 0, None)
         self.ws = None
         self.one = torch.ones(1, device=self.dev, dtype=torch.float32)
         self.loss_ring = torch.zeros(self.LOSS_SLOTS, 2, device=self.dev, dtype=torch.float32)
@@ -118,6 +123,9 @@ class FusedTrainStep(object):
         """Joint 'tap_cg' iteration (train.py:300-313), optional first half: everything of the iteration that does not read tap_feats (index
         staging, the decoder's event-independent part, the gradient-arena fill) starts on the library's prepare stream and runs beside the
         proposal encoder's forward queued next.  Follow with `self(tap_feats, <the same arguments>, prepared=True, ...)`."""
+        if self.clip != 1:
+            raise NotImplementedError("clip_context_type with 'CH': the attended rows are tap_feats and their attention projection is part of the "
+                                      "event-independent half, prepare() runs ahead of them (call without prepare(); JointTrainStep(early_prepare=False))")
         self._setup(None, c3d_feats, lda_feats, lm_labels, ind_select_list, soi_select_list, targets, masks, True, False, None, False)
         L.check(self.lib.echr_train_step_prepare(C.byref(self.a), L.stream_ptr()), 'train_step_prepare')
         self._prepared = True
@@ -200,7 +208,11 @@ class FusedTrainStep(object):
         # (set BEFORE the call: if it fails half-way, helper-stream work may already be queued, and the next _setup must join it before it
         # drops the references to this call's inputs)
         self._pending_deferred = bool(a.defer_update)
-        L.check(lib.echr_train_step(C.byref(a), L.stream_ptr()), 'train_step')
+        if self.clip != 1:
+            self.x.rw, self.x.weight = 0, None
+            L.check(lib.echr_train_step_clip(C.byref(a), C.byref(self.x), L.stream_ptr()), 'train_step_clip')
+        else:
+            L.check(lib.echr_train_step(C.byref(a), L.stream_ptr()), 'train_step')
         if (a.handover_cb or a.mid_cb) and getattr(self, '_cb_error', None) is not None:
             e, self._cb_error = self._cb_error, None
             raise e
@@ -208,7 +220,7 @@ class FusedTrainStep(object):
 
     def _set_tap(self, tap, tap_grad, defer_update, step, forward_only):
         a, d = self.a, self.a.dec
-        if (tap.shape[1] if a.event_parts & 2 else 0) + (d.D if a.event_parts & 1 else 0) != a.tsrm.Din or tap.shape[0] < self._tv_needed:
+        if (tap.shape[1] if a.event_parts & 2 else 0) + (self._dc if a.event_parts & 1 else 0) != a.tsrm.Din or tap.shape[0] < self._tv_needed:
             raise L.EchrHipError('tap_feats %s do not match the model / the event anchors' % (tuple(tap.shape),))
         a.tap, a.Ht = tap.data_ptr(), tap.shape[1]
         self._tap_keep = tap
@@ -316,9 +328,16 @@ class FusedTrainStep(object):
         d = a.dec
         a.tsrm.N = d.N = N
         d.A, d.Tv, d.S, d.rows_disjoint = int(lens.max()), c3d.shape[0], S, 1 if EF.rows_disjoint(soi) else 0
-        if c3d.shape[1] != d.D or lda.numel() != d.Dv:
+        if c3d.shape[1] != self._dc or lda.numel() != d.Dv:
             raise L.EchrHipError('feature widths do not match the model (c3d %d, lda %d)' % (c3d.shape[1], lda.numel()))
         d.c3d, d.video = c3d.data_ptr(), lda.data_ptr()
+        if self.clip != 1:
+            if tap is None:
+                raise NotImplementedError("clip_context_type with 'CH' needs tap_feats (prepare() runs ahead of them)")
+            # the row source: tap_feats ('CH') or [c3d | tap] ('CC+CH') over the rows both cover; c3d travels in the extension struct
+            d.Tv = tap.shape[0] if self.clip == 2 else min(c3d.shape[0], tap.shape[0])
+            d.c3d = None
+            self.x.c3d = c3d.data_ptr()
         # (tgt / msk: converted copies that only the argument struct's raw pointers reference -- after prepare() the caller allocates
         # before the second half reads them, so they must stay alive until the next _setup)
         self._keep = (c3d, lda, host, tgt, msk)
@@ -337,7 +356,11 @@ class FusedTrainStep(object):
             drop = m.lm_model.next_drop_state(m.fusion_model.enc_attn.dropout.p)
             drop.training = m.training
         a.drop = drop.c()
-        need = (lib.echr_train_step_ws_floats if weights is None else lib.echr_train_step_rw_ws_floats)(C.byref(a))
+        if self.clip != 1:
+            self.x.rw = 0 if weights is None else 1
+            need = lib.echr_train_step_clip_ws_floats(C.byref(a), C.byref(self.x))
+        else:
+            need = (lib.echr_train_step_ws_floats if weights is None else lib.echr_train_step_rw_ws_floats)(C.byref(a))
         if self.ws is None or self.ws.numel() < need:
             self.join()                        # (a deferred update may still be reading the old workspace on the helper streams)
             self.ws = None                     # (released in stream order by the caching allocator)
@@ -470,7 +493,11 @@ class SelfCriticalStep(object):
         a.prepared = a.handover = 0
         a.handover_cb = a.handover_user = a.mid_cb = a.mid_user = None
         f._pending_deferred = False
-        L.check(lib.echr_train_step_rw(C.byref(a), None, L.stream_ptr()), 'train_step_rw')
+        if f.clip != 1:
+            f.x.rw, f.x.weight = 1, None
+            L.check(lib.echr_train_step_clip(C.byref(a), C.byref(f.x), L.stream_ptr()), 'train_step_clip')
+        else:
+            L.check(lib.echr_train_step_rw(C.byref(a), None, L.stream_ptr()), 'train_step_rw')
         return f._finish(slot, st, False), gen_h, greedy_h, torch.from_numpy(r)
 
 
@@ -611,6 +638,8 @@ class DataParallelStep(object):
 
     def __init__(self, fused, group=None, overlap=True, algo=None, via=None):
         from . import parallel
+        if fused.clip != 1:
+            raise NotImplementedError("DataParallelStep runs clip_context_type 'CC' only (the 'CH' row gradient is not part of its hand-over stages)")
         self.P, self.fused, self.group, self.overlap, self.algo = parallel, fused, group, bool(overlap), algo
         # how an early range reaches the collective stream: 'callback' (default) = queued from inside the call with the library's stream current
         # (echr_train_step_args.handover_cb), 'event' = a side stream per range that waits for the hand-over event (echr_handover_wait)

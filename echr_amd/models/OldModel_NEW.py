@@ -17,9 +17,12 @@ class ClipView(object):
     """The frame-level ('CC') context without the zero-padded copy: event n's slot a is row
     ev_start[n] + a of `feats` [T,D] (CaptionGenerator.py:140-167 materialises [N,A,D] + mask instead)."""
 
-    def __init__(self, feats, ev_start, ev_len, max_len, rows_disjoint=False):
+    def __init__(self, feats, ev_start, ev_len, max_len, rows_disjoint=False, grad_src=None, grad_col0=0):
         self.feats, self.ev_start, self.ev_len, self.max_len = feats, ev_start, ev_len, int(max_len)
         self.rows_disjoint = bool(rows_disjoint)          # no two events share a row of `feats`
+        # 'CH' / 'CC+CH': the tensor whose rows fill columns [grad_col0, grad_col0 + its width) of `feats` (tap_feats) -- the decoder's backward
+        # returns its gradient; None: `feats` is data ('CC')
+        self.grad_src, self.grad_col0 = grad_src, int(grad_col0)
 
     @property
     def shape(self):
@@ -190,7 +193,7 @@ class OldModel(nn.Module):
         arena = getattr(self, '_echr_arena_ref', None)
         sink = EF.GradSink(arena, self.native_params()) if arena is not None else None
         return EF.DecoderFunction.apply(video, event, cv.feats, cv.ev_start, cv.ev_len, tokens, cv.max_len, cv.rows_disjoint, drop, sink,
-                                        prepared, self._initial_state(video, event, cv), *self.native_params())
+                                        prepared, self._initial_state(video, event, cv), cv.grad_src, cv.grad_col0, *self.native_params())
 
     def _initial_state(self, video, event, cv):
         """None (the recipe: zero state) or h0 [N, 3H] = init_linear(cat([video | event | clip.mean(1)])) (OldModel_NEW.py:79-92) -- the decoder

@@ -43,7 +43,8 @@ def state_dict_shapes(opt):
     tsrm_in = opt.video_dim if 'ER1' in et else (opt.hidden_dim if 'ER2' in et else opt.video_dim + opt.hidden_dim)
     vt = opt.video_context_type
     vi = (opt.lda_dim if 'VL' in vt else 0) + (opt.video_dim if 'VC' in vt else 0) + (opt.hidden_dim if 'VH' in vt else 0)
-    ev, cl = opt.d_o, opt.video_dim                   # context widths for ER3 / CC; vi: VL / VC / VH (CaptionGenerator.py:56-64)
+    ct = getattr(opt, 'clip_context_type', 'CC')      # frame-level rows: 'CC' C3D, 'CH' the SST states, 'CC+CH' both (CaptionGenerator.py:80-84)
+    ev, cl = opt.d_o, (opt.video_dim if 'CC' in ct else 0) + (opt.hidden_dim if 'CH' in ct else 0)      # context widths; vi: VL / VC / VH (:56-64)
     s = {
         'fusion_model.h2a_layer.weight': (10, 10), 'fusion_model.h2a_layer.bias': (10,),
         'fusion_model.event_emb.weight': (Df, tsrm_in), 'fusion_model.event_emb.bias': (Df,),
@@ -67,7 +68,7 @@ def state_dict_shapes(opt):
         s['lm_model.core.layer%d.bias_hh' % k] = (4 * H,)
     s.update({
         'lm_model.core.fusion_layer.weight': (H, 3 * H), 'lm_model.core.fusion_layer.bias': (H,),
-        'lm_model.core.attention.ctx2att.weight': (Ha, D), 'lm_model.core.attention.ctx2att.bias': (Ha,),
+        'lm_model.core.attention.ctx2att.weight': (Ha, cl), 'lm_model.core.attention.ctx2att.bias': (Ha,),
         'lm_model.core.attention.h2att.weight': (Ha, H), 'lm_model.core.attention.h2att.bias': (Ha,),
         'lm_model.core.attention.alpha_net.weight': (1, Ha), 'lm_model.core.attention.alpha_net.bias': (1,),
     })
@@ -172,6 +173,12 @@ CASES = {
     'tiny_eos': dict(opt=dict(video_dim=20, hidden_dim=24, lda_dim=12, d_feats=32, d_o=32, n_head=4, CG_rnn_size=32,
                               CG_input_encoding_size=16, CG_att_hid_size=24, CG_vocab_size=30, CG_seq_length=6),
                      video=dict(N=8, A=7, L=8, seed=13)),
+    # frame-level context over the proposal encoder's states (CaptionGenerator.py:140-167): 'CH' (the clip rows are tap_feats, D = 512) and
+    # 'CC+CH' (c3d and tap rows side by side, D = 1012) at the vctx / er2 shape; 'ch64': 'CH' at the ECHR widths with 64 ragged, overlapping
+    # events (c2-like), where D = 512 runs the persistent recurrence and decoding kernels
+    'ch': dict(opt=dict(clip_context_type='CH', CG_vocab_size=300, CG_seq_length=7), video=dict(N=12, A=40, L=9, seed=71)),
+    'cch': dict(opt=dict(clip_context_type='CC+CH', CG_vocab_size=300, CG_seq_length=7), video=dict(N=12, A=40, L=9, seed=72)),
+    'ch64': dict(opt=dict(clip_context_type='CH', CG_vocab_size=5000, CG_seq_length=19), video=dict(N=64, A=128, L=21, seed=73)),
     # EXACTLY the layout bench.py times (BASELINE config 3): 64 disjoint 128-segment events on a T_v = 8192 video
     'c3bench': dict(opt=dict(CG_vocab_size=5000, CG_seq_length=19), video=dict(N=64, A=128, L=21, seed=1234, disjoint=True)),
 }

@@ -310,6 +310,25 @@ typedef struct {
 
 /* make `stream` wait for an asynchronous decoder-backward tail (echr_dec_grads.async_tail); no-op when none is pending */
 int echr_stream_join(void* stream);
+
+/* Frame-level contexts 'CH' / 'CC+CH' (CaptionGenerator.py:140-167): the decoder's row source echr_dec_args.c3d is then tap_feats [Tv, Ht]
+ * itself ('CH', D = Ht) or the rows [Tv, Dc + Ht] = [c3d | tap] ('CC+CH', echr_clip_rows), and the attention reaches tap_feats.
+ * echr_decoder_row_grad runs after echr_decoder_bwd on the same ws / ws_bwd (any phase-0 form, asynchronous tail included: the call orders
+ * that tail first) and ADDS the gradient of columns [col0, col0 + ncols) of the row source into out (row r at out + r * ld):
+ *   out[start_n + a] += sum_t WT[t,n,a] . (d gates1[t,n] . W_ih1[:, E + col0 + c])  +  (d P_all . W_c2a[:, col0 + c])[start_n + a]
+ * for a < len_n, summed over every event that covers the row.  rows_disjoint = 1: plain updates; otherwise atomic adds, or with the
+ * "deterministic" configuration per-event slabs folded per row in event order (bit-identical run to run).  out must hold dec.Tv rows. */
+typedef struct {
+    int32_t col0;            /* first wanted column of the row source ('CH': 0, 'CC+CH': Dc) */
+    int32_t ncols;           /* wanted columns (Ht) */
+    float* out;              /* [>= Tv, ld] accumulated into (d tap_feats) */
+    int64_t ld;              /* leading dimension of out */
+    float* ws;               /* echr_decoder_row_grad_ws_floats(dec, ncols) floats */
+} echr_row_grad_args;
+int64_t echr_decoder_row_grad_ws_floats(const echr_dec_args* a, int32_t ncols);
+int echr_decoder_row_grad(const echr_dec_args* a, const echr_dec_grads* g, const echr_row_grad_args* r, void* stream);
+/* rows [Tv, Dc + Ht] = [c3d [Tv, Dc] | tap [Tv, Ht]] (the 'CC+CH' row source) */
+int echr_clip_rows(const float* c3d, int32_t Dc, const float* tap, int32_t Ht, float* rows, int32_t Tv, void* stream);
 /* Create the library's helper streams now (they are otherwise created by the first call that needs them) and submit one marker on each.
  * Call it once per process AFTER selecting the device and BEFORE anything else creates streams -- in particular before the RCCL communicator
  * is set up (torch.distributed.init_process_group with device_id): this runtime spreads streams over a handful of hardware queues in creation
@@ -607,6 +626,21 @@ int echr_train_step_rw(const echr_train_step_args* a, const float* weight, void*
  * beside the proposal encoder's forward the caller queues next.  Takes the arguments of the following echr_train_step (tap, g_tap, loss
  * slots may still be unset), which must then pass prepared = 1 and the same workspace.  Needs overlap_encoder = 1. */
 int echr_train_step_prepare(const echr_train_step_args* a, void* stream);
+/* echr_train_step (or, with rw = 1, echr_train_step_rw) with the frame-level context 'CH' or 'CC+CH'.  In `a`, dec.D / dec.Tv describe the
+ * ROW SOURCE (D = Ht or Dc + Ht; Tv <= the rows of c3d and of tap) and dec.c3d is ignored: the library takes tap itself ('CH') or forms
+ * [c3d | tap] in its workspace ('CC+CH').  The event encoder pools `c3d` [>= Tv, Dc].  With g_tap the clip-row gradient (echr_decoder_row_grad)
+ * is added to g_tap and is final when the call returns; defer_update is then ignored (the plain form runs: the row gradient needs the
+ * backward's attention stage, which the deferred form leaves on the helper streams).  Not with prepared = 1 nor with an initial state that
+ * reads the clip (init_use_c). */
+typedef struct {
+    int32_t clip_parts;      /* 2 = 'CH', 3 = 'CC+CH' */
+    int32_t Dc;              /* C3D width (video_dim) */
+    const float* c3d;        /* [>= dec.Tv, Dc] C3D features */
+    int32_t rw;              /* 1: reward-weighted criterion (echr_train_step_rw semantics) */
+    const float* weight;     /* rw = 1 with host_nll = 0: device [N,S] weights; NULL otherwise */
+} echr_clip_step_args;
+int64_t echr_train_step_clip_ws_floats(const echr_train_step_args* a, const echr_clip_step_args* x);
+int echr_train_step_clip(const echr_train_step_args* a, const echr_clip_step_args* x, void* stream);
 /* Hand-over points of the LAST echr_train_step issued with handover = 1 (which: 0 = logit layer, 1 = LSTM layers): makes `stream` wait
  * until that range of flat_g is final.  0 = `stream` now waits; 1 = the call recorded no such point (a configuration without the
  * asynchronous tail: the range is final when the call's own stream reaches its end, like every other); < 0 error. */
