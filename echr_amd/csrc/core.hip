@@ -33,10 +33,10 @@ int check_launch(const char* what) {
 // ---- runtime configuration -------------------------------------------------------------------------------
 static int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
 Config& config() {
-    static Config c = {env_int("ECHR_GEMM_BF16X3", 1), env_int("ECHR_OVERLAP", 0), env_int("ECHR_ATT_SLOTS", 2), env_int("ECHR_CHAINS2", 0),
+    static Config c = {env_int("ECHR_GEMM_BF16X3", 1), env_int("ECHR_ATT_SLOTS", 2),
                        env_int("ECHR_GEMM_H2", 1), env_int("ECHR_PERSIST", 1), env_int("ECHR_PERSIST_STAMPS", 0),
-                       getenv("ECHR_GEMM_TILE") ? (int)getenv("ECHR_GEMM_TILE")[0] : 0, env_int("ECHR_GEMM_SPLIT", 0), env_int("ECHR_PERSIST_BWD", 1), env_int("ECHR_PERSIST_SPLIT", 1), env_int("ECHR_PERSIST_H2", 1), env_int("ECHR_PERSIST_MERGE", 1), env_int("ECHR_PERSIST_KGROUPS", 1), env_int("ECHR_TSRM_FORK", 1),
-                       env_int("ECHR_PERSIST_COOP", 0), 0, env_int("ECHR_PERSIST_SPIN_LIMIT", 0), env_int("ECHR_SST_PERSIST", 1), env_int("ECHR_TAIL_EARLY", 0), 0, env_int("ECHR_EMBED_FUSED", 0), env_int("ECHR_PERSIST_SAMPLE", 1), env_int("ECHR_POSEMB_ROWS", 1), env_int("ECHR_GEMM_SKINNY", 1), env_int("ECHR_POSEMB_PACKED", 1), env_int("ECHR_PAIR_TABLES", 1), 0, env_int("ECHR_PERSIST_SAMPLE_MAX", 512), env_int("ECHR_DETERMINISTIC", 0)};
+                       getenv("ECHR_GEMM_TILE") ? (int)getenv("ECHR_GEMM_TILE")[0] : 0, env_int("ECHR_GEMM_SPLIT", 0), env_int("ECHR_PERSIST_BWD", 1), env_int("ECHR_PERSIST_SPLIT", 1), env_int("ECHR_PERSIST_H2", 1), env_int("ECHR_PERSIST_MERGE", 1), env_int("ECHR_PERSIST_KGROUPS", 1),
+                       env_int("ECHR_PERSIST_COOP", 0), 0, env_int("ECHR_PERSIST_SPIN_LIMIT", 0), env_int("ECHR_SST_PERSIST", 1), 0, env_int("ECHR_PERSIST_SAMPLE", 1), env_int("ECHR_POSEMB_ROWS", 1), env_int("ECHR_GEMM_SKINNY", 1), env_int("ECHR_POSEMB_PACKED", 1), env_int("ECHR_PAIR_TABLES", 1), 0, env_int("ECHR_PERSIST_SAMPLE_MAX", 512), env_int("ECHR_DETERMINISTIC", 0)};
     return c;
 }
 
@@ -1263,11 +1263,9 @@ extern "C" int echr_clamp_adam_counted(float* p, const float* g, float* m, float
     const double bc2 = 1.0 - pow(beta2, (double)step);
     const long n4 = n >> 2;
     int grid = (int)min(max((n4 + 255) / 256, 1L), 4096L);
-    static const int nt = [] { const char* e = getenv("ECHR_ADAM_NT"); return e ? atoi(e) : 2; }();      // A/B switch: 0 = cached accesses, 1 = g / m / v non-temporal, 2 = + the load of p, 3 = + its store
-#define ECHR_ADAM_LAUNCH(L) hipLaunchKernelGGL(clamp_adam_kernel<L>, dim3(grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (long)n, (float)(lr / bc1), \
-                       (float)(1.0 / sqrt(bc2)), (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, clip, persist_abort_word(), applied)
-    if (nt >= 3) ECHR_ADAM_LAUNCH(3); else if (nt == 2) ECHR_ADAM_LAUNCH(2); else if (nt == 1) ECHR_ADAM_LAUNCH(1); else ECHR_ADAM_LAUNCH(0);
-#undef ECHR_ADAM_LAUNCH
+    // NT = 2: g / m / v and the load of p non-temporal, the store of p cached
+    hipLaunchKernelGGL(clamp_adam_kernel<2>, dim3(grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (long)n, (float)(lr / bc1),
+                       (float)(1.0 / sqrt(bc2)), (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, clip, persist_abort_word(), applied);
     return check_launch("clamp_adam");
 }
 
@@ -1326,8 +1324,6 @@ extern "C" int echr_config_set(const char* key, int32_t value) {
     ECHR_REQUIRE(key, "config_set: null key");
     Config& c = config();
     if (!strcmp(key, "gemm_bf16x3")) c.gemm_bf16x3 = value;
-    else if (!strcmp(key, "overlap")) c.overlap = value;
-    else if (!strcmp(key, "chains2")) c.chains2 = value;
     else if (!strcmp(key, "gemm_h2")) c.gemm_h2 = value;
     else if (!strcmp(key, "persist")) c.persist = value;
     else if (!strcmp(key, "persist_stamps")) c.persist_stamps = value;
@@ -1336,12 +1332,9 @@ extern "C" int echr_config_set(const char* key, int32_t value) {
     else if (!strcmp(key, "persist_h2")) c.persist_h2 = value;
     else if (!strcmp(key, "persist_merge")) c.persist_merge = value;
     else if (!strcmp(key, "persist_kgroups")) c.persist_kgroups = value;
-    else if (!strcmp(key, "tsrm_fork")) c.tsrm_fork = value;
     else if (!strcmp(key, "persist_coop")) c.persist_coop = value;
     else if (!strcmp(key, "sst_persist")) c.sst_persist = value;
-    else if (!strcmp(key, "tail_early")) c.tail_early = value;
     else if (!strcmp(key, "diag_skip")) c.diag_skip = value;
-    else if (!strcmp(key, "embed_fused")) c.embed_fused = value;
     else if (!strcmp(key, "persist_sample")) c.persist_sample = value;
     else if (!strcmp(key, "posemb_rows")) c.posemb_rows = value;
     else if (!strcmp(key, "gemm_skinny")) c.gemm_skinny = value;

@@ -39,51 +39,16 @@ DropCfg make_drop(const echr_dropout* d, float p) {
     return c;
 }
 
-// ------------------------------------------------------------------------------------------------------
-// Side stream: the recurrence is a chain of short, latency-bound launches that leaves most CUs idle, while the
-// late-fusion and weight-gradient products are throughput GEMMs with no dependence on it.  They run on a
-// library-owned low-priority HIP stream, forked from / joined to the caller's stream with events (legal under
-// hipGraph capture).  One process drives one GPU (torch.distributed layout), so a process-wide singleton suffices.
-// ------------------------------------------------------------------------------------------------------
-struct Side {
-    hipStream_t s = nullptr;
-    hipEvent_t fork = nullptr, half = nullptr, join = nullptr;
-    bool ok = false;
-};
-static Side& side() {
-    static Side sd;
-    if (!sd.s) {
-        int lo = 0, hi = 0;
-        bool good = hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess;
-        good = good && hipStreamCreateWithPriority(&sd.s, hipStreamNonBlocking, lo) == hipSuccess;
-        good = good && hipEventCreateWithFlags(&sd.fork, echr::sync_event_flags()) == hipSuccess;
-        good = good && hipEventCreateWithFlags(&sd.half, echr::sync_event_flags()) == hipSuccess;
-        good = good && hipEventCreateWithFlags(&sd.join, echr::sync_event_flags()) == hipSuccess;
-        sd.ok = good;
-    }
-    return sd;
-}
 // Tail stream: part B of the decoder backward (attention-parameter and token-embedding gradients: ~10 launches that nothing else in the
 // backward pass depends on) can run on a second stream while autograd continues with the event encoder's / proposal encoder's
 // backward on the caller's stream.  The caller joins with echr_stream_join (the Python side does it in an end-of-backward callback);
 // every later library entry that takes a stream joins first as a safety net.
-static bool helper_stream_create(hipStream_t* s) {
-    const char* e = getenv("ECHR_HELPER_PRIO");
-    if (e && !strcmp(e, "low")) {
-        int least = 0, greatest = 0;
-        if (hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && hipStreamCreateWithPriority(s, hipStreamNonBlocking, least) == hipSuccess) return true;
-        (void)hipGetLastError();
-    }
-    return hipStreamCreateWithFlags(s, hipStreamNonBlocking) == hipSuccess;
-}
 struct Tail { hipStream_t s = nullptr; hipEvent_t fork = nullptr, done = nullptr, fork2 = nullptr, done2 = nullptr, done3 = nullptr; bool ok = false, init = false, pending = false, pending3 = false; };
 static Tail& tail() {
     static Tail t;
     if (!t.init) {
         t.init = true;
-        // (ECHR_HELPER_PRIO=low: least priority -- the helper streams carry chip-filling throughput kernels whose workgroups otherwise delay the
-        // dispatch of the caller's stream's small latency-bound kernels running beside them; A/B switch)
-        bool good = helper_stream_create(&t.s);
+        bool good = hipStreamCreateWithFlags(&t.s, hipStreamNonBlocking) == hipSuccess;
         good = good && hipEventCreateWithFlags(&t.fork, echr::sync_event_flags()) == hipSuccess;
         good = good && hipEventCreateWithFlags(&t.done, echr::sync_event_flags()) == hipSuccess;
         good = good && hipEventCreateWithFlags(&t.fork2, echr::sync_event_flags()) == hipSuccess;
@@ -161,11 +126,6 @@ extern "C" int echr_handover_wait(int which, void* stream) {
     return 0;
 }
 
-static bool overlap_enabled() {
-    // measured neutral on the c3 workload (the recurrent GEMM's two 67 KB-LDS workgroups per CU leave no room for a
-    // co-resident throughput GEMM, so the overlap only trades places): opt-in (ECHR_OVERLAP=1 / echr_config_set)
-    return config().overlap == 1 && side().ok;
-}
 static int hop(hipStream_t from, hipEvent_t ev, hipStream_t to) {      // `to` continues after everything queued on `from`
     if (hipEventRecord(ev, from) != hipSuccess || hipStreamWaitEvent(to, ev, 0) != hipSuccess) {
         set_error("stream fork/join failed");
@@ -632,10 +592,7 @@ static int launch_att_post(const AttDims& d, const float* PALL, const float* QS,
 //   the same k pairing, so the products are exact fp32 sums over the slice.
 // ------------------------------------------------------------------------------------------------------
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-#ifndef ECHR_RK
-#define ECHR_RK 128
-#endif
-constexpr int RK = ECHR_RK;          // k-slice staged per workgroup
+constexpr int RK = 128;          // k-slice staged per workgroup
 constexpr int RQ = RK / 4, RLP = 64 * RQ / 256;      // float4 per row, staging float4 per thread and operand
 constexpr int RLD = RK + 4;          // LDS row stride (floats): 16-byte aligned rows, conflict-free b128 reads
 constexpr int MAXJOBS = 8;
@@ -665,7 +622,8 @@ __global__ __launch_bounds__(256, 2) void rec_gemm_kernel(RecArgs args) {
     f32x16 acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-    // args.kloop (fixed-order mode, grid.y = 1): this workgroup walks ALL k slices of its tile in order and updates the output once
+    // args.kloop (grid.y = 1): this workgroup walks ALL k slices of its tile in order and updates the output once (no host path sets it: the
+    // fixed-order mode runs the slab form of rec_gemm)
     const int ks0 = args.kloop ? 0 : (int)blockIdx.y, ks1 = args.kloop ? (J.K + RK - 1) / RK : ks0 + 1;
     if (n0 >= J.Nout || ks0 * RK >= J.K) return;
     for (int ks = ks0; ks < ks1; ++ks) {
@@ -761,39 +719,31 @@ static int rec_gemm(const RecArgs& a, hipStream_t st) {
     bool any_atomic = false;
     for (int j = 0; j < a.njobs; ++j) any_atomic = any_atomic || a.job[j].atomic;
     if (det_mode() && any_atomic) {
-        // fixed-order mode: the jobs that add into shared accumulators run as one k loop per tile (plain update); slab jobs of the same launch
-        // would then all land in slab 0, so the two kinds are not mixed
+        // fixed-order mode for the jobs that add into shared accumulators (slab jobs are not mixed in)
         for (int j = 0; j < a.njobs; ++j) ECHR_REQUIRE(a.job[j].atomic, "rec_gemm: fixed-order mode cannot mix slab and accumulator jobs");
         for (int j = 1; j < a.njobs; ++j) for (int i = 0; i < j; ++i) ECHR_REQUIRE(a.job[i].P != a.job[j].P, "rec_gemm: fixed-order mode needs distinct outputs per launch");
-        static const bool slabs = [] { const char* e = getenv("ECHR_DET_REC_SLABS"); return !(e && e[0] == '0'); }();      // A/B switch
-        if (slabs) {
-            // every k slice writes its own slab (the launch keeps its k parallelism), then ONE fold launch adds a job's slabs to its accumulator
-            // in slice order: 6 + 4 us instead of one 28-us workgroup per tile walking all sixteen slices
-            RecArgs b = a;
-            RecFold f;
-            f.njobs = a.njobs; f.M = a.M;
-            long need = 0;
-            for (int j = 0; j < a.njobs; ++j) need += (long)ksplit_of(a.job[j].K) * a.M * a.job[j].Nout;
-            float* scr = det_scratch(DET_REC, (size_t)need);
-            if (!scr) return -12;
-            long off = 0, cells = 0;
-            for (int j = 0; j < a.njobs; ++j) {
-                const long sl = (long)a.M * a.job[j].Nout;
-                f.P[j] = a.job[j].P; f.ldp[j] = a.job[j].ldp; f.Nout[j] = a.job[j].Nout; f.nslab[j] = ksplit_of(a.job[j].K); f.slab[j] = scr + off; f.start[j] = cells;
-                b.job[j].P = scr + off; b.job[j].slab_stride = sl; b.job[j].ldp = a.job[j].Nout; b.job[j].atomic = 0;
-                off += sl * f.nslab[j];
-                cells += sl;
-            }
-            f.start[a.njobs] = cells;
-            hipLaunchKernelGGL(rec_gemm_kernel, dim3(maxn, maxk, a.njobs * ((a.M + 63) / 64)), dim3(256), 0, st, b);
-            if (int rc = check_launch("rec_gemm")) return rc;
-            hipLaunchKernelGGL(rec_fold_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, f);
-            return check_launch("rec_fold");
-        }
+        // every k slice writes its own slab (the launch keeps its k parallelism), then ONE fold launch adds a job's slabs to its accumulator
+        // in slice order: 6 + 4 us instead of one 28-us workgroup per tile walking all sixteen slices
         RecArgs b = a;
-        b.kloop = 1;
-        hipLaunchKernelGGL(rec_gemm_kernel, dim3(maxn, 1, a.njobs * ((a.M + 63) / 64)), dim3(256), 0, st, b);
-        return check_launch("rec_gemm");
+        RecFold f;
+        f.njobs = a.njobs; f.M = a.M;
+        long need = 0;
+        for (int j = 0; j < a.njobs; ++j) need += (long)ksplit_of(a.job[j].K) * a.M * a.job[j].Nout;
+        float* scr = det_scratch(DET_REC, (size_t)need);
+        if (!scr) return -12;
+        long off = 0, cells = 0;
+        for (int j = 0; j < a.njobs; ++j) {
+            const long sl = (long)a.M * a.job[j].Nout;
+            f.P[j] = a.job[j].P; f.ldp[j] = a.job[j].ldp; f.Nout[j] = a.job[j].Nout; f.nslab[j] = ksplit_of(a.job[j].K); f.slab[j] = scr + off; f.start[j] = cells;
+            b.job[j].P = scr + off; b.job[j].slab_stride = sl; b.job[j].ldp = a.job[j].Nout; b.job[j].atomic = 0;
+            off += sl * f.nslab[j];
+            cells += sl;
+        }
+        f.start[a.njobs] = cells;
+        hipLaunchKernelGGL(rec_gemm_kernel, dim3(maxn, maxk, a.njobs * ((a.M + 63) / 64)), dim3(256), 0, st, b);
+        if (int rc = check_launch("rec_gemm")) return rc;
+        hipLaunchKernelGGL(rec_fold_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, f);
+        return check_launch("rec_fold");
     }
     hipLaunchKernelGGL(rec_gemm_kernel, dim3(maxn, maxk, a.njobs * ((a.M + 63) / 64)), dim3(256), 0, st, a);
     return check_launch("rec_gemm");
@@ -1099,28 +1049,24 @@ static int init_state_copy(const echr_dec_args* a, const DecWs& w, hipStream_t s
 //   launch 2,3: attention scores, softmax + context
 //   launch 4: attended-context columns of stream 1's W_ih                              -> slabs
 //   launch 5: gate math for the three streams (adds the slabs)
-// `chain`: 0 = all three streams in this call; 1 = only stream 1 (the attention chain); 2 = only streams 0 and 2 (pure LSTM
-// recurrences, independent of the attention chain -> they can run on a second HIP stream, see echr_decoder_fwd).
-static int step_fwd(const echr_dec_args* a, const DecWs& w, int t, const DropCfg& dh, const DropCfg& dout, hipStream_t st, int chain = 0,
-                    bool q_atomic = false, const int* tok = nullptr) {
+static int step_fwd(const echr_dec_args* a, const DecWs& w, int t, const DropCfg& dh, const DropCfg& dout, hipStream_t st, bool q_atomic = false,
+                    const int* tok = nullptr) {
     const int N = a->N, H = a->H, Ha = a->Ha, A = a->A, D = a->D, E = a->E;
     const float* hprev = w.HS + (long)t * N * 3 * H;          // [N,3H] dropped h of step t-1 (zeros at t=0)
     const long gs = (long)N * 4 * H, qs = (long)N * Ha;
     const int nh = ksplit_of(H);
-    const bool do1 = chain != 2, do02 = chain != 1;
     RecArgs ra;
     ra.M = N; ra.njobs = 0;
     // q is re-read by every attention workgroup of an event: accumulate it atomically into one buffer (training) instead of
     // letting each of them sum the k-slice slabs; the sampler keeps the slab form (bitwise reproducible decoding)
     float* qacc = q_atomic ? w.QACC + (long)t * N * Ha : w.QSL;
-    if (do1) ra.job[ra.njobs++] = mkjob(hprev + H, 3 * H, H, a->w_h2a, H, Ha, qacc, qs, Ha, q_atomic ? 1 : 0);
+    ra.job[ra.njobs++] = mkjob(hprev + H, 3 * H, H, a->w_h2a, H, Ha, qacc, qs, Ha, q_atomic ? 1 : 0);
     // training path: the recurrent products add atomically into GATES[k][t], which already holds the input-side pre-activations,
     // so the gate kernel reads one value per gate instead of summing 4..8 slabs (the sampler keeps the reproducible slab form)
     const bool gacc = q_atomic;
     for (int k = 0; k < 3; ++k)
-        if (k == 1 ? do1 : do02)
-            ra.job[ra.njobs++] = gacc ? mkjob(hprev + k * H, 3 * H, H, a->w_hh[k], H, 4 * H, w.GATES[k] + (long)t * gs, gs, 4 * H, 1)
-                                      : mkjob(hprev + k * H, 3 * H, H, a->w_hh[k], H, 4 * H, w.GSL[k], gs, 4 * H);
+        ra.job[ra.njobs++] = gacc ? mkjob(hprev + k * H, 3 * H, H, a->w_hh[k], H, 4 * H, w.GATES[k] + (long)t * gs, gs, 4 * H, 1)
+                                  : mkjob(hprev + k * H, 3 * H, H, a->w_hh[k], H, 4 * H, w.GSL[k], gs, 4 * H);
     const int ne = ksplit_of(E), nd = ksplit_of(D);
     if (tok) {
         // sampler, few events: the token-side products W_ih_k[:, :E] . embed(token) ride in the same launch (A rows gathered from the embedding
@@ -1133,28 +1079,25 @@ static int step_fwd(const echr_dec_args* a, const DecWs& w, int t, const DropCfg
         }
     }
     RC(rec_gemm(ra, st));
-    if (do1) {
-        float* q = w.QS + (long)t * N * Ha;
-        float* sc = w.SC + (long)t * N * A;
-        float* wt = w.WT + (long)t * N * A;
-        float* att = w.ATT + (long)t * N * D;
-        {
-        // algorithmic bytes of one attention step: p_att rows + clip rows + scores/weights/context
-        const double rows = (double)N * A;
-        ProfScope prof(PROF_ATT_FWD, 2.0 * rows * (Ha + D) , 4.0 * (rows * (Ha + D + 2) + (double)N * (Ha + D)), st);
-        const AttDims ad{N, A, Ha, D};
-        RC(launch_att_score(ad, w.PALL, qacc, q_atomic ? 1 : w.nq, qs, a->b_h2a, q, a->w_alpha, a->b_alpha, a->ev_start, a->ev_len, sc, st));
-        hipLaunchKernelGGL(att_context_kernel, dim3(N, (D + 127) / 128), dim3(256), (((A + 31) & ~31) + 8 * 128) * sizeof(float), st, a->c3d, sc,
-                           a->ev_start, a->ev_len, wt, att, A, D);
-        RC(check_launch("att_context"));
-        }
-        ra.njobs = 1;
-        ra.job[0] = gacc ? mkjob(att, D, D, a->w_ih[1] + E, E + D, 4 * H, w.GATES[1] + (long)t * gs, gs, 4 * H, 1)
-                         : mkjob(att, D, D, a->w_ih[1] + E, E + D, 4 * H, w.GSL[1] + nh * gs, gs, 4 * H);
-        RC(rec_gemm(ra, st));
+    float* q = w.QS + (long)t * N * Ha;
+    float* sc = w.SC + (long)t * N * A;
+    float* wt = w.WT + (long)t * N * A;
+    float* att = w.ATT + (long)t * N * D;
+    {
+    // algorithmic bytes of one attention step: p_att rows + clip rows + scores/weights/context
+    const double rows = (double)N * A;
+    ProfScope prof(PROF_ATT_FWD, 2.0 * rows * (Ha + D) , 4.0 * (rows * (Ha + D + 2) + (double)N * (Ha + D)), st);
+    const AttDims ad{N, A, Ha, D};
+    RC(launch_att_score(ad, w.PALL, qacc, q_atomic ? 1 : w.nq, qs, a->b_h2a, q, a->w_alpha, a->b_alpha, a->ev_start, a->ev_len, sc, st));
+    hipLaunchKernelGGL(att_context_kernel, dim3(N, (D + 127) / 128), dim3(256), (((A + 31) & ~31) + 8 * 128) * sizeof(float), st, a->c3d, sc,
+                       a->ev_start, a->ev_len, wt, att, A, D);
+    RC(check_launch("att_context"));
     }
+    ra.njobs = 1;
+    ra.job[0] = gacc ? mkjob(att, D, D, a->w_ih[1] + E, E + D, 4 * H, w.GATES[1] + (long)t * gs, gs, 4 * H, 1)
+                     : mkjob(att, D, D, a->w_ih[1] + E, E + D, 4 * H, w.GSL[1] + nh * gs, gs, 4 * H);
+    RC(rec_gemm(ra, st));
     LstmPtrs P;
-    int nk = 0;
     for (int k = 0; k < 3; ++k) {
         P.gates[k] = w.GATES[k] + (long)t * N * 4 * H;
         P.slab[k] = w.GSL[k];
@@ -1167,11 +1110,10 @@ static int step_fwd(const echr_dec_args* a, const DecWs& w, int t, const DropCfg
         }
         P.c_prev[k] = w.CS[k] + (long)t * N * H;
         P.c_new[k] = w.CS[k] + (long)(t + 1) * N * H;
-        P.kmap[k] = 0;
-        if (k == 1 ? do1 : do02) P.kmap[nk++] = k;
+        P.kmap[k] = k;
     }
     P.slab_stride = gs;
-    hipLaunchKernelGGL(lstm_pointwise_fwd_kernel, dim3((N * H + 255) / 256, nk), dim3(256), 0, st, P,
+    hipLaunchKernelGGL(lstm_pointwise_fwd_kernel, dim3((N * H + 255) / 256, 3), dim3(256), 0, st, P,
                        w.HS + (long)(t + 1) * N * 3 * H, w.OUTD + (long)t * N * 3 * H, N, H, t, dh, dout);
     return check_launch("lstm_pointwise_fwd");
 }
@@ -1217,7 +1159,7 @@ static Prep& prep() {
     static Prep t;
     if (!t.init) {
         t.init = true;
-        bool good = helper_stream_create(&t.s);
+        bool good = hipStreamCreateWithFlags(&t.s, hipStreamNonBlocking) == hipSuccess;
         good = good && hipEventCreateWithFlags(&t.fork, echr::sync_event_flags()) == hipSuccess;
         good = good && hipEventCreateWithFlags(&t.done, echr::sync_event_flags()) == hipSuccess;
         good = good && hipEventCreateWithFlags(&t.fill_done, echr::sync_event_flags()) == hipSuccess;
@@ -1227,7 +1169,7 @@ static Prep& prep() {
     return t;
 }
 // the prepare stream outside a forward pass (idle during the backward pass): a second helper stream for work that is independent of what the
-// caller's stream and the tail stream carry (the event encoder's position-MLP gradients, csrc/tsrm.hip).  fork: it continues after everything
+// caller's stream and the tail stream carry (the decoder backward's LSTM-layer stage).  fork: it continues after everything
 // queued on `from`; join: `to` waits for what was queued on it since.  nullptr / no-op when unavailable or when a prepare is pending.
 namespace echr {
 hipStream_t aux2_fork(hipStream_t from) {
@@ -1241,15 +1183,6 @@ int aux2_join(hipStream_t to) {
     if (hipEventRecord(pr.done, pr.s) != hipSuccess || hipStreamWaitEvent(to, pr.done, 0) != hipSuccess) { set_error("stream join failed"); return -5; }
     return 0;
 }
-// what the prepare stream carries now (work forked onto it by aux2_fork) is part of what echr_stream_join / the next library call waits for
-int aux2_publish() {
-    Prep& pr = prep();
-    Tail& t = tail();
-    if (!pr.ok || !t.ok) { set_error("aux2_publish: helper streams unavailable"); return -5; }
-    if (hipEventRecord(t.done3, pr.s) != hipSuccess) { set_error("aux2_publish: event record failed"); return -5; }
-    t.pending3 = true;
-    return 0;
-}
 // echr_train_step's joint mode (step.hip): the helper streams keep working after the call returns
 bool helpers_available() { return tail().ok && prep().ok && !prep().pending; }
 }  // namespace echr
@@ -1258,8 +1191,7 @@ bool helpers_available() { return tail().ok && prep().ok && !prep().pending; }
 extern "C" int echr_streams_init(void) {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); set_error("streams_init: no device"); return -19; }
-    // (only the two streams every iteration uses: with the caller's stream and the collective library's they fill this runtime's four hardware
-    // queues; the opt-in side stream of `overlap` = 1 stays lazy)
+    // (the two helper streams: with the caller's stream and the collective library's they fill this runtime's four hardware queues)
     Tail& t = tail();
     Prep& p = prep();
     bool ok = true;
@@ -1291,11 +1223,7 @@ int tail_publish() {                           // what the tail stream carries n
 }
 }  // namespace echr
 // will echr_decoder_fwd run the persistent forward launch on these arguments (same test as there)?
-static bool fwd_uses_persist(const echr_dec_args* a) {
-    const bool two = config().chains2 == 1 && side().ok && a->S >= 2;
-    const bool ov = !two && overlap_enabled() && a->S >= 4;
-    return persist_fwd_eligible(a) && !ov && !two;
-}
+static bool fwd_uses_persist(const echr_dec_args* a) { return persist_fwd_eligible(a); }
 static int decoder_fill(const echr_dec_args* a, const DecWs& w, hipStream_t st, bool with_extra = true) {
     const int N = a->N, S = a->S, H = a->H;
     // h(-1) = c(-1) = 0 (init_hidden, :75-78), the atomic q accumulators and the split-K target EVB0 -- and the zeroed part of the persistent
@@ -1329,10 +1257,9 @@ namespace echr {
 // recurrences; echr_decoder_bwd then skips its fill (it waits for the prepare stream's fill event on entry anyway)
 int decoder_bwd_scratch_ahead(const echr_dec_args* a, const echr_dec_grads* g) {
     Prep& pr = prep();
-    static const bool off = [] { const char* e = getenv("ECHR_SCRATCH_AHEAD"); return e && e[0] == '0'; }();
-    if (off || !pr.ok || !pr.pending || !pr.fill_pending || pr.ws != a->ws || !g->ws_bwd || !g->g_event || overlap_enabled()) return 0;
+    if (!pr.ok || !pr.pending || !pr.fill_pending || pr.ws != a->ws || !g->ws_bwd || !g->g_event) return 0;
     const DecWsBwd b = carve_ws_bwd(a, g->ws_bwd);
-    const bool bwd_persist = !(config().chains2 == 1 && side().ok && a->S >= 2) && persist_bwd_eligible(a);
+    const bool bwd_persist = persist_bwd_eligible(a);
     float* zp[FILL_MAX_JOBS];
     long zn[FILL_MAX_JOBS];
     echr_dec_grads gz = *g;
@@ -1363,18 +1290,16 @@ extern "C" int echr_decoder_fwd_prepare(const echr_dec_args* a, void* stream) {
     if (fwd_uses_persist(a)) RC(persist_fwd_prebuild(a, w.XWS, sm));
     // the caller's gradient arena (echr_train_step: 87 MB) is zero-filled LAST on this stream, behind the event this call publishes: nothing of
     // the forward pass waits for it -- a fill has no LDS and a handful of registers, so it also fits beside the recurrence's workgroups -- and
-    // echr_decoder_bwd waits for it on entry.  -10 us per iteration against the fill in front (ECHR_ARENA_FILL_LATE=0, A/B: 1.540 vs 1.550 ms)
-    static const bool late_fill = [] { const char* e = getenv("ECHR_ARENA_FILL_LATE"); return !(e && e[0] == '0'); }();
-    const bool late = late_fill && a->zero_extra && a->zero_extra_count > 0;
+    // echr_decoder_bwd waits for it on entry.  -10 us per iteration against the fill in front (A/B: 1.540 vs 1.550 ms)
+    const bool late = a->zero_extra && a->zero_extra_count > 0;
     RC(decoder_fill(a, w, st, !late));
     // (the event-context gate product of echr_decoder_fwd accumulates into EVB0, zeroed by this fill: it waits for THIS event, not for the
     // whole chain below -- the product then runs beside the chain's last GEMM instead of behind it)
     if (hipEventRecord(pr.fill0, st) != hipSuccess) { set_error("decoder_fwd_prepare: event record failed"); return -5; }
-    // ECHR_WL_ON_CALLER (default 1): the two W_logit images leave the head of the prepare chain for the caller's stream, which has slack in front of
-    // the recurrence since the position branch starts beside the previous update (stage-ahead): 1.450-1.454 vs 1.445-1.465 ms and 1.414-1.422 vs
-    // 1.418-1.431 on two boxes (-5 us in the mean); issued later still, where the forward joins the prepare chain: 1.454-1.463, not kept
-    static const bool wl_caller = [] { const char* e = getenv("ECHR_WL_ON_CALLER"); return !(e && e[0] == '0'); }();      // A/B switch
-    RC(precompute_static(a, w, st, true, true, 1, wl_caller ? sm : nullptr));
+    // the two W_logit images are packed on the caller's stream, not at the head of the prepare chain: it has slack in front of the recurrence
+    // since the position branch starts beside the previous update (stage-ahead): 1.450-1.454 vs 1.445-1.465 ms and 1.414-1.422 vs 1.418-1.431
+    // on two boxes (-5 us in the mean)
+    RC(precompute_static(a, w, st, true, true, 1, sm));
     RC(embed_gather(a->embed, a->tokens, w.XT, a->S * a->N, a->E, a->V1, st));
     RC(input_gates(a, w, w.XT, 0, a->S, st, true));
     if (hipEventRecord(pr.done, st) != hipSuccess) { set_error("decoder_fwd_prepare: event record failed"); return -5; }
@@ -1428,15 +1353,9 @@ static int decoder_fwd_impl(const echr_dec_args* a, const echr_dropout* drop, vo
         Prep& pr = prep();
         ECHR_REQUIRE(pr.ok && pr.pending && pr.ws == a->ws, "decoder_fwd: prepared = 1 without a matching echr_decoder_fwd_prepare on this workspace");
         pr.pending = false;
-        static const bool evb0_first = [] { const char* e = getenv("ECHR_EVB0_FIRST"); return !(e && e[0] == '0'); }();      // A/B switch
-        if (evb0_first) {
-            if (hipStreamWaitEvent(st, pr.fill0, 0) != hipSuccess) { set_error("decoder_fwd: join failed"); return -5; }
-            RC(precompute_static(a, w, st, true, true, 2));
-            if (hipStreamWaitEvent(st, pr.done, 0) != hipSuccess) { set_error("decoder_fwd: join failed"); return -5; }
-        } else {
-        if (hipStreamWaitEvent(st, pr.done, 0) != hipSuccess) { set_error("decoder_fwd: join failed"); return -5; }
+        if (hipStreamWaitEvent(st, pr.fill0, 0) != hipSuccess) { set_error("decoder_fwd: join failed"); return -5; }
         RC(precompute_static(a, w, st, true, true, 2));
-        }
+        if (hipStreamWaitEvent(st, pr.done, 0) != hipSuccess) { set_error("decoder_fwd: join failed"); return -5; }
         evb0_pending = fwd_uses_persist(a) && persist_fwd_adds_evb0();      // the persistent launch's LSTM role adds the event part itself
         if (!evb0_pending) {
             const long n4 = (long)S * N * H;            // 4H / 4 float4 per row
@@ -1450,13 +1369,11 @@ static int decoder_fwd_impl(const echr_dec_args* a, const echr_dropout* drop, vo
         RC(input_gates(a, w, w.XT, 0, S, st));
     }
     if (a->h0) RC(init_state_copy(a, w, st));          // OldModel.init_hidden with CG_init_feats_type (:79-96): behind the zero fill of HS[0] / CS[k][0]
-    // late fusion: logits = OUTD . W_logit^T + b, written [N,S,V1], then row log-softmax in place.  Timesteps [0,th) are
-    // projected on the side stream while the recurrence of [th,S) is still running.
-    auto logits_chunk = [&](int t0, int t1, hipStream_t q) -> int {
+    // late fusion: logits = OUTD . W_logit^T + b, written [N,S,V1], then row log-softmax in place, behind the recurrence
+    auto logits = [&](hipStream_t q) -> int {
         // echr_train_step with the criterion's active rows: logits only for the rows that can reach the loss (compact [n_active, V1] in the
         // log-prob buffer, which nothing else reads on that path), then log-softmax + criterion + d logits in one pass over them
-        static const bool native_compact = [] { const char* e = getenv("ECHR_NATIVE_COMPACT"); return !(e && e[0] == '0'); }();      // A/B switch
-        if (fz && fz->active_rows && fz->n_active > 0 && (config().gemm_h2 || native_compact) && t0 == 0 && t1 == S && fz->nll_target && fz->nll_mask && fz->g_loss && fz->ws_bwd) {
+        if (fz && fz->active_rows && fz->n_active > 0 && fz->nll_target && fz->nll_mask && fz->g_loss && fz->ws_bwd) {
             const DecWsBwd b = carve_ws_bwd(a, fz->ws_bwd);
             if (logsoftmax_nll_dlg_ok(a->V1, b.ldg)) {
                 echr_gemm_desc dc;
@@ -1481,10 +1398,9 @@ static int decoder_fwd_impl(const echr_dec_args* a, const echr_dropout* drop, vo
                                           fz->active_rows, fz->n_active, rw);
             }
         }
-        echr_gemm_desc d = desc_nt(w.OUTD + (long)t0 * N * 3 * H, 3 * H, a->w_logit, 3 * H, a->logp + (long)t0 * a->V1, a->V1,
-                                   (t1 - t0) * N, a->V1, 3 * H);
+        echr_gemm_desc d = desc_nt(w.OUTD, 3 * H, a->w_logit, 3 * H, a->logp, a->V1, S * N, a->V1, 3 * H);
         d.algo = ECHR_GEMM_BF16X3;
-        if (config().gemm_h2 && t0 == 0 && t1 == S) {
+        if (config().gemm_h2) {
             H2PackJob pj = pack_rows(w.OUTD, 3 * H, S * N, 3 * H, w.PK_OUTD);
             RC(h2_pack_multi(&pj, 1, q));
             d = desc_h2(w.PK_OUTD, w.PK_WL, a->logp, a->V1, S * N, a->V1, 3 * H);
@@ -1492,7 +1408,7 @@ static int decoder_fwd_impl(const echr_dec_args* a, const echr_dropout* drop, vo
         }
         d.bias = a->b_logit; d.rowmap_mod = N; d.rowmap_mul = S;
         RC(gemm(d, q));
-        if (fz && t0 == 0 && t1 == S && fz->nll_target && fz->nll_mask && fz->g_loss && fz->ws_bwd) {
+        if (fz && fz->nll_target && fz->nll_mask && fz->g_loss && fz->ws_bwd) {
             const DecWsBwd b = carve_ws_bwd(a, fz->ws_bwd);
             if (logsoftmax_nll_dlg_ok(a->V1, b.ldg)) {
                 if (fused_out) *fused_out = true;
@@ -1500,12 +1416,9 @@ static int decoder_fwd_impl(const echr_dec_args* a, const echr_dropout* drop, vo
                                           nullptr, 0, rw);
             }
         }
-        return logsoftmax_rows(a->logp, a->V1, N, S, t0, t1 - t0, a->V1, q);
+        return logsoftmax_rows(a->logp, a->V1, N, S, 0, S, a->V1, q);
     };
-    const bool two = config().chains2 == 1 && side().ok && S >= 2;     // streams 0/2 recur on the side stream
-    const bool ov = !two && overlap_enabled() && S >= 4;
-    const int th = ov ? S / 2 : 0;
-    if (persist_fwd_eligible(a) && !ov && !two) {
+    if (persist_fwd_eligible(a)) {
         // all S timesteps in ONE persistent launch: recurrent weights stay in LDS, attention operands in registers (csrc/persist.hip)
         PersistFwdBufs pb;
         for (int k = 0; k < 3; ++k) { pb.GATES[k] = w.GATES[k]; pb.CS[k] = w.CS[k]; }
@@ -1513,23 +1426,10 @@ static int decoder_fwd_impl(const echr_dec_args* a, const echr_dropout* drop, vo
         pb.prezeroed = true;                    // decoder_fill covered the exchange workspace's zeroed part
         if (evb0_pending) pb.EVB0 = w.EVB0;
         RC(persist_fwd(a, pb, dh, dout, st));
-    } else if (two) {
-        RC(hop(st, side().fork, side().s));
-        for (int t = 0; t < S; ++t) RC(step_fwd(a, w, t, dh, dout, side().s, 2, true));
-        for (int t = 0; t < S; ++t) RC(step_fwd(a, w, t, dh, dout, st, 1, true));
-        RC(hop(side().s, side().join, st));
     } else {
-        for (int t = 0; t < S; ++t) {
-            RC(step_fwd(a, w, t, dh, dout, st, 0, true));
-            if (ov && t == th - 1) {
-                RC(hop(st, side().fork, side().s));
-                RC(logits_chunk(0, th, side().s));
-            }
-        }
+        for (int t = 0; t < S; ++t) RC(step_fwd(a, w, t, dh, dout, st, true));
     }
-    RC(logits_chunk(th, S, st));
-    if (ov) RC(hop(side().s, side().join, st));
-    return 0;
+    return logits(st);
 }
 
 // d W_logit = DLG^T . OUTD (plain overwrite) and d b_logit on packed operands that the caller has prepared
@@ -1563,7 +1463,7 @@ int echr::decoder_bwd_parts(const echr_dec_args* a, const echr_dec_grads* g, con
         prep().fill_pending = false;
         if (hipStreamWaitEvent((hipStream_t)stream, prep().fill_done, 0) != hipSuccess) { set_error("decoder_bwd: stream wait failed"); return -5; }
     }
-    ECHR_REQUIRE(part == 0 || (g->phase == 0 && g->async_tail == 2 && g->zeroed && config().gemm_h2 && tail().ok && !overlap_enabled()),
+    ECHR_REQUIRE(part == 0 || (g->phase == 0 && g->async_tail == 2 && g->zeroed && config().gemm_h2 && tail().ok),
                  "decoder_bwd: the two-piece form needs phase 0, async_tail 2, zeroed gradients, the h2 path and the helper streams");
     hipStream_t st = (hipStream_t)stream;
     const int N = a->N, S = a->S, H = a->H, E = a->E, Ha = a->Ha, A = a->A, D = a->D, V1 = a->V1;
@@ -1578,9 +1478,8 @@ int echr::decoder_bwd_parts(const echr_dec_args* a, const echr_dec_grads* g, con
     const bool compact = g->dlg_ready && g->active_rows && g->n_active > 0;
     const int SNc = compact ? g->n_active : SN;
     const int* act = compact ? g->active_rows : nullptr;
-    // the recurrent weight gradients / d XT on the active rows too (ECHR_COMPACT_REC=0: all S*N rows, for A/B runs)
-    static const bool rec_env = [] { const char* e = getenv("ECHR_COMPACT_REC"); return !(e && e[0] == '0'); }();
-    const bool crec = compact && rec_env && config().gemm_h2;          // (the k gather rides in the h2 packs: the native products keep all rows there)
+    // the recurrent weight gradients / d XT on the active rows too
+    const bool crec = compact && config().gemm_h2;          // (the k gather rides in the h2 packs: the native products keep all rows there)
     const int SNr = crec ? SNc : SN;
     const int* actr = crec ? act : nullptr;
     ECHR_REQUIRE(!compact || (g->phase == 0 && g->async_tail != 0), "decoder_bwd: active_rows needs the asynchronous tail");
@@ -1592,7 +1491,7 @@ int echr::decoder_bwd_parts(const echr_dec_args* a, const echr_dec_grads* g, con
     const bool do_rec = g->phase == 0 || g->phase == 2 || g->phase == 3;                                // ... and its batched parameter gradients
     const bool do_pb = (g->phase == 0 || g->phase == 2 || g->phase == 4) && part != 1;
     // the reverse recurrence of this call runs as the persistent launch (same test as stage 3 applies)
-    const bool bwd_persist = !overlap_enabled() && !(config().chains2 == 1 && side().ok && S >= 2) && persist_bwd_eligible(a);
+    const bool bwd_persist = persist_bwd_eligible(a);
     // 1. d logits (time-major, padded leading dimension)
     if (do_a) {
     if (!g->dlg_ready) {          // (echr_train_step formed d logits in the pass that read the logits)
@@ -1602,9 +1501,8 @@ int echr::decoder_bwd_parts(const echr_dec_args* a, const echr_dec_grads* g, con
     }
     // scratch that is accumulated into, and the transposed recurrent weights (every d h / d ATT product of the reverse recurrence
     // then has the same NT form as forward): two launches, independent of everything above
-    // (the persistent reverse launch builds its weight images from the untransposed matrices: nothing to transpose then; the test is the
-    // one the recurrence stage applies below, on the same arguments and configuration)
-    if (!(!overlap_enabled() && !(config().chains2 == 1 && side().ok && S >= 2) && persist_bwd_eligible(a))) {
+    // (the persistent reverse launch builds its weight images from the untransposed matrices: nothing to transpose then)
+    if (!bwd_persist) {
         const TransposeJob tj[5] = {{a->w_hh[0], H, b.WT_HH[0], 4 * H, 4 * H, H}, {a->w_hh[1], H, b.WT_HH[1], 4 * H, 4 * H, H},
                                     {a->w_hh[2], H, b.WT_HH[2], 4 * H, 4 * H, H}, {a->w_ih[1] + E, cin[1], b.WT_ATT, 4 * H, 4 * H, D},
                                     {a->w_h2a, H, b.WT_H2A, Ha, Ha, H}};
@@ -1621,16 +1519,11 @@ int echr::decoder_bwd_parts(const echr_dec_args* a, const echr_dec_grads* g, con
     }
     scratch_ahead() = nullptr;
     }
-    // 2. late fusion gradients: the weight/bias gradients do not feed the recurrence -> side stream
-    const bool ov = overlap_enabled() && S >= 4 && g->phase == 0;
-    hipStream_t sq = ov ? side().s : st;
-    if (ov) RC(hop(st, side().fork, sq));
-    // Both late-fusion products run as NT problems on k-contiguous (transposed) operands so that they qualify for the
+    // 2. late fusion gradients.  Both late-fusion products run as NT problems on k-contiguous (transposed) operands so that they qualify for the
     // bf16-split matrix-core path: d W_logit = DLG^T . OUTD  and  d OUTD = DLG . W_logit.
     echr_gemm_desc d;
-    const bool h2 = config().gemm_h2 && !ov;
-    static const bool native_tail = [] { const char* e = getenv("ECHR_NATIVE_TAIL"); return !(e && e[0] == '0'); }();      // A/B switch
-    const bool native_defer_wl = native_tail && !h2 && !ov && part == 0 && g->phase == 0 && g->async_tail != 0 && tail().ok;
+    const bool h2 = config().gemm_h2 != 0;
+    const bool native_defer_wl = !h2 && part == 0 && g->phase == 0 && g->async_tail != 0 && tail().ok;
     ECHR_REQUIRE(h2 || !compact || native_defer_wl, "decoder_bwd: active_rows on the native product path needs the deferred logit-layer gradients");
     const float* outd_rows = (compact && !h2) ? w.PK_OUTD : w.OUTD;          // native + compact: the forward's gathered [n_active, 3H] operand
     if (!do_a) {
@@ -1659,12 +1552,12 @@ int echr::decoder_bwd_parts(const echr_dec_args* a, const echr_dec_grads* g, con
     // (native fp32 / bf16x3 products.  With an asynchronous tail the logit-layer gradients -- which nothing in the backward pass reads -- are formed
     // on the tail stream behind the reverse recurrence, as on the h2 path, instead of in front of it: 0.2 ms off the caller's stream)
     if (!native_defer_wl) {
-    RC(transpose(b.DLG, b.ldg, b.DLGT, b.snp, SN, V1, (int)b.snp, sq));
-    RC(transpose(w.OUTD, 3 * H, b.OUTDT, b.snp, SN, 3 * H, (int)b.snp, sq));
+    RC(transpose(b.DLG, b.ldg, b.DLGT, b.snp, SN, V1, (int)b.snp, st));
+    RC(transpose(w.OUTD, 3 * H, b.OUTDT, b.snp, SN, 3 * H, (int)b.snp, st));
     d = desc_nt(b.DLGT, b.snp, b.OUTDT, b.snp, g->g_w_logit, 3 * H, V1, 3 * H, (int)b.snp);
     d.beta = zb; d.split_k = -1; d.algo = ECHR_GEMM_BF16X3;
-    RC(gemm(d, sq));
-    RC(colsum(b.DLG, b.ldg, SN, V1, g->g_b_logit, z, sq));
+    RC(gemm(d, st));
+    RC(colsum(b.DLG, b.ldg, SN, V1, g->g_b_logit, z, st));
     }
     RC(transpose(a->w_logit, 3 * H, b.WLT, b.ldg, V1, 3 * H, (int)b.ldg, st));
     d = desc_nt(b.DLG, b.ldg, b.WLT, b.ldg, b.DOUT, 3 * H, SNc, 3 * H, (int)b.ldg);
@@ -1674,14 +1567,11 @@ int echr::decoder_bwd_parts(const echr_dec_args* a, const echr_dec_grads* g, con
     }
     // 3. reverse recurrence
     const long hs = (long)N * H, as = (long)N * D;
-    // weight gradients that are sums over timesteps [t0,t1): W_hh_k, W_ih_k[:, :E], W_ih1[:, E:], W_h2a.
+    // weight gradients that are sums over the S timesteps: W_hh_k, W_ih_k[:, :E], W_ih1[:, E:], W_h2a.
     // beta = 0 writes, beta = 1 accumulates.  HS[t] holds h(t-1), so rows t*N.. pair with DG[t].
-    auto wgrad_chunk = [&](int t0, int t1, float beta, hipStream_t q) -> int {
-        if (t1 <= t0) return 0;
-        const long r0 = (long)t0 * N;
-        const int rows = (t1 - t0) * N;
+    auto wgrad = [&](float beta, hipStream_t q) -> int {
         echr_gemm_desc e, ghh[3], gih[3];
-        if (h2 && t0 == 0 && t1 == S) {
+        if (h2) {
             // all S*N rows at once: DG_k^T, h(t-1)_k^T, XT^T, ATT^T, DQ^T packed (transposing) by one launch; DG_k^T is shared by the
             // W_hh, W_ih[:, :E] and W_ih1[:, E:] gradients, h1^T by the W_hh1 and W_h2a gradients
             H2PackJob pj[9];
@@ -1708,26 +1598,23 @@ int echr::decoder_bwd_parts(const echr_dec_args* a, const echr_dec_grads* g, con
             return gemm_grouped(g7, 8, q);
         }
         for (int k = 0; k < 3; ++k) {
-            ghh[k] = desc_tn(b.DG[k] + r0 * 4 * H, 4 * H, w.HS + r0 * 3 * H + k * H, 3 * H, g->g_w_hh[k], H, 4 * H, H, rows);
+            ghh[k] = desc_tn(b.DG[k], 4 * H, w.HS + k * H, 3 * H, g->g_w_hh[k], H, 4 * H, H, SN);
             ghh[k].beta = beta; ghh[k].split_k = -1;
-            gih[k] = desc_tn(b.DG[k] + r0 * 4 * H, 4 * H, w.XT + r0 * E, E, g->g_w_ih[k], cin[k], 4 * H, E, rows);
+            gih[k] = desc_tn(b.DG[k], 4 * H, w.XT, E, g->g_w_ih[k], cin[k], 4 * H, E, SN);
             gih[k].beta = beta; gih[k].split_k = -1;
         }
         RC(gemm_grouped(ghh, 3, q));        // three W_hh gradients in one launch
         RC(gemm_grouped(gih, 3, q));        // three W_ih[:, :E] gradients in one launch
-        e = desc_tn(b.DG[1] + r0 * 4 * H, 4 * H, w.ATT + r0 * D, D, g->g_w_ih[1] + E, cin[1], 4 * H, D, rows);
+        e = desc_tn(b.DG[1], 4 * H, w.ATT, D, g->g_w_ih[1] + E, cin[1], 4 * H, D, SN);
         e.beta = beta; e.split_k = -1;
         RC(gemm(e, q));
-        e = desc_tn(b.DQ + r0 * Ha, Ha, w.HS + r0 * 3 * H + H, 3 * H, g->g_w_h2a, H, Ha, H, rows);
+        e = desc_tn(b.DQ, Ha, w.HS + H, 3 * H, g->g_w_h2a, H, Ha, H, SN);
         e.beta = beta; e.split_k = -1;
         return gemm(e, q);
     };
-    const int th_b = ov ? S / 2 : S;       // timesteps [th_b, S) get their weight gradients on the side stream
-    // one reverse timestep; `chain` as in step_fwd (0 = everything, 1 = attention chain / stream 1, 2 = streams 0 and 2)
-    auto bwd_step = [&](int t, int chain, hipStream_t q) -> int {
-        const bool do1 = chain != 2, do02 = chain != 1;
+    // one reverse timestep
+    auto bwd_step = [&](int t, hipStream_t q) -> int {
         LstmBwdPtrs P;
-        int nk = 0;
         for (int k = 0; k < 3; ++k) {
             P.gates[k] = w.GATES[k] + (long)t * N * 4 * H;
             P.c_prev[k] = w.CS[k] + (long)t * N * H;
@@ -1736,11 +1623,10 @@ int echr::decoder_bwd_parts(const echr_dec_args* a, const echr_dec_grads* g, con
             P.dh_slab[k] = nullptr;
             P.dh_acc[k] = b.DHACC[k];                           // d h(t), added atomically while processing step t+1 (zero at t = S-1)
             P.nslab[k] = 0;
-            P.kmap[k] = 0;
-            if (k == 1 ? do1 : do02) P.kmap[nk++] = k;
+            P.kmap[k] = k;
         }
         P.slab_stride = hs;
-        hipLaunchKernelGGL(lstm_pointwise_bwd_kernel, dim3((N * H + 255) / 256, nk), dim3(256), 0, q, P,
+        hipLaunchKernelGGL(lstm_pointwise_bwd_kernel, dim3((N * H + 255) / 256, 3), dim3(256), 0, q, P,
                            b.DOUT + (long)t * N * 3 * H, b.DC, N, H, t, dh, dout);
         RC(check_launch("lstm_pointwise_bwd"));
         // d h(t-1) = dG_k(t) . W_hh_k  (skipped at t = 0 when h(-1) is the constant zero state; with echr_dec_args.h0 it is d h0);  d ATT = dG_1(t) . W_ih1[:,E:]
@@ -1748,12 +1634,10 @@ int echr::decoder_bwd_parts(const echr_dec_args* a, const echr_dec_grads* g, con
         RecArgs ra;
         ra.M = N; ra.njobs = 0;
         float* datt = b.DASL + (long)t * N * D;     // re-read by every attention workgroup of an event: one atomically summed buffer
-        if (do1) ra.job[ra.njobs++] = mkjob(P.dgates[1], 4 * H, 4 * H, b.WT_ATT, 4 * H, D, datt, as, D, 1);
+        ra.job[ra.njobs++] = mkjob(P.dgates[1], 4 * H, 4 * H, b.WT_ATT, 4 * H, D, datt, as, D, 1);
         if (rec0)
-            for (int k = 0; k < 3; ++k)
-                if (k == 1 ? do1 : do02) ra.job[ra.njobs++] = mkjob(P.dgates[k], 4 * H, 4 * H, b.WT_HH[k], 4 * H, H, b.DHACC[k], hs, H, 1);
-        if (ra.njobs > 0) RC(rec_gemm(ra, q));
-        if (!do1) return 0;
+            for (int k = 0; k < 3; ++k) ra.job[ra.njobs++] = mkjob(P.dgates[k], 4 * H, 4 * H, b.WT_HH[k], 4 * H, H, b.DHACC[k], hs, H, 1);
+        RC(rec_gemm(ra, q));
         // attention backward (needed at every t: feeds d P_all, d alpha, d W_h)
         float* dq = b.DQ + (long)t * N * Ha;
         {
@@ -1769,28 +1653,16 @@ int echr::decoder_bwd_parts(const echr_dec_args* a, const echr_dec_grads* g, con
         }
         return 0;
     };
-    const bool two = !ov && config().chains2 == 1 && side().ok && S >= 2;
     if (!do_rec_main) {
-    } else if (!ov && !two && persist_bwd_eligible(a)) {
+    } else if (bwd_persist) {
         // the whole reverse recurrence in two concurrent persistent launches (csrc/persist.hip)
         PersistBwdBufs pb;
         for (int k = 0; k < 3; ++k) { pb.GATES[k] = w.GATES[k]; pb.CS[k] = w.CS[k]; pb.DG[k] = b.DG[k]; }
         pb.QS = w.QS; pb.WT = w.WT; pb.ATT = w.ATT; pb.PALL = w.PALL; pb.DOUT = b.DOUT; pb.DQ = b.DQ; pb.DSC = b.DSC; pb.xws = b.XWSB;
         pb.prezeroed = do_a;                    // stage 1 of this call zeroed the exchange workspace with the backward scratch
         RC(persist_bwd(a, pb, dh, dout, st));
-    } else if (two) {          // streams 0/2 are independent of the attention chain: their reverse recurrence runs on the side stream
-        RC(hop(st, side().fork, side().s));
-        for (int t = S - 1; t >= 0; --t) RC(bwd_step(t, 2, side().s));
-        for (int t = S - 1; t >= 0; --t) RC(bwd_step(t, 1, st));
-        RC(hop(side().s, side().join, st));
     } else {
-        for (int t = S - 1; t >= 0; --t) {
-            RC(bwd_step(t, 0, st));
-            if (ov && t == th_b) {     // DG / DQ of timesteps [th_b, S) are final: their weight gradients overlap the rest
-                RC(hop(st, side().half, sq));
-                RC(wgrad_chunk(th_b, S, zb, sq));
-            }
-        }
+        for (int t = S - 1; t >= 0; --t) RC(bwd_step(t, st));
     }
     if (do_rec_main && a->h0 && g->g_h0) {          // d loss / d (initial state): what step 0 left in the d h accumulators + the carried d c
         const long n = (long)N * 3 * H;
@@ -1802,11 +1674,10 @@ int echr::decoder_bwd_parts(const echr_dec_args* a, const echr_dec_grads* g, con
     // async_tail = 2: only d event (what the caller's next backward kernels, the event encoder's, wait for) is formed on the caller's stream,
     // first; the rest of part A -- nine transposing packs, the grouped weight-gradient product, bias sums, the context halves of W_ih: ~0.13 ms
     // -- moves to the prepare stream (idle during a backward pass) and is joined by echr_stream_join like the tail
-    static const int dxt_stream = [] { const char* e = getenv("ECHR_DXT_STREAM"); return (e && e[0] >= '0' && e[0] <= '2') ? e[0] - '0' : 2; }();          // 0 = the caller's stream
     bool dxt_done = false;
     //    token embedding: dXT = sum_k DG_k . W_ih_k[:, :E], scatter-added into the (caller-zeroed) table gradient.  Reads what the recurrence
-    //    left (DG) and parameters only, so the chain can ride on either helper stream (ECHR_DXT_STREAM: 1 = tail stream, 2 = prepare stream
-    //    behind the LSTM-layer stage -- whichever leaves the three streams of the backward tail ending together)
+    //    left (DG) and parameters only, so the chain rides on the prepare stream behind the LSTM-layer stage, which leaves the three streams of
+    //    the backward tail ending together
     auto dxt_chain = [&](hipStream_t q) -> int {
         dxt_done = true;
         echr_gemm_desc gx[3];
@@ -1819,33 +1690,26 @@ int echr::decoder_bwd_parts(const echr_dec_args* a, const echr_dec_grads* g, con
             }
             RC(h2_pack_multi(pj, 6, q));
         }
-        // "embed_fused" = 1 (off by default): dXT = sum_k DG_k . W_ih_k[:, :E] is not materialised -- the products' epilogues add row (t, n) straight
-        // into the embedding-table gradient row of its token (echr_gemm_desc.row_index).  Measured on one box, alternating runs: 1.94 vs 1.74 ms per
-        // iteration -- every k-slice of every product then sends its atomics to the table, and the 64 <bos> rows of a batch (plus frequent words)
-        // serialise on the same addresses; the dense d XT buffer takes the k-slice atomics without contention and the scatter pass meets each
-        // duplicate once (20 us, `tools/skip_bounds.py`)
-        // (with compacted rows the products' row i is position act[i]: the scatter through `rowmap` handles that, the fused epilogue -- indexed
-        // by the compact row -- would not, so the switch is ignored there)
-        const bool fused_scatter = config().embed_fused != 0 && !actr && !det_mode();          // (the fused epilogue is atomics by construction)
+        // dXT is materialised, not added by the products' epilogues straight into the table gradient row of its token (echr_gemm_desc.row_index):
+        // measured on one box, alternating runs, 1.74 ms per iteration against 1.94 -- every k-slice of every product would send its atomics to the
+        // table, and the 64 <bos> rows of a batch (plus frequent words) serialise on the same addresses; the dense d XT buffer takes the k-slice
+        // atomics without contention and the scatter pass meets each duplicate once (20 us, `tools/skip_bounds.py`)
         for (int k = 0; k < 3; ++k) {
-            float* out = fused_scatter ? g->g_embed : b.DXT;
-            gx[k] = h2 ? desc_h2(b.PK_DG[k], b.PK_WIHT[k], out, E, SNr, E, 4 * H) : desc_nn(b.DG[k], 4 * H, a->w_ih[k], cin[k], out, E, SN, E, 4 * H);
+            gx[k] = h2 ? desc_h2(b.PK_DG[k], b.PK_WIHT[k], b.DXT, E, SNr, E, 4 * H) : desc_nn(b.DG[k], 4 * H, a->w_ih[k], cin[k], b.DXT, E, SN, E, 4 * H);
             gx[k].split_k = -1; gx[k].beta = 1.f;                // shared, pre-zeroed output: everything adds atomically
-            if (fused_scatter) { gx[k].row_index = a->tokens; gx[k].row_index_max = V1 - 1; }
         }
         RC(gemm_grouped(gx, 3, q));
-        if (!fused_scatter) RC(embed_scatter_add(b.DXT, a->tokens, g->g_embed, h2 ? SNr : SN, E, V1, q, h2 ? actr : nullptr));
+        RC(embed_scatter_add(b.DXT, a->tokens, g->g_embed, h2 ? SNr : SN, E, V1, q, h2 ? actr : nullptr));
         return 0;
     };
     hipStream_t sa2 = nullptr;
     auto part_a = [&]() -> int {
     if (!do_rec) return 0;
-    if (g->phase == 0 && g->async_tail == 2 && z && (h2 || (native_tail && part == 0)) && !ov && tail().ok) {
-        // Both helper streams fork RIGHT BEHIND the reverse recurrence, off ONE recorded event (ECHR_FORK_FIRST=0: behind d event, one record
-        // each): the two records used to sit between the d event product and everything that follows on all three streams (~15 us of an idle
-        // chip).  The prepare stream then forms its own copy of the per-event gate-gradient sums (6 us) instead of waiting for this stream's
-        static const bool fork_first = [] { const char* e = getenv("ECHR_FORK_FIRST"); return !(e && e[0] == '0'); }();      // A/B switch
-        const bool ff = fork_first && part == 0;
+    if (g->phase == 0 && g->async_tail == 2 && z && (h2 || part == 0) && tail().ok) {
+        // Both helper streams fork RIGHT BEHIND the reverse recurrence, off ONE recorded event, not behind d event with one record each: the
+        // two records used to sit between the d event product and everything that follows on all three streams (~15 us of an idle chip).
+        // The prepare stream then forms its own copy of the per-event gate-gradient sums (6 us) instead of waiting for this stream's
+        const bool ff = part == 0;
         if (ff) {
             sa2 = aux2_fork(st);
             if (sa2) fork_event(prep().fork);          // part B's fork waits for the same event
@@ -1861,7 +1725,7 @@ int echr::decoder_bwd_parts(const echr_dec_args* a, const echr_dec_grads* g, con
         const float* dgsum0 = b.DGSUM[0];
         if (sa2 && ff) { RC(sum_over_time(b.DG[0], 4 * H, S, N, 4 * H, b.DGSUM[1], 4 * H, sa2)); dgsum0 = b.DGSUM[1]; }
         if (sa2) {
-            RC(wgrad_chunk(0, S, 1.f, sa2));
+            RC(wgrad(1.f, sa2));
             const ColsumJob cj[4] = {{b.DQ, Ha, SN, Ha, g->g_b_h2a, nullptr, nullptr},
                                      {b.DG[0], 4 * H, SN, 4 * H, g->g_b_ih[0], g->g_b_hh[0], nullptr},
                                      {b.DG[1], 4 * H, SN, 4 * H, g->g_b_ih[1], g->g_b_hh[1], nullptr},
@@ -1873,13 +1737,13 @@ int echr::decoder_bwd_parts(const echr_dec_args* a, const echr_dec_grads* g, con
             RC(rank1_update(b.DGCOL[2], a->video, g->g_w_ih[2] + E, cin[2], 4 * H, a->Dv, false, sa2));          // K = 1: no GEMM launch
             if (g->g_video) RC(vec_mat(b.DGCOL[2], a->w_ih[2] + E, cin[2], g->g_video, 4 * H, a->Dv, sa2));
             RC(handover_mark(ECHR_HANDOVER_LSTM, sa2));          // every gradient of core.layer0..2 is final here
-            if (dxt_stream == 2 && do_pb && !dxt_done) RC(dxt_chain(sa2));
+            if (do_pb && !dxt_done) RC(dxt_chain(sa2));
             if (hipEventRecord(tail().done3, sa2) != hipSuccess) { set_error("decoder_bwd: event record failed"); return -5; }
             tail().pending3 = true;
             return 0;
         }
         // (no second helper stream: the rest follows on the caller's stream; d event is already there)
-        RC(wgrad_chunk(0, S, 1.f, st));
+        RC(wgrad(1.f, st));
         const ColsumJob cj[4] = {{b.DQ, Ha, SN, Ha, g->g_b_h2a, nullptr, nullptr},
                                  {b.DG[0], 4 * H, SN, 4 * H, g->g_b_ih[0], g->g_b_hh[0], nullptr},
                                  {b.DG[1], 4 * H, SN, 4 * H, g->g_b_ih[1], g->g_b_hh[1], nullptr},
@@ -1892,8 +1756,7 @@ int echr::decoder_bwd_parts(const echr_dec_args* a, const echr_dec_grads* g, con
         if (g->g_video) RC(vec_mat(b.DGCOL[2], a->w_ih[2] + E, cin[2], g->g_video, 4 * H, a->Dv, st));
         return 0;
     }
-    if (ov) RC(hop(sq, side().join, st));                     // chunk [th,S) and the logit gradients are complete
-    RC(wgrad_chunk(0, th_b, (ov || z) ? 1.f : 0.f, st));      // W_hh_k, W_ih_k[:, :E], W_ih1[:, E:], W_h2a: sums over timesteps
+    RC(wgrad(zb, st));          // W_hh_k, W_ih_k[:, :E], W_ih1[:, E:], W_h2a: sums over timesteps
     //    bias gradients b_h2a and per stream b_ih = b_hh = column sums of DG_k over all S*N rows (stream 2's also as the plain vector
     //    DGCOL that the scene projection below consumes).  One launch when the gradient buffers accumulate.
     if (z) {
@@ -1923,11 +1786,10 @@ int echr::decoder_bwd_parts(const echr_dec_args* a, const echr_dec_grads* g, con
     return 0;
     };
     // phase 0 + async_tail: nothing downstream in the backward pass needs part B's outputs -> second stream, joined by the caller.  Its three
-    // chains (logit-layer gradients, attention parameters, token embedding) read only what the recurrence left (DLG, OUTD, DG, DQ, DSC), so the
-    // tail may fork right behind the reverse recurrence, AHEAD of part A ("tail_early" = 1) instead of behind it: measured on one box,
-    // alternating runs, 1.731 vs 1.726 ms per iteration -- this phase is bound by its chip-filling GEMMs, packs and att_post (~0.4 ms), not by
-    // stream order, so the default stays the later fork (part A first)
-    const bool async_tail = g->phase == 0 && g->async_tail != 0 && tail().ok && !ov && do_pb;
+    // chains (logit-layer gradients, attention parameters, token embedding) read only what the recurrence left (DLG, OUTD, DG, DQ, DSC); the
+    // tail forks behind part A, not ahead of it: measured on one box, alternating runs, 1.726 vs 1.731 ms per iteration -- this phase is bound
+    // by its chip-filling GEMMs, packs and att_post (~0.4 ms), not by stream order
+    const bool async_tail = g->phase == 0 && g->async_tail != 0 && tail().ok && do_pb;
     hipStream_t sm = st;              // the caller's stream
     bool bias_pending = false;
     auto part_b = [&]() -> int {
@@ -2010,7 +1872,7 @@ int echr::decoder_bwd_parts(const echr_dec_args* a, const echr_dec_grads* g, con
     d.beta = zb;
     RC(gemm(d, st));
     if (!z) RC(colsum(b.DPALL, Ha, a->Tv, Ha, g->g_b_c2a, z, st));
-    if (!dxt_done && !(async_tail && dxt_stream == 0)) RC(dxt_chain(st));
+    if (!dxt_done) RC(dxt_chain(st));
     if (async_tail) {
         if (hipEventRecord(tail().done, st) != hipSuccess) { set_error("decoder_bwd: event record failed"); return -5; }
         tail().pending = true;
@@ -2018,11 +1880,9 @@ int echr::decoder_bwd_parts(const echr_dec_args* a, const echr_dec_grads* g, con
     }
     return 0;
     };
-    int rcp;
-    if (async_tail && config().tail_early) { rcp = part_b(); if (!rcp) rcp = part_a(); }
-    else { rcp = part_a(); if (!rcp) rcp = part_b(); }
+    int rcp = part_a();
+    if (!rcp) rcp = part_b();
     fork_event(nullptr);
-    if (!rcp && !dxt_done && do_pb) rcp = dxt_chain(sm);          // (ECHR_DXT_STREAM=0: on the caller's stream, ahead of the event encoder's backward)
     return rcp;
 }
 
@@ -2196,7 +2056,7 @@ static int chain_step(const echr_dec_args& a, const DecWs& w, const SampWs& s, i
     } else {
         // few events: no embedding gather, no input-gate GEMM -- the token-side products are jobs of the step's first grouped launch
         // (rows gathered from the embedding table by token id), the time-invariant addends are read by the gate kernel
-        RC(step_fwd(&a, w, t, dh, dout, st, 0, false, s.IT));
+        RC(step_fwd(&a, w, t, dh, dout, st, false, s.IT));
     }
     *slab_form = false;
     if (big) {

@@ -17,7 +17,7 @@ struct ProfScope {
 };
 
 // runtime switches (initial values from the environment, changeable through echr_config_set)
-struct Config { int gemm_bf16x3; int overlap; int att_slots; int chains2; int gemm_h2; int persist; int persist_stamps; int gemm_tile; int gemm_split; int persist_bwd; int persist_split; int persist_h2; int persist_merge; int persist_kgroups; int tsrm_fork; int persist_coop; int persist_inject_timeout; int persist_spin_limit; int sst_persist; int tail_early; int diag_skip; int embed_fused; int persist_sample; int posemb_rows; int gemm_skinny; int posemb_packed; int pair_tables; int persist_sample_force_eos; int persist_sample_max; int deterministic; };
+struct Config { int gemm_bf16x3; int att_slots; int gemm_h2; int persist; int persist_stamps; int gemm_tile; int gemm_split; int persist_bwd; int persist_split; int persist_h2; int persist_merge; int persist_kgroups; int persist_coop; int persist_inject_timeout; int persist_spin_limit; int sst_persist; int diag_skip; int persist_sample; int posemb_rows; int gemm_skinny; int posemb_packed; int pair_tables; int persist_sample_force_eos; int persist_sample_max; int deterministic; };
 // diag_skip (diagnostic, tools/skip_bounds.py; results are WRONG while a bit is set): 1 = h2 operand packs, 2 = clamp+Adam kernel, 4 = att_post, 16 = every fp32-path product (gemm_f32 / t128 / bf16x3), 32 = every h2 product, 64 / 128 = the h2m16 product kernel loads only / computes only (tools/h2_ablate.py),
 // 8 = embedding scatter-add -- the launch is skipped, which bounds what removing / hiding that work could gain
 Config& config();
@@ -91,7 +91,6 @@ hipStream_t aux_fork(hipStream_t from);          // nullptr when unavailable
 int aux_join(hipStream_t to);
 hipStream_t aux2_fork(hipStream_t from);         // the same on the decoder's prepare stream (idle during a backward pass); nullptr when unavailable
 int aux2_join(hipStream_t to);
-int aux2_publish();                             // instead of a join: echr_stream_join / the next library call wait for what the prepare stream carries now
 bool helpers_available();
 hipStream_t aux2_stream();
 hipStream_t tail_stream_raw();                   // the tail stream itself, NOT ordered behind anything (echr_train_step's stage-ahead form); nullptr when unavailable
@@ -99,7 +98,6 @@ int prep_stream_wait(hipEvent_t ev);             // the prepare stream waits for
 hipStream_t helpers_merge_to_tail();
 int tail_publish();
 int tsrm_position_early(const echr_tsrm_args* a, hipStream_t from);          // echr_train_step: start the event encoder's position branch right behind the index staging
-void tsrm_bwd_defer_join(bool on);          // echr_train_step: the position branch's stream is joined by echr_stream_join, not inside echr_tsrm_bwd
 int tsrm_bwd_parts(const echr_tsrm_args* a, const echr_tsrm_grads* g, const echr_dropout* drop, void* stream, int part);
 int decoder_bwd_scratch_ahead(const echr_dec_args* a, const echr_dec_grads* g);
 // rw (optional): RewardCriterion's signed weight [N,S] for the criterion gradient formed here (the non-fused d logits; echr_train_step_rw)

@@ -1238,28 +1238,21 @@ static int gemm_impl(const echr_gemm_desc* ds, int ng, hipStream_t st) {
     // products (tile quantisation: 400 big tiles on 256 CUs), so it is the default; 128x128 stays selectable for tuning.
     int BMs = 64, BNs = 64;
     bool w8 = false;
-    // tuning knobs are read from the environment ONCE per process (tools/gemm_bench.py sets them before loading the library); a stray
-    // variable can therefore not change numerics or split order call by call
-    static const int env_h2_bm = getenv("ECHR_H2_BM") ? atoi(getenv("ECHR_H2_BM")) : 128;
     const char tile_code = (char)config().gemm_tile;          // 0 = heuristics; set from ECHR_GEMM_TILE at load or by echr_config_set
     const int env_split = config().gemm_split;
-    if (h2) { BMs = env_h2_bm; BNs = 128; }
+    if (h2) { BMs = 128; BNs = 128; }
     if (use_split) { BMs = 128; BNs = ((long)((d.M + 127) / 128) * ((d.N + 127) / 128) * d.batch >= 96) ? 128 : 64; }
     // large exact-fp32 products: the 128 x 128 double-buffered tile (gemm_f32_t128_kernel) once its tiles fill most of the chip -- measured stand-alone
     // against the 64 x 64 tile (tools/t128_bench.py, us): logits 762 x 5001 x 1536 (240 tiles) 133 vs 155, d W_logit 5001 x 1536 x 764 (480) 118 vs
     // 134, 4096^3 NT 1083 vs 1286; with fewer tiles the 64 x 64 tile's finer grain (7 resident waves per SIMD, 2.5 x more tiles to balance) wins
     // whatever the k split: d OUTD 762 x 1536 x 5004 (72 tiles) 179 vs 143, gin 1280 x 2048 x 512 (160) 48 vs 38, P_all 8192 x 512 x 500 (256) 58 vs 50
-    static const int t128_on = getenv("ECHR_GEMM_T128") ? atoi(getenv("ECHR_GEMM_T128")) : 1;
-    static const int t128_min_tiles = getenv("ECHR_GEMM_T128_TILES") ? atoi(getenv("ECHR_GEMM_T128_TILES")) : 200;
-    static const int t128_min_k = getenv("ECHR_GEMM_T128_K") ? atoi(getenv("ECHR_GEMM_T128_K")) : 1024;
     const long tiles128 = (long)((maxM + 127) / 128) * ((maxN + 127) / 128) * d.batch * ng;
     // ... and K-heavy NT products of 32-128 such tiles (d OUTD 762 x 1536 x 5004: 72 tiles): the eight-wave form on floor(256 / tiles) k slices,
-    // one workgroup per CU -- 132 us against 146 on the 64 x 64 tile's own split (tools/t128_w8.py)
-    static const int t128_ks_on = getenv("ECHR_GEMM_T128_KS") ? atoi(getenv("ECHR_GEMM_T128_KS")) : 1;
-    const bool t128ks = t128_on && t128_ks_on && !h2 && !use_split && !tile_code && akc && bkc && ng == 1 && d.batch == 1 && d.split_k < 0 && d.rowmap_mod == 0 &&
+    // one workgroup per CU -- 132 us against 146 on the 64 x 64 tile's own split
+    const bool t128ks = !h2 && !use_split && !tile_code && akc && bkc && ng == 1 && d.batch == 1 && d.split_k < 0 && d.rowmap_mod == 0 &&
                         d.act == ECHR_ACT_NONE && (d.beta == 0.f || d.beta == 1.f) && tiles128 >= 32 && tiles128 <= 128 && d.K >= 2048 && !deterministic_gemm();
     const bool t128 = !h2 && !use_split && d.K >= 64 && d.rowmap_mod == 0 &&
-                      ((tile_code == 't') || t128ks || (t128_on && !tile_code && tiles128 >= t128_min_tiles && d.K >= t128_min_k && (akc || bkc)));
+                      ((tile_code == 't') || t128ks || (!tile_code && tiles128 >= 200 && d.K >= 1024 && (akc || bkc)));
     if (t128) { BMs = 128; BNs = 128; }
     if (tile_code && tile_code != 't') {          // tuning override (tools/gemm_bench.py); never set in production
         const char e0 = tile_code;
@@ -1351,32 +1344,17 @@ static int gemm_impl(const echr_gemm_desc* ds, int ng, hipStream_t st) {
         }
         p.xcd_n = 8 / best; p.xr_m = (p.tiles_m + best - 1) / best; p.xr_n = (p.tiles_n + p.xcd_n - 1) / p.xcd_n;
         grid.x = 8 * p.xr_m * p.xr_n;
-        static const int wn_sel = getenv("ECHR_H2_WN") ? atoi(getenv("ECHR_H2_WN")) : 32;
         // measured (tools/h2_bench.py): 2 stages x 2 workgroups per CU beats 3-4 stages x 1 workgroup per CU on every c3 shape (270 vs 245
-        // TF/s at 4096^3): the second resident workgroup hides more latency than a deeper ring does; the deeper rings stay selectable
-        static const int ns_sel = getenv("ECHR_H2_STAGES") ? atoi(getenv("ECHR_H2_STAGES")) : 2;
-        constexpr int ST128 = 2 * H2_CHUNK + 2 * H2_SCALES, ST256 = 3 * H2_CHUNK + 3 * H2_SCALES;
+        // TF/s at 4096^3): the second resident workgroup hides more latency than a deeper ring does
+        constexpr int ST128 = 2 * H2_CHUNK + 2 * H2_SCALES;
         static bool attr_done = false;
         if (!attr_done) {          // LDS beyond 64 KB needs the opt-in attribute, once per kernel
             attr_done = true;
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_h2_kernel<128, 32, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * ST128);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_h2_kernel<128, 32, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, 3 * ST128);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_h2_kernel<128, 64, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * ST128);
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_h2_kernel<128, 32, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * ST128);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_h2_kernel<128, 64, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * ST128);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_h2_kernel<256, 64, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * ST256);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_h2_kernel<256, 64, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, 3 * ST256);
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_h2m16_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * ST128);
         }
         // the 16x16x32 form is faster wherever the epilogue is not a many-way atomic split (its stores are 64-byte row pieces)
-        static const int m16_sel = getenv("ECHR_H2_M16") ? atoi(getenv("ECHR_H2_M16")) : 1;
-        if (m16_sel && BMs == 128 && split < 8) hipLaunchKernelGGL((gemm_h2m16_kernel<2>), grid, dim3(512), 2 * ST128, st, p);
-        else if (BMs == 256 && ns_sel >= 3) hipLaunchKernelGGL((gemm_h2_kernel<256, 64, 3>), grid, dim3(512), 3 * ST256, st, p);
-        else if (BMs == 256) hipLaunchKernelGGL((gemm_h2_kernel<256, 64, 2>), grid, dim3(512), 2 * ST256, st, p);
-        else if (wn_sel == 64 && ns_sel >= 4) hipLaunchKernelGGL((gemm_h2_kernel<128, 64, 4>), grid, dim3(256), 4 * ST128, st, p);
-        else if (wn_sel == 64) hipLaunchKernelGGL((gemm_h2_kernel<128, 64, 2>), grid, dim3(256), 2 * ST128, st, p);
-        else if (ns_sel >= 4) hipLaunchKernelGGL((gemm_h2_kernel<128, 32, 4>), grid, dim3(512), 4 * ST128, st, p);
-        else if (ns_sel == 3) hipLaunchKernelGGL((gemm_h2_kernel<128, 32, 3>), grid, dim3(512), 3 * ST128, st, p);
+        if (BMs == 128 && split < 8) hipLaunchKernelGGL((gemm_h2m16_kernel<2>), grid, dim3(512), 2 * ST128, st, p);
         else hipLaunchKernelGGL((gemm_h2_kernel<128, 32, 2>), grid, dim3(512), 2 * ST128, st, p);
     }
     else if (t128) {
@@ -1393,9 +1371,7 @@ static int gemm_impl(const echr_gemm_desc* ds, int ng, hipStream_t st) {
         for (int gi = 0; gi < ng; ++gi) { if (!akc) va = va && ds[gi].M % 4 == 0; if (!bkc) vb = vb && ds[gi].N % 4 == 0; }
         p.vecA = va; p.vecB = vb;
         const size_t lds = 2 * T128_STAGE * sizeof(float);
-        static const int w8_sel = getenv("ECHR_T128_W8") ? atoi(getenv("ECHR_T128_W8")) : 1;
-        static const long w8_max = getenv("ECHR_T128_W8_MAX") ? atol(getenv("ECHR_T128_W8_MAX")) : 256;
-        if (w8_sel && akc && bkc && (long)grid.x * grid.z <= w8_max) {          // at most one workgroup per CU: eight waves per workgroup
+        if (akc && bkc && (long)grid.x * grid.z <= 256) {          // at most one workgroup per CU: eight waves per workgroup
             static bool attr_w8 = false;
             if (!attr_w8) { attr_w8 = true; (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f32_t128_kernel<true, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); }
             hipLaunchKernelGGL((gemm_f32_t128_kernel<true, true, true>), grid, dim3(512), lds, st, p);

@@ -737,14 +737,14 @@ constexpr int HWG = 96, HG1 = 64, HQ = 16;    // workgroups per half: gate, q (t
 // Which role a workgroup of the merged 256-workgroup launches plays.  Plain: blockIdx.x (workgroups 0..95 = half machine 0, 96..191 = half machine
 // 1, 192..255 = the two plain LSTM streams).  Workgroup b of a one-workgroup-per-CU grid runs on XCD b % 8 (round-robin dispatch: speed only, never
 // correctness), so in that order EVERY half machine -- and with it every handed-off operand -- is spread over all eight XCDs, each of whose L2s
-// fetches the operand across the fabric.  xcd_map = 1 (ECHR_PERSIST_XCD): a half machine's 96 workgroups are exactly the 3 x 32 CUs of three
+// fetches the operand across the fabric.  xcd_map = 1 (forward pair): a half machine's 96 workgroups are exactly the 3 x 32 CUs of three
 // XCDs (0-2, 3-5), the 64 LSTM-stream workgroups the two remaining ones: an operand is then fetched into three L2s (LSTM: two) instead of eight.
 __host__ __device__ __forceinline__ int persist_role_index(int bx, int xcd_map) {
     if (!xcd_map) return bx;
     const int x = bx & 7, s = bx >> 3;
     if (x >= 6) return 2 * HWG + (x - 6) * 32 + s;
     const int xr = x % 3;
-    // xcd_map = 2 (reverse pair, ECHR_PERSIST_XCD_BWD): the 64 product workgroups of a half machine (roles 16..79: four k-slices of 16 column tiles)
+    // xcd_map = 2 (reverse pair): the 64 product workgroups of a half machine (roles 16..79: four k-slices of 16 column tiles)
     // fill two XCDs, two k-slices each, so that each of them fetches only ITS half of d G1; the 16 gate-gradient and 16 attention-only roles share
     // the third
     if (xcd_map == 2) return (x / 3) * HWG + (xr == 0 ? (s < 16 ? s : 64 + s) : (xr == 1 ? 16 + s : 48 + s));
@@ -3273,8 +3273,7 @@ void persist_fwd_zero_range(const echr_dec_args* a, float* xws, float** ptr, lon
 static const float*& prebuilt_for() { static const float* p = nullptr; return p; }          // workspace whose images persist_fwd_prebuild queued last
 int persist_fwd_prebuild(const echr_dec_args* a, float* xws, hipStream_t st) {
     prebuilt_for() = nullptr;
-    static const bool on = [] { const char* e = getenv("ECHR_PERSIST_PREBUILD"); return !(e && e[0] == '0'); }();      // A/B switch
-    if (!on || !persist_fwd_eligible(a) || !config().persist_h2 || !config().persist_split || !config().persist_merge || !xws) return 0;
+    if (!persist_fwd_eligible(a) || !config().persist_h2 || !config().persist_split || !config().persist_merge || !xws) return 0;
     const PersistLayout2 L2 = persist_layout2(a->S);
     PersistK2 K2 = {};
     K2.D = a->D; K2.ld_att = a->E + a->D; K2.w_hh1 = a->w_hh[1]; K2.w_h2a = a->w_h2a; K2.w_att = a->w_ih[1] + a->E;
@@ -3304,8 +3303,7 @@ int persist_fwd(const echr_dec_args* a, const PersistFwdBufs& B, const DropCfg& 
     K.abort_word = h.abort_dev; K.host_flag = h.flag_dev;
     K.spin_limit = config().persist_spin_limit > 0 ? (u32)config().persist_spin_limit : SPIN_LIMIT; K.inject = (u32)config().persist_inject_timeout;
     K.dh = dh; K.dout = dout;
-    static const int nt_saved = [] { const char* e = getenv("ECHR_NT_SAVED"); return e ? atoi(e) : 1; }();      // A/B switch
-    K.nt_saved = nt_saved;
+    K.nt_saved = 1;
     K.stamps = nullptr;
     if (config().persist_stamps == 1) {
         if (!h.stamps && hipMalloc(&h.stamps, 4 * 256 * 16 * 8) != hipSuccess) h.stamps = nullptr;
@@ -3314,8 +3312,7 @@ int persist_fwd(const echr_dec_args* a, const PersistFwdBufs& B, const DropCfg& 
     PersistK2 K2;
     K2.pimg = nullptr;
     K2.nt_saved = 0;
-    static const int xcd_map = [] { const char* e = getenv("ECHR_PERSIST_XCD"); return e ? atoi(e) : 1; }();      // A/B switch (default on, round 6)
-    K2.xcd_map = (xcd_map && 2 * HWG + 2 * NS == 256 && HWG == 96) ? 1 : 0;
+    K2.xcd_map = (2 * HWG + 2 * NS == 256 && HWG == 96) ? 1 : 0;
     if (split) {
         K2.N = K.N; K2.A = K.A; K2.D = K.D; K2.S = K.S; K2.ld_att = K.ld_att;
         K2.w_hh1 = a->w_hh[1]; K2.w_h2a = a->w_h2a; K2.b_h2a = a->b_h2a; K2.w_att = K.w_att; K2.w_alpha = a->w_alpha;
@@ -3500,8 +3497,7 @@ static int persist_sample_group(const echr_dec_args* a, const PersistSampleBufs&
     PersistK2 K2;
     // the decoder keeps the plain placement: its 64 LSTM + logits workgroups stream 492 KB of logit weights each per step -- spread over eight
     // XCDs that is 3.9 MB per 4 MB L2, packed onto two it is 15.7 MB (measured: 256 events 2.93 vs 2.61 ms per decode; 64 and 1000 events equal)
-    static const int xcd_map_s = [] { const char* e = getenv("ECHR_PERSIST_XCD_SAMPLE"); return e ? atoi(e) : 0; }();      // A/B switch
-    K2.xcd_map = (xcd_map_s && 2 * HWG + 2 * NS == 256 && HWG == 96) ? 1 : 0;
+    K2.xcd_map = 0;
     K2.N = K.N; K2.A = K.A; K2.D = K.D; K2.S = K.S; K2.ld_att = K.ld_att;
     K2.w_hh1 = a->w_hh[1]; K2.w_h2a = a->w_h2a; K2.b_h2a = a->b_h2a; K2.w_att = K.w_att; K2.w_alpha = a->w_alpha;
     K2.PALL = B.PALL; K2.c3d = a->c3d; K2.ev_start = a->ev_start; K2.ev_len = a->ev_len; K2.c3d_bytes = (unsigned)((size_t)a->Tv * a->D * 4);
@@ -3546,10 +3542,7 @@ static int persist_sample_group(const echr_dec_args* a, const PersistSampleBufs&
     return 0;
 }
 
-bool persist_fwd_adds_evb0() {
-    static const bool off = [] { const char* e = getenv("ECHR_EVB0_FOLD"); return e && e[0] == '0'; }();      // A/B switch (tools/ab_env.sh)
-    return config().persist_h2 != 0 && !off;
-}
+bool persist_fwd_adds_evb0() { return config().persist_h2 != 0; }
 bool persist_bwd_eligible(const echr_dec_args* a) { return config().persist_bwd && !det_mode() && persist_shape_ok(a); }
 
 void persist_bwd_zero_range(const echr_dec_args* a, float* xws, float** ptr, long* count) {
@@ -3584,9 +3577,7 @@ int persist_bwd(const echr_dec_args* a, const PersistBwdBufs& B, const DropCfg& 
         if (!h.stamps && hipMalloc(&h.stamps, 4 * 256 * 16 * 8) != hipSuccess) h.stamps = nullptr;
         if (h.stamps && a->S <= 256) { K.stamps = h.stamps; h.stamps_S = a->S; (void)hipMemsetAsync(h.stamps, 0, 4 * 256 * 16 * 8, st); }
     }
-    static const int xcd_map = [] { const char* e = getenv("ECHR_PERSIST_XCD"); return e ? atoi(e) : 1; }();      // A/B switch (default on, round 6)
-    static const int xcd_bwd = [] { const char* e = getenv("ECHR_PERSIST_XCD_BWD"); return e ? atoi(e) : 2; }();      // A/B switch: 2 (default) = product roles on two XCDs, 1 = roles in order
-    K.xcd_map = (xcd_map && 2 * HWG + 2 * NS == 256 && HWG == 96) ? (xcd_bwd == 2 ? 2 : 1) : 0;
+    K.xcd_map = (2 * HWG + 2 * NS == 256 && HWG == 96) ? 2 : 0;          // 2: the product roles on two XCDs
     PersistB K2 = K;
     if (split) {
         K2.cnt = reinterpret_cast<u32*>(x2 + L2.cnt); K2.XDQ = x2 + L2.xdq; K2.XDA = x2 + L2.xda; K2.XDH = x2 + L2.xdh; K2.XDG = x2 + L2.xdg;

@@ -839,7 +839,7 @@ extern "C" int echr_sst_bwd(const echr_sst_args* a, const echr_sst_grads* g, con
     }
     // parameter gradients (sums over the T rows); h(t-1) pairs with dG(t): rows 1..T-1.  The two layers' products are independent small
     // GEMMs (20-25 us each, half a chip): layer 0's run on the library's helper stream beside layer 1's
-    hipStream_t s0 = config().tsrm_fork ? aux_fork(st) : nullptr;
+    hipStream_t s0 = aux_fork(st);
     const bool fork = s0 != nullptr;
     if (!fork) s0 = st;
     if (z && T > 1 && fork) {

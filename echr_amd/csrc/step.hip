@@ -16,12 +16,6 @@
 namespace echr {
 
 static inline long up64(long n) { return (n + 63) / 64 * 64; }
-// echr_dec_grads.async_tail of the step's backward: 2 (default) = only d event on the caller's stream, 1 = the tail alone (ECHR_ASYNC_LEVEL: A/B)
-static int async_level() {
-    static const int lv = [] { const char* e = getenv("ECHR_ASYNC_LEVEL"); return (e && e[0] == '1') ? 1 : 2; }();
-    return lv;
-}
-
 struct StepWs { long idx, ech, tsrm_ws, event, logp, dec_ws, dec_ws_bwd, g_event, g_ech, tsrm_ws_bwd, h0, g_h0, init_feats, init_dfeats, g_video, g_video_init,
                  rows, row_grad, total; };
 
@@ -81,10 +75,6 @@ __global__ __launch_bounds__(256) void stage_copy_kernel(const int32_t* __restri
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i < n) dst[i] = __builtin_nontemporal_load(src + i);
 }
-static bool stage_kernel_ok() {
-    static const bool on = [] { const char* e = getenv("ECHR_STAGE_KERNEL"); return !(e && e[0] == '0'); }();      // A/B switch
-    return on;
-}
 static int stage_indices(const int32_t* host, int32_t* dev, size_t bytes, hipStream_t st) {
     PinRing& r = ring();
     const int s = r.next;
@@ -103,14 +93,8 @@ static int stage_indices(const int32_t* host, int32_t* dev, size_t bytes, hipStr
     // hipMemcpyAsync takes the DMA-engine path for transfers of this size (~19 KB), whose start-up latency (tens of us) sat at the head of
     // every iteration in front of everything else
     const int n = (int)(bytes / 4);
-    if (stage_kernel_ok()) {
-        hipLaunchKernelGGL(stage_copy_kernel, dim3((n + 255) / 256), dim3(256), 0, st, static_cast<const int32_t*>(r.buf[s]), dev, n);
-        if (hipGetLastError() != hipSuccess) { set_error("train_step: index upload failed"); return -5; }
-    } else if (hipMemcpyAsync(dev, r.buf[s], bytes, hipMemcpyHostToDevice, st) != hipSuccess) {
-        (void)hipGetLastError();
-        set_error("train_step: index upload failed");
-        return -5;
-    }
+    hipLaunchKernelGGL(stage_copy_kernel, dim3((n + 255) / 256), dim3(256), 0, st, static_cast<const int32_t*>(r.buf[s]), dev, n);
+    if (hipGetLastError() != hipSuccess) { set_error("train_step: index upload failed"); return -5; }
     if (hipEventRecord(r.done[s], st) != hipSuccess) { (void)hipGetLastError(); set_error("train_step: index upload failed"); return -5; }
     r.used[s] = true;
     ring_last() = r.done[s];
@@ -230,18 +214,14 @@ extern "C" int echr_train_step_prepare(const echr_train_step_args* a, void* stre
     int32_t* idx = reinterpret_cast<int32_t*>(a->ws + L.idx);
     RC(stage_indices(a->host_index, idx, sizeof(int32_t) * step_index_count(a), st));
     echr_dec_args d = step_dec_args(a, L, idx);
-    // the event encoder's position branch reads indices and parameters only: it starts here too (ECHR_PREPARE_POS=0: with the second half, behind
-    // the proposal encoder's forward, where its ~70 us chain sits in front of the forward recurrence)
-    static const bool prep_pos = [] { const char* e = getenv("ECHR_PREPARE_POS"); return !(e && e[0] == '0'); }();      // A/B switch
-    if (prep_pos) {
-        echr_tsrm_args t = a->tsrm;
-        t.ech = a->ws + L.ech; t.ev_start = idx; t.ev_len = idx + a->dec.N; t.ws = a->ws + L.tsrm_ws; t.out = a->ws + L.event;
-        t.inference = 0; t.max_len = 0; t.max_span = 0;
-        const int rc = tsrm_position_early(&t, st);
-        if (rc) { (void)tsrm_position_early(nullptr, nullptr); (void)aux_join(st); return rc; }
-    }
-    const int rc = echr_decoder_fwd_prepare(&d, stream);
-    if (rc && prep_pos) { (void)tsrm_position_early(nullptr, nullptr); (void)aux_join(st); }
+    // the event encoder's position branch reads indices and parameters only: it starts here too, not with the second half behind the proposal
+    // encoder's forward, where its ~70 us chain would sit in front of the forward recurrence
+    echr_tsrm_args t = a->tsrm;
+    t.ech = a->ws + L.ech; t.ev_start = idx; t.ev_len = idx + a->dec.N; t.ws = a->ws + L.tsrm_ws; t.out = a->ws + L.event;
+    t.inference = 0; t.max_len = 0; t.max_span = 0;
+    int rc = tsrm_position_early(&t, st);
+    if (!rc) rc = echr_decoder_fwd_prepare(&d, stream);
+    if (rc) { (void)tsrm_position_early(nullptr, nullptr); (void)aux_join(st); }
     return rc;
 }
 
@@ -338,8 +318,7 @@ static int train_step_impl(const echr_train_step_args* a, void* stream, bool rw,
     // the event encoder's position branch (pair embedding -> fc1 -> fc2 gates: indices and parameters only) starts right behind the staging
     // CaptionGenerator.forward (:23-30): the decoder's event-independent part starts on the library's second stream and overlaps the event encoder
     if (a->overlap_encoder && !a->prepared) {
-        static const bool one_event = [] { const char* e = getenv("ECHR_ONE_FORK_EVENT"); return !(e && e[0] == '0'); }();      // A/B switch
-        if (one_event || ahead) fork_event(ring_last());          // both forks hang off the staging copy's event: no further record in front of event pooling
+        fork_event(ring_last());          // both forks hang off the staging copy's event: no further record in front of event pooling
         int rc2 = tsrm_position_early(&t, st);
         if (!rc2) rc2 = echr_decoder_fwd_prepare(&d, stream);
         fork_event(nullptr);
@@ -375,7 +354,7 @@ static int train_step_impl(const echr_train_step_args* a, void* stream, bool rw,
     g.g_loss = a->g_loss; g.nll_msum = a->loss + 1;
     g.g_h0 = a->w_init ? ws + L.g_h0 : nullptr;
     if (vh) g.g_video = ws + L.g_video;          // (the caller's own g_video, if any, is not filled then: the span is routed into g_tap)
-    g.ws_bwd = ws + L.dec_ws_bwd; g.zeroed = 1; g.phase = 0; g.async_tail = async_level();
+    g.ws_bwd = ws + L.dec_ws_bwd; g.zeroed = 1; g.phase = 0; g.async_tail = 2;          // only d event on the caller's stream
     if (!a->forward_only && a->overlap_encoder) RC(decoder_bwd_scratch_ahead(&d, &g));          // the backward's scratch fill: behind the prepare chain, not between the recurrences
     // forward (:30) + LanguageModelCriterion (misc/utils.py:66-75).  Training: log-softmax, criterion and its gradient are ONE pass over the
     // logits (d logits land in the backward workspace, the log-probs are never written; the loss is summed behind the backward pass, where
@@ -436,10 +415,7 @@ static int train_step_impl(const echr_train_step_args* a, void* stream, bool rw,
     echr_tsrm_grads tg = a->tsrm_g;
     // d ech (the gradient of the event encoder's INPUT rows) only matters when d tap_feats is asked for: c3d features are data
     tg.g_ech = (a->g_tap && De_tap > 0) ? ws + L.g_ech : nullptr; tg.g_out = ws + L.g_event; tg.ws_bwd = ws + L.tsrm_ws_bwd; tg.zeroed = 1;
-    tsrm_bwd_defer_join(true);          // (this call's workspace outlives the echr_stream_join below)
-    rc = echr_tsrm_bwd(&t, &tg, &a->drop, stream);
-    tsrm_bwd_defer_join(false);
-    RC(rc);
+    RC(echr_tsrm_bwd(&t, &tg, &a->drop, stream));
     if (a->g_tap && De_tap > 0) RC(echr_event_pool_gather_bwd(ws + L.g_ech, ind, a->g_tap, N, De_c3d, De_tap, stream));
     if (fused_nll) RC(decoder_fused_loss(&d, &g, a->loss, st, crit_w != nullptr));
     step_mark(3, st);

@@ -296,11 +296,7 @@ __global__ __launch_bounds__(64) void tsrm_colhead_bwd_kernel(const float* __res
     }
 }
 // the fused per-head kernels serve N <= 64 events with heads of 32 features: the reference's 512 / 16 (MA_attention_8_NEW.py:14-22)
-// (ECHR_TSRM_HEADS=0: the batched-GEMM form, for A/B runs)
-static bool head_fused_ok(int N, int Df, int Do, int G) {
-    static const bool off = [] { const char* e = getenv("ECHR_TSRM_HEADS"); return e && e[0] == '0'; }();
-    return !off && N <= HEAD_MAXN && Df == G * HEAD_DG && Do == G * HEAD_DG;
-}
+static bool head_fused_ok(int N, int Df, int Do, int G) { return N <= HEAD_MAXN && Df == G * HEAD_DG && Do == G * HEAD_DG; }
 
 static inline long rup(long x, long a) { return (x + a - 1) / a * a; }
 
@@ -714,8 +710,7 @@ static int position_branch(const echr_tsrm_args* a, const TsrmWs& w, bool do_pos
 static const void* g_pos_early_ws = nullptr;
 int echr::tsrm_position_early(const echr_tsrm_args* a, hipStream_t from) {
     g_pos_early_ws = nullptr;
-    static const bool off = [] { const char* e = getenv("ECHR_TSRM_EARLY"); return e && e[0] == '0'; }();      // A/B switch
-    if (off || !config().tsrm_fork || !a || a->inference || !a->ws || !a->ev_start || !a->ev_len || a->fst_mode == 4) return 0;
+    if (!a || a->inference || !a->ws || !a->ev_start || !a->ev_len || a->fst_mode == 4) return 0;
     const int N = a->N, Df = a->Df, G = a->G, NN = N * N;
     if (N <= 0 || Df <= 0 || G <= 0 || Df % 4 != 0) return 0;
     TsrmWs w = carve(N, a->Din, Df, a->Do, G, a->ws);
@@ -724,10 +719,9 @@ int echr::tsrm_position_early(const echr_tsrm_args* a, hipStream_t from) {
     if (!sp) return 0;
     const bool packed_pos = config().gemm_h2 && NN >= 4096 && posemb_packed_ok(N, Df);
     // the W_fc1 pack (parameters only) leaves the branch's chain: it runs on the caller's stream, which idles ~40 us waiting for the gates anyway
-    static const bool wfc1_here = [] { const char* e = getenv("ECHR_WFC1_ON_CALLER"); return !(e && e[0] == '0'); }();      // A/B switch
     static hipEvent_t ev_wfc1 = nullptr;
     hipEvent_t ready = nullptr;
-    if (wfc1_here && config().gemm_h2 && NN >= 1024) {
+    if (config().gemm_h2 && NN >= 1024) {
         if (!ev_wfc1 && hipEventCreateWithFlags(&ev_wfc1, echr::sync_event_flags()) != hipSuccess) { (void)hipGetLastError(); ev_wfc1 = nullptr; }
         if (ev_wfc1) {
             H2PackJob pj = pack_rows(a->w_fc1, Df, Df, Df, w.PK_WFC1);
@@ -767,7 +761,7 @@ static int tsrm_fwd_impl(const echr_tsrm_args* a, const echr_dropout* drop, void
     }
     // pairwise position features -> per-head gates (:39-41, :108-116): independent of the event features, so the branch runs on the
     // library's helper stream beside the embedding / query / key products (it needs the zero fill above: GATE accumulates)
-    hipStream_t sp = (config().tsrm_fork && !early && posit) ? aux_fork(st) : nullptr;
+    hipStream_t sp = (!early && posit) ? aux_fork(st) : nullptr;
     const bool fork = sp != nullptr || early;
     if (!sp) sp = st;
     long trc = 0, trl = 0;
@@ -861,8 +855,6 @@ extern "C" int echr_tsrm_bwd(const echr_tsrm_args* a, const echr_tsrm_grads* g, 
 // part 0: the whole backward.  echr_train_step's joint mode (step.hip) wants d ech -- the gradient the proposal encoder waits for -- as early
 // as possible: part 1 = the chain that leads to it (per-head attention backward, d X, d ech) on `stream`; part 2 = every parameter gradient
 // (position MLP, projections, embedding, biases), issued later on a helper stream passed as `stream`.  Parts need zeroed gradient buffers.
-static bool g_tsrm_nojoin = false;
-void echr::tsrm_bwd_defer_join(bool on) { g_tsrm_nojoin = on; }
 int echr::tsrm_bwd_parts(const echr_tsrm_args* a, const echr_tsrm_grads* g, const echr_dropout* drop, void* stream, int part) {
     RC(check(a, "tsrm_bwd"));
     ECHR_REQUIRE(g && g->g_out && g->ws_bwd, "tsrm_bwd: missing buffers");
@@ -907,37 +899,31 @@ int echr::tsrm_bwd_parts(const echr_tsrm_args* a, const echr_tsrm_grads* g, cons
     RC(check_launch("tsrm_softmax_bwd"));
     }
     }
-    // The position-MLP gradients (d W_fc2, d P1, d W_fc1: 4.3 GF over the N^2 pairs) depend on d GATE alone: they run on the decoder's
-    // prepare stream -- idle during a backward pass -- beside the query / key / embedding chain below (ten dependent small launches)
-    // (round 5: off by default.  With the token-embedding chain on the prepare stream behind the LSTM-layer stage (decoder.hip, ECHR_DXT_STREAM)
-    // the three streams of the backward tail end together when THIS stream keeps the position MLP: 1.48 vs 1.54 ms per iteration, same box)
-    static const bool fork2_off = [] { const char* e = getenv("ECHR_TSRM_FORK2"); return !(e && e[0] == '1'); }();      // A/B switch
-    hipStream_t sp = (config().tsrm_fork && !fork2_off && part == 0 && posit) ? aux2_fork(st) : nullptr;
-    const bool fork2 = sp != nullptr;
-    if (!fork2) sp = st;
-    // one streaming pass instead of two latency-bound fp32 products + two column sums (pair_mlp_bwd_kernel; ECHR_TSRM_PAIR_BWD=0: the products)
-    static const bool pm_off = [] { const char* e = getenv("ECHR_TSRM_PAIR_BWD"); return e && e[0] == '0'; }();
-    const bool pair_fused = posit && z && !pm_off && Df == 512 && G == 16 && ((reinterpret_cast<uintptr_t>(w.P1) | reinterpret_cast<uintptr_t>(a->w_fc2) | reinterpret_cast<uintptr_t>(b.DP1)) & 15) == 0;
+    // The position-MLP gradients (d W_fc2, d P1, d W_fc1: 4.3 GF over the N^2 pairs) stay on this stream, not on the decoder's prepare
+    // stream: with the token-embedding chain there behind the LSTM-layer stage (decoder.hip) the three streams of the backward tail end
+    // together when THIS stream keeps the position MLP: 1.48 vs 1.54 ms per iteration, same box
+    // one streaming pass instead of two latency-bound fp32 products + two column sums (pair_mlp_bwd_kernel); other shapes run the products
+    const bool pair_fused = posit && z && Df == 512 && G == 16 && ((reinterpret_cast<uintptr_t>(w.P1) | reinterpret_cast<uintptr_t>(a->w_fc2) | reinterpret_cast<uintptr_t>(b.DP1)) & 15) == 0;
     if (rest_part && posit) {
         // position MLP (depends on d GATE only)
         if (pair_fused) {
-            hipLaunchKernelGGL(pair_mlp_bwd_kernel, dim3((NN + PM_ROWS - 1) / PM_ROWS), dim3(256), 0, sp, b.DGATE, w.P1, a->w_fc2, b.DP1, b.PMP, NN);
+            hipLaunchKernelGGL(pair_mlp_bwd_kernel, dim3((NN + PM_ROWS - 1) / PM_ROWS), dim3(256), 0, st, b.DGATE, w.P1, a->w_fc2, b.DP1, b.PMP, NN);
             RC(check_launch("pair_mlp_bwd"));
         } else {
         d = desc_tn(b.DGATE, G, w.P1, Df, g->g_w_fc2, Df, G, Df, NN); d.beta = zb; d.split_k = -1;
-        RC(gemm(d, sp));
+        RC(gemm(d, st));
         d = desc_nn(b.DGATE, G, a->w_fc2, Df, b.DP1, Df, NN, Df, G); d.act = ECHR_ACT_MUL_DTANH; d.aux = w.P1; d.ld_aux = Df;
-        RC(gemm(d, sp));
+        RC(gemm(d, st));
         }
         if (config().gemm_h2 && NN >= 1024) {
             H2PackJob pj[2] = {pack_cols(b.DP1, Df, Df, NN, b.PK_DP1T), pack_cols(w.POS, Df, Df, NN, b.PK_POST)};
-            RC(h2_pack_multi(pj, 2, sp));
+            RC(h2_pack_multi(pj, 2, st));
             d = desc_h2(b.PK_DP1T, b.PK_POST, g->g_w_fc1, Df, Df, Df, NN);
         } else {
             d = desc_tn(b.DP1, Df, w.POS, Df, g->g_w_fc1, Df, Df, Df, NN); d.split_k = -1;
         }
         d.beta = zb;
-        RC(gemm(d, sp));
+        RC(gemm(d, st));
     }
     // dQ_g = scale * dAFF_g . K_g ; dK_g = scale * dAFF_g^T . Q_g
     if (!heads && main_part) {
@@ -975,23 +961,7 @@ int echr::tsrm_bwd_parts(const echr_tsrm_args* a, const echr_tsrm_grads* g, cons
     // event embedding
     d = desc_tn(b.DX, Df, a->ech, Din, g->g_w_emb, Din, Df, Din, N); d.beta = zb; d.split_k = -1;
     RC(gemm(d, st));
-    // bias gradients: all six column sums in one launch when the gradient buffers accumulate.  With the position branch forked onto the
-    // prepare stream its two sums (d b_fc2, d b_fc1: over the N^2 pair rows it just produced) run THERE, behind the products, and this stream
-    // does not join: nothing later on it reads the branch's outputs, and echr_stream_join / the next library call wait for the prepare
-    // stream's event -- the caller's chain then ends with its own last product instead of with the branch's (it used to: join, six sums, d ech).
-    // Only for callers that keep the workspaces alive until that join (echr_train_step: tsrm_bwd_defer_join); the plain entry joins here
-    if (z && fork2 && g_tsrm_nojoin) {
-        const ColsumJob cp[2] = {{b.DGATE, G, NN, G, g->g_b_fc2, nullptr, nullptr}, {b.DP1, Df, NN, Df, g->g_b_fc1, nullptr, nullptr}};
-        const int nblk = (NN + PM_ROWS - 1) / PM_ROWS;
-        const ColsumJob cq[3] = {{b.PMP, PM_LD, nblk, G * Df, g->g_w_fc2, nullptr, nullptr}, {b.PMP + G * Df, PM_LD, nblk, Df, g->g_b_fc1, nullptr, nullptr},
-                                 {b.PMP + G * Df + Df, PM_LD, nblk, G, g->g_b_fc2, nullptr, nullptr}};
-        if (pair_fused) RC(colsum_multi(cq, 3, sp)); else RC(colsum_multi(cp, 2, sp));
-        RC(aux2_publish());
-        const ColsumJob cj[4] = {{g->g_out, Do, N, Do, g->g_b_out, nullptr, nullptr}, {b.DQ, Df, N, Df, g->g_b_q, nullptr, nullptr},
-                                 {b.DK, Df, N, Df, g->g_b_k, nullptr, nullptr},        {b.DX, Df, N, Df, g->g_b_emb, nullptr, nullptr}};
-        RC(colsum_multi(cj, 4, st));
-    } else {
-    if (fork2) RC(aux2_join(st));
+    // bias gradients: all six column sums in one launch when the gradient buffers accumulate
     if (z) {
         const ColsumJob cj[6] = {{g->g_out, Do, N, Do, g->g_b_out, nullptr, nullptr}, {b.DQ, Df, N, Df, g->g_b_q, nullptr, nullptr},
                                  {b.DK, Df, N, Df, g->g_b_k, nullptr, nullptr},        {b.DX, Df, N, Df, g->g_b_emb, nullptr, nullptr},
@@ -1010,7 +980,6 @@ int echr::tsrm_bwd_parts(const echr_tsrm_args* a, const echr_tsrm_grads* g, cons
         RC(colsum(b.DP1, Df, NN, Df, g->g_b_fc1, false, st));
         }
         RC(colsum(b.DX, Df, N, Df, g->g_b_emb, false, st));
-    }
     }
     if (g->g_ech && part == 0) {
         d = desc_nn(b.DX, Df, a->w_emb, Din, g->g_ech, Din, N, Din, Df); d.split_k = -1; d.beta = 1.f;

@@ -11,6 +11,7 @@ accumulation, other consumers of the log-probs, joint training of the proposal e
 """
 import ctypes as C
 import math
+import os
 
 import numpy as np
 import torch
@@ -19,10 +20,6 @@ from . import _lib as L
 from . import functional as EF
 from .models.OldModel_NEW import n_decoder_steps
 from .optim import ClampAdam
-
-
-import os
-MASKED_ROWS = [os.environ.get('ECHR_MASKED_ROWS', '1') != '0']          # late-fusion stage on the rows with a non-zero criterion mask only
 
 
 class FusedTrainStep(object):
@@ -287,7 +284,7 @@ class FusedTrainStep(object):
         # Criterion inputs.  On the host (numpy / CPU tensors, as the reference's loader hands them over, train.py:273-279): they travel with
         # the index vectors, and the rows whose mask is non-zero are listed -- the masked-out label positions behind a caption's end cannot
         # reach the loss (misc/utils.py:66-75 multiplies by the mask), so training forms logits, d logits and the logit-layer products on the
-        # active rows only (ECHR_MASKED_ROWS=0: all rows).  On the device: used in place, all rows.
+        # active rows only.  On the device: used in place, all rows.
         host_nll = not (isinstance(targets, torch.Tensor) and targets.is_cuda) and not (isinstance(masks, torch.Tensor) and masks.is_cuda)
         if weights is not None and not host_nll:
             raise ValueError('criterion weights travel with host targets / masks')
@@ -297,7 +294,7 @@ class FusedTrainStep(object):
             mk_h = np.ascontiguousarray(np.asarray(masks)[:, :S], dtype=np.float32)
             if tg_h.shape != (N, S) or mk_h.shape != (N, S):
                 raise ValueError('targets / masks must be [N, >= S] (got %s, %s)' % (tuple(np.asarray(targets).shape), tuple(np.asarray(masks).shape)))
-            if MASKED_ROWS[0] and not forward_only:
+            if not forward_only:
                 # active = up to the LAST non-zero mask entry of each caption: a position behind it reaches neither the loss nor, through
                 # the recurrence, any earlier gradient, so every gradient of the reverse recurrence is exactly zero there and the
                 # weight-gradient products skip those rows as well (a zero inside a caption stays listed: later steps feed back into it)

@@ -666,10 +666,9 @@ int echr_prof_read(int kind, double* ms, double* flops, double* bytes, int64_t* 
 /* total ms of `n` back-to-back event pairs around nothing: the fixed per-launch cost of event timing, which bench.py subtracts */
 int echr_prof_event_overhead(double* ms, int64_t* n);
 
-/* Runtime switches (defaults from the environment variables ECHR_GEMM_H2=1, ECHR_GEMM_BF16X3=1, ECHR_OVERLAP=0, ECHR_ATT_SLOTS=2):
+/* Runtime switches (defaults from the environment variables ECHR_GEMM_H2=1, ECHR_GEMM_BF16X3=1, ECHR_ATT_SLOTS=2); any other key returns -22:
  *   "gemm_h2"     0/1  run the decoder's large projections on h2-packed operands (two block-scaled fp16 planes, fp32-grade) or not
  *   "gemm_bf16x3" 0/1  (gemm_h2 = 0) use the three-plane bf16 split product for the large projections or the native fp32 MFMA
- *   "overlap"     0/1  run recurrence-independent GEMMs on a second HIP stream
  *   "att_slots"   2/4/8 attention slots per wave
  *   "persist"     0/1  (default 1, ECHR_PERSIST) run the teacher-forced recurrence as a pair of persistent launches (csrc/persist.hip)
  *                      when the shape allows (N <= 64, A <= 129, H = Ha = 512, D <= 512, a full 256-CU device), else one launch per phase
@@ -681,8 +680,6 @@ int echr_prof_event_overhead(double* ms, int64_t* n);
  *                      of 256 workgroups on the caller's stream (0: two concurrent launches on two streams; needs two free hardware queues)
  *   "persist_kgroups" 0/1 (default 1, ECHR_PERSIST_KGROUPS) reverse LSTM role with the contraction split over 4 workgroup groups (128 KB of
  *                      ingest per workgroup and step plus a small partial-tile exchange) instead of 512 KB per workgroup
- *   "tsrm_fork"   0/1  (default 1, ECHR_TSRM_FORK) echr_tsrm_fwd runs its position branch (pair embedding -> fc1 -> fc2 gates) on the
- *                      library's helper stream beside the event-embedding / query / key products
  *   "persist_coop" 0/1  (default 0, ECHR_PERSIST_COOP) launch the persistent pairs with hipLaunchCooperativeKernel: the dispatch starts only
  *                      when all 256 workgroups can be co-resident, whatever else holds CUs (RCCL kernels of a data-parallel run, another
  *                      process on the device).  echr_amd.parallel / bench.py switch it on when the world size is > 1
@@ -703,17 +700,14 @@ int echr_prof_event_overhead(double* ms, int64_t* n);
  *   "pair_tables" 0/1   (default 1, ECHR_PAIR_TABLES) inference over >= 16384 event pairs with known index bounds: fc1 tabulated over the distinct keys
  *   "gemm_skinny" 0/1   (default 1, ECHR_GEMM_SKINNY) the event encoder's fc2 over >= 4096 event pairs (512 -> <= 16 columns) as a streaming
  *                      16-row-tile kernel instead of the general tiles
- *   "embed_fused" 0/1   (default 0, ECHR_EMBED_FUSED) token-embedding gradient through echr_gemm_desc.row_index instead of d XT + scatter pass
- *                      (measured slower: atomics of all k-slices contend on the <bos> / frequent-word rows)
  *   "deterministic" 0/1 (default 0, ECHR_DETERMINISTIC) fixed-order accumulation: every order-dependent fp32 sum of a training iteration is replaced
  *                      by a fixed-order one -- products run one k loop per output tile (no split-K atomics; grouped problems that share an output run
- *                      one after the other), the recurrences run launch-per-phase with the accumulator products as one k loop per tile (the
+ *                      one after the other), the recurrences run launch-per-phase with the accumulator products' k-slices folded in slice order (the
  *                      persistent kernels' exchange adds are atomics: not used), column sums have one owner workgroup per 64 columns, the token
  *                      scatter-add and the anchor-row scatter have one owner per destination row and add in source order, the attention backward
  *                      writes per-chunk / per-(event, position) / per-workgroup slabs that fold launches sum in index order (scratch owned by the
  *                      library, grown on demand).  Two runs on the same inputs, parameters and dropout seed then agree bit for bit in loss and
  *                      every gradient (the reference's CPU path is run-to-run deterministic at a fixed thread count); cost: see DESIGN.md section 4h
- *   "tail_early"  0/1   (default 0, ECHR_TAIL_EARLY) fork the asynchronous decoder-backward tail ahead of the LSTM-layer gradient stage
  *   "persist_stamps" 0/1/2 diagnostic phase stamps of the forward (1) / reverse (2) pair, see echr_persist_read_stamps
  *   "gemm_tile", "gemm_split"  tuning overrides of the GEMM tile / split-K heuristics (0 = heuristics; tools/gemm_bench.py only) */
 int echr_config_set(const char* key, int32_t value);

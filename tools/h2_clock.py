@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """30 launches of the h2 product on the logits shape in one ablation mode (argv[1]: 0 = whole kernel, 64 = loads only, 128 = compute only), for
-a counter run: GRBM_GUI_ACTIVE / duration = the clock the chip held during the launch (tools/r6_h2_clock.sh)."""
+a counter run (rocprofv3 --pmc GRBM_GUI_ACTIVE): GRBM_GUI_ACTIVE / duration = the clock the chip held during the launch."""
 import ctypes as C
 import os
 import sys
