@@ -125,6 +125,7 @@ SYMBOLS = [
     ('echr_abi_sizeof', i64, [C.c_char_p]),
     ('echr_last_error', C.c_char_p, []),
     ('echr_check_async', i32, []),
+    ('echr_persist_softmax_branch', i32, []),
     ('echr_async_skipped_updates', i64, []),
     ('echr_gemm_f32', i32, [C.POINTER(GemmDesc), C.c_void_p]),
     ('echr_event_pool_gather_fwd', i32, [c_f, c_f, c_f, c_f, c_f, c_f, i32, i32, i32, C.c_void_p]),

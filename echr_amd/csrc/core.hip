@@ -1314,6 +1314,7 @@ extern "C" int echr_prof_event_overhead(double* ms, int64_t* n) {
 }
 
 extern "C" int echr_check_async(void) { return persist_check_async(); }
+extern "C" int echr_persist_softmax_branch(void) { return persist_softmax_branch(); }
 extern "C" int64_t echr_async_skipped_updates(void) { return (int64_t)persist_take_skipped_updates(); }
 
 extern "C" int echr_persist_read_stamps(uint64_t* dst, int32_t max_entries) {

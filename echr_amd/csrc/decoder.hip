@@ -379,7 +379,7 @@ __global__ __launch_bounds__(256) void att_post_kernel(const float* __restrict__
                                                        const float* __restrict__ alpha, const float* __restrict__ DSC,
                                                        const int* __restrict__ ev_start, const int* __restrict__ ev_len,
                                                        float* __restrict__ DPALL, float* __restrict__ g_alpha,
-                                                       float* __restrict__ g_balpha, int S, int N, int A, int Ha, int disjoint, int alpha_rows) {
+                                                       float* __restrict__ g_balpha, int S, int N, int A, int Ha, int disjoint, int alpha_rows, unsigned* __restrict__ dom) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     float* sqt = sm;                   // [TT][Ha]
     float* sds = sqt + TT * Ha;        // [TT][8] dscore tile
@@ -393,12 +393,16 @@ __global__ __launch_bounds__(256) void att_post_kernel(const float* __restrict__
     float4 p[PSLOTS][R], a4[R], dal[R];
     // 1 - tanh^2(p + q) = 4 r (1 - r), tanh(p + q) = 1 - 2 r with r = 1 / (e^{2p} e^{2q} + 1): e^{2p} once per row, e^{2q} once per staged q
     // element -- one fma + rcp per (slot, feature, timestep) instead of an exp + rcp (arguments clamped to +-43: never inf * 0)
+    // The form is tanh(p + q) only while |p| <= 43 and |q| <= 43: an argument outside is reported through `dom` (the host-mapped flag block,
+    // echr_internal.h DOMAIN_WORD_P / DOMAIN_WORD_Q: largest magnitude seen; -EDOM at the next library call), never silently clamped
+    float pmax = 0.f, qmax = 0.f;
 #pragma unroll
     for (int i = 0; i < PSLOTS; ++i) {
         const int a = min(a0 + wave * PSLOTS + i, len - 1);
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             const float4 pv = *reinterpret_cast<const float4*>(PALL + (row0 + a) * Ha + min(lane * 4 + r * 256, Ha - 4));
+            pmax = fmaxf(fmaxf(pmax, fmaxf(fabsf(pv.x), fabsf(pv.y))), fmaxf(fabsf(pv.z), fabsf(pv.w)));
             p[i][r] = make_float4(__expf(2.f * fminf(fmaxf(pv.x, -43.f), 43.f)), __expf(2.f * fminf(fmaxf(pv.y, -43.f), 43.f)),
                                   __expf(2.f * fminf(fmaxf(pv.z, -43.f), 43.f)), __expf(2.f * fminf(fmaxf(pv.w, -43.f), 43.f)));
         }
@@ -418,16 +422,22 @@ __global__ __launch_bounds__(256) void att_post_kernel(const float* __restrict__
     for (int t0 = 0; t0 < S; t0 += TT) {
         const int nt = min(TT, S - t0);
         __syncthreads();
-        for (int idx = threadIdx.x; idx < nt * (Ha >> 2); idx += 256) {
-            const int tt = idx / (Ha >> 2), j4 = idx % (Ha >> 2);
-            const float4 qv = *reinterpret_cast<const float4*>(QS + ((long)(t0 + tt) * N + n) * Ha + 4 * j4);
-            *reinterpret_cast<float4*>(sqt + tt * Ha + 4 * j4) =
-                make_float4(__expf(2.f * fminf(fmaxf(qv.x, -43.f), 43.f)), __expf(2.f * fminf(fmaxf(qv.y, -43.f), 43.f)),
-                            __expf(2.f * fminf(fmaxf(qv.z, -43.f), 43.f)), __expf(2.f * fminf(fmaxf(qv.w, -43.f), 43.f)));
-        }
         for (int idx = threadIdx.x; idx < nt * 8; idx += 256) {
             const int tt = idx >> 3, i = idx & 7;
             sds[idx] = (a0 + i < len) ? DSC[((long)(t0 + tt) * N + n) * A + a0 + i] : 0.f;
+        }
+        __syncthreads();
+        for (int idx = threadIdx.x; idx < nt * (Ha >> 2); idx += 256) {
+            const int tt = idx / (Ha >> 2), j4 = idx % (Ha >> 2);
+            const float4 qv = *reinterpret_cast<const float4*>(QS + ((long)(t0 + tt) * N + n) * Ha + 4 * j4);
+            // (domain check on the rows that are consumed only: a position behind a caption's end has d score = 0 for every slot, is skipped below,
+            // and its q row may never have been written)
+            const float4 d0 = *reinterpret_cast<const float4*>(sds + tt * 8), d1 = *reinterpret_cast<const float4*>(sds + tt * 8 + 4);
+            if (d0.x != 0.f || d0.y != 0.f || d0.z != 0.f || d0.w != 0.f || d1.x != 0.f || d1.y != 0.f || d1.z != 0.f || d1.w != 0.f)
+                qmax = fmaxf(fmaxf(qmax, fmaxf(fabsf(qv.x), fabsf(qv.y))), fmaxf(fabsf(qv.z), fabsf(qv.w)));
+            *reinterpret_cast<float4*>(sqt + tt * Ha + 4 * j4) =
+                make_float4(__expf(2.f * fminf(fmaxf(qv.x, -43.f), 43.f)), __expf(2.f * fminf(fmaxf(qv.y, -43.f), 43.f)),
+                            __expf(2.f * fminf(fmaxf(qv.z, -43.f), 43.f)), __expf(2.f * fminf(fmaxf(qv.w, -43.f), 43.f)));
         }
         __syncthreads();
         for (int tt = 0; tt < nt; ++tt) {
@@ -449,6 +459,10 @@ __global__ __launch_bounds__(256) void att_post_kernel(const float* __restrict__
                 }
             }
         }
+    }
+    if (dom) {
+        if (pmax > 43.f) __hip_atomic_store(dom + DOMAIN_WORD_P, __float_as_uint(pmax), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        if (qmax > 43.f) __hip_atomic_store(dom + DOMAIN_WORD_Q, __float_as_uint(qmax), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
 #pragma unroll
     for (int i = 0; i < PSLOTS; ++i) {
@@ -572,7 +586,7 @@ static int launch_att_post(const AttDims& d, const float* PALL, const float* QS,
     const dim3 grid(d.N, (d.A + 7) / 8), blk(256);
     const size_t sm = ((size_t)TT * d.Ha + TT * 8 + 4 * d.Ha) * sizeof(float);
     switch ((d.Ha + 255) / 256) {
-#define ECHR_CASE(R) case R: hipLaunchKernelGGL((att_post_kernel<R>), grid, blk, sm, st, PALL, QS, alpha, DSC, ev_start, ev_len, DPALL, g_alpha, g_balpha, S, d.N, d.A, d.Ha, disjoint, alpha_rows); break;
+#define ECHR_CASE(R) case R: hipLaunchKernelGGL((att_post_kernel<R>), grid, blk, sm, st, PALL, QS, alpha, DSC, ev_start, ev_len, DPALL, g_alpha, g_balpha, S, d.N, d.A, d.Ha, disjoint, alpha_rows, persist_host_flag()); break;
         ECHR_CASE(1) ECHR_CASE(2) ECHR_CASE(3) ECHR_CASE(4)
 #undef ECHR_CASE
         default: set_error("att_post: Ha too large"); return -22;

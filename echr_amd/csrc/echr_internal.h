@@ -73,6 +73,11 @@ const unsigned* persist_abort_word();
 // word of the 256-byte abort block in which the optimiser kernels count the updates they skipped while the abort word was set
 constexpr int ABORT_SKIPPED_WORD = 16;
 unsigned* persist_host_flag();          // device view of the host-mapped flag persist_check_async reads (nullptr when unavailable)
+// words of that host-mapped block (16 x 32 bit) beside word 0, the abort code: the largest |p| / |q| an attention kernel met outside the domain of
+// its factored tanh (float bits, 0 = none; persist_check_async reports them as -EDOM), and the soft-max branch the last persistent forward
+// launch took (1: no shift, 2: max exchange; read-only diagnostic, echr_persist_softmax_branch)
+constexpr int DOMAIN_WORD_P = 1, DOMAIN_WORD_Q = 2, BRANCH_WORD = 3;
+int persist_softmax_branch();
 // the library's helper stream outside a backward pass (the one the asynchronous decoder-backward tail uses): `aux_fork` makes it continue
 // after everything queued on `from` and returns it, `aux_join` makes `to` wait for what was queued on it since
 // Flags of every event the library uses to order its own streams on ONE device: no timing, and no system-scope fence -- the default event

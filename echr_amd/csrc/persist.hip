@@ -24,6 +24,8 @@
 // Products are exact fp32 (v_mfma_f32_16x16x4_f32).  Saved activations (GATES, CS, HS, OUTD, QS, WT, ATT) are written in the layouts
 // the backward pass and the batched projections expect, off the critical path (after the hand-off is published).
 #include <atomic>
+#include <cstdio>
+#include <cstring>
 #include <functional>
 #include <mutex>
 #include "echr_common.h"
@@ -114,6 +116,15 @@ __device__ __forceinline__ float4 ld16_plain(__amdgpu_buffer_rsrc_t r, u32 off) 
 __device__ __forceinline__ void st16_sc1(__amdgpu_buffer_rsrc_t r, u32 off, float4 v) {
     u32x4 u = {__float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z), __float_as_uint(v.w)};
     __builtin_amdgcn_raw_buffer_store_b128(u, r, off, 0, 16);
+}
+// Domain of the factored tanh (below): tanh(p + q) = 1 - 2 / (e^{2p} e^{2q} + 1) is formed from p and q SEPARATELY, each clamped to +-TANH_ARG_MAX, so
+// it equals tanh(p + q) only while |p| <= 43 and |q| <= 43 (p = 60, q = -50 would give e^{86} e^{-86} = 1, tanh = 0 instead of tanh(10) = 1).  An argument
+// outside is REPORTED, not hidden: the launch runs to its end, the largest magnitude seen goes to word `word` of the host-mapped flag block
+// (DOMAIN_WORD_P: p = ctx2att(clip) rows; DOMAIN_WORD_Q: q = h2att(h1)) and persist_check_async returns -EDOM at the next library call.
+constexpr float TANH_ARG_MAX = 43.f;
+__device__ __forceinline__ float absmax4(float m, const float4 v) { return fmaxf(fmaxf(m, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w))); }
+__device__ __forceinline__ void domain_report(u32* host_flag, int word, float m) {
+    if (m > TANH_ARG_MAX) __hip_atomic_store(host_flag + word, __float_as_uint(m), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 __device__ __forceinline__ void st4_sc1(float* p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, ECHR_AGENT); }
 __device__ __forceinline__ float ld4_sc1(const float* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, ECHR_AGENT); }
@@ -444,7 +455,9 @@ __global__ __launch_bounds__(256, 1) void dec_persist_att_kernel(PersistK P) {
         __syncthreads();
         use_max = (sx[0] + sx[1] + sx[2] + sx[3]) > ALPHA_SAFE;
         __syncthreads();
+        if (b == 0 && tid == 0) __hip_atomic_store(P.host_flag + BRANCH_WORD, use_max ? 2u : 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
+    float pmax = 0.f;          // largest |p| among this lane's operands (domain_report)
     if (att_live) {
         alen = P.ev_len[an];
         const long row0 = P.ev_start[an];
@@ -459,6 +472,7 @@ __global__ __launch_bounds__(256, 1) void dec_persist_att_kernel(PersistK P) {
                 // tanh(p + q) = 1 - 2 / (e^{2p} e^{2q} + 1): e^{2p} is constant over the S timesteps and kept INSTEAD of p (arguments
                 // clamped to +-43 so that neither factor is 0 or inf: the product then saturates to 0 / inf -> tanh = -1 / +1, never NaN)
                 const float4 pv = *reinterpret_cast<const float4*>(pr + 4 * h);
+                pmax = absmax4(pmax, pv);
                 Pr[i][h] = make_float4(__expf(2.f * fminf(fmaxf(pv.x, -43.f), 43.f)), __expf(2.f * fminf(fmaxf(pv.y, -43.f), 43.f)),
                                        __expf(2.f * fminf(fmaxf(pv.z, -43.f), 43.f)), __expf(2.f * fminf(fmaxf(pv.w, -43.f), 43.f)));
                 const int d = 32 * lr + 4 * h;
@@ -473,6 +487,7 @@ __global__ __launch_bounds__(256, 1) void dec_persist_att_kernel(PersistK P) {
 #pragma unroll
             for (int h = 0; h < 8; ++h) Pr[i][h] = Cr[i][h] = make_float4(0.f, 0.f, 0.f, 0.f);
     }
+    domain_report(P.host_flag, DOMAIN_WORD_P, pmax);
     __syncthreads();
 
     const int gn = tid >> 2, gu = tid & 3;          // gate-math ownership: thread (event n, unit u)
@@ -520,6 +535,7 @@ __global__ __launch_bounds__(256, 1) void dec_persist_att_kernel(PersistK P) {
             if (srole >= 0) STAMP(srole, 3);
             publish(cnt(C_Q, t));
             if (srole >= 0) STAMP(srole, 4);
+            if (gn < N) domain_report(P.host_flag, DOMAIN_WORD_Q, absmax4(0.f, qv));          // (behind the hand-off, like the saved q below)
             if (gn < N) *reinterpret_cast<float4*>(P.QS + ((long)t * N + gn) * PH + 16 * cq + 4 * gu) = qv;
         }
         // ---- attention: scores, (split) softmax, context partial ----
@@ -981,6 +997,7 @@ __device__ __forceinline__ void dec_persist_att2_body(const PersistK2& P, const 
         __syncthreads();
         use_max = (sx[0] + sx[1] + sx[2] + sx[3]) > ALPHA_SAFE;
         __syncthreads();
+        if (b == 0 && tid == 0) __hip_atomic_store(P.host_flag + BRANCH_WORD, use_max ? 2u : 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
     auto sst_ = [&](int i) { if (P.stamps && b == 0 && tid == 0) P.stamps[(i >> 1) * 16 + 12 + (i & 1)] = __builtin_amdgcn_s_memrealtime(); };
     sst_(0);
@@ -1056,13 +1073,16 @@ __device__ __forceinline__ void dec_persist_att2_body(const PersistK2& P, const 
                            __expf(2.f * fminf(fmaxf(pv.z, -43.f), 43.f)), __expf(2.f * fminf(fmaxf(pv.w, -43.f), 43.f)));
     };
     if (att_live) {
+        float pmax = 0.f;
 #pragma unroll
         for (int i = 0; i < PSG; ++i)
 #pragma unroll
             for (int h = 0; h < 8; ++h) {
+                pmax = absmax4(pmax, Pr[i][h]);
                 Pr[i][h] = exp2x(Pr[i][h]);
-                if constexpr (BIG) Pr2[i][h] = exp2x(Pr2[i][h]);
+                if constexpr (BIG) { pmax = absmax4(pmax, Pr2[i][h]); Pr2[i][h] = exp2x(Pr2[i][h]); }
             }
+        domain_report(P.host_flag, DOMAIN_WORD_P, pmax);
     }
     if (H2 && att_live) {
         // bound on |context| of this event = max |C3D| over its slots: one atomic max per workgroup (non-negative floats order like uints);
@@ -1185,6 +1205,7 @@ __device__ __forceinline__ void dec_persist_att2_body(const PersistK2& P, const 
             if (srole >= 0) STAMP(srole, 3);
             publish(cnt(C_Q, t));
             if (srole >= 0) STAMP(srole, 4);
+            if (gn < N) domain_report(P.host_flag, DOMAIN_WORD_Q, absmax4(0.f, qv));          // (behind the hand-off, like the saved q below)
             if (!SAMP && gn < N) *reinterpret_cast<float4*>(P.QS + ((long)t * N + gn) * PH + 32 * cq + c4) = qv;
         }
         // ---- attention: scores, (split) softmax, context partial ----
@@ -2513,6 +2534,7 @@ __global__ __launch_bounds__(256, 1) void dec_persist_att_bwd_kernel(PersistB P)
     int alen = 0;
     float4 Pr[PSG][8], Cr[PSG][8];
     for (int j = tid; j < PH; j += 256) sal[j] = P.w_alpha[j];
+    float pmax = 0.f;          // largest |p| among this lane's operands (domain_report)
     if (att_live) {
         alen = P.ev_len[an];
         const long row0 = P.ev_start[an];
@@ -2525,6 +2547,7 @@ __global__ __launch_bounds__(256, 1) void dec_persist_att_bwd_kernel(PersistB P)
 #pragma unroll
             for (int h = 0; h < 8; ++h) {
                 const float4 pv = *reinterpret_cast<const float4*>(pr + 4 * h);
+                pmax = absmax4(pmax, pv);
                 Pr[i][h] = make_float4(__expf(2.f * fminf(fmaxf(pv.x, -43.f), 43.f)), __expf(2.f * fminf(fmaxf(pv.y, -43.f), 43.f)),
                                        __expf(2.f * fminf(fmaxf(pv.z, -43.f), 43.f)), __expf(2.f * fminf(fmaxf(pv.w, -43.f), 43.f)));
                 const int d = 32 * lr + 4 * h;
@@ -2539,6 +2562,7 @@ __global__ __launch_bounds__(256, 1) void dec_persist_att_bwd_kernel(PersistB P)
 #pragma unroll
             for (int h = 0; h < 8; ++h) Pr[i][h] = Cr[i][h] = make_float4(0.f, 0.f, 0.f, 0.f);
     }
+    domain_report(P.host_flag, DOMAIN_WORD_P, pmax);
     __syncthreads();
 
     const int gn = tid >> 2, gq = tid & 3, u0 = 16 * b + 4 * gq;        // gate-gradient ownership (GD role)
@@ -2813,6 +2837,7 @@ __device__ __forceinline__ void dec_persist_att_bwd2_body(const PersistB& P, con
     if (att_live) {
         alen = P.ev_len[an];
         row0 = P.ev_start[an];
+        float pmax = 0.f;
 #pragma unroll
         for (int i = 0; i < PSG; ++i) {
             const int sl = grow_ + 16 * i;
@@ -2821,7 +2846,9 @@ __device__ __forceinline__ void dec_persist_att_bwd2_body(const PersistB& P, con
             const float* cr = P.c3d + (row0 + a) * D;
 #pragma unroll
             for (int h = 0; h < 8; ++h) {
-                Pr[i][h] = exp2x(*reinterpret_cast<const float4*>(pr + 4 * h));
+                const float4 pv = *reinterpret_cast<const float4*>(pr + 4 * h);
+                pmax = absmax4(pmax, pv);
+                Pr[i][h] = exp2x(pv);
                 if constexpr (!BIG) {
                     const int d = 32 * lr + 4 * h;
                     float4 v = *reinterpret_cast<const float4*>(cr + min(d, D - 4));
@@ -2833,9 +2860,14 @@ __device__ __forceinline__ void dec_persist_att_bwd2_body(const PersistB& P, con
                 const int a2 = min(PSET2 + PSL * ap + min(sl, PSL - 1), alen - 1);          // (clamped: only read by events longer than 129 segments)
                 const float* pr2 = P.PALL + (row0 + a2) * PH + 32 * lr;
 #pragma unroll
-                for (int h = 0; h < 8; ++h) Pr2[i][h] = exp2x(*reinterpret_cast<const float4*>(pr2 + 4 * h));
+                for (int h = 0; h < 8; ++h) {
+                    const float4 pv = *reinterpret_cast<const float4*>(pr2 + 4 * h);
+                    pmax = absmax4(pmax, pv);
+                    Pr2[i][h] = exp2x(pv);
+                }
             }
         }
+        domain_report(P.host_flag, DOMAIN_WORD_P, pmax);
     } else {
 #pragma unroll
         for (int i = 0; i < PSG; ++i)
@@ -3137,7 +3169,7 @@ static void phost_init(PersistHost& h, int dev) {
         if (good) h.cus = prop.multiProcessorCount;
         good = good && hipMalloc(&h.abort_dev, 256) == hipSuccess && hipMemset(h.abort_dev, 0, 256) == hipSuccess;
         good = good && hipHostMalloc(&h.flag_host, 64, hipHostMallocMapped) == hipSuccess;
-        if (good) { h.flag_host[0] = 0; good = hipHostGetDevicePointer((void**)&h.flag_dev, h.flag_host, 0) == hipSuccess; }
+        if (good) { for (int i = 0; i < 16; ++i) h.flag_host[i] = 0; good = hipHostGetDevicePointer((void**)&h.flag_dev, h.flag_host, 0) == hipSuccess; }
         good = good && hipFuncSetAttribute(reinterpret_cast<const void*>(dec_persist_att_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES_ATT) == hipSuccess;
         good = good && hipFuncSetAttribute(reinterpret_cast<const void*>(dec_persist_lstm_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES_LSTM) == hipSuccess;
         good = good && hipFuncSetAttribute(reinterpret_cast<const void*>(dec_persist_lstm_h2_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES_LSTM + 1024) == hipSuccess;
@@ -3229,7 +3261,26 @@ int persist_check_async() {
                   "call enqueued since are invalid, and the optimiser kernels enqueued since were skipped (parameters unchanged)", code, code % 1000);
         return -62;   // -ETIME
     }
+    if (h.ok && (h.flag_host[DOMAIN_WORD_P] | h.flag_host[DOMAIN_WORD_Q])) {
+        float pm, qm;
+        const u32 pb = h.flag_host[DOMAIN_WORD_P], qb = h.flag_host[DOMAIN_WORD_Q];
+        std::memcpy(&pm, &pb, 4); std::memcpy(&qm, &qb, 4);
+        h.flag_host[DOMAIN_WORD_P] = 0; h.flag_host[DOMAIN_WORD_Q] = 0;
+        // nothing was aborted or skipped: the launch ran to its end, but what it computed from those elements is the clamped form's value
+        char what[160];
+        if (pb && qb) snprintf(what, sizeof what, "p = ctx2att(clip) [P_all] reached |p| = %.6g and q = h2att(h1) reached |q| = %.6g", pm, qm);
+        else if (pb) snprintf(what, sizeof what, "p = ctx2att(clip) [P_all] reached |p| = %.6g", pm);
+        else snprintf(what, sizeof what, "q = h2att(h1) reached |q| = %.6g", qm);
+        set_error("attention pre-activation outside the domain of the factored tanh (|p| <= 43 and |q| <= 43): %s; the attention weights, log-probs and "
+                  "gradients of the calls since the last check are invalid", what);
+        return -33;   // -EDOM
+    }
     return 0;
+}
+
+int persist_softmax_branch() {
+    PersistHost& h = phost();
+    return h.ok ? (int)h.flag_host[BRANCH_WORD] : 0;
 }
 
 // diagnostic: copy the last stamped launch's s_memrealtime stamps ([4 roles][S][16] uint64, 100 MHz) to the host; returns S

@@ -280,3 +280,68 @@ def make_peaked(labels=None, masks=None):
     if labels is not None:
         vid['labels'], vid['masks'] = np.asarray(labels, np.int64).copy(), np.asarray(masks, np.float32).copy()
     return opt, params, vid
+
+
+# The additive attention at TRAINED-WEIGHT scales.  make_params draws ctx2att / h2att / alpha_net in +-1/sqrt(fan_in) and make_video draws
+# C3D rows from N(0, 1): |p| = |ctx2att(c3d)| and |q| = |h2att(h1)| stay near 1, sum|alpha| near 11 and the slot softmax near uniform.  A trained
+# checkpoint is not there, and three pieces of the attention kernels depend on it: the max exchange of the split softmax (sum|alpha| > 40),
+# the factored tanh(p + q) = 1 - 2 / (e^{2p} e^{2q} + 1) whose factors are formed from p and q separately, and its conditioning at large
+# |p| + |q|.  The variants below are built from make_params / make_video by SCALING only (no stored weights):
+#   alpha_sum   alpha_net.weight rescaled so that sum|alpha| has this value (asserted here)
+#   c2a / h2a   (weight scale, bias scale) of ctx2att / h2att
+#   cross       c: on attention columns 0..3 ctx2att.bias = +c and h2att.bias = -(c - 10) (p ~ +c, q ~ -(c - 10), p + q ~ +10), on columns
+#               4..7 the mirrored signs (p + q ~ -10): both arguments beyond +-43, their sum where tanh is +-1 to 4e-9 but not "0"
+#   coherent    b: ctx2att.bias = b * sign(alpha_j) (with alpha_sum): tanh(p + q) takes the sign of alpha_j on most columns, so the scores of ALL slots
+#               sit near +0.8 sum|alpha| (scores of random sign stay within a few ||alpha||_2 ~ +-30, where an unshifted exp is still finite)
+#   lens        event lengths written over the first events (thirds of an event without a valid slot: 43 / 86 / 129 boundaries)
+ATTSAT = {
+    'below': dict(alpha_sum=39.0, video=dict(N=40, A=129, seed=81)),
+    'above': dict(alpha_sum=41.0, video=dict(N=40, A=129, seed=81)),
+    # N64 x A128, V1 = 5001, 20 steps: the benchmarked shape
+    'above64': dict(alpha_sum=41.0, vocab=5000, seq_length=19, video=dict(N=64, A=128, seed=82)),
+    'alpha_big': dict(alpha_sum=150.0, coherent=2.0, video=dict(N=64, A=129, seed=83)),
+    # three 64-event groups, the last one partly filled (training takes the launch-per-phase recurrences there, decoding the persistent one per group)
+    'alpha_big150': dict(alpha_sum=150.0, coherent=2.0, video=dict(N=150, A=100, seed=88)),
+    'pq_wide': dict(c2a=(12.0, 12.0), h2a=(40.0, 500.0), video=dict(N=40, A=129, seed=84)),
+    'pq_cross': dict(cross=60.0, video=dict(N=12, A=60, seed=85)),
+    'short': dict(alpha_sum=41.0, lens=(1, 2, 43, 44, 86, 87, 129), video=dict(N=40, A=129, seed=86)),
+    'short_big': dict(alpha_sum=41.0, lens=(130, 172, 173, 258, 1, 44, 87), video=dict(N=24, A=258, seed=87, min_len=100)),
+}
+ATTSAT_CROSS_COLS = 4
+
+
+def make_attsat(name, clip_context_type='CC'):
+    """(opt, params, video) of a trained-attention-regime case (see ATTSAT).  Small shapes (vocabulary 300, 6 steps) except 'above64'.
+    `clip_context_type` 'CH' / 'CC+CH': the same construction over the frame-level context of that type (ctx2att is 512 / 1012 wide)."""
+    c = ATTSAT[name]
+    L = c.get('seq_length', 5) + 2
+    opt = default_opt(vocab_size=c.get('vocab', 300), seq_length=L - 2, clip_context_type=clip_context_type)
+    params = make_params(opt, 0)
+    vid = make_video(L=L, V1=opt.CG_vocab_size + 1, **c['video'])
+    att = 'lm_model.core.attention.'
+    f32 = np.float32
+    if 'alpha_sum' in c:
+        w = params[att + 'alpha_net.weight']
+        w = (w.astype(np.float64) * (c['alpha_sum'] / np.abs(w.astype(np.float64)).sum())).astype(f32)
+        got = float(np.abs(w.astype(np.float64)).sum())
+        assert abs(got - c['alpha_sum']) < 1e-3 * c['alpha_sum'], got          # far inside the distance to the switch at 40
+        params[att + 'alpha_net.weight'] = w
+    if 'coherent' in c:
+        params[att + 'ctx2att.bias'] = (f32(c['coherent']) * np.sign(params[att + 'alpha_net.weight'][0])).astype(f32)
+    for key, lin in (('c2a', 'ctx2att'), ('h2a', 'h2att')):
+        if key in c:
+            params[att + lin + '.weight'] = (params[att + lin + '.weight'] * f32(c[key][0])).astype(f32)
+            params[att + lin + '.bias'] = (params[att + lin + '.bias'] * f32(c[key][1])).astype(f32)
+    if 'cross' in c:
+        k, cc = ATTSAT_CROSS_COLS, f32(c['cross'])
+        params[att + 'ctx2att.bias'][:k] = cc
+        params[att + 'h2att.bias'][:k] = -(cc - f32(10.0))
+        params[att + 'ctx2att.bias'][k:2 * k] = -cc
+        params[att + 'h2att.bias'][k:2 * k] = cc - f32(10.0)
+    if 'lens' in c:
+        lens = np.asarray(c['lens'], np.int64)
+        soi = vid['soi']
+        soi[:len(lens), 0] = np.minimum(soi[:len(lens), 0], vid['T_v'] - lens)
+        soi[:len(lens), 1] = soi[:len(lens), 0] + lens
+        vid['ind'] = (soi[:, 1] - 1).astype(np.int64)
+    return opt, params, vid

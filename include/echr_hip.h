@@ -41,8 +41,16 @@ const char* echr_last_error(void);
 /* Asynchronous failures.  The persistent recurrence kernels (csrc/persist.hip) bound every inter-workgroup wait; when one gives up the
  * launch drains, a device word stays set (echr_clamp_adam / echr_clamp then skip their update, so no parameter is touched by the
  * invalid gradients) and the NEXT library call that takes a stream returns -ETIME (-62) once, naming the edge and timestep.
- * echr_check_async() is that check on its own, for callers that want it right after a synchronisation point: 0 or -62. */
+ * echr_check_async() is that check on its own, for callers that want it right after a synchronisation point: 0, -62 or -33.
+ * -EDOM (-33), reported the same way (once, by the next library call that checks): an attention kernel that evaluates tanh(p + q) in its
+ * factored form 1 - 2 / (e^{2p} e^{2q} + 1) (the persistent recurrences, the greedy decoder, the d P_all pass of every backward) met
+ * |p| > 43 (p = ctx2att(clip), tensor P_all) or |q| > 43 (q = h2att(h1)): outside that range the form is not tanh(p + q).  Nothing is aborted
+ * or skipped -- the launch ran to its end -- but the results of the calls since the last check are invalid; the message names the tensor and
+ * the magnitude reached.  The launch-per-phase forward (echr_config_set("persist", 0)) evaluates tanh(p + q) directly and has no such limit. */
 int echr_check_async(void);
+/* Diagnostic: the soft-max branch the last persistent forward / decoding launch took -- 1: no shift (sum|alpha| <= 40), 2: the exact max
+ * exchange between the three workgroups of an event, 0: none yet.  Read it behind a synchronisation point. */
+int echr_persist_softmax_branch(void);
 /* Number of echr_clamp_adam launches (of ANY optimiser state of the process; echr_clamp is not an update and is not counted) that skipped
  * their update because of the asynchronous failure the last -62 reported (read once: the count is cleared).  Process-wide, therefore only
  * a diagnostic when several optimiser states step in one process: a caller that keeps step counts winds each of them back from its OWN

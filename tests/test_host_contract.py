@@ -235,3 +235,55 @@ def test_runtime_switches_are_known_by_name():
     for key in (b'overlap', b'chains2', b'tail_early', b'embed_fused', b'tsrm_fork'):          # retired: only their default path remains
         assert lib.echr_config_set(key, 1) == -22, key
     assert lib.echr_config_set(b'att_slots', 3) != 0          # (only 2, 4 or 8)
+
+
+def test_attsat_variants_satisfy_their_own_conditions():
+    """synth.make_attsat (tests/test_gpu_attention_regime.py): every variant is where it says it is -- sum|alpha| on the intended side of the
+    soft-max switch at 40, max|p| / max|q| of the float64 oracle's own pass in the stated range, the crossing columns present -- so that a later
+    edit of synth.py cannot move the regime back to where nothing is exercised."""
+    att = 'lm_model.core.attention.'
+    asum = lambda P: float(np.abs(P[att + 'alpha_net.weight'].astype(np.float64)).sum())
+    cases = {k: synth.make_attsat(k) for k in synth.ATTSAT}
+    assert 38.0 < asum(cases['below'][1]) < 39.9
+    for k in ('above', 'above64', 'short', 'short_big'):
+        assert 40.1 < asum(cases[k][1]) < 42.0, k
+    for k in ('alpha_big', 'alpha_big150'):
+        assert asum(cases[k][1]) > 100.0, k
+    p, q = U.oracle_pq(*cases['alpha_big'])
+    sc = np.tanh(p[None, :300] + q[:, :1]) @ cases['alpha_big'][1][att + 'alpha_net.weight'][0].astype(np.float64)
+    assert sc.min() > 100.0          # exp(score) overflows float32 (e^88.7) on EVERY slot without the shift
+    for k in ('pq_wide', 'pq_cross'):
+        assert asum(cases[k][1]) < 40.0, k
+    # below / above: identical but for the scale of alpha_net
+    (_, pb, vb), (_, pa, va) = cases['below'], cases['above']
+    for k in pb:
+        assert (k == att + 'alpha_net.weight') != np.array_equal(pb[k], pa[k]), k
+    for k in vb:
+        assert np.array_equal(vb[k], va[k]), k
+    # shapes: the benchmarked one, more than one 64-event group with a partly filled last one
+    o, _, v = cases['above64']
+    assert (len(v['soi']), o.CG_vocab_size + 1, v['labels'].shape[1] - 1) == (64, 5001, 20) and int((v['soi'][:, 1] - v['soi'][:, 0]).max()) == 128
+    assert len(cases['alpha_big150'][2]['soi']) == 150 and 150 % 64 != 0
+    assert len(cases['alpha_big'][2]['soi']) <= 64          # the persistent training kernels take at most 64 events
+    # event lengths around the 43 / 86 / 129 (and 129 + ...) boundaries of the three-workgroup split
+    lens = lambda k: set((cases[k][2]['soi'][:, 1] - cases[k][2]['soi'][:, 0]).tolist())
+    assert {1, 2, 43, 44, 86, 87, 129} <= lens('short') and max(lens('short')) == 129
+    assert {130, 172, 173, 258, 1, 44, 87} <= lens('short_big')
+    for k in ('short', 'short_big'):
+        v = cases[k][2]
+        assert v['soi'].min() >= 0 and v['soi'][:, 1].max() <= v['T_v'] and np.array_equal(v['ind'], v['soi'][:, 1] - 1)
+    # p and q of the float64 oracle
+    p, q = U.oracle_pq(*cases['pq_wide'])
+    assert 20.0 < np.abs(p).max() < 40.0 and 20.0 < np.abs(q).max() < 40.0, (np.abs(p).max(), np.abs(q).max())
+    big = (np.abs(p)[None, :200] > 5) & (np.abs(q[:, :1]) > 5)          # (slot, step) pairs of one event's q against 200 slots
+    opp = ((p[None, :200] * q[:, :1]) < 0) & big
+    assert big.sum() > 1000 and 0.25 < opp.sum() / big.sum() < 0.75
+    p, q = U.oracle_pq(*cases['pq_cross'])
+    k = synth.ATTSAT_CROSS_COLS
+    assert p[:, :k].min() > 43.0 and q[:, :, :k].max() < -43.0 and p[:, k:2 * k].max() < -43.0 and q[:, :, k:2 * k].min() > 43.0
+    s = p[None, :, :2 * k] + q[:, :1, :2 * k]
+    assert 6.0 < np.abs(s).min() and np.abs(s).max() < 14.0           # p + q ~ +-10: tanh is +-1 there, the clamped factored form gives 0
+    assert np.abs(p[:, 2 * k:]).max() < 43.0 and np.abs(q[:, :, 2 * k:]).max() < 43.0
+    for name in ('below', 'alpha_big', 'short'):                      # everything else stays inside the domain
+        p, q = U.oracle_pq(*cases[name])
+        assert np.abs(p).max() < 43.0 and np.abs(q).max() < 43.0, name

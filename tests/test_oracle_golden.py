@@ -51,6 +51,24 @@ def test_config_summaries(case):
         assert np.allclose(v, ref, rtol=1e-4, atol=1e-7 * (1 + np.abs(ref).max())), key
 
 
+@pytest.mark.parametrize('name', ['above', 'pq_wide'])
+@pytest.mark.parametrize('mode', ['eval', 'train'])
+def test_attention_regime_summaries(name, mode):
+    """The float32 oracle on the trained-attention-scale cases (synth.make_attsat: sum|alpha| = 41 / max|p| 34, max|q| 28) against the
+    reference's own summaries (tools/make_golden.py do_attsat)."""
+    opt, params, vid = synth.make_attsat(name)
+    g = U.gold('case_attsat.npz')
+    tag = name + '|' + mode
+    pred, loss, grads = U.run_oracle(opt, params, vid, mode == 'train')
+    assert abs(loss - float(g[tag + '|loss'])) < 1e-5
+    s = SM.summarize_logp(pred)
+    assert np.abs(s['slice'] - g[tag + '|logp|slice']).max() < 1e-5
+    assert np.array_equal(s['argmax'], g[tag + '|logp|argmax'])
+    for key, v in SM.summarize_grads(grads).items():
+        ref = g[tag + '|grad|' + key]
+        assert np.allclose(v, ref, rtol=1e-4, atol=1e-7 * (1 + np.abs(ref).max())), key
+
+
 TOL_NOISE = 1e-5          # 2x the fp32 noise of the peaked case's gradients, of their tensor's max-norm (tests/test_gpu_parity.py TOL_GRAD)
 
 

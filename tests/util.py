@@ -24,12 +24,15 @@ def oracle_drop(opt):
     return drop
 
 
-def run_oracle(opt, params, vid, train_mode, backward=True):
+def run_oracle(opt, params, vid, train_mode, backward=True, dtype=None):
+    """dtype=torch.float64: the same float32 inputs (and the same dropout masks) carried through the oracle in double precision
+    (None: every array in the precision it arrives in)."""
     from oracle import echr_ref_cpu as O
-    P = {k: torch.from_numpy(v.copy()).requires_grad_(backward) for k, v in params.items()}
-    tap, c3d, lda = (torch.from_numpy(vid[k]) for k in ('tap', 'c3d', 'lda'))
+    cast = (lambda t: t) if dtype is None else (lambda t: t.to(dtype))
+    P = {k: cast(torch.from_numpy(v.copy())).requires_grad_(backward) for k, v in params.items()}
+    tap, c3d, lda = (cast(torch.from_numpy(vid[k])) for k in ('tap', 'c3d', 'lda'))
     labels = torch.from_numpy(vid['labels'])
-    masks = torch.from_numpy(vid['masks'])
+    masks = cast(torch.from_numpy(vid['masks']))
     drop = oracle_drop(opt) if train_mode else None
     pred = O.caption_forward(P, tap, c3d, lda, labels, vid['ind'], vid['soi'], 'train', drop, opt.n_head, video_context_type=opt.video_context_type, event_context_type=opt.event_context_type, fST_type=getattr(opt, 'fST_type', 'fST0'), use_posit=opt.use_posit,
                              init_feats_type=opt.CG_init_feats_type)
@@ -39,6 +42,27 @@ def run_oracle(opt, params, vid, train_mode, backward=True):
         loss.backward()
         grads = {k: (p.grad.numpy().copy() if p.grad is not None else None) for k, p in P.items()}
     return pred.detach().numpy(), float(loss.detach()), grads
+
+
+def oracle_pq(opt, params, vid, dtype=torch.float64):
+    """The attention pre-activations of the oracle's own teacher-forced pass (eval mode): p = ctx2att(clip) on the valid slots [n_valid, Ha]
+    and q = h2att(h1) of every step [S, N, Ha]."""
+    from oracle import echr_ref_cpu as O
+    import torch.nn.functional as F
+    rec = dict(p=None, q=[])
+    orig = O.attention
+
+    def spy(P, h, clip, mask, prefix='lm_model.core.attention.'):
+        if rec['p'] is None:
+            rec['p'] = F.linear(clip, P[prefix + 'ctx2att.weight'], P[prefix + 'ctx2att.bias'])[mask.bool()].detach().numpy()
+        rec['q'].append(F.linear(h, P[prefix + 'h2att.weight'], P[prefix + 'h2att.bias']).detach().numpy())
+        return orig(P, h, clip, mask, prefix)
+    O.attention = spy
+    try:
+        run_oracle(opt, params, vid, False, backward=False, dtype=dtype)
+    finally:
+        O.attention = orig
+    return rec['p'], np.stack(rec['q'])
 
 
 def build_gpu_model(opt, params, train_mode):
