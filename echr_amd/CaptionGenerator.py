@@ -97,6 +97,76 @@ class CaptionGenerator(nn.Module):
             return self.lm_model.sample(video, event, clip, clip_mask, {'beam_size': beam_size, 'return_score': return_score})
         return self.lm_model.sample(video, event, clip, clip_mask)
 
+    def forward_batch(self, batch, mode='train', beam_size=1):
+        """`forward` over a multi-video batch (echr_amd.batch.VideoBatch): mode='train' returns the log-probs [N_tot, S, V+1] of all events
+        (rows of video v: batch.event_slices[v]; S = the widest video's step count) with the usual autograd edges -- parameters, and
+        batch.tap through 'ER2' / 'ER3' and 'VH'; mode='eval' returns the greedy (seq, logp) of all rows.  Rows of video v equal what
+        forward() returns for that video alone; apply the criterion with `batch.criterion(crit, logp)` (per-video normalisers, summed).
+        One dropout counter per call, every site keyed by the batch-global element index."""
+        if mode == 'train_rl':
+            raise NotImplementedError("mode='train_rl' takes one video per call: self-critical training over a batch is a follow-up")
+        if mode not in ('train', 'eval'):
+            raise NotImplementedError("mode=%r: batches run 'train' and 'eval'" % (mode,))
+        if beam_size != 1:
+            raise NotImplementedError('beam search takes one video per call: beam_size > 1 over a batch is a follow-up')
+        self._check_batch_options()
+        self._require_live_decoder()
+        if not batch.c3d.is_cuda:
+            raise EF.L.EchrHipError('CaptionGenerator runs on the GPU only: build the batch on the device (VideoBatch.from_videos(..., device=))')
+        if mode == 'train' and batch.labels is None:
+            raise ValueError("mode='train' needs a batch with labels")
+        ev_start, ev_len, ind, A = EF.event_index_tensors(batch.soi, batch.ind, batch.device, batch.c3d.shape[0])
+        vid = batch.dev('vid')
+        lm, fm = self.lm_model, self.fusion_model
+        drop = lm.next_drop_state(fm.enc_attn.dropout.p)
+        drop.training = self.training
+        video = self.get_video_context_batch(batch)
+        parts = {'ER1': 1, 'ER2': 2, 'ER3': 3}[self.opt.event_context_type]
+        ech = EF.EventPoolGather.apply(batch.c3d, batch.tap, ev_start, ev_len, ind, parts)
+        params = fm.native_params()
+        infer = not (torch.is_grad_enabled() and (ech.requires_grad or any(p.requires_grad for p in params)))
+        # (index bounds 0, 0: the tabulated pair MLP of large inference calls is keyed by one video's bounds)
+        event = EF.TSRMBatchFunction.apply(ech, ev_start, ev_len, vid, batch.n_videos, fm.enc_attn.group, drop, fm._grad_sink(),
+                                           (1 if infer else 0, 0, 0, fm.fst_mode()), *params)
+        disjoint = EF.rows_disjoint(batch.soi)
+        if mode == 'eval':
+            with torch.no_grad():
+                if '_sample_tables' not in lm.__dict__:
+                    lm._sample_tables = {}
+                return EF.greedy_sample(video, event, batch.c3d, ev_start, ev_len, A, lm.seq_length, lm.native_params(),
+                                        table_cache=lm._sample_tables, vid=vid)
+        if lm.training and lm.ss_prob > 0.0:
+            raise NotImplementedError('scheduled sampling (ss_prob > 0) is never enabled by the reference and is not on the HIP path')
+        tokens = lm._tokens(batch.labels, batch.device)
+        arena = getattr(lm, '_echr_arena_ref', None)
+        sink = EF.GradSink(arena, lm.native_params()) if arena is not None else None
+        return EF.DecoderBatchFunction.apply(video, event, batch.c3d, ev_start, ev_len, tokens, A, disjoint, drop, sink, vid, *lm.native_params())
+
+    def _check_batch_options(self):
+        """What the batched entry points do not cover yet (follow-ups): an initial state from the contexts, 'CH' rows."""
+        if getattr(self.opt, 'CG_init_feats_type', ''):
+            raise NotImplementedError("CG_init_feats_type=%r: batches start from the zero state (an initial state that reads the scene vector 'V' -- or "
+                                      "any other context -- takes one video per call)" % (self.opt.CG_init_feats_type,))
+        if self.clip_parts() != 1:
+            raise NotImplementedError("clip_context_type=%r: batches attend over the C3D rows ('CC') only" % (self.opt.clip_context_type,))
+        arena = getattr(self, '_echr_arena', None)
+        if arena is not None and (getattr(arena, 'early_grad_hook', None) is not None or getattr(arena, 'early_reducer', None) is not None):
+            raise NotImplementedError('data-parallel gradient hand-over (parallel.EarlyReducer / DataParallelStep) takes one video per rank and '
+                                      'call: a VideoBatch per rank is a follow-up')
+
+    def get_video_context_batch(self, batch):
+        """Scene context of a batch, one vector per video [V, Dv]: 'VL' the video's lda_feats, 'VC' / 'VH' the column mean over THAT video's
+        rows of c3d / tap (echr_seg_col_mean_fwd), concatenated in that order."""
+        vt = self.opt.video_context_type
+        parts = []
+        if 'VL' in vt:
+            parts.append(EF._f32c(batch.lda))
+        if 'VC' in vt:
+            parts.append(EF.SegColMean.apply(batch.c3d, batch.dev('row_offset')))
+        if 'VH' in vt:
+            parts.append(EF.SegColMean.apply(batch.tap, batch.dev('row_offset')))
+        return parts[0] if len(parts) == 1 else torch.cat(parts, 1)
+
     def _train_rl(self, video, event, clip, clip_mask, drop, gen_result):
         """Self-critical training (CaptionGenerator.py:32-37): a multinomial sample under the iteration's dropout state, the greedy baseline in
         eval mode without a graph, both on the same event context; `sample_logprobs` is the teacher-forced recompute of the sample under the

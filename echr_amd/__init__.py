@@ -3,6 +3,7 @@ decoder hot path, behind the reference's own module API (CaptionGenerator, model
 MA_attention_8_NEW).  All arithmetic lives in libechr_hip.so (include/echr_hip.h); there is no CPU fallback."""
 from .CaptionGenerator import CaptionGenerator  # noqa: F401
 from . import models  # noqa: F401
+from .batch import VideoBatch  # noqa: F401
 
 
 def set_deterministic(on=True):

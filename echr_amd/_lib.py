@@ -119,6 +119,10 @@ class ClipStepArgs(C.Structure):
     _fields_ = [('clip_parts', i32), ('Dc', i32), ('c3d', c_f), ('rw', i32), ('weight', c_f)]
 
 
+class BatchExt(C.Structure):          # echr_batch_ext: the multi-video extension of the *_batch entry points
+    _fields_ = [('n_videos', i32), ('vid', c_f), ('video', c_f), ('g_video', c_f), ('ws', c_f)]
+
+
 # every symbol include/echr_hip.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ('echr_version', i32, []),
@@ -192,6 +196,16 @@ SYMBOLS = [
     ('echr_train_step_rw', i32, [C.POINTER(TrainStepArgs), c_f, C.c_void_p]),
     ('echr_train_step_clip_ws_floats', i64, [C.POINTER(TrainStepArgs), C.POINTER(ClipStepArgs)]),
     ('echr_train_step_clip', i32, [C.POINTER(TrainStepArgs), C.POINTER(ClipStepArgs), C.c_void_p]),
+    ('echr_batch_ws_floats', i64, [i32, i32, i32]),
+    ('echr_seg_col_mean_fwd', i32, [c_f, c_f, i32, i32, i64, c_f, i64, C.c_void_p]),
+    ('echr_seg_col_mean_bwd', i32, [c_f, i64, c_f, i32, i32, i64, c_f, C.c_void_p]),
+    ('echr_tsrm_fwd_batch', i32, [C.POINTER(TsrmArgs), C.POINTER(Dropout), C.POINTER(BatchExt), C.c_void_p]),
+    ('echr_tsrm_bwd_batch', i32, [C.POINTER(TsrmArgs), C.POINTER(TsrmGrads), C.POINTER(Dropout), C.POINTER(BatchExt), C.c_void_p]),
+    ('echr_decoder_fwd_batch', i32, [C.POINTER(DecArgs), C.POINTER(Dropout), C.POINTER(BatchExt), C.c_void_p]),
+    ('echr_decoder_bwd_batch', i32, [C.POINTER(DecArgs), C.POINTER(DecGrads), C.POINTER(Dropout), C.POINTER(BatchExt), C.c_void_p]),
+    ('echr_decoder_sample_batch', i32, [C.POINTER(SampleArgs), C.POINTER(BatchExt), C.c_void_p]),
+    ('echr_train_step_batch_ws_floats', i64, [C.POINTER(TrainStepArgs), C.POINTER(BatchExt)]),
+    ('echr_train_step_batch', i32, [C.POINTER(TrainStepArgs), C.POINTER(BatchExt), c_f, c_f, C.c_void_p]),
     ('echr_handover_wait', i32, [i32, C.c_void_p]),
     ('echr_clamp', i32, [c_f, i64, f32, C.c_void_p]),
     ('echr_clamp_adam', i32, [c_f, c_f, c_f, c_f, i64, i32, C.c_double, C.c_double, C.c_double, C.c_double, f32, C.c_void_p]),
@@ -201,7 +215,7 @@ SYMBOLS = [
 ABI_STRUCTS = {'echr_gemm_desc': GemmDesc, 'echr_dropout': Dropout, 'echr_tsrm_args': TsrmArgs, 'echr_tsrm_grads': TsrmGrads,
                'echr_dec_args': DecArgs, 'echr_dec_grads': DecGrads, 'echr_sample_args': SampleArgs, 'echr_sst_args': SstArgs,
                'echr_sst_grads': SstGrads, 'echr_train_step_args': TrainStepArgs, 'echr_init_state_args': InitStateArgs, 'echr_init_state_grads': InitStateGrads,
-               'echr_beam_args': BeamArgs, 'echr_row_grad_args': RowGradArgs, 'echr_clip_step_args': ClipStepArgs}
+               'echr_beam_args': BeamArgs, 'echr_row_grad_args': RowGradArgs, 'echr_clip_step_args': ClipStepArgs, 'echr_batch_ext': BatchExt}
 
 ABI_VERSION = 3          # include/echr_hip.h ECHR_ABI_VERSION
 _lib = None

@@ -1,0 +1,226 @@
+"""Multi-video batches of the caption path: plain data + validation, no kernels.
+
+The reference runs ONE video per call (`batch_size = 1`, opts.py:187) and sums the gradients of `m_batch` videos before one clamp +
+step (train.py:281-283,313-317).  A `VideoBatch` is those `m_batch` videos as one call: the feature rows of the videos are concatenated,
+the event intervals / anchors become batch-absolute row indices, and every event remembers its video (`vid`).  The batched entry points
+(`CaptionGenerator.forward_batch`, `FusedTrainStep.batch`) then compute what V single-video calls compute:
+
+  * an event attends only to the events of its own video, and reads its own video's scene vector;
+  * the loss is the SUM over the videos of LanguageModelCriterion, each video with its own normaliser `sum(mask_v) + 1e-6`, the mask
+    cut to the video's own step count (no 1/V);
+  * gradients are the sum over the videos, then ONE clamp and ONE Adam step;
+  * a batched call consumes ONE dropout counter and keys every site by the batch-global element index.
+"""
+import numpy as np
+import torch
+
+from .models.OldModel_NEW import n_decoder_steps
+
+_KEYS = ('c3d', 'tap', 'lda', 'ind', 'soi')
+
+
+def _np(x, dtype):
+    if isinstance(x, torch.Tensor):
+        x = x.detach().cpu().numpy()
+    return np.asarray(x, dtype=dtype)
+
+
+class VideoBatch(object):
+    """V >= 1 videos as one batch.  Build it with `from_videos`.
+
+    Attributes (V videos, N_tot events, T_tot feature rows):
+      c3d [T_tot, D], tap [T_tot, Ht]   concatenated features (per video its first min(len(c3d), len(tap)) rows); `tap` keeps its graph
+      lda [V, lda_dim]                  one LDA vector per video
+      row_offset int64 [V+1]            feature rows of video v = [row_offset[v], row_offset[v+1])
+      event_offset int64 [V+1]          events of video v = [event_offset[v], event_offset[v+1])
+      vid int32 [N_tot]                 video of event n (non-decreasing)
+      soi int64 [N_tot, 2], ind int64 [N_tot]   batch-absolute event intervals / anchors
+      labels int64 [N_tot, L], masks float32 [N_tot, L]   stacked, zero padded to the widest video's L (host tensors; None without labels);
+                                        a video's mask is zero behind ITS OWN step count S_v (column 1 + S_v onwards)
+      S                                 decoder steps of the stacked labels; steps[v] = S_v
+      event_slices                      slice of the event axis per video; split(x) cuts a [N_tot, ...] result accordingly
+    """
+
+    def __init__(self, c3d, tap, lda, row_offset, event_offset, soi, ind, labels=None, masks=None):
+        self.c3d, self.tap, self.lda = c3d, tap, lda
+        self.row_offset = np.asarray(row_offset, dtype=np.int64)
+        self.event_offset = np.asarray(event_offset, dtype=np.int64)
+        self.soi = np.asarray(soi, dtype=np.int64).reshape(-1, 2)
+        self.ind = np.asarray(ind, dtype=np.int64).reshape(-1)
+        self.n_videos = len(self.row_offset) - 1
+        self.vid = np.repeat(np.arange(self.n_videos, dtype=np.int32), np.diff(self.event_offset)).astype(np.int32)
+        self.labels, self.masks = labels, masks
+        self.steps, self.S = None, 0
+        self._dev = {}
+        self.validate()
+        if labels is not None:
+            self.steps = [n_decoder_steps(labels[s].numpy()) for s in self.event_slices]
+            self.S = n_decoder_steps(labels.numpy())
+
+    # ---- construction -------------------------------------------------------------------------------------------------------
+    @classmethod
+    def from_videos(cls, videos, device=None):
+        """`videos`: a list of dicts with the arguments of a single-video call -- 'c3d' [T, D], 'tap' [T', Ht], 'lda' [lda_dim], 'ind' [N_v],
+        'soi' [N_v, 2] (indices local to the video) and, for training, 'labels' / 'masks' [N_v, L_v] -- or a dict of parallel lists under
+        the same keys.  Features may be numpy arrays or tensors on any device; they are concatenated on `device` (default: the device of
+        the first video's c3d when it is a tensor, else the CPU)."""
+        if isinstance(videos, dict):
+            n = len(videos['c3d'])
+            videos = [{k: v[i] for k, v in videos.items()} for i in range(n)]
+        videos = list(videos)
+        if not videos:
+            raise ValueError('a batch needs at least one video')
+        for i, v in enumerate(videos):
+            missing = [k for k in _KEYS if k not in v]
+            if missing:
+                raise ValueError('video %d lacks %s' % (i, missing))
+        if device is None:
+            c0 = videos[0]['c3d']
+            device = c0.device if isinstance(c0, torch.Tensor) else torch.device('cpu')
+        device = torch.device(device)
+        as_t = lambda x: x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))
+        c3ds, taps, ldas, sois, inds, rows, counts = [], [], [], [], [], [0], [0]
+        with_labels = [('labels' in v and v['labels'] is not None) for v in videos]
+        if any(with_labels) and not all(with_labels):
+            raise ValueError('either every video carries labels / masks or none does')
+        for i, v in enumerate(videos):
+            c3d, tap = as_t(v['c3d']), as_t(v['tap'])
+            if c3d.dim() != 2 or tap.dim() != 2:
+                raise ValueError('video %d: c3d / tap must be [T, D] matrices' % i)
+            T = min(c3d.shape[0], tap.shape[0])
+            soi = _np(v['soi'], np.int64).reshape(-1, 2)
+            ind = _np(v['ind'], np.int64).reshape(-1)
+            if len(soi) == 0:
+                raise ValueError('video %d has no event' % i)
+            if len(ind) != len(soi):
+                raise ValueError('video %d: ind_select_list and soi_select_list differ in length (%d vs %d)' % (i, len(ind), len(soi)))
+            if (soi[:, 1] - soi[:, 0]).min() <= 0:
+                raise ValueError('video %d: every event needs at least one segment (soi=%s)' % (i, soi.tolist()))
+            if soi.min() < 0 or soi[:, 1].max() > T or ind.min() < 0 or ind.max() >= T:
+                raise ValueError('video %d: event intervals / anchors fall outside its %d feature rows' % (i, T))
+            c3ds.append(c3d[:T].to(device=device, dtype=torch.float32))
+            taps.append(tap[:T].to(device=device, dtype=torch.float32))
+            ldas.append(as_t(v['lda']).reshape(-1).to(device=device, dtype=torch.float32))
+            sois.append(soi + rows[-1])
+            inds.append(ind + rows[-1])
+            rows.append(rows[-1] + T)
+            counts.append(counts[-1] + len(soi))
+        if len({c.shape[1] for c in c3ds}) != 1 or len({t.shape[1] for t in taps}) != 1 or len({l.numel() for l in ldas}) != 1:
+            raise ValueError('the videos of a batch must share their feature widths')
+        labels = masks = None
+        if all(with_labels):
+            labels, masks = cls._stack_labels(videos, counts)
+        return cls(torch.cat(c3ds, 0), torch.cat(taps, 0), torch.stack(ldas, 0), rows, counts, np.concatenate(sois, 0), np.concatenate(inds, 0),
+                   labels, masks)
+
+    @staticmethod
+    def _stack_labels(videos, counts):
+        lab = [_np(v['labels'], np.int64) for v in videos]
+        msk = [_np(v['masks'], np.float32) for v in videos]
+        for i, (l, m) in enumerate(zip(lab, msk)):
+            n = counts[i + 1] - counts[i]
+            if l.ndim != 2 or l.shape != m.shape or l.shape[0] != n:
+                raise ValueError('video %d: labels %s / masks %s must both be [%d events, L]' % (i, l.shape, m.shape, n))
+            if l.shape[1] < 2:
+                raise ValueError('video %d: label tensor needs at least two columns' % i)
+        Lw = max(l.shape[1] for l in lab)
+        labels = np.zeros((counts[-1], Lw), np.int64)
+        masks = np.zeros((counts[-1], Lw), np.float32)
+        for i, (l, m) in enumerate(zip(lab, msk)):
+            s_v = n_decoder_steps(l)
+            labels[counts[i]:counts[i + 1], :l.shape[1]] = l
+            # LanguageModelCriterion cuts target and mask to the log-probs' step count (misc/utils.py:66-75): the video's OWN S_v
+            masks[counts[i]:counts[i + 1], :min(l.shape[1], 1 + s_v)] = m[:, :1 + s_v]
+        return torch.from_numpy(labels), torch.from_numpy(masks)
+
+    # ---- validation ---------------------------------------------------------------------------------------------------------
+    def validate(self):
+        """The layout contract: events of a video are contiguous, videos keep their order (vid non-decreasing, every video has an event),
+        and an event's rows and anchor lie inside its own video.  Raises ValueError otherwise."""
+        V, ro, eo = self.n_videos, self.row_offset, self.event_offset
+        if V < 1 or len(eo) != V + 1 or ro[0] != 0 or eo[0] != 0:
+            raise ValueError('a batch needs at least one video and offsets that start at 0')
+        if np.any(np.diff(ro) <= 0) or np.any(np.diff(eo) <= 0):
+            raise ValueError('every video needs at least one feature row and one event')
+        vid = np.asarray(self.vid)
+        N = int(eo[-1])
+        if len(vid) != N or len(self.soi) != N or len(self.ind) != N:
+            raise ValueError('vid / soi / ind must have one entry per event (%d)' % N)
+        if np.any(np.diff(vid) < 0):
+            raise ValueError('events of a video must be contiguous and videos must keep their order (vid non-decreasing)')
+        if not np.array_equal(vid, np.repeat(np.arange(V), np.diff(eo))):
+            raise ValueError('vid does not match event_offset')
+        lo, hi = ro[vid], ro[vid + 1]
+        if np.any(self.soi[:, 1] <= self.soi[:, 0]) or np.any(self.soi[:, 0] < lo) or np.any(self.soi[:, 1] > hi) or \
+                np.any(self.ind < lo) or np.any(self.ind >= hi):
+            raise ValueError('an event interval / anchor falls outside the feature rows of its video')
+        if int(ro[-1]) != self.c3d.shape[0] or self.c3d.shape[0] != self.tap.shape[0] or self.lda.shape[0] != V:
+            raise ValueError('feature tensors do not match the offsets')
+        if (self.labels is None) != (self.masks is None):
+            raise ValueError('labels and masks come together')
+        if self.labels is not None and (tuple(self.labels.shape) != tuple(self.masks.shape) or self.labels.shape[0] != N):
+            raise ValueError('labels / masks must be [%d events, L]' % N)
+
+    # ---- views --------------------------------------------------------------------------------------------------------------
+    @property
+    def n_events(self):
+        return int(self.event_offset[-1])
+
+    @property
+    def device(self):
+        return self.c3d.device
+
+    @property
+    def event_slices(self):
+        eo = self.event_offset
+        return [slice(int(eo[v]), int(eo[v + 1])) for v in range(self.n_videos)]
+
+    def split(self, x):
+        """Cut a [N_tot, ...] result (tensor or array) into its per-video pieces."""
+        if len(x) != self.n_events:
+            raise ValueError('split() takes a result with one row per event (%d), got %d' % (self.n_events, len(x)))
+        return [x[s] for s in self.event_slices]
+
+    def video(self, v):
+        """Video v as the dict of a single-video call (local indices, its own label width and step count)."""
+        s, r0, r1 = self.event_slices[v], int(self.row_offset[v]), int(self.row_offset[v + 1])
+        d = dict(c3d=self.c3d[r0:r1], tap=self.tap[r0:r1], lda=self.lda[v], soi=self.soi[s] - r0, ind=self.ind[s] - r0)
+        if self.labels is not None:
+            w = self.steps[v] + 1          # S_v steps read label columns 0 .. S_v - 1 and target columns 1 .. S_v
+            d['labels'], d['masks'] = self.labels[s, :w], self.masks[s, :w]
+        return d
+
+    def dev(self, name):
+        """int32 device copy of 'vid' / 'row_offset' (cached)."""
+        t = self._dev.get(name)
+        if t is None:
+            t = self._dev[name] = torch.from_numpy(np.asarray(getattr(self, name)).astype(np.int32)).to(self.device)
+        return t
+
+    @property
+    def targets(self):
+        return self.labels[:, 1:]
+
+    @property
+    def crit_masks(self):
+        return self.masks[:, 1:]
+
+    # ---- criterion ----------------------------------------------------------------------------------------------------------
+    def criterion(self, crit, logp):
+        """LanguageModelCriterion per video on the batch's log-probs [N_tot, S, V1]: returns (sum over the videos, per-video losses [V]).
+        Each video keeps its own normaliser sum(mask_v) + 1e-6 (its mask is zero behind its own step count); no 1/V."""
+        if self.labels is None:
+            raise ValueError('the batch carries no labels')
+        per = [crit(logp[s], self.targets[s], self.crit_masks[s]) for s in self.event_slices]
+        per = torch.stack(per)
+        return per.sum(), per
+
+    def criterion_weights(self, S=None):
+        """Per-position weights of the one-call step (host, float32 [N_tot, S]): w[n, t] = mask[n, t] / (sum(mask of video vid[n]) + 1e-6) --
+        with them the batch's loss is sum(-logp[target] * w) and the per-video normalisers cannot be got wrong downstream."""
+        S = self.S if S is None else S
+        mk = np.ascontiguousarray(self.crit_masks.numpy()[:, :S], dtype=np.float32)
+        w = np.empty_like(mk)
+        for s in self.event_slices:
+            w[s] = mk[s] / (mk[s].sum(dtype=np.float32) + np.float32(1e-6))
+        return w

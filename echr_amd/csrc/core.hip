@@ -524,7 +524,7 @@ __global__ __launch_bounds__(256) void logsoftmax_bwd_kernel(const float* __rest
                                                              const void* __restrict__ target, int tgt64, const float* __restrict__ mask,
                                                              const float* __restrict__ g_loss, const float* __restrict__ mask_sum,
                                                              float* __restrict__ out, long ldo, int N, int S, int V1,
-                                                             const float* __restrict__ rw) {
+                                                             const float* __restrict__ rw, int unit) {
     __shared__ float red[4];
     const int row = blockIdx.x;             // time-major row = t*N + n
     const int t = row / N, n = row % N;
@@ -537,7 +537,7 @@ __global__ __launch_bounds__(256) void logsoftmax_bwd_kernel(const float* __rest
         for (int j = threadIdx.x; j < V1; j += 256) o[j] = G[src + j] - expf(logp[src + j]) * s;
     } else {
         // loss = -sum(logp[target]*mask)/(sum(mask)+1e-6)  =>  g[target] = -mask/(den) * g_loss, other entries 0
-        const float gv = RW ? -rw[n * S + t] / mask_sum[0] * g_loss[0] : -mask[n * S + t] / (mask_sum[0] + 1e-6f) * g_loss[0];
+        const float gv = RW ? -rw[n * S + t] / (unit ? 1.f : mask_sum[0]) * g_loss[0] : -mask[n * S + t] / (mask_sum[0] + 1e-6f) * g_loss[0];
         const int tg = load_index(target, n * S + t, tgt64);
         for (int j = threadIdx.x; j < V1; j += 256) o[j] = (j == tg ? gv : 0.f) - expf(logp[src + j]) * gv;
     }
@@ -573,8 +573,8 @@ int logsoftmax_bwd(const float* logp, const float* G, const void* target, int tg
                    const float* mask_sum, float* out, long ldo, int N, int S, int V1, hipStream_t st, const float* rw) {
     if (G && ldo <= 256 * 20 && ldo > 256 * 8) hipLaunchKernelGGL(logsoftmax_bwd_reg_kernel<20>, dim3(N * S), dim3(256), 0, st, logp, G, out, ldo, N, S, V1);
     else if (G && ldo <= 256 * 8) hipLaunchKernelGGL(logsoftmax_bwd_reg_kernel<8>, dim3(N * S), dim3(256), 0, st, logp, G, out, ldo, N, S, V1);
-    else if (rw && !G) hipLaunchKernelGGL(logsoftmax_bwd_kernel<true>, dim3(N * S), dim3(256), 0, st, logp, G, target, tgt64, mask, g_loss, mask_sum, out, ldo, N, S, V1, rw);
-    else hipLaunchKernelGGL(logsoftmax_bwd_kernel<false>, dim3(N * S), dim3(256), 0, st, logp, G, target, tgt64, mask, g_loss, mask_sum, out, ldo, N, S, V1, nullptr);
+    else if (rw && !G) hipLaunchKernelGGL(logsoftmax_bwd_kernel<true>, dim3(N * S), dim3(256), 0, st, logp, G, target, tgt64, mask, g_loss, mask_sum, out, ldo, N, S, V1, rw, crit_unit_den());
+    else hipLaunchKernelGGL(logsoftmax_bwd_kernel<false>, dim3(N * S), dim3(256), 0, st, logp, G, target, tgt64, mask, g_loss, mask_sum, out, ldo, N, S, V1, nullptr, 0);
     return check_launch("logsoftmax_bwd");
 }
 
@@ -588,7 +588,7 @@ template <int EPT, bool RW>
 __global__ __launch_bounds__(256) void logsoftmax_nll_dlg_kernel(const float* __restrict__ X, long ld, const void* __restrict__ target, int tgt64,
                                                                  const float* __restrict__ mask, const float* __restrict__ g_loss, float* __restrict__ out,
                                                                  long ldo, float* __restrict__ row_loss, float* __restrict__ msum_out, int N, int S, int V1,
-                                                                 const int* __restrict__ act, const float* __restrict__ rw) {
+                                                                 const int* __restrict__ act, const float* __restrict__ rw, int unit) {
     __shared__ float red[4];
     // act != nullptr: block i handles the compacted row i = time-major row act[i] (only rows whose mask is non-zero exist: the logits arrive
     // as [n_active, ld], d logits / row_loss leave in the same compact order)
@@ -615,7 +615,7 @@ __global__ __launch_bounds__(256) void logsoftmax_nll_dlg_kernel(const float* __
     s = block_sum(s, red);
     ms = block_sum(ms, red);
     const float lse = m + logf(s);
-    const float gv = RW ? -mk / ms * g_loss[0] : -mk / (ms + 1e-6f) * g_loss[0];
+    const float gv = RW ? -mk / (unit ? 1.f : ms) * g_loss[0] : -mk / (ms + 1e-6f) * g_loss[0];
     float* o = out + (long)row * ldo;
 #pragma unroll
     for (int i = 0; i < EPT; ++i) {
@@ -630,20 +630,20 @@ __global__ __launch_bounds__(256) void logsoftmax_nll_dlg_kernel(const float* __
 }
 // loss[0] = sum(row_loss) / (msum + 1e-6) (RW: / msum), loss[1] = msum: one block, fixed order
 template <bool RW>
-__global__ __launch_bounds__(256) void nll_rows_sum_kernel(const float* __restrict__ row_loss, int NS, const float* __restrict__ msum, float* __restrict__ loss) {
+__global__ __launch_bounds__(256) void nll_rows_sum_kernel(const float* __restrict__ row_loss, int NS, const float* __restrict__ msum, float* __restrict__ loss, int unit) {
     __shared__ float red[4];
     float s = 0.f;
     for (int i = threadIdx.x; i < NS; i += 256) s += row_loss[i];
     s = block_sum(s, red);
-    if (threadIdx.x == 0) { loss[0] = RW ? s / msum[0] : s / (msum[0] + 1e-6f); loss[1] = msum[0]; }
+    if (threadIdx.x == 0) { loss[0] = RW ? s / (unit ? 1.f : msum[0]) : s / (msum[0] + 1e-6f); loss[1] = msum[0]; }
 }
 bool logsoftmax_nll_dlg_ok(int V1, long ldo) { return ldo <= 256 * 40; }
 int logsoftmax_nll_dlg(const float* X, long ld, const void* target, int tgt64, const float* mask, const float* g_loss, float* out, long ldo,
                        float* row_loss, float* msum_out, int N, int S, int V1, hipStream_t st, const int* act, int n_active, const float* rw) {
     const int rows = act ? n_active : N * S;
 #define ECHR_NLL_DLG(EPT) \
-    if (rw) hipLaunchKernelGGL((logsoftmax_nll_dlg_kernel<EPT, true>), dim3(rows), dim3(256), 0, st, X, ld, target, tgt64, mask, g_loss, out, ldo, row_loss, msum_out, N, S, V1, act, rw); \
-    else hipLaunchKernelGGL((logsoftmax_nll_dlg_kernel<EPT, false>), dim3(rows), dim3(256), 0, st, X, ld, target, tgt64, mask, g_loss, out, ldo, row_loss, msum_out, N, S, V1, act, nullptr)
+    if (rw) hipLaunchKernelGGL((logsoftmax_nll_dlg_kernel<EPT, true>), dim3(rows), dim3(256), 0, st, X, ld, target, tgt64, mask, g_loss, out, ldo, row_loss, msum_out, N, S, V1, act, rw, crit_unit_den()); \
+    else hipLaunchKernelGGL((logsoftmax_nll_dlg_kernel<EPT, false>), dim3(rows), dim3(256), 0, st, X, ld, target, tgt64, mask, g_loss, out, ldo, row_loss, msum_out, N, S, V1, act, nullptr, 0)
     if (ldo <= 256 * 8) { ECHR_NLL_DLG(8); }
     else if (ldo <= 256 * 20) { ECHR_NLL_DLG(20); }
     else { ECHR_NLL_DLG(40); }
@@ -651,8 +651,8 @@ int logsoftmax_nll_dlg(const float* X, long ld, const void* target, int tgt64, c
     return check_launch("logsoftmax_nll_dlg");
 }
 int nll_rows_sum(const float* row_loss, int NS, const float* msum, float* loss, hipStream_t st, bool rw) {
-    if (rw) hipLaunchKernelGGL(nll_rows_sum_kernel<true>, dim3(1), dim3(256), 0, st, row_loss, NS, msum, loss);
-    else hipLaunchKernelGGL(nll_rows_sum_kernel<false>, dim3(1), dim3(256), 0, st, row_loss, NS, msum, loss);
+    if (rw) hipLaunchKernelGGL(nll_rows_sum_kernel<true>, dim3(1), dim3(256), 0, st, row_loss, NS, msum, loss, crit_unit_den());
+    else hipLaunchKernelGGL(nll_rows_sum_kernel<false>, dim3(1), dim3(256), 0, st, row_loss, NS, msum, loss, 0);
     return check_launch("nll_rows_sum");
 }
 
@@ -661,7 +661,7 @@ int nll_rows_sum(const float* row_loss, int NS, const float* msum, float* loss, 
 template <bool RW>
 __global__ __launch_bounds__(256) void nll_loss_kernel(const float* __restrict__ logp, const void* __restrict__ target, int tgt64,
                                                        const float* __restrict__ mask, float* __restrict__ out, int NS, int V1,
-                                                       const float* __restrict__ rw) {
+                                                       const float* __restrict__ rw, int unit) {
     __shared__ float red[4];
     float s = 0.f, ms = 0.f;
     // four rows per round: targets and masks first, then the four gathered log-probs in flight together (the gather depends on its target:
@@ -682,7 +682,7 @@ __global__ __launch_bounds__(256) void nll_loss_kernel(const float* __restrict__
     }
     s = block_sum(s, red);
     ms = block_sum(ms, red);
-    if (threadIdx.x == 0) { out[0] = RW ? s / ms : s / (ms + 1e-6f); out[1] = ms; }
+    if (threadIdx.x == 0) { out[0] = RW ? s / (unit ? 1.f : ms) : s / (ms + 1e-6f); out[1] = ms; }
 }
 
 // ---- self-critical training on gathered log-probs (the module path: CaptionGenerator.forward(mode='train_rl') + RewardCriterion) ----
@@ -1096,7 +1096,7 @@ extern "C" int64_t echr_abi_sizeof(const char* name) {
     ECHR_SZ(echr_gemm_desc); ECHR_SZ(echr_dropout); ECHR_SZ(echr_tsrm_args); ECHR_SZ(echr_tsrm_grads); ECHR_SZ(echr_dec_args); ECHR_SZ(echr_dec_grads);
     ECHR_SZ(echr_sample_args); ECHR_SZ(echr_sst_args); ECHR_SZ(echr_sst_grads); ECHR_SZ(echr_train_step_args);
     ECHR_SZ(echr_init_state_args); ECHR_SZ(echr_init_state_grads); ECHR_SZ(echr_beam_args);
-    ECHR_SZ(echr_row_grad_args); ECHR_SZ(echr_clip_step_args);
+    ECHR_SZ(echr_row_grad_args); ECHR_SZ(echr_clip_step_args); ECHR_SZ(echr_batch_ext);
 #undef ECHR_SZ
     return -1;
 }
@@ -1209,16 +1209,117 @@ extern "C" int echr_event_pool_gather_bwd(const float* d_ech, const int32_t* ind
 
 static int nll_fwd(const float* logp, const void* target, int tgt64, const float* mask, float* loss, int32_t N, int32_t S, int32_t V1, void* stream) {
     ECHR_REQUIRE(logp && target && mask && loss && N > 0 && S > 0 && V1 > 0, "nll_loss_fwd: bad arguments");
-    hipLaunchKernelGGL(nll_loss_kernel<false>, dim3(1), dim3(256), 0, (hipStream_t)stream, logp, target, tgt64, mask, loss, N * S, V1, nullptr);
+    hipLaunchKernelGGL(nll_loss_kernel<false>, dim3(1), dim3(256), 0, (hipStream_t)stream, logp, target, tgt64, mask, loss, N * S, V1, nullptr, 0);
     return check_launch("nll_loss_fwd");
 }
 namespace echr {
 int nll_loss_rw(const float* logp, const void* target, int tgt64, const float* mask, const float* rw, float* loss, int N, int S, int V1, hipStream_t st) {
     ECHR_REQUIRE(logp && target && mask && rw && loss && N > 0 && S > 0 && V1 > 0, "nll_loss_rw: bad arguments");
-    hipLaunchKernelGGL(nll_loss_kernel<true>, dim3(1), dim3(256), 0, st, logp, target, tgt64, mask, loss, N * S, V1, rw);
+    hipLaunchKernelGGL(nll_loss_kernel<true>, dim3(1), dim3(256), 0, st, logp, target, tgt64, mask, loss, N * S, V1, rw, crit_unit_den());
     return check_launch("nll_loss_rw");
 }
 }  // namespace echr
+// ---- multi-video batches (echr_batch_ext) ----
+namespace echr {
+static thread_local const echr_batch_ext* g_batch_ext = nullptr;
+const echr_batch_ext* batch_ext() { return g_batch_ext; }
+BatchScope::BatchScope(const echr_batch_ext* x) : prev(g_batch_ext) { g_batch_ext = x; }
+BatchScope::~BatchScope() { g_batch_ext = prev; }
+}  // namespace echr
+
+// column means over row segments: block = (segment v, 64 columns); thread = (column, one of four row lanes); the four partial sums are added
+// in lane order (fixed order: bit-reproducible)
+__global__ __launch_bounds__(256) void seg_col_mean_fwd_kernel(const float* __restrict__ x, const int* __restrict__ row_offset, int cols, long ld,
+                                                               float* __restrict__ out, long ld_out) {
+    __shared__ float part[4][64];
+    const int v = blockIdx.x, c = blockIdx.y * 64 + (threadIdx.x & 63), q = threadIdx.x >> 6;
+    const int r0 = row_offset[v], r1 = row_offset[v + 1];
+    float s = 0.f;
+    if (c < cols) for (int r = r0 + q; r < r1; r += 4) s += x[(long)r * ld + c];
+    part[q][threadIdx.x & 63] = s;
+    __syncthreads();
+    if (q == 0 && c < cols) {
+        const float t = ((part[0][threadIdx.x] + part[1][threadIdx.x]) + part[2][threadIdx.x]) + part[3][threadIdx.x];
+        out[(long)v * ld_out + c] = r1 > r0 ? t / (float)(r1 - r0) : 0.f;
+    }
+}
+// gx[r, c] += g[v, c] / rows(v) for the rows r of segment v (block = (segment, 64 columns); every element has one writer)
+__global__ __launch_bounds__(256) void seg_col_mean_bwd_kernel(const float* __restrict__ g, long ld_g, const int* __restrict__ row_offset, int cols, long ld,
+                                                               float* __restrict__ gx) {
+    const int v = blockIdx.x, c = blockIdx.y * 64 + (threadIdx.x & 63), q = threadIdx.x >> 6;
+    const int r0 = row_offset[v], r1 = row_offset[v + 1];
+    if (c >= cols || r1 <= r0) return;
+    const float gv = g[(long)v * ld_g + c] * (1.0f / (float)(r1 - r0));
+    for (int r = r0 + q; r < r1; r += 4) gx[(long)r * ld + c] += gv;
+}
+extern "C" int echr_seg_col_mean_fwd(const float* x, const int32_t* row_offset, int32_t n_seg, int32_t cols, int64_t ld, float* out, int64_t ld_out,
+                                     void* stream) {
+    ECHR_REQUIRE(x && row_offset && out && n_seg > 0 && cols > 0 && ld >= cols && ld_out >= cols, "seg_col_mean_fwd: bad arguments");
+    hipLaunchKernelGGL(seg_col_mean_fwd_kernel, dim3(n_seg, (cols + 63) / 64), dim3(256), 0, (hipStream_t)stream, x, row_offset, cols, (long)ld, out, (long)ld_out);
+    return check_launch("seg_col_mean_fwd");
+}
+extern "C" int echr_seg_col_mean_bwd(const float* g, int64_t ld_g, const int32_t* row_offset, int32_t n_seg, int32_t cols, int64_t ld, float* gx,
+                                     void* stream) {
+    ECHR_REQUIRE(g && row_offset && gx && n_seg > 0 && cols > 0 && ld >= cols && ld_g >= cols, "seg_col_mean_bwd: bad arguments");
+    hipLaunchKernelGGL(seg_col_mean_bwd_kernel, dim3(n_seg, (cols + 63) / 64), dim3(256), 0, (hipStream_t)stream, g, (long)ld_g, row_offset, cols, (long)ld, gx);
+    return check_launch("seg_col_mean_bwd");
+}
+// segmented row sum by video: block = (video v, 256 columns); a thread adds the rows of its video in ascending order (vid is non-decreasing,
+// so they are one contiguous run; the scan over all N entries of vid is a few hundred loads)
+__global__ __launch_bounds__(256) void seg_rowsum_kernel(const float* __restrict__ X, const int* __restrict__ vid, int N, int cols, long ld,
+                                                         float* __restrict__ out) {
+    const int v = blockIdx.x, c = blockIdx.y * 256 + threadIdx.x;
+    if (c >= cols) return;
+    float s = 0.f;
+    for (int n = 0; n < N; ++n) if (vid[n] == v) s += X[(long)n * ld + c];
+    out[(long)v * ld + c] = s;
+}
+// per-video loss from the fused criterion's per-row terms: block = video, fixed-order block sum
+__global__ __launch_bounds__(256) void video_loss_rows_kernel(const float* __restrict__ row_loss, const int* __restrict__ act, int rows, int N,
+                                                              const int* __restrict__ vid, float* __restrict__ vloss) {
+    __shared__ float red[4];
+    const int v = blockIdx.x;
+    float s = 0.f;
+    for (int i = threadIdx.x; i < rows; i += 256) {
+        const int tm = act ? act[i] : i;
+        if (vid[tm % N] == v) s += row_loss[i];
+    }
+    s = block_sum(s, red);
+    if (threadIdx.x == 0) vloss[v] = s;
+}
+__global__ __launch_bounds__(256) void video_loss_logp_kernel(const float* __restrict__ logp, const void* __restrict__ target, int tgt64,
+                                                              const float* __restrict__ w, int N, int S, int V1, const int* __restrict__ vid,
+                                                              float* __restrict__ vloss) {
+    __shared__ float red[4];
+    const int v = blockIdx.x;
+    float s = 0.f;
+    for (int i = threadIdx.x; i < N * S; i += 256) {
+        if (vid[i / S] != v) continue;
+        const int tg = min(max(load_index(target, i, tgt64), 0), V1 - 1);
+        s -= logp[(long)i * V1 + tg] * w[i];
+    }
+    s = block_sum(s, red);
+    if (threadIdx.x == 0) vloss[v] = s;
+}
+namespace echr {
+int seg_rowsum(const float* X, const int* vid, int N, int V, int cols, long ld, float* out, hipStream_t st) {
+    ECHR_REQUIRE(X && vid && out && N > 0 && V > 0 && cols > 0 && ld >= cols, "seg_rowsum: bad arguments");
+    hipLaunchKernelGGL(seg_rowsum_kernel, dim3(V, (cols + 255) / 256), dim3(256), 0, st, X, vid, N, cols, ld, out);
+    return check_launch("seg_rowsum");
+}
+int video_loss_rows(const float* row_loss, const int* act, int rows, int N, const int* vid, int V, float* vloss, hipStream_t st) {
+    ECHR_REQUIRE(row_loss && vid && vloss && rows > 0 && N > 0 && V > 0, "video_loss_rows: bad arguments");
+    hipLaunchKernelGGL(video_loss_rows_kernel, dim3(V), dim3(256), 0, st, row_loss, act, rows, N, vid, vloss);
+    return check_launch("video_loss_rows");
+}
+int video_loss_logp(const float* logp, const void* target, int tgt64, const float* w, int N, int S, int V1, const int* vid, int V, float* vloss,
+                    hipStream_t st) {
+    ECHR_REQUIRE(logp && target && w && vid && vloss && N > 0 && S > 0 && V1 > 0 && V > 0, "video_loss_logp: bad arguments");
+    hipLaunchKernelGGL(video_loss_logp_kernel, dim3(V), dim3(256), 0, st, logp, target, tgt64, w, N, S, V1, vid, vloss);
+    return check_launch("video_loss_logp");
+}
+}  // namespace echr
+
 extern "C" int echr_gather_tokens_fwd(const float* logp, const int64_t* seq, float* out, int32_t N, int32_t S, int32_t T, int32_t V1, void* stream) {
     ECHR_REQUIRE(logp && seq && out && N > 0 && T > 0 && T <= S && V1 > 0, "gather_tokens_fwd: bad arguments");
     hipLaunchKernelGGL(gather_tokens_kernel, dim3((N * T + 255) / 256), dim3(256), 0, (hipStream_t)stream, logp, reinterpret_cast<const long long*>(seq),

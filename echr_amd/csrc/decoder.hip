@@ -954,6 +954,22 @@ static DecWsBwd carve_ws_bwd(const echr_dec_args* a, float* base) {
     return w;
 }
 
+// Multi-video batches: the caller's scratch echr_batch_ext.ws = VIDB [N, 4H] (scene part of stream 2's gates per EVENT) | VIDV [V, 4H] (per
+// video) | DGSEG [V, 4H] (d gates2 summed over time and over the events of a video).  The workspaces above are those of a single video.
+struct BatchWs { float *VIDB, *VIDV, *DGSEG; long total; };
+static BatchWs carve_batch(long N, long V, long H, float* base) {
+    BatchWs w;
+    long off = 0;
+    auto take = [&](long n) { float* p = base ? base + off : nullptr; off += rup(n, 64); return p; };
+    w.VIDB = take(N * 4 * H); w.VIDV = take(V * 4 * H); w.DGSEG = take(V * 4 * H);
+    w.total = off;
+    return w;
+}
+// the scene part of stream 2's gate pre-activations and its row pitch: one [4H] vector of the workspace, or one row per event of a batch
+static inline float* scene_base(const echr_dec_args* a, const DecWs& w) {
+    const echr_batch_ext* bx = batch_ext();
+    return bx ? carve_batch(a->N, bx->n_videos, a->H, bx->ws).VIDB : w.VIDB;
+}
 static int check_dims(const echr_dec_args* a, const char* who) {
     ECHR_REQUIRE(a, "%s: null args", who);
     ECHR_REQUIRE(a->N > 0 && a->A > 0 && a->Tv > 0 && a->S >= 0, "%s: bad N/A/Tv/S", who);
@@ -1011,6 +1027,15 @@ static int precompute_static(const echr_dec_args* a, const DecWs& w, hipStream_t
     }
     d.bias = a->b_c2a;
     RC(gemm(d, st));
+    if (const echr_batch_ext* bx = batch_ext()) {
+        // multi-video batch: one scene vector per video -> VIDV [V, 4H] (one fixed-order k loop per tile), gathered by vid into the per-event
+        // VIDB [N, 4H] that the gate products / kernels consume exactly as they consume stream 0's per-event EVB0
+        const BatchWs bw = carve_batch(a->N, bx->n_videos, H, bx->ws);
+        d = desc_nt(bx->video, a->Dv, a->w_ih[2] + E, E + a->Dv, bw.VIDV, 4 * H, bx->n_videos, 4 * H, a->Dv);
+        d.bias = a->b_ih[2]; d.bias2 = a->b_hh[2]; d.split_k = 1;
+        RC(gemm(d, st));
+        RC(embed_gather(bw.VIDV, bx->vid, bw.VIDB, a->N, 4 * H, bx->n_videos, st));
+    } else
     RC(row_matvec(a->video, a->w_ih[2] + E, E + a->Dv, a->b_ih[2], a->b_hh[2], w.VIDB, 4 * H, a->Dv, st));      // (M = 1: no GEMM launch)
 event_part:
     if (parts & 2) {
@@ -1120,7 +1145,7 @@ static int step_fwd(const echr_dec_args* a, const DecWs& w, int t, const DropCfg
         if (tok) {
             if (k == 0) { P.base[k] = w.EVB0; P.bmod[k] = N; }
             else if (k == 1) { P.base[k] = a->b_ih[1]; P.base2[k] = a->b_hh[1]; }
-            else P.base[k] = w.VIDB;
+            else { P.base[k] = scene_base(a, w); if (batch_ext()) P.bmod[k] = N; }          // (multi-video batch: per-event scene part)
         }
         P.c_prev[k] = w.CS[k] + (long)t * N * H;
         P.c_new[k] = w.CS[k] + (long)(t + 1) * N * H;
@@ -1151,6 +1176,7 @@ static int input_gates(const echr_dec_args* a, const DecWs& w, const float* xt, 
         d[k].add_mod = N; d[k].ld_add = 4 * H;
         if (k == 0) { if (!no_evb0) d[k].addend = w.EVB0; }
         else if (k == 1) { d[k].bias = a->b_ih[1]; d[k].bias2 = a->b_hh[1]; }
+        else if (batch_ext()) d[k].addend = scene_base(a, w);          // multi-video batch: the scene part is per event, like EVB0
         else d[k].bias = w.VIDB;
         d[k].split_k = force_h2 ? 1 : -1;          // sampler: one fixed-order k loop per tile (bitwise reproducible)
     }
@@ -1161,6 +1187,9 @@ static int input_gates(const echr_dec_args* a, const DecWs& w, const float* xt, 
 
 using namespace echr;
 
+extern "C" int64_t echr_batch_ws_floats(int32_t N, int32_t n_videos, int32_t H) {
+    return (N > 0 && n_videos > 0 && n_videos <= N && H > 0) ? carve_batch(N, n_videos, H, nullptr).total : -1;
+}
 extern "C" int64_t echr_decoder_ws_floats(const echr_dec_args* a) { return a ? carve_ws(a, nullptr).total : -1; }
 extern "C" int64_t echr_decoder_ws_bwd_floats(const echr_dec_args* a) { return a ? carve_ws_bwd(a, nullptr).total : -1; }
 
@@ -1460,6 +1489,30 @@ static int logit_grads(const echr_dec_args* a, const echr_dec_grads* g, const De
 extern "C" int echr_decoder_bwd(const echr_dec_args* a, const echr_dec_grads* g, const echr_dropout* drop, void* stream) {
     return echr::decoder_bwd_checked(a, g, drop, stream, nullptr);
 }
+// ---- multi-video batches: the single-video entries with the extension published for the duration of the call ----
+static int check_batch(const echr_dec_args* a, const echr_batch_ext* x, const char* who) {
+    ECHR_REQUIRE(a && x && x->n_videos > 0 && x->n_videos <= a->N && x->vid && x->video && x->ws, "%s: the batch extension needs 0 < n_videos <= N, vid, video and ws", who);
+    ECHR_REQUIRE(!a->h0, "%s: an initial state (CG_init_feats_type) is not part of the batched entries", who);
+    return 0;
+}
+extern "C" int echr_decoder_fwd_batch(const echr_dec_args* a, const echr_dropout* drop, const echr_batch_ext* x, void* stream) {
+    RC(check_batch(a, x, "decoder_fwd_batch"));
+    ECHR_REQUIRE(!a->prepared, "decoder_fwd_batch: prepared must be 0");
+    BatchScope scope(x);
+    return echr_decoder_fwd(a, drop, stream);
+}
+extern "C" int echr_decoder_bwd_batch(const echr_dec_args* a, const echr_dec_grads* g, const echr_dropout* drop, const echr_batch_ext* x, void* stream) {
+    RC(check_batch(a, x, "decoder_bwd_batch"));
+    BatchScope scope(x);
+    return echr_decoder_bwd(a, g, drop, stream);
+}
+namespace echr {
+int decoder_fused_video_loss(const echr_dec_args* a, const echr_dec_grads* g, const int* vid, int V, float* vloss, hipStream_t st) {
+    const DecWsBwd b = carve_ws_bwd(a, g->ws_bwd);
+    const bool compact = g->active_rows && g->n_active > 0;
+    return video_loss_rows(b.ROWL, compact ? g->active_rows : nullptr, compact ? g->n_active : a->S * a->N, a->N, vid, V, vloss, st);
+}
+}  // namespace echr
 int echr::decoder_bwd_checked(const echr_dec_args* a, const echr_dec_grads* g, const echr_dropout* drop, void* stream, const float* rw) {
     RC(persist_check_async());
     RC(join_tail((hipStream_t)stream));
@@ -1716,6 +1769,31 @@ int echr::decoder_bwd_parts(const echr_dec_args* a, const echr_dec_grads* g, con
         RC(embed_scatter_add(b.DXT, a->tokens, g->g_embed, h2 ? SNr : SN, E, V1, q, h2 ? actr : nullptr));
         return 0;
     };
+    // scene half of W_ih2 and d video.  One video: DGCOL[2] (column sum of d gates2) x the scene vector.  Multi-video batch: what stream 0's
+    // per-event context already does -- d gates2 summed over time per event (DGSUM[2]; have_sum: the caller has formed it), a segmented row
+    // sum by video in a fixed order (DGSEG [V, 4H]), then d W_ih2[:, E:] = DGSEG^T . video (K = V) and d video = DGSEG . W_ih2[:, E:], each
+    // one fixed-order k loop per tile
+    auto scene_grads = [&](hipStream_t q, bool have_sum) -> int {
+        const echr_batch_ext* bx = batch_ext();
+        if (!bx) {
+            RC(rank1_update(b.DGCOL[2], a->video, g->g_w_ih[2] + E, cin[2], 4 * H, a->Dv, false, q));          // K = 1: no GEMM launch
+            if (g->g_video) RC(vec_mat(b.DGCOL[2], a->w_ih[2] + E, cin[2], g->g_video, 4 * H, a->Dv, q));
+            return 0;
+        }
+        const int V = bx->n_videos;
+        if (!have_sum) RC(sum_over_time(b.DG[2], 4 * H, S, N, 4 * H, b.DGSUM[2], 4 * H, q));
+        float* dgseg = carve_batch(N, V, H, bx->ws).DGSEG;
+        RC(seg_rowsum(b.DGSUM[2], bx->vid, N, V, 4 * H, 4 * H, dgseg, q));
+        echr_gemm_desc ds = desc_tn(dgseg, 4 * H, bx->video, a->Dv, g->g_w_ih[2] + E, cin[2], 4 * H, a->Dv, V);
+        ds.split_k = 1;
+        RC(gemm(ds, q));
+        if (bx->g_video) {
+            ds = desc_nn(dgseg, 4 * H, a->w_ih[2] + E, cin[2], bx->g_video, a->Dv, V, a->Dv, 4 * H);
+            ds.split_k = 1;
+            RC(gemm(ds, q));
+        }
+        return 0;
+    };
     hipStream_t sa2 = nullptr;
     auto part_a = [&]() -> int {
     if (!do_rec) return 0;
@@ -1748,8 +1826,7 @@ int echr::decoder_bwd_parts(const echr_dec_args* a, const echr_dec_grads* g, con
             d = desc_tn(dgsum0, 4 * H, a->event, a->De, g->g_w_ih[0] + E, cin[0], 4 * H, a->De, N);
             d.beta = zb; d.split_k = -1;
             RC(gemm(d, sa2));
-            RC(rank1_update(b.DGCOL[2], a->video, g->g_w_ih[2] + E, cin[2], 4 * H, a->Dv, false, sa2));          // K = 1: no GEMM launch
-            if (g->g_video) RC(vec_mat(b.DGCOL[2], a->w_ih[2] + E, cin[2], g->g_video, 4 * H, a->Dv, sa2));
+            RC(scene_grads(sa2, false));
             RC(handover_mark(ECHR_HANDOVER_LSTM, sa2));          // every gradient of core.layer0..2 is final here
             if (do_pb && !dxt_done) RC(dxt_chain(sa2));
             if (hipEventRecord(tail().done3, sa2) != hipSuccess) { set_error("decoder_bwd: event record failed"); return -5; }
@@ -1766,8 +1843,7 @@ int echr::decoder_bwd_parts(const echr_dec_args* a, const echr_dec_grads* g, con
         d = desc_tn(b.DGSUM[0], 4 * H, a->event, a->De, g->g_w_ih[0] + E, cin[0], 4 * H, a->De, N);
         d.beta = zb; d.split_k = -1;
         RC(gemm(d, st));
-        RC(rank1_update(b.DGCOL[2], a->video, g->g_w_ih[2] + E, cin[2], 4 * H, a->Dv, false, st));
-        if (g->g_video) RC(vec_mat(b.DGCOL[2], a->w_ih[2] + E, cin[2], g->g_video, 4 * H, a->Dv, st));
+        RC(scene_grads(st, false));
         return 0;
     }
     RC(wgrad(zb, st));          // W_hh_k, W_ih_k[:, :E], W_ih1[:, E:], W_h2a: sums over timesteps
@@ -1795,8 +1871,7 @@ int echr::decoder_bwd_parts(const echr_dec_args* a, const echr_dec_grads* g, con
     d = desc_nn(b.DGSUM[0], 4 * H, a->w_ih[0] + E, cin[0], g->g_event, a->De, N, a->De, 4 * H);
     d.split_k = -1; d.beta = 1.f;                                // zeroed with the backward scratch above
     RC(gemm(d, st));
-    RC(rank1_update(b.DGCOL[2], a->video, g->g_w_ih[2] + E, cin[2], 4 * H, a->Dv, false, st));
-    if (g->g_video) RC(vec_mat(b.DGCOL[2], a->w_ih[2] + E, cin[2], g->g_video, 4 * H, a->Dv, st));
+    RC(scene_grads(st, !z));          // (the non-accumulating form has formed every stream's per-event sums above)
     return 0;
     };
     // phase 0 + async_tail: nothing downstream in the backward pass needs part B's outputs -> second stream, joined by the caller.  Its three
@@ -2107,6 +2182,12 @@ extern "C" int echr_decoder_sample_train(const echr_sample_args* sa, const echr_
     ECHR_REQUIRE(sa->multinomial, "decoder_sample_train: the training-mode decode is the multinomial one (multinomial = 1)");
     return decoder_sample_impl(sa, drop, stream);
 }
+extern "C" int echr_decoder_sample_batch(const echr_sample_args* sa, const echr_batch_ext* x, void* stream) {
+    ECHR_REQUIRE(sa && !sa->multinomial, "decoder_sample_batch: the batched decode is the greedy one (multinomial = 0)");
+    RC(check_batch(&sa->dec, x, "decoder_sample_batch"));
+    BatchScope scope(x);
+    return decoder_sample_impl(sa, nullptr, stream);
+}
 static int decoder_sample_impl(const echr_sample_args* sa, const echr_dropout* drop, void* stream) {
     ECHR_REQUIRE(sa, "decoder_sample: null args");
     RC(persist_check_async());
@@ -2155,7 +2236,8 @@ static int decoder_sample_impl(const echr_sample_args* sa, const echr_dropout* d
             RC(persist_logit_image(a.w_logit, a.V1, tb.LIMG, st));
         }
         PersistSampleBufs B;
-        B.PALL = w.PALL; B.EVB0 = w.EVB0; B.VIDB = w.VIDB; B.xws = s.PSX;
+        B.PALL = w.PALL; B.EVB0 = w.EVB0; B.VIDB = scene_base(&a, w); B.xws = s.PSX;
+        B.vidb_ld = batch_ext() ? 4L * H : 0;          // multi-video batch: the scene part of stream 2 is per event
         for (int k = 0; k < 3; ++k) B.TG[k] = tb.TG[k];
         B.limg = tb.LIMG; B.sws = s.PSWS;
         B.seq = reinterpret_cast<long long*>(sa->seq); B.seq_logp = sa->seq_logp; B.n_unfinished = sa->n_unfinished;

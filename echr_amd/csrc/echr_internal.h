@@ -56,7 +56,8 @@ long persist_bwd_ws_floats(int S);
 bool persist_bwd_eligible(const echr_dec_args* a);
 int persist_bwd(const echr_dec_args* a, const PersistBwdBufs& B, const DropCfg& dh, const DropCfg& dout, hipStream_t st);
 // greedy decoding on the persistent kernels (64 events per launch, every step on device): see PersistS in csrc/persist.hip
-struct PersistSampleBufs { float* PALL; const float* EVB0; const float* VIDB; float* xws; const float* TG[3]; const float* limg; float* sws; long long* seq; float* seq_logp; int* n_unfinished; };
+struct PersistSampleBufs { float* PALL; const float* EVB0; const float* VIDB; float* xws; const float* TG[3]; const float* limg; float* sws; long long* seq; float* seq_logp; int* n_unfinished;
+                           long vidb_ld = 0; };          // vidb_ld: row pitch of VIDB (0: one [4H] vector for every event; 4H: one row per event, multi-video batches)
 long persist_sample_ws_floats(int S, int V1);          // per group of 64 events
 long persist_sample_x_floats(int S);                   // per group of 64 events
 long persist_logit_image_floats(int V1);
@@ -204,6 +205,25 @@ int logsoftmax_nll_dlg(const float* X, long ld, const void* target, int tgt64, c
 int nll_rows_sum(const float* row_loss, int NS, const float* msum, float* loss, hipStream_t st, bool rw = false);
 // RewardCriterion's loss from log-probs [N,S,V1]: out = (sum(-logp[target] * rw) / sum(mask), sum(mask))
 int nll_loss_rw(const float* logp, const void* target, int tgt64, const float* mask, const float* rw, float* loss, int N, int S, int V1, hipStream_t st);
+
+// Multi-video batches (echr_batch_ext, include/echr_hip.h).  The *_batch entry points publish their extension for the duration of the call;
+// the shared code paths read it here -- nullptr on every single-video entry, which then runs exactly what it ran before:
+//   event encoder: block-diagonal softmax by vid; decoder: per-row scene part of stream 2's gates and its segmented gradients;
+//   criterion: the weighted (rw) form with denominator 1 -- the per-video normalisers sum(mask_v) + 1e-6 arrive inside the weights
+const echr_batch_ext* batch_ext();
+struct BatchScope {
+    const echr_batch_ext* prev;
+    explicit BatchScope(const echr_batch_ext* x);
+    ~BatchScope();
+};
+inline int crit_unit_den() { return batch_ext() ? 1 : 0; }
+// out[v*ld + c] = sum over the rows n with vid[n] == v of X[n*ld + c], rows added in ascending n (fixed order: bit-reproducible)
+int seg_rowsum(const float* X, const int* vid, int N, int V, int cols, long ld, float* out, hipStream_t st);
+// per-video losses of a batch: vloss[v] = sum of row_loss over the rows of video v (row i is the time-major row act[i], or i itself) ...
+int video_loss_rows(const float* row_loss, const int* act, int rows, int N, const int* vid, int V, float* vloss, hipStream_t st);
+// ... or from log-probs [N,S,V1]: vloss[v] = sum over the events n of video v and t of -logp[n,t,target[n,t]] * w[n,t]
+int video_loss_logp(const float* logp, const void* target, int tgt64, const float* w, int N, int S, int V1, const int* vid, int V, float* vloss, hipStream_t st);
+int decoder_fused_video_loss(const echr_dec_args* a, const echr_dec_grads* g, const int* vid, int V, float* vloss, hipStream_t st);
 
 // echr_decoder_fwd with the criterion fused behind the logits product: g carries nll_target / nll_mask / g_loss / ws_bwd; d logits land in ws_bwd
 // (echr_dec_grads.dlg_ready = 1 for the echr_decoder_bwd that follows); returns through *fused whether the fused form applied

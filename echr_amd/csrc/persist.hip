@@ -932,7 +932,8 @@ constexpr int LCHMAX = 3;                      // column chunks of LWG x LCOLS a
 struct PersistS {
     const float* TG[3];            // [V1][4H] token-side gate pre-activations per stream (stream 1: biases folded in)
     const float* base0;            // [N][4H] event part of stream 0 (+ biases)
-    const float* base2;            // [4H] video part of stream 2 (+ biases)
+    const float* base2;            // [4H] video part of stream 2 (+ biases); multi-video batches: [N][4H], one row per event (base2_ld = 4H)
+    long base2_ld;                 // row pitch of base2: 0 = the one vector serves every event
     unsigned long long* KEY;       // [S][64] arg-max keys: ordered(value) << 32 | ~index
     u32* cnt_tok;                  // [S] counters: logits workgroups that have folded step t
     const float4* LIMG;            // logit weights as fp16-pair planes [workgroup 64][stream 3][k step 16][tile 5][plane 2][lane 64] x 16 bytes
@@ -1807,7 +1808,7 @@ __device__ __forceinline__ void dec_persist_lstm_samp_body(const PersistK& P, co
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
             rec[rd][g] = 0.f;
-            base[rd][g] = k == 0 ? Q.base0[(long)min(n, N - 1) * 4 * PH + g * PH + j] : Q.base2[g * PH + j];
+            base[rd][g] = k == 0 ? Q.base0[(long)min(n, N - 1) * 4 * PH + g * PH + j] : Q.base2[(long)min(n, N - 1) * Q.base2_ld + g * PH + j];
         }
     }
     const u32 XB = PROWS * PH * 4, XBH = HR * PH * 4;
@@ -3508,7 +3509,7 @@ int persist_sample(const echr_dec_args* a, const PersistSampleBufs& B, hipStream
         p.N = a->N - n0 < PROWS ? a->N - n0 : PROWS;
         p.ev_start = a->ev_start + n0; p.ev_len = a->ev_len + n0;
         PersistSampleBufs Bg = B;
-        Bg.EVB0 = B.EVB0 + (long)n0 * 4 * PH; Bg.xws = B.xws + (long)g * sx; Bg.sws = B.sws + (long)g * ss;
+        Bg.EVB0 = B.EVB0 + (long)n0 * 4 * PH; Bg.VIDB = B.VIDB + (long)n0 * B.vidb_ld; Bg.xws = B.xws + (long)g * sx; Bg.sws = B.sws + (long)g * ss;
         if (int rc = persist_sample_group(&p, Bg, groups == 1, st)) return rc;
     }
     hipLaunchKernelGGL(sample_finish_kernel, dim3(a->N), dim3(256), 0, st, reinterpret_cast<const unsigned long long*>(B.sws + LS.key), B.sws + LS.lse, a->N, a->S,
@@ -3561,7 +3562,7 @@ static int persist_sample_group(const echr_dec_args* a, const PersistSampleBufs&
     K2.spin_limit = K.spin_limit; K2.inject = K.inject;
     PersistS Q;
     for (int k = 0; k < 3; ++k) Q.TG[k] = B.TG[k];
-    Q.base0 = B.EVB0; Q.base2 = B.VIDB;
+    Q.base0 = B.EVB0; Q.base2 = B.VIDB; Q.base2_ld = B.vidb_ld;
     Q.KEY = reinterpret_cast<unsigned long long*>(B.sws + LS.key);
     Q.cnt_tok = reinterpret_cast<u32*>(B.sws + LS.cnt);
     Q.LIMG = reinterpret_cast<const float4*>(B.limg);

@@ -17,7 +17,7 @@ namespace echr {
 
 static inline long up64(long n) { return (n + 63) / 64 * 64; }
 struct StepWs { long idx, ech, tsrm_ws, event, logp, dec_ws, dec_ws_bwd, g_event, g_ech, tsrm_ws_bwd, h0, g_h0, init_feats, init_dfeats, g_video, g_video_init,
-                 rows, row_grad, total; };
+                 rows, row_grad, batch, total; };
 
 static inline int init_feats_width(const echr_train_step_args* a) {
     return (a->init_use_v ? a->dec.Dv : 0) + (a->init_use_e ? a->dec.De : 0) + (a->init_use_c ? a->dec.D : 0);
@@ -25,13 +25,14 @@ static inline int init_feats_width(const echr_train_step_args* a) {
 
 // rw: echr_train_step_rw -- the index region holds the criterion weights [N,S] too (host_nll = 1)
 // x: echr_train_step_clip -- the 'CC+CH' row source [Tv, Dc + Ht] and the clip-row gradient's scratch
-static StepWs carve_step(const echr_train_step_args* a, bool rw = false, const echr_clip_step_args* x = nullptr) {
+// bx: echr_train_step_batch -- the index region ends with vid [N]; the batch scratch (echr_batch_ws_floats) is carved here too
+static StepWs carve_step(const echr_train_step_args* a, bool rw = false, const echr_clip_step_args* x = nullptr, const echr_batch_ext* bx = nullptr) {
     StepWs w;
     long off = 0;
     auto take = [&](long n) { long o = off; off += up64(n); return o; };
     const echr_tsrm_args& t = a->tsrm;
     const echr_dec_args& d = a->dec;
-    w.idx = take((long)(3 + (rw ? 5 : 4) * d.S) * d.N);  // int32: ev_start | ev_len | ind | tokens [S,N] | active rows [<= S*N] | targets [N,S] | mask fp32 [N,S]
+    w.idx = take((long)(3 + (rw ? 5 : 4) * d.S) * d.N + (bx ? (long)d.N : 0));  // int32: ev_start | ev_len | ind | tokens [S,N] | active rows [<= S*N] | targets [N,S] | mask fp32 [N,S]
                                                           // (| weights fp32 [N,S] with rw)
     w.ech = take((long)t.N * t.Din);
     w.tsrm_ws = take(echr_tsrm_ws_floats(t.N, t.Din, t.Df, t.Do, t.G));
@@ -54,6 +55,7 @@ static StepWs carve_step(const echr_train_step_args* a, bool rw = false, const e
         if (x->clip_parts == 3) w.rows = take((long)d.Tv * d.D);
         w.row_grad = take(echr_decoder_row_grad_ws_floats(&d, a->Ht > 0 ? a->Ht : 1));
     }
+    w.batch = bx ? take(echr_batch_ws_floats(d.N, bx->n_videos, d.H)) : -1;
     w.total = off;
     return w;
 }
@@ -194,8 +196,9 @@ static echr_dec_args step_dec_args(const echr_train_step_args* a, const StepWs& 
     d.h0 = a->w_init ? a->ws + L.h0 : nullptr;
     return d;
 }
-static size_t step_index_count(const echr_train_step_args* a, bool rw = false) {
-    return (size_t)(3 + a->dec.S) * a->dec.N + (size_t)a->n_active + (a->host_nll ? (rw ? 3 : 2) * (size_t)a->dec.S * a->dec.N : 0);
+static size_t step_index_count(const echr_train_step_args* a, bool rw = false, const echr_batch_ext* bx = nullptr) {
+    return (size_t)(3 + a->dec.S) * a->dec.N + (size_t)a->n_active + (a->host_nll ? (rw ? 3 : 2) * (size_t)a->dec.S * a->dec.N : 0) +
+           (bx ? (size_t)a->dec.N : 0);
 }
 
 // Optional first half of echr_train_step for the joint 'tap_cg' iteration (train.py:300-313): everything of the call that does not read
@@ -225,7 +228,8 @@ extern "C" int echr_train_step_prepare(const echr_train_step_args* a, void* stre
     return rc;
 }
 
-static int train_step_impl(const echr_train_step_args* a, void* stream, bool rw, const float* rw_dev, const echr_clip_step_args* x = nullptr);
+static int train_step_impl(const echr_train_step_args* a, void* stream, bool rw, const float* rw_dev, const echr_clip_step_args* x = nullptr,
+                           const echr_batch_ext* bx = nullptr, float* video_loss = nullptr);
 extern "C" int echr_train_step(const echr_train_step_args* a, void* stream) { return train_step_impl(a, stream, false, nullptr); }
 // Frame-level context 'CH' / 'CC+CH' (include/echr_hip.h): the same iteration with tap_feats (or [c3d | tap]) as the attended rows and the
 // clip-row gradient added to g_tap behind the join of the backward's helper streams
@@ -256,7 +260,24 @@ extern "C" int echr_train_step_rw(const echr_train_step_args* a, const float* we
     ECHR_REQUIRE(!a->prepared, "train_step_rw: echr_train_step_prepare does not take the weights (prepared must be 0)");
     return train_step_impl(a, stream, true, a->host_nll ? nullptr : weight);
 }
-static int train_step_impl(const echr_train_step_args* a, void* stream, bool rw, const float* rw_dev, const echr_clip_step_args* x) {
+// Multi-video batch (include/echr_hip.h): the same iteration over the events of V videos.  What differs sits in the pieces the call sequences --
+// per-video scene vectors and their segmented gradients (decoder.hip), the block-diagonal event encoder (tsrm.hip), the criterion's
+// per-video normalisers inside the weights (core.hip) -- which read the extension published here; this file stages vid with
+// the other index vectors and adds the per-video losses.  Stage-ahead, the applied-update count and the asynchronous failure reports are
+// those of echr_train_step: the same code runs.
+extern "C" int64_t echr_train_step_batch_ws_floats(const echr_train_step_args* a, const echr_batch_ext* x) {
+    return (a && x && x->n_videos > 0) ? carve_step(a, true, nullptr, x).total : -1;
+}
+extern "C" int echr_train_step_batch(const echr_train_step_args* a, const echr_batch_ext* x, const float* weight, float* video_loss, void* stream) {
+    ECHR_REQUIRE(a && x && x->n_videos > 0 && x->n_videos <= a->dec.N && x->video, "train_step_batch: the batch extension needs 0 < n_videos <= N and video");
+    ECHR_REQUIRE(a->host_nll || weight, "train_step_batch: the criterion weights are missing (device `weight`, or host_index with host_nll = 1)");
+    ECHR_REQUIRE(!(a->host_nll && weight), "train_step_batch: host_nll = 1 carries the weights in host_index: pass weight = NULL");
+    ECHR_REQUIRE(!a->prepared && !a->defer_update && !a->g_tap && !a->handover, "train_step_batch: prepared, defer_update, g_tap and handover are not part of the batched step");
+    ECHR_REQUIRE(!a->w_init, "train_step_batch: an initial state (CG_init_feats_type) is not part of the batched step");
+    return train_step_impl(a, stream, true, a->host_nll ? nullptr : weight, nullptr, x, video_loss);
+}
+static int train_step_impl(const echr_train_step_args* a, void* stream, bool rw, const float* rw_dev, const echr_clip_step_args* x, const echr_batch_ext* bx,
+                           float* video_loss) {
     ECHR_REQUIRE(a && a->ws && a->host_index && a->loss && a->g_loss && a->flat_g && (a->tap || a->event_parts == 1), "train_step: missing buffers");
     ECHR_REQUIRE(!a->prepared || a->overlap_encoder, "train_step: prepared = 1 needs overlap_encoder = 1");
     const int parts = a->event_parts ? a->event_parts : 3;
@@ -271,9 +292,9 @@ static int train_step_impl(const echr_train_step_args* a, void* stream, bool rw,
     ECHR_REQUIRE(!a->do_step || (a->flat_p && a->adam_m && a->adam_v && a->adam_step >= 1), "train_step: optimiser state missing");
     hipStream_t st = (hipStream_t)stream;
     RC(join_tail(st));          // (a deferred update of the previous call: it reads the index region this call is about to restage)
-    const StepWs L = carve_step(a, rw, x);
+    const StepWs L = carve_step(a, rw, x, bx);
     ECHR_REQUIRE(a->ws_floats >= L.total, "train_step: workspace holds %lld floats, %ld needed (echr_train_step%s_ws_floats)", (long long)a->ws_floats, L.total,
-                 x ? "_clip" : (rw ? "_rw" : ""));
+                 bx ? "_batch" : (x ? "_clip" : (rw ? "_rw" : "")));
     float* ws = a->ws;
     // 'CC+CH': the row source [c3d | tap] is formed first, ahead of every fork of this call (the decoder's event-independent part reads it)
     if (x && x->clip_parts == 3) RC(clip_rows(c3d, Dc, a->tap, a->Ht, ws + L.rows, a->dec.Tv, st));
@@ -288,7 +309,7 @@ static int train_step_impl(const echr_train_step_args* a, void* stream, bool rw,
     if (ahead) {
         hipStream_t ts = tail_stream_raw();
         if (hipStreamWaitEvent(ts, sa.pre, 0) != hipSuccess) { set_error("train_step: stream wait failed"); return -5; }
-        RC(stage_indices(a->host_index, idx, sizeof(int32_t) * step_index_count(a, rw), ts));
+        RC(stage_indices(a->host_index, idx, sizeof(int32_t) * step_index_count(a, rw, bx), ts));
         // the caller's stream: behind the staging copy (its own position is already behind the update).  The prepare stream: behind the
         // caller's stream's position AT ENTRY -- the update, and whatever the caller queued since (this call's inputs: an upload of the next
         // video's features, the proposal encoder's forward; a write to the parameters) -- since the staging event it forks from no longer
@@ -296,7 +317,16 @@ static int train_step_impl(const echr_train_step_args* a, void* stream, bool rw,
         if (hipEventRecord(sa.post, st) != hipSuccess) { set_error("train_step: event record failed"); return -5; }
         RC(prep_stream_wait(sa.post));
         if (hipStreamWaitEvent(st, ring_last(), 0) != hipSuccess) { set_error("train_step: stream wait failed"); return -5; }
-    } else if (!a->prepared) RC(stage_indices(a->host_index, idx, sizeof(int32_t) * step_index_count(a, rw), st));
+    } else if (!a->prepared) RC(stage_indices(a->host_index, idx, sizeof(int32_t) * step_index_count(a, rw, bx), st));
+    // multi-video batch: vid is the tail of the staged index region, the batch scratch a piece of `ws`; everything below reads the extension
+    // through batch_ext()
+    echr_batch_ext bxl;
+    if (bx) {
+        bxl = *bx;
+        bxl.vid = idx + step_index_count(a, rw, nullptr);
+        bxl.ws = ws + L.batch;
+    }
+    BatchScope scope(bx ? &bxl : nullptr);
     const int32_t *ev_start = idx, *ev_len = idx + N, *ind = idx + 2 * N, *active = idx + (3 + S) * N;          // (tokens at idx + 3 N: step_dec_args)
     const void* nll_target = a->nll_target;
     const float* nll_mask = a->nll_mask;
@@ -367,6 +397,8 @@ static int train_step_impl(const echr_train_step_args* a, void* stream, bool rw,
         if (nll_i64) RC(echr_nll_loss_fwd_i64(d.logp, static_cast<const int64_t*>(nll_target), nll_mask, a->loss, N, S, d.V1, stream));
         else RC(echr_nll_loss_fwd(d.logp, static_cast<const int32_t*>(nll_target), nll_mask, a->loss, N, S, d.V1, stream));
     }
+    // (a statement of its own behind the criterion chain above: the per-video losses of a batch from the log-probs)
+    if (bx && video_loss && !fused_nll) RC(video_loss_logp(d.logp, nll_target, nll_i64, crit_w, N, S, d.V1, bxl.vid, bxl.n_videos, video_loss, st));
     if (a->forward_only) return 0;
     step_mark(1, st);
     g.dlg_ready = fused_nll ? 1 : 0;
@@ -418,6 +450,7 @@ static int train_step_impl(const echr_train_step_args* a, void* stream, bool rw,
     RC(echr_tsrm_bwd(&t, &tg, &a->drop, stream));
     if (a->g_tap && De_tap > 0) RC(echr_event_pool_gather_bwd(ws + L.g_ech, ind, a->g_tap, N, De_c3d, De_tap, stream));
     if (fused_nll) RC(decoder_fused_loss(&d, &g, a->loss, st, crit_w != nullptr));
+    if (fused_nll && bx && video_loss) RC(decoder_fused_video_loss(&d, &g, bxl.vid, bxl.n_videos, video_loss, st));
     step_mark(3, st);
     RC(echr_stream_join(stream));          // the decoder backward's asynchronous tail: every gradient is final in `stream` order now
     if (x && a->g_tap) {

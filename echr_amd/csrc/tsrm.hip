@@ -93,20 +93,25 @@ __device__ __forceinline__ void fst_grad(int mode, float gate, float aff, float 
 }
 
 // one wave per (event n, head g): w[m] = softmax_m(gate[n,m,g] * aff[g,n,m]); wd = w * dropout
+// vid (multi-video batches, nullptr otherwise): the softmax runs over the events m of n's own video; every other pair stores weight 0 in WSM
+// and WD.  The backward kernels then need no mask: ds = wsm * (dw - sum) is exactly 0 where wsm is 0, and so are d gate and d aff.
 __global__ __launch_bounds__(64) void tsrm_softmax_fwd_kernel(const float* __restrict__ GATE, const float* __restrict__ AFF,
-                                                              float* __restrict__ WSM, float* __restrict__ WD, int N, int G, DropCfg dc, int mode) {
+                                                              float* __restrict__ WSM, float* __restrict__ WD, int N, int G, DropCfg dc, int mode,
+                                                              const int* __restrict__ vid) {
     const int n = blockIdx.x, g = blockIdx.y, lane = threadIdx.x;
     const float* aff = AFF + ((long)g * N + n) * N;
     auto gt = [&](int j) { return mode == 4 ? 0.f : GATE[((long)n * N + j) * G + g]; };
+    const int vn = vid ? vid[n] : 0;
+    auto same = [&](int j) { return !vid || vid[j] == vn; };
     float m = -INFINITY;
-    for (int j = lane; j < N; j += 64) m = fmaxf(m, fst_combine(mode, gt(j), aff[j]));
+    for (int j = lane; j < N; j += 64) if (same(j)) m = fmaxf(m, fst_combine(mode, gt(j), aff[j]));
     m = wave_max(m);
     float s = 0.f;
-    for (int j = lane; j < N; j += 64) s += expf(fst_combine(mode, gt(j), aff[j]) - m);
+    for (int j = lane; j < N; j += 64) if (same(j)) s += expf(fst_combine(mode, gt(j), aff[j]) - m);
     s = wave_sum(s);
     const float inv = 1.f / s;
     for (int j = lane; j < N; j += 64) {
-        const float w = expf(fst_combine(mode, gt(j), aff[j]) - m) * inv;
+        const float w = same(j) ? expf(fst_combine(mode, gt(j), aff[j]) - m) * inv : 0.f;
         const long o = ((long)g * N + n) * N + j;
         WSM[o] = w;
         WD[o] = w * drop_mult(dc, (unsigned)(((long)n * G + g) * N + j), 0u, SITE_TSRM);
@@ -117,23 +122,26 @@ __global__ __launch_bounds__(64) void tsrm_softmax_fwd_kernel(const float* __res
 // coalesced -- in LDS (row pitch G + 1: conflict-free column reads), then each wave takes heads g = wave, wave + 4, ... and streams
 // the affinity row of (g, n), contiguous over m.  The form above reads the gates 64 bytes apart, three times (0.29 ms at N = 1000).
 __global__ __launch_bounds__(256) void tsrm_softmax_rows_kernel(const float* __restrict__ GATE, const float* __restrict__ AFF,
-                                                               float* __restrict__ WSM, float* __restrict__ WD, int N, int G, DropCfg dc, int mode) {
+                                                               float* __restrict__ WSM, float* __restrict__ WD, int N, int G, DropCfg dc, int mode,
+                                                               const int* __restrict__ vid) {
     extern __shared__ float sg[];                      // [N][G + 1]
     const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6, P = G + 1;
+    const int vn = vid ? vid[n] : 0;
+    auto same = [&](int j) { return !vid || vid[j] == vn; };          // (multi-video batches: see tsrm_softmax_fwd_kernel)
     const float* gp = GATE + (long)n * N * G;
     for (int i = tid; i < N * G; i += 256) sg[(i / G) * P + (i % G)] = mode == 4 ? 0.f : gp[i];
     __syncthreads();
     for (int g = w; g < G; g += 4) {
         const float* aff = AFF + ((long)g * N + n) * N;
         float m = -INFINITY;
-        for (int j = lane; j < N; j += 64) m = fmaxf(m, fst_combine(mode, sg[j * P + g], aff[j]));
+        for (int j = lane; j < N; j += 64) if (same(j)) m = fmaxf(m, fst_combine(mode, sg[j * P + g], aff[j]));
         m = wave_max(m);
         float s = 0.f;
-        for (int j = lane; j < N; j += 64) s += expf(fst_combine(mode, sg[j * P + g], aff[j]) - m);
+        for (int j = lane; j < N; j += 64) if (same(j)) s += expf(fst_combine(mode, sg[j * P + g], aff[j]) - m);
         s = wave_sum(s);
         const float inv = 1.f / s;
         for (int j = lane; j < N; j += 64) {
-            const float wv = expf(fst_combine(mode, sg[j * P + g], aff[j]) - m) * inv;
+            const float wv = same(j) ? expf(fst_combine(mode, sg[j * P + g], aff[j]) - m) * inv : 0.f;
             const long o = ((long)g * N + n) * N + j;
             WSM[o] = wv;
             WD[o] = wv * drop_mult(dc, (unsigned)(((long)n * G + g) * N + j), 0u, SITE_TSRM);
@@ -202,11 +210,14 @@ __device__ __forceinline__ float head_contract(const float* srow, const float (&
 __global__ __launch_bounds__(64) void tsrm_rowhead_fwd_kernel(const float* __restrict__ Q, const float* __restrict__ K, const float* __restrict__ XW,
                                                               const float* __restrict__ GATE, const float* __restrict__ b_out,
                                                               float* __restrict__ AFF, float* __restrict__ WSM, float* __restrict__ WD,
-                                                              float* __restrict__ OUT, int N, int Df, int Do, int G, float scale, DropCfg dc, int mode) {
+                                                              float* __restrict__ OUT, int N, int Df, int Do, int G, float scale, DropCfg dc, int mode,
+                                                              const int* __restrict__ vid) {
     __shared__ __attribute__((aligned(16))) float sw[HEAD_MAXN];
     constexpr int DG = HEAD_DG;
     const int r = blockIdx.x, g = blockIdx.y, j = threadIdx.x;
     const bool on = j < N;
+    // multi-video batches: lane j takes part in row r's softmax only when both events belong to one video (weight 0 otherwise, stored)
+    const bool in = on && (!vid || vid[j] == vid[r]);
     const float gate = (on && mode != 4) ? GATE[((long)r * N + j) * G + g] : 0.f;
     float kj[DG], xw[DG];
     head_row32(K + (long)j * Df + g * DG, kj, on);
@@ -217,12 +228,12 @@ __global__ __launch_bounds__(64) void tsrm_rowhead_fwd_kernel(const float* __res
     for (int k = 0; k < DG; ++k) acc = fmaf(qr[k], kj[k], acc);
     const float aff = scale * acc;
     // gated softmax over j (the arithmetic of tsrm_softmax_fwd_kernel)
-    const float v = on ? fst_combine(mode, gate, aff) : -INFINITY;
+    const float v = in ? fst_combine(mode, gate, aff) : -INFINITY;
     const float m = wave_max(v);
-    const float e = on ? expf(v - m) : 0.f;
+    const float e = in ? expf(v - m) : 0.f;
     const float inv = 1.f / wave_sum(e);
     const float w = e * inv;
-    const float wd = on ? w * drop_mult(dc, (unsigned)(((long)r * G + g) * N + j), 0u, SITE_TSRM) : 0.f;
+    const float wd = in ? w * drop_mult(dc, (unsigned)(((long)r * G + g) * N + j), 0u, SITE_TSRM) : 0.f;
     if (on) {
         const long o = ((long)g * N + r) * N + j;
         AFF[o] = aff;
@@ -657,6 +668,20 @@ extern "C" int echr_tsrm_fwd(const echr_tsrm_args* a, const echr_dropout* drop, 
     RC(check(a, "tsrm_fwd"));
     return tsrm_fwd_impl(a, drop, stream, nullptr, nullptr);
 }
+static int check_batch_ext(const echr_batch_ext* x, const char* who) {
+    ECHR_REQUIRE(x && x->n_videos > 0 && x->vid, "%s: the batch extension needs n_videos > 0 and vid", who);
+    return 0;
+}
+extern "C" int echr_tsrm_fwd_batch(const echr_tsrm_args* a, const echr_dropout* drop, const echr_batch_ext* x, void* stream) {
+    RC(check_batch_ext(x, "tsrm_fwd_batch"));
+    BatchScope scope(x);
+    return echr_tsrm_fwd(a, drop, stream);
+}
+extern "C" int echr_tsrm_bwd_batch(const echr_tsrm_args* a, const echr_tsrm_grads* g, const echr_dropout* drop, const echr_batch_ext* x, void* stream) {
+    RC(check_batch_ext(x, "tsrm_bwd_batch"));
+    BatchScope scope(x);          // (nothing in the backward reads it: the saved weights of cross-video pairs are 0, see tsrm_softmax_fwd_kernel)
+    return echr_tsrm_bwd(a, g, drop, stream);
+}
 
 // attention_module_multi_head.forward on its own (MA_attention_8_NEW.py:101-177): the caller hands in the already embedded events
 // roi_feat [N,Df] and the pairwise position embedding [N,N,Df]; inference-style entry (fST0, use_posit = 1)
@@ -816,11 +841,12 @@ static int tsrm_fwd_impl(const echr_tsrm_args* a, const echr_dropout* drop, void
         else for (int i = 0; i < 3; ++i) RC(gemm(q3[i], st));
     }
     const DropCfg dc = make_drop(drop, drop ? drop->p_tsrm : 0.f);
+    const int* vid = batch_ext() ? batch_ext()->vid : nullptr;          // multi-video batch: block-diagonal softmax
     if (head_fused_ok(N, Df, Do, G)) {
         // few events: affinities, gated softmax, dropout and the weighted sum in one launch, one wave per (event, head) (:138-160)
         if (fork) RC(aux_join(st));
         hipLaunchKernelGGL(tsrm_rowhead_fwd_kernel, dim3(N, G), dim3(64), 0, st, w.Q, w.K, w.XW, w.GATE, a->b_out, w.AFF, w.WSM, w.WD, a->out,
-                           N, Df, Do, G, 1.0f / sqrtf((float)dgq), dc, mode);
+                           N, Df, Do, G, 1.0f / sqrtf((float)dgq), dc, mode, vid);
         return check_launch("tsrm_rowhead_fwd");
     }
     // per-head scaled affinities AFF[g] = Q_g . K_g^T / sqrt(dgq)   (:138-140)
@@ -837,9 +863,9 @@ static int tsrm_fwd_impl(const echr_tsrm_args* a, const echr_dropout* drop, void
         rows_attr.store(ok ? 1 : 2, std::memory_order_relaxed);
     }
     if (N >= 128 && sm_rows <= 150 * 1024 && rows_attr.load(std::memory_order_relaxed) == 1) {
-        hipLaunchKernelGGL(tsrm_softmax_rows_kernel, dim3(N), dim3(256), sm_rows, st, w.GATE, w.AFF, w.WSM, w.WD, N, G, dc, mode);
+        hipLaunchKernelGGL(tsrm_softmax_rows_kernel, dim3(N), dim3(256), sm_rows, st, w.GATE, w.AFF, w.WSM, w.WD, N, G, dc, mode, vid);
     } else {
-        hipLaunchKernelGGL(tsrm_softmax_fwd_kernel, dim3(N, G), dim3(64), 0, st, w.GATE, w.AFF, w.WSM, w.WD, N, G, dc, mode);
+        hipLaunchKernelGGL(tsrm_softmax_fwd_kernel, dim3(N, G), dim3(64), 0, st, w.GATE, w.AFF, w.WSM, w.WD, N, G, dc, mode, vid);
     }
     RC(check_launch("tsrm_softmax_fwd"));
     // OUT[:, g] = WD_g . XW_g + b_out_g

@@ -157,53 +157,97 @@ class EventPoolGather(torch.autograd.Function):
 TSRM_PARAMS = ('w_emb', 'b_emb', 'w_fc1', 'b_fc1', 'w_fc2', 'b_fc2', 'w_q', 'b_q', 'w_k', 'b_k', 'w_out', 'b_out')
 
 
+def batch_ext(vid, video=None, g_video=None, n_videos=None, H=None):
+    """(echr_batch_ext, its scratch tensor or None) of a multi-video batch (echr_amd/batch.py): vid int32 [N] device, video / g_video
+    [V, Dv]; H (decoder entries): rnn_size, sizes the scratch the library works in during the call -- keep the tensor alive until the
+    call's kernels have run."""
+    V = int(n_videos if n_videos is not None else video.shape[0])
+    xws = None
+    if H is not None:
+        xws = torch.empty(L.load().echr_batch_ws_floats(vid.numel(), V, int(H)), device=vid.device, dtype=torch.float32)
+    return L.BatchExt(V, L.ptr(vid, torch.int32), L.ptr(video) if video is not None else None,
+                      L.ptr(g_video) if g_video is not None else None, L.ptr(xws) if xws is not None else None), xws
+
+
 class TSRMFunction(torch.autograd.Function):
     """MA_Attention8.forward (MA_attention_8_NEW.py:35-49, :101-177)."""
 
     @staticmethod
     def forward(ctx, ech, ev_start, ev_len, n_head, drop, sink, bounds, *params):
-        # bounds: None or (inference, max_len, max_span[, fst_mode]) = echr_tsrm_args' last fields.  `inference` must be decided by the CALLER
-        # (grad mode is always off inside forward, and needs_input_grad ignores torch.no_grad())
-        lib = L.load()
-        ctx.sink = sink
-        ech = _f32c(ech)
-        ps = [_f32c(p) for p in params]
-        N, Din = ech.shape
-        Df, Do = ps[0].shape[0], ps[10].shape[0]
-        if ps[0].shape[1] != Din:
-            raise L.EchrHipError('event features are %d wide, fusion_model.event_emb expects %d (video_dim + hidden_dim: CaptionGenerator.py:121-125)'
-                                 % (Din, ps[0].shape[1]))
-        ws = torch.empty(lib.echr_tsrm_ws_floats(N, Din, Df, Do, n_head), device=ech.device, dtype=torch.float32)
-        out = torch.empty(N, Do, device=ech.device, dtype=torch.float32)
-        a = L.TsrmArgs(N, Din, Df, Do, n_head, *[L.ptr(p) for p in ps], L.ptr(ech), L.ptr(ev_start, torch.int32),
-                       L.ptr(ev_len, torch.int32), L.ptr(ws), L.ptr(out), *(bounds or (0, 0, 0)))
-        d = drop.c()
-        L.check(lib.echr_tsrm_fwd(C.byref(a), C.byref(d), L.stream_ptr()), 'tsrm_fwd')
-        ctx.save_for_backward(ech, ev_start, ev_len, ws, out, *ps)
-        ctx.meta = (N, Din, Df, Do, n_head, drop, int(a.fst_mode))
-        return out
+        return _tsrm_forward(ctx, ech, ev_start, ev_len, n_head, drop, sink, bounds, params)
 
     @staticmethod
     def backward(ctx, g_out):
-        lib = L.load()
-        ech, ev_start, ev_len, ws, out, *ps = ctx.saved_tensors
-        N, Din, Df, Do, G, drop, fst_mode = ctx.meta
-        g_out = _f32c(g_out)
-        zeroed = 1 if (ctx.sink is not None and ctx.sink.usable()) else 0
-        grads = ctx.sink.take() if zeroed else [torch.empty_like(p) for p in ps]
-        if zeroed:
-            grads[10] = grads[10].view(ps[10].shape)              # linear_out_1.weight [d_o, d_feats, 1, 1] -> [d_o, d_feats]
-        g_ech = torch.empty_like(ech)
-        wsb = torch.empty(lib.echr_tsrm_ws_bwd_floats(N, Din, Df, Do, G), device=ech.device, dtype=torch.float32)
-        a = L.TsrmArgs(N, Din, Df, Do, G, *[L.ptr(p) for p in ps], L.ptr(ech), L.ptr(ev_start, torch.int32),
-                       L.ptr(ev_len, torch.int32), L.ptr(ws), L.ptr(out), 0, 0, 0, fst_mode)
-        g = L.TsrmGrads(*[L.ptr(x) for x in grads], L.ptr(g_ech), L.ptr(g_out), L.ptr(wsb), zeroed)
-        if not zeroed and fst_mode in (3, 4):          # parameters the chosen combination does not reach: the library writes nothing there
-            for i in ((6, 7, 8, 9) if fst_mode == 3 else (2, 3, 4, 5)):
-                grads[i].zero_()
-        d = drop.c()
+        g_ech, grads = _tsrm_backward(ctx, g_out)
+        return (g_ech, None, None, None, None, None, None) + grads
+
+
+class TSRMBatchFunction(torch.autograd.Function):
+    """TSRMFunction over the events of several videos: an event attends to the events of its own video only (`vid` int32 [N] device,
+    non-decreasing; echr_tsrm_fwd_batch / _bwd_batch)."""
+
+    @staticmethod
+    def forward(ctx, ech, ev_start, ev_len, vid, n_videos, n_head, drop, sink, bounds, *params):
+        return _tsrm_forward(ctx, ech, ev_start, ev_len, n_head, drop, sink, bounds, params, batch=(vid, int(n_videos)))
+
+    @staticmethod
+    def backward(ctx, g_out):
+        g_ech, grads = _tsrm_backward(ctx, g_out)
+        return (g_ech, None, None, None, None, None, None, None, None) + grads
+
+
+def _tsrm_forward(ctx, ech, ev_start, ev_len, n_head, drop, sink, bounds, params, batch=None):
+    # bounds: None or (inference, max_len, max_span[, fst_mode]) = echr_tsrm_args' last fields.  `inference` must be decided by the CALLER
+    # (grad mode is always off inside forward, and needs_input_grad ignores torch.no_grad())
+    lib = L.load()
+    ctx.batch = batch
+    ctx.sink = sink
+    ech = _f32c(ech)
+    ps = [_f32c(p) for p in params]
+    N, Din = ech.shape
+    Df, Do = ps[0].shape[0], ps[10].shape[0]
+    if ps[0].shape[1] != Din:
+        raise L.EchrHipError('event features are %d wide, fusion_model.event_emb expects %d (video_dim + hidden_dim: CaptionGenerator.py:121-125)'
+                             % (Din, ps[0].shape[1]))
+    ws = torch.empty(lib.echr_tsrm_ws_floats(N, Din, Df, Do, n_head), device=ech.device, dtype=torch.float32)
+    out = torch.empty(N, Do, device=ech.device, dtype=torch.float32)
+    a = L.TsrmArgs(N, Din, Df, Do, n_head, *[L.ptr(p) for p in ps], L.ptr(ech), L.ptr(ev_start, torch.int32),
+                   L.ptr(ev_len, torch.int32), L.ptr(ws), L.ptr(out), *(bounds or (0, 0, 0)))
+    d = drop.c()
+    if batch is not None:
+        x, _ = batch_ext(batch[0], n_videos=batch[1])
+        L.check(lib.echr_tsrm_fwd_batch(C.byref(a), C.byref(d), C.byref(x), L.stream_ptr()), 'tsrm_fwd_batch')
+    else:
+        L.check(lib.echr_tsrm_fwd(C.byref(a), C.byref(d), L.stream_ptr()), 'tsrm_fwd')
+    ctx.save_for_backward(ech, ev_start, ev_len, ws, out, *ps)
+    ctx.meta = (N, Din, Df, Do, n_head, drop, int(a.fst_mode))
+    return out
+
+
+def _tsrm_backward(ctx, g_out):
+    lib = L.load()
+    ech, ev_start, ev_len, ws, out, *ps = ctx.saved_tensors
+    N, Din, Df, Do, G, drop, fst_mode = ctx.meta
+    g_out = _f32c(g_out)
+    zeroed = 1 if (ctx.sink is not None and ctx.sink.usable()) else 0
+    grads = ctx.sink.take() if zeroed else [torch.empty_like(p) for p in ps]
+    if zeroed:
+        grads[10] = grads[10].view(ps[10].shape)              # linear_out_1.weight [d_o, d_feats, 1, 1] -> [d_o, d_feats]
+    g_ech = torch.empty_like(ech)
+    wsb = torch.empty(lib.echr_tsrm_ws_bwd_floats(N, Din, Df, Do, G), device=ech.device, dtype=torch.float32)
+    a = L.TsrmArgs(N, Din, Df, Do, G, *[L.ptr(p) for p in ps], L.ptr(ech), L.ptr(ev_start, torch.int32),
+                   L.ptr(ev_len, torch.int32), L.ptr(ws), L.ptr(out), 0, 0, 0, fst_mode)
+    g = L.TsrmGrads(*[L.ptr(x) for x in grads], L.ptr(g_ech), L.ptr(g_out), L.ptr(wsb), zeroed)
+    if not zeroed and fst_mode in (3, 4):          # parameters the chosen combination does not reach: the library writes nothing there
+        for i in ((6, 7, 8, 9) if fst_mode == 3 else (2, 3, 4, 5)):
+            grads[i].zero_()
+    d = drop.c()
+    if ctx.batch is not None:
+        x, _ = batch_ext(ctx.batch[0], n_videos=ctx.batch[1])
+        L.check(lib.echr_tsrm_bwd_batch(C.byref(a), C.byref(g), C.byref(d), C.byref(x), L.stream_ptr()), 'tsrm_bwd_batch')
+    else:
         L.check(lib.echr_tsrm_bwd(C.byref(a), C.byref(g), C.byref(d), L.stream_ptr()), 'tsrm_bwd')
-        return (g_ech, None, None, None, None, None, None) + tuple(grads)
+    return g_ech, tuple(grads)
 
 
 def position_embedding(ev_start, ev_len, d_pos):
@@ -231,7 +275,7 @@ def _dec_args(ps, c3d, ev_start, ev_len, event, video, tokens, A, S, ws, logp, d
     H = wh0.shape[1]
     E = embed.shape[1]
     Ha = w_c2a.shape[0]
-    Dv = video.numel()
+    Dv = video.shape[-1]          # ([Dv], or [V, Dv] in a multi-video batch)
     V1 = embed.shape[0]
     assert wi0.shape[1] == E + De and wi1.shape[1] == E + D and wi2.shape[1] == E + Dv, 'LSTM input widths do not match the contexts'
     return L.DecArgs(N, A, Tv, D, H, E, Ha, De, Dv, V1, S, 1 if disjoint else 0,
@@ -331,127 +375,187 @@ class ColMean(torch.autograd.Function):
         return gx
 
 
+class SegColMean(torch.autograd.Function):
+    """ColMean per video of a batch: [V, D] column means over the row segments [row_offset[v], row_offset[v+1]) of the concatenated
+    feature matrix x [sum T_v, D], one launch (echr_seg_col_mean_fwd / _bwd); row_offset int32 [V+1] device."""
+
+    @staticmethod
+    def forward(ctx, x, row_offset):
+        x = _f32c(x)
+        V = row_offset.numel() - 1
+        out = torch.empty(V, x.shape[1], device=x.device, dtype=torch.float32)
+        L.check(L.load().echr_seg_col_mean_fwd(L.ptr(x), L.ptr(row_offset, torch.int32), V, x.shape[1], x.shape[1], L.ptr(out), x.shape[1],
+                                               L.stream_ptr()), 'seg_col_mean_fwd')
+        ctx.save_for_backward(row_offset)
+        ctx.shape = tuple(x.shape)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        (row_offset,) = ctx.saved_tensors
+        T, D = ctx.shape
+        gx = torch.zeros(T, D, device=g.device, dtype=torch.float32)
+        L.check(L.load().echr_seg_col_mean_bwd(L.ptr(_f32c(g)), D, L.ptr(row_offset, torch.int32), row_offset.numel() - 1, D, D, L.ptr(gx),
+                                               L.stream_ptr()), 'seg_col_mean_bwd')
+        return gx, None
+
+
 class DecoderFunction(torch.autograd.Function):
     """OldModel.forward with the ThreeStream core (OldModel_NEW.py:98-137, :376-401, :801-823): log-probs [N,S,V1]."""
 
     @staticmethod
     def forward(ctx, video, event, c3d, ev_start, ev_len, tokens, A, disjoint, drop, sink, prep, h0, tap=None, col0=0, *params):
-        # tap / col0 ('CH', 'CC+CH'): the rows c3d[:, col0 : col0 + tap width] are tap[:Tv]; backward returns d tap (echr_decoder_row_grad)
-        lib = L.load()
-        ctx.sink = sink
-        ctx.tap_meta = (tuple(tap.shape), int(col0)) if tap is not None else None
-        event = _f32c(event)
-        h0 = _f32c(h0) if h0 is not None else None          # [N, 3H] initial state (OldModel.init_hidden, CG_init_feats_type); None = zeros
-        S, N = tokens.shape
-        if prep is not None:          # decoder_prepare() already ran the event-independent part on this workspace
-            video, c3d, ps, logp, ws = prep['video'], prep['c3d'], prep['ps'], prep['logp'], prep['ws']
-            train = prep['train']
-            a = _dec_args(ps, c3d, ev_start, ev_len, event, video, tokens, A, S, ws, logp, disjoint, prepared=1, train=train, h0=h0)
-        else:
-            video, c3d = _f32c(video), _f32c(c3d)
-            ps = [_f32c(p) for p in params]
-            V1 = ps[0].shape[0]
-            logp = torch.empty(N, S, V1, device=event.device, dtype=torch.float32)
-            train = 1 if any(ctx.needs_input_grad) else 0
-            a = _dec_args(ps, c3d, ev_start, ev_len, event, video, tokens, A, S, None, logp, disjoint, train=train, h0=h0)
-            ws = torch.empty(lib.echr_decoder_ws_floats(C.byref(a)), device=event.device, dtype=torch.float32)
-            a.ws = L.ptr(ws)
-        d = drop.c()
-        L.check(lib.echr_decoder_fwd(C.byref(a), C.byref(d), L.stream_ptr()), 'decoder_fwd')
-        ctx.save_for_backward(video, event, c3d, ev_start, ev_len, tokens, ws, logp, *ps)
-        ctx.h0 = h0
-        ctx.meta = (A, S, drop, disjoint, train)
-        return logp
+        return _decoder_forward(ctx, video, event, c3d, ev_start, ev_len, tokens, A, disjoint, drop, sink, prep, h0, tap, col0, params)
 
     @staticmethod
     def backward(ctx, g_logp):
-        lib = L.load()
-        video, event, c3d, ev_start, ev_len, tokens, ws, logp, *ps = ctx.saved_tensors
-        A, S, drop, disjoint, train = ctx.meta
-        # criterion gradient left here in sparse form by MaskedNLL.backward (LanguageModelCriterion on this node's output)
-        pend = ctx.__dict__.pop('_echr_pending_nll', None)     # one entry per LanguageModelCriterion applied to this node's output
-        fused = None
-        if pend:
-            if len(pend) == 1 and getattr(g_logp, '_echr_nll_placeholder', False) and g_logp.stride() == (0, 0, 0):
-                fused, g_logp = pend[0], None
-            else:          # other consumers of the log-probs (or several criteria): their accumulated gradient plus every criterion's dense one
-                for pe in pend:
-                    g_logp = g_logp + MaskedNLL.dense_grad(pe[0], pe[1], pe[2], pe[3], *logp.shape)
-        if g_logp is not None:
-            g_logp = _f32c(g_logp)
-        zeroed = 1 if (ctx.sink is not None and ctx.sink.usable()) else 0
-        zero_span = None
-        if zeroed:
-            grads, zero_span = ctx.sink.take(defer_zero=True)      # zero-filled inside echr_decoder_bwd's first stage (one fill launch less)
-        else:
-            red = getattr(ctx.sink.arena, 'early_reducer', None) if ctx.sink is not None else None
-            if red is not None:
-                red.check_no_backward_while_in_flight()      # accumulating into ranges whose all-reduce already started
-            grads = [torch.empty_like(p) for p in ps]
-            grads[0].zero_()                                 # embedding table gradient is scatter-added
-        g_event = torch.empty_like(event)
-        g_video = torch.empty_like(video) if ctx.needs_input_grad[0] else None
-        h0 = ctx.h0
-        g_h0 = torch.empty_like(h0) if (h0 is not None and ctx.needs_input_grad[11]) else None
-        want_tap = ctx.tap_meta is not None and ctx.needs_input_grad[12]
-        a = _dec_args(ps, c3d, ev_start, ev_len, event, video, tokens, A, S, ws, logp, disjoint, train=train, h0=h0)
-        wsb = torch.empty(lib.echr_decoder_ws_bwd_floats(C.byref(a)), device=event.device, dtype=torch.float32)
-        gp = [L.ptr(x) for x in grads]
-        g = L.DecGrads(gp[0], gp[1], gp[2], (L.c_f * 3)(*gp[3:6]), (L.c_f * 3)(*gp[6:9]), (L.c_f * 3)(*gp[9:12]),
-                       (L.c_f * 3)(*gp[12:15]), gp[15], gp[16], gp[17], gp[18], gp[19], gp[20],
-                       L.ptr(g_event), L.ptr(g_video), L.ptr(g_logp) if g_logp is not None else None,
-                       L.ptr(fused[0], fused[0].dtype) if fused else None, L.ptr(fused[1]) if fused else None, L.ptr(fused[3]) if fused else None,
-                       L.ptr(wsb), zeroed, 0, 0, L.ptr(fused[2][1:2]) if fused else None,
-                       L.ptr(zero_span) if zero_span is not None else None, zero_span.numel() if zero_span is not None else 0,
-                       1 if (fused and fused[0].dtype == torch.int64) else 0, 0, None, 0, L.ptr(g_h0) if g_h0 is not None else None)
-        d = drop.c()
-        hook = getattr(ctx.sink.arena, 'early_grad_hook', None) if zeroed else None
-        staged = hook is not None and getattr(ctx.sink.arena, 'early_staged', True)
-        if staged:
-            # data parallel: hand gradients to the reducer as soon as they are final; it starts their all-reduce on the collective
-            # stream while the next stage runs on this one.  params order = OldModel.native_params():
-            #   [0] embed, [1] logit.weight, [2] logit.bias, [3:6] weight_ih, [6:9] weight_hh, [9:12] bias_ih, [12:15] bias_hh, ...
-            sp = ctx.sink.params
-            for phase, ready in ((1, [sp[1], sp[2]]), (3, list(sp[3:15])), (4, None)):
-                g.phase = phase
-                L.check(lib.echr_decoder_bwd(C.byref(a), C.byref(g), C.byref(d), L.stream_ptr()), 'decoder_bwd')
-                if ready is not None:
-                    hook(ready)
-        else:
-            # arena path: the returned parameter gradients are views that autograd adopts without touching them, so the last stage of
-            # the backward (attention-parameter / embedding gradients) may still be running on the library's second stream while
-            # autograd goes on with the event encoder's backward; an end-of-backward callback joins the streams and only then lets go
-            # of the workspaces that stage reads
-            # (not when a parameter hook would read those gradients inside the backward pass, nor under create_graph, where autograd may
-            # clone them: the gradients must then be final when this Function returns)
-            g.async_tail = 1 if (zeroed and ASYNC_TAIL[0] and not ctx.sink.has_hooks() and not torch.is_grad_enabled()) else 0
-            if g.async_tail and hook is None:
-                # no data-parallel hand-over waits for the LSTM-layer gradients: only d event is formed on this stream, the rest of that stage
-                # runs on the library's second helper stream and is joined with the tail by the end-of-backward callback
-                g.async_tail = 2
-            L.check(lib.echr_decoder_bwd(C.byref(a), C.byref(g), C.byref(d), L.stream_ptr()), 'decoder_bwd')
-            if hook is not None:
-                # data parallel, one-call form: the LSTM-layer gradients (and everything else part A of the backward produced) are final in
-                # stream order now; the reducer starts their all-reduce, which overlaps the asynchronous tail and the event encoder's backward
-                hook(list(ctx.sink.params[3:15]), after_recurrence=True)
-            if g.async_tail and not want_tap:
-                keep = [ws, wsb, logp, c3d, tokens, ev_start, ev_len, g_logp, fused]
-                sp = L.stream_ptr()
+        g_video, g_event, g_h0, g_tap, grads = _decoder_backward(ctx, g_logp)
+        return (g_video, g_event, None, None, None, None, None, None, None, None, None, g_h0, g_tap, None) + grads
 
-                def _join(keep=keep, sp=sp):
-                    L.check(lib.echr_stream_join(sp), 'stream_join')
-                    del keep[:]
-                torch.autograd.Variable._execution_engine.queue_callback(_join)
-        g_tap = None
-        if want_tap:
-            # d rows of the tap columns (echr_decoder_row_grad): orders the asynchronous tail, whose d P_all it reads, on this stream first --
-            # every workspace read of that tail then precedes this return in stream order
-            (T, Ht), col0 = ctx.tap_meta
-            g_tap = torch.zeros(T, Ht, device=event.device, dtype=torch.float32)
-            rws = torch.empty(lib.echr_decoder_row_grad_ws_floats(C.byref(a), Ht), device=event.device, dtype=torch.float32)
-            r = L.RowGradArgs(col0, Ht, L.ptr(g_tap), Ht, L.ptr(rws))
-            L.check(lib.echr_decoder_row_grad(C.byref(a), C.byref(g), C.byref(r), L.stream_ptr()), 'decoder_row_grad')
-        return (g_video, g_event, None, None, None, None, None, None, None, None, None, g_h0, g_tap, None) + tuple(grads)
+
+class DecoderBatchFunction(torch.autograd.Function):
+    """DecoderFunction over the events of several videos: `video` is [V, Dv], one scene vector per video, and event n reads row vid[n]
+    (echr_decoder_fwd_batch / _bwd_batch); backward returns d video [V, Dv].  Zero initial state, 'CC' rows."""
+
+    @staticmethod
+    def forward(ctx, video, event, c3d, ev_start, ev_len, tokens, A, disjoint, drop, sink, vid, *params):
+        return _decoder_forward(ctx, video, event, c3d, ev_start, ev_len, tokens, A, disjoint, drop, sink, None, None, None, 0, params, vid=vid)
+
+    @staticmethod
+    def backward(ctx, g_logp):
+        g_video, g_event, _, _, grads = _decoder_backward(ctx, g_logp)
+        return (g_video, g_event, None, None, None, None, None, None, None, None, None) + grads
+
+
+def _decoder_forward(ctx, video, event, c3d, ev_start, ev_len, tokens, A, disjoint, drop, sink, prep, h0, tap, col0, params, vid=None):
+    # tap / col0 ('CH', 'CC+CH'): the rows c3d[:, col0 : col0 + tap width] are tap[:Tv]; backward returns d tap (echr_decoder_row_grad)
+    # vid (multi-video batch): int32 [N] device, video is then [V, Dv]
+    lib = L.load()
+    ctx.sink = sink
+    ctx.vid = vid
+    ctx.tap_meta = (tuple(tap.shape), int(col0)) if tap is not None else None
+    event = _f32c(event)
+    h0 = _f32c(h0) if h0 is not None else None          # [N, 3H] initial state (OldModel.init_hidden, CG_init_feats_type); None = zeros
+    S, N = tokens.shape
+    if prep is not None:          # decoder_prepare() already ran the event-independent part on this workspace
+        video, c3d, ps, logp, ws = prep['video'], prep['c3d'], prep['ps'], prep['logp'], prep['ws']
+        train = prep['train']
+        a = _dec_args(ps, c3d, ev_start, ev_len, event, video, tokens, A, S, ws, logp, disjoint, prepared=1, train=train, h0=h0)
+    else:
+        video, c3d = _f32c(video), _f32c(c3d)
+        ps = [_f32c(p) for p in params]
+        V1 = ps[0].shape[0]
+        logp = torch.empty(N, S, V1, device=event.device, dtype=torch.float32)
+        train = 1 if any(ctx.needs_input_grad) else 0
+        a = _dec_args(ps, c3d, ev_start, ev_len, event, video, tokens, A, S, None, logp, disjoint, train=train, h0=h0)
+        ws = torch.empty(lib.echr_decoder_ws_floats(C.byref(a)), device=event.device, dtype=torch.float32)
+        a.ws = L.ptr(ws)
+    d = drop.c()
+    if vid is not None:
+        x, ctx.xws = batch_ext(vid, video, H=ps[6].shape[1])          # (kept with the node: the forward's kernels read it in stream order)
+        L.check(lib.echr_decoder_fwd_batch(C.byref(a), C.byref(d), C.byref(x), L.stream_ptr()), 'decoder_fwd_batch')
+    else:
+        L.check(lib.echr_decoder_fwd(C.byref(a), C.byref(d), L.stream_ptr()), 'decoder_fwd')
+    ctx.save_for_backward(video, event, c3d, ev_start, ev_len, tokens, ws, logp, *ps)
+    ctx.h0 = h0
+    ctx.meta = (A, S, drop, disjoint, train)
+    return logp
+
+
+def _decoder_backward(ctx, g_logp):
+    lib = L.load()
+    video, event, c3d, ev_start, ev_len, tokens, ws, logp, *ps = ctx.saved_tensors
+    A, S, drop, disjoint, train = ctx.meta
+    # criterion gradient left here in sparse form by MaskedNLL.backward (LanguageModelCriterion on this node's output)
+    pend = ctx.__dict__.pop('_echr_pending_nll', None)     # one entry per LanguageModelCriterion applied to this node's output
+    fused = None
+    if pend:
+        if len(pend) == 1 and getattr(g_logp, '_echr_nll_placeholder', False) and g_logp.stride() == (0, 0, 0):
+            fused, g_logp = pend[0], None
+        else:          # other consumers of the log-probs (or several criteria): their accumulated gradient plus every criterion's dense one
+            for pe in pend:
+                g_logp = g_logp + MaskedNLL.dense_grad(pe[0], pe[1], pe[2], pe[3], *logp.shape)
+    if g_logp is not None:
+        g_logp = _f32c(g_logp)
+    zeroed = 1 if (ctx.sink is not None and ctx.sink.usable()) else 0
+    zero_span = None
+    if zeroed:
+        grads, zero_span = ctx.sink.take(defer_zero=True)      # zero-filled inside echr_decoder_bwd's first stage (one fill launch less)
+    else:
+        red = getattr(ctx.sink.arena, 'early_reducer', None) if ctx.sink is not None else None
+        if red is not None:
+            red.check_no_backward_while_in_flight()      # accumulating into ranges whose all-reduce already started
+        grads = [torch.empty_like(p) for p in ps]
+        grads[0].zero_()                                 # embedding table gradient is scatter-added
+    g_event = torch.empty_like(event)
+    g_video = torch.empty_like(video) if ctx.needs_input_grad[0] else None
+    h0 = ctx.h0
+    g_h0 = torch.empty_like(h0) if (h0 is not None and ctx.needs_input_grad[11]) else None
+    want_tap = ctx.tap_meta is not None and ctx.needs_input_grad[12]
+    a = _dec_args(ps, c3d, ev_start, ev_len, event, video, tokens, A, S, ws, logp, disjoint, train=train, h0=h0)
+    wsb = torch.empty(lib.echr_decoder_ws_bwd_floats(C.byref(a)), device=event.device, dtype=torch.float32)
+    gp = [L.ptr(x) for x in grads]
+    g = L.DecGrads(gp[0], gp[1], gp[2], (L.c_f * 3)(*gp[3:6]), (L.c_f * 3)(*gp[6:9]), (L.c_f * 3)(*gp[9:12]),
+                   (L.c_f * 3)(*gp[12:15]), gp[15], gp[16], gp[17], gp[18], gp[19], gp[20],
+                   L.ptr(g_event), L.ptr(g_video) if ctx.vid is None else None, L.ptr(g_logp) if g_logp is not None else None,
+                   L.ptr(fused[0], fused[0].dtype) if fused else None, L.ptr(fused[1]) if fused else None, L.ptr(fused[3]) if fused else None,
+                   L.ptr(wsb), zeroed, 0, 0, L.ptr(fused[2][1:2]) if fused else None,
+                   L.ptr(zero_span) if zero_span is not None else None, zero_span.numel() if zero_span is not None else 0,
+                   1 if (fused and fused[0].dtype == torch.int64) else 0, 0, None, 0, L.ptr(g_h0) if g_h0 is not None else None)
+    d = drop.c()
+    if ctx.vid is not None:
+        x, xws = batch_ext(ctx.vid, video, g_video, H=ps[6].shape[1])
+        bwd = lambda: L.check(lib.echr_decoder_bwd_batch(C.byref(a), C.byref(g), C.byref(d), C.byref(x), L.stream_ptr()), 'decoder_bwd_batch')
+    else:
+        xws = None
+        bwd = lambda: L.check(lib.echr_decoder_bwd(C.byref(a), C.byref(g), C.byref(d), L.stream_ptr()), 'decoder_bwd')
+    hook = getattr(ctx.sink.arena, 'early_grad_hook', None) if zeroed else None
+    staged = hook is not None and getattr(ctx.sink.arena, 'early_staged', True)
+    if staged:
+        # data parallel: hand gradients to the reducer as soon as they are final; it starts their all-reduce on the collective
+        # stream while the next stage runs on this one.  params order = OldModel.native_params():
+        #   [0] embed, [1] logit.weight, [2] logit.bias, [3:6] weight_ih, [6:9] weight_hh, [9:12] bias_ih, [12:15] bias_hh, ...
+        sp = ctx.sink.params
+        for phase, ready in ((1, [sp[1], sp[2]]), (3, list(sp[3:15])), (4, None)):
+            g.phase = phase
+            bwd()
+            if ready is not None:
+                hook(ready)
+    else:
+        # arena path: the returned parameter gradients are views that autograd adopts without touching them, so the last stage of
+        # the backward (attention-parameter / embedding gradients) may still be running on the library's second stream while
+        # autograd goes on with the event encoder's backward; an end-of-backward callback joins the streams and only then lets go
+        # of the workspaces that stage reads
+        # (not when a parameter hook would read those gradients inside the backward pass, nor under create_graph, where autograd may
+        # clone them: the gradients must then be final when this Function returns)
+        g.async_tail = 1 if (zeroed and ASYNC_TAIL[0] and not ctx.sink.has_hooks() and not torch.is_grad_enabled()) else 0
+        if g.async_tail and hook is None:
+            # no data-parallel hand-over waits for the LSTM-layer gradients: only d event is formed on this stream, the rest of that stage
+            # runs on the library's second helper stream and is joined with the tail by the end-of-backward callback
+            g.async_tail = 2
+        bwd()
+        if hook is not None:
+            # data parallel, one-call form: the LSTM-layer gradients (and everything else part A of the backward produced) are final in
+            # stream order now; the reducer starts their all-reduce, which overlaps the asynchronous tail and the event encoder's backward
+            hook(list(ctx.sink.params[3:15]), after_recurrence=True)
+        if g.async_tail and not want_tap:
+            keep = [ws, wsb, logp, c3d, tokens, ev_start, ev_len, g_logp, fused, xws]
+            sp = L.stream_ptr()
+
+            def _join(keep=keep, sp=sp):
+                L.check(lib.echr_stream_join(sp), 'stream_join')
+                del keep[:]
+            torch.autograd.Variable._execution_engine.queue_callback(_join)
+    g_tap = None
+    if want_tap:
+        # d rows of the tap columns (echr_decoder_row_grad): orders the asynchronous tail, whose d P_all it reads, on this stream first --
+        # every workspace read of that tail then precedes this return in stream order
+        (T, Ht), col0 = ctx.tap_meta
+        g_tap = torch.zeros(T, Ht, device=event.device, dtype=torch.float32)
+        rws = torch.empty(lib.echr_decoder_row_grad_ws_floats(C.byref(a), Ht), device=event.device, dtype=torch.float32)
+        r = L.RowGradArgs(col0, Ht, L.ptr(g_tap), Ht, L.ptr(rws))
+        L.check(lib.echr_decoder_row_grad(C.byref(a), C.byref(g), C.byref(r), L.stream_ptr()), 'decoder_row_grad')
+    return g_video, g_event, g_h0, g_tap, tuple(grads)
 
 
 def clip_rows(c3d, tap):
@@ -465,7 +569,7 @@ def clip_rows(c3d, tap):
 
 
 def greedy_sample(video, event, c3d, ev_start, ev_len, A, seq_length, params, debug=None, multinomial=False, temperature=1.0, seed=0,
-                  table_cache=None, h0=None, drop=None):
+                  table_cache=None, h0=None, drop=None, vid=None):
     """OldModel.sample (OldModel_NEW.py:139-187) with every step on device; one host sync at the end.  Greedy arg-max by default
     (sample_max = 1); multinomial=True draws each token from softmax(logp / temperature) (:160-168) with the library's Philox stream
     keyed by `seed`.
@@ -477,7 +581,12 @@ def greedy_sample(video, event, c3d, ev_start, ev_len, A, seq_length, params, de
     `drop` (a training-mode DropState, multinomial only): the sampled pass of self-critical training -- the decoder's dropout is active
     with the masks echr_decoder_fwd draws for the same state at the same step (echr_decoder_sample_train).
 
+    `vid` (int32 [N] device): greedy decode of a multi-video batch -- `video` is [V, Dv] and event n reads row vid[n]
+    (echr_decoder_sample_batch).
+
     Returns (seq int64 [N,T], logp fp32 [N,T]) with T <= seq_length, or ([], []) when nothing was generated."""
+    if vid is not None and (multinomial or drop is not None or h0 is not None):
+        raise NotImplementedError('the batched decode is the greedy one from the zero initial state')
     if drop is not None and not multinomial:
         raise ValueError('a dropout state is taken by the multinomial decode only (the greedy baseline runs in eval mode)')
     lib = L.load()
@@ -507,7 +616,10 @@ def greedy_sample(video, event, c3d, ev_start, ev_len, A, seq_length, params, de
     sa = L.SampleArgs(a, seq_length, L.ptr(seq, torch.int64), L.ptr(slp), L.ptr(nun, torch.int32), L.ptr(wss),
                       1 if multinomial else 0, float(temperature), int(seed) & 0xFFFFFFFFFFFFFFFF,
                       L.ptr(tables) if tables is not None else None, valid)
-    if drop is not None:
+    if vid is not None:
+        x, xws = batch_ext(vid, video, H=ps[6].shape[1])
+        L.check(lib.echr_decoder_sample_batch(C.byref(sa), C.byref(x), L.stream_ptr()), 'decoder_sample_batch')
+    elif drop is not None:
         dc = drop.c()
         L.check(lib.echr_decoder_sample_train(C.byref(sa), C.byref(dc), L.stream_ptr()), 'decoder_sample_train')
     else:

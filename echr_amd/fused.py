@@ -120,6 +120,8 @@ class FusedTrainStep(object):
         """Joint 'tap_cg' iteration (train.py:300-313), optional first half: everything of the iteration that does not read tap_feats (index
         staging, the decoder's event-independent part, the gradient-arena fill) starts on the library's prepare stream and runs beside the
         proposal encoder's forward queued next.  Follow with `self(tap_feats, <the same arguments>, prepared=True, ...)`."""
+        if hasattr(c3d_feats, 'event_slices'):
+            raise NotImplementedError('prepare() runs ahead of ONE video\'s call: it does not take a VideoBatch')
         if self.clip != 1:
             raise NotImplementedError("clip_context_type with 'CH': the attended rows are tap_feats and their attention projection is part of the "
                                       "event-independent half, prepare() runs ahead of them (call without prepare(); JointTrainStep(early_prepare=False))")
@@ -215,6 +217,44 @@ class FusedTrainStep(object):
             raise e
         return self._finish(slot, st, forward_only)
 
+    def batch(self, batch, step=True, forward_only=False, device_criterion=False, video_losses=True, **unsupported):
+        """One iteration over a multi-video batch (echr_amd.batch.VideoBatch) as ONE call (echr_train_step_batch): the reference's
+        `m_batch = V` protocol (train.py:281-283,313-317) -- the loss is the SUM over the videos of LanguageModelCriterion (each video with
+        its own normaliser), the gradients are summed over the videos, then ONE clamp and ONE Adam step.  Returns the summed loss as a 0-d
+        device tensor; `last_video_losses` holds the per-video losses as a device vector [V].  step=False stops after the backward pass and
+        exposes the summed gradients as `.grad` views, forward_only=True stops after the criterion, as __call__ does.
+        `device_criterion=True` hands targets / masks / weights over as device tensors (all rows) instead of with the index vectors;
+        `video_losses=False` skips the per-video losses (`last_video_losses` is then None)."""
+        if unsupported:
+            raise NotImplementedError('FusedTrainStep.batch does not take %s: tap_grad / defer_update / prepared / handover over a batch are '
+                                      'follow-ups (one video per call)' % sorted(unsupported))
+        if getattr(self, '_prepared', False):
+            raise NotImplementedError('prepare() runs ahead of ONE video\'s call: it does not combine with batch()')
+        m = self.model
+        m._check_batch_options()
+        if batch.labels is None:
+            raise ValueError('the batch carries no labels')
+        a, lib = self.a, self.lib
+        L.check(lib.echr_check_async(), 'train_step_batch (asynchronous failure of an earlier call)')
+        with torch.no_grad():
+            video = EF._f32c(m.get_video_context_batch(batch))
+        w = batch.criterion_weights()
+        tg, mk = batch.targets, batch.crit_masks
+        w_dev = None
+        if device_criterion:
+            tg, mk = tg.to(self.dev), mk.to(self.dev)
+            w_dev = torch.from_numpy(w).to(self.dev)
+        slot, st = self._setup(batch.tap, batch.c3d, video, batch.labels, batch.ind, batch.soi, tg, mk, step, forward_only, None, False,
+                               weights=w, batch=batch)
+        a.prepared = a.handover = 0
+        a.handover_cb = a.handover_user = a.mid_cb = a.mid_user = None
+        self._pending_deferred = False
+        self.last_video_losses = torch.empty(batch.n_videos, device=self.dev, dtype=torch.float32) if video_losses else None
+        self._keep = self._keep + (w_dev, video)
+        L.check(lib.echr_train_step_batch(C.byref(a), C.byref(self.bx), L.ptr(w_dev) if w_dev is not None else None,
+                                          L.ptr(self.last_video_losses) if video_losses else None, L.stream_ptr()), 'train_step_batch')
+        return self._finish(slot, st, forward_only)
+
     def _set_tap(self, tap, tap_grad, defer_update, step, forward_only):
         a, d = self.a, self.a.dec
         if (tap.shape[1] if a.event_parts & 2 else 0) + (self._dc if a.event_parts & 1 else 0) != a.tsrm.Din or tap.shape[0] < self._tv_needed:
@@ -238,9 +278,11 @@ class FusedTrainStep(object):
             a.vh_offset, a.tap_rows = -1, 0
 
     def _setup(self, tap_feats, c3d_feats, lda_feats, lm_labels, ind_select_list, soi_select_list, targets, masks, step, forward_only,
-               tap_grad, defer_update, drop=None, weights=None):
+               tap_grad, defer_update, drop=None, weights=None, batch=None):
         """(`drop`: the iteration's dropout state when the caller already drew it -- SelfCriticalStep's sampled pass used it; `weights`:
-        host [N, >= S] criterion weights of echr_train_step_rw, travelling with the index vectors)"""
+        host [N, >= S] criterion weights of echr_train_step_rw, travelling with the index vectors; `batch`: a VideoBatch -- the arguments
+        are then its concatenated features / batch-absolute indices, `lda_feats` is the scene matrix [V, Dv]; with device targets the
+        host `weights` do not travel with the index vectors -- FusedTrainStep.batch hands their device copy to echr_train_step_batch itself)"""
         a, m, ar, lib = self.a, self.model, self.arena, self.lib
         if getattr(self, '_pending_deferred', False):
             # a deferred update may still be reading the previous call's inputs (c3d, the staged indices) on the library's streams: order this
@@ -271,7 +313,7 @@ class FusedTrainStep(object):
         c3d, lda = EF._f32c(c3d_feats), EF._f32c(lda_feats)
         tap = None if tap_feats is None else EF._f32c(tap_feats)
         vt = m.opt.video_context_type
-        if vt != 'VL':
+        if vt != 'VL' and batch is None:
             # scene context 'VC' / 'VH' (CaptionGenerator.py:87-104): the mean rows are formed ahead of the call (two small launches); what the
             # library sees as its `video` vector is the concatenation.  'VH' makes the scene vector a function of tap_feats: with tap_grad the
             # library routes d video's span back into it (echr_train_step_args.vh_offset, _set_tap).  prepare() runs before tap_feats exist
@@ -286,7 +328,7 @@ class FusedTrainStep(object):
         # reach the loss (misc/utils.py:66-75 multiplies by the mask), so training forms logits, d logits and the logit-layer products on the
         # active rows only.  On the device: used in place, all rows.
         host_nll = not (isinstance(targets, torch.Tensor) and targets.is_cuda) and not (isinstance(masks, torch.Tensor) and masks.is_cuda)
-        if weights is not None and not host_nll:
+        if weights is not None and not host_nll and batch is None:
             raise ValueError('criterion weights travel with host targets / masks')
         act = None
         if host_nll:
@@ -303,8 +345,9 @@ class FusedTrainStep(object):
                 if act.size == 0 or act.size == N * S:
                     act = None
         n_act = 0 if act is None else int(act.size)
-        n_w = 0 if weights is None else N * S
-        host = np.empty((3 + S) * N + n_act + (2 * N * S if host_nll else 0) + n_w, dtype=np.int32)
+        n_w = 0 if (weights is None or not host_nll) else N * S
+        n_b = 0 if batch is None else N          # echr_train_step_batch: the index vectors end with vid [N]
+        host = np.empty((3 + S) * N + n_act + (2 * N * S if host_nll else 0) + n_w + n_b, dtype=np.int32)
         host[:N], host[N:2 * N], host[2 * N:3 * N] = soi[:, 0], lens, ind
         host[3 * N:(3 + S) * N] = labels[:, :S].T.reshape(-1)
         o = (3 + S) * N
@@ -317,15 +360,17 @@ class FusedTrainStep(object):
                 w_h = np.ascontiguousarray(np.asarray(weights)[:, :S], dtype=np.float32)
                 if w_h.shape != (N, S):
                     raise ValueError('weights must be [N, >= S] (got %s)' % (tuple(np.asarray(weights).shape),))
-                host[o + n_act + 2 * N * S:] = w_h.reshape(-1).view(np.int32)
+                host[o + n_act + 2 * N * S:o + n_act + 3 * N * S] = w_h.reshape(-1).view(np.int32)
             tgt = msk = None
         else:
             tgt = EF._nll_target(targets if targets.is_cuda else EF.upload(targets, self.dev), S)
             msk = (masks if masks.is_cuda else EF.upload(masks, self.dev))[:, :S].to(torch.float32).contiguous()
+        if n_b:
+            host[-n_b:] = batch.vid
         d = a.dec
         a.tsrm.N = d.N = N
         d.A, d.Tv, d.S, d.rows_disjoint = int(lens.max()), c3d.shape[0], S, 1 if EF.rows_disjoint(soi) else 0
-        if c3d.shape[1] != self._dc or lda.numel() != d.Dv:
+        if c3d.shape[1] != self._dc or (lda.numel() if batch is None else lda.shape[-1]) != d.Dv:
             raise L.EchrHipError('feature widths do not match the model (c3d %d, lda %d)' % (c3d.shape[1], lda.numel()))
         d.c3d, d.video = c3d.data_ptr(), lda.data_ptr()
         if self.clip != 1:
@@ -353,7 +398,10 @@ class FusedTrainStep(object):
             drop = m.lm_model.next_drop_state(m.fusion_model.enc_attn.dropout.p)
             drop.training = m.training
         a.drop = drop.c()
-        if self.clip != 1:
+        if batch is not None:
+            self.bx = L.BatchExt(batch.n_videos, None, lda.data_ptr(), None, None)
+            need = lib.echr_train_step_batch_ws_floats(C.byref(a), C.byref(self.bx))
+        elif self.clip != 1:
             self.x.rw = 0 if weights is None else 1
             need = lib.echr_train_step_clip_ws_floats(C.byref(a), C.byref(self.x))
         else:
@@ -427,6 +475,10 @@ class SelfCriticalStep(object):
         if not isinstance(fused, FusedTrainStep):
             raise TypeError('SelfCriticalStep wraps a FusedTrainStep')
         self.fused, self.reward_fn = fused, reward_fn
+
+    def batch(self, *args, **kwargs):
+        """Multi-video batches (FusedTrainStep.batch) are not part of this step yet: the sampled and greedy decodes and the reward take one video per call."""
+        raise NotImplementedError('SelfCriticalStep takes one video per call: self-critical training over a VideoBatch is a follow-up')
 
     def __call__(self, tap_feats, c3d_feats, lda_feats, ind_select_list, soi_select_list, gen_result=None, reward=None, step=True):
         """Returns (loss 0-d device tensor, gen_result [N,T] int64 host, greedy_res [N,T'] int64 host, reward [N,T] fp32 host).
@@ -541,6 +593,10 @@ class JointTrainStep(object):
                               loss=torch.zeros(65, device=dev, dtype=f32))
             self._buf_key = key
         return self._bufs
+
+    def batch(self, *args, **kwargs):
+        """Multi-video batches (FusedTrainStep.batch) are not part of this step yet: the proposal encoder runs over one video, and d tap_feats (tap_grad) / the deferred update are single-video forms."""
+        raise NotImplementedError('JointTrainStep takes one video per call: the joint iteration (tap_grad, defer_update, prepare) over a VideoBatch is a follow-up')
 
     def __call__(self, c3d_feats, lda_feats, lm_labels, ind_select_list, soi_select_list, targets, masks, tap_masks, tap_labels, w1):
         """Returns (lambda1 * tap_loss + cg_loss) as a 0-d device tensor; `self.tap_loss` / `self.cg_loss` hold the two terms."""
@@ -670,6 +726,10 @@ class DataParallelStep(object):
             return dist.get_backend(self.group) == 'nccl'
         except Exception:
             return False
+
+    def batch(self, *args, **kwargs):
+        """Multi-video batches (FusedTrainStep.batch) are not part of this step yet: the hand-over points are recorded by the single-video call."""
+        raise NotImplementedError('DataParallelStep takes one video per rank and call: a VideoBatch per rank is a follow-up')
 
     def __call__(self, *args, **kw):
         P, f, ar = self.P, self.fused, self.fused.arena

@@ -345,3 +345,52 @@ def make_attsat(name, clip_context_type='CC'):
         soi[:len(lens), 1] = soi[:len(lens), 0] + lens
         vid['ind'] = (soi[:, 1] - 1).astype(np.int64)
     return opt, params, vid
+
+
+# Multi-video batches (echr_amd/batch.py): V videos of a few events each, as caption pre-training on ground-truth events sees them
+# (train.py:268-271), with ragged event counts, event lengths, video lengths and label widths.  Video v of a case is
+# make_video(seed = case seed + v); the per-video shapes come from one RandomState(case seed).
+#   vb16   16 videos, 2..6 events each (N_tot <= 64: the persistent recurrences' shape), events of 3..60 segments, T_v 40..160, up to 20
+#          decoder steps, ECHR widths, V1 = 5001, scene context 'VL'
+#          (case seed 1000: the first of 900, 1000, 1100, ... whose greedy decode keeps a top-1 / top-2 margin above 2e-5 at every step of
+#          every row -- tools/make_golden_vbatch.py asserts it on the reference's own decode)
+#   vbctx  5 videos incl. a one-event video, scene context from all three sources ('VLVCVH': per-video column means), 'ER3', small vocabulary
+#   vb24 / vb33  24 / 33 videos of 4 events, small vocabulary
+VBATCH = {
+    'vb16': dict(opt=dict(CG_vocab_size=5000, CG_seq_length=19), V=16, events=(2, 6), max_events=64, seg=(3, 60), T=(40, 160), L=(12, 21), seed=1000),
+    'vbctx': dict(opt=dict(video_context_type='VLVCVH', CG_vocab_size=300, CG_seq_length=7), V=5, events=(1, 4), single=2, max_events=64, seg=(3, 30),
+                  T=(30, 60), L=(6, 9), seed=950),
+    # more than 64 events: the launch-per-phase recurrences and the event encoder's general softmax kernels (96 events: one wave per (event,
+    # head); 132 events: the row kernel)
+    'vb24': dict(opt=dict(CG_vocab_size=300, CG_seq_length=7), V=24, events=(4, 4), max_events=96, seg=(3, 30), T=(30, 80), L=(6, 9), seed=1200),
+    'vb33': dict(opt=dict(CG_vocab_size=300, CG_seq_length=7), V=33, events=(4, 4), max_events=132, seg=(3, 30), T=(30, 80), L=(6, 9), seed=1300),
+}
+
+
+def make_vbatch_videos(V, events, seg, T, L, V1, seed, max_events=64, single=None, video_dim=500, hidden_dim=512, lda_dim=100):
+    """V synthetic videos (make_video dicts) with events[0]..events[1] events each (`single`: the index of a video that gets exactly one),
+    at most max_events in all, the longest event of a video in seg[0]..seg[1] segments (the others from seg[0] up to it), T_v in T, label
+    width L_v in L (at least one caption of a video uses all L_v - 2 token slots, so the video runs L_v - 1 steps)."""
+    rs = np.random.RandomState(seed)
+    counts = rs.randint(events[0], events[1] + 1, size=V)
+    if single is not None:
+        counts[single] = 1
+    while counts.sum() > max_events:
+        counts[int(np.argmax(counts))] -= 1
+    vids = []
+    for v in range(V):
+        A = int(rs.randint(max(seg[0], 8), seg[1] + 1))
+        Tv = int(rs.randint(max(T[0], A), T[1] + 1))
+        Lv = int(rs.randint(L[0], L[1] + 1))
+        vids.append(make_video(int(counts[v]), A, Lv, V1, seed=seed + v, T_v=Tv, min_len=seg[0], video_dim=video_dim, hidden_dim=hidden_dim,
+                               lda_dim=lda_dim))
+    return vids
+
+
+def make_vbatch(name, param_seed=0):
+    """(opt, params, [video dicts]) of a named multi-video case."""
+    c = VBATCH[name]
+    opt = default_opt(**c['opt'])
+    vids = make_vbatch_videos(c['V'], c['events'], c['seg'], c['T'], c['L'], opt.CG_vocab_size + 1, c['seed'], c['max_events'], c.get('single'),
+                              opt.video_dim, opt.hidden_dim, opt.lda_dim)
+    return opt, make_params(opt, param_seed), vids

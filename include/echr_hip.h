@@ -649,6 +649,56 @@ typedef struct {
 } echr_clip_step_args;
 int64_t echr_train_step_clip_ws_floats(const echr_train_step_args* a, const echr_clip_step_args* x);
 int echr_train_step_clip(const echr_train_step_args* a, const echr_clip_step_args* x, void* stream);
+/* ------------------------------------------------------------------------------------------------
+ * Multi-video batches.  The entry points above take the events of ONE video (the reference's batch_size = 1, opts.py:187); the ones below
+ * take the events of V >= 1 videos in one call.  The feature rows of the videos are concatenated ([sum T_v, D]); ev_start / ind are
+ * batch-absolute row indices; events of a video are contiguous and videos keep their order (vid non-decreasing).  With equal dropout
+ * masks a batched call equals V single-video calls:
+ *   - scene context: one vector per video, `video` [V, Dv]; event n reads row vid[n] (echr_dec_args.video is ignored);
+ *   - event encoder: an event attends to the events of its own video only (block-diagonal softmax; the position embedding is
+ *     unchanged by a row offset);
+ *   - criterion (echr_train_step_batch): loss = sum over v of LanguageModelCriterion of video v, each with its own normaliser
+ *     sum(mask_v) + 1e-6 -- the caller passes the per-position weight w[n,t] = mask[n,t] / (sum(mask of video vid[n]) + 1e-6) and the
+ *     library applies it with denominator 1; gradients are the SUM over the videos (train.py:281-283,313-317 with m_batch = V), then one
+ *     clamp + Adam;
+ *   - dropout: one forward-call counter per batched call, every site keyed by the batch-global element index.
+ * Every entry takes the arguments of its single-video sibling plus this extension; the sibling's structs are unchanged.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct {
+    int32_t n_videos;            /* V */
+    const int32_t* vid;          /* device [N]: video of event n, non-decreasing (echr_train_step_batch: may be NULL, see there) */
+    const float* video;          /* device [V, Dv] scene vectors (the event encoder's entries do not read it) */
+    float* g_video;              /* optional [V, Dv] out: d loss / d video (echr_dec_grads.g_video is ignored) */
+    float* ws;                   /* decoder entries: scratch of echr_batch_ws_floats floats (per-event scene part of stream 2's gates, its per-video
+                                    form and the per-video gate-gradient sums); only read and written inside the call.  echr_train_step_batch
+                                    carves it from its own workspace and ignores this field */
+} echr_batch_ext;
+int64_t echr_batch_ws_floats(int32_t N, int32_t n_videos, int32_t H);
+/* Scene contexts 'VC' / 'VH' of a batch: out[v*ld_out + c] = mean of x[r, c] over the rows r of segment v = [row_offset[v], row_offset[v+1])
+ * (one launch for all n_seg segments; an empty segment is an error of the caller: its mean is written as 0);
+ * bwd: gx[r, c] += g[v*ld_g + c] / rows(v) for the rows of segment v. */
+int echr_seg_col_mean_fwd(const float* x, const int32_t* row_offset, int32_t n_seg, int32_t cols, int64_t ld, float* out, int64_t ld_out,
+                          void* stream);
+int echr_seg_col_mean_bwd(const float* g, int64_t ld_g, const int32_t* row_offset, int32_t n_seg, int32_t cols, int64_t ld, float* gx,
+                          void* stream);
+int echr_tsrm_fwd_batch(const echr_tsrm_args* a, const echr_dropout* drop, const echr_batch_ext* x, void* stream);
+/* (the backward kernels need no mask: the saved softmax weights of cross-video pairs are exactly 0, so d score = w * (..) is 0 there) */
+int echr_tsrm_bwd_batch(const echr_tsrm_args* a, const echr_tsrm_grads* g, const echr_dropout* drop, const echr_batch_ext* x, void* stream);
+/* a->prepared must be 0.  N <= 64 takes the persistent recurrences exactly as a single video does (they read the gate pre-activations,
+ * which already hold the per-row scene part). */
+int echr_decoder_fwd_batch(const echr_dec_args* a, const echr_dropout* drop, const echr_batch_ext* x, void* stream);
+/* d W_ih2[:, E:] = (sum over time and over the events of a video of d gates2)^T . video; x->g_video [V, Dv] the matching data gradient */
+int echr_decoder_bwd_batch(const echr_dec_args* a, const echr_dec_grads* g, const echr_dropout* drop, const echr_batch_ext* x, void* stream);
+/* Greedy decode of a batch (a->multinomial must be 0): echr_decoder_sample with per-row scene vectors. */
+int echr_decoder_sample_batch(const echr_sample_args* a, const echr_batch_ext* x, void* stream);
+/* echr_train_step over a batch.  Criterion weights as in echr_train_step_rw: `weight` device [N,S] with host_nll = 0, or behind the mask
+ * in host_index with host_nll = 1 (then weight = NULL).  host_index additionally ENDS with vid[N]; x->vid and x->ws are ignored (the
+ * library points them at its staged copy / its own workspace).  loss[0] = the summed loss, loss[1] = sum(mask) over the batch;
+ * video_loss: optional device [V] out, the per-video losses (fixed summation order).  Not with prepared, defer_update, g_tap, handover,
+ * nor an initial state (w_init must be NULL: CG_init_feats_type over a batch is a follow-up). */
+int64_t echr_train_step_batch_ws_floats(const echr_train_step_args* a, const echr_batch_ext* x);
+int echr_train_step_batch(const echr_train_step_args* a, const echr_batch_ext* x, const float* weight, float* video_loss, void* stream);
+
 /* Hand-over points of the LAST echr_train_step issued with handover = 1 (which: 0 = logit layer, 1 = LSTM layers): makes `stream` wait
  * until that range of flat_g is final.  0 = `stream` now waits; 1 = the call recorded no such point (a configuration without the
  * asynchronous tail: the range is final when the call's own stream reaches its end, like every other); < 0 error. */
