@@ -123,6 +123,10 @@ class BatchExt(C.Structure):          # echr_batch_ext: the multi-video extensio
     _fields_ = [('n_videos', i32), ('vid', c_f), ('video', c_f), ('g_video', c_f), ('ws', c_f)]
 
 
+class SstBatch(C.Structure):          # echr_sst_batch: the video axis of the proposal encoder's *_batch entry points
+    _fields_ = [('n_videos', i32), ('row_offset', c_f), ('row_offset_host', C.c_void_p)]
+
+
 # every symbol include/echr_hip.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ('echr_version', i32, []),
@@ -182,6 +186,11 @@ SYMBOLS = [
     ('echr_sst_fwd_states', i32, [C.POINTER(SstArgs), C.POINTER(Dropout), C.c_void_p]),
     ('echr_sst_head_fwd', i32, [C.POINTER(SstArgs), C.c_void_p]),
     ('echr_sst_bwd', i32, [C.POINTER(SstArgs), C.POINTER(SstGrads), C.POINTER(Dropout), C.c_void_p]),
+    ('echr_sst_batch_ws_floats', i64, [i32, i32, i32, i32, i32]),
+    ('echr_sst_batch_ws_bwd_floats', i64, [i32, i32, i32, i32, i32]),
+    ('echr_sst_fwd_batch', i32, [C.POINTER(SstArgs), C.POINTER(SstBatch), C.POINTER(Dropout), C.c_void_p]),
+    ('echr_sst_bwd_batch', i32, [C.POINTER(SstArgs), C.POINTER(SstBatch), C.POINTER(SstGrads), C.POINTER(Dropout), C.c_void_p]),
+    ('echr_sst_batch_group', i32, []),
     ('echr_tap_bce_fwd', i32, [c_f, c_f, c_f, c_f, c_f, i32, i32, C.c_void_p]),
     ('echr_tap_bce_fwd_ws', i32, [c_f, c_f, c_f, c_f, c_f, c_f, i32, i32, C.c_void_p]),
     ('echr_tap_bce_bwd', i32, [c_f, c_f, c_f, c_f, c_f, c_f, i32, i32, C.c_void_p]),
@@ -215,7 +224,7 @@ SYMBOLS = [
 ABI_STRUCTS = {'echr_gemm_desc': GemmDesc, 'echr_dropout': Dropout, 'echr_tsrm_args': TsrmArgs, 'echr_tsrm_grads': TsrmGrads,
                'echr_dec_args': DecArgs, 'echr_dec_grads': DecGrads, 'echr_sample_args': SampleArgs, 'echr_sst_args': SstArgs,
                'echr_sst_grads': SstGrads, 'echr_train_step_args': TrainStepArgs, 'echr_init_state_args': InitStateArgs, 'echr_init_state_grads': InitStateGrads,
-               'echr_beam_args': BeamArgs, 'echr_row_grad_args': RowGradArgs, 'echr_clip_step_args': ClipStepArgs, 'echr_batch_ext': BatchExt}
+               'echr_beam_args': BeamArgs, 'echr_row_grad_args': RowGradArgs, 'echr_clip_step_args': ClipStepArgs, 'echr_batch_ext': BatchExt, 'echr_sst_batch': SstBatch}
 
 ABI_VERSION = 3          # include/echr_hip.h ECHR_ABI_VERSION
 _lib = None

@@ -59,11 +59,13 @@ class VideoBatch(object):
 
     # ---- construction -------------------------------------------------------------------------------------------------------
     @classmethod
-    def from_videos(cls, videos, device=None):
+    def from_videos(cls, videos, device=None, tap_model=None):
         """`videos`: a list of dicts with the arguments of a single-video call -- 'c3d' [T, D], 'tap' [T', Ht], 'lda' [lda_dim], 'ind' [N_v],
         'soi' [N_v, 2] (indices local to the video) and, for training, 'labels' / 'masks' [N_v, L_v] -- or a dict of parallel lists under
         the same keys.  Features may be numpy arrays or tensors on any device; they are concatenated on `device` (default: the device of
-        the first video's c3d when it is a tensor, else the CPU)."""
+        the first video's c3d when it is a tensor, else the CPU).
+        With `tap_model` (a models.SST on the GPU) the videos need no 'tap': `tap` is the encoder's forward_batch over the concatenated c3d --
+        ONE call for the V videos -- and keeps its autograd graph into the encoder; a 'tap' entry is then ignored."""
         if isinstance(videos, dict):
             n = len(videos['c3d'])
             videos = [{k: v[i] for k, v in videos.items()} for i in range(n)]
@@ -71,9 +73,11 @@ class VideoBatch(object):
         if not videos:
             raise ValueError('a batch needs at least one video')
         for i, v in enumerate(videos):
-            missing = [k for k in _KEYS if k not in v]
+            missing = [k for k in _KEYS if k not in v and not (k == 'tap' and tap_model is not None)]
             if missing:
                 raise ValueError('video %d lacks %s' % (i, missing))
+        if device is None and tap_model is not None:
+            device = next(tap_model.parameters()).device
         if device is None:
             c0 = videos[0]['c3d']
             device = c0.device if isinstance(c0, torch.Tensor) else torch.device('cpu')
@@ -84,7 +88,8 @@ class VideoBatch(object):
         if any(with_labels) and not all(with_labels):
             raise ValueError('either every video carries labels / masks or none does')
         for i, v in enumerate(videos):
-            c3d, tap = as_t(v['c3d']), as_t(v['tap'])
+            c3d = as_t(v['c3d'])
+            tap = c3d if tap_model is not None else as_t(v['tap'])
             if c3d.dim() != 2 or tap.dim() != 2:
                 raise ValueError('video %d: c3d / tap must be [T, D] matrices' % i)
             T = min(c3d.shape[0], tap.shape[0])
@@ -99,18 +104,21 @@ class VideoBatch(object):
             if soi.min() < 0 or soi[:, 1].max() > T or ind.min() < 0 or ind.max() >= T:
                 raise ValueError('video %d: event intervals / anchors fall outside its %d feature rows' % (i, T))
             c3ds.append(c3d[:T].to(device=device, dtype=torch.float32))
-            taps.append(tap[:T].to(device=device, dtype=torch.float32))
+            if tap_model is None:
+                taps.append(tap[:T].to(device=device, dtype=torch.float32))
             ldas.append(as_t(v['lda']).reshape(-1).to(device=device, dtype=torch.float32))
             sois.append(soi + rows[-1])
             inds.append(ind + rows[-1])
             rows.append(rows[-1] + T)
             counts.append(counts[-1] + len(soi))
-        if len({c.shape[1] for c in c3ds}) != 1 or len({t.shape[1] for t in taps}) != 1 or len({l.numel() for l in ldas}) != 1:
+        if len({c.shape[1] for c in c3ds}) != 1 or len({t.shape[1] for t in taps}) > 1 or len({l.numel() for l in ldas}) != 1:
             raise ValueError('the videos of a batch must share their feature widths')
         labels = masks = None
         if all(with_labels):
             labels, masks = cls._stack_labels(videos, counts)
-        return cls(torch.cat(c3ds, 0), torch.cat(taps, 0), torch.stack(ldas, 0), rows, counts, np.concatenate(sois, 0), np.concatenate(inds, 0),
+        c3d_all = torch.cat(c3ds, 0)
+        tap_all = torch.cat(taps, 0) if tap_model is None else tap_model.forward_batch(c3d_all, rows)[0]
+        return cls(c3d_all, tap_all, torch.stack(ldas, 0), rows, counts, np.concatenate(sois, 0), np.concatenate(inds, 0),
                    labels, masks)
 
     @staticmethod

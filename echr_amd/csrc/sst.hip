@@ -2,7 +2,7 @@
 // inter-layer dropout) over ONE video [1,T,D], Linear(hidden -> K) + sigmoid) and its weighted-BCE criterion
 // (misc/utils.py:78-99).  SURVEY section 8-f row 1: the producer of `tap_feats` for the caption path.
 //
-// Batch size is 1, so the recurrence is a chain of GEMVs: there is no MFMA shape in it.  Layout of the work:
+// One video is batch size 1: its recurrence is a chain of GEMVs with no MFMA shape in it.  Layout of the work:
 //   * layer 0's input-side products are batched over the T rows on the fp32 MFMA GEMM (gemm.hip);
 //   * the two layers run as a WAVEFRONT: launch k = layer 0 at step k || layer 1 at step k-1 (T+1 dependent launches instead of
 //     2T).  A workgroup owns 2 hidden units; wave g (of 4) computes gate g's rows of W_hh . h(t-1) (layer 1: also W_ih1 . h0(t))
@@ -10,9 +10,21 @@
 //     rows of a workgroup always land on the same XCD -> they stay L2-resident across the launches;
 //   * backward mirrors it with the transposed matrices: launch k = layer 1 at step T-1-k || layer 0 at step T-k, where layer 0's
 //     upstream gradient W_ih1^T . dG1(t) (through the inter-layer dropout mask) is formed inside the step;
-//   * weight gradients are batched TN GEMMs over the T rows afterwards.
+//   * weight gradients are batched TN GEMMs over the T rows afterwards;
+//   * H = 512: both wavefronts as ONE persistent launch per direction (below).
+// A multi-video BATCH (echr_sst_fwd_batch / echr_sst_bwd_batch; stage 1 of the reference's recipe sums the gradients of m_batch videos,
+// train.py:281-283,313-317) concatenates the videos' rows; every video starts from the zero state:
+//   * everything batched over rows (layer 0's input product, the head, the input-side weight gradients, the bias sums) is the same
+//     launch over T_tot rows;
+//   * the persistent kernels carry a video loop: the register-resident weight slices serve up to SPB_NV videos inside one step, so the
+//     step's memory round trip is paid once per step instead of once per video and step (sst_persist_*_batch_kernel);
+//   * the launch-per-step wavefront puts the videos on blockIdx.z with per-video row bases (sst_wave_*_batch_kernel): T_max + 1 launches;
+//   * the recurrent weight gradients pair dG(t) with a shifted copy of the states that is ZERO at every video's first row, so no pair
+//     crosses a video boundary; the dropout mask is keyed by the batch-global row.
 #include "echr_common.h"
 #include "echr_internal.h"
+#include <algorithm>
+#include <vector>
 
 namespace echr {
 
@@ -56,9 +68,9 @@ struct SstFwdRole {
     float *act, *hout, *cout, *hdrop;
     int t, active;
 };
-__global__ __launch_bounds__(256) void sst_wave_fwd_kernel(SstFwdRole r0, SstFwdRole r1, int H, DropCfg dc) {
-    const SstFwdRole r = blockIdx.y ? r1 : r0;
-    if (!r.active) return;
+// one workgroup's share of a role (the single-video and the batched kernel differ only in where the role comes from); r.t is the
+// row that keys the dropout mask: the timestep of a single video, the batch-global row of a batch
+__device__ __forceinline__ void sst_wave_fwd_body(const SstFwdRole& r, int H, const DropCfg& dc) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     float* sv = sm;                  // [2][H]
     float* pre = sm + 2 * H;         // [4][UPW]
@@ -107,6 +119,45 @@ __global__ __launch_bounds__(256) void sst_wave_fwd_kernel(SstFwdRole r0, SstFwd
         if (r.hdrop) r.hdrop[u] = h * drop_mult(dc, (unsigned)(r.t * H + u), 0u, SITE_SST);
     }
 }
+__global__ __launch_bounds__(256) void sst_wave_fwd_kernel(SstFwdRole r0, SstFwdRole r1, int H, DropCfg dc) {
+    const SstFwdRole r = blockIdx.y ? r1 : r0;
+    if (!r.active) return;
+    sst_wave_fwd_body(r, H, dc);
+}
+// the batch's wavefront: blockIdx.z = video.  Launch k runs, for every video that has not ended, layer 0 at step k || layer 1 at step k-1 of
+// THAT video (rows row_offset[v] + t of the concatenated layout); T_max + 1 dependent launches serve the whole batch
+struct SstWaveFB {
+    const float *w_hh0, *w_ih1, *w_hh1, *b_ih1, *b_hh1, *GIN0;
+    float *HS0, *H0D, *TAP, *ACT0, *ACT1, *CS0, *CS1;
+    const int* row_offset;
+    int H, k;
+};
+__global__ __launch_bounds__(256) void sst_wave_fwd_batch_kernel(SstWaveFB p, DropCfg dc) {
+    const int v = blockIdx.z, H = p.H, k = p.k;
+    const long base = p.row_offset[v];
+    const int Tv = p.row_offset[v + 1] - (int)base;
+    SstFwdRole r{};
+    if (blockIdx.y == 0) {
+        if (k >= Tv) return;
+        const long row = base + k;
+        r.t = (int)row;
+        r.W[0] = p.w_hh0; r.v[0] = k ? p.HS0 + (row - 1) * H : nullptr;
+        r.base = p.GIN0 + row * 4 * H;
+        r.cprev = k ? p.CS0 + (row - 1) * H : nullptr;
+        r.act = p.ACT0 + row * 4 * H; r.hout = p.HS0 + row * H; r.cout = p.CS0 + row * H; r.hdrop = p.H0D + row * H;
+    } else {
+        const int t = k - 1;
+        if (t < 0 || t >= Tv) return;
+        const long row = base + t;
+        r.t = (int)row;
+        r.W[0] = p.w_ih1; r.v[0] = p.H0D + row * H;
+        r.W[1] = p.w_hh1; r.v[1] = t ? p.TAP + (row - 1) * H : nullptr;
+        r.base = p.b_ih1; r.base2 = p.b_hh1;
+        r.cprev = t ? p.CS1 + (row - 1) * H : nullptr;
+        r.act = p.ACT1 + row * 4 * H; r.hout = p.TAP + row * H; r.cout = p.CS1 + row * H;
+    }
+    sst_wave_fwd_body(r, H, dc);
+}
 
 // backward wavefront: launch k runs layer 1 at step t = T-1-k and layer 0 at step t+1.
 //   d h(t) = dh_base[u] + drop?(WT[0][u,:] . vec[0]) + WT[1][u,:] . vec[1]
@@ -120,9 +171,7 @@ struct SstBwdRole {
     float *dc, *dg;
     int drop_first, t, active;
 };
-__global__ __launch_bounds__(256) void sst_wave_bwd_kernel(SstBwdRole r0, SstBwdRole r1, int H, DropCfg dcfg) {
-    const SstBwdRole r = blockIdx.y ? r1 : r0;
-    if (!r.active) return;
+__device__ __forceinline__ void sst_wave_bwd_body(const SstBwdRole& r, int H, const DropCfg& dcfg) {
     static_assert(UPW == 2, "wave -> (unit, matrix) map below assumes two units per workgroup");
     extern __shared__ __attribute__((aligned(16))) float sm[];
     float* sg = sm;                  // [2][4H]
@@ -164,6 +213,62 @@ __global__ __launch_bounds__(256) void sst_wave_bwd_kernel(SstBwdRole r0, SstBwd
         r.dg[2 * H + u] = dcv * gi * (1.f - gg * gg);
         r.dg[3 * H + u] = dh * tc * go * (1.f - go);
         r.dc[u] = dcv * gf;
+    }
+}
+__global__ __launch_bounds__(256) void sst_wave_bwd_kernel(SstBwdRole r0, SstBwdRole r1, int H, DropCfg dcfg) {
+    const SstBwdRole r = blockIdx.y ? r1 : r0;
+    if (!r.active) return;
+    sst_wave_bwd_body(r, H, dcfg);
+}
+// the batch's reverse wavefront: blockIdx.z = video, every video counts down from ITS OWN last step (launch k = layer 1 at T_v-1-k ||
+// layer 0 at T_v-k) and carries its own d c: DC is [V][2][H]
+struct SstWaveBB {
+    const float *WT0, *WT1, *WT_IH1, *ACT0, *ACT1, *CS0, *CS1, *DHO;
+    float *DG0, *DG1, *DC;
+    const int* row_offset;
+    int H, k;
+};
+__global__ __launch_bounds__(256) void sst_wave_bwd_batch_kernel(SstWaveBB p, DropCfg dcfg) {
+    const int v = blockIdx.z, H = p.H, k = p.k;
+    const long base = p.row_offset[v];
+    const int Tv = p.row_offset[v + 1] - (int)base;
+    SstBwdRole r{};
+    if (blockIdx.y == 0) {
+        const int t = Tv - 1 - k;
+        if (t < 0) return;
+        const long row = base + t;
+        r.t = (int)row;
+        r.WT[0] = p.WT1; r.vec[0] = t + 1 < Tv ? p.DG1 + (row + 1) * 4 * H : nullptr;
+        r.dh_base = p.DHO + row * H;
+        r.act = p.ACT1 + row * 4 * H; r.c = p.CS1 + row * H; r.cprev = t ? p.CS1 + (row - 1) * H : nullptr;
+        r.dc = p.DC + ((long)v * 2 + 1) * H; r.dg = p.DG1 + row * 4 * H;
+    } else {
+        const int t = Tv - k;
+        if (k < 1 || t < 0) return;
+        const long row = base + t;
+        r.t = (int)row; r.drop_first = 1;
+        r.WT[0] = p.WT_IH1; r.vec[0] = p.DG1 + row * 4 * H;
+        r.WT[1] = p.WT0; r.vec[1] = t + 1 < Tv ? p.DG0 + (row + 1) * 4 * H : nullptr;
+        r.act = p.ACT0 + row * 4 * H; r.c = p.CS0 + row * H; r.cprev = t ? p.CS0 + (row - 1) * H : nullptr;
+        r.dc = p.DC + (long)v * 2 * H; r.dg = p.DG0 + row * 4 * H;
+    }
+    sst_wave_bwd_body(r, H, dcfg);
+}
+// h(t-1) per row of the concatenated layout, ZERO at the first row of every video: the recurrent weight gradient dW_hh = dG^T . hprev is then
+// one TN product over all T_tot rows in which no row of one video meets a state of another
+__global__ __launch_bounds__(128) void sst_shift_rows_kernel(const float* __restrict__ h0, const float* __restrict__ h1, float* __restrict__ p0,
+                                                             float* __restrict__ p1, const int* __restrict__ row_offset, int V, int H) {
+    __shared__ int first;
+    const long r = blockIdx.x;
+    if (threadIdx.x == 0) first = 0;
+    __syncthreads();
+    for (int i = threadIdx.x; i < V; i += 128) if (row_offset[i] == (int)r) first = 1;
+    __syncthreads();
+    const bool z = first != 0;
+    for (int c = threadIdx.x * 4; c < H; c += 512) {
+        const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+        *reinterpret_cast<float4*>(p0 + r * H + c) = z ? zero : *reinterpret_cast<const float4*>(h0 + (r - 1) * H + c);
+        *reinterpret_cast<float4*>(p1 + r * H + c) = z ? zero : *reinterpret_cast<const float4*>(h1 + (r - 1) * H + c);
     }
 }
 
@@ -609,6 +714,358 @@ __global__ __launch_bounds__(256, 1) void sst_persist_bwd_kernel(SstPB P) {
     }
 }
 
+// ---- the same two persistent recurrences over a GROUP of up to SPB_NV videos ---------------------------------------------------------
+// The register-resident slices serve every video of the group inside one step: the step's memory round trip (poll -> products -> publish)
+// is paid once per step, not once per video and step.  The host orders a group's videos by length, longest first, so at wavefront step k
+// the videos still running are the slots [0, nact): a video that has ended is neither polled nor multiplied.  Every video starts from the
+// zero state at its own step 0 (forward) / its own last step (reverse); rows are those of the concatenated layout, base[slot] + t.
+// Protocol, spin bound and abort plumbing are the single-video kernels'.
+//   * forward: ONE sweep polls the rows of every running video (6 KB each), then the products of all of them, then lanes 2j / 2j+1 of every
+//     32-lane group finish layers 0 / 1 of slot j in one pass of the cell math;
+//   * reverse (16 KB per video and step: the wait is bandwidth, not only latency): the group runs as two half-groups (even / odd slots) per
+//     step -- half B's rows travel while half A is multiplied, and half A's rows were published half a step ago, so its sweep finds them;
+//   * the vector pieces of the products are read from LDS a few ahead: with one wave per SIMD nothing else hides that latency.
+// (measured alternatives: DESIGN.md section 4m)
+constexpr int SPB_NV = 8;       // reverse: 2 x 4H floats of LDS per video (16 KB) -> 8 videos in 128 KB; forward: 6 KB per video
+struct SstGrp { int nv, base[SPB_NV], len[SPB_NV]; };
+struct SstPFB { SstPF p; SstGrp g; };
+struct SstPBB { SstPB p; SstGrp g; };
+
+// bounded wait of the batched kernels: bit p of `pend` = piece p of this thread is still outstanding; `issue` loads the outstanding pieces
+// (all loads of a sweep back to back: one round trip for the whole half-group), `land` stores a complete piece to LDS.
+template <int NP, typename FL>
+__device__ __forceinline__ u32s spb_check(u32s pend, const u32x4s (&v)[NP], FL&& land) {
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+        if (!(pend & (1u << p))) continue;
+        if (v[p].x != SP_SENT && v[p].y != SP_SENT && v[p].z != SP_SENT && v[p].w != SP_SENT) {
+            land(p, make_float4(__uint_as_float(v[p].x), __uint_as_float(v[p].y), __uint_as_float(v[p].z), __uint_as_float(v[p].w)));
+            pend &= ~(1u << p);
+        }
+    }
+    return pend;
+}
+// false = give up (abort raised here or elsewhere)
+template <int NP, typename FI, typename FL>
+__device__ __forceinline__ bool spb_poll(u32s pend, const SpSync& y, u32s code, FI&& issue, FL&& land) {
+    u32s spins = 0;
+    while (pend) {
+        u32x4s v[NP];
+        issue(pend, v);
+        pend = spb_check<NP>(pend, v, land);
+        if (!pend) break;
+        if ((++spins & 31) == 0) {
+            if (__hip_atomic_load(y.abort_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return false;
+            if (spins > y.spin_limit) {
+                __hip_atomic_store(y.abort_word, code, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(y.host_flag, code, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                return false;
+            }
+        }
+        __builtin_amdgcn_s_sleep(1);
+    }
+    return true;
+}
+
+__global__ __launch_bounds__(256, 1) void sst_persist_fwd_batch_kernel(SstPFB B) {
+    extern __shared__ __attribute__((aligned(16))) float svb[];      // [slot][ h0(k-1) | h0d(k-1) | h1(k-2) ]
+    __shared__ int fail;
+    const SstPF& P = B.p;
+    constexpr int H = SP_H, SLOT4 = 3 * SP_H / 4;                     // float4 per slot
+    const int tid = threadIdx.x, G = tid >> 5, kp = tid & 31;
+    const int u = blockIdx.x * SP_U + G;
+    const int Tmax = P.T;
+    if (tid == 0) fail = 0;
+    float4 W0[4][4], W1[4][8];
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        const long row = (long)(g * H + u) * H;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) W0[g][j] = *reinterpret_cast<const float4*>(P.w_hh0 + row + 4 * kp + 128 * j);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int k = 4 * kp + 128 * j;
+            W1[g][j] = k < H ? *reinterpret_cast<const float4*>(P.w_ih1 + row + k) : *reinterpret_cast<const float4*>(P.w_hh1 + row + k - H);
+        }
+    }
+    // the butterfly leaves every sum in every lane of the 32-lane group: lane 2j finishes layer 0 of slot j, lane 2j+1 its layer 1
+    const int slot = kp >> 1;
+    const bool fin1 = (kp & 1) != 0;
+    int mybase = 0, mylen = 0;                                        // lanes without a video keep length 0: never active
+#pragma unroll
+    for (int i = 0; i < SPB_NV; ++i)
+        if (slot == i && i < B.g.nv) { mybase = B.g.base[i]; mylen = B.g.len[i]; }
+    float bias1[4];
+#pragma unroll
+    for (int g = 0; g < 4; ++g) bias1[g] = P.b_ih1[g * H + u] + P.b_hh1[g * H + u];
+    float cst = 0.f;
+    float4* sv4 = reinterpret_cast<float4*>(svb);
+    for (int i = tid; i < SPB_NV * 128; i += 256) sv4[(i >> 7) * SLOT4 + 256 + (i & 127)] = make_float4(0.f, 0.f, 0.f, 0.f);      // h1(-1) = 0
+    __syncthreads();
+    const u32s ROWB = H * 4;
+    const bool lowhalf = __builtin_amdgcn_readfirstlane(tid) < 128;   // waves 0, 1: h0 and h1 pieces; waves 2, 3: h0d
+    const float* hsrc = lowhalf ? P.HS0 : P.H0D;
+    for (int k = 0; k <= Tmax; ++k) {
+        int nact = 0;
+#pragma unroll
+        for (int i = 0; i < SPB_NV; ++i) nact += (i < B.g.nv && B.g.len[i] >= k) ? 1 : 0;
+        const bool l0 = !fin1 && k < mylen, l1 = fin1 && k >= 1 && k <= mylen;
+        float gin[4] = {0.f, 0.f, 0.f, 0.f};
+        float mk = 1.f;
+        if (l0) {
+#pragma unroll
+            for (int g = 0; g < 4; ++g) gin[g] = P.GIN0[(long)(mybase + k) * 4 * H + g * H + u];
+            mk = drop_mult(P.dc, (unsigned)((mybase + k) * H + u), 0u, SITE_SST);
+        }
+        SP_STAMP(0);
+        if (k >= 1) {
+            u32s pend = 0;
+#pragma unroll
+            for (int i = 0; i < SPB_NV; ++i)
+                if (i < nact) pend |= (1u << (2 * i)) | ((k >= 2 && lowhalf) ? (2u << (2 * i)) : 0u);
+            const u32s off = (u32s)((tid & 127) * 16);
+            const bool ok = spb_poll<2 * SPB_NV>(pend, P.y, 8000u + (u32s)(k % 1000),
+                [&](u32s pd, u32x4s (&v)[2 * SPB_NV]) {
+#pragma unroll
+                    for (int i = 0; i < SPB_NV; ++i) {
+                        if (pd & (1u << (2 * i))) v[2 * i] = sp_ld16(sp_rsrc(hsrc + (long)(B.g.base[i] + k - 1) * H, ROWB), off);
+                        if (pd & (2u << (2 * i))) v[2 * i + 1] = sp_ld16(sp_rsrc(P.TAP + (long)(B.g.base[i] + max(k - 2, 0)) * H, ROWB), off);
+                    }
+                },
+                [&](int p, const float4& x) { sv4[(p >> 1) * SLOT4 + ((p & 1) ? 256 + tid : tid)] = x; });
+            if (!ok) fail = 1;
+        }
+        SP_STAMP(1);
+        __syncthreads();
+        if (fail) return;
+        SP_STAMP(2);
+        float mine[4] = {0.f, 0.f, 0.f, 0.f};
+        if (k >= 1) {
+#pragma unroll
+            for (int i = 0; i < SPB_NV; ++i) {
+                if (i >= nact) continue;
+                const float4* v4 = sv4 + i * SLOT4;
+                f2s a0[4], a1[4];
+#pragma unroll
+                for (int g = 0; g < 4; ++g) { a0[g] = f2s{0.f, 0.f}; a1[g] = f2s{0.f, 0.f}; }
+                // twelve vector pieces per video, XPF of them in flight: with one wave per SIMD nothing else hides the LDS latency
+                constexpr int XPF = 3;
+                float4 xb[XPF + 1];
+#pragma unroll
+                for (int q = 0; q < XPF; ++q) xb[q] = v4[kp + 32 * q];
+#pragma unroll
+                for (int q = 0; q < 12; ++q) {
+                    if (q + XPF < 12) xb[(q + XPF) % (XPF + 1)] = v4[kp + 32 * (q + XPF)];          // h0 | h0d | h1 are contiguous: piece q of [W_hh0 | W_ih1 | W_hh1]
+                    const float4 x = xb[q % (XPF + 1)];
+#pragma unroll
+                    for (int g = 0; g < 4; ++g) {
+                        if (q < 4) sp_dot4(a0[g], W0[g][q], x);
+                        else sp_dot4(a1[g], W1[g][q - 4], x);
+                    }
+                }
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const float s0 = sp_sum32(a0[g].x + a0[g].y), s1 = sp_sum32(a1[g].x + a1[g].y);
+                    if (slot == i) mine[g] = fin1 ? s1 : s0;
+                }
+            }
+        }
+        SP_STAMP(3);
+        // (no barrier: a video's rows of the next step are complete only after every wave of THIS workgroup has published, which it does
+        // behind its reads of every slot)
+        {
+            const float pi = mine[0] + (fin1 ? bias1[0] : gin[0]), pf = mine[1] + (fin1 ? bias1[1] : gin[1]);
+            const float pg = mine[2] + (fin1 ? bias1[2] : gin[2]), po = mine[3] + (fin1 ? bias1[3] : gin[3]);
+            const float gi = fast_sigmoid(pi), gf = fast_sigmoid(pf), gg = fast_tanh(pg), go = fast_sigmoid(po);
+            const float c = gf * cst + gi * gg;
+            const float h = go * fast_tanh(c);
+            if (l0) {
+                const long row = mybase + k;
+                cst = c;
+                sp_store(P.HS0 + row * H + u, h);
+                sp_store(P.H0D + row * H + u, h * mk);
+                float* act = P.ACT0 + row * 4 * H + u;
+                act[0] = gi; act[H] = gf; act[2 * H] = gg; act[3 * H] = go;
+                P.CS0[row * H + u] = c;
+            } else if (l1) {
+                const long row = mybase + k - 1;
+                cst = c;
+                sp_store(P.TAP + row * H + u, h);
+                float* act = P.ACT1 + row * 4 * H + u;
+                act[0] = gi; act[H] = gf; act[2 * H] = gg; act[3 * H] = go;
+                P.CS1[row * H + u] = c;
+            }
+        }
+        SP_STAMP(4);
+    }
+}
+
+__global__ __launch_bounds__(256, 1) void sst_persist_bwd_batch_kernel(SstPBB B) {
+    extern __shared__ __attribute__((aligned(16))) float sdyn[];     // [slot][ dG1(t0) | dG0(t0+1) ]; the set-up staging [8][4H] aliases slots 0..3
+    __shared__ int fail;
+    const SstPB& P = B.p;
+    constexpr int H = SP_H, H4 = 4 * SP_H, SLOT4 = 2 * H4 / 4;
+    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
+    const int Tmax = P.T;
+    if (tid == 0) fail = 0;
+    float4 A1[2][8], A2[2][8], A3[2][8];
+    {
+        float* stage = sdyn;
+        const float* Ws[3] = {P.w_hh1, P.w_ih1, P.w_hh0};
+#pragma unroll
+        for (int mtx = 0; mtx < 3; ++mtx) {
+            for (int idx = tid; idx < H4 * 2; idx += 256) {
+                const int row = idx >> 1, half = idx & 1;
+                const float4 v = *reinterpret_cast<const float4*>(Ws[mtx] + (long)row * H + blockIdx.x * SP_U + 4 * half);
+                stage[(4 * half + 0) * H4 + row] = v.x; stage[(4 * half + 1) * H4 + row] = v.y;
+                stage[(4 * half + 2) * H4 + row] = v.z; stage[(4 * half + 3) * H4 + row] = v.w;
+            }
+            __syncthreads();
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const float4 v = *reinterpret_cast<const float4*>(stage + (2 * w + i) * H4 + 4 * lane + 256 * j);
+                    if (mtx == 0) A1[i][j] = v; else if (mtx == 1) A2[i][j] = v; else A3[i][j] = v;
+                }
+            __syncthreads();
+        }
+    }
+    // lanes 4j .. 4j+3 of the wave finish slot j: unit 2w + (lane & 1), lanes 0 / 1 layer 1 at step t, lanes 2 / 3 layer 0 at step t0
+    const int slot = lane >> 2, ui = lane & 1;
+    const bool fl0 = (lane & 2) != 0;
+    const int u = blockIdx.x * SP_U + 2 * w + ui;
+    int mybase = 0, mylen = 0;
+#pragma unroll
+    for (int i = 0; i < SPB_NV; ++i)
+        if (slot == i && i < B.g.nv) { mybase = B.g.base[i]; mylen = B.g.len[i]; }
+    float dcst = 0.f;
+    float4* sg4 = reinterpret_cast<float4*>(sdyn);
+    const u32s ROWB = H4 * 4;
+    constexpr int HV = SPB_NV / 2;                                    // videos per half-group: half h = slots 2j + h
+    for (int k = 0; k <= Tmax; ++k) {
+        int nact = 0;
+#pragma unroll
+        for (int i = 0; i < SPB_NV; ++i) nact += (i < B.g.nv && B.g.len[i] >= k) ? 1 : 0;
+        const int tt = fl0 ? mylen - k : mylen - 1 - k;               // this lane's timestep inside its video
+        const bool act_on = fl0 ? (k >= 1 && k <= mylen) : (k < mylen);
+        const long row = mybase + tt;
+        float ac[4] = {0.f, 0.f, 0.f, 0.f}, cc = 0.f, cp = 0.f, dho = 0.f, mk = 1.f;
+        if (act_on) {
+            const float* A = fl0 ? P.ACT0 : P.ACT1;
+            const float* Cs = fl0 ? P.CS0 : P.CS1;
+#pragma unroll
+            for (int g = 0; g < 4; ++g) ac[g] = A[row * H4 + g * H + u];
+            cc = Cs[row * H + u]; cp = tt ? Cs[(row - 1) * H + u] : 0.f;
+            if (!fl0) dho = P.DHO[row * H + u];
+            else mk = drop_mult(P.dc, (unsigned)((int)row * H + u), 0u, SITE_SST);
+        }
+        float e1 = 0.f, e2 = 0.f, e3 = 0.f;
+        // pieces of half h: bits 4j, 4j + 1 = the two float4 of dG1(t0) of slot 2j + h, bits 4j + 2, 4j + 3 = dG0(t0 + 1) (from step 2 on)
+        auto pending = [&](int h) {
+            u32s pend = 0;
+#pragma unroll
+            for (int j = 0; j < HV; ++j)
+                if (2 * j + h < nact) pend |= (k >= 2 ? 0xFu : 0x3u) << (4 * j);
+            return pend;
+        };
+        auto issue = [&](int h, u32s pd, u32x4s (&v)[4 * HV]) {
+#pragma unroll
+            for (int j = 0; j < HV; ++j) {
+                if (!(pd & (0xFu << (4 * j)))) continue;
+                const int i = 2 * j + h;
+                const int Ti = B.g.len[i], t0 = Ti - k;
+                const __amdgpu_buffer_rsrc_t r1 = sp_rsrc(P.DG1 + (long)(B.g.base[i] + t0) * H4, ROWB);
+                const __amdgpu_buffer_rsrc_t r0 = sp_rsrc(P.DG0 + (long)(B.g.base[i] + min(t0 + 1, Ti - 1)) * H4, ROWB);
+                if (pd & (1u << (4 * j))) v[4 * j] = sp_ld16(r1, (u32s)(tid * 16));
+                if (pd & (2u << (4 * j))) v[4 * j + 1] = sp_ld16(r1, (u32s)((tid + 256) * 16));
+                if (pd & (4u << (4 * j))) v[4 * j + 2] = sp_ld16(r0, (u32s)(tid * 16));
+                if (pd & (8u << (4 * j))) v[4 * j + 3] = sp_ld16(r0, (u32s)((tid + 256) * 16));
+            }
+        };
+        auto land = [&](int h, int p, const float4& x) { sg4[(2 * (p >> 2) + h) * SLOT4 + (p & 3) * 256 + tid] = x; };
+        auto products = [&](int h) {
+#pragma unroll
+            for (int j = 0; j < HV; ++j) {
+                const int i = 2 * j + h;
+                if (i >= nact) continue;
+                const float4* g4 = sg4 + i * SLOT4;
+                f2s b1[2], b2[2], b3[2];
+#pragma unroll
+                for (int q = 0; q < 2; ++q) b1[q] = b2[q] = b3[q] = f2s{0.f, 0.f};
+                // XPF vector pieces in flight (one wave per SIMD: nothing else hides the LDS latency)
+                constexpr int XPF = 3;
+                float4 xb[XPF + 1];
+#pragma unroll
+                for (int c = 0; c < XPF; ++c) xb[c] = g4[lane + 64 * c];
+#pragma unroll
+                for (int c = 0; c < 8; ++c) {
+                    if (c + XPF < 8) xb[(c + XPF) % (XPF + 1)] = g4[lane + 64 * (c + XPF)];
+                    const float4 x = xb[c % (XPF + 1)];
+#pragma unroll
+                    for (int q = 0; q < 2; ++q) { sp_dot4(b1[q], A1[q][c], x); sp_dot4(b2[q], A2[q][c], x); }
+                }
+                if (k >= 2) {
+#pragma unroll
+                    for (int c = 0; c < XPF; ++c) xb[c] = g4[512 + lane + 64 * c];
+#pragma unroll
+                    for (int c = 0; c < 8; ++c) {
+                        if (c + XPF < 8) xb[(c + XPF) % (XPF + 1)] = g4[512 + lane + 64 * (c + XPF)];
+                        const float4 x = xb[c % (XPF + 1)];
+#pragma unroll
+                        for (int q = 0; q < 2; ++q) sp_dot4(b3[q], A3[q][c], x);
+                    }
+                }
+                float d1[2], d2[2], d3[2];
+#pragma unroll
+                for (int q = 0; q < 2; ++q) { d1[q] = sp_sum64(b1[q].x + b1[q].y); d2[q] = sp_sum64(b2[q].x + b2[q].y); d3[q] = sp_sum64(b3[q].x + b3[q].y); }
+                if (slot == i) { e1 = ui ? d1[1] : d1[0]; e2 = ui ? d2[1] : d2[0]; e3 = ui ? d3[1] : d3[0]; }
+            }
+        };
+        auto cell = [&](int h) {
+            if ((slot & 1) != h || !act_on) return;
+            const float dh = fl0 ? e2 * mk + e3 : dho + e1;
+            const float gi = ac[0], gf = ac[1], gg = ac[2], go = ac[3];
+            const float tc = fast_tanh(cc);
+            const float dcv = dh * go * (1.f - tc * tc) + dcst;
+            float* dg = (fl0 ? P.DG0 : P.DG1) + row * H4 + u;
+            sp_store(dg, dcv * gg * gi * (1.f - gi));
+            sp_store(dg + H, dcv * cp * gf * (1.f - gf));
+            sp_store(dg + 2 * H, dcv * gi * (1.f - gg * gg));
+            sp_store(dg + 3 * H, dh * tc * go * (1.f - go));
+            dcst = dcv * gf;
+        };
+        SP_STAMP(0);
+        if (k >= 1) {
+            if (!spb_poll<4 * HV>(pending(0), P.y, 8500u + (u32s)(k % 500), [&](u32s pd, u32x4s (&v)[4 * HV]) { issue(0, pd, v); },
+                                  [&](int p, const float4& x) { land(0, p, x); })) fail = 1;
+        }
+        SP_STAMP(1);
+        __syncthreads();
+        if (fail) return;
+        SP_STAMP(2);
+        // half B's rows (published at the end of the previous step) travel while half A is multiplied
+        u32x4s vB[4 * HV];
+        u32s pendB = 0;
+        if (k >= 1 && nact >= 2) { pendB = pending(1); issue(1, pendB, vB); }
+        if (k >= 1) products(0);
+        cell(0);
+        SP_STAMP(3);
+        if (nact >= 2) {
+            if (k >= 1) {
+                pendB = spb_check<4 * HV>(pendB, vB, [&](int p, const float4& x) { land(1, p, x); });
+                if (!spb_poll<4 * HV>(pendB, P.y, 8500u + (u32s)(k % 500), [&](u32s pd, u32x4s (&v)[4 * HV]) { issue(1, pd, v); },
+                                      [&](int p, const float4& x) { land(1, p, x); })) fail = 1;
+            }
+            __syncthreads();
+            if (fail) return;
+            if (k >= 1) products(1);
+            cell(1);
+        }
+        SP_STAMP(4);
+    }
+}
+
 }  // namespace
 
 static inline long rup(long x, long a) { return (x + a - 1) / a * a; }
@@ -873,6 +1330,184 @@ extern "C" int echr_sst_bwd(const echr_sst_args* a, const echr_sst_grads* g, con
         } else if (!z) {
             RC(fill_zero(g->g_w_hh[l], (long)4 * H * H, sl));
         }
+        RC(colsum2(b.DG[l], 4 * H, T, 4 * H, g->g_b_ih[l], g->g_b_hh[l], z, sl));
+    }
+    if (fork) RC(aux_join(st));
+    return 0;
+}
+
+// =====================================================================================================================
+// Multi-video batches (echr_sst_batch): V videos concatenated row-wise, every video from the zero state.  Products over rows (layer 0's
+// input product, the head, the input-side weight gradients, the bias sums) are the single-video launches over T_tot rows; the recurrences
+// carry a video axis (persistent form: groups of SPB_NV videos per launch; wavefront form: blockIdx.z).
+// =====================================================================================================================
+namespace echr {
+struct SstWsBB { SstWsB b; float *HP[2], *DCV; long total; };
+static SstWsBB carve_bb(int T, int D, int H, int K, int V, float* base) {
+    SstWsBB w;
+    w.b = carve_b(T, D, H, K, base);
+    long off = w.b.total;
+    auto take = [&](long n) { float* p = base ? base + off : nullptr; off += rup(n, 64); return p; };
+    w.HP[0] = take((long)T * H); w.HP[1] = take((long)T * H);        // h(t-1) per row, zero at video starts (recurrent weight gradients)
+    w.DCV = take((long)V * 2 * H);                                   // wavefront form: d c carried per video and layer
+    w.total = off;
+    return w;
+}
+// groups of the persistent form: videos ordered by length (longest first, ties by index) and cut into runs of SPB_NV -- a group runs
+// len[0] + 1 steps, so neighbours in length share a launch
+static void sst_groups(const echr_sst_batch* x, std::vector<SstGrp>& out) {
+    const int V = x->n_videos;
+    std::vector<int> order(V);
+    for (int v = 0; v < V; ++v) order[v] = v;
+    const int32_t* ro = x->row_offset_host;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return ro[a + 1] - ro[a] > ro[b + 1] - ro[b]; });
+    for (int s = 0; s < V; s += SPB_NV) {
+        SstGrp g{};
+        g.nv = std::min(SPB_NV, V - s);
+        for (int i = 0; i < g.nv; ++i) { g.base[i] = ro[order[s + i]]; g.len[i] = ro[order[s + i] + 1] - ro[order[s + i]]; }
+        out.push_back(g);
+    }
+}
+}  // namespace echr
+
+extern "C" int echr_sst_batch_group(void) { return SPB_NV; }
+extern "C" int64_t echr_sst_batch_ws_floats(int32_t T, int32_t D, int32_t H, int32_t K, int32_t V) { (void)V; return carve(T, D, H, K, nullptr).total; }
+extern "C" int64_t echr_sst_batch_ws_bwd_floats(int32_t T, int32_t D, int32_t H, int32_t K, int32_t V) {
+    return carve_bb(T, D, H, K, V > 0 ? V : 1, nullptr).total;
+}
+
+static int sst_batch_check(const echr_sst_args* a, const echr_sst_batch* x, const char* who) {
+    RC(sst_check(a, who));
+    ECHR_REQUIRE(x && x->n_videos >= 1 && x->n_videos <= 65535 && x->row_offset && x->row_offset_host, "%s: missing batch description (1..65535 videos)", who);
+    ECHR_REQUIRE(x->row_offset_host[0] == 0 && x->row_offset_host[x->n_videos] == a->T, "%s: row_offset must run from 0 to T_tot = %d", who, a->T);
+    for (int v = 0; v < x->n_videos; ++v)
+        ECHR_REQUIRE(x->row_offset_host[v + 1] > x->row_offset_host[v], "%s: video %d has no row", who, v);
+    ECHR_REQUIRE((long)a->T * a->H < (1l << 31), "%s: T_tot * H must stay below 2^31 (dropout keys)", who);
+    return 0;
+}
+static int sst_tmax(const echr_sst_batch* x) {
+    int m = 0;
+    for (int v = 0; v < x->n_videos; ++v) m = std::max(m, (int)(x->row_offset_host[v + 1] - x->row_offset_host[v]));
+    return m;
+}
+
+extern "C" int echr_sst_fwd_batch(const echr_sst_args* a, const echr_sst_batch* x, const echr_dropout* drop, void* stream) {
+    RC(sst_batch_check(a, x, "sst_fwd_batch"));
+    if (x->n_videos == 1) return sst_fwd_impl(a, drop, stream, true);          // one video: today's call, today's dropout keys
+    hipStream_t st = (hipStream_t)stream;
+    const int T = a->T, D = a->D, H = a->H, K = a->K, V = x->n_videos;
+    SstWs w = carve(T, D, H, K, a->ws);
+    const DropCfg dc = make_drop(drop, a->p_drop);
+    echr_gemm_desc d0 = desc_nt(a->x, D, a->w_ih[0], D, w.GIN0, 4 * H, T, 4 * H, D);
+    d0.bias = a->b_ih[0]; d0.bias2 = a->b_hh[0]; d0.split_k = T >= 128 ? 1 : -1;
+    RC(gemm(d0, st));
+    if (sst_persist_ok(H)) {
+        RC(persist_check_async());
+        if (hipMemsetAsync(w.HS[0], 0xFF, sizeof(float) * (size_t)((w.H0D - w.HS[0]) + (long)T * H), st) != hipSuccess ||
+            hipMemsetAsync(a->tap_feats, 0xFF, sizeof(float) * (size_t)T * H, st) != hipSuccess) { set_error("sst_fwd_batch: memset failed"); return -5; }
+        std::vector<SstGrp> groups;
+        sst_groups(x, groups);
+        ProfScope prof(PROF_SST, 2.0 * T * 3.0 * 4 * H * H, 4.0 * (groups.size() * 3.0 * 4 * H * H + (double)T * (4.0 * H + 2 * (4.0 * H + 2.0 * H) + H)), st);
+        for (size_t gi = 0; gi < groups.size(); ++gi) {
+            SstPFB B;
+            SstPF& P = B.p;
+            P.T = groups[gi].len[0]; P.w_hh0 = a->w_hh[0]; P.w_ih1 = a->w_ih[1]; P.w_hh1 = a->w_hh[1]; P.b_ih1 = a->b_ih[1]; P.b_hh1 = a->b_hh[1]; P.GIN0 = w.GIN0;
+            P.HS0 = w.HS[0]; P.H0D = w.H0D; P.TAP = a->tap_feats; P.ACT0 = w.ACT[0]; P.ACT1 = w.ACT[1]; P.CS0 = w.CS[0]; P.CS1 = w.CS[1];
+            P.y = sst_sync(); P.dc = dc;
+            P.stamps = (gi == 0 && config().persist_stamps == 3) ? persist_stamp_buffer(P.T + 1, st) : nullptr;
+            B.g = groups[gi];
+            RC(sst_persist_launch(sst_persist_fwd_batch_kernel, B, "sst_persist_fwd_batch", st, sizeof(float) * SPB_NV * 3 * SP_H));
+        }
+    } else {
+        const int nwg = (H + UPW - 1) / UPW, Tmax = sst_tmax(x);
+        SstWaveFB p;
+        p.w_hh0 = a->w_hh[0]; p.w_ih1 = a->w_ih[1]; p.w_hh1 = a->w_hh[1]; p.b_ih1 = a->b_ih[1]; p.b_hh1 = a->b_hh[1]; p.GIN0 = w.GIN0;
+        p.HS0 = w.HS[0]; p.H0D = w.H0D; p.TAP = a->tap_feats; p.ACT0 = w.ACT[0]; p.ACT1 = w.ACT[1]; p.CS0 = w.CS[0]; p.CS1 = w.CS[1];
+        p.row_offset = x->row_offset; p.H = H;
+        for (int k = 0; k <= Tmax; ++k) {
+            p.k = k;
+            hipLaunchKernelGGL(sst_wave_fwd_batch_kernel, dim3(nwg, 2, V), dim3(256), (2 * H + 4 * UPW) * sizeof(float), st, p, dc);
+        }
+        RC(check_launch("sst_wave_fwd_batch"));
+    }
+    return sst_head_impl(a, st);
+}
+
+extern "C" int echr_sst_bwd_batch(const echr_sst_args* a, const echr_sst_batch* x, const echr_sst_grads* g, const echr_dropout* drop, void* stream) {
+    RC(sst_batch_check(a, x, "sst_bwd_batch"));
+    if (x->n_videos == 1) return echr_sst_bwd(a, g, drop, stream);
+    ECHR_REQUIRE(g && g->ws_bwd && (g->g_tap || g->g_scores), "sst_bwd_batch: missing buffers");
+    hipStream_t st = (hipStream_t)stream;
+    const int T = a->T, D = a->D, H = a->H, K = a->K, V = x->n_videos;
+    SstWs w = carve(T, D, H, K, a->ws);
+    SstWsBB bb = carve_bb(T, D, H, K, V, g->ws_bwd);
+    SstWsB& b = bb.b;
+    const DropCfg dc = make_drop(drop, a->p_drop);
+    const bool z = g->zeroed != 0;
+    const float zb = z ? 1.f : 0.f;
+    echr_gemm_desc d;
+    if (g->g_tap) RC(hipMemcpyAsync(b.DHO, g->g_tap, sizeof(float) * T * H, hipMemcpyDeviceToDevice, st) == hipSuccess ? 0 : -5);
+    else RC(fill_zero(b.DHO, (long)T * H, st));
+    if (g->g_scores) {
+        const long n = (long)T * K;
+        hipLaunchKernelGGL(sigmoid_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a->scores, g->g_scores, b.DZ, n);
+        RC(check_launch("sigmoid_bwd"));
+        d = desc_nn(b.DZ, K, a->w_sc, H, b.DHO, H, T, H, K); d.beta = 1.f; d.split_k = -1;
+        RC(gemm(d, st));
+        d = desc_tn(b.DZ, K, a->tap_feats, H, g->g_w_sc, H, K, H, T); d.split_k = -1; d.beta = zb;
+        RC(gemm(d, st));
+        RC(colsum(b.DZ, K, T, K, g->g_b_sc, z, st));
+    } else if (!z) {
+        RC(fill_zero(g->g_w_sc, (long)K * H, st));
+        RC(fill_zero(g->g_b_sc, K, st));
+    }
+    // previous-state rows for the recurrent weight gradients (reads the forward's states only: ahead of the recurrence, off its tail)
+    hipLaunchKernelGGL(sst_shift_rows_kernel, dim3(T), dim3(128), 0, st, w.HS[0], a->tap_feats, bb.HP[0], bb.HP[1], x->row_offset, V, H);
+    RC(check_launch("sst_shift_rows"));
+    if (sst_persist_ok(H)) {
+        RC(persist_check_async());
+        if (hipMemsetAsync(b.DG[0], 0xFF, sizeof(float) * (size_t)((b.DG[1] - b.DG[0]) + (long)T * 4 * H), st) != hipSuccess) { set_error("sst_bwd_batch: memset failed"); return -5; }
+        std::vector<SstGrp> groups;
+        sst_groups(x, groups);
+        ProfScope prof(PROF_SST, 2.0 * T * 3.0 * 4 * H * H, 4.0 * (groups.size() * 3.0 * 4 * H * H + (double)T * (2 * (4.0 * H + 2.0 * H) + H + 2 * 4.0 * H)), st);
+        for (size_t gi = 0; gi < groups.size(); ++gi) {
+            SstPBB B;
+            SstPB& P = B.p;
+            P.T = groups[gi].len[0]; P.w_hh0 = a->w_hh[0]; P.w_ih1 = a->w_ih[1]; P.w_hh1 = a->w_hh[1];
+            P.ACT0 = w.ACT[0]; P.ACT1 = w.ACT[1]; P.CS0 = w.CS[0]; P.CS1 = w.CS[1]; P.DHO = b.DHO; P.DG0 = b.DG[0]; P.DG1 = b.DG[1];
+            P.y = sst_sync(); P.dc = dc;
+            P.stamps = (gi == 0 && config().persist_stamps == 4) ? persist_stamp_buffer(P.T + 1, st) : nullptr;
+            B.g = groups[gi];
+            RC(sst_persist_launch(sst_persist_bwd_batch_kernel, B, "sst_persist_bwd_batch", st, sizeof(float) * SPB_NV * 2 * 4 * SP_H));
+        }
+    } else {
+        const TransposeJob tj[3] = {{a->w_hh[0], H, b.WT[0], 4 * H, 4 * H, H}, {a->w_hh[1], H, b.WT[1], 4 * H, 4 * H, H},
+                                    {a->w_ih[1], H, b.WT_IH1, 4 * H, 4 * H, H}};
+        RC(transpose_multi(tj, 3, st));
+        RC(fill_zero(bb.DCV, (long)V * 2 * H, st));
+        const int nwg = (H + UPW - 1) / UPW, Tmax = sst_tmax(x);
+        SstWaveBB p;
+        p.WT0 = b.WT[0]; p.WT1 = b.WT[1]; p.WT_IH1 = b.WT_IH1; p.ACT0 = w.ACT[0]; p.ACT1 = w.ACT[1]; p.CS0 = w.CS[0]; p.CS1 = w.CS[1]; p.DHO = b.DHO;
+        p.DG0 = b.DG[0]; p.DG1 = b.DG[1]; p.DC = bb.DCV; p.row_offset = x->row_offset; p.H = H;
+        for (int k = 0; k <= Tmax; ++k) {
+            p.k = k;
+            hipLaunchKernelGGL(sst_wave_bwd_batch_kernel, dim3(nwg, 2, V), dim3(256), (8 * H + 2 * UPW) * sizeof(float), st, p, dc);
+        }
+        RC(check_launch("sst_wave_bwd_batch"));
+    }
+    // parameter gradients: sums over all T_tot rows; the recurrent ones against the shifted states (zero rows at video starts: no pair
+    // crosses a boundary).  Layer 0's products run on the helper stream beside layer 1's, as in echr_sst_bwd
+    hipStream_t s0 = aux_fork(st);
+    const bool fork = s0 != nullptr;
+    if (!fork) s0 = st;
+    for (int l = 1; l >= 0; --l) {
+        hipStream_t sl = l == 0 ? s0 : st;
+        const float* xin = l == 0 ? a->x : w.H0D;
+        const int din = l == 0 ? D : H;
+        d = desc_tn(b.DG[l], 4 * H, xin, din, g->g_w_ih[l], din, 4 * H, din, T); d.split_k = -1; d.beta = zb;
+        RC(gemm(d, sl));
+        d = desc_tn(b.DG[l], 4 * H, bb.HP[l], H, g->g_w_hh[l], H, 4 * H, H, T); d.split_k = -1; d.beta = zb;
+        RC(gemm(d, sl));
         RC(colsum2(b.DG[l], 4 * H, T, 4 * H, g->g_b_ih[l], g->g_b_hh[l], z, sl));
     }
     if (fork) RC(aux_join(st));

@@ -935,6 +935,68 @@ class SSTFunction(torch.autograd.Function):
         return (None, None, None, None) + tuple(grads)
 
 
+def sst_row_offsets(row_offset, rows):
+    """Validated host int32 copy of a batch's row offsets [V+1]: they start at 0, every video has a row, the last one equals `rows`."""
+    ro = np.asarray(row_offset.detach().cpu().numpy() if isinstance(row_offset, torch.Tensor) else row_offset)
+    if ro.ndim != 1 or len(ro) < 2 or not np.issubdtype(ro.dtype, np.integer) and np.any(ro != np.floor(ro)):
+        raise ValueError('row_offset must be a vector of V + 1 integers')
+    ro = ro.astype(np.int64)
+    if ro[0] != 0:
+        raise ValueError('row_offset must start at 0 (got %d)' % ro[0])
+    if np.any(np.diff(ro) <= 0):
+        raise ValueError('every video needs at least one feature row (row_offset=%s)' % ro.tolist())
+    if int(ro[-1]) != int(rows):
+        raise ValueError('row_offset ends at %d but the features have %d rows' % (ro[-1], rows))
+    return np.ascontiguousarray(ro.astype(np.int32))
+
+
+class SSTBatchFunction(torch.autograd.Function):
+    """SST.forward over a multi-video batch (echr_sst_fwd_batch / echr_sst_bwd_batch): x is the concatenated [T_tot, D] matrix, `ro_host` the
+    validated int32 offsets (sst_row_offsets), `ro_dev` their device copy.  Parameter gradients are the sum over the videos."""
+
+    @staticmethod
+    def forward(ctx, x, ro_host, ro_dev, p_drop, drop, sink, *params):
+        lib = L.load()
+        ctx.sink = sink
+        x = _f32c(x)
+        ps = [_f32c(p) for p in params]
+        T, D = x.shape
+        H, K = ps[1].shape[1], ps[8].shape[0]
+        V = len(ro_host) - 1
+        dev = x.device
+        ws = torch.empty(lib.echr_sst_batch_ws_floats(T, D, H, K, V), device=dev, dtype=torch.float32)
+        tap = torch.empty(T, H, device=dev, dtype=torch.float32)
+        scores = torch.empty(T, K, device=dev, dtype=torch.float32)
+        a = SSTFunction._args(ps, x, p_drop, ws, tap, scores)
+        bx = L.SstBatch(V, L.ptr(ro_dev, torch.int32), ro_host.ctypes.data)
+        d = drop.c()
+        L.check(lib.echr_sst_fwd_batch(C.byref(a), C.byref(bx), C.byref(d), L.stream_ptr()), 'sst_fwd_batch')
+        ctx.save_for_backward(x, ws, tap, scores, ro_dev, *ps)
+        ctx.meta = (p_drop, drop, ro_host)
+        return tap, scores
+
+    @staticmethod
+    def backward(ctx, g_tap, g_scores):
+        lib = L.load()
+        x, ws, tap, scores, ro_dev, *ps = ctx.saved_tensors
+        p_drop, drop, ro_host = ctx.meta
+        T, D = x.shape
+        H, K = ps[1].shape[1], ps[8].shape[0]
+        V = len(ro_host) - 1
+        use_arena = ctx.sink is not None and ctx.sink.usable()
+        grads = ctx.sink.take() if use_arena else [torch.empty_like(p) for p in ps]
+        wsb = torch.empty(lib.echr_sst_batch_ws_bwd_floats(T, D, H, K, V), device=x.device, dtype=torch.float32)
+        a = SSTFunction._args(ps, x, p_drop, ws, tap, scores)
+        bx = L.SstBatch(V, L.ptr(ro_dev, torch.int32), ro_host.ctypes.data)
+        two = lambda a_, b_: (L.c_f * 2)(L.ptr(a_), L.ptr(b_))
+        g = L.SstGrads(two(grads[0], grads[4]), two(grads[1], grads[5]), two(grads[2], grads[6]), two(grads[3], grads[7]),
+                       L.ptr(grads[8]), L.ptr(grads[9]), L.ptr(_f32c(g_tap)) if g_tap is not None else None,
+                       L.ptr(_f32c(g_scores)) if g_scores is not None else None, L.ptr(wsb), 1 if use_arena else 0)
+        d = drop.c()
+        L.check(lib.echr_sst_bwd_batch(C.byref(a), C.byref(bx), C.byref(g), C.byref(d), L.stream_ptr()), 'sst_bwd_batch')
+        return (None, None, None, None, None, None) + tuple(grads)
+
+
 class TapBCE(torch.autograd.Function):
     """TAPModelCriterion.forward (misc/utils.py:78-99) on device."""
 

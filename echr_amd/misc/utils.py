@@ -58,6 +58,21 @@ class TAPModelCriterion(nn.Module):
         return EF.TapBCE.apply(scores, masks.to(scores.device), labels.to(scores.device), w1.to(scores.device))
 
 
+def tap_criterion_batch(crit, scores, masks, labels, w1, row_offset):
+    """TAPModelCriterion over a multi-video batch: `scores`, `masks`, `labels` are the concatenated [T_tot, K] matrices, `row_offset` [V+1]
+    the videos' rows, `w1` one [K] weight vector for all videos or a list of V.  Returns (sum over the videos, per-video losses [V]): each
+    video keeps its own mean over its T_v x K elements (no 1/V), as V single-video iterations summed (train.py:281-283)."""
+    ro = [int(r) for r in (row_offset.tolist() if hasattr(row_offset, 'tolist') else row_offset)]
+    if len(ro) < 2 or ro[0] != 0 or any(b <= a for a, b in zip(ro[:-1], ro[1:])) or ro[-1] != scores.shape[0]:
+        raise ValueError('row_offset must start at 0, grow strictly and end at the number of score rows (%d): %s' % (scores.shape[0], ro))
+    per_w1 = isinstance(w1, (list, tuple))
+    if per_w1 and len(w1) != len(ro) - 1:
+        raise ValueError('w1 must be one weight vector or one per video')
+    per = [crit(scores[a:b], masks[a:b], labels[a:b], w1[v] if per_w1 else w1) for v, (a, b) in enumerate(zip(ro[:-1], ro[1:]))]
+    per = torch.stack(per)
+    return per.sum(), per
+
+
 def set_lr(optimizer, lr):
     for group in optimizer.param_groups:
         group['lr'] = lr

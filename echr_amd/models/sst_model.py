@@ -30,6 +30,7 @@ class SST(nn.Module):
                            dropout=opt.rnn_dropout, batch_first=True)
         self._drop_seed = None
         self._drop_calls = 0
+        self._ro_cache = {}
 
     # The reference overrides train()/eval() so that they ONLY switch the LSTM's inter-layer dropout (sst_model.py:25-29);
     # module.training is left alone on purpose.
@@ -63,6 +64,53 @@ class SST(nn.Module):
         arena = getattr(self, '_echr_arena', None)
         sink = EF.GradSink(arena, self.native_params()) if arena is not None else None
         return EF.SSTFunction.apply(features, p, drop, sink, *self.native_params())
+
+    def forward_batch(self, features, row_offset=None):
+        """The encoder over V videos in one call.  `features`: the concatenated [T_tot, video_dim] matrix with `row_offset` [V+1] (video v owns
+        rows row_offset[v] .. row_offset[v+1]), or a list of per-video [T_v, video_dim] matrices (then row_offset is derived).  Returns
+        (tap_feats [T_tot, hidden_dim], scores [T_tot, K]) in the same layout: the rows of a video equal forward() on that video alone (every
+        video starts from the zero state), parameter gradients are the sum over the videos.  One dropout counter per call; the mask is keyed
+        by the batch-global row, so a one-video batch equals forward()."""
+        if isinstance(features, (list, tuple)):
+            if row_offset is not None:
+                raise ValueError('row_offset comes with a concatenated matrix, not with a list of videos')
+            if not features:
+                raise ValueError('a batch needs at least one video')
+            if any((not isinstance(f, torch.Tensor)) or f.dim() != 2 for f in features):
+                raise ValueError('every video must be a [T, video_dim] tensor')
+            row_offset = [0]
+            for f in features:
+                row_offset.append(row_offset[-1] + f.shape[0])
+            ro = EF.sst_row_offsets(row_offset, row_offset[-1])
+            if not all(f.is_cuda for f in features):
+                raise EF.L.EchrHipError('SST runs on the GPU only: move the module and its inputs with .cuda()')
+            features = torch.cat(list(features), 0)
+        else:
+            if row_offset is None:
+                raise ValueError('a concatenated feature matrix needs its row_offset')
+            if features.dim() != 2:
+                raise ValueError('features must be a [T_tot, video_dim] matrix')
+            ro = EF.sst_row_offsets(row_offset, features.shape[0])
+            if not features.is_cuda:
+                raise EF.L.EchrHipError('SST runs on the GPU only: move the module and its inputs with .cuda()')
+        if len(ro) == 2:
+            return self.forward(features)          # one video: today's call (the library's batch entries reduce to it as well)
+        p = float(self.rnn.dropout)
+        if self._drop_seed is None:
+            self._drop_seed = (int(torch.initial_seed()) ^ 0x55AA) & 0xFFFFFFFFFFFFFFFF
+        drop = EF.DropState(self._drop_seed, self._drop_calls, p > 0.0)
+        if p > 0.0:
+            self._drop_calls += 1
+        arena = getattr(self, '_echr_arena', None)
+        sink = EF.GradSink(arena, self.native_params()) if arena is not None else None
+        # device copy of the offsets, kept for the batches a training loop repeats (a pageable host-to-device copy synchronises the stream)
+        key = (ro.tobytes(), str(features.device))
+        ro_dev = self._ro_cache.get(key)
+        if ro_dev is None:
+            if len(self._ro_cache) >= 64:
+                self._ro_cache.clear()
+            ro_dev = self._ro_cache[key] = torch.from_numpy(ro).to(features.device)
+        return EF.SSTBatchFunction.apply(features, ro, ro_dev, p, drop, sink, *self.native_params())
 
     def build_arena(self):
         """Pack parameters and gradients into flat device buffers (echr_amd/arena.py): ClampAdam(..., arena=...) then updates the whole

@@ -11,7 +11,11 @@ and saves checkpoints in the reference's dict layout (:456-461) so that either c
 Both models run natively (echr_amd's SST: echr_sst_fwd/bwd; the caption path: echr_tsrm_* / echr_decoder_*), both optimisers are
 the fused ClampAdam, and `--resume` restores models AND optimiser state (train.py:214-216).
 
-usage: python examples/train_synthetic.py [--iters 20] [--m_batch 2] [--joint] [--save /tmp/echr_ckpt.pth] [--resume /tmp/echr_ckpt.pth]
+`--pre_tap` is stage 1 of the reference's recipe (experiments/train_SST.sh, training_mode 'pre_tap'): the proposal encoder alone, the
+gradients of m_batch videos summed before one clamp + step.  Here the m_batch videos are ONE call: tap_model.forward_batch over the
+concatenated features, utils.tap_criterion_batch (every video its own mean), one backward, one fused step.
+
+usage: python examples/train_synthetic.py [--iters 20] [--m_batch 2] [--joint] [--pre_tap] [--save /tmp/echr_ckpt.pth] [--resume /tmp/echr_ckpt.pth]
 """
 import argparse
 import os
@@ -52,11 +56,35 @@ def save_checkpoint(path, iteration, cg_model, tap_model, cg_opt, tap_opt):
                 'cg_optimizer': cg_opt.state_dict(), 'tap_optimizer': tap_opt.state_dict()}, path)
 
 
+def pre_tap(a, opt, dev, loader, tap_model, cg_model, cg_opt, tap_opt, tap_crit, start):
+    """Stage 1: the SST alone over m_batch videos per call (train.py:281-283,313-317 with the videos of one accumulation as one batch)."""
+    as_dev = lambda vids, k: torch.from_numpy(np.concatenate([v[k] for v in vids], 0)).to(dev)
+    history = []
+    for it in range(start, start + a.iters):
+        vids = [loader[(it * a.m_batch + j) % len(loader)] for j in range(a.m_batch)]
+        set_lr_for_epoch(tap_opt, opt.lr, it * a.m_batch // len(loader))
+        row_offset = np.concatenate([[0], np.cumsum([len(v['c3d']) for v in vids])])
+        tap_opt.zero_grad()
+        _, pred_proposals = tap_model.forward_batch(as_dev(vids, 'c3d'), row_offset)
+        tap_loss, per_video = utils.tap_criterion_batch(tap_crit, pred_proposals, as_dev(vids, 'tap_masks'), as_dev(vids, 'tap_labels'),
+                                                        [torch.from_numpy(v['w1']).to(dev) for v in vids], row_offset)
+        tap_loss.backward()
+        utils.clip_gradient(tap_opt, opt.grad_clip)
+        tap_opt.step()
+        history.append(float(tap_loss.detach()) / a.m_batch)
+        if not a.quiet and (it % 5 == 0 or it == start + a.iters - 1):
+            print('iter %3d  tap_loss %.4f  (mean of %d videos)' % (it, history[-1], a.m_batch), flush=True)
+    if a.save:
+        save_checkpoint(a.save, start + a.iters, cg_model, tap_model, cg_opt, tap_opt)
+    return history, cg_model, tap_model
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--iters', type=int, default=20)
     ap.add_argument('--m_batch', type=int, default=1)
     ap.add_argument('--joint', action='store_true', help="'tap_cg' mode: gradients flow through tap_feats into the SST")
+    ap.add_argument('--pre_tap', action='store_true', help="'pre_tap' mode: train the proposal encoder alone, m_batch videos per forward_batch call")
     ap.add_argument('--events', type=int, default=16)
     ap.add_argument('--segments', type=int, default=32)
     ap.add_argument('--vocab', type=int, default=500)
@@ -98,6 +126,8 @@ def main(argv=None):
         fused = FusedTrainStep(cg_model, cg_opt, grad_clip=opt.grad_clip)
     loader = make_loader(opt, 8, a.events, a.segments, opt.CG_seq_length + 2)
     history = []
+    if a.pre_tap:
+        return pre_tap(a, opt, dev, loader, tap_model, cg_model, cg_opt, tap_opt, tap_crit, start)
     for it in range(start, start + a.iters):
         v = loader[it % len(loader)]
         set_lr_for_epoch(cg_opt, opt.lr, it // len(loader))

@@ -484,6 +484,25 @@ int echr_sst_fwd(const echr_sst_args* a, const echr_dropout* drop, void* stream)
 int echr_sst_fwd_states(const echr_sst_args* a, const echr_dropout* drop, void* stream);
 int echr_sst_head_fwd(const echr_sst_args* a, void* stream);
 int echr_sst_bwd(const echr_sst_args* a, const echr_sst_grads* g, const echr_dropout* drop, void* stream);
+/* The proposal encoder over a multi-video batch (the producer of a batch's tap_feats; stage 1 of the reference's recipe sums the gradients
+ * of m_batch videos, train.py:281-283,313-317).  a->T is T_tot; x, tap_feats, scores and every saved activation use the concatenated
+ * [T_tot, .] layout of the caption path's batches: video v owns rows [row_offset[v], row_offset[v+1]).  Every video starts from the zero
+ * state.  The rows of video v equal what echr_sst_fwd gives for that video alone; parameter gradients are the SUM over the videos.  One
+ * dropout counter per call: the inter-layer mask is keyed by the batch-global element (row_offset[v] + t) * H + u at site 5, so one video
+ * reduces to echr_sst_fwd / echr_sst_bwd exactly.  Products over rows run once over T_tot rows; the recurrences carry a video axis:
+ * the persistent form (H = 512) runs up to echr_sst_batch_group() videos through the register-resident weight slices per launch and
+ * splits a larger batch into ceil(V / group) launches, the launch-per-step wavefront (any H) puts the videos on the grid.  Gradient
+ * buffers, `zeroed` and the deterministic switch behave as in echr_sst_bwd. */
+typedef struct {
+    int32_t n_videos;                   /* V >= 1 */
+    const int32_t* row_offset;          /* device [V+1], row_offset[0] = 0, strictly increasing, row_offset[V] = a->T */
+    const int32_t* row_offset_host;     /* the same values in host memory (the library sizes its loops and groups from them) */
+} echr_sst_batch;
+int64_t echr_sst_batch_ws_floats(int32_t T_tot, int32_t D, int32_t H, int32_t K, int32_t V);
+int64_t echr_sst_batch_ws_bwd_floats(int32_t T_tot, int32_t D, int32_t H, int32_t K, int32_t V);
+int echr_sst_fwd_batch(const echr_sst_args* a, const echr_sst_batch* x, const echr_dropout* drop, void* stream);
+int echr_sst_bwd_batch(const echr_sst_args* a, const echr_sst_batch* x, const echr_sst_grads* g, const echr_dropout* drop, void* stream);
+int echr_sst_batch_group(void);         /* videos one persistent launch carries; a larger V is split by the library */
 /* weighted BCE of the proposal head: loss (device scalar) and its gradient w.r.t. the scores */
 int echr_tap_bce_fwd(const float* scores, const float* masks, const float* labels, const float* w1, float* loss, int32_t T,
                      int32_t K, void* stream);
