@@ -97,18 +97,25 @@ class CaptionGenerator(nn.Module):
             return self.lm_model.sample(video, event, clip, clip_mask, {'beam_size': beam_size, 'return_score': return_score})
         return self.lm_model.sample(video, event, clip, clip_mask)
 
-    def forward_batch(self, batch, mode='train', beam_size=1):
+    def forward_batch(self, batch, mode='train', beam_size=1, event_group_rows=None):
         """`forward` over a multi-video batch (echr_amd.batch.VideoBatch): mode='train' returns the log-probs [N_tot, S, V+1] of all events
         (rows of video v: batch.event_slices[v]; S = the widest video's step count) with the usual autograd edges -- parameters, and
         batch.tap through 'ER2' / 'ER3' and 'VH'; mode='eval' returns the greedy (seq, logp) of all rows.  Rows of video v equal what
         forward() returns for that video alone; apply the criterion with `batch.criterion(crit, logp)` (per-video normalisers, summed).
-        One dropout counter per call, every site keyed by the batch-global element index."""
+        One dropout counter per call, every site keyed by the batch-global element index.
+        `event_group_rows` (mode='eval' only; None = one block-diagonal call over all N_tot events): an integer G runs the event encoder once per
+        run of `batch.event_groups(G)` -- consecutive videos with at most G events together -- so that the pair work and the workspace are bounded
+        by G * N_tot instead of N_tot^2; a run of one video takes the single-video encoder with that video's own inference bounds (the tabulated
+        pair MLP of large inference calls).  The greedy decode stays ONE call over all rows.  The training backward is not grouped."""
         if mode == 'train_rl':
             raise NotImplementedError("mode='train_rl' takes one video per call: self-critical training over a batch is a follow-up")
         if mode not in ('train', 'eval'):
             raise NotImplementedError("mode=%r: batches run 'train' and 'eval'" % (mode,))
         if beam_size != 1:
             raise NotImplementedError('beam search takes one video per call: beam_size > 1 over a batch is a follow-up')
+        if event_group_rows is not None and mode != 'eval':
+            raise ValueError("event_group_rows is taken by mode='eval' only")
+        groups = batch.event_groups(event_group_rows) if event_group_rows is not None else None
         self._check_batch_options()
         self._require_live_decoder()
         if not batch.c3d.is_cuda:
@@ -125,9 +132,12 @@ class CaptionGenerator(nn.Module):
         ech = EF.EventPoolGather.apply(batch.c3d, batch.tap, ev_start, ev_len, ind, parts)
         params = fm.native_params()
         infer = not (torch.is_grad_enabled() and (ech.requires_grad or any(p.requires_grad for p in params)))
-        # (index bounds 0, 0: the tabulated pair MLP of large inference calls is keyed by one video's bounds)
-        event = EF.TSRMBatchFunction.apply(ech, ev_start, ev_len, vid, batch.n_videos, fm.enc_attn.group, drop, fm._grad_sink(),
-                                           (1 if infer else 0, 0, 0, fm.fst_mode()), *params)
+        if groups is not None:
+            event = self._event_context_groups(batch, groups, ech, ev_start, ev_len, vid, drop, params)
+        else:
+            # (index bounds 0, 0: the tabulated pair MLP of large inference calls is keyed by one video's bounds)
+            event = EF.TSRMBatchFunction.apply(ech, ev_start, ev_len, vid, batch.n_videos, fm.enc_attn.group, drop, fm._grad_sink(),
+                                               (1 if infer else 0, 0, 0, fm.fst_mode()), *params)
         disjoint = EF.rows_disjoint(batch.soi)
         if mode == 'eval':
             with torch.no_grad():
@@ -141,6 +151,25 @@ class CaptionGenerator(nn.Module):
         arena = getattr(lm, '_echr_arena_ref', None)
         sink = EF.GradSink(arena, lm.native_params()) if arena is not None else None
         return EF.DecoderBatchFunction.apply(video, event, batch.c3d, ev_start, ev_len, tokens, A, disjoint, drop, sink, vid, *lm.native_params())
+
+    def _event_context_groups(self, batch, groups, ech, ev_start, ev_len, vid, drop, params):
+        """The event encoder of an inference batch, one call per run of videos (VideoBatch.event_groups), into one [N_tot, d_o] matrix.  The
+        kernels compare `vid` for equality only and the pair geometry reads differences of the intervals, so a run is the plain row slice of
+        the batch's tensors (its first vid need not be 0, its rows stay batch-absolute)."""
+        fm = self.fusion_model
+        lens = batch.soi[:, 1] - batch.soi[:, 0]
+        c2 = 2 * batch.soi[:, 0] + lens
+        with torch.no_grad():
+            event = torch.empty(batch.n_events, fm.output_dim, device=batch.device, dtype=torch.float32)
+            for v0, v1, e0, e1 in groups:
+                s = slice(e0, e1)
+                if v1 - v0 == 1:
+                    bounds = (1, int(lens[s].max()), int(c2[s].max() - c2[s].min()), fm.fst_mode())
+                    event[s] = EF.TSRMFunction.apply(ech[s], ev_start[s], ev_len[s], fm.enc_attn.group, drop, None, bounds, *params)
+                else:
+                    event[s] = EF.TSRMBatchFunction.apply(ech[s], ev_start[s], ev_len[s], vid[s], v1 - v0, fm.enc_attn.group, drop, None,
+                                                          (1, 0, 0, fm.fst_mode()), *params)
+        return event
 
     def _check_batch_options(self):
         """What the batched entry points do not cover yet (follow-ups): an initial state from the contexts, 'CH' rows."""

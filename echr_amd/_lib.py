@@ -198,6 +198,8 @@ SYMBOLS = [
     ('echr_h2_pack', i32, [c_f, i32, i32, i64, i64, C.c_void_p, C.c_void_p]),
     ('echr_top_proposals', i32, [c_f, c_f, i32, i32, i32, f32, c_f, c_f, c_f, c_f, C.c_void_p]),
     ('echr_top_proposals_nms', i32, [c_f, i32, i32, i32, C.c_double, c_f, c_f, c_f, c_f, C.c_void_p]),
+    ('echr_top_proposals_batch', i32, [c_f, c_f, c_f, i32, i32, i32, i32, f32, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, C.c_void_p]),
+    ('echr_top_proposals_nms_batch', i32, [c_f, c_f, i32, i32, i32, i32, C.c_double, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, C.c_void_p]),
     ('echr_train_step_ws_floats', i64, [C.POINTER(TrainStepArgs)]),
     ('echr_train_step', i32, [C.POINTER(TrainStepArgs), C.c_void_p]),
     ('echr_train_step_prepare', i32, [C.POINTER(TrainStepArgs), C.c_void_p]),

@@ -189,6 +189,24 @@ class VideoBatch(object):
             raise ValueError('split() takes a result with one row per event (%d), got %d' % (self.n_events, len(x)))
         return [x[s] for s in self.event_slices]
 
+    def event_groups(self, G):
+        """Cut the video axis into runs of consecutive videos whose events number at most `G` together: a list of (v0, v1, e0, e1) -- videos
+        [v0, v1), events [e0, e1) -- in order, every video in exactly one run.  A video with more than G events is a run of its own.  The
+        inference pass runs the event encoder once per run (CaptionGenerator.forward_batch(event_group_rows=G)), so its pair work and
+        workspace are bounded by G * N_tot instead of N_tot^2."""
+        G = int(G)
+        if G < 1:
+            raise ValueError('event_group_rows must be a positive number of events (got %r)' % (G,))
+        eo, V = self.event_offset, self.n_videos
+        runs, v0 = [], 0
+        while v0 < V:
+            v1 = v0 + 1
+            while v1 < V and eo[v1 + 1] - eo[v0] <= G:
+                v1 += 1
+            runs.append((v0, v1, int(eo[v0]), int(eo[v1])))
+            v0 = v1
+        return runs
+
     def video(self, v):
         """Video v as the dict of a single-video call (local indices, its own label width and step count)."""
         s, r0, r1 = self.event_slices[v], int(self.row_offset[v]), int(self.row_offset[v + 1])

@@ -4,6 +4,9 @@
 ordered enumeration in one HIP kernel (echr_top_proposals) instead of a numpy sort + an O(T*K) python double loop; the
 device tensors it produced are also returned by `top_proposals_device` so the caption path can consume them without a
 round trip through python lists.
+
+`caption_videos` is the same flow over V videos in one pass: one batched SST call, one batched selection launch
+(echr_top_proposals_batch / _nms_batch, a workgroup per video), one caption pass over a VideoBatch.
 """
 import ctypes as C
 
@@ -11,7 +14,11 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import functional as EF
+from .batch import VideoBatch
 from .misc import utils
+
+EVENT_GROUP_ROWS = 128          # caption_videos' default event_group_rows: a tuning constant, not a correctness condition
 
 
 def top_proposals_device(pred_proposals, tap_masks, topN=1000, val_score_thres=0.0):
@@ -121,6 +128,184 @@ def caption_video(tap_model, cg_model, c3d_feats, lda_feats, duration, featstamp
         vid_info.append({'sentence': sent, 'timestamp': good_time_stamps[i], 'sentence_confidence': cg_score[i],
                          'proposal_score': float(tap_prob[i]), 're_score': 10 * float(tap_prob[i]) + cg_score[i], 'num': [i, len(sents)]})
     return vid_info, extras
+
+
+def top_proposals_batch_device(pred_proposals, row_offset, tap_masks=None, topN=1000, val_score_thres=0.0, nms_threshold=0.0):
+    """Proposal selection of V videos in one call, no host synchronisation: `pred_proposals` [T_tot, K] is SST.forward_batch's score matrix,
+    `row_offset` [V+1] (host integers) its video boundaries, `tap_masks` [T_tot, K] or None for the causal mask n_local >= k (threshold
+    mode only; the NMS ignores masks, as the reference does).  nms_threshold != 0 selects by greedy NMS, else by score threshold.
+    Returns a dict of device tensors: count int32 [V+2] (picks per video, their total, the largest interval length), event_offset int32
+    [V+1], and -- allocated for the worst case, valid in their first count[V] entries -- vid, ind, ind_abs int32 [cap], feat, feat_abs
+    int32 [cap, 2], conf fp32 [cap]; `row_offset` is the int32 device copy."""
+    lib = L.load()
+    if not isinstance(pred_proposals, torch.Tensor) or not pred_proposals.is_cuda:
+        raise L.EchrHipError('top_proposals_batch_device runs on the GPU: pass the SST scores as a CUDA tensor')
+    scores = pred_proposals.detach().to(torch.float32).contiguous()
+    dev = scores.device
+    T_tot, K = scores.shape
+    ro = EF.sst_row_offsets(row_offset, T_tot)
+    V = len(ro) - 1
+    ro_dev = EF.upload(torch.from_numpy(ro), dev)
+    i32 = dict(device=dev, dtype=torch.int32)
+    nms = nms_threshold != 0
+    topN = int(topN)
+    if nms:
+        topN = max(1, min(topN, int(np.diff(ro).max()) * K))          # a video has at most T_v*K candidates: the picks are the same
+    cap = V * topN if nms else T_tot * K
+    out = dict(count=torch.empty(V + 2, **i32), event_offset=torch.empty(V + 1, **i32), vid=torch.empty(cap, **i32), ind=torch.empty(cap, **i32),
+               feat=torch.empty(cap, 2, **i32), ind_abs=torch.empty(cap, **i32), feat_abs=torch.empty(cap, 2, **i32),
+               conf=torch.empty(cap, device=dev, dtype=torch.float32), row_offset=ro_dev)
+    tail = [L.ptr(out[k], torch.int32) for k in ('count', 'event_offset', 'vid', 'ind', 'feat', 'ind_abs', 'feat_abs')] + [L.ptr(out['conf']), L.stream_ptr()]
+    if nms:
+        live = torch.empty(T_tot * K, device=dev, dtype=torch.float32)
+        L.check(lib.echr_top_proposals_nms_batch(L.ptr(scores), L.ptr(ro_dev, torch.int32), T_tot, V, K, topN, float(nms_threshold), L.ptr(live),
+                                                 *tail), 'top_proposals_nms_batch')
+    else:
+        masks = None
+        if tap_masks is not None:
+            masks = torch.as_tensor(np.asarray(tap_masks) if not isinstance(tap_masks, torch.Tensor) else tap_masks).to(dev, torch.float32).contiguous()
+            if tuple(masks.shape) != (T_tot, K):
+                raise ValueError('tap_masks must be [%d, %d] like the scores (got %s)' % (T_tot, K, tuple(masks.shape)))
+        L.check(lib.echr_top_proposals_batch(L.ptr(scores), L.ptr(masks), L.ptr(ro_dev, torch.int32), T_tot, V, K, topN, float(val_score_thres),
+                                             *tail), 'top_proposals_batch')
+    return out
+
+
+def _to_dev(x, dev):
+    t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))
+    return t.to(device=dev, dtype=torch.float32)
+
+
+def caption_videos(tap_model, cg_model, videos, featstamp_to_time, vocab=None, topN=1000, nms_threshold=0.0, val_score_thres=0.0,
+                   flag_eval_what='tap_cg', event_group_rows=EVENT_GROUP_ROWS):
+    """`caption_video` over V videos in ONE evaluation pass: SST.forward_batch over the concatenated features -> batched proposal selection
+    (a workgroup per video; greedy NMS when nms_threshold != 0, else score threshold) -> one greedy caption pass over a VideoBatch
+    (forward_batch(mode='eval', event_group_rows=...)).  Runs under no_grad with both models switched to eval mode for the call.
+
+    `videos`: a list of dicts with 'c3d' [T_v, D] (CUDA tensor), 'lda', 'duration' and optionally 'tap_masks' [T_v, K] (all videos or none)
+    and 'cg_gts'.  flag_eval_what='cg' captions given events instead of selected ones: every video then carries 'ind', 'soi' and
+    'timestamps' (the reference's gts_ind_select_list / gts_soi_select_list / gt_timestamps; proposal_score is 1).  'tap' skips the
+    caption pass (sentence 0).
+
+    Returns (vid_infos, extras).  vid_infos[v] is the list caption_video returns for video v alone (sentence, timestamp,
+    sentence_confidence, proposal_score, re_score, num); a video without a pick, or whose rows all emit <eos> first, gets [].  The batched
+    decode stops when nobody in the BATCH is unfinished, so every video's sequences and log-probs are cut to the width that video alone
+    would have produced before the confidence is summed.  extras: 'batch' (the VideoBatch of the videos that have events, 'kept' their
+    indices), 'pred_proposals', 'tap_feats', 'row_offset', 'selection' (the device tensors of top_proposals_batch_device), 'seq' /
+    'cg_prob' of the batch and 'per_video' (ind_select_list, soi_select_list, cg_select_list, seq, cg_prob of each video).
+
+    Host reads per call, whatever V is: the selection counts, the selected lists (one packed copy), the decoder's step counts, and the
+    sequences / log-probs of the batch.  Beam search is not batched: use caption_video(beam_size=...) per video.
+
+    The validation loss of the same batch (eval_split's get_eval_loss), with labels stacked into the batch:
+        logp = cg_model.forward_batch(extras['batch'], mode='train')
+        cg_loss, _ = extras['batch'].criterion(cg_crit, logp)
+        tap_loss, _ = utils.tap_criterion_batch(tap_crit, extras['pred_proposals'], tap_masks, tap_labels, w1, extras['row_offset'])"""
+    if flag_eval_what not in ('tap_cg', 'tap', 'cg'):
+        raise ValueError("flag_eval_what=%r: caption_videos runs 'tap_cg', 'tap' and 'cg'" % (flag_eval_what,))
+    videos = list(videos)
+    if not videos:
+        raise ValueError('a batch needs at least one video')
+    if any(not (isinstance(v['c3d'], torch.Tensor) and v['c3d'].is_cuda) for v in videos):
+        raise L.EchrHipError('caption_videos runs on the GPU: move the models and features with .cuda()')
+    if flag_eval_what == 'cg':
+        for i, v in enumerate(videos):
+            missing = [k for k in ('ind', 'soi', 'timestamps') if k not in v]
+            if missing or not (len(v['ind']) == len(v['soi']) == len(v['timestamps'])):
+                raise ValueError("video %d: flag_eval_what='cg' takes the given events as 'ind', 'soi' and 'timestamps' of one length" % i)
+    V, dev = len(videos), videos[0]['c3d'].device
+    rows = np.concatenate([[0], np.cumsum([int(v['c3d'].shape[0]) for v in videos])]).astype(np.int64)
+    sst_dropout, cg_training = tap_model.rnn.dropout, cg_model.training
+    tap_model.eval()
+    cg_model.eval()
+    try:
+        with torch.no_grad():
+            return _caption_videos(tap_model, cg_model, videos, featstamp_to_time, vocab, topN, nms_threshold, val_score_thres, flag_eval_what,
+                                   event_group_rows, V, dev, rows)
+    finally:
+        tap_model.rnn.dropout = sst_dropout
+        cg_model.train(cg_training)
+
+
+def _caption_videos(tap_model, cg_model, videos, featstamp_to_time, vocab, topN, nms_threshold, val_score_thres, flag_eval_what, event_group_rows,
+                    V, dev, rows):
+    c3d_all = torch.cat([_to_dev(v['c3d'], dev) for v in videos], 0)
+    lda_all = torch.stack([_to_dev(v['lda'], dev).reshape(-1) for v in videos], 0)
+    tap_all, scores = tap_model.forward_batch(c3d_all, rows)
+    extras = dict(tap_feats=tap_all, pred_proposals=scores, row_offset=rows, selection=None, batch=None, kept=[], seq=None, cg_prob=None)
+    # ---- events per video: (soi [N_v,2] local, tap_prob [N_v], timestamps) ----
+    if flag_eval_what == 'cg':
+        sois = [np.asarray(v['soi'], dtype=np.int64).reshape(-1, 2) for v in videos]
+        inds = [np.asarray(v['ind'], dtype=np.int64).reshape(-1) for v in videos]
+        probs = [[1] * len(s) for s in sois]
+        stamps = [list(v['timestamps']) for v in videos]
+    else:
+        masks = [v.get('tap_masks') for v in videos]
+        if any(m is not None for m in masks) and not all(m is not None for m in masks):
+            raise ValueError('either every video carries tap_masks or none does')
+        tap_masks = None
+        if masks[0] is not None and nms_threshold == 0:
+            tap_masks = torch.cat([_to_dev(m, dev) for m in masks], 0)
+        sel = extras['selection'] = top_proposals_batch_device(scores, rows, tap_masks, topN, val_score_thres, nms_threshold)
+        cnt = sel['count'].cpu().numpy()                                   # host read 1: the counts
+        n_tot = int(cnt[V])
+        eo = np.concatenate([[0], np.cumsum(cnt[:V])]).astype(np.int64)
+        # host read 2: the lists (intervals and scores; anchors, vid and the absolute indices follow from them), as one packed copy
+        packed = torch.cat([sel['feat'][:n_tot].reshape(-1), sel['conf'][:n_tot].view(torch.int32)]).cpu().numpy()
+        feat, conf = packed[:2 * n_tot].reshape(-1, 2).astype(np.int64), packed[2 * n_tot:].view(np.float32)
+        sois = [feat[eo[v]:eo[v + 1]] for v in range(V)]
+        inds = [s[:, 1] - 1 for s in sois]
+        if nms_threshold != 0:
+            probs = [conf[eo[v]:eo[v + 1]].astype(np.float64) for v in range(V)]
+        else:
+            probs = [conf[eo[v]:eo[v + 1]].tolist() for v in range(V)]
+        stamps = [[featstamp_to_time(int(s), int(e), int(rows[v + 1] - rows[v]), videos[v]['duration']) for s, e in sois[v]] for v in range(V)]
+    per_video = []
+    for v in range(V):
+        gts = videos[v].get('cg_gts', ())
+        cg_sel = [gts[n, n - s] for n, (s, _) in zip(inds[v].tolist(), sois[v].tolist())] if len(gts) else []
+        per_video.append(dict(ind_select_list=inds[v].tolist(), soi_select_list=sois[v].tolist(), cg_select_list=cg_sel, seq=None, cg_prob=None))
+    extras['per_video'] = per_video
+    vid_infos = [[] for _ in range(V)]
+    kept = extras['kept'] = [v for v in range(V) if len(sois[v])]
+    if not kept:
+        return vid_infos, extras
+    # ---- the batch of the videos that have events (VideoBatch.validate refuses a video without one) ----
+    if len(kept) == V:
+        c3d_b, tap_b, lda_b, rows_b = c3d_all, tap_all, lda_all, rows
+    else:                                                                  # rare: re-gather the kept videos' rows
+        c3d_b = torch.cat([c3d_all[rows[v]:rows[v + 1]] for v in kept], 0)
+        tap_b = torch.cat([tap_all[rows[v]:rows[v + 1]] for v in kept], 0)
+        lda_b = lda_all[torch.as_tensor(kept, device=dev)]
+        rows_b = np.concatenate([[0], np.cumsum([rows[v + 1] - rows[v] for v in kept])]).astype(np.int64)
+    eo_b = np.concatenate([[0], np.cumsum([len(sois[v]) for v in kept])]).astype(np.int64)
+    batch = extras['batch'] = VideoBatch(c3d_b, tap_b, lda_b, rows_b, eo_b, np.concatenate([sois[v] + rows_b[i] for i, v in enumerate(kept)], 0),
+                                         np.concatenate([inds[v] + rows_b[i] for i, v in enumerate(kept)], 0))
+    if flag_eval_what == 'tap':
+        for v in kept:
+            n = len(sois[v])
+            vid_infos[v] = _records([0] * n, stamps[v], [0] * n, probs[v])
+        return vid_infos, extras
+    seq, cg_prob = cg_model.forward_batch(batch, mode='eval', event_group_rows=event_group_rows)
+    if len(seq) == 0:
+        return vid_infos, extras
+    extras['seq'], extras['cg_prob'] = seq, cg_prob
+    seq_h, lp_h = seq.cpu().numpy(), cg_prob.cpu()
+    for i, v in enumerate(kept):
+        s = batch.event_slices[i]
+        width = int((seq_h[s] > 0).any(0).sum())          # the steps video v alone would have run (OldModel_NEW.py:176-181): nonzero columns form a prefix
+        if width == 0:
+            continue
+        per_video[v]['seq'], per_video[v]['cg_prob'] = seq[s, :width], cg_prob[s, :width]
+        cg_score = lp_h[s, :width].contiguous().sum(1).numpy().astype('float')
+        sents = utils.decode_sequence(vocab, seq[s, :width]) if vocab is not None else [row[row > 0].tolist() for row in seq_h[s, :width]]
+        vid_infos[v] = _records(sents, stamps[v], cg_score, probs[v])
+    return vid_infos, extras
+
+
+def _records(sents, stamps, cg_score, tap_prob):
+    return [{'sentence': sent, 'timestamp': stamps[i], 'sentence_confidence': cg_score[i], 'proposal_score': float(tap_prob[i]),
+             're_score': 10 * float(tap_prob[i]) + cg_score[i], 'num': [i, len(sents)]} for i, sent in enumerate(sents)]
 
 
 def gettopN_nms(props, prop_scores, sent_score, nms_overlap=0.999, topN=1000):

@@ -527,6 +527,23 @@ int echr_top_proposals(const float* scores, const float* mask, int32_t T, int32_
 int echr_top_proposals_nms(const float* scores, int32_t T, int32_t K, int32_t topN, double overlap, float* scratch,
                            int32_t* out_feat, float* out_conf, int32_t* out_count, void* stream);
 
+/* Both selections over the V videos of a batch in ONE call: scores [T_tot, K] is the concatenated output of echr_sst_fwd_batch,
+ * row_offset int32 [V+1] (device) names video v's rows, workgroup v runs the single-video algorithm over them with n and k local to the
+ * video; a second one-workgroup launch scans the counts and closes the gaps between the videos' lists.  No host synchronisation.
+ *   mask [T_tot, K] or NULL (threshold entry): NULL = the causal mask n_local >= k.
+ *   count int32 [V+2]: picks per video, their total, the largest interval length max(e - s) over all picks (0 without a pick).
+ *   event_offset int32 [V+1]: exclusive scan of the counts.   vid int32 [N_tot]: video of every pick.
+ *   ind [N_tot], feat [N_tot,2]: video-local anchors / intervals, videos in order, inside a video the single-video order;
+ *   ind_abs, feat_abs: the same + row_offset[vid] (rows of the concatenated matrices);   conf [N_tot].
+ * Capacity of vid / ind / feat / ind_abs / feat_abs / conf in entries: T_tot*K (threshold: ties can exceed topN), V*topN (NMS).
+ * live (NMS): T_tot*K floats of scratch.  A video whose offsets are not 0 <= row_offset[v] < row_offset[v+1] <= T_tot selects nothing. */
+int echr_top_proposals_batch(const float* scores, const float* mask, const int32_t* row_offset, int32_t T_tot, int32_t V, int32_t K,
+                             int32_t topN, float val_thres, int32_t* count, int32_t* event_offset, int32_t* vid, int32_t* ind,
+                             int32_t* feat, int32_t* ind_abs, int32_t* feat_abs, float* conf, void* stream);
+int echr_top_proposals_nms_batch(const float* scores, const int32_t* row_offset, int32_t T_tot, int32_t V, int32_t K, int32_t topN,
+                                 double overlap, float* live, int32_t* count, int32_t* event_offset, int32_t* vid, int32_t* ind,
+                                 int32_t* feat, int32_t* ind_abs, int32_t* feat_abs, float* conf, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Fused element-wise clamp(+-clip) + Adam (betas, eps, no weight decay, no amsgrad) over a flat
  * buffer.  Replaces misc/utils.py:107-111 + torch.optim.Adam.step as wired at train.py:209,315-317.
