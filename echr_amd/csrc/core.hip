@@ -35,7 +35,7 @@ static int env_int(const char* name, int dflt) { const char* e = getenv(name); r
 Config& config() {
     static Config c = {env_int("ECHR_GEMM_BF16X3", 1), env_int("ECHR_ATT_SLOTS", 2),
                        env_int("ECHR_GEMM_H2", 1), env_int("ECHR_PERSIST", 1), env_int("ECHR_PERSIST_STAMPS", 0),
-                       getenv("ECHR_GEMM_TILE") ? (int)getenv("ECHR_GEMM_TILE")[0] : 0, env_int("ECHR_GEMM_SPLIT", 0), env_int("ECHR_PERSIST_BWD", 1), env_int("ECHR_PERSIST_SPLIT", 1), env_int("ECHR_PERSIST_H2", 1), env_int("ECHR_PERSIST_MERGE", 1), env_int("ECHR_PERSIST_KGROUPS", 1),
+                       getenv("ECHR_GEMM_TILE") ? (int)getenv("ECHR_GEMM_TILE")[0] : 0, env_int("ECHR_GEMM_SPLIT", 0), env_int("ECHR_PERSIST_BWD", 1), env_int("ECHR_PERSIST_H2", 1),
                        env_int("ECHR_PERSIST_COOP", 0), 0, env_int("ECHR_PERSIST_SPIN_LIMIT", 0), env_int("ECHR_SST_PERSIST", 1), 0, env_int("ECHR_PERSIST_SAMPLE", 1), env_int("ECHR_POSEMB_ROWS", 1), env_int("ECHR_GEMM_SKINNY", 1), env_int("ECHR_POSEMB_PACKED", 1), env_int("ECHR_PAIR_TABLES", 1), 0, env_int("ECHR_PERSIST_SAMPLE_MAX", 512), env_int("ECHR_DETERMINISTIC", 0)};
     return c;
 }
@@ -1430,10 +1430,7 @@ extern "C" int echr_config_set(const char* key, int32_t value) {
     else if (!strcmp(key, "persist")) c.persist = value;
     else if (!strcmp(key, "persist_stamps")) c.persist_stamps = value;
     else if (!strcmp(key, "persist_bwd")) c.persist_bwd = value;
-    else if (!strcmp(key, "persist_split")) c.persist_split = value;
     else if (!strcmp(key, "persist_h2")) c.persist_h2 = value;
-    else if (!strcmp(key, "persist_merge")) c.persist_merge = value;
-    else if (!strcmp(key, "persist_kgroups")) c.persist_kgroups = value;
     else if (!strcmp(key, "persist_coop")) c.persist_coop = value;
     else if (!strcmp(key, "sst_persist")) c.sst_persist = value;
     else if (!strcmp(key, "diag_skip")) c.diag_skip = value;

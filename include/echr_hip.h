@@ -764,16 +764,14 @@ int echr_prof_event_overhead(double* ms, int64_t* n);
  *   "gemm_h2"     0/1  run the decoder's large projections on h2-packed operands (two block-scaled fp16 planes, fp32-grade) or not
  *   "gemm_bf16x3" 0/1  (gemm_h2 = 0) use the three-plane bf16 split product for the large projections or the native fp32 MFMA
  *   "att_slots"   2/4/8 attention slots per wave
- *   "persist"     0/1  (default 1, ECHR_PERSIST) run the teacher-forced recurrence as a pair of persistent launches (csrc/persist.hip)
- *                      when the shape allows (N <= 64, A <= 129, H = Ha = 512, D <= 512, a full 256-CU device), else one launch per phase
+ *   "persist"     0/1  (default 1, ECHR_PERSIST) run the teacher-forced recurrence as ONE persistent launch of 256 workgroups (csrc/persist.hip:
+ *                      the attention chain as two half-chip machines of 32 event rows + the two plain LSTM streams) when the shape allows
+ *                      (N <= 64, A <= 258, H = Ha = 512, D <= 512, a full 256-CU device), else one launch per phase
  *   "persist_bwd" 0/1  (default 1, ECHR_PERSIST_BWD) the same for the reverse recurrence of echr_decoder_bwd (independent of "persist")
- *   "persist_split" 0/1 (default 1, ECHR_PERSIST_SPLIT) attention chain as two half-chip machines of 32 event rows (0: one machine of 64)
  *   "persist_h2"  0/1  (default 1, ECHR_PERSIST_H2) fp16-pair (fp32-grade) MFMA products in the forward persistent kernels (0: exact
  *                      fp32 MFMAs); the reverse kernels always use fp32 MFMAs
- *   "persist_merge" 0/1 (default 1, ECHR_PERSIST_MERGE) each direction's pair (attention chain + the two plain LSTM streams) as ONE launch
- *                      of 256 workgroups on the caller's stream (0: two concurrent launches on two streams; needs two free hardware queues)
- *   "persist_kgroups" 0/1 (default 1, ECHR_PERSIST_KGROUPS) reverse LSTM role with the contraction split over 4 workgroup groups (128 KB of
- *                      ingest per workgroup and step plus a small partial-tile exchange) instead of 512 KB per workgroup
+ *   (the switches that selected the one-machine attention chain, the two-launch pairs and the wide reverse LSTM role are retired: only
+ *                      their default forms remain, and their keys return -22 like any unknown key)
  *   "persist_coop" 0/1  (default 0, ECHR_PERSIST_COOP) launch the persistent pairs with hipLaunchCooperativeKernel: the dispatch starts only
  *                      when all 256 workgroups can be co-resident, whatever else holds CUs (RCCL kernels of a data-parallel run, another
  *                      process on the device).  echr_amd.parallel / bench.py switch it on when the world size is > 1

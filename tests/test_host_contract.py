@@ -232,7 +232,8 @@ def test_runtime_switches_are_known_by_name():
     echr_amd.set_deterministic(False)
     assert lib.echr_config_set(b'no_such_switch', 1) == -22
     assert b'no_such_switch' in lib.echr_last_error()
-    for key in (b'overlap', b'chains2', b'tail_early', b'embed_fused', b'tsrm_fork'):          # retired: only their default path remains
+    for key in (b'overlap', b'chains2', b'tail_early', b'embed_fused', b'tsrm_fork',
+                b'persist_split', b'persist_merge', b'persist_kgroups'):          # retired: only their default path remains
         assert lib.echr_config_set(key, 1) == -22, key
     assert lib.echr_config_set(b'att_slots', 3) != 0          # (only 2, 4 or 8)
 
