@@ -194,6 +194,8 @@ SYMBOLS = [
     ('echr_tap_bce_fwd', i32, [c_f, c_f, c_f, c_f, c_f, i32, i32, C.c_void_p]),
     ('echr_tap_bce_fwd_ws', i32, [c_f, c_f, c_f, c_f, c_f, c_f, i32, i32, C.c_void_p]),
     ('echr_tap_bce_bwd', i32, [c_f, c_f, c_f, c_f, c_f, c_f, i32, i32, C.c_void_p]),
+    ('echr_tap_bce_fwd_batch', i32, [c_f, c_f, c_f, c_f, i32, c_f, i32, i32, c_f, c_f, c_f, C.c_void_p]),
+    ('echr_tap_bce_bwd_batch', i32, [c_f, c_f, c_f, c_f, i32, c_f, i32, i32, i32, c_f, c_f, C.c_void_p]),
     ('echr_h2_bytes', i64, [i32, i32]),
     ('echr_h2_pack', i32, [c_f, i32, i32, i64, i64, C.c_void_p, C.c_void_p]),
     ('echr_top_proposals', i32, [c_f, c_f, i32, i32, i32, f32, c_f, c_f, c_f, c_f, C.c_void_p]),
@@ -217,6 +219,8 @@ SYMBOLS = [
     ('echr_decoder_sample_batch', i32, [C.POINTER(SampleArgs), C.POINTER(BatchExt), C.c_void_p]),
     ('echr_train_step_batch_ws_floats', i64, [C.POINTER(TrainStepArgs), C.POINTER(BatchExt)]),
     ('echr_train_step_batch', i32, [C.POINTER(TrainStepArgs), C.POINTER(BatchExt), c_f, c_f, C.c_void_p]),
+    ('echr_train_step_batch_tap_ws_floats', i64, [C.POINTER(TrainStepArgs), C.POINTER(BatchExt)]),
+    ('echr_train_step_batch_tap', i32, [C.POINTER(TrainStepArgs), C.POINTER(BatchExt), c_f, c_f, c_f, C.c_void_p]),
     ('echr_handover_wait', i32, [i32, C.c_void_p]),
     ('echr_clamp', i32, [c_f, i64, f32, C.c_void_p]),
     ('echr_clamp_adam', i32, [c_f, c_f, c_f, c_f, i64, i32, C.c_double, C.c_double, C.c_double, C.c_double, f32, C.c_void_p]),

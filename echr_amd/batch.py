@@ -59,21 +59,26 @@ class VideoBatch(object):
 
     # ---- construction -------------------------------------------------------------------------------------------------------
     @classmethod
-    def from_videos(cls, videos, device=None, tap_model=None):
+    def from_videos(cls, videos, device=None, tap_model=None, tap_fn=None):
         """`videos`: a list of dicts with the arguments of a single-video call -- 'c3d' [T, D], 'tap' [T', Ht], 'lda' [lda_dim], 'ind' [N_v],
         'soi' [N_v, 2] (indices local to the video) and, for training, 'labels' / 'masks' [N_v, L_v] -- or a dict of parallel lists under
         the same keys.  Features may be numpy arrays or tensors on any device; they are concatenated on `device` (default: the device of
         the first video's c3d when it is a tensor, else the CPU).
         With `tap_model` (a models.SST on the GPU) the videos need no 'tap': `tap` is the encoder's forward_batch over the concatenated c3d --
-        ONE call for the V videos -- and keeps its autograd graph into the encoder; a 'tap' entry is then ignored."""
+        ONE call for the V videos -- and keeps its autograd graph into the encoder; a 'tap' entry is then ignored.
+        `tap_fn(c3d_all, rows)` (instead of tap_model): any other producer of the [T_tot, Ht] matrix from the concatenated c3d and the row
+        offsets (fused.JointBatchStep runs the encoder into its own buffers, without a graph)."""
         if isinstance(videos, dict):
             n = len(videos['c3d'])
             videos = [{k: v[i] for k, v in videos.items()} for i in range(n)]
         videos = list(videos)
+        if tap_fn is not None and tap_model is not None:
+            raise ValueError('tap_model and tap_fn exclude each other')
+        no_tap = tap_model is not None or tap_fn is not None
         if not videos:
             raise ValueError('a batch needs at least one video')
         for i, v in enumerate(videos):
-            missing = [k for k in _KEYS if k not in v and not (k == 'tap' and tap_model is not None)]
+            missing = [k for k in _KEYS if k not in v and not (k == 'tap' and no_tap)]
             if missing:
                 raise ValueError('video %d lacks %s' % (i, missing))
         if device is None and tap_model is not None:
@@ -89,7 +94,7 @@ class VideoBatch(object):
             raise ValueError('either every video carries labels / masks or none does')
         for i, v in enumerate(videos):
             c3d = as_t(v['c3d'])
-            tap = c3d if tap_model is not None else as_t(v['tap'])
+            tap = c3d if no_tap else as_t(v['tap'])
             if c3d.dim() != 2 or tap.dim() != 2:
                 raise ValueError('video %d: c3d / tap must be [T, D] matrices' % i)
             T = min(c3d.shape[0], tap.shape[0])
@@ -104,7 +109,7 @@ class VideoBatch(object):
             if soi.min() < 0 or soi[:, 1].max() > T or ind.min() < 0 or ind.max() >= T:
                 raise ValueError('video %d: event intervals / anchors fall outside its %d feature rows' % (i, T))
             c3ds.append(c3d[:T].to(device=device, dtype=torch.float32))
-            if tap_model is None:
+            if not no_tap:
                 taps.append(tap[:T].to(device=device, dtype=torch.float32))
             ldas.append(as_t(v['lda']).reshape(-1).to(device=device, dtype=torch.float32))
             sois.append(soi + rows[-1])
@@ -117,7 +122,10 @@ class VideoBatch(object):
         if all(with_labels):
             labels, masks = cls._stack_labels(videos, counts)
         c3d_all = torch.cat(c3ds, 0)
-        tap_all = torch.cat(taps, 0) if tap_model is None else tap_model.forward_batch(c3d_all, rows)[0]
+        if tap_fn is not None:
+            tap_all = tap_fn(c3d_all, rows)
+        else:
+            tap_all = torch.cat(taps, 0) if tap_model is None else tap_model.forward_batch(c3d_all, rows)[0]
         return cls(c3d_all, tap_all, torch.stack(ldas, 0), rows, counts, np.concatenate(sois, 0), np.concatenate(inds, 0),
                    labels, masks)
 

@@ -317,12 +317,11 @@ __global__ __launch_bounds__(1024) void tap_bce_fwd_kernel(const float* __restri
 // the same sum in two launches (64 workgroups of partial sums in one fixed order each, then one wave adds the 64 partials in index order):
 // bit-reproducible like the single-workgroup form, 6x faster at T x K = 256 x 256
 constexpr int BCE_PARTS = 64;
-__global__ __launch_bounds__(256) void tap_bce_part_kernel(const float* __restrict__ scores, const float* __restrict__ masks,
-                                                           const float* __restrict__ labels, const float* __restrict__ w1,
-                                                           float* __restrict__ part, int T, int K) {
-    __shared__ float red[4];
-    const long n = (long)T * K;
-    const long per = (n + BCE_PARTS - 1) / BCE_PARTS, i0 = per * blockIdx.x, i1 = min(n, i0 + per);
+// partial sum `part` of BCE_PARTS over the n = T*K elements of ONE video (the caller's pointers start at the video's first row); the value
+// is valid in thread 0.  Shared by the single-video and the batched kernel: the same ranges, the same order, the same bits
+__device__ __forceinline__ float tap_bce_part_sum(const float* __restrict__ scores, const float* __restrict__ masks, const float* __restrict__ labels,
+                                                  const float* __restrict__ w1, long n, int K, int part, float* red) {
+    const long per = (n + BCE_PARTS - 1) / BCE_PARTS, i0 = per * part, i1 = min(n, i0 + per);
     float s4[4] = {0.f, 0.f, 0.f, 0.f};
     for (long b = i0 + threadIdx.x; b < i1; b += 1024) {
 #pragma unroll
@@ -339,27 +338,77 @@ __global__ __launch_bounds__(256) void tap_bce_part_kernel(const float* __restri
     const float s = wave_sum((s4[0] + s4[1]) + (s4[2] + s4[3]));
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
     __syncthreads();
-    if (threadIdx.x == 0) part[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+    return (red[0] + red[1]) + (red[2] + red[3]);
+}
+__device__ __forceinline__ float tap_bce_mean(const float* __restrict__ part, long n, int K) {
+    float t = 0.f;
+    for (int i = 0; i < BCE_PARTS; ++i) t += part[i];
+    return t / (float)n * (float)K;
+}
+// d loss / d scores of one element: g * w * d * m / T  (K / (T*K))
+__device__ __forceinline__ float tap_bce_grad(float sc, float m, float lb, float w1k, float g, float T) {
+    const float y = lb * m, p = sc * m;
+    const float w = y * (1.f - w1k) + (1.f - y) * w1k;
+    // d/dp of -(y log p + (1-y) log(1-p)) with torch's clamp: the clamped branch has zero slope
+    float d = 0.f;
+    if (logf(p) > -100.f) d -= y / p;
+    if (logf(1.f - p) > -100.f) d += (1.f - y) / (1.f - p);
+    return g * w * d * m / T;
+}
+__global__ __launch_bounds__(256) void tap_bce_part_kernel(const float* __restrict__ scores, const float* __restrict__ masks,
+                                                           const float* __restrict__ labels, const float* __restrict__ w1,
+                                                           float* __restrict__ part, int T, int K) {
+    __shared__ float red[4];
+    const float s = tap_bce_part_sum(scores, masks, labels, w1, (long)T * K, K, blockIdx.x, red);
+    if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 __global__ __launch_bounds__(64) void tap_bce_final_kernel(const float* __restrict__ part, float* __restrict__ loss, long n, int K) {
-    if (threadIdx.x == 0) {
-        float t = 0.f;
-        for (int i = 0; i < BCE_PARTS; ++i) t += part[i];
-        loss[0] = t / (float)n * (float)K;
-    }
+    if (threadIdx.x == 0) loss[0] = tap_bce_mean(part, n, K);
 }
 __global__ void tap_bce_bwd_kernel(const float* __restrict__ scores, const float* __restrict__ masks, const float* __restrict__ labels,
                                    const float* __restrict__ w1, const float* __restrict__ g_loss, float* __restrict__ g_scores, int T, int K) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (long)T * K) return;
-    const int k = (int)(i % K);
-    const float m = masks[i], y = labels[i] * m, p = scores[i] * m;
-    const float w = y * (1.f - w1[k]) + (1.f - y) * w1[k];
-    // d/dp of -(y log p + (1-y) log(1-p)) with torch's clamp: the clamped branch has zero slope
-    float d = 0.f;
-    if (logf(p) > -100.f) d -= y / p;
-    if (logf(1.f - p) > -100.f) d += (1.f - y) / (1.f - p);
-    g_scores[i] = g_loss[0] * w * d * m / (float)T;       // K / (T*K)
+    g_scores[i] = tap_bce_grad(scores[i], masks[i], labels[i], w1[(int)(i % K)], g_loss[0], (float)T);
+}
+// The criterion over a multi-video batch (concatenated [T_tot, K] matrices, row_offset [V+1]): grid (BCE_PARTS, V) -- video v's T_v*K
+// elements are cut exactly as tap_bce_part_kernel cuts a single video's -- then ONE launch adds each video's partials in index order
+// (video_loss[v], its own mean over T_v x K, times K) and the V losses in video order (loss_sum): every sum has one fixed order, and video
+// 0 of a one-video batch is echr_tap_bce_fwd_ws bit for bit.  w1_ld = 0: one [K] weight vector for all videos; K: w1 is [V, K]
+__global__ __launch_bounds__(256) void tap_bce_part_batch_kernel(const float* __restrict__ scores, const float* __restrict__ masks,
+                                                                 const float* __restrict__ labels, const float* __restrict__ w1, int w1_ld,
+                                                                 const int* __restrict__ row_offset, float* __restrict__ part, int K) {
+    __shared__ float red[4];
+    const int v = blockIdx.y;
+    const long r0 = row_offset[v], n = ((long)row_offset[v + 1] - r0) * K, o = r0 * K;
+    const float s = tap_bce_part_sum(scores + o, masks + o, labels + o, w1 + (long)v * w1_ld, n, K, blockIdx.x, red);
+    if (threadIdx.x == 0) part[(long)v * BCE_PARTS + blockIdx.x] = s;
+}
+__global__ __launch_bounds__(64) void tap_bce_final_batch_kernel(const float* __restrict__ part, const int* __restrict__ row_offset, int V, int K,
+                                                                 float* __restrict__ video_loss, float* __restrict__ loss_sum) {
+    for (int v = threadIdx.x; v < V; v += 64)
+        video_loss[v] = tap_bce_mean(part + (long)v * BCE_PARTS, ((long)row_offset[v + 1] - row_offset[v]) * K, K);
+    __syncthreads();          // (one workgroup: the losses written above are visible to thread 0 behind the barrier)
+    if (threadIdx.x == 0 && loss_sum) {
+        float t = 0.f;
+        for (int v = 0; v < V; ++v) t += video_loss[v];
+        loss_sum[0] = t;
+    }
+}
+// one launch over the T_tot*K elements; an element's video comes from row_offset: the workgroup's first row is located by a uniform scan
+// (V is small), an element then only steps over the boundaries inside the workgroup's 256 elements
+__global__ __launch_bounds__(256) void tap_bce_bwd_batch_kernel(const float* __restrict__ scores, const float* __restrict__ masks,
+                                                                const float* __restrict__ labels, const float* __restrict__ w1, int w1_ld,
+                                                                const int* __restrict__ row_offset, int V, int K, long n,
+                                                                const float* __restrict__ g_loss, float* __restrict__ g_scores) {
+    const long b0 = (long)blockIdx.x * 256, i = b0 + threadIdx.x;
+    const int first = (int)(b0 / K);
+    int v = 0;
+    while (v + 1 < V && first >= row_offset[v + 1]) ++v;
+    if (i >= n) return;
+    const int row = (int)(i / K), k = (int)(i - (long)row * K);
+    while (v + 1 < V && row >= row_offset[v + 1]) ++v;
+    g_scores[i] = tap_bce_grad(scores[i], masks[i], labels[i], w1[(long)v * w1_ld + k], g_loss[0], (float)(row_offset[v + 1] - row_offset[v]));
 }
 
 // =====================================================================================================================
@@ -1534,4 +1583,22 @@ extern "C" int echr_tap_bce_bwd(const float* scores, const float* masks, const f
     hipLaunchKernelGGL(tap_bce_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, scores, masks, labels, w1,
                        g_loss, g_scores, T, K);
     return check_launch("tap_bce_bwd");
+}
+extern "C" int echr_tap_bce_fwd_batch(const float* scores, const float* masks, const float* labels, const float* w1, int32_t w1_ld,
+                                      const int32_t* row_offset, int32_t V, int32_t K, float* video_loss, float* loss_sum, float* partials, void* stream) {
+    ECHR_REQUIRE(scores && masks && labels && w1 && row_offset && video_loss && partials && V > 0 && K > 0 && (w1_ld == 0 || w1_ld == K),
+                 "tap_bce_fwd_batch: bad arguments (w1_ld must be 0 or K)");
+    hipLaunchKernelGGL(tap_bce_part_batch_kernel, dim3(BCE_PARTS, V), dim3(256), 0, (hipStream_t)stream, scores, masks, labels, w1, w1_ld, row_offset,
+                       partials, K);
+    hipLaunchKernelGGL(tap_bce_final_batch_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, partials, row_offset, V, K, video_loss, loss_sum);
+    return check_launch("tap_bce_fwd_batch");
+}
+extern "C" int echr_tap_bce_bwd_batch(const float* scores, const float* masks, const float* labels, const float* w1, int32_t w1_ld,
+                                      const int32_t* row_offset, int32_t V, int32_t K, int32_t T_tot, const float* g_loss, float* g_scores, void* stream) {
+    ECHR_REQUIRE(scores && masks && labels && w1 && row_offset && g_loss && g_scores && V > 0 && K > 0 && T_tot >= V && (w1_ld == 0 || w1_ld == K),
+                 "tap_bce_bwd_batch: bad arguments (w1_ld must be 0 or K)");
+    const long n = (long)T_tot * K;
+    hipLaunchKernelGGL(tap_bce_bwd_batch_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, scores, masks, labels, w1, w1_ld,
+                       row_offset, V, K, n, g_loss, g_scores);
+    return check_launch("tap_bce_bwd_batch");
 }

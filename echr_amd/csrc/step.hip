@@ -49,7 +49,7 @@ static StepWs carve_step(const echr_train_step_args* a, bool rw = false, const e
         const long h3 = 3L * d.H, dt = init_feats_width(a);
         w.h0 = take((long)d.N * h3); w.g_h0 = take((long)d.N * h3); w.init_feats = take((long)d.N * dt); w.init_dfeats = take((long)d.N * dt);
     }
-    w.g_video = take(d.Dv); w.g_video_init = take(d.Dv);
+    w.g_video = take((bx ? (long)bx->n_videos : 1L) * d.Dv); w.g_video_init = take(d.Dv);          // (a batch: d video is [V, Dv])
     w.rows = w.row_grad = -1;
     if (x) {
         if (x->clip_parts == 3) w.rows = take((long)d.Tv * d.D);
@@ -229,7 +229,7 @@ extern "C" int echr_train_step_prepare(const echr_train_step_args* a, void* stre
 }
 
 static int train_step_impl(const echr_train_step_args* a, void* stream, bool rw, const float* rw_dev, const echr_clip_step_args* x = nullptr,
-                           const echr_batch_ext* bx = nullptr, float* video_loss = nullptr);
+                           const echr_batch_ext* bx = nullptr, float* video_loss = nullptr, const int32_t* row_offset = nullptr);
 extern "C" int echr_train_step(const echr_train_step_args* a, void* stream) { return train_step_impl(a, stream, false, nullptr); }
 // Frame-level context 'CH' / 'CC+CH' (include/echr_hip.h): the same iteration with tap_feats (or [c3d | tap]) as the attended rows and the
 // clip-row gradient added to g_tap behind the join of the backward's helper streams
@@ -276,8 +276,26 @@ extern "C" int echr_train_step_batch(const echr_train_step_args* a, const echr_b
     ECHR_REQUIRE(!a->w_init, "train_step_batch: an initial state (CG_init_feats_type) is not part of the batched step");
     return train_step_impl(a, stream, true, a->host_nll ? nullptr : weight, nullptr, x, video_loss);
 }
+// The joint 'tap_cg' iteration over a batch: echr_train_step_batch that also returns d loss / d tap_feats.  a->g_tap [T_tot, Ht] is zero-filled
+// by the caller and added into: the anchors' rows through the block-diagonal event encoder's d ech (ind is batch-absolute; 'ER1' reads no
+// tap row and adds nothing), and with 'VH' each video's d scene vector spread over that video's OWN rows (row_offset, device [V+1]).
+extern "C" int64_t echr_train_step_batch_tap_ws_floats(const echr_train_step_args* a, const echr_batch_ext* x) {
+    return echr_train_step_batch_ws_floats(a, x);
+}
+extern "C" int echr_train_step_batch_tap(const echr_train_step_args* a, const echr_batch_ext* x, const float* weight, float* video_loss,
+                                         const int32_t* row_offset, void* stream) {
+    ECHR_REQUIRE(a && x && x->n_videos > 0 && x->n_videos <= a->dec.N && x->video, "train_step_batch_tap: the batch extension needs 0 < n_videos <= N and video");
+    ECHR_REQUIRE(a->host_nll || weight, "train_step_batch_tap: the criterion weights are missing (device `weight`, or host_index with host_nll = 1)");
+    ECHR_REQUIRE(!(a->host_nll && weight), "train_step_batch_tap: host_nll = 1 carries the weights in host_index: pass weight = NULL");
+    ECHR_REQUIRE(a->g_tap && a->tap && a->Ht > 0 && !a->forward_only, "train_step_batch_tap: g_tap / tap missing (without g_tap this is echr_train_step_batch)");
+    ECHR_REQUIRE(a->vh_offset < 0 || row_offset, "train_step_batch_tap: the 'VH' scene gradient needs row_offset");
+    ECHR_REQUIRE(!a->prepared && !a->defer_update && !a->handover && !a->mid_cb,
+                 "train_step_batch_tap: prepared, defer_update, handover and mid_cb are not part of the batched step");
+    ECHR_REQUIRE(!a->w_init, "train_step_batch_tap: an initial state (CG_init_feats_type) is not part of the batched step");
+    return train_step_impl(a, stream, true, a->host_nll ? nullptr : weight, nullptr, x, video_loss, row_offset);
+}
 static int train_step_impl(const echr_train_step_args* a, void* stream, bool rw, const float* rw_dev, const echr_clip_step_args* x, const echr_batch_ext* bx,
-                           float* video_loss) {
+                           float* video_loss, const int32_t* row_offset) {
     ECHR_REQUIRE(a && a->ws && a->host_index && a->loss && a->g_loss && a->flat_g && (a->tap || a->event_parts == 1), "train_step: missing buffers");
     ECHR_REQUIRE(!a->prepared || a->overlap_encoder, "train_step: prepared = 1 needs overlap_encoder = 1");
     const int parts = a->event_parts ? a->event_parts : 3;
@@ -325,6 +343,7 @@ static int train_step_impl(const echr_train_step_args* a, void* stream, bool rw,
         bxl = *bx;
         bxl.vid = idx + step_index_count(a, rw, nullptr);
         bxl.ws = ws + L.batch;
+        if (vh) bxl.g_video = ws + L.g_video;          // [V, Dv]: the batched decoder backward writes d video per video (its spans go into g_tap)
     }
     BatchScope scope(bx ? &bxl : nullptr);
     const int32_t *ev_start = idx, *ev_len = idx + N, *ind = idx + 2 * N, *active = idx + (3 + S) * N;          // (tokens at idx + 3 N: step_dec_args)
@@ -459,7 +478,10 @@ static int train_step_impl(const echr_train_step_args* a, void* stream, bool rw,
         r.col0 = x->clip_parts == 3 ? Dc : 0; r.ncols = a->Ht; r.out = a->g_tap; r.ld = a->Ht; r.ws = ws + L.row_grad;
         RC(row_grad(&d, &g, &r, st));
     }
-    if (vh) {
+    if (vh && bx) {
+        // a batch: video v's scene vector is the mean over ITS rows -- d tap[r, :] += d video[v, vh span] / T_v for r in [row_offset[v], row_offset[v+1])
+        RC(echr_seg_col_mean_bwd(ws + L.g_video + a->vh_offset, a->dec.Dv, row_offset, bxl.n_videos, a->Ht, a->Ht, a->g_tap, stream));
+    } else if (vh) {
         // scene context 'VH' = tap.mean(0) (CaptionGenerator.py:95-99): d tap[r, :] += d video[vh span] / rows, for the decoder's d video (final
         // behind the join: it is formed in the LSTM-layer stage on a helper stream) and init_linear's
         RC(echr_col_mean_bwd(ws + L.g_video + a->vh_offset, a->tap_rows, a->Ht, a->Ht, a->g_tap, stream));

@@ -1023,6 +1023,42 @@ class TapBCE(torch.autograd.Function):
         return gs, None, None, None
 
 
+class TapBCEBatch(torch.autograd.Function):
+    """TAPModelCriterion over a multi-video batch (echr_tap_bce_fwd_batch / _bwd_batch): scores / masks / labels are the concatenated
+    [T_tot, K] matrices, `ro_dev` the int32 device row offsets [V+1], w1 [K] (all videos) or [V, K].  Returns (sum over the videos,
+    per-video losses [V]); each video keeps its own mean over T_v x K, no 1/V."""
+
+    @staticmethod
+    def forward(ctx, scores, masks, labels, w1, ro_dev):
+        lib = L.load()
+        scores, masks, labels, w1 = _f32c(scores), _f32c(masks), _f32c(labels), _f32c(w1)
+        T, K = scores.shape
+        V = ro_dev.numel() - 1
+        w1_ld = 0 if w1.numel() == K else K
+        if tuple(masks.shape) != (T, K) or tuple(labels.shape) != (T, K) or (w1_ld and tuple(w1.shape) != (V, K)):
+            raise ValueError('masks / labels must be shaped like scores %s, w1 [K] or [V, K] (got %s, %s, %s)'
+                             % ((T, K), tuple(masks.shape), tuple(labels.shape), tuple(w1.shape)))
+        buf = torch.empty(1 + 64 * V, device=scores.device, dtype=torch.float32)          # sum | 64 partial sums per video
+        per = torch.empty(V, device=scores.device, dtype=torch.float32)
+        L.check(lib.echr_tap_bce_fwd_batch(L.ptr(scores), L.ptr(masks), L.ptr(labels), L.ptr(w1), w1_ld, L.ptr(ro_dev, torch.int32), V, K,
+                                           L.ptr(per), L.ptr(buf[:1]), L.ptr(buf[1:]), L.stream_ptr()), 'tap_bce_fwd_batch')
+        ctx.save_for_backward(scores, masks, labels, w1, ro_dev)
+        ctx.meta = (V, w1_ld)
+        ctx.mark_non_differentiable(per)
+        return buf[0], per
+
+    @staticmethod
+    def backward(ctx, g, _g_per):
+        lib = L.load()
+        scores, masks, labels, w1, ro_dev = ctx.saved_tensors
+        V, w1_ld = ctx.meta
+        T, K = scores.shape
+        gs = torch.empty_like(scores)
+        L.check(lib.echr_tap_bce_bwd_batch(L.ptr(scores), L.ptr(masks), L.ptr(labels), L.ptr(w1), w1_ld, L.ptr(ro_dev, torch.int32), V, K, T,
+                                           L.ptr(_f32c(g).reshape(1)), L.ptr(gs), L.stream_ptr()), 'tap_bce_bwd_batch')
+        return gs, None, None, None, None
+
+
 def h2_pack(x, transposed=False):
     """h2-packed image (two block-scaled fp16 planes, include/echr_hip.h) of the operand x [R,K] -- or, with transposed=True,
     of x^T for x stored [K,R] (the pack transposes on the fly).  Returns (uint8 buffer, R, K)."""

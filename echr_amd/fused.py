@@ -255,6 +255,30 @@ class FusedTrainStep(object):
                                           L.ptr(self.last_video_losses) if video_losses else None, L.stream_ptr()), 'train_step_batch')
         return self._finish(slot, st, forward_only)
 
+    def _batch_tap(self, batch, tap_grad, ro_dev, video_losses, g_loss=None, step=True):
+        """The caption side of the joint iteration over a batch (echr_train_step_batch_tap; fused.JointBatchStep): batch() with the zero-filled
+        `tap_grad` [T_tot, Ht] receiving d loss / d batch.tap.  `ro_dev`: the batch's row offsets as an int32 device vector [V+1];
+        `video_losses`: device [V] out; `g_loss`: a one-element device tensor that scales every gradient (lambda2; None = 1) -- the returned
+        loss and the per-video losses stay unscaled."""
+        a, m = self.a, self.model
+        with torch.no_grad():
+            video = EF._f32c(m.get_video_context_batch(batch))
+        slot, st = self._setup(batch.tap, batch.c3d, video, batch.labels, batch.ind, batch.soi, batch.targets, batch.crit_masks, step, False,
+                               tap_grad, False, weights=batch.criterion_weights(), batch=batch)
+        a.prepared = a.handover = 0
+        a.handover_cb = a.handover_user = a.mid_cb = a.mid_user = None
+        self._pending_deferred = False
+        self._keep = self._keep + (video, g_loss, ro_dev)
+        self.last_video_losses = video_losses
+        if g_loss is not None:
+            a.g_loss = L.ptr(g_loss)
+        try:
+            L.check(self.lib.echr_train_step_batch_tap(C.byref(a), C.byref(self.bx), None, L.ptr(video_losses), L.ptr(ro_dev, torch.int32),
+                                                       L.stream_ptr()), 'train_step_batch_tap')
+        finally:
+            a.g_loss = self.one.data_ptr()
+        return self._finish(slot, st, False)
+
     def _set_tap(self, tap, tap_grad, defer_update, step, forward_only):
         a, d = self.a, self.a.dec
         if (tap.shape[1] if a.event_parts & 2 else 0) + (self._dc if a.event_parts & 1 else 0) != a.tsrm.Din or tap.shape[0] < self._tv_needed:
@@ -564,7 +588,7 @@ class JointTrainStep(object):
     the host's issue of the caption tail; issued from the hook it starts at once and the chip-filling tail follows it instead of
     preceding it.  Same sums as loss.backward() on the joint loss: gradients of both models, both updates."""
 
-    def __init__(self, fused, tap_model, tap_optim, lambda1=1.0, tap_grad_clip=None, early_prepare=True, order=None):
+    def __init__(self, fused, tap_model, tap_optim, lambda1=1.0, tap_grad_clip=None, early_prepare=True, order=None, lambda2=1.0):
         ar = getattr(tap_model, '_echr_arena', None)
         if not isinstance(tap_optim, ClampAdam) or tap_optim.arena is None or tap_optim.arena is not ar or not ar.params_in_arena():
             raise ValueError('JointTrainStep needs the proposal encoder on a flat arena (tap_model.build_arena()) and a ClampAdam built with it')
@@ -578,6 +602,10 @@ class JointTrainStep(object):
         self.order = order or os.environ.get('ECHR_JOINT_ORDER', 'after')
         self.lib, self.dev = fused.lib, fused.dev
         self.lam = torch.full((1,), self.lambda1, device=self.dev, dtype=torch.float32)
+        # lambda2 (train.py:322-329) scales the caption term: it travels as the caption call's g_loss scalar (every caption-side gradient and
+        # d tap_feats carry it) and multiplies the returned cg term; 1.0 keeps the call's own unit scalar and today's arithmetic
+        self.lambda2 = float(lambda2)
+        self.lam2 = None if self.lambda2 == 1.0 else torch.full((1,), self.lambda2, device=self.dev, dtype=torch.float32)
         self._buf_key, self._bufs = None, None
         self.tap_loss = None
 
@@ -596,10 +624,11 @@ class JointTrainStep(object):
 
     def batch(self, *args, **kwargs):
         """Multi-video batches (FusedTrainStep.batch) are not part of this step yet: the proposal encoder runs over one video, and d tap_feats (tap_grad) / the deferred update are single-video forms."""
-        raise NotImplementedError('JointTrainStep takes one video per call: the joint iteration (tap_grad, defer_update, prepare) over a VideoBatch is a follow-up')
+        raise NotImplementedError('JointTrainStep takes one video per call (tap_grad with defer_update / prepare are single-video forms): '
+                                  'the joint iteration over a VideoBatch is fused.JointBatchStep')
 
     def __call__(self, c3d_feats, lda_feats, lm_labels, ind_select_list, soi_select_list, targets, masks, tap_masks, tap_labels, w1):
-        """Returns (lambda1 * tap_loss + cg_loss) as a 0-d device tensor; `self.tap_loss` / `self.cg_loss` hold the two terms."""
+        """Returns (lambda1 * tap_loss + lambda2 * cg_loss) as a 0-d device tensor; `self.tap_loss` / `self.cg_loss` hold the two (unscaled) terms."""
         lib, f, tm = self.lib, self.fused, self.tap_model
         c3d = EF._f32c(c3d_feats)
         ps = [EF._f32c(p) for p in tm.native_params()]
@@ -614,6 +643,8 @@ class JointTrainStep(object):
         if self.early:          # the caption side's tap-independent half beside the proposal encoder's forward (which leaves 192 CUs idle)
             f.prepare(c3d, lda_feats, lm_labels, ind_select_list, soi_select_list, targets, masks)
         try:
+            if self.lam2 is not None:
+                f.a.g_loss = self.lam2.data_ptr()          # (inside the try: whatever raises below, the finally puts the unit scalar back)
             # the gradient span of the proposal encoder and d tap_feats: zero-filled HERE, off the chain that later leads to its backward
             ar.flat_g.zero_()
             B['g_tap'].zero_()
@@ -653,11 +684,183 @@ class JointTrainStep(object):
         except BaseException:
             f.cancel_prepare()
             raise
+        finally:
+            f.a.g_loss = f.one.data_ptr()
         if not f.mid_called:          # the library ran the plain form (options the deferred form declines): the same work, behind the call
             sst_backward()
         self._keep = (c3d, mk, lb, ww, ps)
         self.tap_loss, self.cg_loss = B['loss'][0], cg
+        if self.lam2 is not None:
+            return self.lam[0] * B['loss'][0] + self.lam2[0] * cg
         return self.lam[0] * B['loss'][0] + cg
+
+
+class JointBatchStep(object):
+    """The joint 'tap_cg' iteration (train.py:292-329) over a multi-video batch (echr_amd.batch.VideoBatch) of V videos, without an autograd
+    graph -- the batch contract of echr_amd/batch.py extended to both models:
+
+        echr_sst_fwd_batch (tap_feats and scores of the V videos)  ->  echr_tap_bce_fwd_batch  ->  echr_train_step_batch_tap: the caption side
+        as ONE call that also returns d loss / d batch.tap  ->  echr_tap_bce_bwd_batch, echr_sst_bwd_batch  ->  one clamp + Adam per model.
+
+    loss = lambda1 * sum_v TAPModelCriterion(video v) + lambda2 * sum_v LanguageModelCriterion(video v); each video keeps its own normaliser
+    (the mean over its own T_v x K, times K; sum(mask_v) + 1e-6), there is no 1/V, the gradients of both models are sums over the videos.
+    One dropout counter per model and call, keyed by the batch-global element; a one-video batch computes what JointTrainStep computes.
+    Nothing is deferred or hooked here (defer_update, prepare, mid_cb stay single-video forms)."""
+
+    def __init__(self, fused, tap_model, tap_optim, lambda1=1.0, lambda2=1.0, tap_grad_clip=None):
+        if not isinstance(fused, FusedTrainStep):
+            raise TypeError('JointBatchStep wraps a FusedTrainStep')
+        ar = getattr(tap_model, '_echr_arena', None)
+        if not isinstance(tap_optim, ClampAdam) or tap_optim.arena is None or tap_optim.arena is not ar or not ar.params_in_arena():
+            raise ValueError('JointBatchStep needs the proposal encoder on a flat arena (tap_model.build_arena()) and a ClampAdam built with it')
+        if len(tap_optim.param_groups) != 1 or {id(p) for p in tap_optim.param_groups[0]['params']} != {id(p) for p in ar.params}:
+            raise ValueError('the proposal encoder\'s optimiser must hold exactly its parameters in one group')
+        self.fused, self.tap_model, self.tap_optim, self.tap_arena = fused, tap_model, tap_optim, ar
+        self.lambda1, self.lambda2, self.tap_grad_clip = float(lambda1), float(lambda2), tap_grad_clip
+        self.lib, self.dev = fused.lib, fused.dev
+        self.lam = torch.full((2,), self.lambda1, device=self.dev, dtype=torch.float32)
+        self.lam[1] = self.lambda2
+        self._buf_key, self._bufs = None, None
+        self._ro_cache = {}
+        self.tap_loss = self.cg_loss = self.last_tap_losses = self.last_video_losses = None
+        self.last_batch = None
+
+    def _buffers(self, T, V, D, H, K):
+        key = (T, V, D, H, K)
+        if self._buf_key != key:
+            self.fused.join()          # (work of an earlier call may still read the old tap_feats)
+            lib, dev, f32 = self.lib, self.dev, torch.float32
+            self._bufs = dict(ws=torch.empty(lib.echr_sst_batch_ws_floats(T, D, H, K, V), device=dev, dtype=f32),
+                              wsb=torch.empty(lib.echr_sst_batch_ws_bwd_floats(T, D, H, K, V), device=dev, dtype=f32),
+                              tap=torch.empty(T, H, device=dev, dtype=f32), scores=torch.empty(T, K, device=dev, dtype=f32),
+                              g_tap=torch.empty(T, H, device=dev, dtype=f32), g_scores=torch.empty(T, K, device=dev, dtype=f32),
+                              loss=torch.zeros(1, device=dev, dtype=f32), tap_losses=torch.zeros(V, device=dev, dtype=f32),
+                              video_losses=torch.zeros(V, device=dev, dtype=f32), part=torch.empty(64 * V, device=dev, dtype=f32))
+            self._buf_key = key
+        return self._bufs
+
+    def _row_offsets(self, rows, T):
+        ro = EF.sst_row_offsets(rows, T)
+        key = ro.tobytes()
+        ro_dev = self._ro_cache.get(key)
+        if ro_dev is None:          # (kept for the batches a loop repeats: a pageable host-to-device copy synchronises the stream)
+            if len(self._ro_cache) >= 64:
+                self._ro_cache.clear()
+            ro_dev = self._ro_cache[key] = torch.from_numpy(ro).to(self.dev)
+        return ro, ro_dev
+
+    def _sst_forward(self, c3d, rows):
+        """The proposal encoder over the concatenated c3d rows into this object's buffers (echr_sst_fwd_batch; no graph): returns tap [T_tot, H]."""
+        tm = self.tap_model
+        if not c3d.is_cuda:
+            raise L.EchrHipError('JointBatchStep runs on the GPU only')
+        c3d = EF._f32c(c3d)
+        ps = [EF._f32c(p) for p in tm.native_params()]
+        T, D = c3d.shape
+        H, K = ps[1].shape[1], ps[8].shape[0]
+        if D != ps[0].shape[1]:
+            raise L.EchrHipError('c3d features are %d wide, the proposal encoder reads %d' % (D, ps[0].shape[1]))
+        ro, ro_dev = self._row_offsets(rows, T)
+        V = len(ro) - 1
+        B = self._buffers(T, V, D, H, K)
+        p_drop = float(tm.rnn.dropout)
+        if tm._drop_seed is None:
+            tm._drop_seed = (int(torch.initial_seed()) ^ 0x55AA) & 0xFFFFFFFFFFFFFFFF
+        drop = EF.DropState(tm._drop_seed, tm._drop_calls, p_drop > 0.0)
+        if p_drop > 0.0:
+            tm._drop_calls += 1          # ONE counter per batched call, the mask keyed by the batch-global row (models.SST.forward_batch)
+        sa = EF.SSTFunction._args(ps, c3d, p_drop, B['ws'], B['tap'], B['scores'])
+        bx = L.SstBatch(V, L.ptr(ro_dev, torch.int32), ro.ctypes.data)
+        dc = drop.c()
+        L.check(self.lib.echr_sst_fwd_batch(C.byref(sa), C.byref(bx), C.byref(dc), L.stream_ptr()), 'sst_fwd_batch')
+        self._sst = (sa, bx, dc, ro, ro_dev, ps, c3d, V, T, K)
+        return B['tap']
+
+    def _tap_inputs(self, x, T, K, name):
+        if isinstance(x, (list, tuple)):
+            x = torch.cat([torch.as_tensor(t).to(self.dev) for t in x], 0)
+        x = torch.as_tensor(x)
+        x = EF._f32c(x if x.is_cuda else x.to(self.dev))
+        if tuple(x.shape) != (T, K):
+            raise ValueError('%s must be the concatenated [T_tot, K] = [%d, %d] matrix or one [T_v, K] matrix per video (got %s)' % (name, T, K, tuple(x.shape)))
+        return x
+
+    def __call__(self, videos_or_batch, tap_masks, tap_labels, w1, step=True):
+        """One iteration; returns lambda1 * tap_loss + lambda2 * cg_loss as a 0-d device tensor (no host sync).  `videos_or_batch`: the dicts
+        VideoBatch.from_videos takes (no 'tap' needed), or a ready VideoBatch whose `tap` is ignored: the batch's tap_feats are the proposal
+        encoder's forward of this call.  `tap_masks` / `tap_labels`: the concatenated [T_tot, K] matrices or one [T_v, K] per video; `w1`:
+        one [K] weight vector for all videos, or one per video (a list, or [V, K]).  `tap_loss` / `cg_loss` hold the two sums over the videos,
+        `last_tap_losses` / `last_video_losses` the per-video terms [V] (device tensors), `last_batch` the VideoBatch the call ran on.
+        step=False stops after the backward passes and leaves both models' summed gradients in their arenas (`.grad` views); the proposal
+        encoder's `.grad` views are set after a step as well."""
+        from .batch import VideoBatch
+        lib, f, tm = self.lib, self.fused, self.tap_model
+        m = f.model
+        m._check_batch_options()
+        if getattr(f, '_prepared', False):
+            raise NotImplementedError('prepare() runs ahead of ONE video\'s call: it does not combine with JointBatchStep')
+        L.check(lib.echr_check_async(), 'joint_batch_step (asynchronous failure of an earlier call)')
+        if getattr(f, '_pending_deferred', False):
+            f.join()          # (a deferred single-video update may still read buffers this call rewrites)
+            f._pending_deferred = False
+        ar = self.tap_arena
+        for p in ar.params:
+            p.grad = None
+        ar.deferred_clamp = None
+        ar.end_backward_pass()
+        if isinstance(videos_or_batch, VideoBatch):
+            src = videos_or_batch
+            if src.labels is None:
+                raise ValueError('the batch carries no labels')
+            tap = self._sst_forward(src.c3d, src.row_offset)
+            batch = VideoBatch(src.c3d, tap, src.lda, src.row_offset, src.event_offset, src.soi, src.ind, src.labels, src.masks)
+        else:
+            batch = VideoBatch.from_videos(videos_or_batch, device=self.dev, tap_fn=self._sst_forward)
+            if batch.labels is None:
+                raise ValueError('the videos carry no labels / masks')
+        sa, bx, dc, ro, ro_dev, ps, c3d, V, T, K = self._sst
+        B = self._bufs
+        ar.flat_g.zero_()
+        B['g_tap'].zero_()
+        mk, lb = self._tap_inputs(tap_masks, T, K, 'tap_masks'), self._tap_inputs(tap_labels, T, K, 'tap_labels')
+        if isinstance(w1, (list, tuple)):
+            if len(w1) != V:
+                raise ValueError('w1 must be one weight vector or one per video (%d given for %d videos)' % (len(w1), V))
+            w1 = torch.stack([torch.as_tensor(t).reshape(-1).to(self.dev) for t in w1], 0)
+        ww = torch.as_tensor(w1)
+        ww = EF._f32c(ww if ww.is_cuda else ww.to(self.dev))
+        if ww.numel() == K:
+            ww, w1_ld = ww.reshape(-1), 0
+        elif tuple(ww.shape) == (V, K):
+            w1_ld = K
+        else:
+            raise ValueError('w1 must be [K] = [%d] or [V, K] = [%d, %d] (got %s)' % (K, V, K, tuple(ww.shape)))
+        # proposal criterion (misc/utils.py:78-99 per video): per-video losses and their sum in one fixed order
+        L.check(lib.echr_tap_bce_fwd_batch(L.ptr(B['scores']), L.ptr(mk), L.ptr(lb), L.ptr(ww), w1_ld, L.ptr(ro_dev, torch.int32), V, K,
+                                           L.ptr(B['tap_losses']), L.ptr(B['loss']), L.ptr(B['part']), L.stream_ptr()), 'tap_bce_fwd_batch')
+        # the caption side: forward, criterion, backward, d loss / d batch.tap, clamp + Adam -- ONE call; lambda2 travels as its g_loss scalar
+        cg = f._batch_tap(batch, B['g_tap'], ro_dev, B['video_losses'], g_loss=self.lam[1:], step=step)
+        # d (lambda1 * sum_v tap_loss_v) / d scores, then the proposal encoder's backward with d loss / d tap_feats from the caption side
+        L.check(lib.echr_tap_bce_bwd_batch(L.ptr(B['scores']), L.ptr(mk), L.ptr(lb), L.ptr(ww), w1_ld, L.ptr(ro_dev, torch.int32), V, K, T,
+                                           L.ptr(self.lam[:1]), L.ptr(B['g_scores']), L.stream_ptr()), 'tap_bce_bwd_batch')
+        nps = tm.native_params()
+        one = lambda i: ar.flat_g.data_ptr() + 4 * ar.offsets[ar.slot(nps[i])]
+        two = lambda i, j: (L.c_f * 2)(one(i), one(j))
+        sg = L.SstGrads(two(0, 4), two(1, 5), two(2, 6), two(3, 7), one(8), one(9), L.ptr(B['g_tap']), L.ptr(B['g_scores']), L.ptr(B['wsb']), 1)
+        L.check(lib.echr_sst_bwd_batch(C.byref(sa), C.byref(bx), C.byref(sg), C.byref(dc), L.stream_ptr()), 'sst_bwd_batch')
+        if step:
+            self.tap_optim.step_flat_raw(self.tap_grad_clip)          # train.py:315-317 for tap_optimizer
+        else:
+            ar._zeroed = [(0, ar.total)]
+        # the proposal encoder's summed gradient stays readable as `.grad` views of its arena, as after an autograd iteration (behind a step
+        # too: the update reads the arena and leaves it as it is)
+        for i, p in enumerate(ar.params):
+            p.grad = ar.grad_view(i)
+        self._keep = (c3d, mk, lb, ww, ps, batch)
+        self.last_batch = batch
+        self.tap_loss, self.cg_loss = B['loss'][0], cg
+        self.last_tap_losses, self.last_video_losses = B['tap_losses'], B['video_losses']
+        return self.lam[0] * B['loss'][0] + self.lam[1] * cg
 
 
 class DataParallelStep(object):

@@ -57,6 +57,21 @@ class TAPModelCriterion(nn.Module):
     def forward(self, scores, masks, labels, w1):
         return EF.TapBCE.apply(scores, masks.to(scores.device), labels.to(scores.device), w1.to(scores.device))
 
+    def forward_batch(self, scores, masks, labels, w1, row_offset):
+        """The criterion over a multi-video batch in two launches (echr_tap_bce_fwd_batch) and one for its gradient: `scores`, `masks`,
+        `labels` are the concatenated [T_tot, K] matrices, `row_offset` [V+1] the videos' rows, `w1` one [K] weight vector for all videos, a
+        list of V, or [V, K].  Returns (sum over the videos, per-video losses [V]); the gradient flows through the sum (the per-video losses
+        are reported values).  Each video keeps its own mean over its T_v x K elements, no 1/V -- what tap_criterion_batch computes."""
+        dev = scores.device
+        ro = EF.sst_row_offsets(row_offset, scores.shape[0])
+        if isinstance(w1, (list, tuple)):
+            if len(w1) != len(ro) - 1:
+                raise ValueError('w1 must be one weight vector or one per video')
+            w1 = torch.stack([torch.as_tensor(w).reshape(-1).to(dev) for w in w1], 0)
+        ro_dev = row_offset if (isinstance(row_offset, torch.Tensor) and row_offset.is_cuda and row_offset.dtype == torch.int32) \
+            else torch.from_numpy(ro).to(dev)
+        return EF.TapBCEBatch.apply(scores, masks.to(dev), labels.to(dev), w1.to(dev), ro_dev)
+
 
 def tap_criterion_batch(crit, scores, masks, labels, w1, row_offset):
     """TAPModelCriterion over a multi-video batch: `scores`, `masks`, `labels` are the concatenated [T_tot, K] matrices, `row_offset` [V+1]

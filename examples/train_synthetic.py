@@ -15,6 +15,13 @@ the fused ClampAdam, and `--resume` restores models AND optimiser state (train.p
 gradients of m_batch videos summed before one clamp + step.  Here the m_batch videos are ONE call: tap_model.forward_batch over the
 concatenated features, utils.tap_criterion_batch (every video its own mean), one backward, one fused step.
 
+`--joint --m_batch V` (V > 1) is stage 3 (finetune.sh, training_mode 'tap_cg') with the V videos of one accumulation as ONE batch:
+fused.JointBatchStep -- the proposal encoder, both criteria, the caption side with d loss / d tap_feats, both backward passes and one clamp +
+Adam per model, without an autograd graph (`--no-fused` keeps the V sequential autograd iterations with accumulation).  In this mode, as
+with `--pre_tap`, ONE iteration of `--iters` is one batch of V videos with an update, and the `iteration` that `--save` writes counts such
+batches; the autograd modes count single-video iterations (an update every m_batch of them), so a checkpoint resumed under the other mode
+continues at a different video and epoch.
+
 usage: python examples/train_synthetic.py [--iters 20] [--m_batch 2] [--joint] [--pre_tap] [--save /tmp/echr_ckpt.pth] [--resume /tmp/echr_ckpt.pth]
 """
 import argparse
@@ -79,6 +86,28 @@ def pre_tap(a, opt, dev, loader, tap_model, cg_model, cg_opt, tap_opt, tap_crit,
     return history, cg_model, tap_model
 
 
+def joint_batch(a, opt, dev, loader, tap_model, cg_model, cg_opt, tap_opt, start):
+    """Stage 3 ('tap_cg') over m_batch videos per call: one fused.JointBatchStep call per accumulation (train.py:281-329 with the videos of one
+    accumulation as one batch; lambda1 = 0.01, lambda2 = 1 as opts.py:194-196)."""
+    from echr_amd.fused import FusedTrainStep, JointBatchStep
+    step = JointBatchStep(FusedTrainStep(cg_model, cg_opt, grad_clip=opt.grad_clip), tap_model, tap_opt, lambda1=0.01, lambda2=1.0,
+                          tap_grad_clip=opt.grad_clip)
+    keys = ('c3d', 'lda', 'ind', 'soi', 'labels', 'masks')
+    history = []
+    for it in range(start, start + a.iters):
+        vids = [loader[(it * a.m_batch + j) % len(loader)] for j in range(a.m_batch)]
+        epoch = it * a.m_batch // len(loader)
+        set_lr_for_epoch(cg_opt, opt.lr, epoch)
+        set_lr_for_epoch(tap_opt, opt.lr, epoch)
+        loss = step([{k: v[k] for k in keys} for v in vids], [torch.from_numpy(v['tap_masks']) for v in vids],
+                    [torch.from_numpy(v['tap_labels']) for v in vids], [torch.from_numpy(v['w1']) for v in vids])
+        history.append(float(step.cg_loss) / a.m_batch)
+        if not a.quiet and (it % 5 == 0 or it == start + a.iters - 1):
+            print('iter %3d  JointBatchStep over %d videos: joint_loss %.4f  cg_loss %.4f  tap_loss %.4f  (means over the videos)'
+                  % (it, a.m_batch, float(loss) / a.m_batch, history[-1], float(step.tap_loss) / a.m_batch), flush=True)
+    return history
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--iters', type=int, default=20)
@@ -102,7 +131,9 @@ def main(argv=None):
     cg_model = echr_amd.CaptionGenerator(opt).to(dev)
     tap_model.train()
     cg_model.train()
-    tap_opt = ClampAdam(tap_model.parameters(), lr=opt.lr, betas=(opt.optim_alpha, opt.optim_beta), eps=opt.optim_epsilon)
+    batch_joint = a.joint and a.m_batch > 1 and not a.no_fused and not a.pre_tap          # stage 3 over a batch: fused.JointBatchStep
+    tap_opt = ClampAdam(tap_model.parameters(), lr=opt.lr, betas=(opt.optim_alpha, opt.optim_beta), eps=opt.optim_epsilon,
+                        arena=tap_model.build_arena() if batch_joint else None)
     cg_opt = ClampAdam(cg_model.parameters(), lr=opt.lr, betas=(opt.optim_alpha, opt.optim_beta), eps=opt.optim_epsilon,
                        arena=cg_model.build_arena())
     # the reference clamps the running gradient after EVERY backward (train.py:315-317); ClampAdam keeps that trajectory for any m_batch
@@ -128,7 +159,10 @@ def main(argv=None):
     history = []
     if a.pre_tap:
         return pre_tap(a, opt, dev, loader, tap_model, cg_model, cg_opt, tap_opt, tap_crit, start)
-    for it in range(start, start + a.iters):
+    iters = range(start, start + a.iters)
+    if batch_joint:
+        history, iters = joint_batch(a, opt, dev, loader, tap_model, cg_model, cg_opt, tap_opt, start), ()
+    for it in iters:
         v = loader[it % len(loader)]
         set_lr_for_epoch(cg_opt, opt.lr, it // len(loader))
         c3d, lda = torch.from_numpy(v['c3d']).to(dev), torch.from_numpy(v['lda']).to(dev)

@@ -512,6 +512,17 @@ int echr_tap_bce_fwd_ws(const float* scores, const float* masks, const float* la
                         int32_t T, int32_t K, void* stream);
 int echr_tap_bce_bwd(const float* scores, const float* masks, const float* labels, const float* w1, const float* g_loss,
                      float* g_scores, int32_t T, int32_t K, void* stream);
+/* The criterion over a multi-video batch: scores / masks / labels are the concatenated [T_tot, K] matrices, row_offset device int32 [V+1].
+ * video_loss[v] = TAPModelCriterion of video v (its own mean over T_v x K, times K), loss_sum (optional) = their sum in video order, no 1/V.
+ * w1_ld = 0: one [K] weight vector for all videos; w1_ld = K: w1 is [V, K].  partials: scratch of 64 * V floats.  Every sum runs in one
+ * fixed order; video 0 of a one-video batch equals echr_tap_bce_fwd_ws bit for bit.
+ * bwd: g_scores[t, k] = g_loss * w * d * m / T_v for the video v that owns row t (one launch over T_tot * K; row_offset[V] must be T_tot).
+ * Precondition (the offsets live on the device, the entries cannot check it): row_offset[0] = 0 and row_offset grows STRICTLY -- every video
+ * owns at least one row.  A video without rows would make its mean 0 / 0 and the gradient divide by T_v = 0. */
+int echr_tap_bce_fwd_batch(const float* scores, const float* masks, const float* labels, const float* w1, int32_t w1_ld,
+                           const int32_t* row_offset, int32_t V, int32_t K, float* video_loss, float* loss_sum, float* partials, void* stream);
+int echr_tap_bce_bwd_batch(const float* scores, const float* masks, const float* labels, const float* w1, int32_t w1_ld,
+                           const int32_t* row_offset, int32_t V, int32_t K, int32_t T_tot, const float* g_loss, float* g_scores, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Proposal selection: the index outputs of eval_utils.gettop1000 (eval_utils.py:259-287), bit-exact.
@@ -734,6 +745,14 @@ int echr_decoder_sample_batch(const echr_sample_args* a, const echr_batch_ext* x
  * nor an initial state (w_init must be NULL: CG_init_feats_type over a batch is a follow-up). */
 int64_t echr_train_step_batch_ws_floats(const echr_train_step_args* a, const echr_batch_ext* x);
 int echr_train_step_batch(const echr_train_step_args* a, const echr_batch_ext* x, const float* weight, float* video_loss, void* stream);
+/* The joint 'tap_cg' iteration over a batch: echr_train_step_batch with a->g_tap set.  g_tap [T_tot, Ht] is zero-filled by the caller and
+ * added into in place: d loss / d tap of the anchors' rows through the block-diagonal event encoder (a->dec / host_index `ind` are
+ * batch-absolute; 'ER1' adds nothing), and with 'VH' (a->vh_offset >= 0) each video's d scene vector spread over that video's OWN rows --
+ * row_offset: device int32 [V+1] (may be NULL without 'VH').  a->g_loss (device scalar) scales every gradient, g_tap included (lambda2);
+ * loss and video_loss are reported unscaled.  Not with prepared, defer_update, handover, mid_cb, forward_only nor an initial state. */
+int64_t echr_train_step_batch_tap_ws_floats(const echr_train_step_args* a, const echr_batch_ext* x);
+int echr_train_step_batch_tap(const echr_train_step_args* a, const echr_batch_ext* x, const float* weight, float* video_loss,
+                              const int32_t* row_offset, void* stream);
 
 /* Hand-over points of the LAST echr_train_step issued with handover = 1 (which: 0 = logit layer, 1 = LSTM layers): makes `stream` wait
  * until that range of flat_g is final.  0 = `stream` now waits; 1 = the call recorded no such point (a configuration without the
