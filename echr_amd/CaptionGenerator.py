@@ -9,6 +9,7 @@ every kernel addresses the video features through them.
 """
 import os
 
+import numpy as np
 import torch
 from torch import nn
 
@@ -106,21 +107,42 @@ class CaptionGenerator(nn.Module):
         `event_group_rows` (mode='eval' only; None = one block-diagonal call over all N_tot events): an integer G runs the event encoder once per
         run of `batch.event_groups(G)` -- consecutive videos with at most G events together -- so that the pair work and the workspace are bounded
         by G * N_tot instead of N_tot^2; a run of one video takes the single-video encoder with that video's own inference bounds (the tabulated
-        pair MLP of large inference calls).  The greedy decode stays ONE call over all rows.  The training backward is not grouped."""
+        pair MLP of large inference calls).  The greedy decode stays ONE call over all rows.  The training backward is not grouped.
+        `beam_size` stays 1 here: beam search over a batch is `beam_batch`."""
         if mode == 'train_rl':
             raise NotImplementedError("mode='train_rl' takes one video per call: self-critical training over a batch is a follow-up")
         if mode not in ('train', 'eval'):
             raise NotImplementedError("mode=%r: batches run 'train' and 'eval'" % (mode,))
         if beam_size != 1:
-            raise NotImplementedError('beam search takes one video per call: beam_size > 1 over a batch is a follow-up')
+            raise NotImplementedError('beam search over a batch is beam_batch(batch, beam_size) (eval_utils.caption_videos_beam): forward_batch '
+                                      'decodes greedily')
         if event_group_rows is not None and mode != 'eval':
             raise ValueError("event_group_rows is taken by mode='eval' only")
         groups = batch.event_groups(event_group_rows) if event_group_rows is not None else None
+        video, event, ev_start, ev_len, A, vid, drop = self._batch_contexts(batch, groups, need_labels=mode == 'train')
+        lm = self.lm_model
+        disjoint = EF.rows_disjoint(batch.soi)
+        if mode == 'eval':
+            with torch.no_grad():
+                if '_sample_tables' not in lm.__dict__:
+                    lm._sample_tables = {}
+                return EF.greedy_sample(video, event, batch.c3d, ev_start, ev_len, A, lm.seq_length, lm.native_params(),
+                                        table_cache=lm._sample_tables, vid=vid)
+        if lm.training and lm.ss_prob > 0.0:
+            raise NotImplementedError('scheduled sampling (ss_prob > 0) is never enabled by the reference and is not on the HIP path')
+        tokens = lm._tokens(batch.labels, batch.device)
+        arena = getattr(lm, '_echr_arena_ref', None)
+        sink = EF.GradSink(arena, lm.native_params()) if arena is not None else None
+        return EF.DecoderBatchFunction.apply(video, event, batch.c3d, ev_start, ev_len, tokens, A, disjoint, drop, sink, vid, *lm.native_params())
+
+    def _batch_contexts(self, batch, groups, need_labels=False):
+        """What forward_batch and beam_batch hand to the decoder: the checks of a batched call, then (video [V, Dv], event [N_tot, d_o],
+        ev_start, ev_len, A, vid, drop) -- the scene vectors, and the event encoder as one block-diagonal call or once per run of `groups`."""
         self._check_batch_options()
         self._require_live_decoder()
         if not batch.c3d.is_cuda:
             raise EF.L.EchrHipError('CaptionGenerator runs on the GPU only: build the batch on the device (VideoBatch.from_videos(..., device=))')
-        if mode == 'train' and batch.labels is None:
+        if need_labels and batch.labels is None:
             raise ValueError("mode='train' needs a batch with labels")
         ev_start, ev_len, ind, A = EF.event_index_tensors(batch.soi, batch.ind, batch.device, batch.c3d.shape[0])
         vid = batch.dev('vid')
@@ -138,19 +160,46 @@ class CaptionGenerator(nn.Module):
             # (index bounds 0, 0: the tabulated pair MLP of large inference calls is keyed by one video's bounds)
             event = EF.TSRMBatchFunction.apply(ech, ev_start, ev_len, vid, batch.n_videos, fm.enc_attn.group, drop, fm._grad_sink(),
                                                (1 if infer else 0, 0, 0, fm.fst_mode()), *params)
-        disjoint = EF.rows_disjoint(batch.soi)
-        if mode == 'eval':
-            with torch.no_grad():
-                if '_sample_tables' not in lm.__dict__:
-                    lm._sample_tables = {}
-                return EF.greedy_sample(video, event, batch.c3d, ev_start, ev_len, A, lm.seq_length, lm.native_params(),
-                                        table_cache=lm._sample_tables, vid=vid)
-        if lm.training and lm.ss_prob > 0.0:
-            raise NotImplementedError('scheduled sampling (ss_prob > 0) is never enabled by the reference and is not on the HIP path')
-        tokens = lm._tokens(batch.labels, batch.device)
-        arena = getattr(lm, '_echr_arena_ref', None)
-        sink = EF.GradSink(arena, lm.native_params()) if arena is not None else None
-        return EF.DecoderBatchFunction.apply(video, event, batch.c3d, ev_start, ev_len, tokens, A, disjoint, drop, sink, vid, *lm.native_params())
+        return video, event, ev_start, ev_len, A, vid, drop
+
+    def beam_batch(self, batch, beam_size, event_group_rows=None, max_rows=8192):
+        """Beam search (forward(mode='eval', beam_size=, return_score=True)) over a multi-video batch, eval mode only.  Returns (seq int64
+        [N_tot, T], logp fp32 [N_tot, T], score fp32 [N_tot], video_words host int64 [V]): video_words[v] is the width video v's decode has
+        alone -- its rows batch.event_slices[v], cut to that many columns, are what the single-video call returns for it (an all-zero
+        video_words[v] is that call's ([], [])) -- and T = max(video_words); seq and logp are [] when T == 0.
+        The contexts are forward_batch(mode='eval')'s, `event_group_rows` included.
+        `max_rows`: the decode keeps seq_length + 1 states of every one of its events * beam_size rows, so it runs once per run of
+        `batch.beam_groups(beam_size, max_rows)` -- consecutive videos with at most max_rows rows together; a video above the budget runs
+        alone, None is one decode over the batch.  Each run is one echr_decoder_beam_batch call and one host read (its video_words)."""
+        B = int(beam_size)
+        V1 = self.lm_model.vocab_size + 1
+        if not 1 <= B <= min(EF.BEAM_MAX, V1):
+            raise ValueError('beam_size must be in [1, %d], got %d' % (min(EF.BEAM_MAX, V1), B))
+        if self.training or self.lm_model.training:
+            raise ValueError('beam search is an evaluation decode: call eval() first')
+        groups = batch.event_groups(event_group_rows) if event_group_rows is not None else None
+        runs = batch.beam_groups(B, max_rows)
+        with torch.no_grad():
+            video, event, ev_start, ev_len, A, vid, _ = self._batch_contexts(batch, groups)
+            lm = self.lm_model
+            L, N, ro = lm.seq_length, batch.n_events, batch.row_offset
+            if len(runs) == 1:
+                seq, logp, score, video_words = EF.beam_search_batch(video, event, batch.c3d, ev_start, ev_len, vid, A, L, lm.native_params(), B,
+                                                                     trim=False)
+            else:
+                seq = torch.empty(N, L, device=batch.device, dtype=torch.int64)
+                logp = torch.empty(N, L, device=batch.device, dtype=torch.float32)
+                score = torch.empty(N, device=batch.device, dtype=torch.float32)
+                video_words = np.zeros(batch.n_videos, np.int64)
+                for v0, v1, e0, e1 in runs:          # run-local rows: the run's own feature rows, scene vectors and video numbers
+                    r0, r1 = int(ro[v0]), int(ro[v1])
+                    seq[e0:e1], logp[e0:e1], score[e0:e1], video_words[v0:v1] = EF.beam_search_batch(
+                        video[v0:v1], event[e0:e1], batch.c3d[r0:r1], ev_start[e0:e1] - r0, ev_len[e0:e1], vid[e0:e1] - v0, A, L,
+                        lm.native_params(), B, trim=False)
+        T = int(video_words.max())
+        if T == 0:
+            return [], [], score, video_words
+        return seq[:, :T].contiguous(), logp[:, :T].contiguous(), score, video_words
 
     def _event_context_groups(self, batch, groups, ech, ev_start, ev_len, vid, drop, params):
         """The event encoder of an inference batch, one call per run of videos (VideoBatch.event_groups), into one [N_tot, d_o] matrix.  The

@@ -215,6 +215,19 @@ class VideoBatch(object):
             v0 = v1
         return runs
 
+    def beam_groups(self, beam_size, max_rows):
+        """The runs of a beam decode (CaptionGenerator.beam_batch): consecutive videos whose events * beam_size decoder rows number at most
+        `max_rows` together, as (v0, v1, e0, e1) like event_groups.  A video above the budget is a run of its own; max_rows=None is one
+        run over the batch.  The chain keeps seq_length + 1 states per row, so the budget bounds the decode's workspace."""
+        B = int(beam_size)
+        if B < 1:
+            raise ValueError('beam_size must be positive (got %r)' % (beam_size,))
+        if max_rows is None:
+            return [(0, self.n_videos, 0, self.n_events)]
+        if int(max_rows) < 1:
+            raise ValueError('max_rows must be a positive number of decoder rows (got %r)' % (max_rows,))
+        return self.event_groups(max(1, int(max_rows) // B))
+
     def video(self, v):
         """Video v as the dict of a single-video call (local indices, its own label width and step count)."""
         s, r0, r1 = self.event_slices[v], int(self.row_offset[v]), int(self.row_offset[v + 1])

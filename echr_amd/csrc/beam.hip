@@ -210,6 +210,38 @@ __global__ __launch_bounds__(256) void beam_finalize_kernel(const int* __restric
     if (threadIdx.x == 0) words[E] = max(max(red[0], red[1]), max(red[2], red[3]));
 }
 
+// Multi-video batches (echr_decoder_beam_batch): video_words[v] = the largest words[e] among the events of video v, video_words[V] = the
+// largest of all.  Workgroup v < V owns video v: vid (per ROW, B rows per event, non-decreasing) is searched for the video's run of events
+// -- the first event whose row e*B has vid >= v up to the first with vid >= v+1 -- and the run's maximum is reduced in a fixed tree;
+// workgroup V reduces every event.  Each output element has one writer and no workgroup reads another's, so the caller need not clear
+// the vector and the result does not depend on the order the workgroups run in.  vid is only ever compared, never used as an index.
+__device__ __forceinline__ int beam_first_event_at(const int* __restrict__ vid, int B, int E, int v) {          // first e in [0, E] with vid[e*B] >= v
+    int lo = 0, hi = E;
+    while (lo < hi) {
+        const int mid = lo + (hi - lo) / 2;
+        if (vid[(long)mid * B] >= v) hi = mid; else lo = mid + 1;
+    }
+    return lo;
+}
+__global__ __launch_bounds__(256) void beam_video_words_kernel(const int* __restrict__ words, const int* __restrict__ vid, int E, int B, int V,
+                                                               int* __restrict__ video_words) {
+    __shared__ int red[4];
+    const int v = blockIdx.x;
+    const int e0 = v < V ? beam_first_event_at(vid, B, E, v) : 0;
+    const int e1 = v < V ? beam_first_event_at(vid, B, E, v + 1) : E;
+    int mx = 0;
+    for (int e = e0 + threadIdx.x; e < e1; e += 256) mx = max(mx, words[e]);
+    for (int off = 32; off > 0; off >>= 1) mx = max(mx, __shfl_xor(mx, off, 64));
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
+    __syncthreads();
+    if (threadIdx.x == 0) video_words[v] = max(max(red[0], red[1]), max(red[2], red[3]));
+}
+
+int beam_video_words(const int* words, const int* vid, int E, int B, int V, int* video_words, hipStream_t st) {
+    hipLaunchKernelGGL(beam_video_words_kernel, dim3(V + 1), dim3(256), 0, st, words, vid, E, B, V, video_words);
+    return check_launch("beam_video_words");
+}
+
 int beam_step(const float* logits, int V1, int E, int B, int t, int L, int* IT, const BeamState& bs, float* HS, float* C0, float* C1, float* C2,
               int H, hipStream_t st) {
 #define ECHR_BEAM_LAUNCH(EPW)                                                                                                              \

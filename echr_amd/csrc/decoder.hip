@@ -2321,6 +2321,18 @@ extern "C" int echr_decoder_beam(const echr_beam_args* ba, void* stream) {
     }
     return beam_finalize(bw.b, E, L, reinterpret_cast<long long*>(ba->seq), ba->seq_logp, ba->score, ba->words, st);
 }
+// multi-video batch: the same chain with the per-row scene part published for the call (chain_step's gate products read it through
+// scene_base / batch_ext), then the per-video result widths behind beam_finalize on the same stream
+extern "C" int echr_decoder_beam_batch(const echr_beam_args* ba, const echr_batch_ext* x, int32_t* video_words, void* stream) {
+    ECHR_REQUIRE(ba && video_words, "decoder_beam_batch: null args / video_words");
+    RC(check_batch(&ba->dec, x, "decoder_beam_batch"));
+    ECHR_REQUIRE(!ba->dec.h0, "decoder_beam_batch: batches start from the zero state (dec.h0 must be NULL)");
+    {
+        BatchScope scope(x);
+        RC(echr_decoder_beam(ba, stream));
+    }
+    return beam_video_words(ba->words, x->vid, ba->dec.N / ba->beam_size, ba->beam_size, x->n_videos, video_words, (hipStream_t)stream);
+}
 
 // ------------------------------------------------------------------------------------------------------
 // one decoder timestep with the state passed in and out (OldModel.get_logprobs_state, OldModel_NEW.py:133-137): the building block the

@@ -242,5 +242,7 @@ struct BeamState { float* SCORE; int* ALIVE; int* HTOK; float* HLP; int* BTOK; f
 int beam_step(const float* logits, int V1, int E, int B, int t, int L, int* IT, const BeamState& bs, float* HS, float* C0, float* C1, float* C2,
               int H, hipStream_t st);
 int beam_finalize(const BeamState& bs, int E, int L, long long* seq, float* seq_logp, float* score, int* words, hipStream_t st);
+// echr_decoder_beam_batch: video_words [V+1] = per-video maxima of words [E] (vid per row, B rows per event), then the maximum of all
+int beam_video_words(const int* words, const int* vid, int E, int B, int V, int* video_words, hipStream_t st);
 
 }  // namespace echr

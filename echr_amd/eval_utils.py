@@ -6,7 +6,8 @@ device tensors it produced are also returned by `top_proposals_device` so the ca
 round trip through python lists.
 
 `caption_videos` is the same flow over V videos in one pass: one batched SST call, one batched selection launch
-(echr_top_proposals_batch / _nms_batch, a workgroup per video), one caption pass over a VideoBatch.
+(echr_top_proposals_batch / _nms_batch, a workgroup per video), one caption pass over a VideoBatch.  `caption_videos_beam` is that flow
+with the captions decoded by beam search (CaptionGenerator.beam_batch).
 """
 import ctypes as C
 
@@ -195,12 +196,38 @@ def caption_videos(tap_model, cg_model, videos, featstamp_to_time, vocab=None, t
     'cg_prob' of the batch and 'per_video' (ind_select_list, soi_select_list, cg_select_list, seq, cg_prob of each video).
 
     Host reads per call, whatever V is: the selection counts, the selected lists (one packed copy), the decoder's step counts, and the
-    sequences / log-probs of the batch.  Beam search is not batched: use caption_video(beam_size=...) per video.
+    sequences / log-probs of the batch.  Beam search over the batch is caption_videos_beam.
 
     The validation loss of the same batch (eval_split's get_eval_loss), with labels stacked into the batch:
         logp = cg_model.forward_batch(extras['batch'], mode='train')
         cg_loss, _ = extras['batch'].criterion(cg_crit, logp)
         tap_loss, _ = utils.tap_criterion_batch(tap_crit, extras['pred_proposals'], tap_masks, tap_labels, w1, extras['row_offset'])"""
+    return _caption_videos_checked(tap_model, cg_model, videos, featstamp_to_time, vocab, topN, nms_threshold, val_score_thres, flag_eval_what,
+                                   event_group_rows)
+
+
+def caption_videos_beam(tap_model, cg_model, videos, featstamp_to_time, beam_size, vocab=None, topN=1000, nms_threshold=0.0, val_score_thres=0.0,
+                        flag_eval_what='tap_cg', event_group_rows=EVENT_GROUP_ROWS, max_rows=8192):
+    """`caption_videos` with the captions decoded by beam search (the reference's eval.py --beam_size): the same SST call, selection call
+    and VideoBatch, then CaptionGenerator.beam_batch(batch, beam_size, event_group_rows, max_rows) instead of the greedy pass.  `max_rows`
+    bounds the decode's workspace: it runs once per run of consecutive videos with at most that many events * beam_size rows (None: once).
+
+    vid_infos[v] is what caption_video(beam_size=) returns for video v alone: seq / cg_prob cut to the video's own width
+    video_words[v], sentence_confidence the beam score (the sum of the caption's token log-probs, <eos> included).  A video whose
+    results are all empty (video_words[v] == 0) gets [] and per_video[v]['seq'] None.  extras additionally carries 'score' [N_tot]
+    (device) and 'video_words' (host int64, one entry per kept video).
+
+    Host reads per call do not grow with V: the selection reads, one video_words read per run, the batch's sequences and scores."""
+    V1 = cg_model.lm_model.vocab_size + 1
+    if not 1 <= int(beam_size) <= min(EF.BEAM_MAX, V1):
+        raise ValueError('beam_size must be in [1, %d], got %r' % (min(EF.BEAM_MAX, V1), beam_size))
+    return _caption_videos_checked(tap_model, cg_model, videos, featstamp_to_time, vocab, topN, nms_threshold, val_score_thres, flag_eval_what,
+                                   event_group_rows, int(beam_size), max_rows)
+
+
+def _caption_videos_checked(tap_model, cg_model, videos, featstamp_to_time, vocab, topN, nms_threshold, val_score_thres, flag_eval_what,
+                            event_group_rows, beam=None, max_rows=None):
+    """The argument checks of caption_videos / caption_videos_beam, then _caption_videos under no_grad with both models in eval mode."""
     if flag_eval_what not in ('tap_cg', 'tap', 'cg'):
         raise ValueError("flag_eval_what=%r: caption_videos runs 'tap_cg', 'tap' and 'cg'" % (flag_eval_what,))
     videos = list(videos)
@@ -221,18 +248,20 @@ def caption_videos(tap_model, cg_model, videos, featstamp_to_time, vocab=None, t
     try:
         with torch.no_grad():
             return _caption_videos(tap_model, cg_model, videos, featstamp_to_time, vocab, topN, nms_threshold, val_score_thres, flag_eval_what,
-                                   event_group_rows, V, dev, rows)
+                                   event_group_rows, V, dev, rows, beam, max_rows)
     finally:
         tap_model.rnn.dropout = sst_dropout
         cg_model.train(cg_training)
 
 
 def _caption_videos(tap_model, cg_model, videos, featstamp_to_time, vocab, topN, nms_threshold, val_score_thres, flag_eval_what, event_group_rows,
-                    V, dev, rows):
+                    V, dev, rows, beam=None, max_rows=None):
     c3d_all = torch.cat([_to_dev(v['c3d'], dev) for v in videos], 0)
     lda_all = torch.stack([_to_dev(v['lda'], dev).reshape(-1) for v in videos], 0)
     tap_all, scores = tap_model.forward_batch(c3d_all, rows)
     extras = dict(tap_feats=tap_all, pred_proposals=scores, row_offset=rows, selection=None, batch=None, kept=[], seq=None, cg_prob=None)
+    if beam is not None:
+        extras.update(score=None, video_words=None)
     # ---- events per video: (soi [N_v,2] local, tap_prob [N_v], timestamps) ----
     if flag_eval_what == 'cg':
         sois = [np.asarray(v['soi'], dtype=np.int64).reshape(-1, 2) for v in videos]
@@ -285,6 +314,22 @@ def _caption_videos(tap_model, cg_model, videos, featstamp_to_time, vocab, topN,
         for v in kept:
             n = len(sois[v])
             vid_infos[v] = _records([0] * n, stamps[v], [0] * n, probs[v])
+        return vid_infos, extras
+    if beam is not None:
+        # beam search: the per-video widths come back with the decode (one read per run), the confidence is the beam score
+        seq, cg_prob, score, video_words = cg_model.beam_batch(batch, beam, event_group_rows=event_group_rows, max_rows=max_rows)
+        extras['score'], extras['video_words'] = score, video_words
+        if len(seq) == 0:
+            return vid_infos, extras
+        extras['seq'], extras['cg_prob'] = seq, cg_prob
+        seq_h, score_h = seq.cpu().numpy(), score.cpu().numpy().astype('float')
+        for i, v in enumerate(kept):
+            s, width = batch.event_slices[i], int(video_words[i])
+            if width == 0:
+                continue
+            per_video[v]['seq'], per_video[v]['cg_prob'] = seq[s, :width], cg_prob[s, :width]
+            sents = utils.decode_sequence(vocab, seq[s, :width]) if vocab is not None else [row[row > 0].tolist() for row in seq_h[s, :width]]
+            vid_infos[v] = _records(sents, stamps[v], score_h[s], probs[v])
         return vid_infos, extras
     seq, cg_prob = cg_model.forward_batch(batch, mode='eval', event_group_rows=event_group_rows)
     if len(seq) == 0:

@@ -670,7 +670,8 @@ def beam_search(video, event, c3d, ev_start, ev_len, A, seq_length, params, beam
     ev_start_r = rep(ev_start.to(torch.int32))
     ev_len_r = rep(ev_len.to(torch.int32))
     h0_r = rep(_f32c(h0)) if h0 is not None else None
-    a = _dec_args(ps, c3d, ev_start_r, ev_len_r, rep(event), video, None, A, seq_length, None, None, h0=h0_r)
+    event_r = rep(event)          # (named, like the others: the library holds its raw pointer until the host read below)
+    a = _dec_args(ps, c3d, ev_start_r, ev_len_r, event_r, video, None, A, seq_length, None, None, h0=h0_r)
     ws = torch.empty(lib.echr_decoder_ws_floats(C.byref(a)), device=dev, dtype=torch.float32)
     a.ws = L.ptr(ws)
     seq = torch.empty(N, seq_length, device=dev, dtype=torch.int64)
@@ -686,6 +687,57 @@ def beam_search(video, event, c3d, ev_start, ev_len, A, seq_length, params, beam
     if T == 0:
         return [], [], score
     return seq[:, :T].contiguous(), slp[:, :T].contiguous(), score
+
+
+def beam_search_batch(video, event, c3d, ev_start, ev_len, vid, A, seq_length, params, beam_size, trim=True):
+    """`beam_search` over the events of a multi-video batch in one decode (echr_decoder_beam_batch): `video` is [V, Dv], `vid` int32 [N]
+    (device, non-decreasing) names each event's video, `c3d` / `ev_start` are the batch's concatenated rows and batch-absolute starts.
+    event, ev_start, ev_len and vid are repeated per slot; batches start from the zero state.
+
+    Returns (seq int64 [N,T], logp fp32 [N,T], score fp32 [N], video_words): video_words is a host int64 [V] with the longest result's
+    word count of each video -- the width that video's decode has alone -- and T = max(video_words).  A video's rows are zero from its
+    own width on in seq; its logp may hold the <eos> log-prob of a full-width row in that column.  seq and logp are [] when T == 0.  One
+    host read (video_words) per call.  trim=False returns seq and logp at their full width [N, seq_length] whatever T is (a caller that
+    assembles several decodes into one result, CaptionGenerator.beam_batch, cuts once at the end)."""
+    lib = L.load()
+    ps = [_f32c(p) for p in params]
+    B = int(beam_size)
+    V1 = ps[0].shape[0]
+    if not 1 <= B <= min(BEAM_MAX, V1):
+        raise ValueError('beam_size must be in [1, %d] (and <= the vocabulary size + 1), got %d' % (min(BEAM_MAX, V1), B))
+    if video.dim() != 2:
+        raise ValueError('video must be [V, Dv], one scene vector per video (got %s)' % (tuple(video.shape),))
+    N, V = event.shape[0], video.shape[0]
+    if vid.dim() != 1 or vid.numel() != N or ev_start.numel() != N or ev_len.numel() != N:
+        raise ValueError('vid, ev_start and ev_len need one entry per event (%d)' % N)
+    if not 1 <= V <= N:
+        raise ValueError('a batch has between 1 video and one video per event (V = %d, N = %d)' % (V, N))
+    video, event, c3d = _f32c(video), _f32c(event), _f32c(c3d)
+    dev = event.device
+    rep = lambda x: x.repeat_interleave(B, dim=0).contiguous()          # event-major: row n*B + j is slot j of event n
+    # (named: the library reads these through raw pointers, so they must outlive the call's kernels -- until the host read below)
+    vid_r, ev_start_r, ev_len_r, event_r = rep(vid.to(torch.int32)), rep(ev_start.to(torch.int32)), rep(ev_len.to(torch.int32)), rep(event)
+    a = _dec_args(ps, c3d, ev_start_r, ev_len_r, event_r, video, None, A, seq_length, None, None)
+    ws = torch.empty(lib.echr_decoder_ws_floats(C.byref(a)), device=dev, dtype=torch.float32)
+    a.ws = L.ptr(ws)
+    seq = torch.empty(N, seq_length, device=dev, dtype=torch.int64)
+    slp = torch.empty(N, seq_length, device=dev, dtype=torch.float32)
+    score = torch.empty(N, device=dev, dtype=torch.float32)
+    words = torch.empty(N + 1, device=dev, dtype=torch.int32)
+    vwords = torch.empty(V + 1, device=dev, dtype=torch.int32)
+    ba = L.BeamArgs(a, B, seq_length, L.ptr(seq, torch.int64), L.ptr(slp), L.ptr(score), L.ptr(words, torch.int32), None)
+    wsb = torch.empty(lib.echr_beam_ws_floats(C.byref(ba)), device=dev, dtype=torch.float32)
+    ba.ws_beam = L.ptr(wsb)
+    x, xws = batch_ext(vid_r, video, H=ps[6].shape[1])
+    L.check(lib.echr_decoder_beam_batch(C.byref(ba), C.byref(x), L.ptr(vwords, torch.int32), L.stream_ptr()), 'decoder_beam_batch')
+    vw = vwords.cpu().numpy().astype(np.int64)          # the only device->host sync of the whole decode
+    L.check(lib.echr_check_async(), 'decoder_beam_batch')
+    T = int(vw[V])
+    if not trim:
+        return seq, slp, score, vw[:V]
+    if T == 0:
+        return [], [], score, vw[:V]
+    return seq[:, :T].contiguous(), slp[:, :T].contiguous(), score, vw[:V]
 
 
 def decoder_step(it, video, event, c3d, ev_start, ev_len, A, state, params, drop=None):

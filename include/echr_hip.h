@@ -708,7 +708,9 @@ int echr_train_step_clip(const echr_train_step_args* a, const echr_clip_step_arg
  *     sum(mask_v) + 1e-6 -- the caller passes the per-position weight w[n,t] = mask[n,t] / (sum(mask of video vid[n]) + 1e-6) and the
  *     library applies it with denominator 1; gradients are the SUM over the videos (train.py:281-283,313-317 with m_batch = V), then one
  *     clamp + Adam;
- *   - dropout: one forward-call counter per batched call, every site keyed by the batch-global element index.
+ *   - dropout: one forward-call counter per batched call, every site keyed by the batch-global element index;
+ *   - decoding (echr_decoder_sample_batch greedy, echr_decoder_beam_batch beam search): every event decodes as it does alone; a
+ *     single-video decode stops at the width of ITS longest caption, so the beam entry also reports that width per video.
  * Every entry takes the arguments of its single-video sibling plus this extension; the sibling's structs are unchanged.
  * ---------------------------------------------------------------------------------------------- */
 typedef struct {
@@ -738,6 +740,15 @@ int echr_decoder_fwd_batch(const echr_dec_args* a, const echr_dropout* drop, con
 int echr_decoder_bwd_batch(const echr_dec_args* a, const echr_dec_grads* g, const echr_dropout* drop, const echr_batch_ext* x, void* stream);
 /* Greedy decode of a batch (a->multinomial must be 0): echr_decoder_sample with per-row scene vectors. */
 int echr_decoder_sample_batch(const echr_sample_args* a, const echr_batch_ext* x, void* stream);
+/* Beam search over a batch: echr_decoder_beam with per-row scene vectors.  a->dec.N = events * beam_size event-major rows as there;
+ * x->vid is a device [dec.N] array in which the B rows of an event carry that event's video (non-decreasing), x->video [V, Dv], x->ws
+ * echr_batch_ws_floats(dec.N, V, H) floats; dec.h0 must be NULL (batches start from the zero state) and rows_disjoint 0.  seq, seq_logp,
+ * score and words are echr_decoder_beam's; echr_beam_ws_floats sizes ws_beam.
+ * video_words: device int32 [V+1] out, written behind the result on the same stream -- video_words[v] = the largest word count among
+ * the events of video v (the contiguous run of events e whose row e*B has vid == v; 0 for a video without an event), video_words[V] =
+ * the maximum over the batch.  Every element is written (no zero fill by the caller) and none is read by the device: the host reads
+ * this vector once, instead of words[N/B], and cuts every video's rows to the width that video alone would have produced. */
+int echr_decoder_beam_batch(const echr_beam_args* a, const echr_batch_ext* x, int32_t* video_words, void* stream);
 /* echr_train_step over a batch.  Criterion weights as in echr_train_step_rw: `weight` device [N,S] with host_nll = 0, or behind the mask
  * in host_index with host_nll = 1 (then weight = NULL).  host_index additionally ENDS with vid[N]; x->vid and x->ws are ignored (the
  * library points them at its staged copy / its own workspace).  loss[0] = the summed loss, loss[1] = sum(mask) over the batch;
