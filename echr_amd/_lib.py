@@ -136,6 +136,8 @@ SYMBOLS = [
     ('echr_persist_softmax_branch', i32, []),
     ('echr_async_skipped_updates', i64, []),
     ('echr_gemm_f32', i32, [C.POINTER(GemmDesc), C.c_void_p]),
+    ('echr_gemm_grouped', i32, [C.POINTER(GemmDesc), i32, C.c_void_p]),
+    ('echr_gemm_skinny_nt', i32, [c_f, i64, c_f, i64, c_f, c_f, i64, i32, i32, i32, C.c_void_p]),
     ('echr_event_pool_gather_fwd', i32, [c_f, c_f, c_f, c_f, c_f, c_f, i32, i32, i32, C.c_void_p]),
     ('echr_event_pool_gather_bwd', i32, [c_f, c_f, c_f, i32, i32, i32, C.c_void_p]),
     ('echr_init_state_fwd', i32, [C.POINTER(InitStateArgs), C.c_void_p]),
@@ -198,6 +200,7 @@ SYMBOLS = [
     ('echr_tap_bce_bwd_batch', i32, [c_f, c_f, c_f, c_f, i32, c_f, i32, i32, i32, c_f, c_f, C.c_void_p]),
     ('echr_h2_bytes', i64, [i32, i32]),
     ('echr_h2_pack', i32, [c_f, i32, i32, i64, i64, C.c_void_p, C.c_void_p]),
+    ('echr_h2_pack_gather', i32, [c_f, i32, i32, i64, i64, c_f, C.c_void_p, C.c_void_p]),
     ('echr_top_proposals', i32, [c_f, c_f, i32, i32, i32, f32, c_f, c_f, c_f, c_f, C.c_void_p]),
     ('echr_top_proposals_nms', i32, [c_f, i32, i32, i32, C.c_double, c_f, c_f, c_f, c_f, C.c_void_p]),
     ('echr_top_proposals_batch', i32, [c_f, c_f, c_f, i32, i32, i32, i32, f32, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, C.c_void_p]),

@@ -46,7 +46,8 @@ struct GemmParams {
     int vecA, vecB;
     int diag;                  // diagnostic ablation of the h2 kernels (config diag_skip bits 64 / 128; results WRONG): 1 = loads only, 2 = compute only
     // grouped launch: up to GEMM_MAXG problems in one grid (blockIdx.z = group * split_k + k-slice); per-group operands.  The problems share
-    // K and the epilogue mode; h2 problems may differ in M and N (the grid is sized for the largest, smaller ones retire their spare tiles)
+    // K and the epilogue mode; h2 problems may differ in M and N: the grid is sized for the largest, and a workgroup whose tile lies outside
+    // its own problem (m0 >= M or n0 >= N after select_group) returns before any load or barrier -- in every kernel that takes a grouped launch
     int ngroup;
     const float* gA[GEMM_MAXG]; const float* gB[GEMM_MAXG]; float* gC[GEMM_MAXG];
     long gsbk[GEMM_MAXG], gsbn[GEMM_MAXG], gldc[GEMM_MAXG];
@@ -671,6 +672,7 @@ __global__ __launch_bounds__((BM / 64) * (128 / WN) * 64, (NS == 2 && BM == 128)
     const int x = blockIdx.x & 7, sl = blockIdx.x >> 3;
     const int mb = (x / p.xcd_n) * p.xr_m + sl / p.xr_n, nb = (x % p.xcd_n) * p.xr_n + sl % p.xr_n;
     if (mb >= p.tiles_m || nb >= p.tiles_n) return;
+    if (mb * BM >= p.M || nb * 128 >= p.N) return;          // grouped problems smaller than the largest of the launch: no tile here, and no B chunk to read
     const int ks = z;
     const int KT = (p.K + BK - 1) / BK;
     const int kt0 = ks * p.k_tiles_per_split, kt1 = min(KT, kt0 + p.k_tiles_per_split);
@@ -818,6 +820,7 @@ __global__ __launch_bounds__(512, 2) void gemm_h2m16_kernel(GemmParams pin) {
     const int x = blockIdx.x & 7, sl = blockIdx.x >> 3;
     const int mb = (x / p.xcd_n) * p.xr_m + sl / p.xr_n, nb = (x % p.xcd_n) * p.xr_n + sl % p.xr_n;
     if (mb >= p.tiles_m || nb >= p.tiles_n) return;
+    if (mb * 128 >= p.M || nb * 128 >= p.N) return;         // grouped problems smaller than the largest of the launch (see gemm_h2_kernel)
     const int ks = z;
     const int KT = (p.K + BK - 1) / BK;
     const int kt0 = ks * p.k_tiles_per_split, kt1 = min(KT, kt0 + p.k_tiles_per_split);
@@ -1398,6 +1401,23 @@ extern "C" int64_t echr_h2_bytes(int32_t rows, int32_t cols) { return echr::h2_b
 extern "C" int echr_h2_pack(const float* src, int32_t rows, int32_t cols, int64_t s_row, int64_t s_col, void* dst, void* stream) {
     ECHR_REQUIRE(src && dst && rows > 0 && cols > 0, "h2_pack: bad arguments");
     return echr::h2_pack(src, rows, cols, (long)s_row, (long)s_col, dst, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int echr_h2_pack_gather(const float* src, int32_t rows, int32_t cols, int64_t s_row, int64_t s_col, const int32_t* gather, void* dst, void* stream) {
+    ECHR_REQUIRE(src && dst && gather && rows > 0 && cols > 0, "h2_pack_gather: bad arguments");
+    echr::H2PackJob j{src, static_cast<unsigned char*>(dst), rows, cols, (long)s_row, (long)s_col, gather};
+    return echr::h2_pack_multi(&j, 1, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int echr_gemm_grouped(const echr_gemm_desc* ds, int32_t n, void* stream) {
+    if (!ds) { echr::set_error("echr_gemm_grouped: null descriptors"); return -22; }
+    return echr::gemm_grouped(ds, n, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int echr_gemm_skinny_nt(const float* A, int64_t lda, const float* W, int64_t ldw, const float* bias, float* C, int64_t ldc, int32_t M, int32_t Nc,
+                                   int32_t K, void* stream) {
+    ECHR_REQUIRE(A && W && C, "gemm_skinny_nt: null operand");
+    return echr::gemm_skinny_nt(A, (long)lda, W, (long)ldw, bias, C, (long)ldc, M, Nc, K, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int echr_gemm_f32(const echr_gemm_desc* d, void* stream) {

@@ -102,6 +102,18 @@ typedef struct {
 } echr_gemm_desc;
 
 int echr_gemm_f32(const echr_gemm_desc* d, void* stream);
+/* Test-facing entries of internal launch forms (tests/test_gpu_gemm_contract.py); the product path calls them inside the library.
+ * echr_gemm_grouped: ds[0..n-1], 1 <= n <= 8 problems in ONE launch.  Every problem has batch = 1 and act = NONE, and all of them share K, sam / sak,
+ * which of sbk / sbn is 1, alpha, beta, split_k, algo, rowmap_mod, add_mod and ld_add; M and N are shared too unless every problem is
+ * ECHR_GEMM_H2 (h2 problems may differ in M and N).  A, B, C, sbk / sbn, ldc, bias, bias2 and addend are per problem.  Problems may share
+ * C only in accumulate mode: split_k = -1, beta = 1, K > 32 (they add with fp32 atomics; under echr_config_set("deterministic", 1) they run
+ * one after the other instead, bit-identical run to run). */
+int echr_gemm_grouped(const echr_gemm_desc* ds, int32_t n, void* stream);
+/* echr_gemm_skinny_nt: C[M, Nc] = A[M, K] . W[Nc, K]^T + bias (bias may be null) as one stream over a very tall A.  Requires M >= 4096,
+ * 1 <= Nc <= 16, K = 256 or 512, lda % 4 == 0, ldw % 4 == 0, A and W 16-byte aligned, and the "gemm_skinny" switch on; anything else
+ * returns -22. */
+int echr_gemm_skinny_nt(const float* A, int64_t lda, const float* W, int64_t ldw, const float* bias, float* C, int64_t ldc, int32_t M, int32_t Nc,
+                        int32_t K, void* stream);
 
 /* h2 operands: a logical [rows x cols] fp32 operand (cols = the contraction axis) rewritten as two fp16 planes with one shared
  * power-of-two scale per row and 256-wide k segment (8 blocks of 32): xs = x * 2^(14 - floor(log2 blockmax)), h1 = fp16(xs), h2 = fp16(xs - h1).
@@ -111,6 +123,10 @@ int echr_gemm_f32(const echr_gemm_desc* d, void* stream);
  * without a separate transpose).  dst: echr_h2_bytes(rows, cols) bytes, 16-byte aligned. */
 int64_t echr_h2_bytes(int32_t rows, int32_t cols);
 int echr_h2_pack(const float* src, int32_t rows, int32_t cols, int64_t s_row, int64_t s_col, void* dst, void* stream);
+/* The same with a gathered strided axis (test-facing entry of the packs the decoder issues over token rows): index i of the axis whose stride
+ * is NOT 1 -- operand rows when s_col == 1, k when s_row == 1 -- is read from gather[i] (rows resp. cols device int32 entries, each a
+ * valid index of the source; entries may repeat). */
+int echr_h2_pack_gather(const float* src, int32_t rows, int32_t cols, int64_t s_row, int64_t s_col, const int32_t* gather, void* dst, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Dropout configuration shared by all training-mode entry points (counter-based Philox-4x32-10;
