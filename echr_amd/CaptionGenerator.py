@@ -110,7 +110,8 @@ class CaptionGenerator(nn.Module):
         pair MLP of large inference calls).  The greedy decode stays ONE call over all rows.  The training backward is not grouped.
         `beam_size` stays 1 here: beam search over a batch is `beam_batch`."""
         if mode == 'train_rl':
-            raise NotImplementedError("mode='train_rl' takes one video per call: self-critical training over a batch is a follow-up")
+            raise NotImplementedError("mode='train_rl' takes one video per call: self-critical training over a batch is "
+                                      "train_rl_batch(batch) (one call: fused.SelfCriticalBatchStep)")
         if mode not in ('train', 'eval'):
             raise NotImplementedError("mode=%r: batches run 'train' and 'eval'" % (mode,))
         if beam_size != 1:
@@ -200,6 +201,45 @@ class CaptionGenerator(nn.Module):
         if T == 0:
             return [], [], score, video_words
         return seq[:, :T].contiguous(), logp[:, :T].contiguous(), score, video_words
+
+    def train_rl_batch(self, batch, gen_result=None, seed=None):
+        """Self-critical training (forward(mode='train_rl'), CaptionGenerator.py:32-37) over a multi-video batch: the reference's m_batch = V
+        protocol in one pass.  One training-mode event context under the call's dropout state; the multinomial decode of all N_tot rows with
+        the decoder's dropout active under that state (echr_decoder_sample_train_batch; draws keyed by `seed`, default the model's next
+        sample seed); the greedy baseline in eval mode without a graph; then the teacher-forced recompute on [0 | gen | 0] under the SAME
+        state, gathered at the tokens, with the autograd edges of forward_batch('train').
+        Returns (gen_result int64 [N_tot, T], sample_logprobs [N_tot, T], greedy_res, video_words host int64 [V]): video_words[v] is the
+        width video v's own call cuts its sample at and T = max(video_words) -- rows batch.event_slices[v] cut to video_words[v] columns
+        are what forward(mode='train_rl') returns for that video.  Apply the criterion with `batch.reward_criterion(crit, sample_logprobs,
+        gen_result, reward, video_words)`.  gen_result and sample_logprobs are [] when T == 0.
+        `gen_result` [N_tot, >= T]: score these captions instead of drawing them.  The batch need not carry labels."""
+        video, event, ev_start, ev_len, A, vid, drop = self._batch_contexts(batch, None)
+        lm = self.lm_model
+        if lm.training and lm.ss_prob > 0.0:
+            raise NotImplementedError('scheduled sampling (ss_prob > 0) is never enabled by the reference and is not on the HIP path')
+        if gen_result is None:
+            seed = lm._sample_seed() if seed is None else int(seed)
+            with torch.no_grad():
+                gen, _, video_words = EF.sample_train_batch(video, event.detach(), batch.c3d, ev_start, ev_len, vid, A, lm.seq_length,
+                                                            lm.native_params(), drop, seed=seed)
+        else:
+            video_words = batch.caption_widths(gen_result)
+            gen = torch.as_tensor(gen_result)[:, :int(video_words.max())].to(device=batch.device, dtype=torch.int64).contiguous()
+        with torch.no_grad():
+            if '_sample_tables' not in lm.__dict__:
+                lm._sample_tables = {}
+            greedy_res, _ = EF.greedy_sample(video, event.detach(), batch.c3d, ev_start, ev_len, A, lm.seq_length, lm.native_params(),
+                                             table_cache=lm._sample_tables, vid=vid)
+        if isinstance(gen, list) or gen.numel() == 0:
+            return [], [], greedy_res, video_words          # every row drew <eos> first (OldModel.sample returns [] then, :186-187)
+        N, T = gen.shape
+        labels = torch.zeros(N, T + 2, dtype=torch.int64, device=gen.device)
+        labels[:, 1:T + 1] = gen
+        arena = getattr(lm, '_echr_arena_ref', None)
+        sink = EF.GradSink(arena, lm.native_params()) if arena is not None else None
+        logp = EF.DecoderBatchFunction.apply(video, event, batch.c3d, ev_start, ev_len, lm._tokens(labels, batch.device), A,
+                                             EF.rows_disjoint(batch.soi), drop, sink, vid, *lm.native_params())
+        return gen, EF.GatherTokens.apply(logp, gen), greedy_res, video_words
 
     def _event_context_groups(self, batch, groups, ech, ev_start, ev_len, vid, drop, params):
         """The event encoder of an inference batch, one call per run of videos (VideoBatch.event_groups), into one [N_tot, d_o] matrix.  The

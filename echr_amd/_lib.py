@@ -221,6 +221,7 @@ SYMBOLS = [
     ('echr_decoder_bwd_batch', i32, [C.POINTER(DecArgs), C.POINTER(DecGrads), C.POINTER(Dropout), C.POINTER(BatchExt), C.c_void_p]),
     ('echr_decoder_sample_batch', i32, [C.POINTER(SampleArgs), C.POINTER(BatchExt), C.c_void_p]),
     ('echr_decoder_beam_batch', i32, [C.POINTER(BeamArgs), C.POINTER(BatchExt), c_f, C.c_void_p]),
+    ('echr_decoder_sample_train_batch', i32, [C.POINTER(SampleArgs), C.POINTER(Dropout), C.POINTER(BatchExt), c_f, C.c_void_p]),
     ('echr_train_step_batch_ws_floats', i64, [C.POINTER(TrainStepArgs), C.POINTER(BatchExt)]),
     ('echr_train_step_batch', i32, [C.POINTER(TrainStepArgs), C.POINTER(BatchExt), c_f, c_f, C.c_void_p]),
     ('echr_train_step_batch_tap_ws_floats', i64, [C.POINTER(TrainStepArgs), C.POINTER(BatchExt)]),

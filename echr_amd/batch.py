@@ -271,3 +271,71 @@ class VideoBatch(object):
         for s in self.event_slices:
             w[s] = mk[s] / (mk[s].sum(dtype=np.float32) + np.float32(1e-6))
         return w
+
+    # ---- self-critical training (CaptionGenerator.train_rl_batch, fused.SelfCriticalBatchStep) --------------------------------------
+    def caption_widths(self, gen_result):
+        """video_words (host int64 [V]) of sampled captions gen_result [N_tot, T]: the largest number of non-zero tokens among the rows of
+        each video -- the width at which that video's own call cuts its output (it stops at the first step after which none of its rows is
+        unfinished, OldModel_NEW.py:179-180)."""
+        g = _np(gen_result, np.int64)
+        if g.ndim != 2 or g.shape[0] != self.n_events:
+            raise ValueError('gen_result must be [%d events, T] (got %s)' % (self.n_events, g.shape))
+        words = (g != 0).sum(1)
+        return np.asarray([int(words[s].max()) for s in self.event_slices], dtype=np.int64)
+
+    def _reward_matrix(self, reward, N, T):
+        r = _np(reward, np.float32)
+        if r.ndim == 1:
+            r = np.repeat(r[:, None], T, 1)
+        if r.shape[0] != N or r.ndim != 2 or r.shape[1] < T:
+            raise ValueError('reward must be [N_tot, T] or [N_tot] (got %s for gen_result %s)' % (r.shape, (N, T)))
+        return r[:, :T]
+
+    def reward_criterion(self, crit, sample_logprobs, gen_result, reward, video_words):
+        """RewardCriterion per video: `crit` on the rows of video v and its first video_words[v] columns -- the tensors that video's own
+        call returns, so its longest row's <eos> position stays outside the criterion -- each video with its own normaliser sum(mask_v), no
+        1/V.  A video of width 0 is skipped (its own call returns []: loss 0, no gradient).  `reward`: [N_tot, T] or [N_tot].
+        Returns (sum over the videos, per-video losses [V])."""
+        vw = np.asarray(video_words, dtype=np.int64).reshape(-1)
+        if len(vw) != self.n_videos:
+            raise ValueError('video_words needs one width per video (%d), got %d' % (self.n_videos, len(vw)))
+        gen = torch.as_tensor(gen_result)
+        N, T = gen.shape
+        if int(vw.max()) > T or sample_logprobs.shape[0] != N or sample_logprobs.shape[1] < int(vw.max()):
+            raise ValueError('video_words %s exceed gen_result %s / sample_logprobs %s' % (vw.tolist(), (N, T), tuple(sample_logprobs.shape)))
+        r = torch.from_numpy(np.ascontiguousarray(self._reward_matrix(reward, N, T)))
+        per = []
+        for s, w in zip(self.event_slices, vw.tolist()):
+            if w == 0:
+                per.append(sample_logprobs.new_zeros(()))
+            else:
+                per.append(crit(sample_logprobs[s, :w].contiguous(), gen[s, :w].contiguous(), r[s, :w].contiguous()))
+        per = torch.stack(per)
+        return per.sum(), per
+
+    def reward_weights(self, gen_result, reward, video_words):
+        """The criterion of reward_criterion as the one-call step takes it (host arrays): labels int64 [N_tot, T+2] = [0 | gen | 0] (T+1
+        teacher-forced steps), mask float32 [N_tot, T+1] -- RewardCriterion's [1 | gen > 0][:, :-1], zero from the row's video's own width
+        on (at the batch's width the longest row of a narrower video would otherwise gain its <eos> position) -- and
+        w[n, t] = reward[n, t] * mask[n, t] / sum(mask of video vid[n]): the loss is sum(-logp[target] * w) with denominator 1."""
+        g = _np(gen_result, np.int64)
+        vw = np.asarray(video_words, dtype=np.int64).reshape(-1)
+        if g.ndim != 2 or g.shape[0] != self.n_events or len(vw) != self.n_videos:
+            raise ValueError('gen_result must be [%d events, T] and video_words [%d]' % (self.n_events, self.n_videos))
+        T = int(vw.max()) if len(vw) else 0
+        if T > g.shape[1]:
+            raise ValueError('video_words %s exceed gen_result %s' % (vw.tolist(), g.shape))
+        g = g[:, :T]
+        N = g.shape[0]
+        r = self._reward_matrix(reward, N, T)
+        labels = np.zeros((N, T + 2), np.int64)
+        labels[:, 1:T + 1] = g
+        mask = np.zeros((N, T + 1), np.float32)
+        w = np.zeros((N, T + 1), np.float32)
+        for s, wv in zip(self.event_slices, vw.tolist()):
+            if wv == 0:
+                continue
+            mask[s, 0] = 1.0
+            mask[s, 1:wv] = g[s, :wv - 1] > 0
+            w[s, :wv] = r[s, :wv] * mask[s, :wv] / mask[s, :wv].sum(dtype=np.float32)
+        return labels, mask, w

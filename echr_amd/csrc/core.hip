@@ -392,18 +392,26 @@ int vec_mat(const float* x, const float* W, long ldw, float* out, int M, int N, 
 // out[c] = sum_k x[k] * W[c, k] + b1[c] + b2[c]  (one input row against N weight rows of K <= a few hundred contiguous floats): one WAVE per
 // output (the lanes stride k, one reduction) -- the scene-context gate bias W_ih2[:, E:] . video + b_ih2 + b_hh2 without a GEMM launch.  (A
 // quarter wave per output walked 25 dependent loads: 14 us on the decoder's prepare chain.)
-__global__ __launch_bounds__(256) void row_matvec_kernel(const float* __restrict__ x, const float* __restrict__ W, long ldw, const float* __restrict__ b1,
-                                                         const float* __restrict__ b2, float* __restrict__ out, int N, int K) {
+// out[m, c] = x[m, :] . W[c, :] + b1[c] + b2[c] for the M vectors x [M, ldx] (blockIdx.y), one wave per output element; M = 1 is row_matvec.
+// Every row is computed by the same code whatever M is: a video's scene part is bit-identical alone and in a batch.
+__global__ __launch_bounds__(256) void rows_matvec_kernel(const float* __restrict__ x, long ldx, const float* __restrict__ W, long ldw,
+                                                          const float* __restrict__ b1, const float* __restrict__ b2, float* __restrict__ out, long ldo,
+                                                          int N, int K) {
     const int c = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const float* xr = x + (long)blockIdx.y * ldx;
     float s = 0.f;
     if (c < N)
-        for (int k = lane; k < K; k += 64) s = fmaf(x[k], W[(long)c * ldw + k], s);
+        for (int k = lane; k < K; k += 64) s = fmaf(xr[k], W[(long)c * ldw + k], s);
     s = wave_sum(s);
-    if (c < N && lane == 0) out[c] = s + (b1 ? b1[c] : 0.f) + (b2 ? b2[c] : 0.f);
+    if (c < N && lane == 0) out[(long)blockIdx.y * ldo + c] = s + (b1 ? b1[c] : 0.f) + (b2 ? b2[c] : 0.f);
+}
+int rows_matvec(const float* x, long ldx, const float* W, long ldw, const float* b1, const float* b2, float* out, long ldo, int M, int N, int K,
+                hipStream_t st) {
+    hipLaunchKernelGGL(rows_matvec_kernel, dim3((N + 3) / 4, M), dim3(256), 0, st, x, ldx, W, ldw, b1, b2, out, ldo, N, K);
+    return check_launch("rows_matvec");
 }
 int row_matvec(const float* x, const float* W, long ldw, const float* b1, const float* b2, float* out, int N, int K, hipStream_t st) {
-    hipLaunchKernelGGL(row_matvec_kernel, dim3((N + 3) / 4), dim3(256), 0, st, x, W, ldw, b1, b2, out, N, K);
-    return check_launch("row_matvec");
+    return rows_matvec(x, K, W, ldw, b1, b2, out, N, 1, N, K, st);
 }
 
 // ---- embedding gather / scatter-add ----------------------------------------------------------------
@@ -1085,6 +1093,181 @@ int greedy_step(float* logits, long ld, int N, int V1, int t, int seq_len, int* 
     return check_launch("greedy_step");
 }
 
+// ---- multinomial step of the batched training-mode decode (echr_decoder_sample_train_batch): slab sum + draw in ONE launch, the row on chip ---
+// sample_step_kernel walks its row four times with one dependent global load per iteration behind a separate slab-sum launch.  Here the
+// workgroup forms the row itself (k-slice slabs four at a time in slab order, then the bias: slab_sum_bias_kernel's order) or reads the
+// finished logits, every load of a thread in flight at once, and keeps it in registers (the strided max / exp-sum passes) and LDS (the
+// contiguous-chunk mass pass and the walk).  The arithmetic and its order are sample_step_kernel's, so token and log-prob agree bit for bit.
+template <int EPT>
+__device__ __forceinline__ void sample_row_to_regs(float (&rv)[EPT], const float* __restrict__ x, const float* __restrict__ slabs, long slab_stride,
+                                                   int nslab, int n, int V1, const float* __restrict__ bias) {
+    if (!slabs) {
+#pragma unroll
+        for (int i = 0; i < EPT; ++i) { const int j = threadIdx.x + 256 * i; rv[i] = x[j < V1 ? j : 0]; }
+        return;
+    }
+    // per chunk of up to 24 elements: rounds of two slabs' loads in flight (register budget of the long rows); (S0 + S1) + (S2 + S3) per group
+    // of four slabs, groups in order
+    constexpr int CHK = EPT < 24 ? EPT : 24;
+    static_assert(EPT % CHK == 0, "row chunking");
+#pragma unroll
+    for (int c0 = 0; c0 < EPT; c0 += CHK) {
+        float s0[CHK], s1[CHK], pa[CHK];
+        for (int sb = 0; sb < nslab; sb += 4) {
+#pragma unroll
+            for (int hf = 0; hf < 2; ++hf) {
+#pragma unroll
+                for (int i = 0; i < CHK; ++i) {
+                    const int j = threadIdx.x + 256 * (c0 + i);
+                    const float* sp = slabs + (long)(sb + 2 * hf) * slab_stride + (long)n * V1 + (j < V1 ? j : 0);
+                    s0[i] = sp[0]; s1[i] = sp[slab_stride];
+                }
+#pragma unroll
+                for (int i = 0; i < CHK; ++i) {
+                    if (hf == 0) pa[i] = s0[i] + s1[i];
+                    else { const float part = pa[i] + (s0[i] + s1[i]); rv[c0 + i] = sb == 0 ? part : rv[c0 + i] + part; }
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < EPT; ++i) { const int j = threadIdx.x + 256 * i; rv[i] += bias ? bias[j < V1 ? j : 0] : 0.f; }
+}
+
+template <int EPT>          // EPT > 0: V1 <= 256 EPT, the row in registers + V1 floats of dynamic LDS; 0: any V1, streamed through `logits`
+__global__ __launch_bounds__(256, 1) void sample_row_step_kernel(float* __restrict__ logits, long ld, int V1, int t, int seq_len,
+                                                                 int* __restrict__ it_next, int* __restrict__ unfinished,
+                                                                 long long* __restrict__ seq, float* __restrict__ seq_logp,
+                                                                 int* __restrict__ n_unfinished, const float* __restrict__ slabs, long slab_stride,
+                                                                 const float* __restrict__ bias, int nslab, float inv_temp, unsigned k0, unsigned k1) {
+    extern __shared__ float srow[];
+    __shared__ float red[4];
+    __shared__ float pre[257];
+    const int n = blockIdx.x, th = threadIdx.x;
+    float* xg = logits + (long)n * ld;
+    const float* x;
+    float m = -INFINITY, s = 0.f;
+    if constexpr (EPT > 0) {
+        float rv[EPT];
+        sample_row_to_regs<EPT>(rv, xg, slabs, slab_stride, nslab, n, V1, bias);
+#pragma unroll
+        for (int i = 0; i < EPT; ++i) {
+            const int j = th + 256 * i;
+            if (j < V1) { m = fmaxf(m, rv[i]); srow[j] = rv[i]; }
+        }
+        m = block_max(m, red);          // (its barriers also publish srow)
+#pragma unroll
+        for (int i = 0; i < EPT; ++i) if (th + 256 * i < V1) s += expf(rv[i] - m);
+        x = srow;
+    } else {
+        if (slabs) {
+            for (int j = th; j < V1; j += 256) {
+                float v = 0.f;
+                for (int sb = 0; sb < nslab; sb += 4) {
+                    const float* sp = slabs + (long)sb * slab_stride + (long)n * V1 + j;
+                    const float part = (sp[0] + sp[slab_stride]) + (sp[2 * slab_stride] + sp[3 * slab_stride]);
+                    v = sb == 0 ? part : v + part;
+                }
+                xg[j] = v + (bias ? bias[j] : 0.f);
+            }
+            __syncthreads();          // the chunk pass reads what other threads of the workgroup wrote
+        }
+        for (int j = th; j < V1; j += 256) m = fmaxf(m, xg[j]);
+        m = block_max(m, red);
+        for (int j = th; j < V1; j += 256) s += expf(xg[j] - m);
+        x = xg;
+    }
+    s = block_sum(s, red);
+    const int CH = (V1 + 255) / 256, j0 = th * CH, j1 = min(V1, j0 + CH);
+    const float lz = m + logf(s);
+    float mass = 0.f;
+    for (int j = j0; j < j1; ++j) mass += expf((x[j] - m) * inv_temp);
+    pre[th + 1] = mass;
+    if (th == 0) pre[0] = 0.f;
+    __syncthreads();
+    if (th == 0) {
+        float acc = 0.f;
+        for (int i = 1; i <= 256; ++i) { acc += pre[i]; pre[i] = acc; }
+    }
+    __syncthreads();
+    const float total = pre[256];
+    const unsigned w = philox_word((unsigned)n, (unsigned)t, SITE_SAMPLE, 0u, k0, k1);
+    const float target = (float)(w >> 8) * (1.0f / 16777216.0f) * total;
+    const bool mine = (pre[th] <= target && target < pre[th + 1]) || (th == 255 && target >= total);
+    if (mine) {
+        float acc = pre[th];
+        int pick = -1;
+        for (int j = j0; j < j1; ++j) {
+            acc += expf((x[j] - m) * inv_temp);
+            if (acc > target) { pick = j; break; }
+        }
+        if (pick < 0) {
+            pick = max(0, min(V1, j1) - 1);
+            while (pick > 0 && !(expf((x[pick] - m) * inv_temp) > 0.f)) --pick;
+        }
+        const float lp = x[pick] - lz;
+        int un = (t == 0) ? 1 : unfinished[n];
+        un = un && (pick > 0);
+        unfinished[n] = un;
+        it_next[n] = pick;
+        if (t < seq_len) {
+            seq[(long)n * seq_len + t] = un ? pick : 0;
+            seq_logp[(long)n * seq_len + t] = lp;
+        }
+        if (un) atomicAdd(&n_unfinished[t + 1], 1);
+    }
+}
+
+int sample_row_step(float* logits, long ld, int N, int V1, int t, int seq_len, int* it_next, int* unfinished, long long* seq, float* seq_logp,
+                    int* n_unfinished, float temperature, unsigned long long seed, hipStream_t st, const float* slabs, long slab_stride,
+                    const float* bias, int nslab) {
+    const float inv_temp = 1.0f / (temperature > 0.f ? temperature : 1.0f);
+    const unsigned k0 = (unsigned)(seed & 0xFFFFFFFFull), k1 = (unsigned)(seed >> 32);
+#define ECHR_SAMPLE_ROW_LAUNCH(EPT, LDS)                                                                                                      \
+    hipLaunchKernelGGL(sample_row_step_kernel<EPT>, dim3(N), dim3(256), (LDS), st, logits, ld, V1, t, seq_len, it_next, unfinished, seq, seq_logp, \
+                       n_unfinished, slabs, slab_stride, bias, nslab, inv_temp, k0, k1)
+    const size_t lds = (size_t)V1 * sizeof(float);
+    if (V1 <= 256 * 8) ECHR_SAMPLE_ROW_LAUNCH(8, lds);
+    else if (V1 <= 256 * 20) ECHR_SAMPLE_ROW_LAUNCH(20, lds);
+    else if (V1 <= 256 * 48) ECHR_SAMPLE_ROW_LAUNCH(48, lds);          // 12 288 words: 48 KiB of LDS
+    else ECHR_SAMPLE_ROW_LAUNCH(0, 0);
+#undef ECHR_SAMPLE_ROW_LAUNCH
+    return check_launch("sample_row_step");
+}
+
+// video_words [V+1] of echr_decoder_sample_train_batch: workgroup v < V owns video v -- the run of rows with vid == v (vid non-decreasing, only
+// ever compared) -- and writes the largest count of non-zero tokens among them (seq is zero from a row's <eos> on); workgroup V covers every
+// row.  One writer per element, nothing read back: the caller need not clear the vector.
+__device__ __forceinline__ int first_row_at(const int* __restrict__ vid, int N, int v) {          // first n in [0, N] with vid[n] >= v
+    int lo = 0, hi = N;
+    while (lo < hi) {
+        const int mid = lo + (hi - lo) / 2;
+        if (vid[mid] >= v) hi = mid; else lo = mid + 1;
+    }
+    return lo;
+}
+__global__ __launch_bounds__(256) void sample_video_words_kernel(const long long* __restrict__ seq, const int* __restrict__ vid, int N, int L, int V,
+                                                                 int* __restrict__ video_words) {
+    __shared__ int red[4];
+    const int v = blockIdx.x;
+    const int n0 = v < V ? first_row_at(vid, N, v) : 0;
+    const int n1 = v < V ? first_row_at(vid, N, v + 1) : N;
+    int mx = 0;
+    for (int n = n0 + threadIdx.x; n < n1; n += 256) {
+        int w = 0;
+        for (int t = 0; t < L; ++t) w += seq[(long)n * L + t] != 0 ? 1 : 0;
+        mx = max(mx, w);
+    }
+    for (int off = 32; off > 0; off >>= 1) mx = max(mx, __shfl_xor(mx, off, 64));
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
+    __syncthreads();
+    if (threadIdx.x == 0) video_words[v] = max(max(red[0], red[1]), max(red[2], red[3]));
+}
+int sample_video_words(const long long* seq, const int* vid, int N, int L, int V, int* video_words, hipStream_t st) {
+    hipLaunchKernelGGL(sample_video_words_kernel, dim3(V + 1), dim3(256), 0, st, seq, vid, N, L, V, video_words);
+    return check_launch("sample_video_words");
+}
+
 }  // namespace echr
 
 using namespace echr;
@@ -1223,8 +1406,10 @@ int nll_loss_rw(const float* logp, const void* target, int tgt64, const float* m
 namespace echr {
 static thread_local const echr_batch_ext* g_batch_ext = nullptr;
 const echr_batch_ext* batch_ext() { return g_batch_ext; }
-BatchScope::BatchScope(const echr_batch_ext* x) : prev(g_batch_ext) { g_batch_ext = x; }
-BatchScope::~BatchScope() { g_batch_ext = prev; }
+static thread_local bool g_batch_scene_rows = false;
+bool batch_scene_rows() { return g_batch_scene_rows; }
+BatchScope::BatchScope(const echr_batch_ext* x, bool scene_rows) : prev(g_batch_ext), prev_rows(g_batch_scene_rows) { g_batch_ext = x; g_batch_scene_rows = scene_rows; }
+BatchScope::~BatchScope() { g_batch_ext = prev; g_batch_scene_rows = prev_rows; }
 }  // namespace echr
 
 // column means over row segments: block = (segment v, 64 columns); thread = (column, one of four row lanes); the four partial sums are added

@@ -1031,9 +1031,13 @@ static int precompute_static(const echr_dec_args* a, const DecWs& w, hipStream_t
         // multi-video batch: one scene vector per video -> VIDV [V, 4H] (one fixed-order k loop per tile), gathered by vid into the per-event
         // VIDB [N, 4H] that the gate products / kernels consume exactly as they consume stream 0's per-event EVB0
         const BatchWs bw = carve_batch(a->N, bx->n_videos, H, bx->ws);
-        d = desc_nt(bx->video, a->Dv, a->w_ih[2] + E, E + a->Dv, bw.VIDV, 4 * H, bx->n_videos, 4 * H, a->Dv);
-        d.bias = a->b_ih[2]; d.bias2 = a->b_hh[2]; d.split_k = 1;
-        RC(gemm(d, st));
+        if (batch_scene_rows()) {          // every video's vector exactly as its own call forms it (BatchScope)
+            RC(rows_matvec(bx->video, a->Dv, a->w_ih[2] + E, E + a->Dv, a->b_ih[2], a->b_hh[2], bw.VIDV, 4 * H, bx->n_videos, 4 * H, a->Dv, st));
+        } else {
+            d = desc_nt(bx->video, a->Dv, a->w_ih[2] + E, E + a->Dv, bw.VIDV, 4 * H, bx->n_videos, 4 * H, a->Dv);
+            d.bias = a->b_ih[2]; d.bias2 = a->b_hh[2]; d.split_k = 1;
+            RC(gemm(d, st));
+        }
         RC(embed_gather(bw.VIDV, bx->vid, bw.VIDB, a->N, 4 * H, bx->n_videos, st));
     } else
     RC(row_matvec(a->video, a->w_ih[2] + E, E + a->Dv, a->b_ih[2], a->b_hh[2], w.VIDB, 4 * H, a->Dv, st));      // (M = 1: no GEMM launch)
@@ -2175,7 +2179,8 @@ static int chain_step(const echr_dec_args& a, const DecWs& w, const SampWs& s, i
 
 // drop != nullptr: echr_decoder_sample_train -- the launch-per-step chain with the caller's training-mode dropout masks, keyed like
 // echr_decoder_fwd's step t: (element, t, site, drop->offset)
-static int decoder_sample_impl(const echr_sample_args* sa, const echr_dropout* drop, void* stream);
+// row_step: the multinomial step as ONE launch that forms the row from the slabs and draws (sample_row_step; the batched training decode)
+static int decoder_sample_impl(const echr_sample_args* sa, const echr_dropout* drop, void* stream, bool row_step = false);
 extern "C" int echr_decoder_sample(const echr_sample_args* sa, void* stream) { return decoder_sample_impl(sa, nullptr, stream); }
 extern "C" int echr_decoder_sample_train(const echr_sample_args* sa, const echr_dropout* drop, void* stream) {
     ECHR_REQUIRE(sa && drop, "decoder_sample_train: null args");
@@ -2188,7 +2193,22 @@ extern "C" int echr_decoder_sample_batch(const echr_sample_args* sa, const echr_
     BatchScope scope(x);
     return decoder_sample_impl(sa, nullptr, stream);
 }
-static int decoder_sample_impl(const echr_sample_args* sa, const echr_dropout* drop, void* stream) {
+// The sampled pass of self-critical training over a multi-video batch: echr_decoder_sample_train with the per-row scene part published for
+// the call, the multinomial step as one launch per step, and the per-video widths behind the last step on the same stream
+extern "C" int echr_decoder_sample_train_batch(const echr_sample_args* sa, const echr_dropout* drop, const echr_batch_ext* x, int32_t* video_words,
+                                               void* stream) {
+    ECHR_REQUIRE(sa && drop && video_words, "decoder_sample_train_batch: null args / video_words");
+    ECHR_REQUIRE(sa->multinomial, "decoder_sample_train_batch: the training-mode decode is the multinomial one (multinomial = 1)");
+    RC(check_batch(&sa->dec, x, "decoder_sample_train_batch"));
+    ECHR_REQUIRE(x->n_videos <= 65535, "decoder_sample_train_batch: at most 65535 videos per call (got %d)", x->n_videos);
+    {
+        BatchScope scope(x, true);
+        RC(decoder_sample_impl(sa, drop, stream, true));
+    }
+    return sample_video_words(reinterpret_cast<const long long*>(sa->seq), x->vid, sa->dec.N, sa->seq_len, x->n_videos, video_words,
+                              (hipStream_t)stream);
+}
+static int decoder_sample_impl(const echr_sample_args* sa, const echr_dropout* drop, void* stream, bool row_step) {
     ECHR_REQUIRE(sa, "decoder_sample: null args");
     RC(persist_check_async());
     DeterministicScope det;                    // `seq` is an index output: bitwise reproducible logits (no atomic split-K anywhere below)
@@ -2249,8 +2269,11 @@ static int decoder_sample_impl(const echr_sample_args* sa, const echr_dropout* d
     const int nsl4 = (samp_slabs(&a) + 3) / 4 * 4;
     for (int t = 0; t < L; ++t) {
         bool slab_form = false;
-        RC(chain_step(a, w, s, t, big, dh, dout, sa->multinomial != 0, &slab_form, st));
-        if (sa->multinomial)
+        RC(chain_step(a, w, s, t, big, dh, dout, sa->multinomial != 0 && !row_step, &slab_form, st));
+        if (sa->multinomial && row_step)
+            RC(sample_row_step(s.LOGITS, a.V1, N, a.V1, t, L, s.IT, s.UNF, reinterpret_cast<long long*>(sa->seq), sa->seq_logp, sa->n_unfinished,
+                               sa->temperature, sa->seed, st, slab_form ? s.SLABS : nullptr, (long)N * a.V1, a.b_logit, nsl4));
+        else if (sa->multinomial)
             RC(sample_step(s.LOGITS, a.V1, N, a.V1, t, L, s.IT, s.UNF, reinterpret_cast<long long*>(sa->seq), sa->seq_logp, sa->n_unfinished,
                            sa->temperature, sa->seed, st));
         else

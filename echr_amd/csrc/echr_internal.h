@@ -191,6 +191,8 @@ int transpose_multi(const TransposeJob* jobs, int n, hipStream_t st);           
 int transpose(const float* in, long ld_in, float* out, long ld_out, int rows, int cols, int rows_pad, hipStream_t st);
 int embed_gather(const float* W, const int* tok, float* out, int rows, int E, int V1, hipStream_t st);
 int row_matvec(const float* x, const float* W, long ldw, const float* b1, const float* b2, float* out, int N, int K, hipStream_t st);
+// row_matvec for M vectors x [M, ldx] -> out [M, ldo] in one launch (row_matvec is its M = 1 case: a row is bit-identical alone and among M)
+int rows_matvec(const float* x, long ldx, const float* W, long ldw, const float* b1, const float* b2, float* out, long ldo, int M, int N, int K, hipStream_t st);
 int rank1_update(const float* x, const float* y, float* C, long ldc, int M, int N, bool accumulate, hipStream_t st);
 int vec_mat(const float* x, const float* W, long ldw, float* out, int M, int N, hipStream_t st);
 int embed_scatter_add(const float* dX, const int* tok, float* gW, int rows, int E, int V1, hipStream_t st, const int* rowmap = nullptr);
@@ -213,9 +215,14 @@ int nll_loss_rw(const float* logp, const void* target, int tgt64, const float* m
 const echr_batch_ext* batch_ext();
 struct BatchScope {
     const echr_batch_ext* prev;
-    explicit BatchScope(const echr_batch_ext* x);
+    bool prev_rows;
+    // scene_rows: the per-video scene part of stream 2's gates is formed with the single-video entry's own arithmetic (row_matvec per video)
+    // instead of one product over the V scene vectors, so a row decodes as it does alone to the bit (echr_decoder_sample_train_batch: a
+    // last-bit difference in a logit can flip a draw)
+    explicit BatchScope(const echr_batch_ext* x, bool scene_rows = false);
     ~BatchScope();
 };
+bool batch_scene_rows();
 inline int crit_unit_den() { return batch_ext() ? 1 : 0; }
 // out[v*ld + c] = sum over the rows n with vid[n] == v of X[n*ld + c], rows added in ascending n (fixed order: bit-reproducible)
 int seg_rowsum(const float* X, const int* vid, int N, int V, int cols, long ld, float* out, hipStream_t st);
@@ -233,6 +240,13 @@ int decoder_fwd_fused(const echr_dec_args* a, const echr_dec_grads* g, const ech
 int decoder_fused_loss(const echr_dec_args* a, const echr_dec_grads* g, float* loss, hipStream_t st, bool rw = false);
 int sample_step(const float* logits, long ld, int N, int V1, int t, int seq_len, int* it_next, int* unfinished, long long* seq,
                 float* seq_logp, int* n_unfinished, float temperature, unsigned long long seed, hipStream_t st);
+// the multinomial step with the row on chip (echr_decoder_sample_train_batch): sample_step's draw, bit for bit, with the slab sum folded in
+// (slabs != nullptr: the row is formed from the k-slice slabs + bias; else read from `logits`); V1 floats of LDS up to 12 288 words
+int sample_row_step(float* logits, long ld, int N, int V1, int t, int seq_len, int* it_next, int* unfinished, long long* seq, float* seq_logp,
+                    int* n_unfinished, float temperature, unsigned long long seed, hipStream_t st, const float* slabs, long slab_stride,
+                    const float* bias, int nslab);
+// video_words [V+1] = per-video maxima of the rows' non-zero token counts in seq [N,L] (vid per row, non-decreasing), then the maximum of all
+int sample_video_words(const long long* seq, const int* vid, int N, int L, int V, int* video_words, hipStream_t st);
 // slabs != nullptr: logits rows are formed here from four k-slice slabs (+ bias) in a fixed order and written to `logits`
 int greedy_step(float* logits, long ld, int N, int V1, int t, int seq_len, int* it_next, int* unfinished,
                 long long* seq, float* seq_logp, int* n_unfinished, hipStream_t st, const float* slabs = nullptr, long slab_stride = 0,

@@ -569,7 +569,7 @@ def clip_rows(c3d, tap):
 
 
 def greedy_sample(video, event, c3d, ev_start, ev_len, A, seq_length, params, debug=None, multinomial=False, temperature=1.0, seed=0,
-                  table_cache=None, h0=None, drop=None, vid=None):
+                  table_cache=None, h0=None, drop=None, vid=None, defer=False):
     """OldModel.sample (OldModel_NEW.py:139-187) with every step on device; one host sync at the end.  Greedy arg-max by default
     (sample_max = 1); multinomial=True draws each token from softmax(logp / temperature) (:160-168) with the library's Philox stream
     keyed by `seed`.
@@ -584,7 +584,9 @@ def greedy_sample(video, event, c3d, ev_start, ev_len, A, seq_length, params, de
     `vid` (int32 [N] device): greedy decode of a multi-video batch -- `video` is [V, Dv] and event n reads row vid[n]
     (echr_decoder_sample_batch).
 
-    Returns (seq int64 [N,T], logp fp32 [N,T]) with T <= seq_length, or ([], []) when nothing was generated."""
+    Returns (seq int64 [N,T], logp fp32 [N,T]) with T <= seq_length, or ([], []) when nothing was generated.
+    `defer=True`: the decode is queued and a function is returned that performs the host read and returns the result -- a caller with
+    several decodes in flight pays one stream drain for all of them (fused.SelfCriticalBatchStep)."""
     if vid is not None and (multinomial or drop is not None or h0 is not None):
         raise NotImplementedError('the batched decode is the greedy one from the zero initial state')
     if drop is not None and not multinomial:
@@ -616,6 +618,7 @@ def greedy_sample(video, event, c3d, ev_start, ev_len, A, seq_length, params, de
     sa = L.SampleArgs(a, seq_length, L.ptr(seq, torch.int64), L.ptr(slp), L.ptr(nun, torch.int32), L.ptr(wss),
                       1 if multinomial else 0, float(temperature), int(seed) & 0xFFFFFFFFFFFFFFFF,
                       L.ptr(tables) if tables is not None else None, valid)
+    xws = None
     if vid is not None:
         x, xws = batch_ext(vid, video, H=ps[6].shape[1])
         L.check(lib.echr_decoder_sample_batch(C.byref(sa), C.byref(x), L.stream_ptr()), 'decoder_sample_batch')
@@ -624,24 +627,79 @@ def greedy_sample(video, event, c3d, ev_start, ev_len, A, seq_length, params, de
         L.check(lib.echr_decoder_sample_train(C.byref(sa), C.byref(dc), L.stream_ptr()), 'decoder_sample_train')
     else:
         L.check(lib.echr_decoder_sample(C.byref(sa), L.stream_ptr()), 'decoder_sample')
-    counts = nun.cpu().numpy()                 # the only device->host sync of the whole decode
-    L.check(lib.echr_check_async(), 'decoder_sample')
-    if tables is not None:
-        table_cache['key'] = key
-    if debug is not None:                      # tests: the raw logits [N,V1] of the last decoder step (sampler workspace: XT | LOGITS | ...)
-        E, V1 = ps[0].shape[1], ps[0].shape[0]
-        o = (N * E + 63) // 64 * 64
-        debug['last_logits'] = wss[o:o + N * V1].view(N, V1).clone()
-        debug['seq_full'], debug['logp_full'] = seq.clone(), slp.clone()
-        debug['stopped_early'] = int(counts[0])      # persistent decoder: 1 = every event had emitted <eos> before seq_length and the launch stopped there
-    T = seq_length
-    for t in range(1, seq_length + 1):        # OldModel_NEW.py:179-180: stop at the first step with nobody unfinished
-        if counts[t] == 0:
-            T = t - 1
-            break
-    if T == 0:
-        return [], []
-    return seq[:, :T].contiguous(), slp[:, :T].contiguous()
+
+    def finish():          # (holds the workspaces and converted inputs the queued kernels use until the host read below)
+        keep = (ws, wss, xws, video, event, c3d, ps, h0)          # noqa: F841
+        counts = nun.cpu().numpy()                 # the only device->host sync of the whole decode
+        L.check(lib.echr_check_async(), 'decoder_sample')
+        if tables is not None:
+            table_cache['key'] = key
+        if debug is not None:                      # tests: the raw logits [N,V1] of the last decoder step (sampler workspace: XT | LOGITS | ...)
+            E, V1 = ps[0].shape[1], ps[0].shape[0]
+            o = (N * E + 63) // 64 * 64
+            debug['last_logits'] = wss[o:o + N * V1].view(N, V1).clone()
+            debug['seq_full'], debug['logp_full'] = seq.clone(), slp.clone()
+            debug['stopped_early'] = int(counts[0])      # persistent decoder: 1 = every event had emitted <eos> before seq_length and the launch stopped there
+        T = seq_length
+        for t in range(1, seq_length + 1):        # OldModel_NEW.py:179-180: stop at the first step with nobody unfinished
+            if counts[t] == 0:
+                T = t - 1
+                break
+        if T == 0:
+            return [], []
+        return seq[:, :T].contiguous(), slp[:, :T].contiguous()
+    return finish if defer else finish()
+
+
+def sample_train_batch(video, event, c3d, ev_start, ev_len, vid, A, seq_length, params, drop, temperature=1.0, seed=0, defer=False):
+    """The sampled pass of self-critical training over a multi-video batch (echr_decoder_sample_train_batch): `greedy_sample(...,
+    multinomial=True, drop=)` with `video` [V, Dv] and `vid` int32 [N] (device, non-decreasing) naming each event's video.  The decoder's
+    dropout is active under `drop` with the masks the batched teacher-forced forward draws at the same step; the draws are keyed (seed,
+    batch-global row, step); batches start from the zero state.
+
+    Returns (seq int64 [N,T], logp fp32 [N,T], video_words): video_words is a host int64 [V] with the width each video's own call cuts its
+    output at (the largest number of non-zero tokens among its rows) and T = max(video_words); ([], [], zeros) when T == 0.  One host read
+    per call: the per-step unfinished counts and video_words travel in one vector.  `defer=True`: as in greedy_sample."""
+    if drop is None:
+        raise ValueError('the sampled pass of self-critical training needs the iteration\'s dropout state')
+    if video.dim() != 2:
+        raise ValueError('video must be [V, Dv], one scene vector per video (got %s)' % (tuple(video.shape),))
+    lib = L.load()
+    N, V = event.shape[0], video.shape[0]
+    if vid.dim() != 1 or vid.numel() != N or ev_start.numel() != N or ev_len.numel() != N:
+        raise ValueError('vid, ev_start and ev_len need one entry per event (%d)' % N)
+    if not 1 <= V <= N:
+        raise ValueError('a batch has between 1 video and one video per event (V = %d, N = %d)' % (V, N))
+    video, event, c3d = _f32c(video), _f32c(event), _f32c(c3d)
+    ps = [_f32c(p) for p in params]
+    dev = event.device
+    a = _dec_args(ps, c3d, ev_start, ev_len, event, video, None, A, seq_length, None, None)
+    ws = torch.empty(lib.echr_decoder_ws_floats(C.byref(a)), device=dev, dtype=torch.float32)
+    a.ws = L.ptr(ws)
+    wss = torch.empty(lib.echr_sampler_ws_floats(C.byref(a)), device=dev, dtype=torch.float32)
+    seq = torch.empty(N, seq_length, device=dev, dtype=torch.int64)
+    slp = torch.empty(N, seq_length, device=dev, dtype=torch.float32)
+    counts = torch.empty(seq_length + 1 + V + 1, device=dev, dtype=torch.int32)          # n_unfinished [L+1] | video_words [V+1]
+    sa = L.SampleArgs(a, seq_length, L.ptr(seq, torch.int64), L.ptr(slp), L.ptr(counts, torch.int32), L.ptr(wss), 1, float(temperature),
+                      int(seed) & 0xFFFFFFFFFFFFFFFF, None, 0)
+    x, xws = batch_ext(vid, video, H=ps[6].shape[1])
+    dc = drop.c()
+    L.check(lib.echr_decoder_sample_train_batch(C.byref(sa), C.byref(dc), C.byref(x), counts.data_ptr() + 4 * (seq_length + 1), L.stream_ptr()),
+            'decoder_sample_train_batch')
+
+    def finish():          # (holds ws / wss / xws and the converted inputs until the host read below)
+        keep = (ws, wss, xws, video, event, c3d, ps)          # noqa: F841
+        host = counts.cpu().numpy()                # the only device->host sync of the whole decode
+        L.check(lib.echr_check_async(), 'decoder_sample_train_batch')
+        nun, vw = host[:seq_length + 1], host[seq_length + 1:].astype(np.int64)
+        T = int(vw[V])
+        stop = next((t - 1 for t in range(1, seq_length + 1) if nun[t] == 0), seq_length)          # OldModel_NEW.py:179-180
+        if stop != T:
+            raise L.EchrHipError('decoder_sample_train_batch: widths %s disagree with the unfinished counts %s' % (vw.tolist(), nun.tolist()))
+        if T == 0:
+            return [], [], vw[:V]
+        return seq[:, :T].contiguous(), slp[:, :T].contiguous(), vw[:V]
+    return finish if defer else finish()
 
 
 BEAM_MAX = 16          # echr_decoder_beam's largest beam

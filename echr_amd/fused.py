@@ -502,7 +502,8 @@ class SelfCriticalStep(object):
 
     def batch(self, *args, **kwargs):
         """Multi-video batches (FusedTrainStep.batch) are not part of this step yet: the sampled and greedy decodes and the reward take one video per call."""
-        raise NotImplementedError('SelfCriticalStep takes one video per call: self-critical training over a VideoBatch is a follow-up')
+        raise NotImplementedError('SelfCriticalStep takes one video per call: self-critical training over a VideoBatch is '
+                                  'SelfCriticalBatchStep(fused)(batch) (the module path: CaptionGenerator.train_rl_batch)')
 
     def __call__(self, tap_feats, c3d_feats, lda_feats, ind_select_list, soi_select_list, gen_result=None, reward=None, step=True):
         """Returns (loss 0-d device tensor, gen_result [N,T] int64 host, greedy_res [N,T'] int64 host, reward [N,T] fp32 host).
@@ -572,6 +573,100 @@ class SelfCriticalStep(object):
         else:
             L.check(lib.echr_train_step_rw(C.byref(a), None, L.stream_ptr()), 'train_step_rw')
         return f._finish(slot, st, False), gen_h, greedy_h, torch.from_numpy(r)
+
+
+class SelfCriticalBatchStep(object):
+    """One self-critical training iteration over a multi-video batch (echr_amd.batch.VideoBatch) on the one-call path of `fused`: the
+    reference's m_batch = V protocol past --self_critical_after (train.py:241-245, 281-283, 303-308) without V sequential calls.
+
+      ONE training-mode event context over the batch under the iteration's dropout state -> the sampled decode of all N_tot rows with the
+      decoder's dropout active under that state (echr_decoder_sample_train_batch) -> the greedy baseline of all rows (eval mode) -> ONE
+      host sync (both decodes are queued before either is read) -> reward_fn per video on the host -> echr_train_step_batch on the
+      teacher-forced tokens [0 | gen_result | 0] with the same dropout state and the weights of VideoBatch.reward_weights: the loss is
+      the SUM over the videos of RewardCriterion, each video at its own width and with its own normaliser; gradients are summed over the
+      videos, then one clamp + Adam (applied-update counting as SelfCriticalStep).
+
+    `reward_fn(gen_v, greedy_v)` is called once per video, in order, with that video's rows cut to its own widths -- the arguments a
+    single-video SelfCriticalStep passes -- and returns [N_v, T_v] or [N_v]; it is not called for a video whose sample has width 0 (that
+    video contributes loss 0 and no gradient); `current_video` names the video of the call in progress.  `last_video_losses` holds the
+    per-video losses as a device vector [V]."""
+
+    def __init__(self, fused, reward_fn=None):
+        if not isinstance(fused, FusedTrainStep):
+            raise TypeError('SelfCriticalBatchStep wraps a FusedTrainStep')
+        self.fused, self.reward_fn = fused, reward_fn
+        self.last_video_losses, self.current_video = None, None
+
+    def __call__(self, batch, gen_result=None, reward=None, step=True):
+        """Returns (loss 0-d device tensor, gen_result [N_tot,T] int64 host, greedy_res [N_tot,T'] int64 host, reward [N_tot,T] fp32 host,
+        video_words int64 [V] host); T = max(video_words).  `gen_result` [N_tot, >= T]: score these captions instead of drawing them;
+        `reward` ([N_tot,T] or [N_tot]): use it instead of calling reward_fn.  step=False stops after the backward pass (the summed
+        gradients as `.grad` views).  The batch need not carry labels.  Raises ValueError when every video's sample has width 0."""
+        f = self.fused
+        m = f.model
+        lm = m.lm_model
+        if getattr(f, '_prepared', False):
+            raise NotImplementedError('prepare() runs ahead of ONE video\'s call: it does not combine with a batch step')
+        L.check(f.lib.echr_check_async(), 'self_critical_batch_step (asynchronous failure of an earlier call)')
+        if getattr(f, '_pending_deferred', False):
+            f.join()
+            f._pending_deferred = False
+        N, V = batch.n_events, batch.n_videos
+        with torch.no_grad():
+            video, event, ev_start, ev_len, A, vid, drop = m._batch_contexts(batch, None)
+            video = EF._f32c(video)
+            self.last_event = event          # the event context the decodes read (inspection: the step recomputes it)
+            ps = lm.native_params()
+            sampled = None
+            if gen_result is None:
+                sampled = EF.sample_train_batch(video, event, batch.c3d, ev_start, ev_len, vid, A, lm.seq_length, ps, drop,
+                                                seed=lm._sample_seed(), defer=True)
+            if '_sample_tables' not in lm.__dict__:
+                lm._sample_tables = {}
+            greedy_f = EF.greedy_sample(video, event, batch.c3d, ev_start, ev_len, A, lm.seq_length, ps, table_cache=lm._sample_tables,
+                                        vid=vid, defer=True)
+            # the one host sync of the iteration: the first read drains the stream, both decodes included
+            if sampled is not None:
+                gen, _, vw = sampled()
+                gen_h = gen.cpu() if isinstance(gen, torch.Tensor) else torch.zeros(N, 0, dtype=torch.int64)
+            else:
+                vw = batch.caption_widths(gen_result)
+                gen_h = torch.as_tensor(np.asarray(gen_result.cpu() if isinstance(gen_result, torch.Tensor) else gen_result,
+                                                   dtype=np.int64))[:, :int(vw.max())].contiguous()
+            greedy, _ = greedy_f()
+        greedy_h = greedy.cpu() if isinstance(greedy, torch.Tensor) else torch.zeros(N, 0, dtype=torch.int64)
+        T = int(vw.max())
+        if T == 0:
+            raise ValueError('every caption drew <eos> at its first step: nothing to train on (OldModel.sample returns [] then)')
+        if reward is None:
+            if self.reward_fn is None:
+                raise ValueError('SelfCriticalBatchStep needs reward_fn or an explicit reward')
+            gw = batch.caption_widths(greedy_h)
+            r = np.zeros((N, T), dtype=np.float32)
+            for v, (s, wv, wg) in enumerate(zip(batch.event_slices, vw.tolist(), gw.tolist())):
+                if wv == 0:
+                    continue
+                self.current_video = v
+                rv = self.reward_fn(gen_h[s, :wv], greedy_h[s, :wg])
+                rv = np.asarray(rv.cpu() if isinstance(rv, torch.Tensor) else rv, dtype=np.float32)
+                if rv.ndim == 1:
+                    rv = np.repeat(rv[:, None], wv, 1)
+                if rv.shape != (s.stop - s.start, wv):
+                    raise ValueError('reward_fn must return [N_v, T_v] or [N_v] (got %s for a video of %s)' % (rv.shape, (s.stop - s.start, wv)))
+                r[s, :wv] = rv
+        else:
+            r = np.ascontiguousarray(batch._reward_matrix(reward, N, T))
+        labels, mask, w = batch.reward_weights(gen_h, r, vw)
+        a, lib = f.a, f.lib
+        slot, st = f._setup(batch.tap, batch.c3d, video, labels, batch.ind, batch.soi, labels[:, 1:], mask, step, False, None, False,
+                            drop=drop, weights=w, batch=batch)
+        a.prepared = a.handover = 0
+        a.handover_cb = a.handover_user = a.mid_cb = a.mid_user = None
+        f._pending_deferred = False
+        self.last_video_losses = f.last_video_losses = torch.empty(V, device=f.dev, dtype=torch.float32)
+        f._keep = f._keep + (video,)
+        L.check(lib.echr_train_step_batch(C.byref(a), C.byref(f.bx), None, L.ptr(self.last_video_losses), L.stream_ptr()), 'train_step_batch')
+        return f._finish(slot, st, False), gen_h, greedy_h, torch.from_numpy(r), vw
 
 
 class JointTrainStep(object):

@@ -356,6 +356,7 @@ def make_attsat(name, clip_context_type='CC'):
 #          every row -- tools/make_golden_vbatch.py asserts it on the reference's own decode)
 #   vbctx  5 videos incl. a one-event video, scene context from all three sources ('VLVCVH': per-video column means), 'ER3', small vocabulary
 #   vb24 / vb33  24 / 33 videos of 4 events, small vocabulary
+#   vbscst 4 videos of 3..6 events at the 'tiny_eos' widths (self-critical training over a batch)
 VBATCH = {
     'vb16': dict(opt=dict(CG_vocab_size=5000, CG_seq_length=19), V=16, events=(2, 6), max_events=64, seg=(3, 60), T=(40, 160), L=(12, 21), seed=1000),
     'vbctx': dict(opt=dict(video_context_type='VLVCVH', CG_vocab_size=300, CG_seq_length=7), V=5, events=(1, 4), single=2, max_events=64, seg=(3, 30),
@@ -364,6 +365,11 @@ VBATCH = {
     # head); 132 events: the row kernel)
     'vb24': dict(opt=dict(CG_vocab_size=300, CG_seq_length=7), V=24, events=(4, 4), max_events=96, seg=(3, 30), T=(30, 80), L=(6, 9), seed=1200),
     'vb33': dict(opt=dict(CG_vocab_size=300, CG_seq_length=7), V=33, events=(4, 4), max_events=132, seg=(3, 30), T=(30, 80), L=(6, 9), seed=1300),
+    # self-critical training over a batch (tests/golden/case_scst_batch.npz): the 'tiny_eos' widths (V1 = 31, seq_length 6), 4 videos of 3..6
+    # events; tools/make_golden_scst_batch.py picks the reference's draw seeds whose per-video sample widths differ
+    'vbscst': dict(opt=dict(video_dim=20, hidden_dim=24, lda_dim=12, d_feats=32, d_o=32, n_head=4, CG_rnn_size=32, CG_input_encoding_size=16,
+                            CG_att_hid_size=24, CG_vocab_size=30, CG_seq_length=6),
+                   V=4, events=(3, 6), max_events=64, seg=(3, 9), T=(12, 24), L=(8, 8), seed=1400),
 }
 
 

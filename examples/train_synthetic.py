@@ -22,7 +22,13 @@ with `--pre_tap`, ONE iteration of `--iters` is one batch of V videos with an up
 batches; the autograd modes count single-video iterations (an update every m_batch of them), so a checkpoint resumed under the other mode
 continues at a different video and epoch.
 
-usage: python examples/train_synthetic.py [--iters 20] [--m_batch 2] [--joint] [--pre_tap] [--save /tmp/echr_ckpt.pth] [--resume /tmp/echr_ckpt.pth]
+`--self_critical` is the stage past `--self_critical_after` (train.py:241-245, 303-308): a sampled and a greedy caption per event, the
+reward-weighted step on the sample.  m_batch = 1 runs fused.SelfCriticalStep per video, m_batch = V > 1 runs fused.SelfCriticalBatchStep on
+the V videos of one accumulation as ONE batch (one iteration of `--iters` is then one batch with an update).  The reward is synthetic:
+the token overlap of the sampled caption with the video's ground-truth caption minus the same for the greedy caption.
+
+usage: python examples/train_synthetic.py [--iters 20] [--m_batch 2] [--joint] [--pre_tap] [--self_critical] [--save /tmp/echr_ckpt.pth]
+                                          [--resume /tmp/echr_ckpt.pth]
 """
 import argparse
 import os
@@ -108,12 +114,56 @@ def joint_batch(a, opt, dev, loader, tap_model, cg_model, cg_opt, tap_opt, start
     return history
 
 
+def overlap_reward(labels):
+    """reward_fn of the self-critical steps for events with the ground-truth `labels` [N, L] (host, <bos> in column 0): per caption, the
+    fraction of its tokens that occur in the event's ground-truth caption, sampled minus greedy (a stand-in for CIDEr differences)."""
+    truth = [set(int(t) for t in row[1:] if t > 0) for row in np.asarray(labels)]
+
+    def score(seq):
+        out = np.zeros(len(truth), np.float32)
+        for n, row in enumerate(np.asarray(seq)):
+            toks = [int(t) for t in row if t > 0]
+            out[n] = sum(t in truth[n] for t in toks) / max(len(toks), 1)
+        return out
+    return lambda gen, greedy: score(gen) - score(greedy)
+
+
+def self_critical(a, opt, dev, loader, tap_model, cg_model, cg_opt, start):
+    """Self-critical training of the captioner (the proposal encoder idle, its states without a graph): SelfCriticalStep per video, or
+    SelfCriticalBatchStep over the m_batch videos of one accumulation as one batch."""
+    from echr_amd.batch import VideoBatch
+    from echr_amd.fused import FusedTrainStep, SelfCriticalBatchStep, SelfCriticalStep
+    fused = FusedTrainStep(cg_model, cg_opt, grad_clip=opt.grad_clip)
+    history = []
+    for it in range(start, start + a.iters):
+        vids = [loader[(it * a.m_batch + j) % len(loader)] for j in range(a.m_batch)]
+        set_lr_for_epoch(cg_opt, opt.lr, it * a.m_batch // len(loader))
+        if a.m_batch == 1:
+            v = vids[0]
+            c3d, lda = torch.from_numpy(v['c3d']).to(dev), torch.from_numpy(v['lda']).to(dev)
+            with torch.no_grad():
+                tap_feats, _ = tap_model(c3d)
+            loss = SelfCriticalStep(fused, overlap_reward(v['labels']))(tap_feats, c3d, lda, v['ind'], v['soi'])[0]
+        else:
+            rewards = [overlap_reward(v['labels']) for v in vids]          # reward_fn is called once per video (step.current_video)
+            with torch.no_grad():
+                batch = VideoBatch.from_videos([{k: v[k] for k in ('c3d', 'lda', 'ind', 'soi')} for v in vids], device=dev, tap_model=tap_model)
+            step = SelfCriticalBatchStep(fused, lambda gen, greedy: rewards[step.current_video](gen, greedy))
+            loss = step(batch)[0]
+        history.append(float(loss) / a.m_batch)
+        if not a.quiet and (it % 5 == 0 or it == start + a.iters - 1):
+            print('iter %3d  self-critical loss %.4f  (mean of %d videos)' % (it, history[-1], a.m_batch), flush=True)
+    return history
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--iters', type=int, default=20)
     ap.add_argument('--m_batch', type=int, default=1)
     ap.add_argument('--joint', action='store_true', help="'tap_cg' mode: gradients flow through tap_feats into the SST")
     ap.add_argument('--pre_tap', action='store_true', help="'pre_tap' mode: train the proposal encoder alone, m_batch videos per forward_batch call")
+    ap.add_argument('--self_critical', action='store_true', help='self-critical training of the captioner: SelfCriticalStep (m_batch = 1) or '
+                                                                 'SelfCriticalBatchStep over the m_batch videos as one batch')
     ap.add_argument('--events', type=int, default=16)
     ap.add_argument('--segments', type=int, default=32)
     ap.add_argument('--vocab', type=int, default=500)
@@ -160,6 +210,10 @@ def main(argv=None):
     if a.pre_tap:
         return pre_tap(a, opt, dev, loader, tap_model, cg_model, cg_opt, tap_opt, tap_crit, start)
     iters = range(start, start + a.iters)
+    if a.self_critical:
+        if a.joint or a.no_fused:
+            raise SystemExit('--self_critical trains the captioner on the one-call path: not with --joint / --no-fused')
+        history, iters = self_critical(a, opt, dev, loader, tap_model, cg_model, cg_opt, start), ()
     if batch_joint:
         history, iters = joint_batch(a, opt, dev, loader, tap_model, cg_model, cg_opt, tap_opt, start), ()
     for it in iters:

@@ -765,6 +765,17 @@ int echr_decoder_sample_batch(const echr_sample_args* a, const echr_batch_ext* x
  * the maximum over the batch.  Every element is written (no zero fill by the caller) and none is read by the device: the host reads
  * this vector once, instead of words[N/B], and cuts every video's rows to the width that video alone would have produced. */
 int echr_decoder_beam_batch(const echr_beam_args* a, const echr_batch_ext* x, int32_t* video_words, void* stream);
+/* The sampled pass of self-critical training over a batch: echr_decoder_sample_train (a->multinomial must be 1, training-mode dropout under
+ * `drop` with the masks echr_decoder_fwd_batch draws at the same step, zero initial state, the launch-per-step chain) with per-row scene
+ * vectors.  Draws are keyed (seed, batch-global row, step), so a one-video batch equals echr_decoder_sample_train bit for bit.  The
+ * multinomial step is ONE launch per step: the workgroup of a row forms it from the k-slice slabs of the logits product (or reads the
+ * finished logits of the many-row chain), keeps it on chip and draws -- the token and log-prob of the single-video entry's slab-sum + draw
+ * pair on the same logits; vocabularies above 12 288 words stream the row instead.
+ * video_words: device int32 [V+1] out, written behind the last step on the same stream (one launch, no host synchronisation) --
+ * video_words[v] = the largest number of non-zero tokens among the rows of video v, i.e. the width at which that video's own call cuts its
+ * output, video_words[V] = the maximum over the batch.  Every element is written and none is read by the device. */
+int echr_decoder_sample_train_batch(const echr_sample_args* a, const echr_dropout* drop, const echr_batch_ext* x, int32_t* video_words,
+                                    void* stream);
 /* echr_train_step over a batch.  Criterion weights as in echr_train_step_rw: `weight` device [N,S] with host_nll = 0, or behind the mask
  * in host_index with host_nll = 1 (then weight = NULL).  host_index additionally ENDS with vid[N]; x->vid and x->ws are ignored (the
  * library points them at its staged copy / its own workspace).  loss[0] = the summed loss, loss[1] = sum(mask) over the batch;
