@@ -127,19 +127,27 @@ class CaptionGenerator(nn.Module):
             with torch.no_grad():
                 if '_sample_tables' not in lm.__dict__:
                     lm._sample_tables = {}
-                return EF.greedy_sample(video, event, batch.c3d, ev_start, ev_len, A, lm.seq_length, lm.native_params(),
+                return EF.greedy_sample(video, event, batch.clip_rows(), ev_start, ev_len, A, lm.seq_length, lm.native_params(),
                                         table_cache=lm._sample_tables, vid=vid)
         if lm.training and lm.ss_prob > 0.0:
             raise NotImplementedError('scheduled sampling (ss_prob > 0) is never enabled by the reference and is not on the HIP path')
         tokens = lm._tokens(batch.labels, batch.device)
         arena = getattr(lm, '_echr_arena_ref', None)
         sink = EF.GradSink(arena, lm.native_params()) if arena is not None else None
-        return EF.DecoderBatchFunction.apply(video, event, batch.c3d, ev_start, ev_len, tokens, A, disjoint, drop, sink, vid, *lm.native_params())
+        return EF.DecoderBatchFunction.apply(video, event, batch.clip_rows(), ev_start, ev_len, tokens, A, disjoint, drop, sink, vid,
+                                             *(tuple(lm.native_params()) + self._batch_clip_tail(batch)))
+
+    @staticmethod
+    def _batch_clip_tail(batch):
+        """What follows the parameters in DecoderBatchFunction.apply: nothing for 'CC'; (batch.tap, its first column in the row source) for
+        'CH' / 'CC+CH' -- the row source carries no graph, the decoder's backward returns d tap itself (as ClipView.grad_src / grad_col0
+        arrange for one video)."""
+        return () if batch.clip_parts == 1 else (batch.tap, int(batch.clip_col0))
 
     def _batch_contexts(self, batch, groups, need_labels=False):
         """What forward_batch and beam_batch hand to the decoder: the checks of a batched call, then (video [V, Dv], event [N_tot, d_o],
         ev_start, ev_len, A, vid, drop) -- the scene vectors, and the event encoder as one block-diagonal call or once per run of `groups`."""
-        self._check_batch_options()
+        self._check_batch_options(batch)
         self._require_live_decoder()
         if not batch.c3d.is_cuda:
             raise EF.L.EchrHipError('CaptionGenerator runs on the GPU only: build the batch on the device (VideoBatch.from_videos(..., device=))')
@@ -184,8 +192,9 @@ class CaptionGenerator(nn.Module):
             video, event, ev_start, ev_len, A, vid, _ = self._batch_contexts(batch, groups)
             lm = self.lm_model
             L, N, ro = lm.seq_length, batch.n_events, batch.row_offset
+            rows = batch.clip_rows()
             if len(runs) == 1:
-                seq, logp, score, video_words = EF.beam_search_batch(video, event, batch.c3d, ev_start, ev_len, vid, A, L, lm.native_params(), B,
+                seq, logp, score, video_words = EF.beam_search_batch(video, event, rows, ev_start, ev_len, vid, A, L, lm.native_params(), B,
                                                                      trim=False)
             else:
                 seq = torch.empty(N, L, device=batch.device, dtype=torch.int64)
@@ -195,7 +204,7 @@ class CaptionGenerator(nn.Module):
                 for v0, v1, e0, e1 in runs:          # run-local rows: the run's own feature rows, scene vectors and video numbers
                     r0, r1 = int(ro[v0]), int(ro[v1])
                     seq[e0:e1], logp[e0:e1], score[e0:e1], video_words[v0:v1] = EF.beam_search_batch(
-                        video[v0:v1], event[e0:e1], batch.c3d[r0:r1], ev_start[e0:e1] - r0, ev_len[e0:e1], vid[e0:e1] - v0, A, L,
+                        video[v0:v1], event[e0:e1], rows[r0:r1], ev_start[e0:e1] - r0, ev_len[e0:e1], vid[e0:e1] - v0, A, L,
                         lm.native_params(), B, trim=False)
         T = int(video_words.max())
         if T == 0:
@@ -220,7 +229,7 @@ class CaptionGenerator(nn.Module):
         if gen_result is None:
             seed = lm._sample_seed() if seed is None else int(seed)
             with torch.no_grad():
-                gen, _, video_words = EF.sample_train_batch(video, event.detach(), batch.c3d, ev_start, ev_len, vid, A, lm.seq_length,
+                gen, _, video_words = EF.sample_train_batch(video, event.detach(), batch.clip_rows(), ev_start, ev_len, vid, A, lm.seq_length,
                                                             lm.native_params(), drop, seed=seed)
         else:
             video_words = batch.caption_widths(gen_result)
@@ -228,7 +237,7 @@ class CaptionGenerator(nn.Module):
         with torch.no_grad():
             if '_sample_tables' not in lm.__dict__:
                 lm._sample_tables = {}
-            greedy_res, _ = EF.greedy_sample(video, event.detach(), batch.c3d, ev_start, ev_len, A, lm.seq_length, lm.native_params(),
+            greedy_res, _ = EF.greedy_sample(video, event.detach(), batch.clip_rows(), ev_start, ev_len, A, lm.seq_length, lm.native_params(),
                                              table_cache=lm._sample_tables, vid=vid)
         if isinstance(gen, list) or gen.numel() == 0:
             return [], [], greedy_res, video_words          # every row drew <eos> first (OldModel.sample returns [] then, :186-187)
@@ -237,8 +246,9 @@ class CaptionGenerator(nn.Module):
         labels[:, 1:T + 1] = gen
         arena = getattr(lm, '_echr_arena_ref', None)
         sink = EF.GradSink(arena, lm.native_params()) if arena is not None else None
-        logp = EF.DecoderBatchFunction.apply(video, event, batch.c3d, ev_start, ev_len, lm._tokens(labels, batch.device), A,
-                                             EF.rows_disjoint(batch.soi), drop, sink, vid, *lm.native_params())
+        logp = EF.DecoderBatchFunction.apply(video, event, batch.clip_rows(), ev_start, ev_len, lm._tokens(labels, batch.device), A,
+                                             EF.rows_disjoint(batch.soi), drop, sink, vid,
+                                             *(tuple(lm.native_params()) + self._batch_clip_tail(batch)))
         return gen, EF.GatherTokens.apply(logp, gen), greedy_res, video_words
 
     def _event_context_groups(self, batch, groups, ech, ev_start, ev_len, vid, drop, params):
@@ -260,13 +270,21 @@ class CaptionGenerator(nn.Module):
                                                           (1, 0, 0, fm.fst_mode()), *params)
         return event
 
-    def _check_batch_options(self):
-        """What the batched entry points do not cover yet (follow-ups): an initial state from the contexts, 'CH' rows."""
+    def _check_batch_options(self, batch=None):
+        """What the batched entry points do not cover yet (follow-ups): an initial state from the contexts, a batch per data-parallel rank;
+        and the batch must have been built for the model's frame-level context (VideoBatch.from_videos(..., clip_context_type=))."""
         if getattr(self.opt, 'CG_init_feats_type', ''):
             raise NotImplementedError("CG_init_feats_type=%r: batches start from the zero state (an initial state that reads the scene vector 'V' -- or "
                                       "any other context -- takes one video per call)" % (self.opt.CG_init_feats_type,))
-        if self.clip_parts() != 1:
-            raise NotImplementedError("clip_context_type=%r: batches attend over the C3D rows ('CC') only" % (self.opt.clip_context_type,))
+        # (batch None: the entry builds the batch itself, for this model's clip context)
+        have = self.clip_parts() if batch is None else getattr(batch, 'clip_parts', 1)
+        if self.clip_parts() != have:
+            if have == 1:
+                raise NotImplementedError("clip_context_type=%r: a plain batch attends over the C3D rows ('CC') only -- build it for the model's "
+                                          "clip context: VideoBatch.from_videos(..., clip_context_type=%r)"
+                                          % (self.opt.clip_context_type, self.opt.clip_context_type))
+            raise ValueError('the batch was built for clip_context_type=%r, the model has %r'
+                             % (getattr(batch, 'clip_context_type', 'CC'), self.opt.clip_context_type))
         arena = getattr(self, '_echr_arena', None)
         if arena is not None and (getattr(arena, 'early_grad_hook', None) is not None or getattr(arena, 'early_reducer', None) is not None):
             raise NotImplementedError('data-parallel gradient hand-over (parallel.EarlyReducer / DataParallelStep) takes one video per rank and '

@@ -226,6 +226,8 @@ SYMBOLS = [
     ('echr_train_step_batch', i32, [C.POINTER(TrainStepArgs), C.POINTER(BatchExt), c_f, c_f, C.c_void_p]),
     ('echr_train_step_batch_tap_ws_floats', i64, [C.POINTER(TrainStepArgs), C.POINTER(BatchExt)]),
     ('echr_train_step_batch_tap', i32, [C.POINTER(TrainStepArgs), C.POINTER(BatchExt), c_f, c_f, c_f, C.c_void_p]),
+    ('echr_train_step_batch_clip_ws_floats', i64, [C.POINTER(TrainStepArgs), C.POINTER(ClipStepArgs), C.POINTER(BatchExt)]),
+    ('echr_train_step_batch_clip', i32, [C.POINTER(TrainStepArgs), C.POINTER(ClipStepArgs), C.POINTER(BatchExt), c_f, c_f, c_f, C.c_void_p]),
     ('echr_handover_wait', i32, [i32, C.c_void_p]),
     ('echr_clamp', i32, [c_f, i64, f32, C.c_void_p]),
     ('echr_clamp_adam', i32, [c_f, c_f, c_f, c_f, i64, i32, C.c_double, C.c_double, C.c_double, C.c_double, f32, C.c_void_p]),

@@ -10,6 +10,10 @@ the event intervals / anchors become batch-absolute row indices, and every event
     cut to the video's own step count (no 1/V);
   * gradients are the sum over the videos, then ONE clamp and ONE Adam step;
   * a batched call consumes ONE dropout counter and keys every site by the batch-global element index.
+
+A batch is built for ONE frame-level context (`clip_context_type`, default 'CC'): with 'CH' / 'CC+CH' the decoder attends over
+`clip_rows()` -- tap, or [c3d | tap] -- and d tap gains the attended rows' gradient; the entry points refuse a batch built for another
+context than the model's.
 """
 import numpy as np
 import torch
@@ -39,10 +43,18 @@ class VideoBatch(object):
                                         a video's mask is zero behind ITS OWN step count S_v (column 1 + S_v onwards)
       S                                 decoder steps of the stacked labels; steps[v] = S_v
       event_slices                      slice of the event axis per video; split(x) cuts a [N_tot, ...] result accordingly
+      clip_context_type, clip_parts     the frame-level context the batch was built for: 1 = 'CC' (default), 2 = 'CH', 3 = 'CC+CH';
+                                        clip_rows() is the decoder's row source -- c3d, tap or [c3d | tap]
     """
 
-    def __init__(self, c3d, tap, lda, row_offset, event_offset, soi, ind, labels=None, masks=None):
+    def __init__(self, c3d, tap, lda, row_offset, event_offset, soi, ind, labels=None, masks=None, clip_context_type='CC'):
         self.c3d, self.tap, self.lda = c3d, tap, lda
+        # the frame-level context the batch is built for, tested with `in` as CaptionGenerator.clip_parts does ('CCCH' means 'CC+CH')
+        self.clip_context_type = clip_context_type
+        self.clip_parts = (1 if 'CC' in clip_context_type else 0) | (2 if 'CH' in clip_context_type else 0)
+        if not self.clip_parts:
+            raise ValueError("clip_context_type=%r: a batch attends over 'CC', 'CH' or 'CC+CH' rows" % (clip_context_type,))
+        self._clip_rows = None
         self.row_offset = np.asarray(row_offset, dtype=np.int64)
         self.event_offset = np.asarray(event_offset, dtype=np.int64)
         self.soi = np.asarray(soi, dtype=np.int64).reshape(-1, 2)
@@ -59,7 +71,7 @@ class VideoBatch(object):
 
     # ---- construction -------------------------------------------------------------------------------------------------------
     @classmethod
-    def from_videos(cls, videos, device=None, tap_model=None, tap_fn=None):
+    def from_videos(cls, videos, device=None, tap_model=None, tap_fn=None, clip_context_type='CC'):
         """`videos`: a list of dicts with the arguments of a single-video call -- 'c3d' [T, D], 'tap' [T', Ht], 'lda' [lda_dim], 'ind' [N_v],
         'soi' [N_v, 2] (indices local to the video) and, for training, 'labels' / 'masks' [N_v, L_v] -- or a dict of parallel lists under
         the same keys.  Features may be numpy arrays or tensors on any device; they are concatenated on `device` (default: the device of
@@ -67,7 +79,9 @@ class VideoBatch(object):
         With `tap_model` (a models.SST on the GPU) the videos need no 'tap': `tap` is the encoder's forward_batch over the concatenated c3d --
         ONE call for the V videos -- and keeps its autograd graph into the encoder; a 'tap' entry is then ignored.
         `tap_fn(c3d_all, rows)` (instead of tap_model): any other producer of the [T_tot, Ht] matrix from the concatenated c3d and the row
-        offsets (fused.JointBatchStep runs the encoder into its own buffers, without a graph)."""
+        offsets (fused.JointBatchStep runs the encoder into its own buffers, without a graph).
+        `clip_context_type`: the model's frame-level context ('CC', 'CH', 'CC+CH'); the batched entry points refuse a batch built for
+        another one."""
         if isinstance(videos, dict):
             n = len(videos['c3d'])
             videos = [{k: v[i] for k, v in videos.items()} for i in range(n)]
@@ -127,7 +141,7 @@ class VideoBatch(object):
         else:
             tap_all = torch.cat(taps, 0) if tap_model is None else tap_model.forward_batch(c3d_all, rows)[0]
         return cls(c3d_all, tap_all, torch.stack(ldas, 0), rows, counts, np.concatenate(sois, 0), np.concatenate(inds, 0),
-                   labels, masks)
+                   labels, masks, clip_context_type=clip_context_type)
 
     @staticmethod
     def _stack_labels(videos, counts):
@@ -231,11 +245,29 @@ class VideoBatch(object):
     def video(self, v):
         """Video v as the dict of a single-video call (local indices, its own label width and step count)."""
         s, r0, r1 = self.event_slices[v], int(self.row_offset[v]), int(self.row_offset[v + 1])
-        d = dict(c3d=self.c3d[r0:r1], tap=self.tap[r0:r1], lda=self.lda[v], soi=self.soi[s] - r0, ind=self.ind[s] - r0)
+        d = dict(c3d=self.c3d[r0:r1], tap=self.tap[r0:r1], lda=self.lda[v], soi=self.soi[s] - r0, ind=self.ind[s] - r0,
+                 clip_context_type=self.clip_context_type)
         if self.labels is not None:
             w = self.steps[v] + 1          # S_v steps read label columns 0 .. S_v - 1 and target columns 1 .. S_v
             d['labels'], d['masks'] = self.labels[s, :w], self.masks[s, :w]
         return d
+
+    def clip_rows(self):
+        """The decoder's row source over the T_tot rows: c3d ('CC'), tap ('CH') or [c3d | tap] ('CC+CH'; formed once per batch by
+        functional.clip_rows and cached).  It carries no graph: the decoder's backward returns d tap itself."""
+        if self.clip_parts == 1:
+            return self.c3d
+        if self.clip_parts == 2:
+            return self.tap
+        if self._clip_rows is None:
+            from . import functional as EF
+            self._clip_rows = EF.clip_rows(self.c3d, self.tap)
+        return self._clip_rows
+
+    @property
+    def clip_col0(self):
+        """First tap column of clip_rows() (the decoder's d tap reads the row gradient from there)."""
+        return self.c3d.shape[1] if self.clip_parts == 3 else 0
 
     def dev(self, name):
         """int32 device copy of 'vid' / 'row_offset' (cached)."""

@@ -37,6 +37,7 @@ __global__ __launch_bounds__(256) void live_rows_kernel(const int* __restrict__ 
 // Rows t*N + n that are not live (behind a caption's last masked position on the compacted one-call path) count as zero: skipped, never read
 // as values.  mode 0: plain read-modify-write of out (no two events share a row); 1: atomic adds; 2: slab[(n*A + a)*nc + c] (fixed order).
 constexpr int RG_SLOTS = 8;
+constexpr int RG_LIST_MAX_S = 4096;          // row_grad_scatter_list_kernel: 16 KB of LDS flags at most
 __global__ __launch_bounds__(256) void row_grad_scatter_kernel(const float* __restrict__ WT, const float* __restrict__ DATT, const int* __restrict__ live,
                                                                const int* __restrict__ ev_start, const int* __restrict__ ev_len,
                                                                float* __restrict__ out, long ld, float* __restrict__ slab, int S, int N, int A, int nc, int mode) {
@@ -52,6 +53,52 @@ __global__ __launch_bounds__(256) void row_grad_scatter_kernel(const float* __re
         for (int t = 0; t < S; ++t) {
             const long rn = (long)t * N + n;
             if (live && !live[rn]) continue;
+            const float v = DATT[rn * nc + c];
+            const float* w = WT + rn * A + a0;
+#pragma unroll
+            for (int k = 0; k < RG_SLOTS; ++k)
+                if (k < na) s[k] += w[k] * v;
+        }
+#pragma unroll
+        for (int k = 0; k < RG_SLOTS; ++k) {
+            if (k >= na) break;
+            if (mode == 2) slab[((long)n * A + a0 + k) * nc + c] = s[k];
+            else if (mode == 1) atomicAdd(out + (start + a0 + k) * ld + c, s[k]);
+            else out[(start + a0 + k) * ld + c] += s[k];
+        }
+    }
+}
+
+// The same term with the compacted row list read directly (echr_train_step_batch_clip): the workgroup of an (event, chunk) first marks its event's
+// live steps in LDS -- lv[t] = 1 for every listed row t*N + n' with n' == n -- then runs the loop above in the same t order, so the sums are those
+// of row_grad_scatter_kernel bit for bit.  No [S*N] flag array, no fill and no marking launch in front of it.  act == nullptr: every row is live.
+// Dynamic LDS: S ints.  Dead rows are skipped, never read as values.
+__global__ __launch_bounds__(256) void row_grad_scatter_list_kernel(const float* __restrict__ WT, const float* __restrict__ DATT, const int* __restrict__ act,
+                                                                    int n_act, const int* __restrict__ ev_start, const int* __restrict__ ev_len,
+                                                                    float* __restrict__ out, long ld, float* __restrict__ slab, int S, int N, int A, int nc,
+                                                                    int mode) {
+    extern __shared__ int lv[];
+    const int n = blockIdx.y, a0 = blockIdx.x * RG_SLOTS;
+    const int len = ev_len[n];
+    if (a0 >= len) return;          // (uniform over the workgroup: in front of every barrier)
+    const int na = min(RG_SLOTS, len - a0);
+    const long start = ev_start[n];
+    if (act) {
+        for (int t = threadIdx.x; t < S; t += 256) lv[t] = 0;
+        __syncthreads();
+        for (int i = threadIdx.x; i < n_act; i += 256) {
+            const int r = act[i], t = r / N;
+            if (r >= 0 && t < S && r - t * N == n) lv[t] = 1;
+        }
+        __syncthreads();
+    }
+    for (int c = threadIdx.x; c < nc; c += 256) {
+        float s[RG_SLOTS];
+#pragma unroll
+        for (int k = 0; k < RG_SLOTS; ++k) s[k] = 0.f;
+        for (int t = 0; t < S; ++t) {
+            if (act && !lv[t]) continue;
+            const long rn = (long)t * N + n;
             const float v = DATT[rn * nc + c];
             const float* w = WT + rn * A + a0;
 #pragma unroll
@@ -98,7 +145,7 @@ int clip_rows(const float* c3d, int Dc, const float* tap, int Ht, float* rows, i
     return check_launch("clip_rows");
 }
 
-int row_grad(const echr_dec_args* a, const echr_dec_grads* g, const echr_row_grad_args* r, hipStream_t st) {
+int row_grad(const echr_dec_args* a, const echr_dec_grads* g, const echr_row_grad_args* r, hipStream_t st, bool list_form) {
     ECHR_REQUIRE(a && g && r, "decoder_row_grad: null arguments");
     ECHR_REQUIRE(a->ws && g->ws_bwd && r->out && r->ws, "decoder_row_grad: missing buffers");
     ECHR_REQUIRE(r->ncols > 0 && r->col0 >= 0 && r->col0 + r->ncols <= a->D && r->ld >= r->ncols,
@@ -118,7 +165,10 @@ int row_grad(const echr_dec_args* a, const echr_dec_grads* g, const echr_row_gra
     echr_gemm_desc d = desc_nn(DG1, 4 * H, a->w_ih[1] + E + r->col0, cin1, w.DATT, nc, (int)SN, nc, 4 * H);
     RC(gemm(d, st));
     const int* live = nullptr;
-    if (g->active_rows && g->n_active > 0) {
+    const bool compact = g->active_rows && g->n_active > 0;
+    // (the list form keeps S flags in LDS: a step count beyond that budget -- never a caption's -- takes the flag form)
+    list_form = list_form && config().row_grad_list && S <= RG_LIST_MAX_S;
+    if (compact && !list_form) {
         RC(fill_zero(reinterpret_cast<float*>(w.LIVE), SN, st));
         hipLaunchKernelGGL(live_rows_kernel, dim3((g->n_active + 255) / 256), dim3(256), 0, st, g->active_rows, g->n_active, w.LIVE);
         RC(check_launch("row_grad_live"));
@@ -128,6 +178,10 @@ int row_grad(const echr_dec_args* a, const echr_dec_grads* g, const echr_row_gra
     float* slab = nullptr;
     if (fixed) { slab = det_scratch(DET_ROWG, (size_t)N * A * nc); if (!slab) return -12; }
     const int mode = fixed ? 2 : (a->rows_disjoint ? 0 : 1);
+    if (list_form)
+        hipLaunchKernelGGL(row_grad_scatter_list_kernel, dim3((A + RG_SLOTS - 1) / RG_SLOTS, N), dim3(256), sizeof(int) * (size_t)S, st, WT, w.DATT,
+                           compact ? g->active_rows : nullptr, compact ? g->n_active : 0, a->ev_start, a->ev_len, r->out, (long)r->ld, slab, S, N, A, nc, mode);
+    else
     hipLaunchKernelGGL(row_grad_scatter_kernel, dim3((A + RG_SLOTS - 1) / RG_SLOTS, N), dim3(256), 0, st, WT, w.DATT, live, a->ev_start, a->ev_len,
                        r->out, (long)r->ld, slab, S, N, A, nc, mode);
     RC(check_launch("row_grad_scatter"));

@@ -36,7 +36,7 @@ Config& config() {
     static Config c = {env_int("ECHR_GEMM_BF16X3", 1), env_int("ECHR_ATT_SLOTS", 2),
                        env_int("ECHR_GEMM_H2", 1), env_int("ECHR_PERSIST", 1), env_int("ECHR_PERSIST_STAMPS", 0),
                        getenv("ECHR_GEMM_TILE") ? (int)getenv("ECHR_GEMM_TILE")[0] : 0, env_int("ECHR_GEMM_SPLIT", 0), env_int("ECHR_PERSIST_BWD", 1), env_int("ECHR_PERSIST_H2", 1),
-                       env_int("ECHR_PERSIST_COOP", 0), 0, env_int("ECHR_PERSIST_SPIN_LIMIT", 0), env_int("ECHR_SST_PERSIST", 1), 0, env_int("ECHR_PERSIST_SAMPLE", 1), env_int("ECHR_POSEMB_ROWS", 1), env_int("ECHR_GEMM_SKINNY", 1), env_int("ECHR_POSEMB_PACKED", 1), env_int("ECHR_PAIR_TABLES", 1), 0, env_int("ECHR_PERSIST_SAMPLE_MAX", 512), env_int("ECHR_DETERMINISTIC", 0)};
+                       env_int("ECHR_PERSIST_COOP", 0), 0, env_int("ECHR_PERSIST_SPIN_LIMIT", 0), env_int("ECHR_SST_PERSIST", 1), 0, env_int("ECHR_PERSIST_SAMPLE", 1), env_int("ECHR_POSEMB_ROWS", 1), env_int("ECHR_GEMM_SKINNY", 1), env_int("ECHR_POSEMB_PACKED", 1), env_int("ECHR_PAIR_TABLES", 1), 0, env_int("ECHR_PERSIST_SAMPLE_MAX", 512), env_int("ECHR_DETERMINISTIC", 0), env_int("ECHR_ROW_GRAD_LIST", 1)};
     return c;
 }
 
@@ -1629,6 +1629,7 @@ extern "C" int echr_config_set(const char* key, int32_t value) {
     else if (!strcmp(key, "persist_inject_timeout")) c.persist_inject_timeout = value;
     else if (!strcmp(key, "persist_spin_limit")) c.persist_spin_limit = value;
     else if (!strcmp(key, "deterministic")) c.deterministic = value ? 1 : 0;
+    else if (!strcmp(key, "row_grad_list")) c.row_grad_list = value ? 1 : 0;
     else if (!strcmp(key, "gemm_tile")) c.gemm_tile = value;          // tuning only: ASCII code of the tile selector ('1','6','a','b','c','s'), 0 = heuristics
     else if (!strcmp(key, "gemm_split")) c.gemm_split = value;        // tuning only: forced k-slice count of auto-split products, 0 = heuristics
     else if (!strcmp(key, "att_slots")) { ECHR_REQUIRE(value == 2 || value == 4 || value == 8, "config_set: att_slots must be 2, 4 or 8"); c.att_slots = value; }

@@ -17,7 +17,7 @@ struct ProfScope {
 };
 
 // runtime switches (initial values from the environment, changeable through echr_config_set)
-struct Config { int gemm_bf16x3; int att_slots; int gemm_h2; int persist; int persist_stamps; int gemm_tile; int gemm_split; int persist_bwd; int persist_h2; int persist_coop; int persist_inject_timeout; int persist_spin_limit; int sst_persist; int diag_skip; int persist_sample; int posemb_rows; int gemm_skinny; int posemb_packed; int pair_tables; int persist_sample_force_eos; int persist_sample_max; int deterministic; };
+struct Config { int gemm_bf16x3; int att_slots; int gemm_h2; int persist; int persist_stamps; int gemm_tile; int gemm_split; int persist_bwd; int persist_h2; int persist_coop; int persist_inject_timeout; int persist_spin_limit; int sst_persist; int diag_skip; int persist_sample; int posemb_rows; int gemm_skinny; int posemb_packed; int pair_tables; int persist_sample_force_eos; int persist_sample_max; int deterministic; int row_grad_list; };
 // diag_skip (diagnostic, tools/skip_bounds.py; results are WRONG while a bit is set): 1 = h2 operand packs, 2 = clamp+Adam kernel, 4 = att_post, 16 = every fp32-path product (gemm_f32 / t128 / bf16x3), 32 = every h2 product, 64 / 128 = the h2m16 product kernel loads only / computes only (tools/h2_ablate.py),
 // 8 = embedding scatter-add -- the launch is skipped, which bounds what removing / hiding that work could gain
 Config& config();
@@ -116,7 +116,9 @@ void handover_request(bool on, echr_handover_fn cb = nullptr, void* user = nullp
 void decoder_bwd_views(const echr_dec_args* a, const echr_dec_grads* g, const float** dg1, const float** dpall);
 const float* decoder_fwd_wt(const echr_dec_args* a);
 int check_dims_public(const echr_dec_args* a, const char* who);
-int row_grad(const echr_dec_args* a, const echr_dec_grads* g, const echr_row_grad_args* r, hipStream_t st);
+// list_form: the context-term scatter reads the compacted active_rows list itself (echr_train_step_batch_clip; "row_grad_list" = 0 or a step count
+// beyond its LDS flags: the flag form every other entry launches)
+int row_grad(const echr_dec_args* a, const echr_dec_grads* g, const echr_row_grad_args* r, hipStream_t st, bool list_form = false);
 int clip_rows(const float* c3d, int Dc, const float* tap, int Ht, float* rows, int Tv, hipStream_t st);
 int join_tail(hipStream_t st);          // make st wait for an asynchronous decoder-backward tail (decoder.hip); no-op when none is pending
 int persist_read_stamps(unsigned long long* dst, int max_entries);

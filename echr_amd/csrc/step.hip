@@ -294,6 +294,27 @@ extern "C" int echr_train_step_batch_tap(const echr_train_step_args* a, const ec
     ECHR_REQUIRE(!a->w_init, "train_step_batch_tap: an initial state (CG_init_feats_type) is not part of the batched step");
     return train_step_impl(a, stream, true, a->host_nll ? nullptr : weight, nullptr, x, video_loss, row_offset);
 }
+// The frame-level contexts over a batch: echr_train_step_batch (and, with g_tap, echr_train_step_batch_tap) with the row source of
+// echr_train_step_clip over the T_tot concatenated rows.  ev_start is batch-absolute, so the attention, its backward and the clip-row gradient
+// address the rows as they do for one video; g_tap gains the anchors' rows, the 'VH' span over each video's own rows and the clip-row gradient.
+extern "C" int64_t echr_train_step_batch_clip_ws_floats(const echr_train_step_args* a, const echr_clip_step_args* x, const echr_batch_ext* bx) {
+    return (a && x && bx && bx->n_videos > 0 && (x->clip_parts == 2 || x->clip_parts == 3)) ? carve_step(a, true, x, bx).total : -1;
+}
+extern "C" int echr_train_step_batch_clip(const echr_train_step_args* a, const echr_clip_step_args* x, const echr_batch_ext* bx, const float* weight,
+                                          float* video_loss, const int32_t* row_offset, void* stream) {
+    ECHR_REQUIRE(a && x && (x->clip_parts == 2 || x->clip_parts == 3), "train_step_batch_clip: clip_parts must be 2 ('CH') or 3 ('CC+CH')");
+    ECHR_REQUIRE(bx && bx->n_videos > 0 && bx->n_videos <= a->dec.N && bx->video, "train_step_batch_clip: the batch extension needs 0 < n_videos <= N and video");
+    ECHR_REQUIRE(x->c3d && x->Dc > 0 && a->tap && a->Ht > 0, "train_step_batch_clip: c3d / tap missing");
+    ECHR_REQUIRE(a->dec.D == (x->clip_parts == 3 ? x->Dc + a->Ht : a->Ht), "train_step_batch_clip: dec.D = %d is not the width of the clip rows", a->dec.D);
+    ECHR_REQUIRE(a->host_nll || weight, "train_step_batch_clip: the criterion weights are missing (device `weight`, or host_index with host_nll = 1)");
+    ECHR_REQUIRE(!(a->host_nll && weight), "train_step_batch_clip: host_nll = 1 carries the weights in host_index: pass weight = NULL");
+    ECHR_REQUIRE(!a->prepared && !a->defer_update && !a->handover && !a->mid_cb,
+                 "train_step_batch_clip: prepared, defer_update, handover and mid_cb are not part of the batched step");
+    ECHR_REQUIRE(!a->w_init, "train_step_batch_clip: an initial state (CG_init_feats_type) is not part of the batched step");
+    ECHR_REQUIRE(!a->g_tap || !a->forward_only, "train_step_batch_clip: g_tap needs the backward pass (forward_only must be 0)");
+    ECHR_REQUIRE(!a->g_tap || a->vh_offset < 0 || row_offset, "train_step_batch_clip: the 'VH' scene gradient needs row_offset");
+    return train_step_impl(a, stream, true, a->host_nll ? nullptr : weight, x, bx, video_loss, row_offset);
+}
 static int train_step_impl(const echr_train_step_args* a, void* stream, bool rw, const float* rw_dev, const echr_clip_step_args* x, const echr_batch_ext* bx,
                            float* video_loss, const int32_t* row_offset) {
     ECHR_REQUIRE(a && a->ws && a->host_index && a->loss && a->g_loss && a->flat_g && (a->tap || a->event_parts == 1), "train_step: missing buffers");
@@ -312,7 +333,7 @@ static int train_step_impl(const echr_train_step_args* a, void* stream, bool rw,
     RC(join_tail(st));          // (a deferred update of the previous call: it reads the index region this call is about to restage)
     const StepWs L = carve_step(a, rw, x, bx);
     ECHR_REQUIRE(a->ws_floats >= L.total, "train_step: workspace holds %lld floats, %ld needed (echr_train_step%s_ws_floats)", (long long)a->ws_floats, L.total,
-                 bx ? "_batch" : (x ? "_clip" : (rw ? "_rw" : "")));
+                 bx ? (x ? "_batch_clip" : "_batch") : (x ? "_clip" : (rw ? "_rw" : "")));
     float* ws = a->ws;
     // 'CC+CH': the row source [c3d | tap] is formed first, ahead of every fork of this call (the decoder's event-independent part reads it)
     if (x && x->clip_parts == 3) RC(clip_rows(c3d, Dc, a->tap, a->Ht, ws + L.rows, a->dec.Tv, st));
@@ -476,7 +497,7 @@ static int train_step_impl(const echr_train_step_args* a, void* stream, bool rw,
         // 'CH' / 'CC+CH': d tap_feats gains the attended rows' gradient (the tap columns of the row source), from what the backward left
         echr_row_grad_args r;
         r.col0 = x->clip_parts == 3 ? Dc : 0; r.ncols = a->Ht; r.out = a->g_tap; r.ld = a->Ht; r.ws = ws + L.row_grad;
-        RC(row_grad(&d, &g, &r, st));
+        RC(row_grad(&d, &g, &r, st, bx != nullptr));          // (a batch: the scatter reads the compacted row list itself, clipctx.hip)
     }
     if (vh && bx) {
         // a batch: video v's scene vector is the mean over ITS rows -- d tap[r, :] += d video[v, vh span] / T_v for r in [row_offset[v], row_offset[v+1])

@@ -415,25 +415,34 @@ class DecoderFunction(torch.autograd.Function):
 
 class DecoderBatchFunction(torch.autograd.Function):
     """DecoderFunction over the events of several videos: `video` is [V, Dv], one scene vector per video, and event n reads row vid[n]
-    (echr_decoder_fwd_batch / _bwd_batch); backward returns d video [V, Dv].  Zero initial state, 'CC' rows."""
+    (echr_decoder_fwd_batch / _bwd_batch); backward returns d video [V, Dv].  Zero initial state.  `c3d` is the batch's row source
+    (VideoBatch.clip_rows()); with 'CH' / 'CC+CH' the parameters are followed by `tap` (batch.tap) and `col0` (int: its first column in the
+    row source), and backward returns d tap [T_tot, Ht] (echr_decoder_row_grad behind echr_decoder_bwd_batch)."""
 
     @staticmethod
     def forward(ctx, video, event, c3d, ev_start, ev_len, tokens, A, disjoint, drop, sink, vid, *params):
-        return _decoder_forward(ctx, video, event, c3d, ev_start, ev_len, tokens, A, disjoint, drop, sink, None, None, None, 0, params, vid=vid)
+        # (*params, or *params + (tap, col0): the clip pair trails the parameters, so 'CC' callers pass what they always passed)
+        tap, col0 = None, 0
+        if params and isinstance(params[-1], int):
+            tap, col0, params = params[-2], params[-1], params[:-2]
+        return _decoder_forward(ctx, video, event, c3d, ev_start, ev_len, tokens, A, disjoint, drop, sink, None, None, tap, col0, params, vid=vid,
+                                tap_arg=11 + len(params))
 
     @staticmethod
     def backward(ctx, g_logp):
-        g_video, g_event, _, _, grads = _decoder_backward(ctx, g_logp)
-        return (g_video, g_event, None, None, None, None, None, None, None, None, None) + grads
+        g_video, g_event, _, g_tap, grads = _decoder_backward(ctx, g_logp)
+        out = (g_video, g_event, None, None, None, None, None, None, None, None, None) + grads
+        return out + (g_tap, None) if ctx.tap_meta is not None else out
 
 
-def _decoder_forward(ctx, video, event, c3d, ev_start, ev_len, tokens, A, disjoint, drop, sink, prep, h0, tap, col0, params, vid=None):
+def _decoder_forward(ctx, video, event, c3d, ev_start, ev_len, tokens, A, disjoint, drop, sink, prep, h0, tap, col0, params, vid=None, tap_arg=12):
     # tap / col0 ('CH', 'CC+CH'): the rows c3d[:, col0 : col0 + tap width] are tap[:Tv]; backward returns d tap (echr_decoder_row_grad)
     # vid (multi-video batch): int32 [N] device, video is then [V, Dv]
     lib = L.load()
     ctx.sink = sink
     ctx.vid = vid
     ctx.tap_meta = (tuple(tap.shape), int(col0)) if tap is not None else None
+    ctx.tap_arg = tap_arg          # position of `tap` among the Function's inputs (needs_input_grad)
     event = _f32c(event)
     h0 = _f32c(h0) if h0 is not None else None          # [N, 3H] initial state (OldModel.init_hidden, CG_init_feats_type); None = zeros
     S, N = tokens.shape
@@ -491,7 +500,7 @@ def _decoder_backward(ctx, g_logp):
     g_video = torch.empty_like(video) if ctx.needs_input_grad[0] else None
     h0 = ctx.h0
     g_h0 = torch.empty_like(h0) if (h0 is not None and ctx.needs_input_grad[11]) else None
-    want_tap = ctx.tap_meta is not None and ctx.needs_input_grad[12]
+    want_tap = ctx.tap_meta is not None and ctx.needs_input_grad[ctx.tap_arg]
     a = _dec_args(ps, c3d, ev_start, ev_len, event, video, tokens, A, S, ws, logp, disjoint, train=train, h0=h0)
     wsb = torch.empty(lib.echr_decoder_ws_bwd_floats(C.byref(a)), device=event.device, dtype=torch.float32)
     gp = [L.ptr(x) for x in grads]

@@ -224,14 +224,16 @@ class FusedTrainStep(object):
         device tensor; `last_video_losses` holds the per-video losses as a device vector [V].  step=False stops after the backward pass and
         exposes the summed gradients as `.grad` views, forward_only=True stops after the criterion, as __call__ does.
         `device_criterion=True` hands targets / masks / weights over as device tensors (all rows) instead of with the index vectors;
-        `video_losses=False` skips the per-video losses (`last_video_losses` is then None)."""
+        `video_losses=False` skips the per-video losses (`last_video_losses` is then None).
+        A model with 'CH' / 'CC+CH' rows takes a batch built for them (VideoBatch.from_videos(..., clip_context_type=)) and runs
+        echr_train_step_batch_clip."""
         if unsupported:
             raise NotImplementedError('FusedTrainStep.batch does not take %s: tap_grad / defer_update / prepared / handover over a batch are '
                                       'follow-ups (one video per call)' % sorted(unsupported))
         if getattr(self, '_prepared', False):
             raise NotImplementedError('prepare() runs ahead of ONE video\'s call: it does not combine with batch()')
         m = self.model
-        m._check_batch_options()
+        m._check_batch_options(batch)
         if batch.labels is None:
             raise ValueError('the batch carries no labels')
         a, lib = self.a, self.lib
@@ -251,9 +253,17 @@ class FusedTrainStep(object):
         self._pending_deferred = False
         self.last_video_losses = torch.empty(batch.n_videos, device=self.dev, dtype=torch.float32) if video_losses else None
         self._keep = self._keep + (w_dev, video)
-        L.check(lib.echr_train_step_batch(C.byref(a), C.byref(self.bx), L.ptr(w_dev) if w_dev is not None else None,
-                                          L.ptr(self.last_video_losses) if video_losses else None, L.stream_ptr()), 'train_step_batch')
+        self._call_batch(L.ptr(w_dev) if w_dev is not None else None, L.ptr(self.last_video_losses) if video_losses else None)
         return self._finish(slot, st, forward_only)
+
+    def _call_batch(self, weight, video_loss):
+        """echr_train_step_batch on what _setup(batch=) described, or with 'CH' / 'CC+CH' echr_train_step_batch_clip (no g_tap, no row offsets)."""
+        a, lib = self.a, self.lib
+        if self.clip != 1:
+            L.check(lib.echr_train_step_batch_clip(C.byref(a), C.byref(self.x), C.byref(self.bx), weight, video_loss, None, L.stream_ptr()),
+                    'train_step_batch_clip')
+        else:
+            L.check(lib.echr_train_step_batch(C.byref(a), C.byref(self.bx), weight, video_loss, L.stream_ptr()), 'train_step_batch')
 
     def _batch_tap(self, batch, tap_grad, ro_dev, video_losses, g_loss=None, step=True):
         """The caption side of the joint iteration over a batch (echr_train_step_batch_tap; fused.JointBatchStep): batch() with the zero-filled
@@ -273,8 +283,12 @@ class FusedTrainStep(object):
         if g_loss is not None:
             a.g_loss = L.ptr(g_loss)
         try:
-            L.check(self.lib.echr_train_step_batch_tap(C.byref(a), C.byref(self.bx), None, L.ptr(video_losses), L.ptr(ro_dev, torch.int32),
-                                                       L.stream_ptr()), 'train_step_batch_tap')
+            if self.clip != 1:          # the clip-row gradient joins the anchors' rows and the 'VH' span in tap_grad
+                L.check(self.lib.echr_train_step_batch_clip(C.byref(a), C.byref(self.x), C.byref(self.bx), None, L.ptr(video_losses),
+                                                            L.ptr(ro_dev, torch.int32), L.stream_ptr()), 'train_step_batch_clip')
+            else:
+                L.check(self.lib.echr_train_step_batch_tap(C.byref(a), C.byref(self.bx), None, L.ptr(video_losses), L.ptr(ro_dev, torch.int32),
+                                                           L.stream_ptr()), 'train_step_batch_tap')
         finally:
             a.g_loss = self.one.data_ptr()
         return self._finish(slot, st, False)
@@ -424,7 +438,11 @@ class FusedTrainStep(object):
         a.drop = drop.c()
         if batch is not None:
             self.bx = L.BatchExt(batch.n_videos, None, lda.data_ptr(), None, None)
-            need = lib.echr_train_step_batch_ws_floats(C.byref(a), C.byref(self.bx))
+            if self.clip != 1:
+                self.x.rw, self.x.weight = 0, None          # (not read by the batched entry: the weights travel as echr_train_step_batch's)
+                need = lib.echr_train_step_batch_clip_ws_floats(C.byref(a), C.byref(self.x), C.byref(self.bx))
+            else:
+                need = lib.echr_train_step_batch_ws_floats(C.byref(a), C.byref(self.bx))
         elif self.clip != 1:
             self.x.rw = 0 if weights is None else 1
             need = lib.echr_train_step_clip_ws_floats(C.byref(a), C.byref(self.x))
@@ -619,11 +637,11 @@ class SelfCriticalBatchStep(object):
             ps = lm.native_params()
             sampled = None
             if gen_result is None:
-                sampled = EF.sample_train_batch(video, event, batch.c3d, ev_start, ev_len, vid, A, lm.seq_length, ps, drop,
+                sampled = EF.sample_train_batch(video, event, batch.clip_rows(), ev_start, ev_len, vid, A, lm.seq_length, ps, drop,
                                                 seed=lm._sample_seed(), defer=True)
             if '_sample_tables' not in lm.__dict__:
                 lm._sample_tables = {}
-            greedy_f = EF.greedy_sample(video, event, batch.c3d, ev_start, ev_len, A, lm.seq_length, ps, table_cache=lm._sample_tables,
+            greedy_f = EF.greedy_sample(video, event, batch.clip_rows(), ev_start, ev_len, A, lm.seq_length, ps, table_cache=lm._sample_tables,
                                         vid=vid, defer=True)
             # the one host sync of the iteration: the first read drains the stream, both decodes included
             if sampled is not None:
@@ -665,7 +683,7 @@ class SelfCriticalBatchStep(object):
         f._pending_deferred = False
         self.last_video_losses = f.last_video_losses = torch.empty(V, device=f.dev, dtype=torch.float32)
         f._keep = f._keep + (video,)
-        L.check(lib.echr_train_step_batch(C.byref(a), C.byref(f.bx), None, L.ptr(self.last_video_losses), L.stream_ptr()), 'train_step_batch')
+        f._call_batch(None, L.ptr(self.last_video_losses))
         return f._finish(slot, st, False), gen_h, greedy_h, torch.from_numpy(r), vw
 
 
@@ -891,7 +909,8 @@ class JointBatchStep(object):
         from .batch import VideoBatch
         lib, f, tm = self.lib, self.fused, self.tap_model
         m = f.model
-        m._check_batch_options()
+        # (a list of video dicts becomes a batch built for the model's clip context below; a ready batch must already be)
+        m._check_batch_options(videos_or_batch if isinstance(videos_or_batch, VideoBatch) else None)
         if getattr(f, '_prepared', False):
             raise NotImplementedError('prepare() runs ahead of ONE video\'s call: it does not combine with JointBatchStep')
         L.check(lib.echr_check_async(), 'joint_batch_step (asynchronous failure of an earlier call)')
@@ -908,9 +927,11 @@ class JointBatchStep(object):
             if src.labels is None:
                 raise ValueError('the batch carries no labels')
             tap = self._sst_forward(src.c3d, src.row_offset)
-            batch = VideoBatch(src.c3d, tap, src.lda, src.row_offset, src.event_offset, src.soi, src.ind, src.labels, src.masks)
+            batch = VideoBatch(src.c3d, tap, src.lda, src.row_offset, src.event_offset, src.soi, src.ind, src.labels, src.masks,
+                               clip_context_type=src.clip_context_type)
         else:
-            batch = VideoBatch.from_videos(videos_or_batch, device=self.dev, tap_fn=self._sst_forward)
+            batch = VideoBatch.from_videos(videos_or_batch, device=self.dev, tap_fn=self._sst_forward,
+                                           clip_context_type=m.opt.clip_context_type)
             if batch.labels is None:
                 raise ValueError('the videos carry no labels / masks')
         sa, bx, dc, ro, ro_dev, ps, c3d, V, T, K = self._sst

@@ -357,6 +357,9 @@ def make_attsat(name, clip_context_type='CC'):
 #   vbctx  5 videos incl. a one-event video, scene context from all three sources ('VLVCVH': per-video column means), 'ER3', small vocabulary
 #   vb24 / vb33  24 / 33 videos of 4 events, small vocabulary
 #   vbscst 4 videos of 3..6 events at the 'tiny_eos' widths (self-critical training over a batch)
+#   vbch / vbcch  the vbctx construction (5 videos incl. a one-event video, 'VLVCVH', 'ER3', ragged label widths) with at most 16 events and the
+#          frame-level context 'CH' (D = 512: the persistent recurrences, all three gradient paths into tap) / 'CC+CH' (D = 1012: launch-per-phase)
+#   vbch33 'CH' over 33 videos of 4 events (132 rows: launch-per-phase recurrences, the chain sampler, the event encoder's general kernels)
 VBATCH = {
     'vb16': dict(opt=dict(CG_vocab_size=5000, CG_seq_length=19), V=16, events=(2, 6), max_events=64, seg=(3, 60), T=(40, 160), L=(12, 21), seed=1000),
     'vbctx': dict(opt=dict(video_context_type='VLVCVH', CG_vocab_size=300, CG_seq_length=7), V=5, events=(1, 4), single=2, max_events=64, seg=(3, 30),
@@ -370,6 +373,14 @@ VBATCH = {
     'vbscst': dict(opt=dict(video_dim=20, hidden_dim=24, lda_dim=12, d_feats=32, d_o=32, n_head=4, CG_rnn_size=32, CG_input_encoding_size=16,
                             CG_att_hid_size=24, CG_vocab_size=30, CG_seq_length=6),
                    V=4, events=(3, 6), max_events=64, seg=(3, 9), T=(12, 24), L=(8, 8), seed=1400),
+    # frame-level contexts over a batch (tests/golden/case_clip_batch.npz; case seeds picked like vb16's: tools/make_golden_clip_batch.py asserts
+    # the greedy margins)
+    'vbch': dict(opt=dict(clip_context_type='CH', video_context_type='VLVCVH', CG_vocab_size=300, CG_seq_length=7), V=5, events=(1, 4), single=2,
+                 max_events=16, seg=(3, 30), T=(30, 60), L=(6, 9), seed=1500),
+    'vbcch': dict(opt=dict(clip_context_type='CC+CH', video_context_type='VLVCVH', CG_vocab_size=300, CG_seq_length=7), V=5, events=(1, 4), single=2,
+                  max_events=16, seg=(3, 30), T=(30, 60), L=(6, 9), seed=1600),
+    'vbch33': dict(opt=dict(clip_context_type='CH', CG_vocab_size=300, CG_seq_length=7), V=33, events=(4, 4), max_events=132, seg=(3, 30), T=(30, 80),
+                   L=(6, 9), seed=1700),
 }
 
 

@@ -147,7 +147,8 @@ def self_critical(a, opt, dev, loader, tap_model, cg_model, cg_opt, start):
         else:
             rewards = [overlap_reward(v['labels']) for v in vids]          # reward_fn is called once per video (step.current_video)
             with torch.no_grad():
-                batch = VideoBatch.from_videos([{k: v[k] for k in ('c3d', 'lda', 'ind', 'soi')} for v in vids], device=dev, tap_model=tap_model)
+                batch = VideoBatch.from_videos([{k: v[k] for k in ('c3d', 'lda', 'ind', 'soi')} for v in vids], device=dev, tap_model=tap_model,
+                                                 clip_context_type=opt.clip_context_type)
             step = SelfCriticalBatchStep(fused, lambda gen, greedy: rewards[step.current_video](gen, greedy))
             loss = step(batch)[0]
         history.append(float(loss) / a.m_batch)
@@ -168,6 +169,8 @@ def main(argv=None):
     ap.add_argument('--segments', type=int, default=32)
     ap.add_argument('--vocab', type=int, default=500)
     ap.add_argument('--lr', type=float, default=5e-4)
+    ap.add_argument('--clip_context_type', type=str, default='CC', help="frame-level context: 'CC', 'CH' or 'CC+CH' (opts.py:130); the batches of "
+                                                                        "--m_batch V are built for it")
     ap.add_argument('--save', type=str, default='')
     ap.add_argument('--resume', type=str, default='', help='checkpoint written by --save (or by the reference): models + optimiser state')
     ap.add_argument('--quiet', action='store_true')
@@ -176,6 +179,7 @@ def main(argv=None):
     a = ap.parse_args(argv)
     dev = torch.device('cuda')
     opt = synth.default_opt(vocab_size=a.vocab, seq_length=10, K=32, lr=a.lr)
+    opt.clip_context_type = a.clip_context_type
     torch.manual_seed(0)
     tap_model = models.setup_tap(opt).to(dev)
     cg_model = echr_amd.CaptionGenerator(opt).to(dev)

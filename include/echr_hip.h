@@ -341,7 +341,9 @@ int echr_stream_join(void* stream);
  * that tail first) and ADDS the gradient of columns [col0, col0 + ncols) of the row source into out (row r at out + r * ld):
  *   out[start_n + a] += sum_t WT[t,n,a] . (d gates1[t,n] . W_ih1[:, E + col0 + c])  +  (d P_all . W_c2a[:, col0 + c])[start_n + a]
  * for a < len_n, summed over every event that covers the row.  rows_disjoint = 1: plain updates; otherwise atomic adds, or with the
- * "deterministic" configuration per-event slabs folded per row in event order (bit-identical run to run).  out must hold dec.Tv rows. */
+ * "deterministic" configuration per-event slabs folded per row in event order (bit-identical run to run).  out must hold dec.Tv rows.
+ * Equally valid behind echr_decoder_bwd_batch on the same ws / ws_bwd (the batch extension changes neither workspace layout; ev_start and
+ * dec.Tv are then batch-absolute / T_tot, and a row only ever gains from events of its own video). */
 typedef struct {
     int32_t col0;            /* first wanted column of the row source ('CH': 0, 'CC+CH': Dc) */
     int32_t ncols;           /* wanted columns (Ht) */
@@ -791,6 +793,18 @@ int echr_train_step_batch(const echr_train_step_args* a, const echr_batch_ext* x
 int64_t echr_train_step_batch_tap_ws_floats(const echr_train_step_args* a, const echr_batch_ext* x);
 int echr_train_step_batch_tap(const echr_train_step_args* a, const echr_batch_ext* x, const float* weight, float* video_loss,
                               const int32_t* row_offset, void* stream);
+/* echr_train_step_batch with the frame-level context 'CH' / 'CC+CH' of echr_clip_step_args.  In `a`, dec.D / dec.Tv describe the ROW SOURCE
+ * over the T_tot concatenated rows (D = Ht or Dc + Ht) and dec.c3d is ignored: the library takes tap itself ('CH') or forms [c3d | tap] in
+ * the call's workspace ('CC+CH'); x->c3d [T_tot, Dc] feeds the event encoder.  ev_start is batch-absolute, so an event attends over rows of
+ * its own video only.  Criterion weights as in echr_train_step_batch (`weight`, or behind the mask in host_index); x->rw and x->weight are
+ * not read.  With a->g_tap set ([T_tot, Ht], zero-filled by the caller) it is also the joint form of echr_train_step_batch_tap: g_tap gains
+ * the anchors' rows through the block-diagonal event encoder, the 'VH' span spread over each video's own rows (row_offset, device [V+1];
+ * may be NULL without 'VH') and the clip-row gradient (echr_decoder_row_grad's sum; its context term reads the compacted active rows
+ * directly, "row_grad_list"), all three scaled by a->g_loss, and is final when the call returns.  Not with prepared, defer_update,
+ * handover, mid_cb nor an initial state; dec.D must match clip_parts. */
+int64_t echr_train_step_batch_clip_ws_floats(const echr_train_step_args* a, const echr_clip_step_args* x, const echr_batch_ext* bx);
+int echr_train_step_batch_clip(const echr_train_step_args* a, const echr_clip_step_args* x, const echr_batch_ext* bx, const float* weight,
+                               float* video_loss, const int32_t* row_offset, void* stream);
 
 /* Hand-over points of the LAST echr_train_step issued with handover = 1 (which: 0 = logit layer, 1 = LSTM layers): makes `stream` wait
  * until that range of flat_g is final.  0 = `stream` now waits; 1 = the call recorded no such point (a configuration without the
@@ -857,6 +871,9 @@ int echr_prof_event_overhead(double* ms, int64_t* n);
  *                      writes per-chunk / per-(event, position) / per-workgroup slabs that fold launches sum in index order (scratch owned by the
  *                      library, grown on demand).  Two runs on the same inputs, parameters and dropout seed then agree bit for bit in loss and
  *                      every gradient (the reference's CPU path is run-to-run deterministic at a fixed thread count); cost: see DESIGN.md section 4h
+ *   "row_grad_list" 0/1 (default 1, ECHR_ROW_GRAD_LIST) echr_train_step_batch_clip: the clip-row gradient's context term reads the compacted active
+ *                      rows directly and marks an event's live steps in LDS; 0 = the flag form of the single-video entries (fill + mark + scatter).
+ *                      The same sums in the same order either way
  *   "persist_stamps" 0/1/2 diagnostic phase stamps of the forward (1) / reverse (2) pair, see echr_persist_read_stamps
  *   "gemm_tile", "gemm_split"  tuning overrides of the GEMM tile / split-K heuristics (0 = heuristics; tools/gemm_bench.py only) */
 int echr_config_set(const char* key, int32_t value);
