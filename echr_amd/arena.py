@@ -101,6 +101,16 @@ class ParamArena(object):
     def end_backward_pass(self):
         self._whole_zero_task = None
 
+    def zero_as_final(self):
+        """The step's gradient is ZERO (a data-parallel rank without work of its own): no stale `.grad` view or deferred clamp survives, the
+        whole buffer is zero-filled and noted as such -- the state a raw-pointer backward leaves behind, with nothing added."""
+        for p in self.params:
+            p.grad = None
+        self.deferred_clamp = None
+        self.end_backward_pass()
+        self.flat_g.zero_()
+        self._zeroed = [(0, self.total)]
+
     def note_zeroed(self, lo, hi):
         """A backward Function zero-filled flat_g[lo:hi] this step (GradSink.take)."""
         self._zeroed.append((lo, hi))

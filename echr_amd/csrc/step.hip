@@ -272,7 +272,8 @@ extern "C" int echr_train_step_batch(const echr_train_step_args* a, const echr_b
     ECHR_REQUIRE(a && x && x->n_videos > 0 && x->n_videos <= a->dec.N && x->video, "train_step_batch: the batch extension needs 0 < n_videos <= N and video");
     ECHR_REQUIRE(a->host_nll || weight, "train_step_batch: the criterion weights are missing (device `weight`, or host_index with host_nll = 1)");
     ECHR_REQUIRE(!(a->host_nll && weight), "train_step_batch: host_nll = 1 carries the weights in host_index: pass weight = NULL");
-    ECHR_REQUIRE(!a->prepared && !a->defer_update && !a->g_tap && !a->handover, "train_step_batch: prepared, defer_update, g_tap and handover are not part of the batched step");
+    ECHR_REQUIRE(!a->prepared && !a->defer_update && !a->g_tap, "train_step_batch: prepared, defer_update and g_tap are not part of the batched step");
+    ECHR_REQUIRE(!a->handover || !a->do_step, "train_step_batch: handover = 1 needs do_step = 0 (the caller reduces the gradients, then steps)");
     ECHR_REQUIRE(!a->w_init, "train_step_batch: an initial state (CG_init_feats_type) is not part of the batched step");
     return train_step_impl(a, stream, true, a->host_nll ? nullptr : weight, nullptr, x, video_loss);
 }
@@ -289,8 +290,8 @@ extern "C" int echr_train_step_batch_tap(const echr_train_step_args* a, const ec
     ECHR_REQUIRE(!(a->host_nll && weight), "train_step_batch_tap: host_nll = 1 carries the weights in host_index: pass weight = NULL");
     ECHR_REQUIRE(a->g_tap && a->tap && a->Ht > 0 && !a->forward_only, "train_step_batch_tap: g_tap / tap missing (without g_tap this is echr_train_step_batch)");
     ECHR_REQUIRE(a->vh_offset < 0 || row_offset, "train_step_batch_tap: the 'VH' scene gradient needs row_offset");
-    ECHR_REQUIRE(!a->prepared && !a->defer_update && !a->handover && !a->mid_cb,
-                 "train_step_batch_tap: prepared, defer_update, handover and mid_cb are not part of the batched step");
+    ECHR_REQUIRE(!a->prepared && !a->defer_update && !a->mid_cb, "train_step_batch_tap: prepared, defer_update and mid_cb are not part of the batched step");
+    ECHR_REQUIRE(!a->handover || !a->do_step, "train_step_batch_tap: handover = 1 needs do_step = 0 (the caller reduces the gradients, then steps)");
     ECHR_REQUIRE(!a->w_init, "train_step_batch_tap: an initial state (CG_init_feats_type) is not part of the batched step");
     return train_step_impl(a, stream, true, a->host_nll ? nullptr : weight, nullptr, x, video_loss, row_offset);
 }
@@ -308,8 +309,8 @@ extern "C" int echr_train_step_batch_clip(const echr_train_step_args* a, const e
     ECHR_REQUIRE(a->dec.D == (x->clip_parts == 3 ? x->Dc + a->Ht : a->Ht), "train_step_batch_clip: dec.D = %d is not the width of the clip rows", a->dec.D);
     ECHR_REQUIRE(a->host_nll || weight, "train_step_batch_clip: the criterion weights are missing (device `weight`, or host_index with host_nll = 1)");
     ECHR_REQUIRE(!(a->host_nll && weight), "train_step_batch_clip: host_nll = 1 carries the weights in host_index: pass weight = NULL");
-    ECHR_REQUIRE(!a->prepared && !a->defer_update && !a->handover && !a->mid_cb,
-                 "train_step_batch_clip: prepared, defer_update, handover and mid_cb are not part of the batched step");
+    ECHR_REQUIRE(!a->prepared && !a->defer_update && !a->mid_cb, "train_step_batch_clip: prepared, defer_update and mid_cb are not part of the batched step");
+    ECHR_REQUIRE(!a->handover || !a->do_step, "train_step_batch_clip: handover = 1 needs do_step = 0 (the caller reduces the gradients, then steps)");
     ECHR_REQUIRE(!a->w_init, "train_step_batch_clip: an initial state (CG_init_feats_type) is not part of the batched step");
     ECHR_REQUIRE(!a->g_tap || !a->forward_only, "train_step_batch_clip: g_tap needs the backward pass (forward_only must be 0)");
     ECHR_REQUIRE(!a->g_tap || a->vh_offset < 0 || row_offset, "train_step_batch_clip: the 'VH' scene gradient needs row_offset");

@@ -170,23 +170,7 @@ class FusedTrainStep(object):
             slot, st = self._setup(tap_feats, c3d_feats, lda_feats, lm_labels, ind_select_list, soi_select_list, targets, masks, step, forward_only,
                                    tap_grad, defer_update)
             a.prepared = 0
-        a.handover = 1 if (handover and not step and not forward_only) else 0
-        if a.handover and handover_cb is not None:
-            # ONE ctypes trampoline per object (building a CFUNCTYPE per call is host time inside the timed multi-rank loop); it forwards to
-            # the callback of the current call.  An exception inside a ctypes callback cannot propagate: kept and re-raised behind the call
-            self._cb_error, self._cb_cur = None, handover_cb
-            if getattr(self, '_cb_keep', None) is None:
-                def _tramp(which, stream, _user):
-                    try:
-                        self._cb_cur(int(which), int(stream))
-                    except BaseException as e:          # noqa: BLE001
-                        self._cb_error = e
-                self._cb_keep = L.HANDOVER_FN(_tramp)
-                self._cb_ptr = C.cast(self._cb_keep, C.c_void_p)
-            a.handover_cb = self._cb_ptr
-        else:
-            a.handover_cb = None
-        a.handover_user = None
+        self._set_handover(handover and not step and not forward_only, handover_cb)
         self.mid_called = False
         if mid_cb is not None:
             self._mid_cur = mid_cb
@@ -212,10 +196,35 @@ class FusedTrainStep(object):
             L.check(lib.echr_train_step_clip(C.byref(a), C.byref(self.x), L.stream_ptr()), 'train_step_clip')
         else:
             L.check(lib.echr_train_step(C.byref(a), L.stream_ptr()), 'train_step')
+        self._raise_cb_error()
+        return self._finish(slot, st, forward_only)
+
+    def _set_handover(self, on, handover_cb):
+        """The hand-over fields of the argument struct for the call about to be made (echr_train_step_args.handover / handover_cb)."""
+        a = self.a
+        a.handover = 1 if on else 0
+        if a.handover and handover_cb is not None:
+            # ONE ctypes trampoline per object (building a CFUNCTYPE per call is host time inside the timed multi-rank loop); it forwards to
+            # the callback of the current call.  An exception inside a ctypes callback cannot propagate: kept and re-raised behind the call
+            self._cb_error, self._cb_cur = None, handover_cb
+            if getattr(self, '_cb_keep', None) is None:
+                def _tramp(which, stream, _user):
+                    try:
+                        self._cb_cur(int(which), int(stream))
+                    except BaseException as e:          # noqa: BLE001
+                        self._cb_error = e
+                self._cb_keep = L.HANDOVER_FN(_tramp)
+                self._cb_ptr = C.cast(self._cb_keep, C.c_void_p)
+            a.handover_cb = self._cb_ptr
+        else:
+            a.handover_cb = None
+        a.handover_user = None
+
+    def _raise_cb_error(self):
+        a = self.a
         if (a.handover_cb or a.mid_cb) and getattr(self, '_cb_error', None) is not None:
             e, self._cb_error = self._cb_error, None
             raise e
-        return self._finish(slot, st, forward_only)
 
     def batch(self, batch, step=True, forward_only=False, device_criterion=False, video_losses=True, **unsupported):
         """One iteration over a multi-video batch (echr_amd.batch.VideoBatch) as ONE call (echr_train_step_batch): the reference's
@@ -228,8 +237,18 @@ class FusedTrainStep(object):
         A model with 'CH' / 'CC+CH' rows takes a batch built for them (VideoBatch.from_videos(..., clip_context_type=)) and runs
         echr_train_step_batch_clip."""
         if unsupported:
-            raise NotImplementedError('FusedTrainStep.batch does not take %s: tap_grad / defer_update / prepared / handover over a batch are '
-                                      'follow-ups (one video per call)' % sorted(unsupported))
+            raise NotImplementedError('FusedTrainStep.batch does not take %s: tap_grad / defer_update / prepared over a batch are follow-ups '
+                                      '(one video per call); the hand-over points of a batch are batch_handover(), the data-parallel step over '
+                                      'batches is DataParallelBatchStep' % sorted(unsupported))
+        return self._batch_call(batch, step, forward_only, device_criterion, video_losses)
+
+    def batch_handover(self, batch, handover_cb=None, device_criterion=False, video_losses=True):
+        """batch(step=False) with the data-parallel hand-over points recorded (echr_train_step_args.handover over echr_train_step_batch /
+        echr_train_step_batch_clip): `handover_cb(which, stream_ptr)` is called on the host from inside the call at each point, as __call__
+        does for one video; echr_handover_wait is the event form.  DataParallelBatchStep is the caller."""
+        return self._batch_call(batch, False, False, device_criterion, video_losses, True, handover_cb)
+
+    def _batch_call(self, batch, step, forward_only, device_criterion, video_losses, handover=False, handover_cb=None):
         if getattr(self, '_prepared', False):
             raise NotImplementedError('prepare() runs ahead of ONE video\'s call: it does not combine with batch()')
         m = self.model
@@ -248,12 +267,14 @@ class FusedTrainStep(object):
             w_dev = torch.from_numpy(w).to(self.dev)
         slot, st = self._setup(batch.tap, batch.c3d, video, batch.labels, batch.ind, batch.soi, tg, mk, step, forward_only, None, False,
                                weights=w, batch=batch)
-        a.prepared = a.handover = 0
-        a.handover_cb = a.handover_user = a.mid_cb = a.mid_user = None
+        a.prepared = 0
+        a.mid_cb = a.mid_user = None
+        self._set_handover(handover and not step and not forward_only, handover_cb)
         self._pending_deferred = False
         self.last_video_losses = torch.empty(batch.n_videos, device=self.dev, dtype=torch.float32) if video_losses else None
         self._keep = self._keep + (w_dev, video)
         self._call_batch(L.ptr(w_dev) if w_dev is not None else None, L.ptr(self.last_video_losses) if video_losses else None)
+        self._raise_cb_error()
         return self._finish(slot, st, forward_only)
 
     def _call_batch(self, weight, video_loss):
@@ -265,18 +286,19 @@ class FusedTrainStep(object):
         else:
             L.check(lib.echr_train_step_batch(C.byref(a), C.byref(self.bx), weight, video_loss, L.stream_ptr()), 'train_step_batch')
 
-    def _batch_tap(self, batch, tap_grad, ro_dev, video_losses, g_loss=None, step=True):
+    def _batch_tap(self, batch, tap_grad, ro_dev, video_losses, g_loss=None, step=True, handover=False, handover_cb=None):
         """The caption side of the joint iteration over a batch (echr_train_step_batch_tap; fused.JointBatchStep): batch() with the zero-filled
         `tap_grad` [T_tot, Ht] receiving d loss / d batch.tap.  `ro_dev`: the batch's row offsets as an int32 device vector [V+1];
         `video_losses`: device [V] out; `g_loss`: a one-element device tensor that scales every gradient (lambda2; None = 1) -- the returned
-        loss and the per-video losses stay unscaled."""
+        loss and the per-video losses stay unscaled.  `handover` / `handover_cb` (with step=False): as batch_handover."""
         a, m = self.a, self.model
         with torch.no_grad():
             video = EF._f32c(m.get_video_context_batch(batch))
         slot, st = self._setup(batch.tap, batch.c3d, video, batch.labels, batch.ind, batch.soi, batch.targets, batch.crit_masks, step, False,
                                tap_grad, False, weights=batch.criterion_weights(), batch=batch)
-        a.prepared = a.handover = 0
-        a.handover_cb = a.handover_user = a.mid_cb = a.mid_user = None
+        a.prepared = 0
+        a.mid_cb = a.mid_user = None
+        self._set_handover(handover and not step, handover_cb)
         self._pending_deferred = False
         self._keep = self._keep + (video, g_loss, ro_dev)
         self.last_video_losses = video_losses
@@ -291,6 +313,7 @@ class FusedTrainStep(object):
                                                            L.stream_ptr()), 'train_step_batch_tap')
         finally:
             a.g_loss = self.one.data_ptr()
+        self._raise_cb_error()
         return self._finish(slot, st, False)
 
     def _set_tap(self, tap, tap_grad, defer_update, step, forward_only):
@@ -620,6 +643,13 @@ class SelfCriticalBatchStep(object):
         video_words int64 [V] host); T = max(video_words).  `gen_result` [N_tot, >= T]: score these captions instead of drawing them;
         `reward` ([N_tot,T] or [N_tot]): use it instead of calling reward_fn.  step=False stops after the backward pass (the summed
         gradients as `.grad` views).  The batch need not carry labels.  Raises ValueError when every video's sample has width 0."""
+        return self._run(batch, gen_result, reward, step, False, None)
+
+    def handover(self, batch, handover_cb=None, gen_result=None, reward=None):
+        """__call__(step=False) with the data-parallel hand-over points recorded, as FusedTrainStep.batch_handover (DataParallelBatchStep)."""
+        return self._run(batch, gen_result, reward, False, True, handover_cb)
+
+    def _run(self, batch, gen_result, reward, step, handover, handover_cb):
         f = self.fused
         m = f.model
         lm = m.lm_model
@@ -678,12 +708,14 @@ class SelfCriticalBatchStep(object):
         a, lib = f.a, f.lib
         slot, st = f._setup(batch.tap, batch.c3d, video, labels, batch.ind, batch.soi, labels[:, 1:], mask, step, False, None, False,
                             drop=drop, weights=w, batch=batch)
-        a.prepared = a.handover = 0
-        a.handover_cb = a.handover_user = a.mid_cb = a.mid_user = None
+        a.prepared = 0
+        a.mid_cb = a.mid_user = None
+        f._set_handover(handover and not step, handover_cb)
         f._pending_deferred = False
         self.last_video_losses = f.last_video_losses = torch.empty(V, device=f.dev, dtype=torch.float32)
         f._keep = f._keep + (video,)
         f._call_batch(None, L.ptr(self.last_video_losses))
+        f._raise_cb_error()
         return f._finish(slot, st, False), gen_h, greedy_h, torch.from_numpy(r), vw
 
 
@@ -898,14 +930,16 @@ class JointBatchStep(object):
             raise ValueError('%s must be the concatenated [T_tot, K] = [%d, %d] matrix or one [T_v, K] matrix per video (got %s)' % (name, T, K, tuple(x.shape)))
         return x
 
-    def __call__(self, videos_or_batch, tap_masks, tap_labels, w1, step=True):
+    def __call__(self, videos_or_batch, tap_masks, tap_labels, w1, step=True, handover=False, handover_cb=None, cg_done=None):
         """One iteration; returns lambda1 * tap_loss + lambda2 * cg_loss as a 0-d device tensor (no host sync).  `videos_or_batch`: the dicts
         VideoBatch.from_videos takes (no 'tap' needed), or a ready VideoBatch whose `tap` is ignored: the batch's tap_feats are the proposal
         encoder's forward of this call.  `tap_masks` / `tap_labels`: the concatenated [T_tot, K] matrices or one [T_v, K] per video; `w1`:
         one [K] weight vector for all videos, or one per video (a list, or [V, K]).  `tap_loss` / `cg_loss` hold the two sums over the videos,
         `last_tap_losses` / `last_video_losses` the per-video terms [V] (device tensors), `last_batch` the VideoBatch the call ran on.
         step=False stops after the backward passes and leaves both models' summed gradients in their arenas (`.grad` views); the proposal
-        encoder's `.grad` views are set after a step as well."""
+        encoder's `.grad` views are set after a step as well.  `handover` / `handover_cb` (with step=False): the caption call records the
+        data-parallel hand-over points of the captioner's arena (FusedTrainStep.batch_handover); `cg_done()`: called right behind the caption
+        call, where the captioner's whole arena is final in stream order and the proposal encoder's backward is not yet queued."""
         from .batch import VideoBatch
         lib, f, tm = self.lib, self.fused, self.tap_model
         m = f.model
@@ -955,7 +989,9 @@ class JointBatchStep(object):
         L.check(lib.echr_tap_bce_fwd_batch(L.ptr(B['scores']), L.ptr(mk), L.ptr(lb), L.ptr(ww), w1_ld, L.ptr(ro_dev, torch.int32), V, K,
                                            L.ptr(B['tap_losses']), L.ptr(B['loss']), L.ptr(B['part']), L.stream_ptr()), 'tap_bce_fwd_batch')
         # the caption side: forward, criterion, backward, d loss / d batch.tap, clamp + Adam -- ONE call; lambda2 travels as its g_loss scalar
-        cg = f._batch_tap(batch, B['g_tap'], ro_dev, B['video_losses'], g_loss=self.lam[1:], step=step)
+        cg = f._batch_tap(batch, B['g_tap'], ro_dev, B['video_losses'], g_loss=self.lam[1:], step=step, handover=handover, handover_cb=handover_cb)
+        if cg_done is not None:
+            cg_done()
         # d (lambda1 * sum_v tap_loss_v) / d scores, then the proposal encoder's backward with d loss / d tap_feats from the caption side
         L.check(lib.echr_tap_bce_bwd_batch(L.ptr(B['scores']), L.ptr(mk), L.ptr(lb), L.ptr(ww), w1_ld, L.ptr(ro_dev, torch.int32), V, K, T,
                                            L.ptr(self.lam[:1]), L.ptr(B['g_scores']), L.stream_ptr()), 'tap_bce_bwd_batch')
@@ -979,39 +1015,12 @@ class JointBatchStep(object):
         return self.lam[0] * B['loss'][0] + self.lam[1] * cg
 
 
-class DataParallelStep(object):
-    """One data-parallel iteration on the one-call path: the SAME host path for every world size.
+class _DataParallelExchange(object):
+    """What DataParallelStep and DataParallelBatchStep share: the hand-over ranges of the captioner's arena, how an early range reaches the
+    collective stream (`via`), the ONE wait, the exchange instrumentation.  The collective sequencing itself is parallel.StagedExchange."""
 
-    rank r:  echr_train_step(step=False, handover) on its own video  ->  SUM over ranks of the flat gradient arena  ->  clip_gradient + Adam,
-    identically on every rank -- the reference's m_batch accumulation (train.py:281-283 sums the per-video gradients, :313-317 clamps the sum
-    and steps once) with the m_batch videos on R ranks: SUM without 1/R, clamp AFTER the reduce.
-
-    The exchange is staged: the backward pass inside the call hands over two contiguous arena ranges long before its last kernel -- the
-    logit layer (35 % of the gradient bytes, final ~0.1 ms behind the reverse recurrence, on the library's tail stream) and the three LSTM
-    layers (39 %, final behind the grouped weight-gradient product on its prepare stream).  For each, the library calls back on the host
-    right behind the last launch that writes the range (echr_train_step_args.handover_cb) and the range's collective is queued with that
-    library stream as the CURRENT stream (torch.distributed orders its collective stream behind the current stream), so it runs beside the
-    rest of the tail and the event encoder's backward without any further stream or event (`via='event'`: the older form -- one side
-    stream per range waits for the hand-over event, echr_handover_wait); the remaining ranges (event encoder + embedding, attention: 26 %)
-    follow from the caller's stream, asynchronously too, and the caller's stream waits ONCE, for the last collective queued.  Every collective starts behind the reverse recurrence and is
-    waited for before clamp + Adam, i.e. before the next iteration's forward recurrence: no collective kernel is ever resident beside a
-    persistent pair.  `overlap=False`: ONE collective on the whole arena behind the call."""
-
-    def exchange_report(self):
-        """After a measured pass (`self.measure = True`, then a device synchronisation): median / max of the time the caller's stream
-        waited for the collectives per step [ms] -- the EXPOSED part of the exchange -- and the ranges of the last step."""
-        ms = sorted(a.elapsed_time(b) for a, b in self.exposed_ms)
-        self.exposed_ms = []
-        names = {0: 'logit layer', 1: 'LSTM layers'}
-        rmap = {(lo, hi): names[w] for w, (lo, hi) in self._range.items()}
-        return dict(exposed_ms_median=round(ms[len(ms) // 2], 4) if ms else None, exposed_ms_max=round(ms[-1], 4) if ms else None, steps=len(ms),
-                    ranges=[dict(name=rmap.get((r['lo'], r['hi']), 'remainder'), bytes=r['bytes'], early=r['early']) for r in self.last_ranges],
-                    n_collectives=self.n_collectives, n_early=self.n_early)
-
-    def __init__(self, fused, group=None, overlap=True, algo=None, via=None):
+    def _init_exchange(self, fused, group, overlap, algo, via):
         from . import parallel
-        if fused.clip != 1:
-            raise NotImplementedError("DataParallelStep runs clip_context_type 'CC' only (the 'CH' row gradient is not part of its hand-over stages)")
         self.P, self.fused, self.group, self.overlap, self.algo = parallel, fused, group, bool(overlap), algo
         # how an early range reaches the collective stream: 'callback' (default) = queued from inside the call with the library's stream current
         # (echr_train_step_args.handover_cb), 'event' = a side stream per range that waits for the hand-over event (echr_handover_wait)
@@ -1027,6 +1036,7 @@ class DataParallelStep(object):
                 self.ranges.append((which,) + tuple(ar.span(slots)))
         self._range = {which: (lo, hi) for which, lo, hi in self.ranges}
         self.side = [torch.cuda.Stream(device=fused.dev) for _ in self.ranges] if (self.overlap and self.via != 'callback') else []
+        self.ex = parallel.StagedExchange(group, algo)
         self.n_collectives = 0
         self.n_early = 0
         # opt-in instrumentation (bench.py's exchange pass): HIP events around the caller's stream's wait for the collectives -- what of the
@@ -1034,6 +1044,18 @@ class DataParallelStep(object):
         self.measure = False
         self.exposed_ms = []
         self.last_ranges = []
+
+    def exchange_report(self):
+        """After a measured pass (`self.measure = True`, then a device synchronisation): median / max of the time the caller's stream
+        waited for the collectives per step [ms] -- the EXPOSED part of the exchange -- and the ranges of the last step."""
+        ms = sorted(a.elapsed_time(b) for a, b in self.exposed_ms)
+        self.exposed_ms = []
+        names = {0: 'logit layer', 1: 'LSTM layers'}
+        rmap = {(lo, hi): names[w] for w, (lo, hi) in self._range.items()}
+        return dict(exposed_ms_median=round(ms[len(ms) // 2], 4) if ms else None, exposed_ms_max=round(ms[-1], 4) if ms else None, steps=len(ms),
+                    ranges=[dict(name=r.get('name') or rmap.get((r['lo'], r['hi']), 'remainder'), bytes=r['bytes'], early=r['early'])
+                            for r in self.last_ranges],
+                    n_collectives=self.n_collectives, n_early=self.n_early)
 
     def _in_order(self):
         """True when every collective of this step ran on ONE in-order device stream (the nccl = RCCL backend: one stream per process group
@@ -1046,76 +1068,262 @@ class DataParallelStep(object):
         except Exception:
             return False
 
+    @staticmethod
+    def _active():
+        import torch.distributed as dist
+        return dist.is_available() and dist.is_initialized()
+
+    def _at_handover(self, which, stream_ptr):
+        # host callback from inside the one-call step, right behind the last launch that writes the range: the collective is queued with the
+        # library's own stream as the CURRENT stream, so torch.distributed orders its collective stream behind exactly this point -- no side
+        # stream, no further event (five or more streams on this runtime's four hardware queues share queues, and a wait queued on a shared
+        # queue stalls the unrelated stream behind it: measured +0.2 ms per iteration with two side streams)
+        rng = self._range.get(which)
+        if rng is None:
+            return
+        f = self.fused
+        ext = self._ext.get(stream_ptr)
+        if ext is None:
+            ext = self._ext[stream_ptr] = torch.cuda.ExternalStream(stream_ptr, device=f.dev)
+        with torch.cuda.stream(ext):
+            self.ex.reduce_early(f.arena.flat_g, rng[0], rng[1])
+
+    def _early_by_event(self):
+        """The event form (echr_handover_wait): one side stream per range."""
+        f = self.fused
+        for (which, lo, hi), s in zip(self.ranges, self.side):
+            with torch.cuda.stream(s):
+                rc = f.lib.echr_handover_wait(which, L.stream_ptr())
+                if rc < 0:
+                    L.check(rc, 'handover_wait')
+                if rc == 0:          # (1: this configuration recorded no hand-over point -- the range joins the remainder)
+                    self.ex.reduce_early(f.arena.flat_g, lo, hi)
+
+    def _wait(self):
+        """The remaining ranges are queued: the caller's stream waits ONCE, for the last collective, where one in-order stream ran them all."""
+        ex = self.ex
+        self.n_early, self.n_collectives, self.last_ranges = ex.n_early, ex.n_collectives, ex.ranges
+        ev = None
+        if self.measure:
+            ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+            ev[0].record()          # the caller's stream is behind the whole backward pass here: what follows is waiting for the wire
+        ex.wait(self._in_order())
+        self._keep = ex.works          # (the handles not waited for only have to stay alive until the last one is done)
+        if ev is not None:
+            ev[1].record()
+            self.exposed_ms.append(ev)
+
+
+class DataParallelStep(_DataParallelExchange):
+    """One data-parallel iteration on the one-call path: the SAME host path for every world size.
+
+    rank r:  echr_train_step(step=False, handover) on its own video  ->  SUM over ranks of the flat gradient arena  ->  clip_gradient + Adam,
+    identically on every rank -- the reference's m_batch accumulation (train.py:281-283 sums the per-video gradients, :313-317 clamps the sum
+    and steps once) with the m_batch videos on R ranks: SUM without 1/R, clamp AFTER the reduce.
+
+    The exchange is staged: the backward pass inside the call hands over two contiguous arena ranges long before its last kernel -- the
+    logit layer (35 % of the gradient bytes, final ~0.1 ms behind the reverse recurrence, on the library's tail stream) and the three LSTM
+    layers (39 %, final behind the grouped weight-gradient product on its prepare stream).  For each, the library calls back on the host
+    right behind the last launch that writes the range (echr_train_step_args.handover_cb) and the range's collective is queued with that
+    library stream as the CURRENT stream (torch.distributed orders its collective stream behind the current stream), so it runs beside the
+    rest of the tail and the event encoder's backward without any further stream or event (`via='event'`: the older form -- one side
+    stream per range waits for the hand-over event, echr_handover_wait); the remaining ranges (event encoder + embedding, attention: 26 %)
+    follow from the caller's stream, asynchronously too, and the caller's stream waits ONCE, for the last collective queued.  Every collective starts behind the reverse recurrence and is
+    waited for before clamp + Adam, i.e. before the next iteration's forward recurrence: no collective kernel is ever resident beside a
+    persistent pair.  `overlap=False`: ONE collective on the whole arena behind the call.  A FusedTrainStep built for 'CH' / 'CC+CH' runs
+    echr_train_step_clip, which records the same two points (the clip-row gradient is no part of the arena)."""
+
+    def __init__(self, fused, group=None, overlap=True, algo=None, via=None):
+        self._init_exchange(fused, group, overlap, algo, via)
+
     def batch(self, *args, **kwargs):
-        """Multi-video batches (FusedTrainStep.batch) are not part of this step yet: the hand-over points are recorded by the single-video call."""
-        raise NotImplementedError('DataParallelStep takes one video per rank and call: a VideoBatch per rank is a follow-up')
+        """Multi-video batches are not part of this step: one video per rank and call."""
+        raise NotImplementedError('DataParallelStep takes one video per rank and call: a VideoBatch per rank is DataParallelBatchStep')
 
     def __call__(self, *args, **kw):
-        P, f, ar = self.P, self.fused, self.fused.arena
-        import torch.distributed as dist
-        active = dist.is_available() and dist.is_initialized()
-        pend = []
-
-        def at_handover(which, stream_ptr):
-            # host callback from inside echr_train_step, right behind the last launch that writes the range: the collective is queued with the
-            # library's own stream as the CURRENT stream, so torch.distributed orders its collective stream behind exactly this point -- no side
-            # stream, no further event (five or more streams on this runtime's four hardware queues share queues, and a wait queued on a shared
-            # queue stalls the unrelated stream behind it: measured +0.2 ms per iteration with two side streams)
-            rng = self._range.get(which)
-            if rng is None:
-                return
-            ext = self._ext.get(stream_ptr)
-            if ext is None:
-                ext = self._ext[stream_ptr] = torch.cuda.ExternalStream(stream_ptr, device=f.dev)
-            with torch.cuda.stream(ext):
-                pend.append((rng[0], rng[1], P.reduce_sum_(ar.flat_g[rng[0]:rng[1]], self.group, self.algo, async_op=True)))
-
+        f, ar = self.fused, self.fused.arena
+        active = self._active()
+        self.ex.begin()
         use_cb = self.overlap and active and self.via == 'callback'
-        loss = f(*args, step=False, handover=self.overlap and active, handover_cb=at_handover if use_cb else None, **kw)
-        n = 0
+        loss = f(*args, step=False, handover=self.overlap and active, handover_cb=self._at_handover if use_cb else None, **kw)
         if active:
-            if self.overlap and not use_cb:          # the event form (echr_handover_wait): one side stream per range
-                for (which, lo, hi), s in zip(self.ranges, self.side):
-                    with torch.cuda.stream(s):
-                        rc = f.lib.echr_handover_wait(which, L.stream_ptr())
-                        if rc < 0:
-                            L.check(rc, 'handover_wait')
-                        if rc == 0:          # (1: this configuration recorded no hand-over point -- the range joins the remainder below)
-                            pend.append((lo, hi, P.reduce_sum_(ar.flat_g[lo:hi], self.group, self.algo, async_op=True)))
-            self.n_early = len(pend)
+            if self.overlap and not use_cb:
+                self._early_by_event()
             # the remaining ranges, asynchronously as well: queued back to back on the collective stream behind the caller's stream's position
             # (= the end of the backward pass), waited for ONCE -- a blocking collective costs two cross-stream edges (10-20 us each on this
             # runtime) before the next one may even be queued
-            works = [w for _, _, w in pend]
-            pos = 0
-            rng_log = [dict(lo=lo, hi=hi, bytes=4 * (hi - lo), early=True) for lo, hi, _ in pend]
-            for lo, hi, _ in sorted(pend, key=lambda t: t[0]) + [(ar.total, ar.total, None)]:
-                if lo > pos:
-                    works.append(P.reduce_sum_(ar.flat_g[pos:lo], self.group, self.algo, async_op=True))
-                    rng_log.append(dict(lo=pos, hi=lo, bytes=4 * (lo - pos), early=False))
-                    n += 1
-                pos = max(pos, hi)
-            n += len(pend)
-            self.last_ranges = rng_log
-            ev = None
-            if self.measure:
-                ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-                ev[0].record()          # the caller's stream is behind the whole backward pass here: what follows is waiting for the wire
-            if works and self._in_order():
-                # one process group = one collective stream, in order: the caller's stream waits for the LAST collective queued (the early ones
-                # were queued first); the other handles only have to stay alive until then
-                works[-1].wait()
-                self._keep = works
-            else:
-                for w in works:
-                    w.wait()          # the caller's stream continues behind the collectives
-            if ev is not None:
-                ev[1].record()
-                self.exposed_ms.append(ev)
-        self.n_collectives = n
+            self.ex.reduce_rest(ar.flat_g)
+            self._wait()
+        else:
+            self.n_collectives = 0
         o = f.optim
         if f.grad_clip is not None:
             from .misc.utils import clip_gradient
             clip_gradient(o, f.grad_clip)          # (recorded; the clamp itself is fused into the step kernel)
         o.step()
+        return loss
+
+
+class DataParallelBatchStep(_DataParallelExchange):
+    """One data-parallel iteration over multi-video batches: the batch steps times DataParallelStep.  `inner` is a FusedTrainStep (run
+    through its batch form), a JointBatchStep or a SelfCriticalBatchStep.
+
+    rank r:  the inner step on the rank's own VideoBatch -- its shard of the update's m_batch videos (parallel.shard_batch) -- with step=False
+    and the hand-over points recorded  ->  SUM over ranks of every flat arena the step filled  ->  ONE clamp + Adam per model
+    (ClampAdam.step_flat_raw), identically on every rank.  The reference's m_batch protocol (train.py:281-283,313-317) with the videos on R
+    ranks: loss and gradients are the SUM over all videos of all ranks, no 1/R and no 1/V, every video with its own criterion normaliser,
+    the clamp AFTER the reduce.
+
+    The captioner's arena goes staged exactly as DataParallelStep's (the shared parallel.StagedExchange: the logit-layer and LSTM-layer
+    ranges from the hand-over callback, or `via='event'`; the remainder behind the call; `overlap=False`: one collective).  With a
+    JointBatchStep the remainder is queued right behind the caption call and the proposal encoder's arena follows as one more collective
+    behind echr_sst_bwd_batch.  One wait for the last collective where one in-order stream runs them all (RCCL).
+
+    A rank whose shard is empty passes None: it zero-fills its arena(s), runs no library step and queues the same collectives in the same
+    order from the caller's stream.  Which early ranges exist is the library's to say (a configuration may record neither point, or one),
+    and an empty rank cannot see it, so the ranks AGREE once: the first call of every rank records which points fired without queueing
+    from them, one two-element MIN collective (its result read on the host: the one synchronisation, of the first call only) settles the
+    set, and that call's early ranges go out behind it from the caller's stream.  From then on working ranks queue exactly the agreed
+    points from the hand-over callback (or event), empty ranks the same ranges in the same order -- LSTM layers, then logit layer from
+    the callback; logit, LSTM in the event form -- and a point outside the set joins the remainder on every rank.  A rank whose later
+    call misses an agreed point raises instead of queueing a different sequence.  Replicas never diverge, no rank blocks.
+
+    The call returns the rank-local summed loss as a 0-d device tensor (no host sync; 0 for an empty shard).  `reduce_loss=True`: the SUM
+    over ranks instead, from one further one-element collective; with `n_videos` (the update's global video count, sharded round-robin)
+    that collective also carries the per-video losses and `last_video_losses` holds the global batch's in rank-major shard order
+    (parallel.shard_order, parallel.loss_slots).  Dropout: the rank is mixed into the model's seed (OldModel.next_drop_state);
+    set_dropout_state pins it."""
+
+    def __init__(self, inner, group=None, overlap=True, algo=None, via=None, reduce_loss=False):
+        if isinstance(inner, FusedTrainStep):
+            kind, fused = 'caption', inner
+        elif isinstance(inner, JointBatchStep):
+            kind, fused = 'joint', inner.fused
+        elif isinstance(inner, SelfCriticalBatchStep):
+            kind, fused = 'scst', inner.fused
+        else:
+            raise TypeError('DataParallelBatchStep wraps a FusedTrainStep, a JointBatchStep or a SelfCriticalBatchStep')
+        self.inner, self.kind = inner, kind
+        self._init_exchange(fused, group, overlap, algo, via)
+        self.reduce_loss = bool(reduce_loss)
+        self.last_video_losses = self.last_result = None
+        self._zero = torch.zeros(1, device=fused.dev, dtype=torch.float32)
+        self.points = None          # the hand-over points the ranks agreed on (a tuple in queueing order), None before the first call
+        self._fired = set()
+
+    def _order(self, points):
+        return tuple(w for w in ((1, 0) if self.via == 'callback' else (0, 1)) if w in points and w in self._range)
+
+    def _at_handover(self, which, stream_ptr):
+        self._fired.add(which)
+        if self.points is not None and which in self.points:
+            _DataParallelExchange._at_handover(self, which, stream_ptr)
+
+    def _captioner_exchange(self, empty):
+        """Behind the caption call (an empty rank: behind its zero fill), on the caller's stream: the captioner's arena is final in stream
+        order.  First call: the agreement, then its early ranges from here; later calls: the empty rank's early ranges, the event form's
+        waits; then the remainder."""
+        import torch.distributed as dist
+        f, ex = self.fused, self.ex
+        flat = f.arena.flat_g
+        if self.overlap and self.points is None:
+            if empty:
+                have = [1, 1]
+            elif self.via == 'callback':
+                have = [int(w in self._fired) for w in (0, 1)]
+            else:
+                have = []
+                for w in (0, 1):
+                    rc = f.lib.echr_handover_wait(w, L.stream_ptr())
+                    if rc < 0:
+                        L.check(rc, 'handover_wait')
+                    have.append(int(rc == 0))
+            mask = torch.tensor(have, device=f.dev, dtype=torch.int32)
+            dist.all_reduce(mask, op=dist.ReduceOp.MIN, group=self.group)
+            self.points = self._order({w for w, ok in enumerate(mask.tolist()) if ok})
+            for w in self.points:
+                ex.reduce_early(flat, *self._range[w])
+        elif self.overlap and empty:
+            for w in self.points:
+                ex.reduce_early(flat, *self._range[w])
+        elif self.overlap:
+            if self.via != 'callback':
+                for (which, lo, hi), s in zip(self.ranges, self.side):
+                    if which in self.points:
+                        with torch.cuda.stream(s):
+                            rc = f.lib.echr_handover_wait(which, L.stream_ptr())
+                            if rc < 0:
+                                L.check(rc, 'handover_wait')
+                            if rc == 0:
+                                self._fired.add(which)
+                                ex.reduce_early(flat, lo, hi)
+            missing = [w for w in self.points if w not in self._fired]
+            if missing:
+                raise RuntimeError('this rank\'s call recorded no hand-over point %s, which the ranks agreed on at their first call: every rank '
+                                   'must keep the configuration it started with (its collectives would no longer match the other ranks\')' % missing)
+        ex.reduce_rest(flat)
+
+    def __call__(self, batch, *args, n_videos=None, **kw):
+        """`batch`: the rank's VideoBatch (JointBatchStep: or its list of video dicts), None for an empty shard; further arguments are the
+        inner step's (JointBatchStep: tap_masks, tap_labels, w1; SelfCriticalBatchStep: gen_result=, reward=).  Returns the loss; a
+        SelfCriticalBatchStep's other results are kept in `last_result`."""
+        import torch.distributed as dist
+        f, inner = self.fused, self.inner
+        active = self._active()
+        ex = self.ex.begin()
+        ho = self.overlap and active
+        cb = self._at_handover if (ho and self.via == 'callback') else None
+        empty = batch is None or (isinstance(batch, (list, tuple)) and len(batch) == 0)
+        self._fired = set()
+        self.last_result = None
+        cg_done = (lambda: self._captioner_exchange(empty)) if active else None
+        if empty:
+            L.check(f.lib.echr_check_async(), 'data_parallel_batch_step (asynchronous failure of an earlier call)')
+            if getattr(f, '_pending_deferred', False):
+                f.join()
+                f._pending_deferred = False
+            f.arena.zero_as_final()
+            if self.kind == 'joint':
+                inner.tap_arena.zero_as_final()
+            loss, losses = self._zero[0], None
+        elif self.kind == 'caption':
+            loss = f.batch_handover(batch, cb, **kw) if ho else f.batch(batch, step=False, **kw)
+            losses = f.last_video_losses
+        elif self.kind == 'scst':
+            out = inner.handover(batch, cb, *args, **kw) if ho else inner(batch, *args, step=False, **kw)
+            loss, self.last_result = out[0], out[1:]
+            losses = inner.last_video_losses
+        else:
+            loss = inner(batch, *args, step=False, handover=ho, handover_cb=cb, cg_done=cg_done, **kw)
+            losses = inner.lam[0] * inner.last_tap_losses + inner.lam[1] * inner.last_video_losses
+        if cg_done is not None and (empty or self.kind != 'joint'):
+            cg_done()
+        if active:
+            if self.kind == 'joint':          # the proposal encoder's arena: one more collective, behind echr_sst_bwd_batch
+                ex.reduce_rest(inner.tap_arena.flat_g)
+                ex.ranges[-1]['name'] = 'proposal encoder'
+            if self.reduce_loss:
+                # the loss (and, with n_videos, the per-video losses at their rank-major slots: every other rank adds zeros there) as ONE
+                # further collective; no host sync -- the slots are device copies
+                n, lo = self.P.loss_slots(n_videos, dist.get_rank(self.group), dist.get_world_size(self.group), 0 if losses is None else len(losses))
+                buf = torch.zeros(n, device=f.dev, dtype=torch.float32)
+                buf[0] = loss
+                if n > 1 and losses is not None:
+                    buf[lo:lo + len(losses)] = losses
+                ex.reduce_rest(buf)
+                ex.ranges[-1]['name'] = 'loss'
+                loss = buf[0]
+                self.last_video_losses = buf[1:] if n > 1 else losses
+            else:
+                self.last_video_losses = losses
+            self._wait()
+        else:
+            self.n_collectives = self.n_early = 0
+            self.last_video_losses = losses
+        L.check(f.lib.echr_check_async(), 'data_parallel_batch_step')
+        f.optim.step_flat_raw(f.grad_clip)
+        f.arena._zeroed = []          # (as behind the one-call step's own update: the arena holds the reduced gradient, not zeros)
+        if self.kind == 'joint':
+            inner.tap_optim.step_flat_raw(inner.tap_grad_clip)
+            inner.tap_arena._zeroed = []
         return loss

@@ -230,3 +230,79 @@ def allreduce_gradients(module, group=None, bucket_bytes=64 << 20, force=False, 
 def shard_videos(n_videos, rank, world):
     """Indices of the videos rank `rank` processes (round-robin: independent units, no data-path collective)."""
     return list(range(rank, n_videos, world))
+
+
+def shard_batch(videos, rank, world):
+    """The videos of one update that rank `rank` runs as its batch (the round-robin shard of shard_videos, order kept within the shard);
+    empty when there are fewer videos than ranks -- fused.DataParallelBatchStep takes such a rank's batch as None."""
+    videos = list(videos)
+    return [videos[i] for i in shard_videos(len(videos), rank, world)]
+
+
+def shard_order(n_videos, world):
+    """Global video index of every slot of the rank-major shard order (rank 0's shard, then rank 1's, ...): what
+    DataParallelBatchStep(reduce_loss=True).last_video_losses is laid out in."""
+    return [i for r in range(world) for i in shard_videos(n_videos, r, world)]
+
+
+def loss_slots(n_videos, rank, world, n_local):
+    """Layout of the reduced loss buffer of DataParallelBatchStep(reduce_loss=True): element 0 is the loss, elements 1.. the per-video
+    losses of the update's `n_videos` videos in rank-major shard order (shard_order).  Returns (buffer length, first slot of this rank's
+    `n_local` videos); every rank writes its own slots and zeros elsewhere, so ONE sum fills them all.  n_videos None: (1, 1)."""
+    if n_videos is None:
+        return 1, 1
+    n_videos = int(n_videos)
+    mine = len(shard_videos(n_videos, rank, world))
+    if n_local != mine:
+        raise ValueError('n_videos = %d over %d ranks gives rank %d a shard of %d videos, its batch has %d' % (n_videos, world, rank, mine, n_local))
+    return 1 + n_videos, 1 + sum(len(shard_videos(n_videos, r, world)) for r in range(rank))
+
+
+class StagedExchange(object):
+    """The collective sequencing of ONE data-parallel update (fused.DataParallelStep / DataParallelBatchStep): SUM over ranks of one or more
+    flat gradient buffers, staged -- ranges that are final early are queued first (`reduce_early`, from wherever the backward pass hands
+    them over), what they did not cover follows (`reduce_rest`), whole further buffers ride behind (`reduce_rest` on them), everything
+    asynchronous; `wait` then waits ONCE for the last collective queued where all of them share one in-order stream, else for each.
+
+    Every rank must queue the same collectives in the same order (torch.distributed matches them by position): a rank without work of its
+    own queues its zero-filled buffers the same way.  Plain torch.distributed: nothing here touches the library, the buffers may be CPU
+    tensors (tests/test_dp_batch_host.py)."""
+
+    def __init__(self, group=None, algo=None):
+        self.group, self.algo = group, algo
+        self.begin()
+
+    def begin(self):
+        self.works, self.ranges, self.n_collectives, self.n_early = [], [], 0, 0
+        self._early = {}          # id(flat) -> [(lo, hi)] queued early
+        return self
+
+    def _queue(self, flat, lo, hi, early):
+        self.works.append(reduce_sum_(flat[lo:hi], self.group, self.algo, async_op=True))
+        self.ranges.append(dict(lo=lo, hi=hi, bytes=flat.element_size() * (hi - lo), early=early))
+        self.n_collectives += 1
+
+    def reduce_early(self, flat, lo, hi):
+        """flat[lo:hi] is final on the CURRENT stream: its collective starts behind that stream's position."""
+        self._queue(flat, lo, hi, True)
+        self._early.setdefault(id(flat), []).append((lo, hi))
+        self.n_early += 1
+
+    def reduce_rest(self, flat):
+        """Everything of `flat` that no early collective covered, in ascending order; returns the number of collectives queued."""
+        pos, n = 0, 0
+        for lo, hi in sorted(self._early.get(id(flat), [])) + [(flat.numel(), flat.numel())]:
+            if lo > pos:
+                self._queue(flat, pos, lo, False)
+                n += 1
+            pos = max(pos, hi)
+        return n
+
+    def wait(self, in_order=False):
+        """The caller's stream (CPU tensors: the host) continues behind the collectives.  in_order: one collective stream ran them all, so
+        the last one queued stands for all of them; the other handles only have to stay alive until then (kept until the next begin)."""
+        if self.works and in_order:
+            self.works[-1].wait()
+        else:
+            for w in self.works:
+                w.wait()

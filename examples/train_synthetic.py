@@ -27,6 +27,12 @@ reward-weighted step on the sample.  m_batch = 1 runs fused.SelfCriticalStep per
 the V videos of one accumulation as ONE batch (one iteration of `--iters` is then one batch with an update).  The reward is synthetic:
 the token overlap of the sampled caption with the video's ground-truth caption minus the same for the greedy caption.
 
+Under `torchrun --nproc_per_node R` (RANK / WORLD_SIZE in the environment) with `--m_batch V` (V > 1) the V videos of an update are sharded
+over the R ranks (parallel.shard_batch) and every rank runs fused.DataParallelBatchStep around the stage's batch step -- FusedTrainStep's
+batch form, JointBatchStep with `--joint`, SelfCriticalBatchStep with `--self_critical`: gradients and loss are the sum over all videos of all
+ranks, one clamp + Adam per model, identical on every rank.  `--dist_backend gloo` with fewer devices than ranks is the one-GPU rehearsal:
+every rank on cuda:0, launch-per-phase recurrences.  Without a process group nothing changes.
+
 usage: python examples/train_synthetic.py [--iters 20] [--m_batch 2] [--joint] [--pre_tap] [--self_critical] [--save /tmp/echr_ckpt.pth]
                                           [--resume /tmp/echr_ckpt.pth]
 """
@@ -90,6 +96,70 @@ def pre_tap(a, opt, dev, loader, tap_model, cg_model, cg_opt, tap_opt, tap_crit,
     if a.save:
         save_checkpoint(a.save, start + a.iters, cg_model, tap_model, cg_opt, tap_opt)
     return history, cg_model, tap_model
+
+
+def init_distributed(a):
+    """torchrun's process group (None without RANK / WORLD_SIZE): RCCL with one device per rank, or the gloo rehearsal on a shared device."""
+    if 'RANK' not in os.environ or 'WORLD_SIZE' not in os.environ:
+        return None
+    import torch.distributed as dist
+    from echr_amd import _lib
+    rank, world, local = int(os.environ['RANK']), int(os.environ['WORLD_SIZE']), int(os.environ.get('LOCAL_RANK', '0'))
+    shared = torch.cuda.device_count() < world
+    if shared and a.dist_backend != 'gloo':
+        raise SystemExit('%d ranks on %d device(s): RCCL wants one device per rank (--dist_backend gloo rehearses on a shared one)'
+                         % (world, torch.cuda.device_count()))
+    torch.cuda.set_device(0 if shared else local)
+    _lib.check(_lib.load().echr_streams_init(), 'streams_init')          # (the library's helper streams ahead of the communicator: INTEGRATION.md)
+    if a.dist_backend == 'nccl':
+        dist.init_process_group('nccl', rank=rank, world_size=world, device_id=torch.device('cuda', local))
+    else:
+        dist.init_process_group(a.dist_backend, rank=rank, world_size=world)
+    if shared:          # two ranks' persistent grids must never share a device: launch-per-phase recurrences and proposal encoder
+        for key in (b'persist', b'persist_bwd', b'sst_persist'):
+            _lib.check(_lib.load().echr_config_set(key, 0), 'config_set')
+    return rank, world
+
+
+def data_parallel_batch(a, opt, dev, loader, tap_model, cg_model, cg_opt, tap_opt, start, rank, world):
+    """`--m_batch V` under a process group: the V videos of an update sharded over the ranks, fused.DataParallelBatchStep around the stage's
+    batch step (train.py:281-283,313-317 with the m_batch videos on R ranks).  Every rank prints the same, reduced loss."""
+    from echr_amd import parallel
+    from echr_amd.batch import VideoBatch
+    from echr_amd.fused import DataParallelBatchStep, FusedTrainStep, JointBatchStep, SelfCriticalBatchStep
+    fused = FusedTrainStep(cg_model, cg_opt, grad_clip=opt.grad_clip)
+    keys = ('c3d', 'lda', 'ind', 'soi', 'labels', 'masks')
+    rewards = []
+    if a.joint:
+        inner, stage = JointBatchStep(fused, tap_model, tap_opt, lambda1=0.01, lambda2=1.0, tap_grad_clip=opt.grad_clip), 'JointBatchStep'
+    elif a.self_critical:
+        inner, stage = SelfCriticalBatchStep(fused, lambda gen, greedy: rewards[inner.current_video](gen, greedy)), 'SelfCriticalBatchStep'
+    else:
+        inner, stage = fused, 'FusedTrainStep.batch'
+    dp = DataParallelBatchStep(inner, reduce_loss=True)
+    history = []
+    for it in range(start, start + a.iters):
+        vids = parallel.shard_batch([loader[(it * a.m_batch + j) % len(loader)] for j in range(a.m_batch)], rank, world)
+        epoch = it * a.m_batch // len(loader)
+        set_lr_for_epoch(cg_opt, opt.lr, epoch)
+        if a.joint:
+            set_lr_for_epoch(tap_opt, opt.lr, epoch)
+        if not vids:          # fewer videos than ranks: this rank adds zeros and takes part in every collective and in the update
+            loss = dp(None)
+        elif a.joint:
+            loss = dp([{k: v[k] for k in keys} for v in vids], [torch.from_numpy(v['tap_masks']) for v in vids],
+                      [torch.from_numpy(v['tap_labels']) for v in vids], [torch.from_numpy(v['w1']) for v in vids])
+        else:
+            with torch.no_grad():          # the proposal encoder is idle in these stages: its states carry no graph
+                batch = VideoBatch.from_videos([{k: v[k] for k in (keys[:4] if a.self_critical else keys)} for v in vids], device=dev,
+                                               tap_model=tap_model, clip_context_type=opt.clip_context_type)
+            rewards[:] = [overlap_reward(v['labels']) for v in vids]
+            loss = dp(batch)
+        history.append(float(loss) / a.m_batch)
+        if not a.quiet and rank == 0 and (it % 5 == 0 or it == start + a.iters - 1):
+            print('iter %3d  DataParallelBatchStep(%s) over %d videos on %d ranks: loss %.4f  (mean over the videos; %d collectives, %d early)'
+                  % (it, stage, a.m_batch, world, history[-1], dp.n_collectives, dp.n_early), flush=True)
+    return history
 
 
 def joint_batch(a, opt, dev, loader, tap_model, cg_model, cg_opt, tap_opt, start):
@@ -171,12 +241,19 @@ def main(argv=None):
     ap.add_argument('--lr', type=float, default=5e-4)
     ap.add_argument('--clip_context_type', type=str, default='CC', help="frame-level context: 'CC', 'CH' or 'CC+CH' (opts.py:130); the batches of "
                                                                         "--m_batch V are built for it")
+    ap.add_argument('--dist_backend', type=str, default='nccl', help="under torchrun: 'nccl' (RCCL, one device per rank) or 'gloo' (also the "
+                                                                     "rehearsal with every rank on one device)")
     ap.add_argument('--save', type=str, default='')
     ap.add_argument('--resume', type=str, default='', help='checkpoint written by --save (or by the reference): models + optimiser state')
     ap.add_argument('--quiet', action='store_true')
     ap.add_argument('--no-fused', action='store_true', help="keep the autograd path also where one echr_train_step call per iteration applies "
                                                              "('pre_cg' mode with m_batch = 1)")
     a = ap.parse_args(argv)
+    if 'RANK' in os.environ and 'WORLD_SIZE' in os.environ and (a.m_batch < 2 or a.no_fused or a.pre_tap):
+        # every rank would train its own replica on the single-process path, without any exchange
+        raise SystemExit('under torchrun this driver runs fused.DataParallelBatchStep: it needs --m_batch V with V > 1 and takes neither '
+                         '--no-fused nor --pre_tap')
+    ranks = init_distributed(a)
     dev = torch.device('cuda')
     opt = synth.default_opt(vocab_size=a.vocab, seq_length=10, K=32, lr=a.lr)
     opt.clip_context_type = a.clip_context_type
@@ -186,6 +263,7 @@ def main(argv=None):
     tap_model.train()
     cg_model.train()
     batch_joint = a.joint and a.m_batch > 1 and not a.no_fused and not a.pre_tap          # stage 3 over a batch: fused.JointBatchStep
+    dp_batch = ranks is not None and a.m_batch > 1 and not a.no_fused and not a.pre_tap          # ... and any stage's batch step over the ranks
     tap_opt = ClampAdam(tap_model.parameters(), lr=opt.lr, betas=(opt.optim_alpha, opt.optim_beta), eps=opt.optim_epsilon,
                         arena=tap_model.build_arena() if batch_joint else None)
     cg_opt = ClampAdam(cg_model.parameters(), lr=opt.lr, betas=(opt.optim_alpha, opt.optim_beta), eps=opt.optim_epsilon,
@@ -214,11 +292,13 @@ def main(argv=None):
     if a.pre_tap:
         return pre_tap(a, opt, dev, loader, tap_model, cg_model, cg_opt, tap_opt, tap_crit, start)
     iters = range(start, start + a.iters)
-    if a.self_critical:
-        if a.joint or a.no_fused:
-            raise SystemExit('--self_critical trains the captioner on the one-call path: not with --joint / --no-fused')
+    if a.self_critical and (a.joint or a.no_fused):
+        raise SystemExit('--self_critical trains the captioner on the one-call path: not with --joint / --no-fused')
+    if a.self_critical and not dp_batch:
         history, iters = self_critical(a, opt, dev, loader, tap_model, cg_model, cg_opt, start), ()
-    if batch_joint:
+    if dp_batch:
+        history, iters = data_parallel_batch(a, opt, dev, loader, tap_model, cg_model, cg_opt, tap_opt, start, *ranks), ()
+    elif batch_joint:
         history, iters = joint_batch(a, opt, dev, loader, tap_model, cg_model, cg_opt, tap_opt, start), ()
     for it in iters:
         v = loader[it % len(loader)]
@@ -282,8 +362,11 @@ def main(argv=None):
         seq, logp = cg_model(tap_feats, c3d, lda, [], v['ind'], v['soi'], mode='eval')
     if not a.quiet:
         print('greedy captions (token ids) of video 0:', seq[:3].tolist() if len(seq) else seq)
-    if a.save:
+    if a.save and (ranks is None or ranks[0] == 0):
         save_checkpoint(a.save, start + a.iters, cg_model, tap_model, cg_opt, tap_opt)
+    if ranks is not None:
+        import torch.distributed as dist
+        dist.destroy_process_group()
     return history, cg_model, tap_model
 
 

@@ -781,15 +781,17 @@ int echr_decoder_sample_train_batch(const echr_sample_args* a, const echr_dropou
 /* echr_train_step over a batch.  Criterion weights as in echr_train_step_rw: `weight` device [N,S] with host_nll = 0, or behind the mask
  * in host_index with host_nll = 1 (then weight = NULL).  host_index additionally ENDS with vid[N]; x->vid and x->ws are ignored (the
  * library points them at its staged copy / its own workspace).  loss[0] = the summed loss, loss[1] = sum(mask) over the batch;
- * video_loss: optional device [V] out, the per-video losses (fixed summation order).  Not with prepared, defer_update, g_tap, handover,
- * nor an initial state (w_init must be NULL: CG_init_feats_type over a batch is a follow-up). */
+ * video_loss: optional device [V] out, the per-video losses (fixed summation order).  Not with prepared, defer_update, g_tap nor an
+ * initial state (w_init must be NULL: CG_init_feats_type over a batch is a follow-up).  handover = 1 (with do_step = 0) records both
+ * hand-over points, see echr_handover_wait. */
 int64_t echr_train_step_batch_ws_floats(const echr_train_step_args* a, const echr_batch_ext* x);
 int echr_train_step_batch(const echr_train_step_args* a, const echr_batch_ext* x, const float* weight, float* video_loss, void* stream);
 /* The joint 'tap_cg' iteration over a batch: echr_train_step_batch with a->g_tap set.  g_tap [T_tot, Ht] is zero-filled by the caller and
  * added into in place: d loss / d tap of the anchors' rows through the block-diagonal event encoder (a->dec / host_index `ind` are
  * batch-absolute; 'ER1' adds nothing), and with 'VH' (a->vh_offset >= 0) each video's d scene vector spread over that video's OWN rows --
  * row_offset: device int32 [V+1] (may be NULL without 'VH').  a->g_loss (device scalar) scales every gradient, g_tap included (lambda2);
- * loss and video_loss are reported unscaled.  Not with prepared, defer_update, handover, mid_cb, forward_only nor an initial state. */
+ * loss and video_loss are reported unscaled.  Not with prepared, defer_update, mid_cb, forward_only nor an initial state.  handover = 1
+ * (with do_step = 0) records both hand-over points (g_tap and the 'VH' span are no part of flat_g), see echr_handover_wait. */
 int64_t echr_train_step_batch_tap_ws_floats(const echr_train_step_args* a, const echr_batch_ext* x);
 int echr_train_step_batch_tap(const echr_train_step_args* a, const echr_batch_ext* x, const float* weight, float* video_loss,
                               const int32_t* row_offset, void* stream);
@@ -801,14 +803,26 @@ int echr_train_step_batch_tap(const echr_train_step_args* a, const echr_batch_ex
  * the anchors' rows through the block-diagonal event encoder, the 'VH' span spread over each video's own rows (row_offset, device [V+1];
  * may be NULL without 'VH') and the clip-row gradient (echr_decoder_row_grad's sum; its context term reads the compacted active rows
  * directly, "row_grad_list"), all three scaled by a->g_loss, and is final when the call returns.  Not with prepared, defer_update,
- * handover, mid_cb nor an initial state; dec.D must match clip_parts. */
+ * mid_cb nor an initial state; dec.D must match clip_parts.  handover = 1 (with do_step = 0) records both hand-over points (the clip-row
+ * gradient goes into g_tap, behind the join of the helper streams: no part of flat_g), see echr_handover_wait. */
 int64_t echr_train_step_batch_clip_ws_floats(const echr_train_step_args* a, const echr_clip_step_args* x, const echr_batch_ext* bx);
 int echr_train_step_batch_clip(const echr_train_step_args* a, const echr_clip_step_args* x, const echr_batch_ext* bx, const float* weight,
                                float* video_loss, const int32_t* row_offset, void* stream);
 
-/* Hand-over points of the LAST echr_train_step issued with handover = 1 (which: 0 = logit layer, 1 = LSTM layers): makes `stream` wait
+/* Hand-over points of the LAST one-call step issued with handover = 1 (which: 0 = logit layer, 1 = LSTM layers): makes `stream` wait
  * until that range of flat_g is final.  0 = `stream` now waits; 1 = the call recorded no such point (a configuration without the
- * asynchronous tail: the range is final when the call's own stream reaches its end, like every other); < 0 error. */
+ * asynchronous tail: the range is final when the call's own stream reaches its end, like every other); < 0 error.
+ * Which entries record which points.  Both points are recorded inside the shared decoder backward, so every entry that reaches it with
+ * handover = 1 and do_step = 0 records the same two: echr_train_step, echr_train_step_rw (the reward weights only change d logits),
+ * echr_train_step_clip, echr_train_step_batch, echr_train_step_batch_tap and echr_train_step_batch_clip -- with the persistent and the
+ * launch-per-phase recurrences, and in the fixed-order mode (its fold launches sit on the stream of the product they fold, in front of the
+ * mark).  ECHR_HANDOVER_LSTM sits on the prepare stream behind the grouped weight-gradient product, the bias sums, the event half of W_ih0
+ * and the scene half of W_ih2 (a batch: the segmented row sum by video and its two products); ECHR_HANDOVER_LOGIT on the tail stream behind
+ * d W_logit and d b_logit.  What follows a mark writes other ranges (embedding, attention, event encoder) or no part of flat_g at all
+ * (g_tap: the anchors' rows, the 'VH' span, the clip-row gradient; a batch's d video).  No point is recorded, and 1 is returned, without
+ * the helper streams (LOGIT: also on the native product path without its deferred logit-layer gradients), with do_step = 1 and by the
+ * deferred joint form (defer_update).  A forward_only call returns ahead of the backward pass and leaves the points of an earlier call as
+ * they were (their events have long completed); echr_train_step_prepare records none. */
 /* Memory scope of the library's ordering points.  echr_handover_wait's events carry a system-scope release (their consumers sit outside the
  * library: collectives read by peers, copy engines).  echr_stream_join -- and every entry that joins the helper streams by itself -- orders
  * `stream` behind the helper streams with AGENT-scope events (no cache write-back for the host or other devices: ~2 us less per edge, a dozen
