@@ -10,6 +10,10 @@ csrc/echr_common.h (`echr_keep`); this numpy version must stay bit-identical to 
 Counter layout (4 x u32):  c0 = element_index >> 2, c1 = step, c2 = site, c3 = offset
 Key (2 x u32):             k0 = seed & 0xffffffff, k1 = seed >> 32
 Element e uses output word (e & 3).  keep  <=>  word >= floor(p * 2**32).
+
+Site 6 (SITE_SAMPLE) is not a dropout site: it feeds the multinomial draw of the sampling decoders (csrc/core.hip, sample_step_kernel /
+sample_row_step_kernel).  The draw of (row, step) uses element index = row, offset 0 and the decode's seed as the key; the device forms
+u = (word >> 8) * 2**-24 (`sample_u24`).
 """
 import numpy as np
 
@@ -19,6 +23,7 @@ SITE_H1 = 2
 SITE_H2 = 3
 SITE_OUT = 4       # [N, 3H]    p = CG_drop_prob
 SITE_SST = 5       # [T, H]     p = rnn_dropout (SST inter-layer dropout; step counter 0, element t*H + j)
+SITE_SAMPLE = 6    # [N]        the multinomial draw of (row, step): element = row (batch-global in a multi-video batch), offset 0
 
 _M0 = np.uint64(0xD2511F53)
 _M1 = np.uint64(0xCD9E8D57)
@@ -72,3 +77,15 @@ def scale_mask(shape, p, seed, offset, site, step):
     k = keep_mask(n, p, seed, offset, site, step)
     s = np.float32(1.0) / (np.float32(1.0) - np.float32(p))
     return (k.astype(np.float32) * s).reshape(shape)
+
+
+def sample_u24(rows, steps, seed):
+    """int64 [rows, steps]: the 24-bit integers behind the multinomial draws of a decode keyed by `seed` -- word >> 8 of
+    philox_word(elem = row, step, SITE_SAMPLE, offset = 0, seed lo, seed hi), i.e. counter c0 = row >> 2 and output word row & 3.  The device
+    draws token j of (row, step) by inverse CDF at u = u24 * 2**-24."""
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    n = np.broadcast_to(np.arange(rows, dtype=np.uint64)[:, None], (rows, steps))
+    t = np.broadcast_to(np.arange(steps, dtype=np.uint64)[None, :], (rows, steps))
+    w = np.stack(philox4x32_10(n >> np.uint64(2), t, SITE_SAMPLE, 0, seed & 0xFFFFFFFF, seed >> 32), axis=-1)          # [rows, steps, 4]
+    sel = np.take_along_axis(w, (n & np.uint64(3)).astype(np.int64)[..., None], axis=-1)[..., 0]
+    return (sel >> np.uint32(8)).astype(np.int64)
