@@ -128,14 +128,16 @@ class CaptionGenerator(nn.Module):
                 if '_sample_tables' not in lm.__dict__:
                     lm._sample_tables = {}
                 return EF.greedy_sample(video, event, batch.clip_rows(), ev_start, ev_len, A, lm.seq_length, lm.native_params(),
-                                        table_cache=lm._sample_tables, vid=vid)
+                                        table_cache=lm._sample_tables, vid=vid,
+                                        h0=self._batch_initial_state(batch, video, event, ev_start, ev_len, vid))
         if lm.training and lm.ss_prob > 0.0:
             raise NotImplementedError('scheduled sampling (ss_prob > 0) is never enabled by the reference and is not on the HIP path')
         tokens = lm._tokens(batch.labels, batch.device)
         arena = getattr(lm, '_echr_arena_ref', None)
         sink = EF.GradSink(arena, lm.native_params()) if arena is not None else None
+        h0 = self._batch_initial_state(batch, video, event, ev_start, ev_len, vid)
         return EF.DecoderBatchFunction.apply(video, event, batch.clip_rows(), ev_start, ev_len, tokens, A, disjoint, drop, sink, vid,
-                                             *(tuple(lm.native_params()) + self._batch_clip_tail(batch)))
+                                             *(tuple(lm.native_params()) + self._batch_tail(batch, h0)))
 
     @staticmethod
     def _batch_clip_tail(batch):
@@ -143,6 +145,24 @@ class CaptionGenerator(nn.Module):
         'CH' / 'CC+CH' -- the row source carries no graph, the decoder's backward returns d tap itself (as ClipView.grad_src / grad_col0
         arrange for one video)."""
         return () if batch.clip_parts == 1 else (batch.tap, int(batch.clip_col0))
+
+    @classmethod
+    def _batch_tail(cls, batch, h0):
+        """_batch_clip_tail behind the initial state, when the model has one: (h0,) + the clip pair."""
+        return (() if h0 is None else (h0,)) + cls._batch_clip_tail(batch)
+
+    def _batch_initial_state(self, batch, video, event, ev_start, ev_len, vid):
+        """None (the recipe: zero state) or h0 [N_tot, 3H] of CG_init_feats_type over a batch (functional.InitStateBatch): every event from
+        its own video's scene vector, its event context and its clip mean over its own video's padded clip length.  The clip mean reads
+        C3D rows only (the constructor refuses 'C' with 'CH' rows)."""
+        lm = self.lm_model
+        if not getattr(lm, 'CG_init_feats_dim', 0):
+            return None
+        t = lm.CG_init_feats_type
+        arena = getattr(lm, '_echr_arena_ref', None)
+        sink = EF.GradSink(arena, (lm.init_linear.weight, lm.init_linear.bias)) if arena is not None else None
+        return EF.InitStateBatch.apply(video, event, batch.clip_rows(), ev_start, ev_len, vid, ('V' in t, 'E' in t, 'C' in t), sink,
+                                       lm.init_linear.weight, lm.init_linear.bias)
 
     def _batch_contexts(self, batch, groups, need_labels=False):
         """What forward_batch and beam_batch hand to the decoder: the checks of a batched call, then (video [V, Dv], event [N_tot, d_o],
@@ -193,9 +213,10 @@ class CaptionGenerator(nn.Module):
             lm = self.lm_model
             L, N, ro = lm.seq_length, batch.n_events, batch.row_offset
             rows = batch.clip_rows()
+            h0 = self._batch_initial_state(batch, video, event, ev_start, ev_len, vid)          # (run-local rows below: the plain row slice)
             if len(runs) == 1:
                 seq, logp, score, video_words = EF.beam_search_batch(video, event, rows, ev_start, ev_len, vid, A, L, lm.native_params(), B,
-                                                                     trim=False)
+                                                                     trim=False, h0=h0)
             else:
                 seq = torch.empty(N, L, device=batch.device, dtype=torch.int64)
                 logp = torch.empty(N, L, device=batch.device, dtype=torch.float32)
@@ -205,7 +226,7 @@ class CaptionGenerator(nn.Module):
                     r0, r1 = int(ro[v0]), int(ro[v1])
                     seq[e0:e1], logp[e0:e1], score[e0:e1], video_words[v0:v1] = EF.beam_search_batch(
                         video[v0:v1], event[e0:e1], rows[r0:r1], ev_start[e0:e1] - r0, ev_len[e0:e1], vid[e0:e1] - v0, A, L,
-                        lm.native_params(), B, trim=False)
+                        lm.native_params(), B, trim=False, h0=None if h0 is None else h0[e0:e1])
         T = int(video_words.max())
         if T == 0:
             return [], [], score, video_words
@@ -226,11 +247,14 @@ class CaptionGenerator(nn.Module):
         lm = self.lm_model
         if lm.training and lm.ss_prob > 0.0:
             raise NotImplementedError('scheduled sampling (ss_prob > 0) is never enabled by the reference and is not on the HIP path')
+        # (the initial state once, with its graph: the two decodes read its values, the teacher-forced recompute carries the gradient)
+        h0 = self._batch_initial_state(batch, video, event, ev_start, ev_len, vid)
+        h0_d = None if h0 is None else h0.detach()
         if gen_result is None:
             seed = lm._sample_seed() if seed is None else int(seed)
             with torch.no_grad():
                 gen, _, video_words = EF.sample_train_batch(video, event.detach(), batch.clip_rows(), ev_start, ev_len, vid, A, lm.seq_length,
-                                                            lm.native_params(), drop, seed=seed)
+                                                            lm.native_params(), drop, seed=seed, h0=h0_d)
         else:
             video_words = batch.caption_widths(gen_result)
             gen = torch.as_tensor(gen_result)[:, :int(video_words.max())].to(device=batch.device, dtype=torch.int64).contiguous()
@@ -238,7 +262,7 @@ class CaptionGenerator(nn.Module):
             if '_sample_tables' not in lm.__dict__:
                 lm._sample_tables = {}
             greedy_res, _ = EF.greedy_sample(video, event.detach(), batch.clip_rows(), ev_start, ev_len, A, lm.seq_length, lm.native_params(),
-                                             table_cache=lm._sample_tables, vid=vid)
+                                             table_cache=lm._sample_tables, vid=vid, h0=h0_d)
         if isinstance(gen, list) or gen.numel() == 0:
             return [], [], greedy_res, video_words          # every row drew <eos> first (OldModel.sample returns [] then, :186-187)
         N, T = gen.shape
@@ -248,7 +272,7 @@ class CaptionGenerator(nn.Module):
         sink = EF.GradSink(arena, lm.native_params()) if arena is not None else None
         logp = EF.DecoderBatchFunction.apply(video, event, batch.clip_rows(), ev_start, ev_len, lm._tokens(labels, batch.device), A,
                                              EF.rows_disjoint(batch.soi), drop, sink, vid,
-                                             *(tuple(lm.native_params()) + self._batch_clip_tail(batch)))
+                                             *(tuple(lm.native_params()) + self._batch_tail(batch, h0)))
         return gen, EF.GatherTokens.apply(logp, gen), greedy_res, video_words
 
     def _event_context_groups(self, batch, groups, ech, ev_start, ev_len, vid, drop, params):
@@ -271,11 +295,17 @@ class CaptionGenerator(nn.Module):
         return event
 
     def _check_batch_options(self, batch=None):
-        """What the batched entry points do not cover yet (follow-ups): an initial state from the contexts, a batch per data-parallel rank;
-        and the batch must have been built for the model's frame-level context (VideoBatch.from_videos(..., clip_context_type=))."""
-        if getattr(self.opt, 'CG_init_feats_type', ''):
-            raise NotImplementedError("CG_init_feats_type=%r: batches start from the zero state (an initial state that reads the scene vector 'V' -- or "
-                                      "any other context -- takes one video per call)" % (self.opt.CG_init_feats_type,))
+        """The batch must have been built for the model's initial decoder state and frame-level context (VideoBatch.from_videos(...,
+        CG_init_feats_type=, clip_context_type=)): a plain batch with a model that has either raises NotImplementedError and names the
+        keyword, any other mismatch is a ValueError.  Not covered (follow-up): a batch per rank of the per-video data-parallel hand-over."""
+        # (batch None: the entry builds the batch itself, for this model's options)
+        want = getattr(self.opt, 'CG_init_feats_type', '') or ''
+        got = want if batch is None else (getattr(batch, 'CG_init_feats_type', '') or '')
+        if set(want) != set(got):
+            if not got:
+                raise NotImplementedError("CG_init_feats_type=%r: a plain batch starts from the zero state -- build it for the model's initial "
+                                          "state: VideoBatch.from_videos(..., CG_init_feats_type=%r)" % (want, want))
+            raise ValueError('the batch was built for CG_init_feats_type=%r, the model has %r' % (got, want))
         # (batch None: the entry builds the batch itself, for this model's clip context)
         have = self.clip_parts() if batch is None else getattr(batch, 'clip_parts', 1)
         if self.clip_parts() != have:

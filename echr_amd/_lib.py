@@ -215,6 +215,8 @@ SYMBOLS = [
     ('echr_batch_ws_floats', i64, [i32, i32, i32]),
     ('echr_seg_col_mean_fwd', i32, [c_f, c_f, i32, i32, i64, c_f, i64, C.c_void_p]),
     ('echr_seg_col_mean_bwd', i32, [c_f, i64, c_f, i32, i32, i64, c_f, C.c_void_p]),
+    ('echr_init_state_fwd_batch', i32, [C.POINTER(InitStateArgs), C.POINTER(BatchExt), c_f, C.c_void_p]),
+    ('echr_init_state_bwd_batch', i32, [C.POINTER(InitStateArgs), C.POINTER(InitStateGrads), C.POINTER(BatchExt), C.c_void_p]),
     ('echr_tsrm_fwd_batch', i32, [C.POINTER(TsrmArgs), C.POINTER(Dropout), C.POINTER(BatchExt), C.c_void_p]),
     ('echr_tsrm_bwd_batch', i32, [C.POINTER(TsrmArgs), C.POINTER(TsrmGrads), C.POINTER(Dropout), C.POINTER(BatchExt), C.c_void_p]),
     ('echr_decoder_fwd_batch', i32, [C.POINTER(DecArgs), C.POINTER(Dropout), C.POINTER(BatchExt), C.c_void_p]),

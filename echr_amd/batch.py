@@ -13,7 +13,9 @@ the event intervals / anchors become batch-absolute row indices, and every event
 
 A batch is built for ONE frame-level context (`clip_context_type`, default 'CC'): with 'CH' / 'CC+CH' the decoder attends over
 `clip_rows()` -- tap, or [c3d | tap] -- and d tap gains the attended rows' gradient; the entry points refuse a batch built for another
-context than the model's.
+context than the model's.  Likewise a batch is built for the model's initial decoder state (`CG_init_feats_type`, default '': zeros):
+with 'V' / 'E' / 'C' every event starts from init_linear over its OWN video's scene vector, its event context and its clip mean over
+its own video's padded clip length.
 """
 import numpy as np
 import torch
@@ -45,10 +47,14 @@ class VideoBatch(object):
       event_slices                      slice of the event axis per video; split(x) cuts a [N_tot, ...] result accordingly
       clip_context_type, clip_parts     the frame-level context the batch was built for: 1 = 'CC' (default), 2 = 'CH', 3 = 'CC+CH';
                                         clip_rows() is the decoder's row source -- c3d, tap or [c3d | tap]
+      CG_init_feats_type                the initial decoder state the batch was built for ('' = zeros, else from 'V', 'E', 'C')
     """
 
-    def __init__(self, c3d, tap, lda, row_offset, event_offset, soi, ind, labels=None, masks=None, clip_context_type='CC'):
+    def __init__(self, c3d, tap, lda, row_offset, event_offset, soi, ind, labels=None, masks=None, *, CG_init_feats_type='', clip_context_type='CC'):
         self.c3d, self.tap, self.lda = c3d, tap, lda
+        self.CG_init_feats_type = str(CG_init_feats_type or '')
+        if set(self.CG_init_feats_type) - set('VEC') or len(set(self.CG_init_feats_type)) != len(self.CG_init_feats_type):
+            raise ValueError("CG_init_feats_type=%r: the initial state reads 'V', 'E' and / or 'C', each at most once" % (CG_init_feats_type,))
         # the frame-level context the batch is built for, tested with `in` as CaptionGenerator.clip_parts does ('CCCH' means 'CC+CH')
         self.clip_context_type = clip_context_type
         self.clip_parts = (1 if 'CC' in clip_context_type else 0) | (2 if 'CH' in clip_context_type else 0)
@@ -71,7 +77,7 @@ class VideoBatch(object):
 
     # ---- construction -------------------------------------------------------------------------------------------------------
     @classmethod
-    def from_videos(cls, videos, device=None, tap_model=None, tap_fn=None, clip_context_type='CC'):
+    def from_videos(cls, videos, device=None, tap_model=None, tap_fn=None, *, CG_init_feats_type='', clip_context_type='CC'):
         """`videos`: a list of dicts with the arguments of a single-video call -- 'c3d' [T, D], 'tap' [T', Ht], 'lda' [lda_dim], 'ind' [N_v],
         'soi' [N_v, 2] (indices local to the video) and, for training, 'labels' / 'masks' [N_v, L_v] -- or a dict of parallel lists under
         the same keys.  Features may be numpy arrays or tensors on any device; they are concatenated on `device` (default: the device of
@@ -81,7 +87,9 @@ class VideoBatch(object):
         `tap_fn(c3d_all, rows)` (instead of tap_model): any other producer of the [T_tot, Ht] matrix from the concatenated c3d and the row
         offsets (fused.JointBatchStep runs the encoder into its own buffers, without a graph).
         `clip_context_type`: the model's frame-level context ('CC', 'CH', 'CC+CH'); the batched entry points refuse a batch built for
-        another one."""
+        another one.
+        `CG_init_feats_type`: the model's initial decoder state ('' = zeros; else from 'V', 'E', 'C'), under the same rule.  Both
+        options are keyword-only."""
         if isinstance(videos, dict):
             n = len(videos['c3d'])
             videos = [{k: v[i] for k, v in videos.items()} for i in range(n)]
@@ -141,7 +149,7 @@ class VideoBatch(object):
         else:
             tap_all = torch.cat(taps, 0) if tap_model is None else tap_model.forward_batch(c3d_all, rows)[0]
         return cls(c3d_all, tap_all, torch.stack(ldas, 0), rows, counts, np.concatenate(sois, 0), np.concatenate(inds, 0),
-                   labels, masks, clip_context_type=clip_context_type)
+                   labels, masks, clip_context_type=clip_context_type, CG_init_feats_type=CG_init_feats_type)
 
     @staticmethod
     def _stack_labels(videos, counts):
@@ -246,7 +254,7 @@ class VideoBatch(object):
         """Video v as the dict of a single-video call (local indices, its own label width and step count)."""
         s, r0, r1 = self.event_slices[v], int(self.row_offset[v]), int(self.row_offset[v + 1])
         d = dict(c3d=self.c3d[r0:r1], tap=self.tap[r0:r1], lda=self.lda[v], soi=self.soi[s] - r0, ind=self.ind[s] - r0,
-                 clip_context_type=self.clip_context_type)
+                 clip_context_type=self.clip_context_type, CG_init_feats_type=self.CG_init_feats_type)
         if self.labels is not None:
             w = self.steps[v] + 1          # S_v steps read label columns 0 .. S_v - 1 and target columns 1 .. S_v
             d['labels'], d['masks'] = self.labels[s, :w], self.masks[s, :w]

@@ -1347,6 +1347,98 @@ extern "C" int echr_init_state_bwd(const echr_init_state_args* a, const echr_ini
     return 0;
 }
 
+// ---- the initial state over a multi-video batch: row n is what echr_init_state_fwd forms for that event in its own video ----
+// video_len[v] = the largest ev_len among the events of video v: the padded clip length of that video's own clip tensor (the divisor of
+// its clip.mean(1)).  One block per video; 0 for a video without an event.
+__global__ __launch_bounds__(256) void video_max_len_kernel(const int32_t* __restrict__ ev_len, const int32_t* __restrict__ vid, int N, int32_t* __restrict__ video_len) {
+    __shared__ int red[256];
+    const int v = blockIdx.x;
+    int m = 0;
+    for (int n = threadIdx.x; n < N; n += 256)
+        if (vid[n] == v) m = max(m, ev_len[n]);
+    red[threadIdx.x] = m;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) red[threadIdx.x] = max(red[threadIdx.x], red[threadIdx.x + s]);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) video_len[v] = red[0];
+}
+// init_feats_kernel with the scene vector of the event's own video and that video's padded clip length (same summation order, same
+// product with the reciprocal: a one-video batch forms the rows of the single-video kernel bit for bit)
+__global__ __launch_bounds__(256) void init_feats_batch_kernel(echr_init_state_args a, int Dtot, const float* __restrict__ video, const int32_t* __restrict__ vid,
+                                                               const int32_t* __restrict__ video_len, int V) {
+    const int n = blockIdx.x;
+    const int v = min(max(vid[n], 0), V - 1);
+    float* o = a.feats + (long)n * Dtot;
+    int off = 0;
+    if (a.use_v) { const float* vr = video + (long)v * a.Dv; for (int j = threadIdx.x; j < a.Dv; j += 256) o[j] = vr[j]; off += a.Dv; }
+    if (a.use_e) { for (int j = threadIdx.x; j < a.De; j += 256) o[off + j] = a.event[(long)n * a.De + j]; off += a.De; }
+    if (a.use_c) {
+        const int s = a.ev_start[n], len = a.ev_len[n];
+        const float inv = 1.0f / (float)max(video_len[v], 1);
+        for (int j = threadIdx.x; j < a.D; j += 256) {
+            float acc = 0.f;
+            for (int r = 0; r < len; ++r) acc += a.c3d[(long)(s + r) * a.D + j];
+            o[off + j] = acc * inv;
+        }
+    }
+}
+// g_video[v, j] = sum over the events n of video v (ascending n: vid is non-decreasing, so a contiguous run) of dfeats[n, j] -- one thread
+// per element, one fixed order, no atomics: bitwise reproducible
+__global__ __launch_bounds__(256) void init_video_grad_kernel(const float* __restrict__ dfeats, const int32_t* __restrict__ vid, float* __restrict__ g_video,
+                                                              int N, int Dv, int Dtot) {
+    const int v = blockIdx.x, j = blockIdx.y * 256 + threadIdx.x;
+    if (j >= Dv) return;
+    int lo = 0, hi = N;          // first event with vid >= v
+    while (lo < hi) { const int mid = (lo + hi) >> 1; if (vid[mid] < v) lo = mid + 1; else hi = mid; }
+    float acc = 0.f;
+    for (int n = lo; n < N && vid[n] == v; ++n) acc += dfeats[(long)n * Dtot + j];
+    g_video[(long)v * Dv + j] = acc;
+}
+extern "C" int echr_init_state_fwd_batch(const echr_init_state_args* a, const echr_batch_ext* x, int32_t* video_len, void* stream) {
+    ECHR_REQUIRE(a && a->N > 0 && a->H3 > 0 && a->w && a->b && a->feats && a->h0 && init_dtot(a) > 0, "init_state_fwd_batch: bad arguments");
+    ECHR_REQUIRE(x && x->n_videos > 0 && x->n_videos <= a->N && x->vid, "init_state_fwd_batch: the batch extension needs 0 < n_videos <= N and vid");
+    ECHR_REQUIRE((!a->use_v || x->video) && (!a->use_e || a->event) && (!a->use_c || (a->c3d && a->ev_start && a->ev_len && video_len)),
+                 "init_state_fwd_batch: missing inputs ('V': x->video [V,Dv]; 'C': c3d, ev_start, ev_len and video_len [V])");
+    hipStream_t st = (hipStream_t)stream;
+    const int Dtot = init_dtot(a);
+    if (a->use_c) {
+        hipLaunchKernelGGL(video_max_len_kernel, dim3(x->n_videos), dim3(256), 0, st, a->ev_len, x->vid, a->N, video_len);
+        if (int rc = check_launch("video_max_len")) return rc;
+    }
+    hipLaunchKernelGGL(init_feats_batch_kernel, dim3(a->N), dim3(256), 0, st, *a, Dtot, x->video, x->vid, video_len, x->n_videos);
+    if (int rc = check_launch("init_feats_batch")) return rc;
+    echr_gemm_desc d = desc_nt(a->feats, Dtot, a->w, Dtot, a->h0, a->H3, a->N, a->H3, Dtot);          // init_linear: echr_init_state_fwd's product
+    d.bias = a->b;
+    return gemm(d, st);
+}
+extern "C" int echr_init_state_bwd_batch(const echr_init_state_args* a, const echr_init_state_grads* g, const echr_batch_ext* x, void* stream) {
+    ECHR_REQUIRE(a && g && g->g_h0 && g->g_w && g->g_b && g->dfeats && a->feats && a->w && a->N > 0, "init_state_bwd_batch: bad arguments");
+    ECHR_REQUIRE(x && x->n_videos > 0 && x->n_videos <= a->N && x->vid, "init_state_bwd_batch: the batch extension needs 0 < n_videos <= N and vid");
+    hipStream_t st = (hipStream_t)stream;
+    const int Dtot = init_dtot(a);
+    const bool z = g->zeroed != 0;
+    echr_gemm_desc d = desc_tn(g->g_h0, a->H3, a->feats, Dtot, g->g_w, Dtot, a->H3, Dtot, a->N);          // d W = d h0^T . feats, over all rows of all videos
+    d.beta = z ? 1.f : 0.f;
+    if (int rc = gemm(d, st)) return rc;
+    if (int rc = colsum(g->g_h0, a->H3, a->N, a->H3, g->g_b, z, st)) return rc;
+    const bool want_v = x->g_video && a->use_v, want_e = g->g_event && a->use_e;
+    if (!want_v && !want_e) return 0;
+    d = desc_nn(g->g_h0, a->H3, a->w, Dtot, g->dfeats, Dtot, a->N, Dtot, a->H3);                          // d feats = d h0 . W
+    if (int rc = gemm(d, st)) return rc;
+    if (want_v) {          // (g->g_video is ignored: d video is per video, x->g_video [V, Dv])
+        hipLaunchKernelGGL(init_video_grad_kernel, dim3(x->n_videos, (a->Dv + 255) / 256), dim3(256), 0, st, g->dfeats, x->vid, x->g_video, a->N, a->Dv, Dtot);
+        if (int rc = check_launch("init_video_grad")) return rc;
+    }
+    if (want_e) {
+        const long n = (long)a->N * a->De;
+        hipLaunchKernelGGL(init_event_grad_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, g->dfeats, g->g_event, a->N, a->De, Dtot, a->use_v ? a->Dv : 0);
+        return check_launch("init_event_grad");
+    }
+    return 0;
+}
+
 // ---- scene context 'VC' / 'VH' (CaptionGenerator.py:95-99): the mean over all T_v rows of c3d_feats / tap_feats ----
 __global__ __launch_bounds__(256) void col_scale_kernel(float* __restrict__ v, int n, float s) {
     const int i = blockIdx.x * 256 + threadIdx.x;

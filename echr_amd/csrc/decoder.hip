@@ -1496,7 +1496,6 @@ extern "C" int echr_decoder_bwd(const echr_dec_args* a, const echr_dec_grads* g,
 // ---- multi-video batches: the single-video entries with the extension published for the duration of the call ----
 static int check_batch(const echr_dec_args* a, const echr_batch_ext* x, const char* who) {
     ECHR_REQUIRE(a && x && x->n_videos > 0 && x->n_videos <= a->N && x->vid && x->video && x->ws, "%s: the batch extension needs 0 < n_videos <= N, vid, video and ws", who);
-    ECHR_REQUIRE(!a->h0, "%s: an initial state (CG_init_feats_type) is not part of the batched entries", who);
     return 0;
 }
 extern "C" int echr_decoder_fwd_batch(const echr_dec_args* a, const echr_dropout* drop, const echr_batch_ext* x, void* stream) {
@@ -2349,7 +2348,6 @@ extern "C" int echr_decoder_beam(const echr_beam_args* ba, void* stream) {
 extern "C" int echr_decoder_beam_batch(const echr_beam_args* ba, const echr_batch_ext* x, int32_t* video_words, void* stream) {
     ECHR_REQUIRE(ba && video_words, "decoder_beam_batch: null args / video_words");
     RC(check_batch(&ba->dec, x, "decoder_beam_batch"));
-    ECHR_REQUIRE(!ba->dec.h0, "decoder_beam_batch: batches start from the zero state (dec.h0 must be NULL)");
     {
         BatchScope scope(x);
         RC(echr_decoder_beam(ba, stream));

@@ -17,7 +17,7 @@ namespace echr {
 
 static inline long up64(long n) { return (n + 63) / 64 * 64; }
 struct StepWs { long idx, ech, tsrm_ws, event, logp, dec_ws, dec_ws_bwd, g_event, g_ech, tsrm_ws_bwd, h0, g_h0, init_feats, init_dfeats, g_video, g_video_init,
-                 rows, row_grad, batch, total; };
+                 init_vlen, rows, row_grad, batch, total; };
 
 static inline int init_feats_width(const echr_train_step_args* a) {
     return (a->init_use_v ? a->dec.Dv : 0) + (a->init_use_e ? a->dec.De : 0) + (a->init_use_c ? a->dec.D : 0);
@@ -49,7 +49,9 @@ static StepWs carve_step(const echr_train_step_args* a, bool rw = false, const e
         const long h3 = 3L * d.H, dt = init_feats_width(a);
         w.h0 = take((long)d.N * h3); w.g_h0 = take((long)d.N * h3); w.init_feats = take((long)d.N * dt); w.init_dfeats = take((long)d.N * dt);
     }
-    w.g_video = take((bx ? (long)bx->n_videos : 1L) * d.Dv); w.g_video_init = take(d.Dv);          // (a batch: d video is [V, Dv])
+    // (a batch: d video is [V, Dv]; with an initial state so is init_linear's, and the per-video padded clip lengths [V] int32 are formed here)
+    w.g_video = take((bx ? (long)bx->n_videos : 1L) * d.Dv); w.g_video_init = take(((bx && a->w_init) ? (long)bx->n_videos : 1L) * d.Dv);
+    w.init_vlen = (bx && a->w_init) ? take(bx->n_videos) : -1;
     w.rows = w.row_grad = -1;
     if (x) {
         if (x->clip_parts == 3) w.rows = take((long)d.Tv * d.D);
@@ -274,7 +276,6 @@ extern "C" int echr_train_step_batch(const echr_train_step_args* a, const echr_b
     ECHR_REQUIRE(!(a->host_nll && weight), "train_step_batch: host_nll = 1 carries the weights in host_index: pass weight = NULL");
     ECHR_REQUIRE(!a->prepared && !a->defer_update && !a->g_tap, "train_step_batch: prepared, defer_update and g_tap are not part of the batched step");
     ECHR_REQUIRE(!a->handover || !a->do_step, "train_step_batch: handover = 1 needs do_step = 0 (the caller reduces the gradients, then steps)");
-    ECHR_REQUIRE(!a->w_init, "train_step_batch: an initial state (CG_init_feats_type) is not part of the batched step");
     return train_step_impl(a, stream, true, a->host_nll ? nullptr : weight, nullptr, x, video_loss);
 }
 // The joint 'tap_cg' iteration over a batch: echr_train_step_batch that also returns d loss / d tap_feats.  a->g_tap [T_tot, Ht] is zero-filled
@@ -292,7 +293,6 @@ extern "C" int echr_train_step_batch_tap(const echr_train_step_args* a, const ec
     ECHR_REQUIRE(a->vh_offset < 0 || row_offset, "train_step_batch_tap: the 'VH' scene gradient needs row_offset");
     ECHR_REQUIRE(!a->prepared && !a->defer_update && !a->mid_cb, "train_step_batch_tap: prepared, defer_update and mid_cb are not part of the batched step");
     ECHR_REQUIRE(!a->handover || !a->do_step, "train_step_batch_tap: handover = 1 needs do_step = 0 (the caller reduces the gradients, then steps)");
-    ECHR_REQUIRE(!a->w_init, "train_step_batch_tap: an initial state (CG_init_feats_type) is not part of the batched step");
     return train_step_impl(a, stream, true, a->host_nll ? nullptr : weight, nullptr, x, video_loss, row_offset);
 }
 // The frame-level contexts over a batch: echr_train_step_batch (and, with g_tap, echr_train_step_batch_tap) with the row source of
@@ -311,7 +311,7 @@ extern "C" int echr_train_step_batch_clip(const echr_train_step_args* a, const e
     ECHR_REQUIRE(!(a->host_nll && weight), "train_step_batch_clip: host_nll = 1 carries the weights in host_index: pass weight = NULL");
     ECHR_REQUIRE(!a->prepared && !a->defer_update && !a->mid_cb, "train_step_batch_clip: prepared, defer_update and mid_cb are not part of the batched step");
     ECHR_REQUIRE(!a->handover || !a->do_step, "train_step_batch_clip: handover = 1 needs do_step = 0 (the caller reduces the gradients, then steps)");
-    ECHR_REQUIRE(!a->w_init, "train_step_batch_clip: an initial state (CG_init_feats_type) is not part of the batched step");
+    ECHR_REQUIRE(!(a->w_init && a->init_use_c), "train_step_batch_clip: an initial state that reads the clip has no row gradient");
     ECHR_REQUIRE(!a->g_tap || !a->forward_only, "train_step_batch_clip: g_tap needs the backward pass (forward_only must be 0)");
     ECHR_REQUIRE(!a->g_tap || a->vh_offset < 0 || row_offset, "train_step_batch_clip: the 'VH' scene gradient needs row_offset");
     return train_step_impl(a, stream, true, a->host_nll ? nullptr : weight, x, bx, video_loss, row_offset);
@@ -415,7 +415,8 @@ static int train_step_impl(const echr_train_step_args* a, void* stream, bool rw,
         ia.use_v = a->init_use_v; ia.use_e = a->init_use_e; ia.use_c = a->init_use_c; ia.A = a->dec.A;
         ia.video = a->dec.video; ia.event = ws + L.event; ia.c3d = d.c3d; ia.ev_start = ev_start; ia.ev_len = ev_len;
         ia.w = a->w_init; ia.b = a->b_init; ia.feats = ws + L.init_feats; ia.h0 = ws + L.h0;
-        rc = echr_init_state_fwd(&ia, stream);
+        // (a batch: the scene vector of the event's own video and that video's padded clip length, formed on the device from ev_len / vid)
+        rc = bx ? echr_init_state_fwd_batch(&ia, &bxl, reinterpret_cast<int32_t*>(ws + L.init_vlen), stream) : echr_init_state_fwd(&ia, stream);
         if (rc) { if (a->overlap_encoder) (void)echr_decoder_fwd_prepare_cancel(stream); return rc; }
     }
     echr_dec_grads g = a->dec_g;
@@ -483,6 +484,11 @@ static int train_step_impl(const echr_train_step_args* a, void* stream, bool rw,
         ig.g_video = (vh && a->init_use_v) ? ws + L.g_video_init : nullptr;
         ig.g_event = a->init_use_e ? ws + L.g_event : nullptr;
         ig.dfeats = ws + L.init_dfeats;
+        if (bx) {          // d video per video [V, Dv], a fixed-order segmented sum (wanted for the 'VH' span only, like the decoder's)
+            echr_batch_ext bi = bxl;
+            bi.g_video = (vh && a->init_use_v) ? ws + L.g_video_init : nullptr;
+            RC(echr_init_state_bwd_batch(&ia, &ig, &bi, stream));
+        } else
         RC(echr_init_state_bwd(&ia, &ig, stream));
     }
     echr_tsrm_grads tg = a->tsrm_g;
@@ -503,6 +509,8 @@ static int train_step_impl(const echr_train_step_args* a, void* stream, bool rw,
     if (vh && bx) {
         // a batch: video v's scene vector is the mean over ITS rows -- d tap[r, :] += d video[v, vh span] / T_v for r in [row_offset[v], row_offset[v+1])
         RC(echr_seg_col_mean_bwd(ws + L.g_video + a->vh_offset, a->dec.Dv, row_offset, bxl.n_videos, a->Ht, a->Ht, a->g_tap, stream));
+        if (a->w_init && a->init_use_v)          // init_linear's d video reaches each video's own rows the same way
+            RC(echr_seg_col_mean_bwd(ws + L.g_video_init + a->vh_offset, a->dec.Dv, row_offset, bxl.n_videos, a->Ht, a->Ht, a->g_tap, stream));
     } else if (vh) {
         // scene context 'VH' = tap.mean(0) (CaptionGenerator.py:95-99): d tap[r, :] += d video[vh span] / rows, for the decoder's d video (final
         // behind the join: it is formed in the LSTM-layer stage on a helper stream) and init_linear's

@@ -310,7 +310,8 @@ def _caption_videos(tap_model, cg_model, videos, featstamp_to_time, vocab, topN,
     eo_b = np.concatenate([[0], np.cumsum([len(sois[v]) for v in kept])]).astype(np.int64)
     batch = extras['batch'] = VideoBatch(c3d_b, tap_b, lda_b, rows_b, eo_b, np.concatenate([sois[v] + rows_b[i] for i, v in enumerate(kept)], 0),
                                          np.concatenate([inds[v] + rows_b[i] for i, v in enumerate(kept)], 0),
-                                         clip_context_type=cg_model.opt.clip_context_type)
+                                         clip_context_type=cg_model.opt.clip_context_type,
+                                         CG_init_feats_type=getattr(cg_model.opt, 'CG_init_feats_type', ''))
     if flag_eval_what == 'tap':
         for v in kept:
             n = len(sois[v])

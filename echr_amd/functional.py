@@ -356,6 +356,59 @@ class InitState(torch.autograd.Function):
         return g_video, g_event, None, None, None, None, None, None, g_w, g_b
 
 
+class InitStateBatch(torch.autograd.Function):
+    """InitState over the events of several videos (echr_init_state_fwd_batch / _bwd_batch): `video` is [V, Dv] and event n reads row vid[n];
+    the clip mean of an event divides by the padded clip length of ITS video (the largest ev_len among that video's events, formed on the
+    device).  Row n of h0 [N_tot, 3H] is what InitState returns for that event in its own video; backward returns d video [V, Dv] (a
+    fixed-order segmented sum) and d event, and accumulates init_linear's gradients over all rows (GradSink arena accumulation)."""
+
+    @staticmethod
+    def forward(ctx, video, event, c3d, ev_start, ev_len, vid, use, sink, w, b):
+        lib = L.load()
+        use_v, use_e, use_c = use
+        video, event, c3d, w, b = _f32c(video), _f32c(event), _f32c(c3d), _f32c(w), _f32c(b)
+        if video.dim() != 2:
+            raise ValueError('video must be [V, Dv], one scene vector per video (got %s)' % (tuple(video.shape),))
+        N, De = event.shape
+        V, Dv = video.shape
+        D, H3, Dtot = c3d.shape[1], w.shape[0], w.shape[1]
+        if vid.numel() != N or ev_start.numel() != N or ev_len.numel() != N or not 1 <= V <= N:
+            raise ValueError('vid, ev_start and ev_len need one entry per event (%d) and 1 <= V <= N (V = %d)' % (N, V))
+        if Dtot != (Dv if use_v else 0) + (De if use_e else 0) + (D if use_c else 0):
+            raise L.EchrHipError('init_linear is %d wide, the selected contexts give %d' % (Dtot, (Dv if use_v else 0) + (De if use_e else 0) + (D if use_c else 0)))
+        feats = torch.empty(N, Dtot, device=event.device, dtype=torch.float32)
+        h0 = torch.empty(N, H3, device=event.device, dtype=torch.float32)
+        vlen = torch.empty(V, device=event.device, dtype=torch.int32)
+        a = L.InitStateArgs(N, Dv, De, D, H3, int(use_v), int(use_e), int(use_c), 0, None, L.ptr(event), L.ptr(c3d),
+                            L.ptr(ev_start, torch.int32), L.ptr(ev_len, torch.int32), L.ptr(w), L.ptr(b), L.ptr(feats), L.ptr(h0))
+        x, _ = batch_ext(vid, video)
+        L.check(lib.echr_init_state_fwd_batch(C.byref(a), C.byref(x), L.ptr(vlen, torch.int32), L.stream_ptr()), 'init_state_fwd_batch')
+        ctx.save_for_backward(video, event, c3d, ev_start, ev_len, vid, w, b, feats)
+        ctx.use = use
+        ctx.sink = sink
+        ctx.video_len = vlen          # the per-video padded clip lengths the device formed (written with 'C' only; h0.grad_fn.video_len)
+        return h0
+
+    @staticmethod
+    def backward(ctx, g_h0):
+        lib = L.load()
+        video, event, c3d, ev_start, ev_len, vid, w, b, feats = ctx.saved_tensors
+        use_v, use_e, use_c = ctx.use
+        N, De = event.shape
+        g_h0 = _f32c(g_h0)
+        zeroed = 1 if (ctx.sink is not None and ctx.sink.usable()) else 0
+        g_w, g_b = ctx.sink.take() if zeroed else (torch.empty_like(w), torch.empty_like(b))
+        g_video = torch.empty_like(video) if (use_v and ctx.needs_input_grad[0]) else None
+        g_event = torch.zeros_like(event) if (use_e and ctx.needs_input_grad[1]) else None
+        dfeats = torch.empty_like(feats)
+        a = L.InitStateArgs(N, video.shape[1], De, c3d.shape[1], w.shape[0], int(use_v), int(use_e), int(use_c), 0, None, L.ptr(event),
+                            L.ptr(c3d), L.ptr(ev_start, torch.int32), L.ptr(ev_len, torch.int32), L.ptr(w), L.ptr(b), L.ptr(feats), None)
+        g = L.InitStateGrads(L.ptr(g_h0), L.ptr(g_w), L.ptr(g_b), None, L.ptr(g_event) if g_event is not None else None, L.ptr(dfeats), zeroed)
+        x, _ = batch_ext(vid, video, g_video)
+        L.check(lib.echr_init_state_bwd_batch(C.byref(a), C.byref(g), C.byref(x), L.stream_ptr()), 'init_state_bwd_batch')
+        return g_video, g_event, None, None, None, None, None, None, g_w, g_b
+
+
 class ColMean(torch.autograd.Function):
     """x.mean(0) of a [T, D] feature matrix: the 'VC' / 'VH' scene contexts (CaptionGenerator.py:95-99)."""
 
@@ -415,27 +468,32 @@ class DecoderFunction(torch.autograd.Function):
 
 class DecoderBatchFunction(torch.autograd.Function):
     """DecoderFunction over the events of several videos: `video` is [V, Dv], one scene vector per video, and event n reads row vid[n]
-    (echr_decoder_fwd_batch / _bwd_batch); backward returns d video [V, Dv].  Zero initial state.  `c3d` is the batch's row source
-    (VideoBatch.clip_rows()); with 'CH' / 'CC+CH' the parameters are followed by `tap` (batch.tap) and `col0` (int: its first column in the
-    row source), and backward returns d tap [T_tot, Ht] (echr_decoder_row_grad behind echr_decoder_bwd_batch)."""
+    (echr_decoder_fwd_batch / _bwd_batch); backward returns d video [V, Dv].  `c3d` is the batch's row source (VideoBatch.clip_rows()).
+    What may follow the parameters, in this order: `h0` [N_tot, 3H] (InitStateBatch's rows: the initial state of CG_init_feats_type;
+    absent = zeros), and backward returns d h0; with 'CH' / 'CC+CH' `tap` (batch.tap) and `col0` (int: its first column in the row
+    source), and backward returns d tap [T_tot, Ht] (echr_decoder_row_grad behind echr_decoder_bwd_batch)."""
 
     @staticmethod
     def forward(ctx, video, event, c3d, ev_start, ev_len, tokens, A, disjoint, drop, sink, vid, *params):
-        # (*params, or *params + (tap, col0): the clip pair trails the parameters, so 'CC' callers pass what they always passed)
-        tap, col0 = None, 0
+        # (*params [+ (h0,)] [+ (tap, col0)]: the optional inputs trail the parameters, so zero-state 'CC' callers pass what they always passed)
+        tap, col0, h0 = None, 0, None
         if params and isinstance(params[-1], int):
             tap, col0, params = params[-2], params[-1], params[:-2]
-        return _decoder_forward(ctx, video, event, c3d, ev_start, ev_len, tokens, A, disjoint, drop, sink, None, None, tap, col0, params, vid=vid,
-                                tap_arg=11 + len(params))
+        if len(params) == len(DEC_PARAMS) + 1:
+            h0, params = params[-1], params[:-1]
+        n = 11 + len(params)
+        ctx.has_h0 = h0 is not None
+        return _decoder_forward(ctx, video, event, c3d, ev_start, ev_len, tokens, A, disjoint, drop, sink, None, h0, tap, col0, params, vid=vid,
+                                tap_arg=n + (1 if h0 is not None else 0), h0_arg=n)
 
     @staticmethod
     def backward(ctx, g_logp):
-        g_video, g_event, _, g_tap, grads = _decoder_backward(ctx, g_logp)
-        out = (g_video, g_event, None, None, None, None, None, None, None, None, None) + grads
+        g_video, g_event, g_h0, g_tap, grads = _decoder_backward(ctx, g_logp)
+        out = (g_video, g_event, None, None, None, None, None, None, None, None, None) + grads + ((g_h0,) if ctx.has_h0 else ())
         return out + (g_tap, None) if ctx.tap_meta is not None else out
 
 
-def _decoder_forward(ctx, video, event, c3d, ev_start, ev_len, tokens, A, disjoint, drop, sink, prep, h0, tap, col0, params, vid=None, tap_arg=12):
+def _decoder_forward(ctx, video, event, c3d, ev_start, ev_len, tokens, A, disjoint, drop, sink, prep, h0, tap, col0, params, vid=None, tap_arg=12, h0_arg=11):
     # tap / col0 ('CH', 'CC+CH'): the rows c3d[:, col0 : col0 + tap width] are tap[:Tv]; backward returns d tap (echr_decoder_row_grad)
     # vid (multi-video batch): int32 [N] device, video is then [V, Dv]
     lib = L.load()
@@ -443,6 +501,7 @@ def _decoder_forward(ctx, video, event, c3d, ev_start, ev_len, tokens, A, disjoi
     ctx.vid = vid
     ctx.tap_meta = (tuple(tap.shape), int(col0)) if tap is not None else None
     ctx.tap_arg = tap_arg          # position of `tap` among the Function's inputs (needs_input_grad)
+    ctx.h0_arg = h0_arg
     event = _f32c(event)
     h0 = _f32c(h0) if h0 is not None else None          # [N, 3H] initial state (OldModel.init_hidden, CG_init_feats_type); None = zeros
     S, N = tokens.shape
@@ -499,7 +558,7 @@ def _decoder_backward(ctx, g_logp):
     g_event = torch.empty_like(event)
     g_video = torch.empty_like(video) if ctx.needs_input_grad[0] else None
     h0 = ctx.h0
-    g_h0 = torch.empty_like(h0) if (h0 is not None and ctx.needs_input_grad[11]) else None
+    g_h0 = torch.empty_like(h0) if (h0 is not None and ctx.needs_input_grad[ctx.h0_arg]) else None
     want_tap = ctx.tap_meta is not None and ctx.needs_input_grad[ctx.tap_arg]
     a = _dec_args(ps, c3d, ev_start, ev_len, event, video, tokens, A, S, ws, logp, disjoint, train=train, h0=h0)
     wsb = torch.empty(lib.echr_decoder_ws_bwd_floats(C.byref(a)), device=event.device, dtype=torch.float32)
@@ -542,6 +601,12 @@ def _decoder_backward(ctx, g_logp):
             # no data-parallel hand-over waits for the LSTM-layer gradients: only d event is formed on this stream, the rest of that stage
             # runs on the library's second helper stream and is joined with the tail by the end-of-backward callback
             g.async_tail = 2
+        if g.async_tail == 2 and g_video is not None:
+            # Rule: a gradient this Function RETURNS is final in this stream's order.  With async_tail = 2 the LSTM-layer stage, which forms
+            # d video, runs on a helper stream that is joined only at the end of the backward pass, while d video's consumers -- the scene
+            # mean's backward, autograd's sum with InitState's d video -- run on this stream right behind this node without a join.  So a node
+            # whose d video is wanted ('VH' with a tap_feats that requires grad) keeps that stage on this stream; only the tail is asynchronous
+            g.async_tail = 1
         bwd()
         if hook is not None:
             # data parallel, one-call form: the LSTM-layer gradients (and everything else part A of the backward produced) are final in
@@ -591,13 +656,13 @@ def greedy_sample(video, event, c3d, ev_start, ev_len, A, seq_length, params, de
     with the masks echr_decoder_fwd draws for the same state at the same step (echr_decoder_sample_train).
 
     `vid` (int32 [N] device): greedy decode of a multi-video batch -- `video` is [V, Dv] and event n reads row vid[n]
-    (echr_decoder_sample_batch).
+    (echr_decoder_sample_batch); `h0` is then InitStateBatch's [N, 3H] (an initial state takes the per-step chain at every row count).
 
     Returns (seq int64 [N,T], logp fp32 [N,T]) with T <= seq_length, or ([], []) when nothing was generated.
     `defer=True`: the decode is queued and a function is returned that performs the host read and returns the result -- a caller with
     several decodes in flight pays one stream drain for all of them (fused.SelfCriticalBatchStep)."""
-    if vid is not None and (multinomial or drop is not None or h0 is not None):
-        raise NotImplementedError('the batched decode is the greedy one from the zero initial state')
+    if vid is not None and (multinomial or drop is not None):
+        raise NotImplementedError('the batched decode here is the greedy one (the sampled pass of a batch is sample_train_batch)')
     if drop is not None and not multinomial:
         raise ValueError('a dropout state is taken by the multinomial decode only (the greedy baseline runs in eval mode)')
     lib = L.load()
@@ -660,11 +725,11 @@ def greedy_sample(video, event, c3d, ev_start, ev_len, A, seq_length, params, de
     return finish if defer else finish()
 
 
-def sample_train_batch(video, event, c3d, ev_start, ev_len, vid, A, seq_length, params, drop, temperature=1.0, seed=0, defer=False):
+def sample_train_batch(video, event, c3d, ev_start, ev_len, vid, A, seq_length, params, drop, temperature=1.0, seed=0, defer=False, h0=None):
     """The sampled pass of self-critical training over a multi-video batch (echr_decoder_sample_train_batch): `greedy_sample(...,
     multinomial=True, drop=)` with `video` [V, Dv] and `vid` int32 [N] (device, non-decreasing) naming each event's video.  The decoder's
     dropout is active under `drop` with the masks the batched teacher-forced forward draws at the same step; the draws are keyed (seed,
-    batch-global row, step); batches start from the zero state.
+    batch-global row, step); `h0` [N, 3H]: InitStateBatch's initial state (None = zeros).
 
     Returns (seq int64 [N,T], logp fp32 [N,T], video_words): video_words is a host int64 [V] with the width each video's own call cuts its
     output at (the largest number of non-zero tokens among its rows) and T = max(video_words); ([], [], zeros) when T == 0.  One host read
@@ -682,7 +747,8 @@ def sample_train_batch(video, event, c3d, ev_start, ev_len, vid, A, seq_length, 
     video, event, c3d = _f32c(video), _f32c(event), _f32c(c3d)
     ps = [_f32c(p) for p in params]
     dev = event.device
-    a = _dec_args(ps, c3d, ev_start, ev_len, event, video, None, A, seq_length, None, None)
+    h0 = _f32c(h0) if h0 is not None else None
+    a = _dec_args(ps, c3d, ev_start, ev_len, event, video, None, A, seq_length, None, None, h0=h0)
     ws = torch.empty(lib.echr_decoder_ws_floats(C.byref(a)), device=dev, dtype=torch.float32)
     a.ws = L.ptr(ws)
     wss = torch.empty(lib.echr_sampler_ws_floats(C.byref(a)), device=dev, dtype=torch.float32)
@@ -697,7 +763,7 @@ def sample_train_batch(video, event, c3d, ev_start, ev_len, vid, A, seq_length, 
             'decoder_sample_train_batch')
 
     def finish():          # (holds ws / wss / xws and the converted inputs until the host read below)
-        keep = (ws, wss, xws, video, event, c3d, ps)          # noqa: F841
+        keep = (ws, wss, xws, video, event, c3d, ps, h0)          # noqa: F841
         host = counts.cpu().numpy()                # the only device->host sync of the whole decode
         L.check(lib.echr_check_async(), 'decoder_sample_train_batch')
         nun, vw = host[:seq_length + 1], host[seq_length + 1:].astype(np.int64)
@@ -756,10 +822,10 @@ def beam_search(video, event, c3d, ev_start, ev_len, A, seq_length, params, beam
     return seq[:, :T].contiguous(), slp[:, :T].contiguous(), score
 
 
-def beam_search_batch(video, event, c3d, ev_start, ev_len, vid, A, seq_length, params, beam_size, trim=True):
+def beam_search_batch(video, event, c3d, ev_start, ev_len, vid, A, seq_length, params, beam_size, trim=True, h0=None):
     """`beam_search` over the events of a multi-video batch in one decode (echr_decoder_beam_batch): `video` is [V, Dv], `vid` int32 [N]
     (device, non-decreasing) names each event's video, `c3d` / `ev_start` are the batch's concatenated rows and batch-absolute starts.
-    event, ev_start, ev_len and vid are repeated per slot; batches start from the zero state.
+    event, ev_start, ev_len, vid and `h0` (InitStateBatch's [N, 3H]; None = zeros) are repeated per slot.
 
     Returns (seq int64 [N,T], logp fp32 [N,T], score fp32 [N], video_words): video_words is a host int64 [V] with the longest result's
     word count of each video -- the width that video's decode has alone -- and T = max(video_words).  A video's rows are zero from its
@@ -784,7 +850,8 @@ def beam_search_batch(video, event, c3d, ev_start, ev_len, vid, A, seq_length, p
     rep = lambda x: x.repeat_interleave(B, dim=0).contiguous()          # event-major: row n*B + j is slot j of event n
     # (named: the library reads these through raw pointers, so they must outlive the call's kernels -- until the host read below)
     vid_r, ev_start_r, ev_len_r, event_r = rep(vid.to(torch.int32)), rep(ev_start.to(torch.int32)), rep(ev_len.to(torch.int32)), rep(event)
-    a = _dec_args(ps, c3d, ev_start_r, ev_len_r, event_r, video, None, A, seq_length, None, None)
+    h0_r = rep(_f32c(h0)) if h0 is not None else None
+    a = _dec_args(ps, c3d, ev_start_r, ev_len_r, event_r, video, None, A, seq_length, None, None, h0=h0_r)
     ws = torch.empty(lib.echr_decoder_ws_floats(C.byref(a)), device=dev, dtype=torch.float32)
     a.ws = L.ptr(ws)
     seq = torch.empty(N, seq_length, device=dev, dtype=torch.int64)

@@ -235,7 +235,8 @@ class FusedTrainStep(object):
         `device_criterion=True` hands targets / masks / weights over as device tensors (all rows) instead of with the index vectors;
         `video_losses=False` skips the per-video losses (`last_video_losses` is then None).
         A model with 'CH' / 'CC+CH' rows takes a batch built for them (VideoBatch.from_videos(..., clip_context_type=)) and runs
-        echr_train_step_batch_clip."""
+        echr_train_step_batch_clip; a model with an initial decoder state takes a batch built for it (CG_init_feats_type=): the call
+        forms the state of all rows and init_linear's gradients itself (echr_init_state_fwd_batch / _bwd_batch)."""
         if unsupported:
             raise NotImplementedError('FusedTrainStep.batch does not take %s: tap_grad / defer_update / prepared over a batch are follow-ups '
                                       '(one video per call); the hand-over points of a batch are batch_handover(), the data-parallel step over '
@@ -665,14 +666,16 @@ class SelfCriticalBatchStep(object):
             video = EF._f32c(video)
             self.last_event = event          # the event context the decodes read (inspection: the step recomputes it)
             ps = lm.native_params()
+            # (CG_init_feats_type: both decodes start from the batch's initial state; the step below recomputes it inside the call)
+            h0 = m._batch_initial_state(batch, video, event, ev_start, ev_len, vid)
             sampled = None
             if gen_result is None:
                 sampled = EF.sample_train_batch(video, event, batch.clip_rows(), ev_start, ev_len, vid, A, lm.seq_length, ps, drop,
-                                                seed=lm._sample_seed(), defer=True)
+                                                seed=lm._sample_seed(), defer=True, h0=h0)
             if '_sample_tables' not in lm.__dict__:
                 lm._sample_tables = {}
             greedy_f = EF.greedy_sample(video, event, batch.clip_rows(), ev_start, ev_len, A, lm.seq_length, ps, table_cache=lm._sample_tables,
-                                        vid=vid, defer=True)
+                                        vid=vid, defer=True, h0=h0)
             # the one host sync of the iteration: the first read drains the stream, both decodes included
             if sampled is not None:
                 gen, _, vw = sampled()
@@ -962,10 +965,11 @@ class JointBatchStep(object):
                 raise ValueError('the batch carries no labels')
             tap = self._sst_forward(src.c3d, src.row_offset)
             batch = VideoBatch(src.c3d, tap, src.lda, src.row_offset, src.event_offset, src.soi, src.ind, src.labels, src.masks,
-                               clip_context_type=src.clip_context_type)
+                               clip_context_type=src.clip_context_type, CG_init_feats_type=src.CG_init_feats_type)
         else:
             batch = VideoBatch.from_videos(videos_or_batch, device=self.dev, tap_fn=self._sst_forward,
-                                           clip_context_type=m.opt.clip_context_type)
+                                           clip_context_type=m.opt.clip_context_type,
+                                           CG_init_feats_type=getattr(m.opt, 'CG_init_feats_type', ''))
             if batch.labels is None:
                 raise ValueError('the videos carry no labels / masks')
         sa, bx, dc, ro, ro_dev, ps, c3d, V, T, K = self._sst

@@ -360,6 +360,10 @@ def make_attsat(name, clip_context_type='CC'):
 #   vbch / vbcch  the vbctx construction (5 videos incl. a one-event video, 'VLVCVH', 'ER3', ragged label widths) with at most 16 events and the
 #          frame-level context 'CH' (D = 512: the persistent recurrences, all three gradient paths into tap) / 'CC+CH' (D = 1012: launch-per-phase)
 #   vbch33 'CH' over 33 videos of 4 events (132 rows: launch-per-phase recurrences, the chain sampler, the event encoder's general kernels)
+#   vbinit / vbinitch  the vbctx construction with at most 16 events and the non-zero initial decoder state: 'VEC' over 'CC' rows (<= 64 rows: a
+#          zero-state batch would take the persistent recurrences here, this one must not; the per-video longest events differ, so a batch-wide
+#          divisor of the clip mean shows) / 'VE' over 'CH' rows (init_linear's d video through 'VH' into tap beside the three other paths)
+#   vbinit33 'VEC' over 33 videos of 4 events (132 rows: the chain sampler, the event encoder's general kernels)
 VBATCH = {
     'vb16': dict(opt=dict(CG_vocab_size=5000, CG_seq_length=19), V=16, events=(2, 6), max_events=64, seg=(3, 60), T=(40, 160), L=(12, 21), seed=1000),
     'vbctx': dict(opt=dict(video_context_type='VLVCVH', CG_vocab_size=300, CG_seq_length=7), V=5, events=(1, 4), single=2, max_events=64, seg=(3, 30),
@@ -381,6 +385,17 @@ VBATCH = {
                   max_events=16, seg=(3, 30), T=(30, 60), L=(6, 9), seed=1600),
     'vbch33': dict(opt=dict(clip_context_type='CH', CG_vocab_size=300, CG_seq_length=7), V=33, events=(4, 4), max_events=132, seg=(3, 30), T=(30, 80),
                    L=(6, 9), seed=1700),
+    # the initial decoder state over a batch (tests/golden/case_init_batch.npz; case seeds picked like vb16's: tools/make_golden_init_batch.py
+    # asserts the greedy margins; vbinit's is also the first of 1800, 1900, ... whose longest event sits in a one-event video, so that every
+    # multi-event video's padded clip length is below the batch-wide one)
+    'vbinit': dict(opt=dict(CG_init_feats_type='VEC', video_context_type='VLVCVH', CG_vocab_size=300, CG_seq_length=7), V=5, events=(1, 4), single=2,
+                   max_events=16, seg=(3, 30), T=(30, 60), L=(6, 9), seed=2800),
+    'vbinitch': dict(opt=dict(CG_init_feats_type='VE', clip_context_type='CH', video_context_type='VLVCVH', CG_vocab_size=300, CG_seq_length=7), V=5,
+                     events=(1, 4), single=2, max_events=16, seg=(3, 30), T=(30, 60), L=(6, 9), seed=1900),
+    # (vbinit33 has no reference fixture: its seed is the first of 2000, 2100, ... whose ORACLE greedy margin exceeds 2e-5 -- init_batch_ref.greedy_margin,
+    # asserted by tests/test_init_batch_host.py)
+    'vbinit33': dict(opt=dict(CG_init_feats_type='VEC', CG_vocab_size=300, CG_seq_length=7), V=33, events=(4, 4), max_events=132, seg=(3, 30), T=(30, 80),
+                     L=(6, 9), seed=2300),
 }
 
 

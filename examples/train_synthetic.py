@@ -152,7 +152,8 @@ def data_parallel_batch(a, opt, dev, loader, tap_model, cg_model, cg_opt, tap_op
         else:
             with torch.no_grad():          # the proposal encoder is idle in these stages: its states carry no graph
                 batch = VideoBatch.from_videos([{k: v[k] for k in (keys[:4] if a.self_critical else keys)} for v in vids], device=dev,
-                                               tap_model=tap_model, clip_context_type=opt.clip_context_type)
+                                               tap_model=tap_model, clip_context_type=opt.clip_context_type,
+                                               CG_init_feats_type=opt.CG_init_feats_type)
             rewards[:] = [overlap_reward(v['labels']) for v in vids]
             loss = dp(batch)
         history.append(float(loss) / a.m_batch)
@@ -218,7 +219,7 @@ def self_critical(a, opt, dev, loader, tap_model, cg_model, cg_opt, start):
             rewards = [overlap_reward(v['labels']) for v in vids]          # reward_fn is called once per video (step.current_video)
             with torch.no_grad():
                 batch = VideoBatch.from_videos([{k: v[k] for k in ('c3d', 'lda', 'ind', 'soi')} for v in vids], device=dev, tap_model=tap_model,
-                                                 clip_context_type=opt.clip_context_type)
+                                                 clip_context_type=opt.clip_context_type, CG_init_feats_type=opt.CG_init_feats_type)
             step = SelfCriticalBatchStep(fused, lambda gen, greedy: rewards[step.current_video](gen, greedy))
             loss = step(batch)[0]
         history.append(float(loss) / a.m_batch)
@@ -241,6 +242,8 @@ def main(argv=None):
     ap.add_argument('--lr', type=float, default=5e-4)
     ap.add_argument('--clip_context_type', type=str, default='CC', help="frame-level context: 'CC', 'CH' or 'CC+CH' (opts.py:130); the batches of "
                                                                         "--m_batch V are built for it")
+    ap.add_argument('--CG_init_feats_type', type=str, default='', help="non-zero initial decoder state from 'V', 'E', 'C' (opts.py); the batches "
+                                                                       "of --m_batch V are built for it")
     ap.add_argument('--dist_backend', type=str, default='nccl', help="under torchrun: 'nccl' (RCCL, one device per rank) or 'gloo' (also the "
                                                                      "rehearsal with every rank on one device)")
     ap.add_argument('--save', type=str, default='')
@@ -257,6 +260,7 @@ def main(argv=None):
     dev = torch.device('cuda')
     opt = synth.default_opt(vocab_size=a.vocab, seq_length=10, K=32, lr=a.lr)
     opt.clip_context_type = a.clip_context_type
+    opt.CG_init_feats_type = a.CG_init_feats_type
     torch.manual_seed(0)
     tap_model = models.setup_tap(opt).to(dev)
     cg_model = echr_amd.CaptionGenerator(opt).to(dev)

@@ -748,19 +748,30 @@ int echr_seg_col_mean_fwd(const float* x, const int32_t* row_offset, int32_t n_s
                           void* stream);
 int echr_seg_col_mean_bwd(const float* g, int64_t ld_g, const int32_t* row_offset, int32_t n_seg, int32_t cols, int64_t ld, float* gx,
                           void* stream);
+/* Non-zero initial decoder state (CG_init_feats_type) of a batch: row n of a->h0 [N, 3H] is what echr_init_state_fwd forms for event n in
+ * its own video.  'V' reads x->video[vid[n], :] (a->video is ignored); 'C' divides the sum over the event's rows by the padded clip length
+ * of ITS video, the largest ev_len among that video's events (a->A is ignored) -- video_len: device int32 [V] scratch, written on the
+ * device by the call (may be NULL without 'C'); no host index is added.  A one-video batch equals echr_init_state_fwd bit for bit (same
+ * summation order, same product).  x->ws is not read.
+ * bwd: init_linear's gradients summed over all rows of all videos (written, or accumulated when `zeroed`); d event ADDED to g->g_event;
+ * x->g_video [V, Dv] (optional; g->g_video is ignored) WRITTEN with the sum over the rows of each video in ascending row order -- vid is
+ * non-decreasing, so a contiguous run: one fixed order, no atomics. */
+int echr_init_state_fwd_batch(const echr_init_state_args* a, const echr_batch_ext* x, int32_t* video_len, void* stream);
+int echr_init_state_bwd_batch(const echr_init_state_args* a, const echr_init_state_grads* g, const echr_batch_ext* x, void* stream);
 int echr_tsrm_fwd_batch(const echr_tsrm_args* a, const echr_dropout* drop, const echr_batch_ext* x, void* stream);
 /* (the backward kernels need no mask: the saved softmax weights of cross-video pairs are exactly 0, so d score = w * (..) is 0 there) */
 int echr_tsrm_bwd_batch(const echr_tsrm_args* a, const echr_tsrm_grads* g, const echr_dropout* drop, const echr_batch_ext* x, void* stream);
 /* a->prepared must be 0.  N <= 64 takes the persistent recurrences exactly as a single video does (they read the gate pre-activations,
- * which already hold the per-row scene part). */
+ * which already hold the per-row scene part); with a->h0 (echr_init_state_fwd_batch's rows) the launch-per-phase ones run at every row
+ * count, as for one video, and echr_decoder_bwd_batch writes g->g_h0. */
 int echr_decoder_fwd_batch(const echr_dec_args* a, const echr_dropout* drop, const echr_batch_ext* x, void* stream);
 /* d W_ih2[:, E:] = (sum over time and over the events of a video of d gates2)^T . video; x->g_video [V, Dv] the matching data gradient */
 int echr_decoder_bwd_batch(const echr_dec_args* a, const echr_dec_grads* g, const echr_dropout* drop, const echr_batch_ext* x, void* stream);
-/* Greedy decode of a batch (a->multinomial must be 0): echr_decoder_sample with per-row scene vectors. */
+/* Greedy decode of a batch (a->multinomial must be 0): echr_decoder_sample with per-row scene vectors (dec.h0: the per-step chain). */
 int echr_decoder_sample_batch(const echr_sample_args* a, const echr_batch_ext* x, void* stream);
 /* Beam search over a batch: echr_decoder_beam with per-row scene vectors.  a->dec.N = events * beam_size event-major rows as there;
  * x->vid is a device [dec.N] array in which the B rows of an event carry that event's video (non-decreasing), x->video [V, Dv], x->ws
- * echr_batch_ws_floats(dec.N, V, H) floats; dec.h0 must be NULL (batches start from the zero state) and rows_disjoint 0.  seq, seq_logp,
+ * echr_batch_ws_floats(dec.N, V, H) floats; dec.h0 (optional, echr_init_state_fwd_batch's rows) repeated B times per event; rows_disjoint 0.  seq, seq_logp,
  * score and words are echr_decoder_beam's; echr_beam_ws_floats sizes ws_beam.
  * video_words: device int32 [V+1] out, written behind the result on the same stream -- video_words[v] = the largest word count among
  * the events of video v (the contiguous run of events e whose row e*B has vid == v; 0 for a video without an event), video_words[V] =
@@ -768,7 +779,7 @@ int echr_decoder_sample_batch(const echr_sample_args* a, const echr_batch_ext* x
  * this vector once, instead of words[N/B], and cuts every video's rows to the width that video alone would have produced. */
 int echr_decoder_beam_batch(const echr_beam_args* a, const echr_batch_ext* x, int32_t* video_words, void* stream);
 /* The sampled pass of self-critical training over a batch: echr_decoder_sample_train (a->multinomial must be 1, training-mode dropout under
- * `drop` with the masks echr_decoder_fwd_batch draws at the same step, zero initial state, the launch-per-step chain) with per-row scene
+ * `drop` with the masks echr_decoder_fwd_batch draws at the same step, the initial state of dec.h0 or zeros, the launch-per-step chain) with per-row scene
  * vectors.  Draws are keyed (seed, batch-global row, step), so a one-video batch equals echr_decoder_sample_train bit for bit.  The
  * multinomial step is ONE launch per step: the workgroup of a row forms it from the k-slice slabs of the logits product (or reads the
  * finished logits of the many-row chain), keeps it on chip and draws -- the token and log-prob of the single-video entry's slab-sum + draw
@@ -781,16 +792,18 @@ int echr_decoder_sample_train_batch(const echr_sample_args* a, const echr_dropou
 /* echr_train_step over a batch.  Criterion weights as in echr_train_step_rw: `weight` device [N,S] with host_nll = 0, or behind the mask
  * in host_index with host_nll = 1 (then weight = NULL).  host_index additionally ENDS with vid[N]; x->vid and x->ws are ignored (the
  * library points them at its staged copy / its own workspace).  loss[0] = the summed loss, loss[1] = sum(mask) over the batch;
- * video_loss: optional device [V] out, the per-video losses (fixed summation order).  Not with prepared, defer_update, g_tap nor an
- * initial state (w_init must be NULL: CG_init_feats_type over a batch is a follow-up).  handover = 1 (with do_step = 0) records both
- * hand-over points, see echr_handover_wait. */
+ * video_loss: optional device [V] out, the per-video losses (fixed summation order).  Not with prepared, defer_update nor g_tap.  With
+ * w_init (CG_init_feats_type) echr_init_state_fwd_batch / _bwd_batch run around the decoder as echr_init_state_fwd / _bwd do for one
+ * video: the per-video padded clip lengths are formed on the device, the recurrences are the launch-per-phase ones at every row count.
+ * handover = 1 (with do_step = 0) records both hand-over points, see echr_handover_wait (init_linear's slots lie in neither range). */
 int64_t echr_train_step_batch_ws_floats(const echr_train_step_args* a, const echr_batch_ext* x);
 int echr_train_step_batch(const echr_train_step_args* a, const echr_batch_ext* x, const float* weight, float* video_loss, void* stream);
 /* The joint 'tap_cg' iteration over a batch: echr_train_step_batch with a->g_tap set.  g_tap [T_tot, Ht] is zero-filled by the caller and
  * added into in place: d loss / d tap of the anchors' rows through the block-diagonal event encoder (a->dec / host_index `ind` are
  * batch-absolute; 'ER1' adds nothing), and with 'VH' (a->vh_offset >= 0) each video's d scene vector spread over that video's OWN rows --
  * row_offset: device int32 [V+1] (may be NULL without 'VH').  a->g_loss (device scalar) scales every gradient, g_tap included (lambda2);
- * loss and video_loss are reported unscaled.  Not with prepared, defer_update, mid_cb, forward_only nor an initial state.  handover = 1
+ * loss and video_loss are reported unscaled.  Not with prepared, defer_update, mid_cb nor forward_only.  With w_init and 'V', init_linear's
+ * d video [V, Dv] is spread over each video's own rows like the decoder's.  handover = 1
  * (with do_step = 0) records both hand-over points (g_tap and the 'VH' span are no part of flat_g), see echr_handover_wait. */
 int64_t echr_train_step_batch_tap_ws_floats(const echr_train_step_args* a, const echr_batch_ext* x);
 int echr_train_step_batch_tap(const echr_train_step_args* a, const echr_batch_ext* x, const float* weight, float* video_loss,
@@ -802,8 +815,8 @@ int echr_train_step_batch_tap(const echr_train_step_args* a, const echr_batch_ex
  * not read.  With a->g_tap set ([T_tot, Ht], zero-filled by the caller) it is also the joint form of echr_train_step_batch_tap: g_tap gains
  * the anchors' rows through the block-diagonal event encoder, the 'VH' span spread over each video's own rows (row_offset, device [V+1];
  * may be NULL without 'VH') and the clip-row gradient (echr_decoder_row_grad's sum; its context term reads the compacted active rows
- * directly, "row_grad_list"), all three scaled by a->g_loss, and is final when the call returns.  Not with prepared, defer_update,
- * mid_cb nor an initial state; dec.D must match clip_parts.  handover = 1 (with do_step = 0) records both hand-over points (the clip-row
+ * directly, "row_grad_list"), all three scaled by a->g_loss, and is final when the call returns.  Not with prepared, defer_update nor
+ * mid_cb, nor with an initial state that reads the clip ('C': it has no row gradient); dec.D must match clip_parts.  handover = 1 (with do_step = 0) records both hand-over points (the clip-row
  * gradient goes into g_tap, behind the join of the helper streams: no part of flat_g), see echr_handover_wait. */
 int64_t echr_train_step_batch_clip_ws_floats(const echr_train_step_args* a, const echr_clip_step_args* x, const echr_batch_ext* bx);
 int echr_train_step_batch_clip(const echr_train_step_args* a, const echr_clip_step_args* x, const echr_batch_ext* bx, const float* weight,
