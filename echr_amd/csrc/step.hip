@@ -23,10 +23,22 @@ static inline int init_feats_width(const echr_train_step_args* a) {
     return (a->init_use_v ? a->dec.Dv : 0) + (a->init_use_e ? a->dec.De : 0) + (a->init_use_c ? a->dec.D : 0);
 }
 
-// rw: echr_train_step_rw -- the index region holds the criterion weights [N,S] too (host_nll = 1)
-// x: echr_train_step_clip -- the 'CC+CH' row source [Tv, Dc + Ht] and the clip-row gradient's scratch
-// bx: echr_train_step_batch -- the index region ends with vid [N]; the batch scratch (echr_batch_ws_floats) is carved here too
-static StepWs carve_step(const echr_train_step_args* a, bool rw = false, const echr_clip_step_args* x = nullptr, const echr_batch_ext* bx = nullptr) {
+// One call of any of the six entries (echr_train_step and _rw, _clip, _batch, _batch_tap, _batch_clip): what the entry was handed, and
+// the rules it checks in the order it checks them (validate_step).
+// rw: the criterion is weighted -- the index region holds the weights [N,S] too (host_nll = 1), or rw_dev is their device form
+// x: 'CH' / 'CC+CH' -- the 'CC+CH' row source [Tv, Dc + Ht] and the clip-row gradient's scratch
+// bx: a multi-video batch -- the index region ends with vid [N]; the batch scratch (echr_batch_ws_floats) is carved here too
+enum StepRule : char { R_END, R_CLIP, R_BATCH, R_ROWS, R_WIDTH, R_WEIGHTS, R_PREPARED, R_BATCHED, R_HANDOVER, R_INIT_C, R_TAP, R_TAP_BWD, R_VH };
+struct StepCall {
+    const echr_train_step_args* a; const char* name; const StepRule* rules;          // (name: the entry's suffix, for messages)
+    const char* no_prepare = nullptr;          // why a single-video entry refuses prepared = 1 (R_PREPARED on its list)
+    bool rw = false; const float* rw_dev = nullptr; const echr_clip_step_args* x = nullptr; const echr_batch_ext* bx = nullptr;
+    float* video_loss = nullptr; const int32_t* row_offset = nullptr;
+    bool no_g_tap = false;                     // echr_train_step_batch: g_tap is refused (R_TAP on the list: required; otherwise either way)
+};
+
+static StepWs carve_step(const StepCall& c) {
+    const echr_train_step_args* a = c.a; const echr_clip_step_args* x = c.x; const echr_batch_ext* bx = c.bx; const bool rw = c.rw;
     StepWs w;
     long off = 0;
     auto take = [&](long n) { long o = off; off += up64(n); return o; };
@@ -130,7 +142,74 @@ using namespace echr;
 
 #define RC(x) do { int rc__ = (x); if (rc__) return rc__; } while (0)
 
-extern "C" int64_t echr_train_step_ws_floats(const echr_train_step_args* a) { return a ? carve_step(a).total : -1; }
+// ---- the six entries: their descriptors and the one validator --------------------------------------------------------------------
+//   entry          g_tap      prepared                     defer_update / mid_cb      rules, in the entry's own order: RULES_* below
+//   ""             either     taken                        taken
+//   "_rw"          either     refused (no weights there)   taken
+//   "_clip"        either     refused (rows = tap_feats)   taken
+//   "_batch"       REFUSED    refused                      defer refused, mid unread
+//   "_batch_tap"   REQUIRED   refused                      both refused
+//   "_batch_clip"  either     refused                      both refused
+static const StepRule RULES_PLAIN[] = {R_END}, RULES_RW[] = {R_WEIGHTS, R_PREPARED, R_END},
+                      RULES_CLIP[] = {R_CLIP, R_ROWS, R_WIDTH, R_PREPARED, R_INIT_C, R_WEIGHTS, R_END},
+                      RULES_BATCH[] = {R_BATCH, R_WEIGHTS, R_BATCHED, R_HANDOVER, R_END},
+                      RULES_BATCH_TAP[] = {R_BATCH, R_WEIGHTS, R_TAP, R_VH, R_BATCHED, R_HANDOVER, R_END},
+                      RULES_BATCH_CLIP[] = {R_CLIP, R_BATCH, R_ROWS, R_WIDTH, R_WEIGHTS, R_BATCHED, R_HANDOVER, R_INIT_C, R_TAP_BWD, R_VH, R_END};
+
+static StepCall plain_call(const echr_train_step_args* a) { return StepCall{a, "", RULES_PLAIN}; }
+static StepCall rw_call(const echr_train_step_args* a, const float* weight = nullptr) {
+    return StepCall{a, "_rw", RULES_RW, "echr_train_step_prepare does not take the weights", true, weight};
+}
+static StepCall clip_call(const echr_train_step_args* a, const echr_clip_step_args* x) {
+    const bool rw = x && x->rw;
+    return StepCall{a, "_clip", RULES_CLIP, "the clip rows are tap_feats: echr_train_step_prepare cannot run ahead of them", rw, rw ? x->weight : nullptr, x};
+}
+static StepCall batch_call(const echr_train_step_args* a, const echr_batch_ext* bx, const float* weight = nullptr, float* video_loss = nullptr) {
+    StepCall c{a, "_batch", RULES_BATCH};
+    c.rw = c.no_g_tap = true; c.rw_dev = weight; c.bx = bx; c.video_loss = video_loss;
+    return c;
+}
+static StepCall batch_tap_call(const echr_train_step_args* a, const echr_batch_ext* bx, const float* weight, float* video_loss, const int32_t* row_offset) {
+    StepCall c = batch_call(a, bx, weight, video_loss); c.name = "_batch_tap"; c.rules = RULES_BATCH_TAP; c.no_g_tap = false; c.row_offset = row_offset;
+    return c;
+}
+static StepCall batch_clip_call(const echr_train_step_args* a, const echr_clip_step_args* x, const echr_batch_ext* bx, const float* weight = nullptr,
+                                float* video_loss = nullptr, const int32_t* row_offset = nullptr) {
+    StepCall c = batch_tap_call(a, bx, weight, video_loss, row_offset); c.name = "_batch_clip"; c.rules = RULES_BATCH_CLIP; c.x = x;
+    return c;
+}
+static int check_n_active(const echr_train_step_args* a) {
+    ECHR_REQUIRE(a->n_active >= 0 && a->n_active <= a->dec.S * a->dec.N, "train_step: n_active out of range");
+    return 0;
+}
+
+// every argument rule of the entries, each stated once; an entry checks the ones on its list, in that order
+static int validate_step(const StepCall& c) {
+    const echr_train_step_args* a = c.a; const echr_clip_step_args* x = c.x; const echr_batch_ext* bx = c.bx; const char* n = c.name;
+    for (const StepRule* r = c.rules; *r != R_END; ++r) switch (*r) {
+    case R_CLIP: ECHR_REQUIRE(a && x && (x->clip_parts == 2 || x->clip_parts == 3), "train_step%s: clip_parts must be 2 ('CH') or 3 ('CC+CH')", n); break;
+    case R_BATCH: ECHR_REQUIRE(a && bx && bx->n_videos > 0 && bx->n_videos <= a->dec.N && bx->video, "train_step%s: the batch extension needs 0 < n_videos <= N and video", n); break;
+    case R_ROWS: ECHR_REQUIRE(x->c3d && x->Dc > 0 && a->tap && a->Ht > 0, "train_step%s: c3d / tap missing", n); break;
+    case R_WIDTH: ECHR_REQUIRE(a->dec.D == (x->clip_parts == 3 ? x->Dc + a->Ht : a->Ht), "train_step%s: dec.D = %d is not the width of the clip rows", n, a->dec.D); break;
+    case R_WEIGHTS:          // (after this rule rw_dev is the device weight or, with host_nll = 1, NULL)
+        if (!c.rw) break;
+        ECHR_REQUIRE(a && (a->host_nll || c.rw_dev), "train_step%s: the criterion weights are missing (device `weight`, or host_index with host_nll = 1)", n);
+        ECHR_REQUIRE(!(a->host_nll && c.rw_dev), "train_step%s: host_nll = 1 carries the weights in host_index: pass weight = NULL", n);
+        break;
+    case R_PREPARED: ECHR_REQUIRE(!a->prepared, "train_step%s: %s (prepared must be 0)", n, c.no_prepare); break;
+    case R_BATCHED:          // (echr_train_step_batch never reads mid_cb: the form that calls it needs g_tap)
+        ECHR_REQUIRE(!a->prepared && !a->defer_update && !(c.no_g_tap ? (const void*)a->g_tap : (const void*)a->mid_cb),
+                     "train_step%s: prepared, defer_update and %s are not part of the batched step", n, c.no_g_tap ? "g_tap" : "mid_cb");
+        break;
+    case R_HANDOVER: ECHR_REQUIRE(!a->handover || !a->do_step, "train_step%s: handover = 1 needs do_step = 0 (the caller reduces the gradients, then steps)", n); break;
+    case R_INIT_C: ECHR_REQUIRE(!(a->w_init && a->init_use_c), "train_step%s: an initial state that reads the clip has no row gradient", n); break;
+    case R_TAP: ECHR_REQUIRE(a->g_tap && a->tap && a->Ht > 0 && !a->forward_only, "train_step%s: g_tap / tap missing (without g_tap this is echr_train_step_batch)", n); break;
+    case R_TAP_BWD: ECHR_REQUIRE(!a->g_tap || !a->forward_only, "train_step%s: g_tap needs the backward pass (forward_only must be 0)", n); break;
+    case R_VH: ECHR_REQUIRE(!a->g_tap || a->vh_offset < 0 || c.row_offset, "train_step%s: the 'VH' scene gradient needs row_offset", n); break;
+    case R_END: break;
+    }
+    return 0;
+}
 
 // diagnostic (ECHR_STEP_TIMING=1): HIP events at the phase boundaries of the call on the caller's stream; every 50th call prints the averages
 struct StepTiming { hipEvent_t e[6][8] = {}; int calls = 0; bool on = false, init = false; double acc[5] = {0, 0, 0, 0, 0}; int n = 0; };
@@ -198,10 +277,12 @@ static echr_dec_args step_dec_args(const echr_train_step_args* a, const StepWs& 
     d.h0 = a->w_init ? a->ws + L.h0 : nullptr;
     return d;
 }
-static size_t step_index_count(const echr_train_step_args* a, bool rw = false, const echr_batch_ext* bx = nullptr) {
-    return (size_t)(3 + a->dec.S) * a->dec.N + (size_t)a->n_active + (a->host_nll ? (rw ? 3 : 2) * (size_t)a->dec.S * a->dec.N : 0) +
-           (bx ? (size_t)a->dec.N : 0);
+// the staged index region in int32 words: what every call stages (the offset of a batch's vid), and with vid [N] behind it
+static size_t step_vid_offset(const StepCall& c) {
+    const echr_train_step_args* a = c.a;
+    return (size_t)(3 + a->dec.S) * a->dec.N + (size_t)a->n_active + (a->host_nll ? (c.rw ? 3 : 2) * (size_t)a->dec.S * a->dec.N : 0);
 }
+static size_t step_index_count(const StepCall& c) { return step_vid_offset(c) + (c.bx ? (size_t)c.a->dec.N : 0); }
 
 // Optional first half of echr_train_step for the joint 'tap_cg' iteration (train.py:300-313): everything of the call that does not read
 // tap_feats -- index staging and the decoder's event-independent part (attention projections of the video, token-side gates, operand packs,
@@ -213,11 +294,12 @@ extern "C" int echr_train_step_prepare(const echr_train_step_args* a, void* stre
     ECHR_REQUIRE(a->overlap_encoder, "train_step_prepare: needs overlap_encoder = 1");
     hipStream_t st = (hipStream_t)stream;
     RC(join_tail(st));
-    const StepWs L = carve_step(a);
+    const StepCall c = plain_call(a);
+    const StepWs L = carve_step(c);
     ECHR_REQUIRE(a->ws_floats >= L.total, "train_step_prepare: workspace holds %lld floats, %ld needed (echr_train_step_ws_floats)", (long long)a->ws_floats, L.total);
-    ECHR_REQUIRE(a->n_active >= 0 && a->n_active <= a->dec.S * a->dec.N, "train_step: n_active out of range");
+    RC(check_n_active(a));
     int32_t* idx = reinterpret_cast<int32_t*>(a->ws + L.idx);
-    RC(stage_indices(a->host_index, idx, sizeof(int32_t) * step_index_count(a), st));
+    RC(stage_indices(a->host_index, idx, sizeof(int32_t) * step_index_count(c), st));
     echr_dec_args d = step_dec_args(a, L, idx);
     // the event encoder's position branch reads indices and parameters only: it starts here too, not with the second half behind the proposal
     // encoder's forward, where its ~70 us chain would sit in front of the forward recurrence
@@ -230,53 +312,32 @@ extern "C" int echr_train_step_prepare(const echr_train_step_args* a, void* stre
     return rc;
 }
 
-static int train_step_impl(const echr_train_step_args* a, void* stream, bool rw, const float* rw_dev, const echr_clip_step_args* x = nullptr,
-                           const echr_batch_ext* bx = nullptr, float* video_loss = nullptr, const int32_t* row_offset = nullptr);
-extern "C" int echr_train_step(const echr_train_step_args* a, void* stream) { return train_step_impl(a, stream, false, nullptr); }
+static int train_step_impl(const StepCall& c, void* stream);          // validate_step, then the iteration
+extern "C" int64_t echr_train_step_ws_floats(const echr_train_step_args* a) { return a ? carve_step(plain_call(a)).total : -1; }
+extern "C" int echr_train_step(const echr_train_step_args* a, void* stream) { return train_step_impl(plain_call(a), stream); }
 // Frame-level context 'CH' / 'CC+CH' (include/echr_hip.h): the same iteration with tap_feats (or [c3d | tap]) as the attended rows and the
 // clip-row gradient added to g_tap behind the join of the backward's helper streams
 extern "C" int64_t echr_train_step_clip_ws_floats(const echr_train_step_args* a, const echr_clip_step_args* x) {
-    return (a && x) ? carve_step(a, x->rw != 0, x).total : -1;
+    return (a && x) ? carve_step(clip_call(a, x)).total : -1;
 }
-extern "C" int echr_train_step_clip(const echr_train_step_args* a, const echr_clip_step_args* x, void* stream) {
-    ECHR_REQUIRE(a && x && (x->clip_parts == 2 || x->clip_parts == 3), "train_step_clip: clip_parts must be 2 ('CH') or 3 ('CC+CH')");
-    ECHR_REQUIRE(x->c3d && x->Dc > 0 && a->tap && a->Ht > 0, "train_step_clip: c3d / tap missing");
-    ECHR_REQUIRE(a->dec.D == (x->clip_parts == 3 ? x->Dc + a->Ht : a->Ht), "train_step_clip: dec.D = %d is not the width of the clip rows", a->dec.D);
-    ECHR_REQUIRE(!a->prepared, "train_step_clip: the clip rows are tap_feats: echr_train_step_prepare cannot run ahead of them (prepared must be 0)");
-    ECHR_REQUIRE(!(a->w_init && a->init_use_c), "train_step_clip: an initial state that reads the clip has no row gradient");
-    if (x->rw) {
-        ECHR_REQUIRE(a->host_nll || x->weight, "train_step_clip: the criterion weights are missing (device `weight`, or host_index with host_nll = 1)");
-        ECHR_REQUIRE(!(a->host_nll && x->weight), "train_step_clip: host_nll = 1 carries the weights in host_index: pass weight = NULL");
-    }
-    return train_step_impl(a, stream, x->rw != 0, (x->rw && !a->host_nll) ? x->weight : nullptr, x);
-}
-extern "C" int64_t echr_train_step_rw_ws_floats(const echr_train_step_args* a) { return a ? carve_step(a, true).total : -1; }
+extern "C" int echr_train_step_clip(const echr_train_step_args* a, const echr_clip_step_args* x, void* stream) { return train_step_impl(clip_call(a, x), stream); }
 // Self-critical training (RewardCriterion, misc/utils.py:48-59): the same iteration with the criterion's numerator weighted by the signed
 // rw[n,t] = reward * mask.  Stage-ahead needs no extra guard here: the decodes a caller runs between two calls (the sampled and the greedy pass,
 // the event context they read) use workspaces of their own and never this call's `ws`, index ring or gradient arena, and they are queued on
 // the caller's stream behind the update they read the parameters of; the next call's staging is the only work that runs beside that update,
 // and everything else of it is ordered behind the caller's stream's position at its entry, i.e. behind those decodes.
-extern "C" int echr_train_step_rw(const echr_train_step_args* a, const float* weight, void* stream) {
-    ECHR_REQUIRE(a && (a->host_nll || weight), "train_step_rw: the criterion weights are missing (device `weight`, or host_index with host_nll = 1)");
-    ECHR_REQUIRE(!(a->host_nll && weight), "train_step_rw: host_nll = 1 carries the weights in host_index: pass weight = NULL");
-    ECHR_REQUIRE(!a->prepared, "train_step_rw: echr_train_step_prepare does not take the weights (prepared must be 0)");
-    return train_step_impl(a, stream, true, a->host_nll ? nullptr : weight);
-}
+extern "C" int64_t echr_train_step_rw_ws_floats(const echr_train_step_args* a) { return a ? carve_step(rw_call(a)).total : -1; }
+extern "C" int echr_train_step_rw(const echr_train_step_args* a, const float* weight, void* stream) { return train_step_impl(rw_call(a, weight), stream); }
 // Multi-video batch (include/echr_hip.h): the same iteration over the events of V videos.  What differs sits in the pieces the call sequences --
 // per-video scene vectors and their segmented gradients (decoder.hip), the block-diagonal event encoder (tsrm.hip), the criterion's
 // per-video normalisers inside the weights (core.hip) -- which read the extension published here; this file stages vid with
 // the other index vectors and adds the per-video losses.  Stage-ahead, the applied-update count and the asynchronous failure reports are
 // those of echr_train_step: the same code runs.
 extern "C" int64_t echr_train_step_batch_ws_floats(const echr_train_step_args* a, const echr_batch_ext* x) {
-    return (a && x && x->n_videos > 0) ? carve_step(a, true, nullptr, x).total : -1;
+    return (a && x && x->n_videos > 0) ? carve_step(batch_call(a, x)).total : -1;
 }
 extern "C" int echr_train_step_batch(const echr_train_step_args* a, const echr_batch_ext* x, const float* weight, float* video_loss, void* stream) {
-    ECHR_REQUIRE(a && x && x->n_videos > 0 && x->n_videos <= a->dec.N && x->video, "train_step_batch: the batch extension needs 0 < n_videos <= N and video");
-    ECHR_REQUIRE(a->host_nll || weight, "train_step_batch: the criterion weights are missing (device `weight`, or host_index with host_nll = 1)");
-    ECHR_REQUIRE(!(a->host_nll && weight), "train_step_batch: host_nll = 1 carries the weights in host_index: pass weight = NULL");
-    ECHR_REQUIRE(!a->prepared && !a->defer_update && !a->g_tap, "train_step_batch: prepared, defer_update and g_tap are not part of the batched step");
-    ECHR_REQUIRE(!a->handover || !a->do_step, "train_step_batch: handover = 1 needs do_step = 0 (the caller reduces the gradients, then steps)");
-    return train_step_impl(a, stream, true, a->host_nll ? nullptr : weight, nullptr, x, video_loss);
+    return train_step_impl(batch_call(a, x, weight, video_loss), stream);
 }
 // The joint 'tap_cg' iteration over a batch: echr_train_step_batch that also returns d loss / d tap_feats.  a->g_tap [T_tot, Ht] is zero-filled
 // by the caller and added into: the anchors' rows through the block-diagonal event encoder's d ech (ind is batch-absolute; 'ER1' reads no
@@ -286,38 +347,23 @@ extern "C" int64_t echr_train_step_batch_tap_ws_floats(const echr_train_step_arg
 }
 extern "C" int echr_train_step_batch_tap(const echr_train_step_args* a, const echr_batch_ext* x, const float* weight, float* video_loss,
                                          const int32_t* row_offset, void* stream) {
-    ECHR_REQUIRE(a && x && x->n_videos > 0 && x->n_videos <= a->dec.N && x->video, "train_step_batch_tap: the batch extension needs 0 < n_videos <= N and video");
-    ECHR_REQUIRE(a->host_nll || weight, "train_step_batch_tap: the criterion weights are missing (device `weight`, or host_index with host_nll = 1)");
-    ECHR_REQUIRE(!(a->host_nll && weight), "train_step_batch_tap: host_nll = 1 carries the weights in host_index: pass weight = NULL");
-    ECHR_REQUIRE(a->g_tap && a->tap && a->Ht > 0 && !a->forward_only, "train_step_batch_tap: g_tap / tap missing (without g_tap this is echr_train_step_batch)");
-    ECHR_REQUIRE(a->vh_offset < 0 || row_offset, "train_step_batch_tap: the 'VH' scene gradient needs row_offset");
-    ECHR_REQUIRE(!a->prepared && !a->defer_update && !a->mid_cb, "train_step_batch_tap: prepared, defer_update and mid_cb are not part of the batched step");
-    ECHR_REQUIRE(!a->handover || !a->do_step, "train_step_batch_tap: handover = 1 needs do_step = 0 (the caller reduces the gradients, then steps)");
-    return train_step_impl(a, stream, true, a->host_nll ? nullptr : weight, nullptr, x, video_loss, row_offset);
+    return train_step_impl(batch_tap_call(a, x, weight, video_loss, row_offset), stream);
 }
 // The frame-level contexts over a batch: echr_train_step_batch (and, with g_tap, echr_train_step_batch_tap) with the row source of
 // echr_train_step_clip over the T_tot concatenated rows.  ev_start is batch-absolute, so the attention, its backward and the clip-row gradient
 // address the rows as they do for one video; g_tap gains the anchors' rows, the 'VH' span over each video's own rows and the clip-row gradient.
 extern "C" int64_t echr_train_step_batch_clip_ws_floats(const echr_train_step_args* a, const echr_clip_step_args* x, const echr_batch_ext* bx) {
-    return (a && x && bx && bx->n_videos > 0 && (x->clip_parts == 2 || x->clip_parts == 3)) ? carve_step(a, true, x, bx).total : -1;
+    const bool ok = a && x && bx && bx->n_videos > 0 && (x->clip_parts == 2 || x->clip_parts == 3);
+    return ok ? carve_step(batch_clip_call(a, x, bx)).total : -1;
 }
 extern "C" int echr_train_step_batch_clip(const echr_train_step_args* a, const echr_clip_step_args* x, const echr_batch_ext* bx, const float* weight,
                                           float* video_loss, const int32_t* row_offset, void* stream) {
-    ECHR_REQUIRE(a && x && (x->clip_parts == 2 || x->clip_parts == 3), "train_step_batch_clip: clip_parts must be 2 ('CH') or 3 ('CC+CH')");
-    ECHR_REQUIRE(bx && bx->n_videos > 0 && bx->n_videos <= a->dec.N && bx->video, "train_step_batch_clip: the batch extension needs 0 < n_videos <= N and video");
-    ECHR_REQUIRE(x->c3d && x->Dc > 0 && a->tap && a->Ht > 0, "train_step_batch_clip: c3d / tap missing");
-    ECHR_REQUIRE(a->dec.D == (x->clip_parts == 3 ? x->Dc + a->Ht : a->Ht), "train_step_batch_clip: dec.D = %d is not the width of the clip rows", a->dec.D);
-    ECHR_REQUIRE(a->host_nll || weight, "train_step_batch_clip: the criterion weights are missing (device `weight`, or host_index with host_nll = 1)");
-    ECHR_REQUIRE(!(a->host_nll && weight), "train_step_batch_clip: host_nll = 1 carries the weights in host_index: pass weight = NULL");
-    ECHR_REQUIRE(!a->prepared && !a->defer_update && !a->mid_cb, "train_step_batch_clip: prepared, defer_update and mid_cb are not part of the batched step");
-    ECHR_REQUIRE(!a->handover || !a->do_step, "train_step_batch_clip: handover = 1 needs do_step = 0 (the caller reduces the gradients, then steps)");
-    ECHR_REQUIRE(!(a->w_init && a->init_use_c), "train_step_batch_clip: an initial state that reads the clip has no row gradient");
-    ECHR_REQUIRE(!a->g_tap || !a->forward_only, "train_step_batch_clip: g_tap needs the backward pass (forward_only must be 0)");
-    ECHR_REQUIRE(!a->g_tap || a->vh_offset < 0 || row_offset, "train_step_batch_clip: the 'VH' scene gradient needs row_offset");
-    return train_step_impl(a, stream, true, a->host_nll ? nullptr : weight, x, bx, video_loss, row_offset);
+    return train_step_impl(batch_clip_call(a, x, bx, weight, video_loss, row_offset), stream);
 }
-static int train_step_impl(const echr_train_step_args* a, void* stream, bool rw, const float* rw_dev, const echr_clip_step_args* x, const echr_batch_ext* bx,
-                           float* video_loss, const int32_t* row_offset) {
+static int train_step_impl(const StepCall& c, void* stream) {
+    RC(validate_step(c));
+    const echr_train_step_args* a = c.a; const echr_clip_step_args* x = c.x; const echr_batch_ext* bx = c.bx; const bool rw = c.rw;
+    float* video_loss = c.video_loss; const int32_t* row_offset = c.row_offset;
     ECHR_REQUIRE(a && a->ws && a->host_index && a->loss && a->g_loss && a->flat_g && (a->tap || a->event_parts == 1), "train_step: missing buffers");
     ECHR_REQUIRE(!a->prepared || a->overlap_encoder, "train_step: prepared = 1 needs overlap_encoder = 1");
     const int parts = a->event_parts ? a->event_parts : 3;
@@ -332,16 +378,16 @@ static int train_step_impl(const echr_train_step_args* a, void* stream, bool rw,
     ECHR_REQUIRE(!a->do_step || (a->flat_p && a->adam_m && a->adam_v && a->adam_step >= 1), "train_step: optimiser state missing");
     hipStream_t st = (hipStream_t)stream;
     RC(join_tail(st));          // (a deferred update of the previous call: it reads the index region this call is about to restage)
-    const StepWs L = carve_step(a, rw, x, bx);
+    const StepWs L = carve_step(c);
     ECHR_REQUIRE(a->ws_floats >= L.total, "train_step: workspace holds %lld floats, %ld needed (echr_train_step%s_ws_floats)", (long long)a->ws_floats, L.total,
-                 bx ? (x ? "_batch_clip" : "_batch") : (x ? "_clip" : (rw ? "_rw" : "")));
+                 c.bx && !c.x ? "_batch" : c.name);
     float* ws = a->ws;
     // 'CC+CH': the row source [c3d | tap] is formed first, ahead of every fork of this call (the decoder's event-independent part reads it)
     if (x && x->clip_parts == 3) RC(clip_rows(c3d, Dc, a->tap, a->Ht, ws + L.rows, a->dec.Tv, st));
     const int N = a->dec.N, S = a->dec.S;
     step_mark(0, st);
     int32_t* idx = reinterpret_cast<int32_t*>(ws + L.idx);
-    ECHR_REQUIRE(a->n_active >= 0 && a->n_active <= S * N, "train_step: n_active out of range");
+    RC(check_n_active(a));
     StageAhead& sa = stage_ahead();
     const bool ahead = sa.ok && sa.valid && !a->prepared && a->overlap_encoder && sa.st == st && sa.ws == a->ws && sa.flat_g == a->flat_g &&
                        helpers_available() && tail_stream_raw();
@@ -349,7 +395,7 @@ static int train_step_impl(const echr_train_step_args* a, void* stream, bool rw,
     if (ahead) {
         hipStream_t ts = tail_stream_raw();
         if (hipStreamWaitEvent(ts, sa.pre, 0) != hipSuccess) { set_error("train_step: stream wait failed"); return -5; }
-        RC(stage_indices(a->host_index, idx, sizeof(int32_t) * step_index_count(a, rw, bx), ts));
+        RC(stage_indices(a->host_index, idx, sizeof(int32_t) * step_index_count(c), ts));
         // the caller's stream: behind the staging copy (its own position is already behind the update).  The prepare stream: behind the
         // caller's stream's position AT ENTRY -- the update, and whatever the caller queued since (this call's inputs: an upload of the next
         // video's features, the proposal encoder's forward; a write to the parameters) -- since the staging event it forks from no longer
@@ -357,13 +403,13 @@ static int train_step_impl(const echr_train_step_args* a, void* stream, bool rw,
         if (hipEventRecord(sa.post, st) != hipSuccess) { set_error("train_step: event record failed"); return -5; }
         RC(prep_stream_wait(sa.post));
         if (hipStreamWaitEvent(st, ring_last(), 0) != hipSuccess) { set_error("train_step: stream wait failed"); return -5; }
-    } else if (!a->prepared) RC(stage_indices(a->host_index, idx, sizeof(int32_t) * step_index_count(a, rw, bx), st));
+    } else if (!a->prepared) RC(stage_indices(a->host_index, idx, sizeof(int32_t) * step_index_count(c), st));
     // multi-video batch: vid is the tail of the staged index region, the batch scratch a piece of `ws`; everything below reads the extension
     // through batch_ext()
     echr_batch_ext bxl;
     if (bx) {
         bxl = *bx;
-        bxl.vid = idx + step_index_count(a, rw, nullptr);
+        bxl.vid = idx + step_vid_offset(c);
         bxl.ws = ws + L.batch;
         if (vh) bxl.g_video = ws + L.g_video;          // [V, Dv]: the batched decoder backward writes d video per video (its spans go into g_tap)
     }
@@ -372,7 +418,7 @@ static int train_step_impl(const echr_train_step_args* a, void* stream, bool rw,
     const void* nll_target = a->nll_target;
     const float* nll_mask = a->nll_mask;
     int nll_i64 = a->nll_target_i64;
-    const float* crit_w = rw_dev;
+    const float* crit_w = c.rw_dev;
     if (a->host_nll) {          // targets / mask (/ weights) came with the index vectors
         nll_target = active + a->n_active;
         nll_mask = reinterpret_cast<const float*>(active + a->n_active + (size_t)S * N);

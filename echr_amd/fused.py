@@ -24,6 +24,16 @@ from .optim import ClampAdam
 
 class FusedTrainStep(object):
     LOSS_SLOTS = 16
+    # The library entries of the one-call step (csrc/step.hip).  ENTRIES: which argument structs lead an entry's argument list -- they are
+    # ALL the arguments of its *_ws_floats -- and how many of (weight, video_loss, row_offset) follow them in front of the stream.
+    ENTRIES = {'train_step': ('a', 0), 'train_step_rw': ('a', 1), 'train_step_clip': ('ax', 0),
+               'train_step_batch': ('ab', 2), 'train_step_batch_tap': ('ab', 3), 'train_step_batch_clip': ('axb', 3)}
+    # ROUTES: which entry runs a call, keyed by (a VideoBatch?, 'CH' / 'CC+CH' rows?, tap_grad?, weighted criterion?).  _setup sizes the
+    # workspace and _launch calls the entry through this ONE table (per object: _routes).  (echr_train_step_clip reads `weighted` from
+    # x.rw; a batch always brings weights; echr_train_step_batch_clip runs with tap_grad or without.)
+    ROUTES = {(b, c, g, w): ('train_step_batch_clip' if c else 'train_step_batch_tap' if g else 'train_step_batch') if b else
+                            ('train_step_clip' if c else 'train_step_rw' if w else 'train_step')
+              for b in (False, True) for c in (False, True) for g in (False, True) for w in (False, True)}
 
     def __init__(self, model, optimizer, grad_clip=None):
         if not isinstance(optimizer, ClampAdam) or optimizer.arena is None:
@@ -49,6 +59,17 @@ class FusedTrainStep(object):
         self.clip = model.clip_parts()
         self._dc = model.opt.video_dim
         self.x = L.ClipStepArgs(self.clip, self._dc, None, 0, None)
+        self.bx = L.BatchExt(0, None, None, None, None)          # the multi-video extension: _setup(batch=) fills n_videos and video
+        ra, rx, rb = C.byref(self.a), C.byref(self.x), C.byref(self.bx)
+        refs = dict(a=(ra,), ax=(ra, rx), ab=(ra, rb), axb=(ra, rx, rb))
+        self._routes = {k: (e, refs[self.ENTRIES[e][0]], self.ENTRIES[e][1]) for k, e in self.ROUTES.items()}          # key -> (entry, structs, n)
+        self._batched = self._prepared = self._pending_deferred = self.mid_called = False
+        self._unused = self.last_video_losses = None
+        # ONE ctypes trampoline per callback and object (building a CFUNCTYPE per call is host time inside the timed multi-rank loop); each
+        # forwards to the callback of the current call.  An exception inside a ctypes callback cannot propagate: kept, re-raised behind the call
+        self._cb_error = self._cb_cur = self._mid_cur = None
+        self._cb_keep, self._mid_keep = L.HANDOVER_FN(self._on_handover), L.MID_FN(self._on_mid)
+        self._cb_ptr, self._mid_ptr = C.cast(self._cb_keep, C.c_void_p), C.cast(self._mid_keep, C.c_void_p)
         self.ws = None
         self.one = torch.ones(1, device=self.dev, dtype=torch.float32)
         self.loss_ring = torch.zeros(self.LOSS_SLOTS, 2, device=self.dev, dtype=torch.float32)
@@ -58,6 +79,58 @@ class FusedTrainStep(object):
     def join(self):
         """Make the current stream wait for a deferred update (defer_update=True); no-op otherwise."""
         L.check(self.lib.echr_stream_join(L.stream_ptr()), 'stream_join')
+
+    def _join_deferred(self):
+        if self._pending_deferred:
+            # a deferred update may still be reading the previous call's inputs (c3d, the staged indices) on the library's streams: order this
+            # stream behind it BEFORE the references to them are dropped and torch's allocator may hand that memory to someone else
+            self.join()
+            self._pending_deferred = False
+
+    def _begin(self, what, prepare=None):
+        """The head of every step that runs on this object.  `prepare`: what a pending prepare() means to the caller -- None: its second
+        half has to come first; a name: a batch form, with which prepare() does not combine; True: nothing (the caller is that second half,
+        or runs no library step)."""
+        if self._prepared and prepare is not True:
+            if prepare is None:
+                raise RuntimeError('prepare() must be followed by a call with prepared=True')
+            raise NotImplementedError('prepare() runs ahead of ONE video\'s call: it does not combine with %s' % prepare)
+        # a persistent launch of an EARLIER iteration gave up: the optimiser kernels queued behind it skipped their updates (parameters and
+        # moments untouched) while the step was already counted -- L.check lets every optimiser wind its count back to the updates its own
+        # device word says were applied (ClampAdam._on_async_abort), here and at every other site that can surface the -62
+        rc = self.lib.echr_check_async()
+        if rc:
+            L.check(rc, what + ' (asynchronous failure of an earlier call)')
+        self._join_deferred()
+
+    def _launch(self, slot, st, forward_only, *, rw=False, weight=None, video_loss=None, row_offset=None, handover=False, handover_cb=None,
+                mid_cb=None, g_loss=None, prepared=False, keep=()):
+        """The ONE place that calls a train-step entry, on what _setup (or prepare() + _set_tap) described.  `rw`: the criterion is weighted
+        (`weight`: the weights as a device tensor when they did not travel with the index vectors); `video_loss` [V] out and `row_offset`
+        int32 [V+1]: device tensors of the batch entries; `g_loss`: a one-element device tensor in place of the unit scalar, for this call
+        only; `keep`: what else must stay alive until the next _setup.  Returns the loss (_finish)."""
+        a = self.a
+        a.prepared, a.handover = 1 if prepared else 0, 1 if handover else 0
+        # (echr_train_step_args.handover_cb / mid_cb; handover_user / mid_user stay NULL)
+        self._cb_error, self._cb_cur, self._mid_cur, self.mid_called = None, handover_cb, mid_cb, False
+        a.handover_cb = self._cb_ptr if (handover and handover_cb is not None) else None
+        a.mid_cb = self._mid_ptr if mid_cb is not None else None
+        # (set BEFORE the call: if it fails half-way, helper-stream work may already be queued, and the next _setup must join it before it
+        # drops the references to this call's inputs)
+        self._pending_deferred = bool(a.defer_update)
+        self._keep = self._keep + (weight, row_offset, g_loss) + tuple(keep)
+        entry, refs, n = self._routes[self._batched, self.clip != 1, bool(a.g_tap), rw]
+        if g_loss is not None:
+            a.g_loss = L.ptr(g_loss)
+        try:
+            extra = (L.ptr(weight), L.ptr(video_loss), L.ptr(row_offset, torch.int32))[:n] if n else ()
+            L.check(getattr(self.lib, 'echr_' + entry)(*refs, *extra, L.stream_ptr()), entry)
+        finally:
+            a.g_loss = self.one.data_ptr()
+        if self._cb_error is not None:
+            e, self._cb_error = self._cb_error, None
+            raise e
+        return self._finish(slot, st, forward_only)
 
     # ---- pointers that never change: parameters and their gradient slots ------------------------------------------------------
     def _fill_static(self):
@@ -132,12 +205,12 @@ class FusedTrainStep(object):
     def cancel_prepare(self):
         """Abandon a prepare() whose second half will not follow (the caller's code between the two raised): the prepare stream's work is
         ordered before the workspace can be reused and the object accepts ordinary calls again."""
-        if getattr(self, '_prepared', False):
+        if self._prepared:
             self._prepared = False
             L.check(self.lib.echr_decoder_fwd_prepare_cancel(L.stream_ptr()), 'decoder_fwd_prepare_cancel')
 
     def __call__(self, tap_feats, c3d_feats, lda_feats, lm_labels, ind_select_list, soi_select_list, targets, masks, step=True, forward_only=False,
-                 tap_grad=None, defer_update=False, prepared=False, handover=False, handover_cb=None, mid_cb=None):
+                 tap_grad=None, defer_update=False, prepared=False, handover=False, handover_cb=None, mid_cb=None, g_loss=None):
         """One iteration; returns the loss as a 0-d device tensor (no host sync).  `targets` / `masks`: what the reference hands its
         criterion (labels[:, 1:], masks[:, 1:]), host or device tensors.  step=False stops after the backward pass and exposes the
         gradients as `.grad` views of the arena (data-parallel reduce, inspection); the caller then steps the optimiser itself.
@@ -151,80 +224,33 @@ class FusedTrainStep(object):
         `handover_cb(which, stream_ptr)`: called on the host from inside the call at each point (echr_train_step_args.handover_cb).
         `mid_cb()` (joint form): called on the host from inside the call right behind the work that leads to tap_grad, before the
         parameter-gradient tail is forked (echr_train_step_args.mid_cb; JointTrainStep queues the proposal encoder's backward there);
-        `self.mid_called` says whether the library took that form."""
-        a, lib = self.a, self.lib
-        # a persistent launch of an EARLIER iteration gave up: the optimiser kernels queued behind it skipped their updates (parameters and
-        # moments untouched) while the step was already counted -- L.check lets every optimiser wind its count back to the updates its own
-        # device word says were applied (ClampAdam._on_async_abort), here and at every other site that can surface the -62
-        L.check(lib.echr_check_async(), 'train_step (asynchronous failure of an earlier call)')
+        `self.mid_called` says whether the library took that form.  `g_loss`: a one-element device tensor that scales every gradient of
+        this call (JointTrainStep's lambda2); the returned loss stays unscaled."""
+        self._begin('train_step', True if prepared else None)
         if prepared:
-            if not getattr(self, '_prepared', False) or not step or forward_only:
+            if not self._prepared or not step or forward_only:
                 raise RuntimeError('prepared=True needs a preceding prepare() and a full training step')
             self._prepared = False
             self._set_tap(EF._f32c(tap_feats), tap_grad, defer_update, True, False)
-            a.prepared = 1
             slot, st = self._slot, self._state
         else:
-            if getattr(self, '_prepared', False):
-                raise RuntimeError('prepare() must be followed by a call with prepared=True')
             slot, st = self._setup(tap_feats, c3d_feats, lda_feats, lm_labels, ind_select_list, soi_select_list, targets, masks, step, forward_only,
                                    tap_grad, defer_update)
-            a.prepared = 0
-        self._set_handover(handover and not step and not forward_only, handover_cb)
-        self.mid_called = False
-        if mid_cb is not None:
-            self._mid_cur = mid_cb
-            if getattr(self, '_mid_keep', None) is None:
-                def _mid(_stream, _user):
-                    self.mid_called = True
-                    try:
-                        self._mid_cur()
-                    except BaseException as e:          # noqa: BLE001  (cannot propagate through ctypes: re-raised behind the call)
-                        self._cb_error = e
-                self._mid_keep = L.MID_FN(_mid)
-                self._mid_ptr = C.cast(self._mid_keep, C.c_void_p)
-            self._cb_error = None
-            a.mid_cb = self._mid_ptr
-        else:
-            a.mid_cb = None
-        a.mid_user = None
-        # (set BEFORE the call: if it fails half-way, helper-stream work may already be queued, and the next _setup must join it before it
-        # drops the references to this call's inputs)
-        self._pending_deferred = bool(a.defer_update)
-        if self.clip != 1:
-            self.x.rw, self.x.weight = 0, None
-            L.check(lib.echr_train_step_clip(C.byref(a), C.byref(self.x), L.stream_ptr()), 'train_step_clip')
-        else:
-            L.check(lib.echr_train_step(C.byref(a), L.stream_ptr()), 'train_step')
-        self._raise_cb_error()
-        return self._finish(slot, st, forward_only)
+        return self._launch(slot, st, forward_only, handover=handover and not step and not forward_only, handover_cb=handover_cb, mid_cb=mid_cb,
+                            g_loss=g_loss, prepared=prepared)
 
-    def _set_handover(self, on, handover_cb):
-        """The hand-over fields of the argument struct for the call about to be made (echr_train_step_args.handover / handover_cb)."""
-        a = self.a
-        a.handover = 1 if on else 0
-        if a.handover and handover_cb is not None:
-            # ONE ctypes trampoline per object (building a CFUNCTYPE per call is host time inside the timed multi-rank loop); it forwards to
-            # the callback of the current call.  An exception inside a ctypes callback cannot propagate: kept and re-raised behind the call
-            self._cb_error, self._cb_cur = None, handover_cb
-            if getattr(self, '_cb_keep', None) is None:
-                def _tramp(which, stream, _user):
-                    try:
-                        self._cb_cur(int(which), int(stream))
-                    except BaseException as e:          # noqa: BLE001
-                        self._cb_error = e
-                self._cb_keep = L.HANDOVER_FN(_tramp)
-                self._cb_ptr = C.cast(self._cb_keep, C.c_void_p)
-            a.handover_cb = self._cb_ptr
-        else:
-            a.handover_cb = None
-        a.handover_user = None
+    def _on_handover(self, which, stream, _user):
+        try:
+            self._cb_cur(int(which), int(stream))
+        except BaseException as e:          # noqa: BLE001
+            self._cb_error = e
 
-    def _raise_cb_error(self):
-        a = self.a
-        if (a.handover_cb or a.mid_cb) and getattr(self, '_cb_error', None) is not None:
-            e, self._cb_error = self._cb_error, None
-            raise e
+    def _on_mid(self, _stream, _user):
+        self.mid_called = True
+        try:
+            self._mid_cur()
+        except BaseException as e:          # noqa: BLE001
+            self._cb_error = e
 
     def batch(self, batch, step=True, forward_only=False, device_criterion=False, video_losses=True, **unsupported):
         """One iteration over a multi-video batch (echr_amd.batch.VideoBatch) as ONE call (echr_train_step_batch): the reference's
@@ -250,14 +276,11 @@ class FusedTrainStep(object):
         return self._batch_call(batch, False, False, device_criterion, video_losses, True, handover_cb)
 
     def _batch_call(self, batch, step, forward_only, device_criterion, video_losses, handover=False, handover_cb=None):
-        if getattr(self, '_prepared', False):
-            raise NotImplementedError('prepare() runs ahead of ONE video\'s call: it does not combine with batch()')
         m = self.model
         m._check_batch_options(batch)
+        self._begin('train_step_batch', 'batch()')
         if batch.labels is None:
             raise ValueError('the batch carries no labels')
-        a, lib = self.a, self.lib
-        L.check(lib.echr_check_async(), 'train_step_batch (asynchronous failure of an earlier call)')
         with torch.no_grad():
             video = EF._f32c(m.get_video_context_batch(batch))
         w = batch.criterion_weights()
@@ -268,54 +291,22 @@ class FusedTrainStep(object):
             w_dev = torch.from_numpy(w).to(self.dev)
         slot, st = self._setup(batch.tap, batch.c3d, video, batch.labels, batch.ind, batch.soi, tg, mk, step, forward_only, None, False,
                                weights=w, batch=batch)
-        a.prepared = 0
-        a.mid_cb = a.mid_user = None
-        self._set_handover(handover and not step and not forward_only, handover_cb)
-        self._pending_deferred = False
         self.last_video_losses = torch.empty(batch.n_videos, device=self.dev, dtype=torch.float32) if video_losses else None
-        self._keep = self._keep + (w_dev, video)
-        self._call_batch(L.ptr(w_dev) if w_dev is not None else None, L.ptr(self.last_video_losses) if video_losses else None)
-        self._raise_cb_error()
-        return self._finish(slot, st, forward_only)
-
-    def _call_batch(self, weight, video_loss):
-        """echr_train_step_batch on what _setup(batch=) described, or with 'CH' / 'CC+CH' echr_train_step_batch_clip (no g_tap, no row offsets)."""
-        a, lib = self.a, self.lib
-        if self.clip != 1:
-            L.check(lib.echr_train_step_batch_clip(C.byref(a), C.byref(self.x), C.byref(self.bx), weight, video_loss, None, L.stream_ptr()),
-                    'train_step_batch_clip')
-        else:
-            L.check(lib.echr_train_step_batch(C.byref(a), C.byref(self.bx), weight, video_loss, L.stream_ptr()), 'train_step_batch')
+        return self._launch(slot, st, forward_only, rw=True, weight=w_dev, video_loss=self.last_video_losses,
+                            handover=handover and not step and not forward_only, handover_cb=handover_cb, keep=(video,))
 
     def _batch_tap(self, batch, tap_grad, ro_dev, video_losses, g_loss=None, step=True, handover=False, handover_cb=None):
         """The caption side of the joint iteration over a batch (echr_train_step_batch_tap; fused.JointBatchStep): batch() with the zero-filled
         `tap_grad` [T_tot, Ht] receiving d loss / d batch.tap.  `ro_dev`: the batch's row offsets as an int32 device vector [V+1];
         `video_losses`: device [V] out; `g_loss`: a one-element device tensor that scales every gradient (lambda2; None = 1) -- the returned
         loss and the per-video losses stay unscaled.  `handover` / `handover_cb` (with step=False): as batch_handover."""
-        a, m = self.a, self.model
         with torch.no_grad():
-            video = EF._f32c(m.get_video_context_batch(batch))
+            video = EF._f32c(self.model.get_video_context_batch(batch))
         slot, st = self._setup(batch.tap, batch.c3d, video, batch.labels, batch.ind, batch.soi, batch.targets, batch.crit_masks, step, False,
                                tap_grad, False, weights=batch.criterion_weights(), batch=batch)
-        a.prepared = 0
-        a.mid_cb = a.mid_user = None
-        self._set_handover(handover and not step, handover_cb)
-        self._pending_deferred = False
-        self._keep = self._keep + (video, g_loss, ro_dev)
         self.last_video_losses = video_losses
-        if g_loss is not None:
-            a.g_loss = L.ptr(g_loss)
-        try:
-            if self.clip != 1:          # the clip-row gradient joins the anchors' rows and the 'VH' span in tap_grad
-                L.check(self.lib.echr_train_step_batch_clip(C.byref(a), C.byref(self.x), C.byref(self.bx), None, L.ptr(video_losses),
-                                                            L.ptr(ro_dev, torch.int32), L.stream_ptr()), 'train_step_batch_clip')
-            else:
-                L.check(self.lib.echr_train_step_batch_tap(C.byref(a), C.byref(self.bx), None, L.ptr(video_losses), L.ptr(ro_dev, torch.int32),
-                                                           L.stream_ptr()), 'train_step_batch_tap')
-        finally:
-            a.g_loss = self.one.data_ptr()
-        self._raise_cb_error()
-        return self._finish(slot, st, False)
+        return self._launch(slot, st, False, rw=True, video_loss=video_losses, row_offset=ro_dev, handover=handover and not step,
+                            handover_cb=handover_cb, g_loss=g_loss, keep=(video,))
 
     def _set_tap(self, tap, tap_grad, defer_update, step, forward_only):
         a, d = self.a, self.a.dec
@@ -346,11 +337,7 @@ class FusedTrainStep(object):
         are then its concatenated features / batch-absolute indices, `lda_feats` is the scene matrix [V, Dv]; with device targets the
         host `weights` do not travel with the index vectors -- FusedTrainStep.batch hands their device copy to echr_train_step_batch itself)"""
         a, m, ar, lib = self.a, self.model, self.arena, self.lib
-        if getattr(self, '_pending_deferred', False):
-            # a deferred update may still be reading the previous call's inputs (c3d, the staged indices) on the library's streams: order this
-            # stream behind it BEFORE the references below are dropped and torch's allocator may hand that memory to someone else
-            self.join()
-            self._pending_deferred = False
+        self._join_deferred()
         if not c3d_feats.is_cuda:
             raise L.EchrHipError('FusedTrainStep runs on the GPU only')
         if (ar.flat_p.data_ptr(), ar.flat_g.data_ptr()) != self._epoch_ptrs or not ar.params_in_arena():
@@ -460,18 +447,13 @@ class FusedTrainStep(object):
             drop = m.lm_model.next_drop_state(m.fusion_model.enc_attn.dropout.p)
             drop.training = m.training
         a.drop = drop.c()
+        self._batched = batch is not None
         if batch is not None:
-            self.bx = L.BatchExt(batch.n_videos, None, lda.data_ptr(), None, None)
-            if self.clip != 1:
-                self.x.rw, self.x.weight = 0, None          # (not read by the batched entry: the weights travel as echr_train_step_batch's)
-                need = lib.echr_train_step_batch_clip_ws_floats(C.byref(a), C.byref(self.x), C.byref(self.bx))
-            else:
-                need = lib.echr_train_step_batch_ws_floats(C.byref(a), C.byref(self.bx))
-        elif self.clip != 1:
-            self.x.rw = 0 if weights is None else 1
-            need = lib.echr_train_step_clip_ws_floats(C.byref(a), C.byref(self.x))
-        else:
-            need = (lib.echr_train_step_ws_floats if weights is None else lib.echr_train_step_rw_ws_floats)(C.byref(a))
+            self.bx.n_videos, self.bx.video = batch.n_videos, lda.data_ptr()
+        # ('CH' / 'CC+CH': x.rw says whether ONE video's criterion is weighted; a batch's weights travel as the batched entry's own)
+        self.x.rw = 1 if (weights is not None and batch is None) else 0
+        entry, refs, _ = self._routes[self._batched, self.clip != 1, bool(a.g_tap), weights is not None]
+        need = getattr(lib, 'echr_%s_ws_floats' % entry)(*refs)
         if self.ws is None or self.ws.numel() < need:
             self.join()                        # (a deferred update may still be reading the old workspace on the helper streams)
             self.ws = None                     # (released in stream order by the caching allocator)
@@ -514,7 +496,7 @@ class FusedTrainStep(object):
         elif not forward_only:
             # gradients are final in stream order: expose them the way the autograd path does (views of the arena); never-used
             # parameters keep .grad None (their slots are zero)
-            unused = getattr(self, '_unused', None)
+            unused = self._unused
             if unused is None:
                 unused = self._unused = {id(p) for p in list(m.lm_model.core.fusion_layer.parameters()) + list(m.fusion_model.h2a_layer.parameters())}
             for i, p in enumerate(ar.params):
@@ -554,10 +536,7 @@ class SelfCriticalStep(object):
         f = self.fused
         m = f.model
         lm = m.lm_model
-        L.check(f.lib.echr_check_async(), 'self_critical_step (asynchronous failure of an earlier call)')
-        if getattr(f, '_pending_deferred', False):
-            f.join()
-            f._pending_deferred = False
+        f._begin('self_critical_step')
         drop = lm.next_drop_state(m.fusion_model.enc_attn.dropout.p)
         drop.training = m.training
         with torch.no_grad():
@@ -601,20 +580,9 @@ class SelfCriticalStep(object):
         mask[:, 1:T] = g[:, :T - 1] > 0
         w = np.zeros((N, T + 1), dtype=np.float32)
         w[:, :T] = r * mask[:, :T]
-        a, lib = f.a, f.lib
-        if getattr(f, '_prepared', False):
-            raise RuntimeError('prepare() must be followed by a call with prepared=True')
         slot, st = f._setup(tap_feats, c3d_feats, lda_feats, labels, ind_select_list, soi_select_list, labels[:, 1:], mask, step, False, None,
                             False, drop=drop, weights=w)
-        a.prepared = a.handover = 0
-        a.handover_cb = a.handover_user = a.mid_cb = a.mid_user = None
-        f._pending_deferred = False
-        if f.clip != 1:
-            f.x.rw, f.x.weight = 1, None
-            L.check(lib.echr_train_step_clip(C.byref(a), C.byref(f.x), L.stream_ptr()), 'train_step_clip')
-        else:
-            L.check(lib.echr_train_step_rw(C.byref(a), None, L.stream_ptr()), 'train_step_rw')
-        return f._finish(slot, st, False), gen_h, greedy_h, torch.from_numpy(r)
+        return f._launch(slot, st, False, rw=True), gen_h, greedy_h, torch.from_numpy(r)
 
 
 class SelfCriticalBatchStep(object):
@@ -654,12 +622,8 @@ class SelfCriticalBatchStep(object):
         f = self.fused
         m = f.model
         lm = m.lm_model
-        if getattr(f, '_prepared', False):
-            raise NotImplementedError('prepare() runs ahead of ONE video\'s call: it does not combine with a batch step')
-        L.check(f.lib.echr_check_async(), 'self_critical_batch_step (asynchronous failure of an earlier call)')
-        if getattr(f, '_pending_deferred', False):
-            f.join()
-            f._pending_deferred = False
+        m._check_batch_options(batch)          # (ahead of everything that touches the device)
+        f._begin('self_critical_batch_step', 'a batch step')
         N, V = batch.n_events, batch.n_videos
         with torch.no_grad():
             video, event, ev_start, ev_len, A, vid, drop = m._batch_contexts(batch, None)
@@ -708,21 +672,60 @@ class SelfCriticalBatchStep(object):
         else:
             r = np.ascontiguousarray(batch._reward_matrix(reward, N, T))
         labels, mask, w = batch.reward_weights(gen_h, r, vw)
-        a, lib = f.a, f.lib
         slot, st = f._setup(batch.tap, batch.c3d, video, labels, batch.ind, batch.soi, labels[:, 1:], mask, step, False, None, False,
                             drop=drop, weights=w, batch=batch)
-        a.prepared = 0
-        a.mid_cb = a.mid_user = None
-        f._set_handover(handover and not step, handover_cb)
-        f._pending_deferred = False
         self.last_video_losses = f.last_video_losses = torch.empty(V, device=f.dev, dtype=torch.float32)
-        f._keep = f._keep + (video,)
-        f._call_batch(None, L.ptr(self.last_video_losses))
-        f._raise_cb_error()
-        return f._finish(slot, st, False), gen_h, greedy_h, torch.from_numpy(r), vw
+        loss = f._launch(slot, st, False, rw=True, video_loss=self.last_video_losses, handover=handover and not step, handover_cb=handover_cb,
+                         keep=(video,))
+        return loss, gen_h, greedy_h, torch.from_numpy(r), vw
 
 
-class JointTrainStep(object):
+class _JointStep(object):
+    """What JointTrainStep and JointBatchStep share: the constructor checks and the proposal encoder's bookkeeping around its own calls."""
+
+    def _init_joint(self, fused, tap_model, tap_optim, lambda1, lambda2, tap_grad_clip):
+        name = type(self).__name__
+        if not isinstance(fused, FusedTrainStep):
+            raise TypeError('%s wraps a FusedTrainStep' % name)
+        ar = getattr(tap_model, '_echr_arena', None)
+        if not isinstance(tap_optim, ClampAdam) or tap_optim.arena is None or tap_optim.arena is not ar or not ar.params_in_arena():
+            raise ValueError('%s needs the proposal encoder on a flat arena (tap_model.build_arena()) and a ClampAdam built with it' % name)
+        if len(tap_optim.param_groups) != 1 or {id(p) for p in tap_optim.param_groups[0]['params']} != {id(p) for p in ar.params}:
+            raise ValueError('the proposal encoder\'s optimiser must hold exactly its parameters in one group')
+        self.fused, self.tap_model, self.tap_optim, self.tap_arena = fused, tap_model, tap_optim, ar
+        self.lambda1, self.lambda2, self.tap_grad_clip = float(lambda1), float(lambda2), tap_grad_clip
+        self.lib, self.dev = fused.lib, fused.dev
+        self._buf_key, self._bufs = None, None
+
+    def _new_tap_backward(self):
+        """The proposal encoder's arena at the head of an iteration: no stale `.grad` view or deferred clamp survives into the new backward."""
+        ar = self.tap_arena
+        for p in ar.params:
+            p.grad = None
+        ar.deferred_clamp = None
+        ar.end_backward_pass()
+
+    def _tap_drop(self):
+        """(p, DropState) of the proposal encoder for this call: ONE counter per call, over a batch too (the mask is keyed by the batch-global
+        row, models.SST.forward_batch)."""
+        tm = self.tap_model
+        p_drop = float(tm.rnn.dropout)
+        if tm._drop_seed is None:
+            tm._drop_seed = (int(torch.initial_seed()) ^ 0x55AA) & 0xFFFFFFFFFFFFFFFF
+        drop = EF.DropState(tm._drop_seed, tm._drop_calls, p_drop > 0.0)
+        if p_drop > 0.0:
+            tm._drop_calls += 1
+        return p_drop, drop
+
+    def _sst_grads(self, B):
+        """echr_sst_grads: the proposal encoder's gradient slots in its arena, d tap_feats and d scores from the buffers `B`."""
+        ar, nps = self.tap_arena, self.tap_model.native_params()
+        one = lambda i: ar.flat_g.data_ptr() + 4 * ar.offsets[ar.slot(nps[i])]
+        two = lambda i, j: (L.c_f * 2)(one(i), one(j))
+        return L.SstGrads(two(0, 4), two(1, 5), two(2, 6), two(3, 7), one(8), one(9), L.ptr(B['g_tap']), L.ptr(B['g_scores']), L.ptr(B['wsb']), 1)
+
+
+class JointTrainStep(_JointStep):
     """The joint 'tap_cg' iteration of the reference (train.py:292-329: tap_feats, props = tap_model(c3d); cg forward; loss = lambda1 *
     tap_loss + lambda2 * cg_loss; backward; clip + step of both optimisers) around `FusedTrainStep`, without an autograd graph:
 
@@ -737,24 +740,16 @@ class JointTrainStep(object):
     preceding it.  Same sums as loss.backward() on the joint loss: gradients of both models, both updates."""
 
     def __init__(self, fused, tap_model, tap_optim, lambda1=1.0, tap_grad_clip=None, early_prepare=True, order=None, lambda2=1.0):
-        ar = getattr(tap_model, '_echr_arena', None)
-        if not isinstance(tap_optim, ClampAdam) or tap_optim.arena is None or tap_optim.arena is not ar or not ar.params_in_arena():
-            raise ValueError('JointTrainStep needs the proposal encoder on a flat arena (tap_model.build_arena()) and a ClampAdam built with it')
-        if len(tap_optim.param_groups) != 1 or {id(p) for p in tap_optim.param_groups[0]['params']} != {id(p) for p in ar.params}:
-            raise ValueError('the proposal encoder\'s optimiser must hold exactly its parameters in one group')
-        self.fused, self.tap_model, self.tap_optim, self.tap_arena = fused, tap_model, tap_optim, ar
-        self.lambda1, self.tap_grad_clip, self.early = float(lambda1), tap_grad_clip, bool(early_prepare)
+        self._init_joint(fused, tap_model, tap_optim, lambda1, lambda2, tap_grad_clip)
+        self.early = bool(early_prepare)
         # 'after' (default): the proposal encoder's backward is queued when the caption call has returned -- on the caller's stream right behind
         # d tap_feats, BESIDE the caption side's tail on the library's streams; 'hook': from inside the call, the tail forked behind it
         # (serialised: measured 3.19 vs 3.00 ms per config-5 iteration, DESIGN.md section 4h)
         self.order = order or os.environ.get('ECHR_JOINT_ORDER', 'after')
-        self.lib, self.dev = fused.lib, fused.dev
         self.lam = torch.full((1,), self.lambda1, device=self.dev, dtype=torch.float32)
         # lambda2 (train.py:322-329) scales the caption term: it travels as the caption call's g_loss scalar (every caption-side gradient and
         # d tap_feats carry it) and multiplies the returned cg term; 1.0 keeps the call's own unit scalar and today's arithmetic
-        self.lambda2 = float(lambda2)
         self.lam2 = None if self.lambda2 == 1.0 else torch.full((1,), self.lambda2, device=self.dev, dtype=torch.float32)
-        self._buf_key, self._bufs = None, None
         self.tap_loss = None
 
     def _buffers(self, T, D, H, K):
@@ -784,24 +779,14 @@ class JointTrainStep(object):
         H, K = ps[1].shape[1], ps[8].shape[0]
         B = self._buffers(T, D, H, K)
         ar = self.tap_arena
-        for p in ar.params:
-            p.grad = None
-        ar.deferred_clamp = None
-        ar.end_backward_pass()
+        self._new_tap_backward()
         if self.early:          # the caption side's tap-independent half beside the proposal encoder's forward (which leaves 192 CUs idle)
             f.prepare(c3d, lda_feats, lm_labels, ind_select_list, soi_select_list, targets, masks)
         try:
-            if self.lam2 is not None:
-                f.a.g_loss = self.lam2.data_ptr()          # (inside the try: whatever raises below, the finally puts the unit scalar back)
             # the gradient span of the proposal encoder and d tap_feats: zero-filled HERE, off the chain that later leads to its backward
             ar.flat_g.zero_()
             B['g_tap'].zero_()
-            p_drop = float(tm.rnn.dropout)
-            if tm._drop_seed is None:
-                tm._drop_seed = (int(torch.initial_seed()) ^ 0x55AA) & 0xFFFFFFFFFFFFFFFF
-            drop = EF.DropState(tm._drop_seed, tm._drop_calls, p_drop > 0.0)
-            if p_drop > 0.0:
-                tm._drop_calls += 1
+            p_drop, drop = self._tap_drop()
             sa = EF.SSTFunction._args(ps, c3d, p_drop, B['ws'], B['tap'], B['scores'])
             dc = drop.c()
             L.check(lib.echr_sst_fwd_states(C.byref(sa), C.byref(dc), L.stream_ptr()), 'sst_fwd_states')           # models/sst_model.py:31-37
@@ -820,20 +805,14 @@ class JointTrainStep(object):
                 tap_criterion()
                 L.check(lib.echr_tap_bce_bwd(L.ptr(B['scores']), L.ptr(mk), L.ptr(lb), L.ptr(ww), L.ptr(self.lam), L.ptr(B['g_scores']), T, K,
                                              L.stream_ptr()), 'tap_bce_bwd')
-                two = lambda i, j: (L.c_f * 2)(ar.flat_g.data_ptr() + 4 * ar.offsets[ar.slot(tm.native_params()[i])],
-                                               ar.flat_g.data_ptr() + 4 * ar.offsets[ar.slot(tm.native_params()[j])])
-                one = lambda i: ar.flat_g.data_ptr() + 4 * ar.offsets[ar.slot(tm.native_params()[i])]
-                sg = L.SstGrads(two(0, 4), two(1, 5), two(2, 6), two(3, 7), one(8), one(9), L.ptr(B['g_tap']), L.ptr(B['g_scores']), L.ptr(B['wsb']), 1)
-                L.check(lib.echr_sst_bwd(C.byref(sa), C.byref(sg), C.byref(dc), L.stream_ptr()), 'sst_bwd')
+                L.check(lib.echr_sst_bwd(C.byref(sa), C.byref(self._sst_grads(B)), C.byref(dc), L.stream_ptr()), 'sst_bwd')
                 self.tap_optim.step_flat_raw(self.tap_grad_clip)                                                         # train.py:315-317 for tap_optimizer
 
             cg = f(B['tap'], c3d, lda_feats, lm_labels, ind_select_list, soi_select_list, targets, masks, tap_grad=B['g_tap'], defer_update=True,
-                   prepared=self.early, mid_cb=sst_backward if self.order == 'hook' else None)
+                   prepared=self.early, mid_cb=sst_backward if self.order == 'hook' else None, g_loss=self.lam2)
         except BaseException:
             f.cancel_prepare()
             raise
-        finally:
-            f.a.g_loss = f.one.data_ptr()
         if not f.mid_called:          # the library ran the plain form (options the deferred form declines): the same work, behind the call
             sst_backward()
         self._keep = (c3d, mk, lb, ww, ps)
@@ -843,7 +822,7 @@ class JointTrainStep(object):
         return self.lam[0] * B['loss'][0] + cg
 
 
-class JointBatchStep(object):
+class JointBatchStep(_JointStep):
     """The joint 'tap_cg' iteration (train.py:292-329) over a multi-video batch (echr_amd.batch.VideoBatch) of V videos, without an autograd
     graph -- the batch contract of echr_amd/batch.py extended to both models:
 
@@ -856,19 +835,9 @@ class JointBatchStep(object):
     Nothing is deferred or hooked here (defer_update, prepare, mid_cb stay single-video forms)."""
 
     def __init__(self, fused, tap_model, tap_optim, lambda1=1.0, lambda2=1.0, tap_grad_clip=None):
-        if not isinstance(fused, FusedTrainStep):
-            raise TypeError('JointBatchStep wraps a FusedTrainStep')
-        ar = getattr(tap_model, '_echr_arena', None)
-        if not isinstance(tap_optim, ClampAdam) or tap_optim.arena is None or tap_optim.arena is not ar or not ar.params_in_arena():
-            raise ValueError('JointBatchStep needs the proposal encoder on a flat arena (tap_model.build_arena()) and a ClampAdam built with it')
-        if len(tap_optim.param_groups) != 1 or {id(p) for p in tap_optim.param_groups[0]['params']} != {id(p) for p in ar.params}:
-            raise ValueError('the proposal encoder\'s optimiser must hold exactly its parameters in one group')
-        self.fused, self.tap_model, self.tap_optim, self.tap_arena = fused, tap_model, tap_optim, ar
-        self.lambda1, self.lambda2, self.tap_grad_clip = float(lambda1), float(lambda2), tap_grad_clip
-        self.lib, self.dev = fused.lib, fused.dev
+        self._init_joint(fused, tap_model, tap_optim, lambda1, lambda2, tap_grad_clip)
         self.lam = torch.full((2,), self.lambda1, device=self.dev, dtype=torch.float32)
         self.lam[1] = self.lambda2
-        self._buf_key, self._bufs = None, None
         self._ro_cache = {}
         self.tap_loss = self.cg_loss = self.last_tap_losses = self.last_video_losses = None
         self.last_batch = None
@@ -911,12 +880,7 @@ class JointBatchStep(object):
         ro, ro_dev = self._row_offsets(rows, T)
         V = len(ro) - 1
         B = self._buffers(T, V, D, H, K)
-        p_drop = float(tm.rnn.dropout)
-        if tm._drop_seed is None:
-            tm._drop_seed = (int(torch.initial_seed()) ^ 0x55AA) & 0xFFFFFFFFFFFFFFFF
-        drop = EF.DropState(tm._drop_seed, tm._drop_calls, p_drop > 0.0)
-        if p_drop > 0.0:
-            tm._drop_calls += 1          # ONE counter per batched call, the mask keyed by the batch-global row (models.SST.forward_batch)
+        p_drop, drop = self._tap_drop()
         sa = EF.SSTFunction._args(ps, c3d, p_drop, B['ws'], B['tap'], B['scores'])
         bx = L.SstBatch(V, L.ptr(ro_dev, torch.int32), ro.ctypes.data)
         dc = drop.c()
@@ -944,21 +908,13 @@ class JointBatchStep(object):
         data-parallel hand-over points of the captioner's arena (FusedTrainStep.batch_handover); `cg_done()`: called right behind the caption
         call, where the captioner's whole arena is final in stream order and the proposal encoder's backward is not yet queued."""
         from .batch import VideoBatch
-        lib, f, tm = self.lib, self.fused, self.tap_model
+        lib, f = self.lib, self.fused
         m = f.model
         # (a list of video dicts becomes a batch built for the model's clip context below; a ready batch must already be)
         m._check_batch_options(videos_or_batch if isinstance(videos_or_batch, VideoBatch) else None)
-        if getattr(f, '_prepared', False):
-            raise NotImplementedError('prepare() runs ahead of ONE video\'s call: it does not combine with JointBatchStep')
-        L.check(lib.echr_check_async(), 'joint_batch_step (asynchronous failure of an earlier call)')
-        if getattr(f, '_pending_deferred', False):
-            f.join()          # (a deferred single-video update may still read buffers this call rewrites)
-            f._pending_deferred = False
+        f._begin('joint_batch_step', 'JointBatchStep')          # (a deferred single-video update may still read buffers this call rewrites)
         ar = self.tap_arena
-        for p in ar.params:
-            p.grad = None
-        ar.deferred_clamp = None
-        ar.end_backward_pass()
+        self._new_tap_backward()
         if isinstance(videos_or_batch, VideoBatch):
             src = videos_or_batch
             if src.labels is None:
@@ -999,11 +955,7 @@ class JointBatchStep(object):
         # d (lambda1 * sum_v tap_loss_v) / d scores, then the proposal encoder's backward with d loss / d tap_feats from the caption side
         L.check(lib.echr_tap_bce_bwd_batch(L.ptr(B['scores']), L.ptr(mk), L.ptr(lb), L.ptr(ww), w1_ld, L.ptr(ro_dev, torch.int32), V, K, T,
                                            L.ptr(self.lam[:1]), L.ptr(B['g_scores']), L.stream_ptr()), 'tap_bce_bwd_batch')
-        nps = tm.native_params()
-        one = lambda i: ar.flat_g.data_ptr() + 4 * ar.offsets[ar.slot(nps[i])]
-        two = lambda i, j: (L.c_f * 2)(one(i), one(j))
-        sg = L.SstGrads(two(0, 4), two(1, 5), two(2, 6), two(3, 7), one(8), one(9), L.ptr(B['g_tap']), L.ptr(B['g_scores']), L.ptr(B['wsb']), 1)
-        L.check(lib.echr_sst_bwd_batch(C.byref(sa), C.byref(bx), C.byref(sg), C.byref(dc), L.stream_ptr()), 'sst_bwd_batch')
+        L.check(lib.echr_sst_bwd_batch(C.byref(sa), C.byref(bx), C.byref(self._sst_grads(B)), C.byref(dc), L.stream_ptr()), 'sst_bwd_batch')
         if step:
             self.tap_optim.step_flat_raw(self.tap_grad_clip)          # train.py:315-317 for tap_optimizer
         else:
@@ -1282,10 +1234,7 @@ class DataParallelBatchStep(_DataParallelExchange):
         self.last_result = None
         cg_done = (lambda: self._captioner_exchange(empty)) if active else None
         if empty:
-            L.check(f.lib.echr_check_async(), 'data_parallel_batch_step (asynchronous failure of an earlier call)')
-            if getattr(f, '_pending_deferred', False):
-                f.join()
-                f._pending_deferred = False
+            f._begin('data_parallel_batch_step', True)
             f.arena.zero_as_final()
             if self.kind == 'joint':
                 inner.tap_arena.zero_as_final()
