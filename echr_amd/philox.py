@@ -9,7 +9,7 @@ csrc/echr_common.h (`echr_keep`); this numpy version must stay bit-identical to 
 
 Counter layout (4 x u32):  c0 = element_index >> 2, c1 = step, c2 = site, c3 = offset
 Key (2 x u32):             k0 = seed & 0xffffffff, k1 = seed >> 32
-Element e uses output word (e & 3).  keep  <=>  word >= floor(p * 2**32).
+Element e uses output word (e & 3).  keep  <=>  word >= floor(float32(p) * 2**32).
 
 Site 6 (SITE_SAMPLE) is not a dropout site: it feeds the multinomial draw of the sampling decoders (csrc/core.hip, sample_step_kernel /
 sample_row_step_kernel).  The draw of (row, step) uses element index = row, offset 0 and the decode's seed as the key; the device forms
@@ -56,8 +56,11 @@ def philox4x32_10(c0, c1, c2, c3, k0, k1):
 
 
 def drop_threshold(p):
-    """u32 threshold: an element is kept iff its random word >= threshold."""
-    return int(np.floor(float(p) * 4294967296.0)) & 0xFFFFFFFF if p < 1.0 else 0xFFFFFFFF
+    """u32 threshold: an element is kept iff its random word >= threshold.  The device receives p as a float32 (echr_dropout.p_*) and
+    floors float32(p) * 2**32 in double (csrc/decoder.hip, drop_thresh): p is rounded to float32 first here too (p = 0.3: 1288490240,
+    not the 1288490188 of the double 0.3)."""
+    p = float(np.float32(p))
+    return int(np.floor(p * 4294967296.0)) & 0xFFFFFFFF if p < 1.0 else 0xFFFFFFFF
 
 
 def keep_mask(numel, p, seed, offset, site, step):

@@ -1,7 +1,10 @@
 """Actual parity errors of the HIP path against the reference-generated fixtures (tests/golden), per GEMM path (GPU box only).
 
 --attsat: the attention-regime variants (synth.make_attsat) instead -- e_ref (float32 oracle vs float64 oracle, runs on the CPU) and, when a GPU is
-present, the HIP path against the same float64 oracle beside it, persistent and launch-per-phase (the table of tests/test_gpu_attention_regime.py)."""
+present, the HIP path against the same float64 oracle beside it, persistent and launch-per-phase (the table of tests/test_gpu_attention_regime.py).
+
+--tsrm: the event encoder's route cases (tests/tsrm_ref.py) -- e_ref per case as the lines of E_REF in tests/test_gpu_tsrm_routes.py and, when a GPU is
+present, the HIP path's errors beside them."""
 import sys, os; sys.path.insert(0, os.environ.get('GRAFT_REPO_ROOT', '/root/repo')); sys.path.insert(0, os.path.join(os.environ.get('GRAFT_REPO_ROOT', '/root/repo'), 'tests'))
 import numpy as np, torch
 import util as U
@@ -37,6 +40,26 @@ def attsat_report():
             print(line, flush=True)
 
 
+def tsrm_report():
+    """e_ref of every case of tests/tsrm_ref.py (the E_REF table of tests/test_gpu_tsrm_routes.py) and, when a GPU is present, the HIP path against
+    the same float64 oracle beside it."""
+    from tests import tsrm_ref as R
+    gpu = torch.cuda.is_available()
+    if gpu:
+        from tests import test_gpu_tsrm_routes as T
+    for name, spec in R.CASES.items():
+        e = R.e_ref(spec)
+        line = "    %r: (%.1e, %.1e, %.1e),%s# %s" % (name, e[0], e[1], e[3], ' ' * max(1, 30 - len(name)), e[2].replace(R.PREFIX, ''))
+        if gpu:
+            b = R.bounds(R.case_inputs(spec)[2]) if spec['inference'] else (0, 0)
+            h = T.errors(spec, T.gpu_run(spec, bounds=b), R.reference(spec))
+            line += ' | HIP: out %.1e grad %.1e (%s) noise %.1e' % (h[0], h[1], h[2].replace(R.PREFIX, ''), h[3])
+        print(line, flush=True)
+
+
+if '--tsrm' in sys.argv:
+    tsrm_report()
+    sys.exit(0)
 if '--attsat' in sys.argv:
     attsat_report()
     sys.exit(0)
