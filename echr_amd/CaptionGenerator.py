@@ -125,44 +125,33 @@ class CaptionGenerator(nn.Module):
         disjoint = EF.rows_disjoint(batch.soi)
         if mode == 'eval':
             with torch.no_grad():
-                if '_sample_tables' not in lm.__dict__:
-                    lm._sample_tables = {}
                 return EF.greedy_sample(video, event, batch.clip_rows(), ev_start, ev_len, A, lm.seq_length, lm.native_params(),
-                                        table_cache=lm._sample_tables, vid=vid,
+                                        table_cache=lm.sample_tables(), vid=vid,
                                         h0=self._batch_initial_state(batch, video, event, ev_start, ev_len, vid))
         if lm.training and lm.ss_prob > 0.0:
             raise NotImplementedError('scheduled sampling (ss_prob > 0) is never enabled by the reference and is not on the HIP path')
         tokens = lm._tokens(batch.labels, batch.device)
-        arena = getattr(lm, '_echr_arena_ref', None)
-        sink = EF.GradSink(arena, lm.native_params()) if arena is not None else None
         h0 = self._batch_initial_state(batch, video, event, ev_start, ev_len, vid)
-        return EF.DecoderBatchFunction.apply(video, event, batch.clip_rows(), ev_start, ev_len, tokens, A, disjoint, drop, sink, vid,
-                                             *(tuple(lm.native_params()) + self._batch_tail(batch, h0)))
+        return self._batch_decoder(batch, video, event, ev_start, ev_len, tokens, A, disjoint, drop, h0, vid)
 
-    @staticmethod
-    def _batch_clip_tail(batch):
-        """What follows the parameters in DecoderBatchFunction.apply: nothing for 'CC'; (batch.tap, its first column in the row source) for
-        'CH' / 'CC+CH' -- the row source carries no graph, the decoder's backward returns d tap itself (as ClipView.grad_src / grad_col0
-        arrange for one video)."""
-        return () if batch.clip_parts == 1 else (batch.tap, int(batch.clip_col0))
-
-    @classmethod
-    def _batch_tail(cls, batch, h0):
-        """_batch_clip_tail behind the initial state, when the model has one: (h0,) + the clip pair."""
-        return (() if h0 is None else (h0,)) + cls._batch_clip_tail(batch)
+    def _batch_decoder(self, batch, video, event, ev_start, ev_len, tokens, A, disjoint, drop, h0, vid):
+        """The teacher-forced log-probs of a batch (functional.DecoderFunction with vid).  With 'CH' / 'CC+CH' rows it takes batch.tap and its
+        first column in the row source: the row source carries no graph, the decoder's backward returns d tap itself (as ClipView.grad_src /
+        grad_col0 arrange for one video)."""
+        ps = self.lm_model.native_params()
+        return EF.DecoderFunction.apply(video, event, batch.clip_rows(), ev_start, ev_len, tokens, A, disjoint, drop, self.lm_model._grad_sink(ps),
+                                        None, h0, batch.tap if batch.clip_parts > 1 else None, int(batch.clip_col0), vid, *ps)
 
     def _batch_initial_state(self, batch, video, event, ev_start, ev_len, vid):
-        """None (the recipe: zero state) or h0 [N_tot, 3H] of CG_init_feats_type over a batch (functional.InitStateBatch): every event from
+        """None (the recipe: zero state) or h0 [N_tot, 3H] of CG_init_feats_type over a batch (functional.InitState with vid): every event from
         its own video's scene vector, its event context and its clip mean over its own video's padded clip length.  The clip mean reads
         C3D rows only (the constructor refuses 'C' with 'CH' rows)."""
         lm = self.lm_model
         if not getattr(lm, 'CG_init_feats_dim', 0):
             return None
         t = lm.CG_init_feats_type
-        arena = getattr(lm, '_echr_arena_ref', None)
-        sink = EF.GradSink(arena, (lm.init_linear.weight, lm.init_linear.bias)) if arena is not None else None
-        return EF.InitStateBatch.apply(video, event, batch.clip_rows(), ev_start, ev_len, vid, ('V' in t, 'E' in t, 'C' in t), sink,
-                                       lm.init_linear.weight, lm.init_linear.bias)
+        w, b = lm.init_linear.weight, lm.init_linear.bias
+        return EF.InitState.apply(video, event, batch.clip_rows(), ev_start, ev_len, 0, vid, ('V' in t, 'E' in t, 'C' in t), lm._grad_sink((w, b)), w, b)
 
     def _batch_contexts(self, batch, groups, need_labels=False):
         """What forward_batch and beam_batch hand to the decoder: the checks of a batched call, then (video [V, Dv], event [N_tot, d_o],
@@ -200,10 +189,7 @@ class CaptionGenerator(nn.Module):
         `max_rows`: the decode keeps seq_length + 1 states of every one of its events * beam_size rows, so it runs once per run of
         `batch.beam_groups(beam_size, max_rows)` -- consecutive videos with at most max_rows rows together; a video above the budget runs
         alone, None is one decode over the batch.  Each run is one echr_decoder_beam_batch call and one host read (its video_words)."""
-        B = int(beam_size)
-        V1 = self.lm_model.vocab_size + 1
-        if not 1 <= B <= min(EF.BEAM_MAX, V1):
-            raise ValueError('beam_size must be in [1, %d], got %d' % (min(EF.BEAM_MAX, V1), B))
+        B = EF._check_beam_size(beam_size, self.lm_model.vocab_size + 1)
         if self.training or self.lm_model.training:
             raise ValueError('beam search is an evaluation decode: call eval() first')
         groups = batch.event_groups(event_group_rows) if event_group_rows is not None else None
@@ -259,20 +245,15 @@ class CaptionGenerator(nn.Module):
             video_words = batch.caption_widths(gen_result)
             gen = torch.as_tensor(gen_result)[:, :int(video_words.max())].to(device=batch.device, dtype=torch.int64).contiguous()
         with torch.no_grad():
-            if '_sample_tables' not in lm.__dict__:
-                lm._sample_tables = {}
             greedy_res, _ = EF.greedy_sample(video, event.detach(), batch.clip_rows(), ev_start, ev_len, A, lm.seq_length, lm.native_params(),
-                                             table_cache=lm._sample_tables, vid=vid, h0=h0_d)
+                                             table_cache=lm.sample_tables(), vid=vid, h0=h0_d)
         if isinstance(gen, list) or gen.numel() == 0:
             return [], [], greedy_res, video_words          # every row drew <eos> first (OldModel.sample returns [] then, :186-187)
         N, T = gen.shape
         labels = torch.zeros(N, T + 2, dtype=torch.int64, device=gen.device)
         labels[:, 1:T + 1] = gen
-        arena = getattr(lm, '_echr_arena_ref', None)
-        sink = EF.GradSink(arena, lm.native_params()) if arena is not None else None
-        logp = EF.DecoderBatchFunction.apply(video, event, batch.clip_rows(), ev_start, ev_len, lm._tokens(labels, batch.device), A,
-                                             EF.rows_disjoint(batch.soi), drop, sink, vid,
-                                             *(tuple(lm.native_params()) + self._batch_tail(batch, h0)))
+        logp = self._batch_decoder(batch, video, event, ev_start, ev_len, lm._tokens(labels, batch.device), A, EF.rows_disjoint(batch.soi), drop,
+                                   h0, vid)
         return gen, EF.GatherTokens.apply(logp, gen), greedy_res, video_words
 
     def _event_context_groups(self, batch, groups, ech, ev_start, ev_len, vid, drop, params):

@@ -218,11 +218,9 @@ def caption_videos_beam(tap_model, cg_model, videos, featstamp_to_time, beam_siz
     (device) and 'video_words' (host int64, one entry per kept video).
 
     Host reads per call do not grow with V: the selection reads, one video_words read per run, the batch's sequences and scores."""
-    V1 = cg_model.lm_model.vocab_size + 1
-    if not 1 <= int(beam_size) <= min(EF.BEAM_MAX, V1):
-        raise ValueError('beam_size must be in [1, %d], got %r' % (min(EF.BEAM_MAX, V1), beam_size))
+    B = EF._check_beam_size(beam_size, cg_model.lm_model.vocab_size + 1)
     return _caption_videos_checked(tap_model, cg_model, videos, featstamp_to_time, vocab, topN, nms_threshold, val_score_thres, flag_eval_what,
-                                   event_group_rows, int(beam_size), max_rows)
+                                   event_group_rows, B, max_rows)
 
 
 def _caption_videos_checked(tap_model, cg_model, videos, featstamp_to_time, vocab, topN, nms_threshold, val_score_thres, flag_eval_what,

@@ -6,6 +6,7 @@ is missing -- there is no eager/PyTorch fallback.
 """
 import ctypes as C
 import os
+import types
 
 import numpy as np
 import torch
@@ -265,6 +266,7 @@ def position_embedding(ev_start, ev_len, d_pos):
 DEC_PARAMS = ('embed', 'w_logit', 'b_logit',
               'w_ih0', 'w_ih1', 'w_ih2', 'w_hh0', 'w_hh1', 'w_hh2', 'b_ih0', 'b_ih1', 'b_ih2', 'b_hh0', 'b_hh1', 'b_hh2',
               'w_c2a', 'b_c2a', 'w_h2a', 'b_h2a', 'w_alpha', 'b_alpha')
+DEC_H0_ARG, DEC_TAP_ARG = 11, 12          # positions of `h0` and `tap` among DecoderFunction's inputs (needs_input_grad)
 
 
 def _dec_args(ps, c3d, ev_start, ev_len, event, video, tokens, A, S, ws, logp, disjoint=False, n_de=None, prepared=0, train=0, h0=None):
@@ -301,8 +303,7 @@ def decoder_prepare(video, c3d, ev_start, ev_len, tokens, A, disjoint, params):
     # echr_dec_args.train: a backward pass can follow (decided here: grad mode is off inside the Function's forward)
     train = 1 if (torch.is_grad_enabled() and any(p.requires_grad for p in params)) else 0
     a = _dec_args(ps, c3d, ev_start, ev_len, None, video, tokens, A, S, None, logp, disjoint, n_de=(N, De), train=train)
-    ws = torch.empty(lib.echr_decoder_ws_floats(C.byref(a)), device=c3d.device, dtype=torch.float32)
-    a.ws = L.ptr(ws)
+    ws = _decoder_ws(a, c3d.device)
     L.check(lib.echr_decoder_fwd_prepare(C.byref(a), L.stream_ptr()), 'decoder_fwd_prepare')
     return dict(ws=ws, logp=logp, video=video, c3d=c3d, ps=ps, tokens=tokens, A=A, disjoint=disjoint, train=train)
 
@@ -315,23 +316,40 @@ def decoder_prepare_cancel():
 
 class InitState(torch.autograd.Function):
     """OldModel.init_hidden with CG_init_feats_type (OldModel_NEW.py:79-96): h0 [N, 3H] = init_linear(cat([video | event | clip.mean(1)])) -- the
-    tensor the reference then views as (N, 3, H) and transposes; the decoder entry points take it in this layout (echr_dec_args.h0)."""
+    tensor the reference then views as (N, 3, H) and transposes; the decoder entry points take it in this layout (echr_dec_args.h0).
+
+    `vid` (int32 [N] device; None = one video, `video` [Dv]): the events of several videos (echr_init_state_fwd_batch / _bwd_batch) -- `video` is
+    [V, Dv] and event n reads row vid[n], `A` is not read; the clip mean of an event divides by the padded clip length of ITS video (the
+    largest ev_len among that video's events, formed on the device: h0.grad_fn.video_len).  Row n of h0 [N_tot, 3H] is what the single-video
+    call returns for that event in its own video; backward returns d video [V, Dv] (a fixed-order segmented sum) and d event, and
+    accumulates init_linear's gradients over all rows (GradSink arena accumulation)."""
 
     @staticmethod
-    def forward(ctx, video, event, c3d, ev_start, ev_len, A, use, sink, w, b):
+    def forward(ctx, video, event, c3d, ev_start, ev_len, A, vid, use, sink, w, b):
         lib = L.load()
-        use_v, use_e, use_c = use
         video, event, c3d, w, b = _f32c(video), _f32c(event), _f32c(c3d), _f32c(w), _f32c(b)
         N, De = event.shape
-        Dv, D, H3, Dtot = video.numel(), c3d.shape[1], w.shape[0], w.shape[1]
-        if Dtot != (Dv if use_v else 0) + (De if use_e else 0) + (D if use_c else 0):
-            raise L.EchrHipError('init_linear is %d wide, the selected contexts give %d' % (Dtot, (Dv if use_v else 0) + (De if use_e else 0) + (D if use_c else 0)))
-        feats = torch.empty(N, Dtot, device=event.device, dtype=torch.float32)
-        h0 = torch.empty(N, H3, device=event.device, dtype=torch.float32)
-        a = L.InitStateArgs(N, Dv, De, D, H3, int(use_v), int(use_e), int(use_c), int(A), L.ptr(video), L.ptr(event), L.ptr(c3d),
-                            L.ptr(ev_start, torch.int32), L.ptr(ev_len, torch.int32), L.ptr(w), L.ptr(b), L.ptr(feats), L.ptr(h0))
-        L.check(lib.echr_init_state_fwd(C.byref(a), L.stream_ptr()), 'init_state_fwd')
-        ctx.save_for_backward(video, event, c3d, ev_start, ev_len, w, b, feats)
+        if vid is not None:
+            if video.dim() != 2:
+                raise ValueError('video must be [V, Dv], one scene vector per video (got %s)' % (tuple(video.shape),))
+            V = video.shape[0]
+            if vid.numel() != N or ev_start.numel() != N or ev_len.numel() != N or not 1 <= V <= N:
+                raise ValueError('vid, ev_start and ev_len need one entry per event (%d) and 1 <= V <= N (V = %d)' % (N, V))
+        Dv = video.numel() if vid is None else video.shape[1]
+        Dsel = sum(d for u, d in zip(use, (Dv, De, c3d.shape[1])) if u)
+        if w.shape[1] != Dsel:
+            raise L.EchrHipError('init_linear is %d wide, the selected contexts give %d' % (w.shape[1], Dsel))
+        feats = torch.empty(N, w.shape[1], device=event.device, dtype=torch.float32)
+        h0 = torch.empty(N, w.shape[0], device=event.device, dtype=torch.float32)
+        a = _init_state_args(video, event, c3d, ev_start, ev_len, A, vid, use, w, b, feats, h0)
+        if vid is not None:
+            vlen = torch.empty(V, device=event.device, dtype=torch.int32)
+            x, _ = batch_ext(vid, video)
+            L.check(lib.echr_init_state_fwd_batch(C.byref(a), C.byref(x), L.ptr(vlen, torch.int32), L.stream_ptr()), 'init_state_fwd_batch')
+            ctx.video_len = vlen          # the per-video padded clip lengths the device formed (written with 'C' only; h0.grad_fn.video_len)
+        else:
+            L.check(lib.echr_init_state_fwd(C.byref(a), L.stream_ptr()), 'init_state_fwd')
+        ctx.save_for_backward(video, event, c3d, ev_start, ev_len, vid, w, b, feats)
         ctx.meta = (A, use)
         ctx.sink = sink
         return h0
@@ -339,74 +357,32 @@ class InitState(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_h0):
         lib = L.load()
-        video, event, c3d, ev_start, ev_len, w, b, feats = ctx.saved_tensors
-        A, (use_v, use_e, use_c) = ctx.meta
-        N, De = event.shape
-        g_h0 = _f32c(g_h0)
-        zeroed = 1 if (ctx.sink is not None and ctx.sink.usable()) else 0
-        g_w, g_b = ctx.sink.take() if zeroed else (torch.empty_like(w), torch.empty_like(b))
-        g_video = torch.empty_like(video) if (use_v and ctx.needs_input_grad[0]) else None
-        g_event = torch.zeros_like(event) if (use_e and ctx.needs_input_grad[1]) else None
-        dfeats = torch.empty_like(feats)
-        a = L.InitStateArgs(N, video.numel(), De, c3d.shape[1], w.shape[0], int(use_v), int(use_e), int(use_c), int(A), L.ptr(video), L.ptr(event),
-                            L.ptr(c3d), L.ptr(ev_start, torch.int32), L.ptr(ev_len, torch.int32), L.ptr(w), L.ptr(b), L.ptr(feats), None)
-        g = L.InitStateGrads(L.ptr(g_h0), L.ptr(g_w), L.ptr(g_b), L.ptr(g_video) if g_video is not None else None,
-                             L.ptr(g_event) if g_event is not None else None, L.ptr(dfeats), zeroed)
-        L.check(lib.echr_init_state_bwd(C.byref(a), C.byref(g), L.stream_ptr()), 'init_state_bwd')
-        return g_video, g_event, None, None, None, None, None, None, g_w, g_b
-
-
-class InitStateBatch(torch.autograd.Function):
-    """InitState over the events of several videos (echr_init_state_fwd_batch / _bwd_batch): `video` is [V, Dv] and event n reads row vid[n];
-    the clip mean of an event divides by the padded clip length of ITS video (the largest ev_len among that video's events, formed on the
-    device).  Row n of h0 [N_tot, 3H] is what InitState returns for that event in its own video; backward returns d video [V, Dv] (a
-    fixed-order segmented sum) and d event, and accumulates init_linear's gradients over all rows (GradSink arena accumulation)."""
-
-    @staticmethod
-    def forward(ctx, video, event, c3d, ev_start, ev_len, vid, use, sink, w, b):
-        lib = L.load()
-        use_v, use_e, use_c = use
-        video, event, c3d, w, b = _f32c(video), _f32c(event), _f32c(c3d), _f32c(w), _f32c(b)
-        if video.dim() != 2:
-            raise ValueError('video must be [V, Dv], one scene vector per video (got %s)' % (tuple(video.shape),))
-        N, De = event.shape
-        V, Dv = video.shape
-        D, H3, Dtot = c3d.shape[1], w.shape[0], w.shape[1]
-        if vid.numel() != N or ev_start.numel() != N or ev_len.numel() != N or not 1 <= V <= N:
-            raise ValueError('vid, ev_start and ev_len need one entry per event (%d) and 1 <= V <= N (V = %d)' % (N, V))
-        if Dtot != (Dv if use_v else 0) + (De if use_e else 0) + (D if use_c else 0):
-            raise L.EchrHipError('init_linear is %d wide, the selected contexts give %d' % (Dtot, (Dv if use_v else 0) + (De if use_e else 0) + (D if use_c else 0)))
-        feats = torch.empty(N, Dtot, device=event.device, dtype=torch.float32)
-        h0 = torch.empty(N, H3, device=event.device, dtype=torch.float32)
-        vlen = torch.empty(V, device=event.device, dtype=torch.int32)
-        a = L.InitStateArgs(N, Dv, De, D, H3, int(use_v), int(use_e), int(use_c), 0, None, L.ptr(event), L.ptr(c3d),
-                            L.ptr(ev_start, torch.int32), L.ptr(ev_len, torch.int32), L.ptr(w), L.ptr(b), L.ptr(feats), L.ptr(h0))
-        x, _ = batch_ext(vid, video)
-        L.check(lib.echr_init_state_fwd_batch(C.byref(a), C.byref(x), L.ptr(vlen, torch.int32), L.stream_ptr()), 'init_state_fwd_batch')
-        ctx.save_for_backward(video, event, c3d, ev_start, ev_len, vid, w, b, feats)
-        ctx.use = use
-        ctx.sink = sink
-        ctx.video_len = vlen          # the per-video padded clip lengths the device formed (written with 'C' only; h0.grad_fn.video_len)
-        return h0
-
-    @staticmethod
-    def backward(ctx, g_h0):
-        lib = L.load()
         video, event, c3d, ev_start, ev_len, vid, w, b, feats = ctx.saved_tensors
-        use_v, use_e, use_c = ctx.use
-        N, De = event.shape
+        A, use = ctx.meta
         g_h0 = _f32c(g_h0)
         zeroed = 1 if (ctx.sink is not None and ctx.sink.usable()) else 0
         g_w, g_b = ctx.sink.take() if zeroed else (torch.empty_like(w), torch.empty_like(b))
-        g_video = torch.empty_like(video) if (use_v and ctx.needs_input_grad[0]) else None
-        g_event = torch.zeros_like(event) if (use_e and ctx.needs_input_grad[1]) else None
+        g_video = torch.empty_like(video) if (use[0] and ctx.needs_input_grad[0]) else None
+        g_event = torch.zeros_like(event) if (use[1] and ctx.needs_input_grad[1]) else None
         dfeats = torch.empty_like(feats)
-        a = L.InitStateArgs(N, video.shape[1], De, c3d.shape[1], w.shape[0], int(use_v), int(use_e), int(use_c), 0, None, L.ptr(event),
-                            L.ptr(c3d), L.ptr(ev_start, torch.int32), L.ptr(ev_len, torch.int32), L.ptr(w), L.ptr(b), L.ptr(feats), None)
-        g = L.InitStateGrads(L.ptr(g_h0), L.ptr(g_w), L.ptr(g_b), None, L.ptr(g_event) if g_event is not None else None, L.ptr(dfeats), zeroed)
-        x, _ = batch_ext(vid, video, g_video)
-        L.check(lib.echr_init_state_bwd_batch(C.byref(a), C.byref(g), C.byref(x), L.stream_ptr()), 'init_state_bwd_batch')
-        return g_video, g_event, None, None, None, None, None, None, g_w, g_b
+        a = _init_state_args(video, event, c3d, ev_start, ev_len, A, vid, use, w, b, feats, None)
+        # (d video of a batch travels in echr_batch_ext, like `video` itself)
+        g = L.InitStateGrads(L.ptr(g_h0), L.ptr(g_w), L.ptr(g_b), L.ptr(g_video) if vid is None else None, L.ptr(g_event), L.ptr(dfeats), zeroed)
+        if vid is not None:
+            x, _ = batch_ext(vid, video, g_video)
+            L.check(lib.echr_init_state_bwd_batch(C.byref(a), C.byref(g), C.byref(x), L.stream_ptr()), 'init_state_bwd_batch')
+        else:
+            L.check(lib.echr_init_state_bwd(C.byref(a), C.byref(g), L.stream_ptr()), 'init_state_bwd')
+        return g_video, g_event, None, None, None, None, None, None, None, g_w, g_b
+
+
+def _init_state_args(video, event, c3d, ev_start, ev_len, A, vid, use, w, b, feats, h0):
+    """echr_init_state_args of InitState's forward (h0: the output) and backward (h0 None).  A batch (vid) passes `video` in echr_batch_ext
+    and A = 0."""
+    one = vid is None
+    return L.InitStateArgs(event.shape[0], video.numel() if one else video.shape[1], event.shape[1], c3d.shape[1], w.shape[0],
+                           int(use[0]), int(use[1]), int(use[2]), int(A) if one else 0, L.ptr(video) if one else None, L.ptr(event), L.ptr(c3d),
+                           L.ptr(ev_start, torch.int32), L.ptr(ev_len, torch.int32), L.ptr(w), L.ptr(b), L.ptr(feats), L.ptr(h0))
 
 
 class ColMean(torch.autograd.Function):
@@ -454,58 +430,44 @@ class SegColMean(torch.autograd.Function):
 
 
 class DecoderFunction(torch.autograd.Function):
-    """OldModel.forward with the ThreeStream core (OldModel_NEW.py:98-137, :376-401, :801-823): log-probs [N,S,V1]."""
+    """OldModel.forward with the ThreeStream core (OldModel_NEW.py:98-137, :376-401, :801-823): log-probs [N,S,V1].  Every input has a fixed
+    position (DEC_H0_ARG, DEC_TAP_ARG: where backward reads needs_input_grad); the absent optional ones are None, None, 0, None:
+
+    `prep`: the handle of decoder_prepare(), which already ran the event-independent part on its workspace (one video only).
+    `h0` [N, 3H]: the initial state of CG_init_feats_type (InitState's rows; None = zeros); backward returns d h0.
+    `tap`, `col0` ('CH' / 'CC+CH'): the rows c3d[:, col0 : col0 + tap width] are tap[:Tv]; backward returns d tap [T, Ht]
+    (echr_decoder_row_grad behind echr_decoder_bwd).
+    `vid` (int32 [N] device): the events of several videos (echr_decoder_fwd_batch / _bwd_batch) -- `video` is [V, Dv], one scene vector per
+    video, and event n reads row vid[n]; `c3d` is the batch's row source (VideoBatch.clip_rows()); backward returns d video [V, Dv]."""
 
     @staticmethod
-    def forward(ctx, video, event, c3d, ev_start, ev_len, tokens, A, disjoint, drop, sink, prep, h0, tap=None, col0=0, *params):
-        return _decoder_forward(ctx, video, event, c3d, ev_start, ev_len, tokens, A, disjoint, drop, sink, prep, h0, tap, col0, params)
-
-    @staticmethod
-    def backward(ctx, g_logp):
-        g_video, g_event, g_h0, g_tap, grads = _decoder_backward(ctx, g_logp)
-        return (g_video, g_event, None, None, None, None, None, None, None, None, None, g_h0, g_tap, None) + grads
-
-
-class DecoderBatchFunction(torch.autograd.Function):
-    """DecoderFunction over the events of several videos: `video` is [V, Dv], one scene vector per video, and event n reads row vid[n]
-    (echr_decoder_fwd_batch / _bwd_batch); backward returns d video [V, Dv].  `c3d` is the batch's row source (VideoBatch.clip_rows()).
-    What may follow the parameters, in this order: `h0` [N_tot, 3H] (InitStateBatch's rows: the initial state of CG_init_feats_type;
-    absent = zeros), and backward returns d h0; with 'CH' / 'CC+CH' `tap` (batch.tap) and `col0` (int: its first column in the row
-    source), and backward returns d tap [T_tot, Ht] (echr_decoder_row_grad behind echr_decoder_bwd_batch)."""
-
-    @staticmethod
-    def forward(ctx, video, event, c3d, ev_start, ev_len, tokens, A, disjoint, drop, sink, vid, *params):
-        # (*params [+ (h0,)] [+ (tap, col0)]: the optional inputs trail the parameters, so zero-state 'CC' callers pass what they always passed)
-        tap, col0, h0 = None, 0, None
-        if params and isinstance(params[-1], int):
-            tap, col0, params = params[-2], params[-1], params[:-2]
-        if len(params) == len(DEC_PARAMS) + 1:
-            h0, params = params[-1], params[:-1]
-        n = 11 + len(params)
-        ctx.has_h0 = h0 is not None
-        return _decoder_forward(ctx, video, event, c3d, ev_start, ev_len, tokens, A, disjoint, drop, sink, None, h0, tap, col0, params, vid=vid,
-                                tap_arg=n + (1 if h0 is not None else 0), h0_arg=n)
+    def forward(ctx, video, event, c3d, ev_start, ev_len, tokens, A, disjoint, drop, sink, prep, h0, tap, col0, vid, *params):
+        if prep is not None and vid is not None:
+            raise ValueError('a decoder_prepare() handle belongs to one video: a batch (vid) runs its forward without one')
+        return _decoder_forward(ctx, video, event, c3d, ev_start, ev_len, tokens, A, disjoint, drop, sink, prep, h0, tap, col0, vid, params)
 
     @staticmethod
     def backward(ctx, g_logp):
         g_video, g_event, g_h0, g_tap, grads = _decoder_backward(ctx, g_logp)
-        out = (g_video, g_event, None, None, None, None, None, None, None, None, None) + grads + ((g_h0,) if ctx.has_h0 else ())
-        return out + (g_tap, None) if ctx.tap_meta is not None else out
+        return (g_video, g_event, None, None, None, None, None, None, None, None, None, g_h0, g_tap, None, None) + grads
 
 
-def _decoder_forward(ctx, video, event, c3d, ev_start, ev_len, tokens, A, disjoint, drop, sink, prep, h0, tap, col0, params, vid=None, tap_arg=12, h0_arg=11):
-    # tap / col0 ('CH', 'CC+CH'): the rows c3d[:, col0 : col0 + tap width] are tap[:Tv]; backward returns d tap (echr_decoder_row_grad)
-    # vid (multi-video batch): int32 [N] device, video is then [V, Dv]
+def _decoder_ws(a, dev):
+    """The workspace of the decoder call `a` (echr_decoder_ws_floats), allocated on `dev` and entered as a.ws."""
+    ws = torch.empty(L.load().echr_decoder_ws_floats(C.byref(a)), device=dev, dtype=torch.float32)
+    a.ws = L.ptr(ws)
+    return ws
+
+
+def _decoder_forward(ctx, video, event, c3d, ev_start, ev_len, tokens, A, disjoint, drop, sink, prep, h0, tap, col0, vid, params):
     lib = L.load()
     ctx.sink = sink
     ctx.vid = vid
     ctx.tap_meta = (tuple(tap.shape), int(col0)) if tap is not None else None
-    ctx.tap_arg = tap_arg          # position of `tap` among the Function's inputs (needs_input_grad)
-    ctx.h0_arg = h0_arg
     event = _f32c(event)
-    h0 = _f32c(h0) if h0 is not None else None          # [N, 3H] initial state (OldModel.init_hidden, CG_init_feats_type); None = zeros
+    h0 = _f32c(h0) if h0 is not None else None
     S, N = tokens.shape
-    if prep is not None:          # decoder_prepare() already ran the event-independent part on this workspace
+    if prep is not None:
         video, c3d, ps, logp, ws = prep['video'], prep['c3d'], prep['ps'], prep['logp'], prep['ws']
         train = prep['train']
         a = _dec_args(ps, c3d, ev_start, ev_len, event, video, tokens, A, S, ws, logp, disjoint, prepared=1, train=train, h0=h0)
@@ -516,8 +478,7 @@ def _decoder_forward(ctx, video, event, c3d, ev_start, ev_len, tokens, A, disjoi
         logp = torch.empty(N, S, V1, device=event.device, dtype=torch.float32)
         train = 1 if any(ctx.needs_input_grad) else 0
         a = _dec_args(ps, c3d, ev_start, ev_len, event, video, tokens, A, S, None, logp, disjoint, train=train, h0=h0)
-        ws = torch.empty(lib.echr_decoder_ws_floats(C.byref(a)), device=event.device, dtype=torch.float32)
-        a.ws = L.ptr(ws)
+        ws = _decoder_ws(a, event.device)
     d = drop.c()
     if vid is not None:
         x, ctx.xws = batch_ext(vid, video, H=ps[6].shape[1])          # (kept with the node: the forward's kernels read it in stream order)
@@ -558,8 +519,8 @@ def _decoder_backward(ctx, g_logp):
     g_event = torch.empty_like(event)
     g_video = torch.empty_like(video) if ctx.needs_input_grad[0] else None
     h0 = ctx.h0
-    g_h0 = torch.empty_like(h0) if (h0 is not None and ctx.needs_input_grad[ctx.h0_arg]) else None
-    want_tap = ctx.tap_meta is not None and ctx.needs_input_grad[ctx.tap_arg]
+    g_h0 = torch.empty_like(h0) if (h0 is not None and ctx.needs_input_grad[DEC_H0_ARG]) else None
+    want_tap = ctx.tap_meta is not None and ctx.needs_input_grad[DEC_TAP_ARG]
     a = _dec_args(ps, c3d, ev_start, ev_len, event, video, tokens, A, S, ws, logp, disjoint, train=train, h0=h0)
     wsb = torch.empty(lib.echr_decoder_ws_bwd_floats(C.byref(a)), device=event.device, dtype=torch.float32)
     gp = [L.ptr(x) for x in grads]
@@ -642,6 +603,121 @@ def clip_rows(c3d, tap):
     return rows
 
 
+def _check_beam_size(beam_size, V1, note=''):
+    """int(beam_size), or ValueError outside [1, min(BEAM_MAX, V1)]; `note` follows the range in the message (functional's own wording)."""
+    B = int(beam_size)
+    if not 1 <= B <= min(BEAM_MAX, V1):
+        raise ValueError('beam_size must be in [1, %d]%s, got %d' % (min(BEAM_MAX, V1), note, B))
+    return B
+
+
+def _stop_step(counts, L_):
+    """The width a decode over L_ steps is cut at: t - 1 for the first step t in 1 .. L_ with counts[t] == 0, nobody unfinished
+    (OldModel_NEW.py:179-180), or L_."""
+    return next((t - 1 for t in range(1, L_ + 1) if counts[t] == 0), L_)
+
+
+def _cut(seq, slp, T):
+    return ([], []) if T == 0 else (seq[:, :T].contiguous(), slp[:, :T].contiguous())
+
+
+def _decode_inputs(video, event, c3d, ev_start, ev_len, params, h0, vid, rep=1, check_batch=False):
+    """The tensors a decode call reads, converted, as one object (fields video, event, c3d, ev_start, ev_len, ps, h0, vid; _decode_call adds
+    the workspaces ws / xws, a launcher its own).  rep > 1 (beam slots): event, ev_start, ev_len, h0 and vid are repeated per slot,
+    event-major -- row n * rep + j is slot j of event n; the clip rows and scene vectors stay shared.  check_batch: the shape rules of a
+    batch (ValueError)."""
+    if check_batch:
+        if video.dim() != 2:
+            raise ValueError('video must be [V, Dv], one scene vector per video (got %s)' % (tuple(video.shape),))
+        N, V = event.shape[0], video.shape[0]
+        if vid.dim() != 1 or vid.numel() != N or ev_start.numel() != N or ev_len.numel() != N:
+            raise ValueError('vid, ev_start and ev_len need one entry per event (%d)' % N)
+        if not 1 <= V <= N:
+            raise ValueError('a batch has between 1 video and one video per event (V = %d, N = %d)' % (V, N))
+    k = types.SimpleNamespace(video=_f32c(video), event=_f32c(event), c3d=_f32c(c3d), ev_start=ev_start, ev_len=ev_len,
+                              ps=[_f32c(p) for p in params], h0=_f32c(h0) if h0 is not None else None, vid=vid, ws=None, xws=None)
+    if rep > 1:
+        # (event, the large one, LAST: repeated first it cost the single-video beam decode about 10 us per call, measured -- the later repeats
+        # appear to wait for its copy kernel, which otherwise runs behind the host's set-up of the call)
+        for name in ('vid', 'ev_start', 'ev_len', 'h0', 'event'):
+            if getattr(k, name) is not None:
+                setattr(k, name, getattr(k, name).repeat_interleave(rep, dim=0).contiguous())
+    return k
+
+
+def _decode_call(video, event, c3d, ev_start, ev_len, A, seq_length, params, h0, vid, rep=1, check_batch=False):
+    """The set-up every decode launcher shares: (echr_dec_args without tokens / logp, echr_batch_ext or None, keep).  `keep`
+    (_decode_inputs) holds EVERY tensor whose raw pointer went into the two structs -- converted inputs and parameters, repeated rows,
+    the decoder workspace, the batch scratch.  The library reads them until the call's kernels have run: a launcher adds the buffers it
+    allocates itself and holds `keep` until its host read and echr_check_async are behind it."""
+    k = _decode_inputs(video, event, c3d, ev_start, ev_len, params, h0, vid, rep, check_batch)
+    a = _dec_args(k.ps, k.c3d, k.ev_start, k.ev_len, k.event, k.video, None, A, seq_length, None, None, h0=k.h0)
+    k.ws = _decoder_ws(a, k.event.device)
+    x = None
+    if vid is not None:
+        x, k.xws = batch_ext(k.vid, k.video, H=k.ps[6].shape[1])
+    return a, x, k
+
+
+def _sample(video, event, c3d, ev_start, ev_len, A, seq_length, params, h0, vid, drop, multinomial, temperature, seed, table_cache, debug,
+            defer, widths):
+    """The launcher of greedy_sample and (widths=True: the per-video widths behind the unfinished counts, checked against them and returned)
+    of sample_train_batch."""
+    lib = L.load()
+    a, x, keep = _decode_call(video, event, c3d, ev_start, ev_len, A, seq_length, params, h0, vid, check_batch=widths)
+    N, dev = keep.event.shape[0], keep.event.device
+    V = keep.video.shape[0] if widths else 0
+    wss = keep.wss = torch.empty(lib.echr_sampler_ws_floats(C.byref(a)), device=dev, dtype=torch.float32)
+    seq = torch.empty(N, seq_length, device=dev, dtype=torch.int64)
+    slp = torch.empty(N, seq_length, device=dev, dtype=torch.float32)
+    counts = torch.empty(seq_length + 1 + (V + 1 if widths else 0), device=dev, dtype=torch.int32)          # n_unfinished [L+1] (| video_words [V+1])
+    tables, valid = None, 0
+    if table_cache is not None and not multinomial:
+        nt = lib.echr_sampler_table_floats(C.byref(a))
+        if nt > 0:
+            key = (PARAM_EPOCH[0], nt, str(dev)) + tuple((p.data_ptr(), p._version) for p in params)
+            tables = table_cache.get('tables')
+            if tables is None or tables.numel() != nt or tables.device != dev:
+                tables = table_cache['tables'] = torch.empty(nt, device=dev, dtype=torch.float32)
+                table_cache['key'] = None
+            valid = 1 if table_cache.get('key') == key else 0
+            table_cache['key'] = None      # marked valid again only once this call has completed without an error
+    sa = L.SampleArgs(a, seq_length, L.ptr(seq, torch.int64), L.ptr(slp), L.ptr(counts, torch.int32), L.ptr(wss),
+                      1 if multinomial else 0, float(temperature), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                      L.ptr(tables) if tables is not None else None, valid)
+    dc = drop.c() if drop is not None else None
+    what = 'decoder_sample_train_batch' if widths else 'decoder_sample'
+    if widths:
+        L.check(lib.echr_decoder_sample_train_batch(C.byref(sa), C.byref(dc), C.byref(x), counts.data_ptr() + 4 * (seq_length + 1), L.stream_ptr()), what)
+    elif vid is not None:
+        L.check(lib.echr_decoder_sample_batch(C.byref(sa), C.byref(x), L.stream_ptr()), 'decoder_sample_batch')
+    elif drop is not None:
+        L.check(lib.echr_decoder_sample_train(C.byref(sa), C.byref(dc), L.stream_ptr()), 'decoder_sample_train')
+    else:
+        L.check(lib.echr_decoder_sample(C.byref(sa), L.stream_ptr()), what)
+
+    def finish(keep=keep):          # (`keep`: what the queued kernels read, held until the host read below)
+        host = counts.cpu().numpy()                # the only device->host sync of the whole decode
+        L.check(lib.echr_check_async(), what)
+        if tables is not None:
+            table_cache['key'] = key
+        if debug is not None:                      # tests: the raw logits [N,V1] of the last decoder step (sampler workspace: XT | LOGITS | ...)
+            V1, E = keep.ps[0].shape
+            o = (N * E + 63) // 64 * 64
+            debug['last_logits'] = wss[o:o + N * V1].view(N, V1).clone()
+            debug['seq_full'], debug['logp_full'] = seq.clone(), slp.clone()
+            debug['stopped_early'] = int(host[0])      # persistent decoder: 1 = every event had emitted <eos> before seq_length and the launch stopped there
+        T = _stop_step(host, seq_length)
+        if not widths:
+            return _cut(seq, slp, T)
+        vw = host[seq_length + 1:].astype(np.int64)
+        if int(vw[V]) != T:
+            raise L.EchrHipError('decoder_sample_train_batch: widths %s disagree with the unfinished counts %s'
+                                 % (vw.tolist(), host[:seq_length + 1].tolist()))
+        return _cut(seq, slp, T) + (vw[:V],)
+    return finish if defer else finish()
+
+
 def greedy_sample(video, event, c3d, ev_start, ev_len, A, seq_length, params, debug=None, multinomial=False, temperature=1.0, seed=0,
                   table_cache=None, h0=None, drop=None, vid=None, defer=False):
     """OldModel.sample (OldModel_NEW.py:139-187) with every step on device; one host sync at the end.  Greedy arg-max by default
@@ -656,7 +732,7 @@ def greedy_sample(video, event, c3d, ev_start, ev_len, A, seq_length, params, de
     with the masks echr_decoder_fwd draws for the same state at the same step (echr_decoder_sample_train).
 
     `vid` (int32 [N] device): greedy decode of a multi-video batch -- `video` is [V, Dv] and event n reads row vid[n]
-    (echr_decoder_sample_batch); `h0` is then InitStateBatch's [N, 3H] (an initial state takes the per-step chain at every row count).
+    (echr_decoder_sample_batch); `h0` is then the batched InitState's [N, 3H] (an initial state takes the per-step chain at every row count).
 
     Returns (seq int64 [N,T], logp fp32 [N,T]) with T <= seq_length, or ([], []) when nothing was generated.
     `defer=True`: the decode is queued and a function is returned that performs the host read and returns the result -- a caller with
@@ -665,119 +741,54 @@ def greedy_sample(video, event, c3d, ev_start, ev_len, A, seq_length, params, de
         raise NotImplementedError('the batched decode here is the greedy one (the sampled pass of a batch is sample_train_batch)')
     if drop is not None and not multinomial:
         raise ValueError('a dropout state is taken by the multinomial decode only (the greedy baseline runs in eval mode)')
-    lib = L.load()
-    video, event, c3d = _f32c(video), _f32c(event), _f32c(c3d)
-    ps = [_f32c(p) for p in params]
-    N = event.shape[0]
-    dev = event.device
-    h0 = _f32c(h0) if h0 is not None else None
-    a = _dec_args(ps, c3d, ev_start, ev_len, event, video, None, A, seq_length, None, None, h0=h0)
-    ws = torch.empty(lib.echr_decoder_ws_floats(C.byref(a)), device=dev, dtype=torch.float32)
-    a.ws = L.ptr(ws)
-    wss = torch.empty(lib.echr_sampler_ws_floats(C.byref(a)), device=dev, dtype=torch.float32)
-    seq = torch.empty(N, seq_length, device=dev, dtype=torch.int64)
-    slp = torch.empty(N, seq_length, device=dev, dtype=torch.float32)
-    nun = torch.empty(seq_length + 1, device=dev, dtype=torch.int32)
-    tables, valid = None, 0
-    if table_cache is not None and not multinomial:
-        nt = lib.echr_sampler_table_floats(C.byref(a))
-        if nt > 0:
-            key = (PARAM_EPOCH[0], nt, str(dev)) + tuple((p.data_ptr(), p._version) for p in params)
-            tables = table_cache.get('tables')
-            if tables is None or tables.numel() != nt or tables.device != dev:
-                tables = table_cache['tables'] = torch.empty(nt, device=dev, dtype=torch.float32)
-                table_cache['key'] = None
-            valid = 1 if table_cache.get('key') == key else 0
-            table_cache['key'] = None      # marked valid again only once this call has completed without an error
-    sa = L.SampleArgs(a, seq_length, L.ptr(seq, torch.int64), L.ptr(slp), L.ptr(nun, torch.int32), L.ptr(wss),
-                      1 if multinomial else 0, float(temperature), int(seed) & 0xFFFFFFFFFFFFFFFF,
-                      L.ptr(tables) if tables is not None else None, valid)
-    xws = None
-    if vid is not None:
-        x, xws = batch_ext(vid, video, H=ps[6].shape[1])
-        L.check(lib.echr_decoder_sample_batch(C.byref(sa), C.byref(x), L.stream_ptr()), 'decoder_sample_batch')
-    elif drop is not None:
-        dc = drop.c()
-        L.check(lib.echr_decoder_sample_train(C.byref(sa), C.byref(dc), L.stream_ptr()), 'decoder_sample_train')
-    else:
-        L.check(lib.echr_decoder_sample(C.byref(sa), L.stream_ptr()), 'decoder_sample')
-
-    def finish():          # (holds the workspaces and converted inputs the queued kernels use until the host read below)
-        keep = (ws, wss, xws, video, event, c3d, ps, h0)          # noqa: F841
-        counts = nun.cpu().numpy()                 # the only device->host sync of the whole decode
-        L.check(lib.echr_check_async(), 'decoder_sample')
-        if tables is not None:
-            table_cache['key'] = key
-        if debug is not None:                      # tests: the raw logits [N,V1] of the last decoder step (sampler workspace: XT | LOGITS | ...)
-            E, V1 = ps[0].shape[1], ps[0].shape[0]
-            o = (N * E + 63) // 64 * 64
-            debug['last_logits'] = wss[o:o + N * V1].view(N, V1).clone()
-            debug['seq_full'], debug['logp_full'] = seq.clone(), slp.clone()
-            debug['stopped_early'] = int(counts[0])      # persistent decoder: 1 = every event had emitted <eos> before seq_length and the launch stopped there
-        T = seq_length
-        for t in range(1, seq_length + 1):        # OldModel_NEW.py:179-180: stop at the first step with nobody unfinished
-            if counts[t] == 0:
-                T = t - 1
-                break
-        if T == 0:
-            return [], []
-        return seq[:, :T].contiguous(), slp[:, :T].contiguous()
-    return finish if defer else finish()
+    return _sample(video, event, c3d, ev_start, ev_len, A, seq_length, params, h0, vid, drop, multinomial, temperature, seed, table_cache, debug,
+                   defer, False)
 
 
 def sample_train_batch(video, event, c3d, ev_start, ev_len, vid, A, seq_length, params, drop, temperature=1.0, seed=0, defer=False, h0=None):
     """The sampled pass of self-critical training over a multi-video batch (echr_decoder_sample_train_batch): `greedy_sample(...,
     multinomial=True, drop=)` with `video` [V, Dv] and `vid` int32 [N] (device, non-decreasing) naming each event's video.  The decoder's
     dropout is active under `drop` with the masks the batched teacher-forced forward draws at the same step; the draws are keyed (seed,
-    batch-global row, step); `h0` [N, 3H]: InitStateBatch's initial state (None = zeros).
+    batch-global row, step); `h0` [N, 3H]: the batched InitState's initial state (None = zeros).
 
     Returns (seq int64 [N,T], logp fp32 [N,T], video_words): video_words is a host int64 [V] with the width each video's own call cuts its
     output at (the largest number of non-zero tokens among its rows) and T = max(video_words); ([], [], zeros) when T == 0.  One host read
     per call: the per-step unfinished counts and video_words travel in one vector.  `defer=True`: as in greedy_sample."""
     if drop is None:
         raise ValueError('the sampled pass of self-critical training needs the iteration\'s dropout state')
-    if video.dim() != 2:
-        raise ValueError('video must be [V, Dv], one scene vector per video (got %s)' % (tuple(video.shape),))
-    lib = L.load()
-    N, V = event.shape[0], video.shape[0]
-    if vid.dim() != 1 or vid.numel() != N or ev_start.numel() != N or ev_len.numel() != N:
-        raise ValueError('vid, ev_start and ev_len need one entry per event (%d)' % N)
-    if not 1 <= V <= N:
-        raise ValueError('a batch has between 1 video and one video per event (V = %d, N = %d)' % (V, N))
-    video, event, c3d = _f32c(video), _f32c(event), _f32c(c3d)
-    ps = [_f32c(p) for p in params]
-    dev = event.device
-    h0 = _f32c(h0) if h0 is not None else None
-    a = _dec_args(ps, c3d, ev_start, ev_len, event, video, None, A, seq_length, None, None, h0=h0)
-    ws = torch.empty(lib.echr_decoder_ws_floats(C.byref(a)), device=dev, dtype=torch.float32)
-    a.ws = L.ptr(ws)
-    wss = torch.empty(lib.echr_sampler_ws_floats(C.byref(a)), device=dev, dtype=torch.float32)
-    seq = torch.empty(N, seq_length, device=dev, dtype=torch.int64)
-    slp = torch.empty(N, seq_length, device=dev, dtype=torch.float32)
-    counts = torch.empty(seq_length + 1 + V + 1, device=dev, dtype=torch.int32)          # n_unfinished [L+1] | video_words [V+1]
-    sa = L.SampleArgs(a, seq_length, L.ptr(seq, torch.int64), L.ptr(slp), L.ptr(counts, torch.int32), L.ptr(wss), 1, float(temperature),
-                      int(seed) & 0xFFFFFFFFFFFFFFFF, None, 0)
-    x, xws = batch_ext(vid, video, H=ps[6].shape[1])
-    dc = drop.c()
-    L.check(lib.echr_decoder_sample_train_batch(C.byref(sa), C.byref(dc), C.byref(x), counts.data_ptr() + 4 * (seq_length + 1), L.stream_ptr()),
-            'decoder_sample_train_batch')
-
-    def finish():          # (holds ws / wss / xws and the converted inputs until the host read below)
-        keep = (ws, wss, xws, video, event, c3d, ps, h0)          # noqa: F841
-        host = counts.cpu().numpy()                # the only device->host sync of the whole decode
-        L.check(lib.echr_check_async(), 'decoder_sample_train_batch')
-        nun, vw = host[:seq_length + 1], host[seq_length + 1:].astype(np.int64)
-        T = int(vw[V])
-        stop = next((t - 1 for t in range(1, seq_length + 1) if nun[t] == 0), seq_length)          # OldModel_NEW.py:179-180
-        if stop != T:
-            raise L.EchrHipError('decoder_sample_train_batch: widths %s disagree with the unfinished counts %s' % (vw.tolist(), nun.tolist()))
-        if T == 0:
-            return [], [], vw[:V]
-        return seq[:, :T].contiguous(), slp[:, :T].contiguous(), vw[:V]
-    return finish if defer else finish()
+    return _sample(video, event, c3d, ev_start, ev_len, A, seq_length, params, h0, vid, drop, True, temperature, seed, None, None, defer, True)
 
 
 BEAM_MAX = 16          # echr_decoder_beam's largest beam
+
+
+def _beam(video, event, c3d, ev_start, ev_len, vid, A, seq_length, params, beam_size, h0):
+    """The launcher of beam_search (vid None: echr_decoder_beam) and beam_search_batch (echr_decoder_beam_batch): (seq [N, seq_length], logp,
+    score, widths) with `widths` the one host read of the decode as host int64 -- [T] for one video, video_words [V] | T for a batch."""
+    lib = L.load()
+    B = _check_beam_size(beam_size, params[0].shape[0], ' (and <= the vocabulary size + 1)')
+    i32 = lambda t: t.to(torch.int32)
+    a, x, keep = _decode_call(video, event, c3d, i32(ev_start), i32(ev_len), A, seq_length, params, h0, i32(vid) if vid is not None else None,
+                              rep=B, check_batch=vid is not None)
+    N, dev = event.shape[0], keep.event.device
+    seq = torch.empty(N, seq_length, device=dev, dtype=torch.int64)
+    slp = torch.empty(N, seq_length, device=dev, dtype=torch.float32)
+    score = torch.empty(N, device=dev, dtype=torch.float32)
+    words = torch.empty(N + 1, device=dev, dtype=torch.int32)
+    ba = L.BeamArgs(a, B, seq_length, L.ptr(seq, torch.int64), L.ptr(slp), L.ptr(score), L.ptr(words, torch.int32), None)
+    keep.wsb = torch.empty(lib.echr_beam_ws_floats(C.byref(ba)), device=dev, dtype=torch.float32)
+    ba.ws_beam = L.ptr(keep.wsb)
+    if vid is None:          # (either branch ends in the only device->host sync of the whole decode)
+        what = 'decoder_beam'
+        L.check(lib.echr_decoder_beam(C.byref(ba), L.stream_ptr()), what)
+        widths = [words[N].item()]
+    else:
+        what, vwords = 'decoder_beam_batch', torch.empty(keep.video.shape[0] + 1, device=dev, dtype=torch.int32)
+        L.check(lib.echr_decoder_beam_batch(C.byref(ba), C.byref(x), L.ptr(vwords, torch.int32), L.stream_ptr()), what)
+        widths = vwords.cpu().numpy()
+    L.check(lib.echr_check_async(), what)
+    del keep          # (held up to here: the library read its tensors through raw pointers)
+    return seq, slp, score, np.asarray(widths, dtype=np.int64)
 
 
 def beam_search(video, event, c3d, ev_start, ev_len, A, seq_length, params, beam_size, h0=None):
@@ -790,88 +801,22 @@ def beam_search(video, event, c3d, ev_start, ev_len, A, seq_length, params, beam
     Returns (seq int64 [N,T], logp fp32 [N,T], score fp32 [N]): T = the longest result's word count, seq its words then zeros, logp
     its token log-probs with the <eos> one at each row's word count (when inside T) then zeros, score the sum of its log-probs (<eos>
     included).  seq and logp are [] when T == 0.  beam_size = 1 gives the greedy decode's seq up to each row's first <eos>."""
-    lib = L.load()
-    video, event, c3d = _f32c(video), _f32c(event), _f32c(c3d)
-    ps = [_f32c(p) for p in params]
-    B = int(beam_size)
-    V1 = ps[0].shape[0]
-    if not 1 <= B <= min(BEAM_MAX, V1):
-        raise ValueError('beam_size must be in [1, %d] (and <= the vocabulary size + 1), got %d' % (min(BEAM_MAX, V1), B))
-    N = event.shape[0]
-    dev = event.device
-    rep = lambda x: x.repeat_interleave(B, dim=0).contiguous()          # event-major: row n*B + j is slot j of event n
-    ev_start_r = rep(ev_start.to(torch.int32))
-    ev_len_r = rep(ev_len.to(torch.int32))
-    h0_r = rep(_f32c(h0)) if h0 is not None else None
-    event_r = rep(event)          # (named, like the others: the library holds its raw pointer until the host read below)
-    a = _dec_args(ps, c3d, ev_start_r, ev_len_r, event_r, video, None, A, seq_length, None, None, h0=h0_r)
-    ws = torch.empty(lib.echr_decoder_ws_floats(C.byref(a)), device=dev, dtype=torch.float32)
-    a.ws = L.ptr(ws)
-    seq = torch.empty(N, seq_length, device=dev, dtype=torch.int64)
-    slp = torch.empty(N, seq_length, device=dev, dtype=torch.float32)
-    score = torch.empty(N, device=dev, dtype=torch.float32)
-    words = torch.empty(N + 1, device=dev, dtype=torch.int32)
-    ba = L.BeamArgs(a, B, seq_length, L.ptr(seq, torch.int64), L.ptr(slp), L.ptr(score), L.ptr(words, torch.int32), None)
-    wsb = torch.empty(lib.echr_beam_ws_floats(C.byref(ba)), device=dev, dtype=torch.float32)
-    ba.ws_beam = L.ptr(wsb)
-    L.check(lib.echr_decoder_beam(C.byref(ba), L.stream_ptr()), 'decoder_beam')
-    T = int(words[N].item())                   # the only device->host sync of the whole decode
-    L.check(lib.echr_check_async(), 'decoder_beam')
-    if T == 0:
-        return [], [], score
-    return seq[:, :T].contiguous(), slp[:, :T].contiguous(), score
+    seq, slp, score, widths = _beam(video, event, c3d, ev_start, ev_len, None, A, seq_length, params, beam_size, h0)
+    return _cut(seq, slp, int(widths[0])) + (score,)
 
 
 def beam_search_batch(video, event, c3d, ev_start, ev_len, vid, A, seq_length, params, beam_size, trim=True, h0=None):
     """`beam_search` over the events of a multi-video batch in one decode (echr_decoder_beam_batch): `video` is [V, Dv], `vid` int32 [N]
     (device, non-decreasing) names each event's video, `c3d` / `ev_start` are the batch's concatenated rows and batch-absolute starts.
-    event, ev_start, ev_len, vid and `h0` (InitStateBatch's [N, 3H]; None = zeros) are repeated per slot.
+    event, ev_start, ev_len, vid and `h0` (the batched InitState's [N, 3H]; None = zeros) are repeated per slot.
 
     Returns (seq int64 [N,T], logp fp32 [N,T], score fp32 [N], video_words): video_words is a host int64 [V] with the longest result's
     word count of each video -- the width that video's decode has alone -- and T = max(video_words).  A video's rows are zero from its
     own width on in seq; its logp may hold the <eos> log-prob of a full-width row in that column.  seq and logp are [] when T == 0.  One
     host read (video_words) per call.  trim=False returns seq and logp at their full width [N, seq_length] whatever T is (a caller that
     assembles several decodes into one result, CaptionGenerator.beam_batch, cuts once at the end)."""
-    lib = L.load()
-    ps = [_f32c(p) for p in params]
-    B = int(beam_size)
-    V1 = ps[0].shape[0]
-    if not 1 <= B <= min(BEAM_MAX, V1):
-        raise ValueError('beam_size must be in [1, %d] (and <= the vocabulary size + 1), got %d' % (min(BEAM_MAX, V1), B))
-    if video.dim() != 2:
-        raise ValueError('video must be [V, Dv], one scene vector per video (got %s)' % (tuple(video.shape),))
-    N, V = event.shape[0], video.shape[0]
-    if vid.dim() != 1 or vid.numel() != N or ev_start.numel() != N or ev_len.numel() != N:
-        raise ValueError('vid, ev_start and ev_len need one entry per event (%d)' % N)
-    if not 1 <= V <= N:
-        raise ValueError('a batch has between 1 video and one video per event (V = %d, N = %d)' % (V, N))
-    video, event, c3d = _f32c(video), _f32c(event), _f32c(c3d)
-    dev = event.device
-    rep = lambda x: x.repeat_interleave(B, dim=0).contiguous()          # event-major: row n*B + j is slot j of event n
-    # (named: the library reads these through raw pointers, so they must outlive the call's kernels -- until the host read below)
-    vid_r, ev_start_r, ev_len_r, event_r = rep(vid.to(torch.int32)), rep(ev_start.to(torch.int32)), rep(ev_len.to(torch.int32)), rep(event)
-    h0_r = rep(_f32c(h0)) if h0 is not None else None
-    a = _dec_args(ps, c3d, ev_start_r, ev_len_r, event_r, video, None, A, seq_length, None, None, h0=h0_r)
-    ws = torch.empty(lib.echr_decoder_ws_floats(C.byref(a)), device=dev, dtype=torch.float32)
-    a.ws = L.ptr(ws)
-    seq = torch.empty(N, seq_length, device=dev, dtype=torch.int64)
-    slp = torch.empty(N, seq_length, device=dev, dtype=torch.float32)
-    score = torch.empty(N, device=dev, dtype=torch.float32)
-    words = torch.empty(N + 1, device=dev, dtype=torch.int32)
-    vwords = torch.empty(V + 1, device=dev, dtype=torch.int32)
-    ba = L.BeamArgs(a, B, seq_length, L.ptr(seq, torch.int64), L.ptr(slp), L.ptr(score), L.ptr(words, torch.int32), None)
-    wsb = torch.empty(lib.echr_beam_ws_floats(C.byref(ba)), device=dev, dtype=torch.float32)
-    ba.ws_beam = L.ptr(wsb)
-    x, xws = batch_ext(vid_r, video, H=ps[6].shape[1])
-    L.check(lib.echr_decoder_beam_batch(C.byref(ba), C.byref(x), L.ptr(vwords, torch.int32), L.stream_ptr()), 'decoder_beam_batch')
-    vw = vwords.cpu().numpy().astype(np.int64)          # the only device->host sync of the whole decode
-    L.check(lib.echr_check_async(), 'decoder_beam_batch')
-    T = int(vw[V])
-    if not trim:
-        return seq, slp, score, vw[:V]
-    if T == 0:
-        return [], [], score, vw[:V]
-    return seq[:, :T].contiguous(), slp[:, :T].contiguous(), score, vw[:V]
+    seq, slp, score, widths = _beam(video, event, c3d, ev_start, ev_len, vid, A, seq_length, params, beam_size, h0)
+    return ((seq, slp) if not trim else _cut(seq, slp, int(widths[-1]))) + (score, widths[:-1])
 
 
 def decoder_step(it, video, event, c3d, ev_start, ev_len, A, state, params, drop=None):
@@ -890,8 +835,7 @@ def decoder_step(it, video, event, c3d, ev_start, ev_len, A, state, params, drop
         raise ValueError('state must be a pair of [3,N,H] tensors (got %s, %s)' % (tuple(h_in.shape), tuple(c_in.shape)))
     logp = torch.empty(N, V1, device=dev, dtype=torch.float32)
     a = _dec_args(ps, c3d, ev_start, ev_len, event, video, tok, A, 1, None, logp)
-    ws = torch.empty(lib.echr_decoder_ws_floats(C.byref(a)), device=dev, dtype=torch.float32)
-    a.ws = L.ptr(ws)
+    ws = _decoder_ws(a, dev)          # noqa: F841
     h_out, c_out = torch.empty_like(h_in), torch.empty_like(c_in)
     d = (drop if drop is not None else DropState(training=False)).c()
     L.check(lib.echr_decoder_step(C.byref(a), L.ptr(h_in), L.ptr(c_in), L.ptr(h_out), L.ptr(c_out), C.byref(d), L.stream_ptr()), 'decoder_step')

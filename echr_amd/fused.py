@@ -636,9 +636,7 @@ class SelfCriticalBatchStep(object):
             if gen_result is None:
                 sampled = EF.sample_train_batch(video, event, batch.clip_rows(), ev_start, ev_len, vid, A, lm.seq_length, ps, drop,
                                                 seed=lm._sample_seed(), defer=True, h0=h0)
-            if '_sample_tables' not in lm.__dict__:
-                lm._sample_tables = {}
-            greedy_f = EF.greedy_sample(video, event, batch.clip_rows(), ev_start, ev_len, A, lm.seq_length, ps, table_cache=lm._sample_tables,
+            greedy_f = EF.greedy_sample(video, event, batch.clip_rows(), ev_start, ev_len, A, lm.seq_length, ps, table_cache=lm.sample_tables(),
                                         vid=vid, defer=True, h0=h0)
             # the one host sync of the iteration: the first read drains the stream, both decodes included
             if sampled is not None:

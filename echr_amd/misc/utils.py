@@ -29,7 +29,9 @@ class LanguageModelCriterion(nn.Module):
     def forward(self, input, target, mask):
         # when `input` comes straight from the native decoder, its backward takes the criterion's gradient in fused form
         # (echr_dec_grads.nll_*: softmax - one-hot in one pass) instead of a dense [N,S,V+1] tensor; see MaskedNLL.backward
-        node = input.grad_fn if (EF.FUSED_NLL[0] and type(input.grad_fn).__name__ == 'DecoderFunctionBackward') else None
+        # (a one-video node only, vid None: the log-probs of a batch go through VideoBatch.criterion's per-video slices and take the dense gradient)
+        fn = input.grad_fn
+        node = fn if (EF.FUSED_NLL[0] and type(fn).__name__ == 'DecoderFunctionBackward' and fn.vid is None) else None
         return EF.MaskedNLL.apply(input, target.to(input.device), mask.to(input.device), node)
 
 

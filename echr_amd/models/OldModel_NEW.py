@@ -148,6 +148,16 @@ class OldModel(nn.Module):
         d.pop('_sample_tables', None)
         return d
 
+    def sample_tables(self):
+        """The dict the greedy decodes keep their parameter-derived operands in (EF.greedy_sample's table_cache), reused across calls until
+        invalidate_native_caches() drops it."""
+        return self.__dict__.setdefault('_sample_tables', {})
+
+    def _grad_sink(self, params):
+        """Where the backward of a Function over `params` writes their gradients: the module's flat arena, or None without one."""
+        arena = getattr(self, '_echr_arena_ref', None)
+        return EF.GradSink(arena, params) if arena is not None else None
+
     def _native_params_now(self):
         c = self.core
         a = c.attention
@@ -190,10 +200,9 @@ class OldModel(nn.Module):
         tokens = prepared['tokens'] if prepared is not None else self._tokens(seq, event.device)
         if drop is None:
             drop = self.next_drop_state()
-        arena = getattr(self, '_echr_arena_ref', None)
-        sink = EF.GradSink(arena, self.native_params()) if arena is not None else None
-        return EF.DecoderFunction.apply(video, event, cv.feats, cv.ev_start, cv.ev_len, tokens, cv.max_len, cv.rows_disjoint, drop, sink,
-                                        prepared, self._initial_state(video, event, cv), cv.grad_src, cv.grad_col0, *self.native_params())
+        ps = self.native_params()
+        return EF.DecoderFunction.apply(video, event, cv.feats, cv.ev_start, cv.ev_len, tokens, cv.max_len, cv.rows_disjoint, drop,
+                                        self._grad_sink(ps), prepared, self._initial_state(video, event, cv), cv.grad_src, cv.grad_col0, None, *ps)
 
     def _initial_state(self, video, event, cv):
         """None (the recipe: zero state) or h0 [N, 3H] = init_linear(cat([video | event | clip.mean(1)])) (OldModel_NEW.py:79-92) -- the decoder
@@ -201,10 +210,9 @@ class OldModel(nn.Module):
         if not self.CG_init_feats_dim:
             return None
         t = self.CG_init_feats_type
-        arena = getattr(self, '_echr_arena_ref', None)
-        sink = EF.GradSink(arena, (self.init_linear.weight, self.init_linear.bias)) if arena is not None else None
-        return EF.InitState.apply(video, event, cv.feats, cv.ev_start, cv.ev_len, cv.max_len, ('V' in t, 'E' in t, 'C' in t), sink,
-                                  self.init_linear.weight, self.init_linear.bias)
+        w, b = self.init_linear.weight, self.init_linear.bias
+        return EF.InitState.apply(video, event, cv.feats, cv.ev_start, cv.ev_len, cv.max_len, None, ('V' in t, 'E' in t, 'C' in t),
+                                  self._grad_sink((w, b)), w, b)
 
     def init_hidden(self, video, event, clip, clip_mask=None):
         """Initial state (h, c), each [3,N,H] (OldModel_NEW.py:72-96): zeros, or -- with CG_init_feats_type -- the init_linear map for both."""
@@ -238,8 +246,7 @@ class OldModel(nn.Module):
         result's token log-probs (<eos> included)."""
         beam = int(opt.get('beam_size', 1))
         if beam != 1:
-            if not 1 <= beam <= min(EF.BEAM_MAX, self.vocab_size + 1):
-                raise ValueError('beam_size must be in [1, %d], got %d' % (min(EF.BEAM_MAX, self.vocab_size + 1), beam))
+            EF._check_beam_size(beam, self.vocab_size + 1)
             if opt.get('sample_max', 1) != 1:
                 raise ValueError('beam search decodes by score: it does not combine with sample_max = 0')
             if self.training:
@@ -253,11 +260,9 @@ class OldModel(nn.Module):
         multinomial = opt.get('sample_max', 1) != 1
         seed = self._sample_seed() if multinomial else 0
         with torch.no_grad():
-            if '_sample_tables' not in self.__dict__:
-                self._sample_tables = {}          # decoding operands derived from the parameters alone, reused across calls (EF.greedy_sample)
             return EF.greedy_sample(video, event, cv.feats, cv.ev_start, cv.ev_len, cv.max_len, self.seq_length,
                                     self.native_params(), multinomial=multinomial, temperature=float(opt.get('temperature', 1.0)),
-                                    seed=seed, table_cache=self._sample_tables, h0=self._initial_state(video, event, cv))
+                                    seed=seed, table_cache=self.sample_tables(), h0=self._initial_state(video, event, cv))
 
 
     def _sample_seed(self):

@@ -158,7 +158,7 @@ def _run_kernels(k, use, seed=11):
     t = lambda x, g=False: torch.from_numpy(x).to(dev).requires_grad_(g)
     video, event, wt, bt = t(k['video'], True), t(k['event'], True), t(w, True), t(b, True)
     args = (t(k['c3d']), t(k['ev_start']), t(k['ev_len']), t(k['vid']))
-    h0 = EF.InitStateBatch.apply(video, event, *args, use, None, wt, bt)
+    h0 = EF.InitState.apply(video, event, *args[:3], 0, args[3], use, None, wt, bt)
     vlen = h0.grad_fn.video_len.cpu().numpy() if use[2] else None          # the padded clip lengths the device formed ('C' only)
     h0.backward(t(g_h0))
     torch.cuda.synchronize()
@@ -209,8 +209,8 @@ def test_one_video_batch_is_bit_equal_to_the_single_video_entry():
     t = lambda x: torch.from_numpy(x).to(dev)
     use = (True, True, True)
     with torch.no_grad():
-        one = EF.InitState.apply(t(k['video'][0]), t(k['event']), t(k['c3d']), t(k['ev_start']), t(k['ev_len']), int(k['ev_len'].max()), use, None, w, b)
-        bat = EF.InitStateBatch.apply(t(k['video']), t(k['event']), t(k['c3d']), t(k['ev_start']), t(k['ev_len']), t(k['vid']), use, None, w, b)
+        one = EF.InitState.apply(t(k['video'][0]), t(k['event']), t(k['c3d']), t(k['ev_start']), t(k['ev_len']), int(k['ev_len'].max()), None, use, None, w, b)
+        bat = EF.InitState.apply(t(k['video']), t(k['event']), t(k['c3d']), t(k['ev_start']), t(k['ev_len']), 0, t(k['vid']), use, None, w, b)
     assert torch.equal(one, bat)
 
 

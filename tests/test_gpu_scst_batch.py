@@ -214,8 +214,8 @@ def test_batched_sampled_decode_equals_teacher_forced_recompute(case):
         N, T = gen.shape
         labels = torch.zeros(N, T + 2, dtype=torch.int64, device=gen.device)
         labels[:, 1:T + 1] = gen
-        logp = EF.DecoderBatchFunction.apply(video, event, b.c3d, ev_start, ev_len, lm._tokens(labels, b.device), A, EF.rows_disjoint(b.soi), drop,
-                                             None, vid, *lm.native_params())
+        logp = EF.DecoderFunction.apply(video, event, b.c3d, ev_start, ev_len, lm._tokens(labels, b.device), A, EF.rows_disjoint(b.soi), drop,
+                                        None, None, None, None, 0, vid, *lm.native_params())
         tf = EF.GatherTokens.apply(logp, gen)
     assert torch.equal(gen, gen2) and torch.equal(slp, slp2) and np.array_equal(vw, vw2)
     g = gen.cpu().numpy()
