@@ -349,10 +349,9 @@ __device__ __forceinline__ float tap_bce_mean(const float* __restrict__ part, lo
 __device__ __forceinline__ float tap_bce_grad(float sc, float m, float lb, float w1k, float g, float T) {
     const float y = lb * m, p = sc * m;
     const float w = y * (1.f - w1k) + (1.f - y) * w1k;
-    // d/dp of -(y log p + (1-y) log(1-p)) with torch's clamp: the clamped branch has zero slope
-    float d = 0.f;
-    if (logf(p) > -100.f) d -= y / p;
-    if (logf(1.f - p) > -100.f) d += (1.f - y) / (1.f - p);
+    // torch's BCELoss backward: (p - y) / max(p (1 - p), 1e-12).  The -100 clamp of the forward's logs has no part in it: at p = 0 or 1 the
+    // floor of the denominator bounds the slope (|d| <= 1e12) and a correctly saturated element (p = y) gets exactly 0
+    const float d = (p - y) / fmaxf(p * (1.f - p), 1e-12f);
     return g * w * d * m / T;
 }
 __global__ __launch_bounds__(256) void tap_bce_part_kernel(const float* __restrict__ scores, const float* __restrict__ masks,

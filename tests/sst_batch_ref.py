@@ -49,20 +49,30 @@ def module(params, D, H, K, train, p=0.5):
     return m
 
 
-def run(params, x, wt, ws, ro, train, p=0.5):
-    """The oracle once per video: dict(tap [T_tot, H], scores [T_tot, K], grads {name: summed gradient})."""
+def run(params, x, wt, ws, ro, train, p=0.5, dtype=None, loss=None):
+    """The oracle once per video: dict(tap [T_tot, H], scores [T_tot, K], grads {name: summed gradient}, loss = the videos' sum).
+    dtype=torch.float64: the same float32 inputs (and the same dropout mask) carried through the oracle in double precision.
+    loss(v, a, b, tap, scores) -> video v's scalar (rows a..b of the batch), or (scalar to differentiate, scalar to report); None: the weighted
+    sums (tap * wt).sum() + (scores * ws).sum()."""
     from echr_amd import philox
+    cast = (lambda t: t) if dtype is None else (lambda t: t.to(dtype))
     H = params['rnn.weight_hh_l0'].shape[1]
     T = ro[-1]
     mask = torch.from_numpy(philox.scale_mask((T, H), p, U.SEED, U.OFFSET, philox.SITE_SST, 0)) if train else None
-    P = {k: torch.from_numpy(v.copy()).requires_grad_(True) for k, v in params.items()}
-    taps, scs = [], []
-    for a, b in zip(ro[:-1], ro[1:]):
-        tap, sc = O.sst_forward(P, torch.from_numpy(x[a:b]), mask[a:b].contiguous() if mask is not None else None)
-        ((tap * torch.from_numpy(wt[a:b])).sum() + (sc * torch.from_numpy(ws[a:b])).sum()).backward()          # .grad accumulates: the sum
+    P = {k: cast(torch.from_numpy(v.copy())).requires_grad_(True) for k, v in params.items()}
+    taps, scs, total = [], [], 0.0
+    for v, (a, b) in enumerate(zip(ro[:-1], ro[1:])):
+        tap, sc = O.sst_forward(P, cast(torch.from_numpy(x[a:b])), cast(mask[a:b].contiguous()) if mask is not None else None)
+        if loss is None:
+            l = (tap * cast(torch.from_numpy(wt[a:b]))).sum() + (sc * cast(torch.from_numpy(ws[a:b]))).sum()
+        else:
+            l = loss(v, a, b, tap, sc)
+        l, rep = l if isinstance(l, tuple) else (l, l)
+        l.backward()          # .grad accumulates: the sum
+        total += float(rep.detach())
         taps.append(tap.detach().numpy())
         scs.append(sc.detach().numpy())
-    return dict(tap=np.concatenate(taps, 0), scores=np.concatenate(scs, 0), grads={k: P[k].grad.numpy() for k in NAMES})
+    return dict(tap=np.concatenate(taps, 0), scores=np.concatenate(scs, 0), grads={k: P[k].grad.numpy() for k in NAMES}, loss=total)
 
 
 def gpu_pass(m, x, wt, ws, ro):

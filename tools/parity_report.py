@@ -4,7 +4,11 @@
 present, the HIP path against the same float64 oracle beside it, persistent and launch-per-phase (the table of tests/test_gpu_attention_regime.py).
 
 --tsrm: the event encoder's route cases (tests/tsrm_ref.py) -- e_ref per case as the lines of E_REF in tests/test_gpu_tsrm_routes.py and, when a GPU is
-present, the HIP path's errors beside them."""
+present, the HIP path's errors beside them.
+
+--sst: the proposal encoder's trained-regime variants (tests/proposal_regime_ref.py) -- e_ref per variant, mode and one video / batch (the E_REF table
+of tests/test_gpu_proposal_regime.py holds the largest of each column) and, when a GPU is present, the HIP path against the same float64 oracle beside
+it, persistent and wavefront."""
 import sys, os; sys.path.insert(0, os.environ.get('GRAFT_REPO_ROOT', '/root/repo')); sys.path.insert(0, os.path.join(os.environ.get('GRAFT_REPO_ROOT', '/root/repo'), 'tests'))
 import numpy as np, torch
 import util as U
@@ -57,6 +61,24 @@ def tsrm_report():
         print(line, flush=True)
 
 
+def sst_report():
+    from tests import proposal_regime_ref as P
+    gpu = torch.cuda.is_available()
+    if gpu:
+        from tests import test_gpu_proposal_regime as T
+    fmt = 'tap %.1e scores %.1e loss %.1e grad %.1e (%s)'
+    for name in P.VARIANTS:
+        for batch in (False, True):
+            for train in (False, True):
+                line = '%-10s %s %s  e_ref: ' % (name, 'batch' if batch else 'video', 'train' if train else 'eval ') + fmt % P.e_ref(name, train, batch)
+                for persist in ((1, 0) if gpu and P.VARIANTS[name]['H'] == 512 else (0,) if gpu else ()):
+                    line += ' | HIP %s: ' % ('persistent' if persist else 'wavefront') + fmt % P.errors(T._route(name, train, batch, persist), P.oracle64(name, train, batch))
+                print(line, flush=True)
+
+
+if '--sst' in sys.argv:
+    sst_report()
+    sys.exit(0)
 if '--tsrm' in sys.argv:
     tsrm_report()
     sys.exit(0)
