@@ -127,6 +127,12 @@ class SstBatch(C.Structure):          # echr_sst_batch: the video axis of the pr
     _fields_ = [('n_videos', i32), ('row_offset', c_f), ('row_offset_host', C.c_void_p)]
 
 
+class CiderdArgs(C.Structure):        # echr_ciderd_args
+    _fields_ = [('N', i32), ('L', i32), ('cand', c_f), ('cand_i32', i32), ('T', i32), ('ld', i64), ('cs', i64), ('counts', c_f),
+                ('refs', c_f), ('ref_len', c_f), ('ref_offset', c_f), ('R_tot', i32), ('n_keys', i32), ('keys', c_f), ('idf', c_f),
+                ('idf_unseen', C.c_double), ('base', c_f), ('weight', f32), ('out', c_f)]
+
+
 # every symbol include/echr_hip.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ('echr_version', i32, []),
@@ -234,12 +240,14 @@ SYMBOLS = [
     ('echr_clamp', i32, [c_f, i64, f32, C.c_void_p]),
     ('echr_clamp_adam', i32, [c_f, c_f, c_f, c_f, i64, i32, C.c_double, C.c_double, C.c_double, C.c_double, f32, C.c_void_p]),
     ('echr_clamp_adam_counted', i32, [c_f, c_f, c_f, c_f, i64, i32, C.c_double, C.c_double, C.c_double, C.c_double, f32, c_f, C.c_void_p]),
+    ('echr_ciderd_score', i32, [C.POINTER(CiderdArgs), C.c_void_p]),
 ]
 
 ABI_STRUCTS = {'echr_gemm_desc': GemmDesc, 'echr_dropout': Dropout, 'echr_tsrm_args': TsrmArgs, 'echr_tsrm_grads': TsrmGrads,
                'echr_dec_args': DecArgs, 'echr_dec_grads': DecGrads, 'echr_sample_args': SampleArgs, 'echr_sst_args': SstArgs,
                'echr_sst_grads': SstGrads, 'echr_train_step_args': TrainStepArgs, 'echr_init_state_args': InitStateArgs, 'echr_init_state_grads': InitStateGrads,
-               'echr_beam_args': BeamArgs, 'echr_row_grad_args': RowGradArgs, 'echr_clip_step_args': ClipStepArgs, 'echr_batch_ext': BatchExt, 'echr_sst_batch': SstBatch}
+               'echr_beam_args': BeamArgs, 'echr_row_grad_args': RowGradArgs, 'echr_clip_step_args': ClipStepArgs, 'echr_batch_ext': BatchExt, 'echr_sst_batch': SstBatch,
+               'echr_ciderd_args': CiderdArgs}
 
 ABI_VERSION = 3          # include/echr_hip.h ECHR_ABI_VERSION
 _lib = None

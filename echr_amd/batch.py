@@ -48,10 +48,13 @@ class VideoBatch(object):
       clip_context_type, clip_parts     the frame-level context the batch was built for: 1 = 'CC' (default), 2 = 'CH', 3 = 'CC+CH';
                                         clip_rows() is the decoder's row source -- c3d, tap or [c3d | tap]
       CG_init_feats_type                the initial decoder state the batch was built for ('' = zeros, else from 'V', 'E', 'C')
+      refs                              optional, set by the caller: the packed references of the N_tot events in row order
+                                        (echr_amd.reward.pack_refs) -- what fused.SelfCriticalBatchStep scores a CiderDReward against
     """
 
     def __init__(self, c3d, tap, lda, row_offset, event_offset, soi, ind, labels=None, masks=None, *, CG_init_feats_type='', clip_context_type='CC'):
         self.c3d, self.tap, self.lda = c3d, tap, lda
+        self.refs = None
         self.CG_init_feats_type = str(CG_init_feats_type or '')
         if set(self.CG_init_feats_type) - set('VEC') or len(set(self.CG_init_feats_type)) != len(self.CG_init_feats_type):
             raise ValueError("CG_init_feats_type=%r: the initial state reads 'V', 'E' and / or 'C', each at most once" % (CG_init_feats_type,))

@@ -381,3 +381,17 @@ def reranking(vid_info):
     scores = np.sort(np.array([v['re_score'] for v in vid_info]))
     threshold = scores[-min(len(scores), 10)]
     return [v for v in vid_info if v['re_score'] >= threshold]
+
+
+def ciderd_of(extras_or_seq, scorer, refs):
+    """Mean CIDEr-D (a float; echr_amd.reward.CiderD.score) of the captions of a `caption_video` / `caption_videos`
+    result -- its `extras` dict (the batch's 'seq') or the seq [N, T] itself -- against `refs`, the packed references of the N caption rows
+    in row order (echr_amd.reward.pack_refs).  A result without captions ([] / None: every row emitted <eos> first) scores the empty
+    captions.  A validation score with nothing installed; one host read."""
+    seq = extras_or_seq.get('seq') if isinstance(extras_or_seq, dict) else extras_or_seq
+    width = None
+    if not isinstance(seq, torch.Tensor) or seq.numel() == 0:
+        n = torch.as_tensor(refs[2]).numel() - 1
+        scorer.cuda()
+        seq, width = torch.zeros(n, 1, dtype=torch.int64, device=scorer.device), 0
+    return float(scorer.score(seq, refs, width=width).mean().cpu())

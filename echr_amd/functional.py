@@ -715,6 +715,9 @@ def _sample(video, event, c3d, ev_start, ev_len, A, seq_length, params, h0, vid,
             raise L.EchrHipError('decoder_sample_train_batch: widths %s disagree with the unfinished counts %s'
                                  % (vw.tolist(), host[:seq_length + 1].tolist()))
         return _cut(seq, slp, T) + (vw[:V],)
+    # a deferred decode's uncut output for work queued ahead of the host read (echr_amd.reward): seq [N, seq_length] is written up to the
+    # stop step only, counts[:seq_length + 1] is n_unfinished
+    finish.seq, finish.counts = seq, counts
     return finish if defer else finish()
 
 

@@ -18,6 +18,7 @@ import torch
 
 from . import _lib as L
 from . import functional as EF
+from . import reward as RW
 from .models.OldModel_NEW import n_decoder_steps
 from .optim import ClampAdam
 
@@ -529,14 +530,19 @@ class SelfCriticalStep(object):
         raise NotImplementedError('SelfCriticalStep takes one video per call: self-critical training over a VideoBatch is '
                                   'SelfCriticalBatchStep(fused)(batch) (the module path: CaptionGenerator.train_rl_batch)')
 
-    def __call__(self, tap_feats, c3d_feats, lda_feats, ind_select_list, soi_select_list, gen_result=None, reward=None, step=True):
+    def __call__(self, tap_feats, c3d_feats, lda_feats, ind_select_list, soi_select_list, gen_result=None, reward=None, step=True, refs=None):
         """Returns (loss 0-d device tensor, gen_result [N,T] int64 host, greedy_res [N,T'] int64 host, reward [N,T] fp32 host).
         `gen_result` (optional): score these captions instead of drawing them (tests pin the sample this way); `reward` (optional): use
-        it instead of calling reward_fn.  step=False stops after the backward pass (gradients as `.grad` views, as FusedTrainStep)."""
+        it instead of calling reward_fn.  step=False stops after the backward pass (gradients as `.grad` views, as FusedTrainStep).
+        `refs` (with an echr_amd.reward.CiderDReward as reward_fn): the packed references of the events in row order -- the reward is
+        then scored on the device behind the greedy decode and read behind the greedy decode's own stream drain."""
         f = self.fused
         m = f.model
         lm = m.lm_model
+        on_device = RW.check_reward_refs(self.reward_fn, refs, reward)
         f._begin('self_critical_step')
+        if on_device:          # (uploads, if any, ahead of everything the iteration queues)
+            refs = self.reward_fn.scorer.to(c3d_feats.device).device_refs(refs)
         drop = lm.next_drop_state(m.fusion_model.enc_attn.dropout.p)
         drop.training = m.training
         with torch.no_grad():
@@ -549,10 +555,17 @@ class SelfCriticalStep(object):
                 gen, _ = lm.sample_train(video, event, clip, clip_mask, drop)
             else:
                 gen = torch.as_tensor(gen_result).to(dtype=torch.int64)
+            gen_d = gen.to(c3d_feats.device) if on_device and isinstance(gen, torch.Tensor) else None
             was_training = lm.training
             lm.eval()
             try:
-                greedy, _ = lm.sample(video, event, clip, clip_mask)
+                if on_device:
+                    greedy_f = lm.sample(video, event, clip, clip_mask, {'defer': True})
+                    if gen_d is not None and gen_d.shape[1] > 0:          # gen at its own width, the greedy decode at its device counts
+                        reward = self.reward_fn(gen_d, greedy_f.seq, refs, greedy_counts=greedy_f.counts)
+                    greedy, _ = greedy_f()
+                else:
+                    greedy, _ = lm.sample(video, event, clip, clip_mask)
             finally:
                 lm.train(was_training)
         # the one host sync of the iteration (the greedy decode's own counter read has already drained the stream)
@@ -611,20 +624,32 @@ class SelfCriticalBatchStep(object):
         """Returns (loss 0-d device tensor, gen_result [N_tot,T] int64 host, greedy_res [N_tot,T'] int64 host, reward [N_tot,T] fp32 host,
         video_words int64 [V] host); T = max(video_words).  `gen_result` [N_tot, >= T]: score these captions instead of drawing them;
         `reward` ([N_tot,T] or [N_tot]): use it instead of calling reward_fn.  step=False stops after the backward pass (the summed
-        gradients as `.grad` views).  The batch need not carry labels.  Raises ValueError when every video's sample has width 0."""
-        return self._run(batch, gen_result, reward, step, False, None)
+        gradients as `.grad` views).  The batch need not carry labels.  Raises ValueError when every video's sample has width 0.
+        With an echr_amd.reward.CiderDReward as reward_fn the references travel with the batch: `batch.refs`, the packed references of its
+        events in row order (echr_amd.reward.pack_refs).  Both decodes are then scored on the device (their uncut sequences and device
+        counts) ahead of the iteration's one host read, and the [N_tot] reward is read behind the same stream drain; a video whose sample
+        has width 0 gets reward 0, as with a callable.  A CiderDReward without batch.refs is a ValueError, batch.refs with a plain
+        callable a TypeError."""
+        return self._run(batch, gen_result, reward, step, False, None, batch.refs)
 
-    def handover(self, batch, handover_cb=None, gen_result=None, reward=None):
-        """__call__(step=False) with the data-parallel hand-over points recorded, as FusedTrainStep.batch_handover (DataParallelBatchStep)."""
-        return self._run(batch, gen_result, reward, False, True, handover_cb)
+    def handover(self, batch, handover_cb=None, gen_result=None, reward=None, refs=None):
+        """__call__(step=False) with the data-parallel hand-over points recorded, as FusedTrainStep.batch_handover (DataParallelBatchStep).
+        `refs`: instead of batch.refs."""
+        return self._run(batch, gen_result, reward, False, True, handover_cb, batch.refs if refs is None else refs)
 
-    def _run(self, batch, gen_result, reward, step, handover, handover_cb):
+    def _run(self, batch, gen_result, reward, step, handover, handover_cb, refs=None):
         f = self.fused
         m = f.model
         lm = m.lm_model
         m._check_batch_options(batch)          # (ahead of everything that touches the device)
+        on_device = RW.check_reward_refs(self.reward_fn, refs, reward)
         f._begin('self_critical_batch_step', 'a batch step')
         N, V = batch.n_events, batch.n_videos
+        gen_d = r_dev = None
+        if on_device:          # (uploads ahead of everything the iteration queues: a host-to-device copy waits for the stream)
+            refs = self.reward_fn.scorer.to(f.dev).device_refs(refs)
+            if gen_result is not None:
+                gen_d = torch.as_tensor(gen_result).to(f.dev)
         with torch.no_grad():
             video, event, ev_start, ev_len, A, vid, drop = m._batch_contexts(batch, None)
             video = EF._f32c(video)
@@ -638,6 +663,11 @@ class SelfCriticalBatchStep(object):
                                                 seed=lm._sample_seed(), defer=True, h0=h0)
             greedy_f = EF.greedy_sample(video, event, batch.clip_rows(), ev_start, ev_len, A, lm.seq_length, ps, table_cache=lm.sample_tables(),
                                         vid=vid, defer=True, h0=h0)
+            if on_device:          # queued behind both decodes, ahead of the read; a pinned gen_result is scored at its own width
+                if sampled is not None:
+                    r_dev = self.reward_fn(sampled.seq, greedy_f.seq, refs, gen_counts=sampled.counts, greedy_counts=greedy_f.counts)
+                else:
+                    r_dev = self.reward_fn(gen_d, greedy_f.seq, refs, gen_width=min(gen_d.shape[1], lm.seq_length), greedy_counts=greedy_f.counts)
             # the one host sync of the iteration: the first read drains the stream, both decodes included
             if sampled is not None:
                 gen, _, vw = sampled()
@@ -651,7 +681,12 @@ class SelfCriticalBatchStep(object):
         T = int(vw.max())
         if T == 0:
             raise ValueError('every caption drew <eos> at its first step: nothing to train on (OldModel.sample returns [] then)')
-        if reward is None:
+        if r_dev is not None:
+            r1 = r_dev.cpu().numpy()          # (the stream is drained: a copy of N_tot floats)
+            r = np.zeros((N, T), dtype=np.float32)
+            for s, wv in zip(batch.event_slices, vw.tolist()):
+                r[s, :wv] = r1[s, None]
+        elif reward is None:
             if self.reward_fn is None:
                 raise ValueError('SelfCriticalBatchStep needs reward_fn or an explicit reward')
             gw = batch.caption_widths(greedy_h)

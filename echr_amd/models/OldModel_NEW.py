@@ -243,7 +243,8 @@ class OldModel(nn.Module):
         beam_size = B > 1 (the reference's `--beam_size`, whose beam branch is commented out there): beam search on device
         (functional.beam_search), eval mode and sample_max = 1 only.  Returns (seq, logp) like the greedy decode; logp is 0 after a row's
         <eos> where the greedy decode keeps the raw arg-max log-probs.  opt['return_score'] = True appends score [N], the sum of each
-        result's token log-probs (<eos> included)."""
+        result's token log-probs (<eos> included).  opt['defer'] = True (beam_size 1): the decode is queued and EF.greedy_sample's deferred
+        handle is returned instead of the result."""
         beam = int(opt.get('beam_size', 1))
         if beam != 1:
             EF._check_beam_size(beam, self.vocab_size + 1)
@@ -262,7 +263,8 @@ class OldModel(nn.Module):
         with torch.no_grad():
             return EF.greedy_sample(video, event, cv.feats, cv.ev_start, cv.ev_len, cv.max_len, self.seq_length,
                                     self.native_params(), multinomial=multinomial, temperature=float(opt.get('temperature', 1.0)),
-                                    seed=seed, table_cache=self.sample_tables(), h0=self._initial_state(video, event, cv))
+                                    seed=seed, table_cache=self.sample_tables(), h0=self._initial_state(video, event, cv),
+                                    defer=bool(opt.get('defer', False)))
 
 
     def _sample_seed(self):

@@ -33,7 +33,7 @@ batch form, JointBatchStep with `--joint`, SelfCriticalBatchStep with `--self_cr
 ranks, one clamp + Adam per model, identical on every rank.  `--dist_backend gloo` with fewer devices than ranks is the one-GPU rehearsal:
 every rank on cuda:0, launch-per-phase recurrences.  Without a process group nothing changes.
 
-usage: python examples/train_synthetic.py [--iters 20] [--m_batch 2] [--joint] [--pre_tap] [--self_critical] [--save /tmp/echr_ckpt.pth]
+usage: python examples/train_synthetic.py [--iters 20] [--m_batch 2] [--joint] [--pre_tap] [--self_critical [--reward ciderd]] [--save /tmp/echr_ckpt.pth]
                                           [--resume /tmp/echr_ckpt.pth]
 """
 import argparse
@@ -205,6 +205,15 @@ def self_critical(a, opt, dev, loader, tap_model, cg_model, cg_opt, start):
     from echr_amd.batch import VideoBatch
     from echr_amd.fused import FusedTrainStep, SelfCriticalBatchStep, SelfCriticalStep
     fused = FusedTrainStep(cg_model, cg_opt, grad_clip=opt.grad_clip)
+    ciderd = None
+    if a.reward == 'ciderd':
+        # CIDEr-D on the device: the corpus is every synthetic video's labels (one document per event), an event's reference its own label;
+        # the references are packed and uploaded once per video, outside the iterations
+        from echr_amd.reward import CiderD, CiderDReward
+        scorer = CiderD.from_corpus([[lab] for v in loader for lab in np.asarray(v['labels'])], opt.CG_seq_length, opt.CG_vocab_size).to(dev)
+        ciderd = CiderDReward(scorer)
+        packed = {id(v): scorer.pack_refs([[lab] for lab in np.asarray(v['labels'])]).to(dev) for v in loader}
+        one, many = SelfCriticalStep(fused, ciderd), SelfCriticalBatchStep(fused, ciderd)
     history = []
     for it in range(start, start + a.iters):
         vids = [loader[(it * a.m_batch + j) % len(loader)] for j in range(a.m_batch)]
@@ -214,14 +223,26 @@ def self_critical(a, opt, dev, loader, tap_model, cg_model, cg_opt, start):
             c3d, lda = torch.from_numpy(v['c3d']).to(dev), torch.from_numpy(v['lda']).to(dev)
             with torch.no_grad():
                 tap_feats, _ = tap_model(c3d)
-            loss = SelfCriticalStep(fused, overlap_reward(v['labels']))(tap_feats, c3d, lda, v['ind'], v['soi'])[0]
+            if ciderd is not None:
+                loss = one(tap_feats, c3d, lda, v['ind'], v['soi'], refs=packed[id(v)])[0]
+            else:
+                loss = SelfCriticalStep(fused, overlap_reward(v['labels']))(tap_feats, c3d, lda, v['ind'], v['soi'])[0]
         else:
             rewards = [overlap_reward(v['labels']) for v in vids]          # reward_fn is called once per video (step.current_video)
             with torch.no_grad():
                 batch = VideoBatch.from_videos([{k: v[k] for k in ('c3d', 'lda', 'ind', 'soi')} for v in vids], device=dev, tap_model=tap_model,
                                                  clip_context_type=opt.clip_context_type, CG_init_feats_type=opt.CG_init_feats_type)
-            step = SelfCriticalBatchStep(fused, lambda gen, greedy: rewards[step.current_video](gen, greedy))
-            loss = step(batch)[0]
+            if ciderd is not None:          # the batch's references: its videos' packed rows in batch order
+                from echr_amd.reward import PackedRefs
+                parts = [packed[id(v)] for v in vids]
+                base = np.cumsum([0] + [int(p.refs.shape[0]) for p in parts])
+                refs = PackedRefs(torch.cat([p.refs for p in parts]), torch.cat([p.ref_len for p in parts]),
+                                  torch.cat([parts[0].ref_offset[:1]] + [p.ref_offset[1:] + int(o) for p, o in zip(parts, base)]))
+                batch.refs = refs
+                loss = many(batch)[0]
+            else:
+                step = SelfCriticalBatchStep(fused, lambda gen, greedy: rewards[step.current_video](gen, greedy))
+                loss = step(batch)[0]
         history.append(float(loss) / a.m_batch)
         if not a.quiet and (it % 5 == 0 or it == start + a.iters - 1):
             print('iter %3d  self-critical loss %.4f  (mean of %d videos)' % (it, history[-1], a.m_batch), flush=True)
@@ -236,6 +257,9 @@ def main(argv=None):
     ap.add_argument('--pre_tap', action='store_true', help="'pre_tap' mode: train the proposal encoder alone, m_batch videos per forward_batch call")
     ap.add_argument('--self_critical', action='store_true', help='self-critical training of the captioner: SelfCriticalStep (m_batch = 1) or '
                                                                  'SelfCriticalBatchStep over the m_batch videos as one batch')
+    ap.add_argument('--reward', choices=('overlap', 'ciderd'), default='overlap', help="--self_critical: the host stand-in overlap_reward, or "
+                                                                                       "CIDEr-D scored on the device (echr_amd.reward) against "
+                                                                                       "each event's own label")
     ap.add_argument('--events', type=int, default=16)
     ap.add_argument('--segments', type=int, default=32)
     ap.add_argument('--vocab', type=int, default=500)
@@ -298,6 +322,8 @@ def main(argv=None):
     iters = range(start, start + a.iters)
     if a.self_critical and (a.joint or a.no_fused):
         raise SystemExit('--self_critical trains the captioner on the one-call path: not with --joint / --no-fused')
+    if a.reward == 'ciderd' and (not a.self_critical or dp_batch):
+        raise SystemExit('--reward ciderd goes with --self_critical in one process (the data-parallel driver keeps overlap_reward)')
     if a.self_critical and not dp_batch:
         history, iters = self_critical(a, opt, dev, loader, tap_model, cg_model, cg_opt, start), ()
     if dp_batch:

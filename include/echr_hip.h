@@ -461,6 +461,40 @@ int echr_reward_loss_fwd(const float* input, const int64_t* seq, const float* re
 int echr_reward_loss_bwd(const int64_t* seq, const float* reward, const float* fwd_out, const float* g_loss, float* g_input,
                          int32_t N, int32_t T, void* stream);
 
+/* CIDEr-D over token ids: the reward of self-critical training, score(sampled) - score(greedy), and a validation
+ * metric without external tools.  The sequence of candidate row n under seq_length L is the l tokens before its first 0 among columns
+ * < T (l = T when there is none), then one end token 0 iff l < L; columns >= T are never read.  References arrive in that form already.
+ * For n = 1..4: w(g) = tf(g) * idf(g) over the order-n n-grams g, norm_n = sqrt(sum w^2); against reference r,
+ *   val_n = sum_{g in h} min(w_h(g), w_r(g)) * w_r(g), divided by norm_n(h) * norm_n(r) iff both are non-zero, times
+ *   exp(-(len_h - len_r)^2 / 72)  (sigma = 6; len counts the end token);   score = 10 * mean_n(sum_r val_n) / R.
+ * idf comes from a table of exact keys -- key(g) = sum_i (tok_i + 1) << 16 i, i < n, tokens <= 65534 -- sorted strictly increasing as
+ * uint64, with idf[k] = log(n_docs) - log(max(1, df[k])); an n-gram that is not in the table has idf_unseen = log(n_docs).
+ * All arithmetic is fp64 in one fixed order, one workgroup per row: bitwise reproducible and independent of which rows share a launch.
+ * out[n] = score, or weight * (score - base[n]) when `base` is given (the greedy scores of a previous call: the reward). */
+typedef struct {
+    int32_t N;                   /* candidate rows */
+    int32_t L;                   /* the model's seq_length, 1 .. 63 */
+    const void* cand;            /* [N, >= T] token ids, int64 (cand_i32 = 0) or int32 (1): element (n, t) at n * ld + t * cs */
+    int32_t cand_i32;
+    int32_t T;                   /* the width, 0 .. L; used when counts == NULL */
+    int64_t ld, cs;              /* row and column stride of cand in elements */
+    const int32_t* counts;       /* optional: a decode's n_unfinished [L + 1]; the width is t - 1 for the first t in 1 .. L with
+                                    counts[t] == 0, else L (what the host cuts echr_decoder_sample's output at) */
+    const int32_t* refs;         /* [R_tot, L] reference sequences, zero-padded */
+    const int32_t* ref_len;      /* [R_tot] their lengths, 1 .. L, end token included */
+    const int32_t* ref_offset;   /* [N + 1]: row n is scored against references ref_offset[n] .. ref_offset[n + 1] - 1 (at least one;
+                                    a row without any scores 0) */
+    int32_t R_tot;
+    int32_t n_keys;              /* table entries, 0 = empty */
+    const uint64_t* keys;        /* [n_keys] strictly increasing */
+    const double* idf;           /* [n_keys] */
+    double idf_unseen;
+    const float* base;           /* optional [N] */
+    float weight;                /* with base only */
+    float* out;                  /* [N] */
+} echr_ciderd_args;
+int echr_ciderd_score(const echr_ciderd_args* a, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * SST proposal encoder.  Replaces models/sst_model.py:31-40 (nn.LSTM over one video + Linear + sigmoid)
  * and TAPModelCriterion (misc/utils.py:78-99).  Parameters use nn.LSTM's layout: w_ih[l] [4H, D or H], w_hh[l] [4H,H],
