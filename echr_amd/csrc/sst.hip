@@ -13,14 +13,19 @@
 //   * weight gradients are batched TN GEMMs over the T rows afterwards;
 //   * H = 512: both wavefronts as ONE persistent launch per direction (below).
 // A multi-video BATCH (echr_sst_fwd_batch / echr_sst_bwd_batch; stage 1 of the reference's recipe sums the gradients of m_batch videos,
-// train.py:281-283,313-317) concatenates the videos' rows; every video starts from the zero state:
+// train.py:281-283,313-317) concatenates the videos' rows; every video starts from the zero state.  One video is a batch of one: every
+// entry is a wrapper around ONE sst_forward / sst_backward, which differ between V = 1 and V > 1 only where this list says so:
 //   * everything batched over rows (layer 0's input product, the head, the input-side weight gradients, the bias sums) is the same
 //     launch over T_tot rows;
-//   * the persistent kernels carry a video loop: the register-resident weight slices serve up to SPB_NV videos inside one step, so the
-//     step's memory round trip is paid once per step instead of once per video and step (sst_persist_*_batch_kernel);
-//   * the launch-per-step wavefront puts the videos on blockIdx.z with per-video row bases (sst_wave_*_batch_kernel): T_max + 1 launches;
-//   * the recurrent weight gradients pair dG(t) with a shifted copy of the states that is ZERO at every video's first row, so no pair
-//     crosses a video boundary; the dropout mask is keyed by the batch-global row.
+//   * the persistent form picks its kernel from V: one video runs sst_persist_*_kernel (one-piece sweep), a batch runs groups of up to
+//     SPB_NV videos through sst_persist_*_batch_kernel, whose register-resident weight slices serve the whole group inside one step (the
+//     step's memory round trip is paid once per step instead of once per video and step).  Each is the measured better form on its side
+//     of that choice and keeps its own code, set-up included (shared set-up functions compile to other code: DESIGN.md section 4m);
+//   * the launch-per-step wavefront is one kernel pair: videos on blockIdx.z with per-video row bases (sst_wave_*_batch_kernel), T_max + 1
+//     launches; one video is the (nwg, 2, 1) grid with its length in the parameter block instead of a device offsets array;
+//   * the recurrent weight gradients of a batch pair dG(t) with a shifted copy of the states that is ZERO at every video's first row, so no
+//     pair crosses a video boundary (one video pairs rows 1..T-1 with the states themselves); the dropout mask is keyed by the batch-global
+//     row, which is the timestep when there is one video.
 #include "echr_common.h"
 #include "echr_internal.h"
 #include <algorithm>
@@ -66,10 +71,9 @@ struct SstFwdRole {
     const float* base2;       // [4H] second bias (layer 1: b_hh) or null
     const float* cprev;
     float *act, *hout, *cout, *hdrop;
-    int t, active;
+    int t;
 };
-// one workgroup's share of a role (the single-video and the batched kernel differ only in where the role comes from); r.t is the
-// row that keys the dropout mask: the timestep of a single video, the batch-global row of a batch
+// one workgroup's share of a role; r.t is the row that keys the dropout mask: the batch-global row (the timestep of a single video)
 __device__ __forceinline__ void sst_wave_fwd_body(const SstFwdRole& r, int H, const DropCfg& dc) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     float* sv = sm;                  // [2][H]
@@ -119,23 +123,21 @@ __device__ __forceinline__ void sst_wave_fwd_body(const SstFwdRole& r, int H, co
         if (r.hdrop) r.hdrop[u] = h * drop_mult(dc, (unsigned)(r.t * H + u), 0u, SITE_SST);
     }
 }
-__global__ __launch_bounds__(256) void sst_wave_fwd_kernel(SstFwdRole r0, SstFwdRole r1, int H, DropCfg dc) {
-    const SstFwdRole r = blockIdx.y ? r1 : r0;
-    if (!r.active) return;
-    sst_wave_fwd_body(r, H, dc);
-}
-// the batch's wavefront: blockIdx.z = video.  Launch k runs, for every video that has not ended, layer 0 at step k || layer 1 at step k-1 of
-// THAT video (rows row_offset[v] + t of the concatenated layout); T_max + 1 dependent launches serve the whole batch
+// the wavefront: blockIdx.z = video.  Launch k runs, for every video that has not ended, layer 0 at step k || layer 1 at step k-1 of
+// THAT video (rows row_offset[v] + t of the concatenated layout); T_max + 1 dependent launches serve the whole batch.  The single-video
+// entries have no device offsets: ONE (the host's row_offset = null) is one video of T1 rows from row 0.  A compile-time switch, not a test
+// of the pointer: the test in front of the two offset loads cost the batch's forward 1 % (2.647 -> 2.675 ms at V = 8, T = 256)
 struct SstWaveFB {
     const float *w_hh0, *w_ih1, *w_hh1, *b_ih1, *b_hh1, *GIN0;
     float *HS0, *H0D, *TAP, *ACT0, *ACT1, *CS0, *CS1;
     const int* row_offset;
-    int H, k;
+    int H, k, T1;
 };
+template <bool ONE>
 __global__ __launch_bounds__(256) void sst_wave_fwd_batch_kernel(SstWaveFB p, DropCfg dc) {
     const int v = blockIdx.z, H = p.H, k = p.k;
-    const long base = p.row_offset[v];
-    const int Tv = p.row_offset[v + 1] - (int)base;
+    const long base = ONE ? 0 : p.row_offset[v];
+    const int Tv = ONE ? p.T1 : p.row_offset[v + 1] - (int)base;
     SstFwdRole r{};
     if (blockIdx.y == 0) {
         if (k >= Tv) return;
@@ -169,7 +171,7 @@ struct SstBwdRole {
     const float* dh_base;     // [H] or null
     const float *act, *c, *cprev;
     float *dc, *dg;
-    int drop_first, t, active;
+    int drop_first, t;
 };
 __device__ __forceinline__ void sst_wave_bwd_body(const SstBwdRole& r, int H, const DropCfg& dcfg) {
     static_assert(UPW == 2, "wave -> (unit, matrix) map below assumes two units per workgroup");
@@ -215,23 +217,21 @@ __device__ __forceinline__ void sst_wave_bwd_body(const SstBwdRole& r, int H, co
         r.dc[u] = dcv * gf;
     }
 }
-__global__ __launch_bounds__(256) void sst_wave_bwd_kernel(SstBwdRole r0, SstBwdRole r1, int H, DropCfg dcfg) {
-    const SstBwdRole r = blockIdx.y ? r1 : r0;
-    if (!r.active) return;
-    sst_wave_bwd_body(r, H, dcfg);
-}
-// the batch's reverse wavefront: blockIdx.z = video, every video counts down from ITS OWN last step (launch k = layer 1 at T_v-1-k ||
-// layer 0 at T_v-k) and carries its own d c: DC is [V][2][H]
+// the reverse wavefront: blockIdx.z = video, every video counts down from ITS OWN last step (launch k = layer 1 at T_v-1-k || layer 0 at
+// T_v-k) and carries its own d c: layer l of video v at DCl + v * dc_stride ([V][2][H] for a batch; the two [H] carves of the single-video
+// workspace with one video).  ONE as in the forward
 struct SstWaveBB {
     const float *WT0, *WT1, *WT_IH1, *ACT0, *ACT1, *CS0, *CS1, *DHO;
-    float *DG0, *DG1, *DC;
+    float *DG0, *DG1, *DC0, *DC1;
+    long dc_stride;
     const int* row_offset;
-    int H, k;
+    int H, k, T1;
 };
+template <bool ONE>
 __global__ __launch_bounds__(256) void sst_wave_bwd_batch_kernel(SstWaveBB p, DropCfg dcfg) {
     const int v = blockIdx.z, H = p.H, k = p.k;
-    const long base = p.row_offset[v];
-    const int Tv = p.row_offset[v + 1] - (int)base;
+    const long base = ONE ? 0 : p.row_offset[v];
+    const int Tv = ONE ? p.T1 : p.row_offset[v + 1] - (int)base;
     SstBwdRole r{};
     if (blockIdx.y == 0) {
         const int t = Tv - 1 - k;
@@ -241,7 +241,7 @@ __global__ __launch_bounds__(256) void sst_wave_bwd_batch_kernel(SstWaveBB p, Dr
         r.WT[0] = p.WT1; r.vec[0] = t + 1 < Tv ? p.DG1 + (row + 1) * 4 * H : nullptr;
         r.dh_base = p.DHO + row * H;
         r.act = p.ACT1 + row * 4 * H; r.c = p.CS1 + row * H; r.cprev = t ? p.CS1 + (row - 1) * H : nullptr;
-        r.dc = p.DC + ((long)v * 2 + 1) * H; r.dg = p.DG1 + row * 4 * H;
+        r.dc = p.DC1 + v * p.dc_stride; r.dg = p.DG1 + row * 4 * H;
     } else {
         const int t = Tv - k;
         if (k < 1 || t < 0) return;
@@ -250,7 +250,7 @@ __global__ __launch_bounds__(256) void sst_wave_bwd_batch_kernel(SstWaveBB p, Dr
         r.WT[0] = p.WT_IH1; r.vec[0] = p.DG1 + row * 4 * H;
         r.WT[1] = p.WT0; r.vec[1] = t + 1 < Tv ? p.DG0 + (row + 1) * 4 * H : nullptr;
         r.act = p.ACT0 + row * 4 * H; r.c = p.CS0 + row * H; r.cprev = t ? p.CS0 + (row - 1) * H : nullptr;
-        r.dc = p.DC + (long)v * 2 * H; r.dg = p.DG0 + row * 4 * H;
+        r.dc = p.DC0 + v * p.dc_stride; r.dg = p.DG0 + row * 4 * H;
     }
     sst_wave_bwd_body(r, H, dcfg);
 }
@@ -1183,12 +1183,74 @@ static int sst_persist_launch(K kernel, P& args, const char* what, hipStream_t s
     return check_launch(what);
 }
 
+// what a batch's backward holds behind the single-video workspace
+struct SstWsBB { SstWsB b; float *HP[2], *DCV; long total; };
+static SstWsBB carve_bb(int T, int D, int H, int K, int V, float* base) {
+    SstWsBB w;
+    w.b = carve_b(T, D, H, K, base);
+    long off = w.b.total;
+    auto take = [&](long n) { float* p = base ? base + off : nullptr; off += rup(n, 64); return p; };
+    w.HP[0] = take((long)T * H); w.HP[1] = take((long)T * H);        // h(t-1) per row, zero at video starts (recurrent weight gradients)
+    w.DCV = take((long)V * 2 * H);                                   // wavefront form: d c carried per video and layer
+    w.total = off;
+    return w;
+}
+// a null batch description, or one video in it: the single-video call (no offsets array is read on the device, today's kernels and keys)
+static bool sst_one(const echr_sst_batch* x) { return !x || x->n_videos == 1; }
+// groups of the persistent form: videos ordered by length (longest first, ties by index) and cut into runs of SPB_NV -- a group runs
+// len[0] + 1 steps, so neighbours in length share a launch.  One video is one group of one
+static void sst_groups(const echr_sst_batch* x, int T, std::vector<SstGrp>& out) {
+    if (sst_one(x)) {
+        SstGrp g{};
+        g.nv = 1; g.len[0] = T;
+        out.push_back(g);
+        return;
+    }
+    const int V = x->n_videos;
+    std::vector<int> order(V);
+    for (int v = 0; v < V; ++v) order[v] = v;
+    const int32_t* ro = x->row_offset_host;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return ro[a + 1] - ro[a] > ro[b + 1] - ro[b]; });
+    for (int s = 0; s < V; s += SPB_NV) {
+        SstGrp g{};
+        g.nv = std::min(SPB_NV, V - s);
+        for (int i = 0; i < g.nv; ++i) { g.base[i] = ro[order[s + i]]; g.len[i] = ro[order[s + i] + 1] - ro[order[s + i]]; }
+        out.push_back(g);
+    }
+}
+static int sst_tmax(const echr_sst_batch* x, int T) {
+    if (sst_one(x)) return T;
+    int m = 0;
+    for (int v = 0; v < x->n_videos; ++v) m = std::max(m, (int)(x->row_offset_host[v + 1] - x->row_offset_host[v]));
+    return m;
+}
+// the persistent kernels' parameter blocks for a launch of T + 1 steps (stamps off)
+static SstPF sst_pf(const echr_sst_args* a, const SstWs& w, const DropCfg& dc, int T) {
+    SstPF P;
+    P.T = T; P.w_hh0 = a->w_hh[0]; P.w_ih1 = a->w_ih[1]; P.w_hh1 = a->w_hh[1]; P.b_ih1 = a->b_ih[1]; P.b_hh1 = a->b_hh[1]; P.GIN0 = w.GIN0;
+    P.HS0 = w.HS[0]; P.H0D = w.H0D; P.TAP = a->tap_feats; P.ACT0 = w.ACT[0]; P.ACT1 = w.ACT[1]; P.CS0 = w.CS[0]; P.CS1 = w.CS[1];
+    P.y = sst_sync(); P.dc = dc; P.stamps = nullptr;
+    return P;
+}
+static SstPB sst_pb(const echr_sst_args* a, const SstWs& w, const SstWsB& b, const DropCfg& dc, int T) {
+    SstPB P;
+    P.T = T; P.w_hh0 = a->w_hh[0]; P.w_ih1 = a->w_ih[1]; P.w_hh1 = a->w_hh[1];
+    P.ACT0 = w.ACT[0]; P.ACT1 = w.ACT[1]; P.CS0 = w.CS[0]; P.CS1 = w.CS[1]; P.DHO = b.DHO; P.DG0 = b.DG[0]; P.DG1 = b.DG[1];
+    P.y = sst_sync(); P.dc = dc; P.stamps = nullptr;
+    return P;
+}
+
 }  // namespace echr
 
 using namespace echr;
 
 extern "C" int64_t echr_sst_ws_floats(int32_t T, int32_t D, int32_t H, int32_t K) { return carve(T, D, H, K, nullptr).total; }
 extern "C" int64_t echr_sst_ws_bwd_floats(int32_t T, int32_t D, int32_t H, int32_t K) { return carve_b(T, D, H, K, nullptr).total; }
+extern "C" int echr_sst_batch_group(void) { return SPB_NV; }
+extern "C" int64_t echr_sst_batch_ws_floats(int32_t T, int32_t D, int32_t H, int32_t K, int32_t V) { (void)V; return carve(T, D, H, K, nullptr).total; }
+extern "C" int64_t echr_sst_batch_ws_bwd_floats(int32_t T, int32_t D, int32_t H, int32_t K, int32_t V) {
+    return carve_bb(T, D, H, K, V > 0 ? V : 1, nullptr).total;
+}
 
 static int sst_check(const echr_sst_args* a, const char* who) {
     ECHR_REQUIRE(a, "%s: null args", who);
@@ -1198,71 +1260,19 @@ static int sst_check(const echr_sst_args* a, const char* who) {
     ECHR_REQUIRE(a->w_sc && a->b_sc, "%s: missing head parameters", who);
     return 0;
 }
+static int sst_batch_check(const echr_sst_args* a, const echr_sst_batch* x, const char* who) {
+    RC(sst_check(a, who));
+    ECHR_REQUIRE(x && x->n_videos >= 1 && x->n_videos <= 65535 && x->row_offset && x->row_offset_host, "%s: missing batch description (1..65535 videos)", who);
+    ECHR_REQUIRE(x->row_offset_host[0] == 0 && x->row_offset_host[x->n_videos] == a->T, "%s: row_offset must run from 0 to T_tot = %d", who, a->T);
+    for (int v = 0; v < x->n_videos; ++v)
+        ECHR_REQUIRE(x->row_offset_host[v + 1] > x->row_offset_host[v], "%s: video %d has no row", who, v);
+    ECHR_REQUIRE((long)a->T * a->H < (1l << 31), "%s: T_tot * H must stay below 2^31 (dropout keys)", who);
+    return 0;
+}
 
-static int sst_head_impl(const echr_sst_args* a, hipStream_t st);
-static int sst_fwd_impl(const echr_sst_args* a, const echr_dropout* drop, void* stream, bool with_head);
-extern "C" int echr_sst_fwd(const echr_sst_args* a, const echr_dropout* drop, void* stream) { return sst_fwd_impl(a, drop, stream, true); }
-// the two halves of echr_sst_fwd on their own (joint iteration: the caption side waits for tap_feats alone, so its caller queues the proposal
-// head -- scores = sigmoid(tap_feats . W_sc^T + b_sc), models/sst_model.py:38-39 -- BEHIND the caption call instead of in front of it)
-extern "C" int echr_sst_fwd_states(const echr_sst_args* a, const echr_dropout* drop, void* stream) { return sst_fwd_impl(a, drop, stream, false); }
-extern "C" int echr_sst_head_fwd(const echr_sst_args* a, void* stream) {
-    RC(sst_check(a, "sst_head_fwd"));
-    return sst_head_impl(a, (hipStream_t)stream);
-}
-static int sst_fwd_impl(const echr_sst_args* a, const echr_dropout* drop, void* stream, bool with_head) {
-    RC(sst_check(a, "sst_fwd"));
-    hipStream_t st = (hipStream_t)stream;
-    const int T = a->T, D = a->D, H = a->H, K = a->K;
-    SstWs w = carve(T, D, H, K, a->ws);
-    const DropCfg dc = make_drop(drop, a->p_drop);
-    const int nwg = (H + UPW - 1) / UPW;
-    // layer 0's input-side pre-activations for all T rows: X . W_ih0^T + b_ih0 + b_hh0 (batched MFMA GEMM)
-    echr_gemm_desc d0 = desc_nt(a->x, D, a->w_ih[0], D, w.GIN0, 4 * H, T, 4 * H, D);
-    d0.bias = a->b_ih[0]; d0.bias2 = a->b_hh[0]; d0.split_k = T >= 128 ? 1 : -1;      // T x 4H output tiles fill the chip from T = 128 on: no split, no zero fill
-    RC(gemm(d0, st));
-    if (sst_persist_ok(H)) {
-        RC(persist_check_async());
-        // exchange rows = saved activations: sentinel-fill h0 | h0d (adjacent) and the output rows h1 = tap_feats, then ONE launch
-        if (hipMemsetAsync(w.HS[0], 0xFF, sizeof(float) * (size_t)((w.H0D - w.HS[0]) + (long)T * H), st) != hipSuccess ||
-            hipMemsetAsync(a->tap_feats, 0xFF, sizeof(float) * (size_t)T * H, st) != hipSuccess) { set_error("sst_fwd: memset failed"); return -5; }
-        SstPF P;
-        P.T = T; P.w_hh0 = a->w_hh[0]; P.w_ih1 = a->w_ih[1]; P.w_hh1 = a->w_hh[1]; P.b_ih1 = a->b_ih[1]; P.b_hh1 = a->b_hh[1]; P.GIN0 = w.GIN0;
-        P.HS0 = w.HS[0]; P.H0D = w.H0D; P.TAP = a->tap_feats; P.ACT0 = w.ACT[0]; P.ACT1 = w.ACT[1]; P.CS0 = w.CS[0]; P.CS1 = w.CS[1];
-        P.y = sst_sync(); P.dc = dc;
-        P.stamps = config().persist_stamps == 3 ? persist_stamp_buffer(T + 1, st) : nullptr;
-        // algorithmic bytes: the three recurrent matrices once + per step the pre-activation row in and gates / cells / outputs of both layers out
-        ProfScope prof(PROF_SST, 2.0 * T * 3.0 * 4 * H * H, 4.0 * (3.0 * 4 * H * H + (double)T * (4.0 * H + 2 * (4.0 * H + 2.0 * H) + H)), st);
-        RC(sst_persist_launch(sst_persist_fwd_kernel, P, "sst_persist_fwd", st));
-    } else {
-    // wavefront: launch k = layer 0 at step k  ||  layer 1 at step k-1 (reads the dropped layer-0 output of step k-1)
-        for (int k = 0; k <= T; ++k) {
-            SstFwdRole r0{}, r1{};
-            if (k < T) {
-                r0.active = 1; r0.t = k;
-                r0.W[0] = a->w_hh[0]; r0.v[0] = k ? w.HS[0] + (long)(k - 1) * H : nullptr;
-                r0.base = w.GIN0 + (long)k * 4 * H;
-                r0.cprev = k ? w.CS[0] + (long)(k - 1) * H : nullptr;
-                r0.act = w.ACT[0] + (long)k * 4 * H; r0.hout = w.HS[0] + (long)k * H; r0.cout = w.CS[0] + (long)k * H;
-                r0.hdrop = w.H0D + (long)k * H;
-            }
-            if (k >= 1) {
-                const int t = k - 1;
-                r1.active = 1; r1.t = t;
-                r1.W[0] = a->w_ih[1]; r1.v[0] = w.H0D + (long)t * H;
-                r1.W[1] = a->w_hh[1]; r1.v[1] = t ? a->tap_feats + (long)(t - 1) * H : nullptr;
-                r1.base = a->b_ih[1]; r1.base2 = a->b_hh[1];
-                r1.cprev = t ? w.CS[1] + (long)(t - 1) * H : nullptr;
-                r1.act = w.ACT[1] + (long)t * 4 * H; r1.hout = a->tap_feats + (long)t * H; r1.cout = w.CS[1] + (long)t * H;
-            }
-            hipLaunchKernelGGL(sst_wave_fwd_kernel, dim3(nwg, 2), dim3(256), (2 * H + 4 * UPW) * sizeof(float), st, r0, r1, H, dc);
-        }
-        RC(check_launch("sst_wave_fwd"));
-    }
-    return with_head ? sst_head_impl(a, st) : 0;
-}
-static int sst_head_impl(const echr_sst_args* a, hipStream_t st) {
+// proposal head: scores = sigmoid(tap_feats . W_sc^T + b_sc) (models/sst_model.py:38-39)
+static int sst_head(const echr_sst_args* a, hipStream_t st) {
     const int T = a->T, H = a->H, K = a->K;
-    // proposal head
     echr_gemm_desc d = desc_nt(a->tap_feats, H, a->w_sc, H, a->scores, K, T, K, H);
     d.bias = a->b_sc; d.split_k = -1;
     RC(gemm(d, st));
@@ -1271,15 +1281,62 @@ static int sst_head_impl(const echr_sst_args* a, hipStream_t st) {
     return check_launch("sst_head");
 }
 
-extern "C" int echr_sst_bwd(const echr_sst_args* a, const echr_sst_grads* g, const echr_dropout* drop, void* stream) {
-    RC(sst_check(a, "sst_bwd"));
-    ECHR_REQUIRE(g && g->ws_bwd && (g->g_tap || g->g_scores), "sst_bwd: missing buffers");
-    hipStream_t st = (hipStream_t)stream;
+// The forward of every entry (arguments checked by the caller).  x: the batch description; null or one video in it = the single-video call.
+// `who` names the entry in messages (a one-video batch answers as the single-video entry)
+static int sst_forward(const echr_sst_args* a, const echr_sst_batch* x, const echr_dropout* drop, hipStream_t st, bool with_head, const char* who) {
     const int T = a->T, D = a->D, H = a->H, K = a->K;
+    const bool one = sst_one(x);
     SstWs w = carve(T, D, H, K, a->ws);
-    SstWsB b = carve_b(T, D, H, K, g->ws_bwd);
     const DropCfg dc = make_drop(drop, a->p_drop);
-    const int nwg = (H + UPW - 1) / UPW;
+    // layer 0's input-side pre-activations for all T rows: X . W_ih0^T + b_ih0 + b_hh0 (batched MFMA GEMM)
+    echr_gemm_desc d0 = desc_nt(a->x, D, a->w_ih[0], D, w.GIN0, 4 * H, T, 4 * H, D);
+    d0.bias = a->b_ih[0]; d0.bias2 = a->b_hh[0]; d0.split_k = T >= 128 ? 1 : -1;      // T x 4H output tiles fill the chip from T = 128 on: no split, no zero fill
+    RC(gemm(d0, st));
+    if (sst_persist_ok(H)) {
+        RC(persist_check_async());
+        // exchange rows = saved activations: sentinel-fill h0 | h0d (adjacent) and the output rows h1 = tap_feats, then ONE launch per group
+        if (hipMemsetAsync(w.HS[0], 0xFF, sizeof(float) * (size_t)((w.H0D - w.HS[0]) + (long)T * H), st) != hipSuccess ||
+            hipMemsetAsync(a->tap_feats, 0xFF, sizeof(float) * (size_t)T * H, st) != hipSuccess) { set_error("%s: memset failed", who); return -5; }
+        std::vector<SstGrp> groups;
+        sst_groups(x, T, groups);
+        // algorithmic bytes: the three recurrent matrices once per launch + per step the pre-activation row in and gates / cells / outputs of both layers out
+        ProfScope prof(PROF_SST, 2.0 * T * 3.0 * 4 * H * H, 4.0 * (groups.size() * 3.0 * 4 * H * H + (double)T * (4.0 * H + 2 * (4.0 * H + 2.0 * H) + H)), st);
+        for (size_t gi = 0; gi < groups.size(); ++gi) {
+            SstPFB B;
+            B.p = sst_pf(a, w, dc, groups[gi].len[0]);
+            B.p.stamps = (gi == 0 && config().persist_stamps == 3) ? persist_stamp_buffer(B.p.T + 1, st) : nullptr;
+            B.g = groups[gi];
+            if (one) RC(sst_persist_launch(sst_persist_fwd_kernel, B.p, "sst_persist_fwd", st));
+            else RC(sst_persist_launch(sst_persist_fwd_batch_kernel, B, "sst_persist_fwd_batch", st, sizeof(float) * SPB_NV * 3 * SP_H));
+        }
+    } else {
+        // wavefront: launch k = layer 0 at step k  ||  layer 1 at step k-1 (reads the dropped layer-0 output of step k-1), per video
+        const int nwg = (H + UPW - 1) / UPW, Tmax = sst_tmax(x, T), V = one ? 1 : x->n_videos;
+        SstWaveFB p;
+        p.w_hh0 = a->w_hh[0]; p.w_ih1 = a->w_ih[1]; p.w_hh1 = a->w_hh[1]; p.b_ih1 = a->b_ih[1]; p.b_hh1 = a->b_hh[1]; p.GIN0 = w.GIN0;
+        p.HS0 = w.HS[0]; p.H0D = w.H0D; p.TAP = a->tap_feats; p.ACT0 = w.ACT[0]; p.ACT1 = w.ACT[1]; p.CS0 = w.CS[0]; p.CS1 = w.CS[1];
+        p.row_offset = one ? nullptr : x->row_offset; p.H = H; p.T1 = T;
+        for (int k = 0; k <= Tmax; ++k) {
+            p.k = k;
+            hipLaunchKernelGGL(one ? sst_wave_fwd_batch_kernel<true> : sst_wave_fwd_batch_kernel<false>, dim3(nwg, 2, V), dim3(256), (2 * H + 4 * UPW) * sizeof(float), st, p, dc);
+        }
+        RC(check_launch(one ? "sst_wave_fwd" : "sst_wave_fwd_batch"));
+    }
+    return with_head ? sst_head(a, st) : 0;
+}
+
+// The backward of every entry; x and who as in sst_forward
+static int sst_backward(const echr_sst_args* a, const echr_sst_batch* x, const echr_sst_grads* g, const echr_dropout* drop, hipStream_t st, const char* who) {
+    ECHR_REQUIRE(g && g->ws_bwd && (g->g_tap || g->g_scores), "%s: missing buffers", who);
+    const int T = a->T, D = a->D, H = a->H, K = a->K;
+    const bool one = sst_one(x);
+    const int V = one ? 1 : x->n_videos;
+    SstWs w = carve(T, D, H, K, a->ws);
+    SstWsBB bb{};                                 // (one video: the single-video workspace, no shifted states and no per-video d c)
+    if (one) bb.b = carve_b(T, D, H, K, g->ws_bwd);
+    else bb = carve_bb(T, D, H, K, V, g->ws_bwd);
+    SstWsB& b = bb.b;
+    const DropCfg dc = make_drop(drop, a->p_drop);
     const bool z = g->zeroed != 0;             // gradient buffers arrive zero-filled (flat arena): accumulate, no per-product fills
     const float zb = z ? 1.f : 0.f;
     echr_gemm_desc d;
@@ -1299,61 +1356,59 @@ extern "C" int echr_sst_bwd(const echr_sst_args* a, const echr_sst_grads* g, con
         RC(fill_zero(g->g_w_sc, (long)K * H, st));
         RC(fill_zero(g->g_b_sc, K, st));
     }
+    if (!one) {
+        // previous-state rows for the recurrent weight gradients (reads the forward's states only: ahead of the recurrence, off its tail)
+        hipLaunchKernelGGL(sst_shift_rows_kernel, dim3(T), dim3(128), 0, st, w.HS[0], a->tap_feats, bb.HP[0], bb.HP[1], x->row_offset, V, H);
+        RC(check_launch("sst_shift_rows"));
+    }
     if (sst_persist_ok(H)) {
         RC(persist_check_async());
-        if (hipMemsetAsync(b.DG[0], 0xFF, sizeof(float) * (size_t)((b.DG[1] - b.DG[0]) + (long)T * 4 * H), st) != hipSuccess) { set_error("sst_bwd: memset failed"); return -5; }
-        SstPB P;
-        P.T = T; P.w_hh0 = a->w_hh[0]; P.w_ih1 = a->w_ih[1]; P.w_hh1 = a->w_hh[1];
-        P.ACT0 = w.ACT[0]; P.ACT1 = w.ACT[1]; P.CS0 = w.CS[0]; P.CS1 = w.CS[1]; P.DHO = b.DHO; P.DG0 = b.DG[0]; P.DG1 = b.DG[1];
-        P.y = sst_sync(); P.dc = dc;
-        P.stamps = config().persist_stamps == 4 ? persist_stamp_buffer(T + 1, st) : nullptr;
-        ProfScope prof(PROF_SST, 2.0 * T * 3.0 * 4 * H * H, 4.0 * (3.0 * 4 * H * H + (double)T * (2 * (4.0 * H + 2.0 * H) + H + 2 * 4.0 * H)), st);
-        RC(sst_persist_launch(sst_persist_bwd_kernel, P, "sst_persist_bwd", st, sizeof(float) * (2 + 8) * 4 * SP_H));
+        if (hipMemsetAsync(b.DG[0], 0xFF, sizeof(float) * (size_t)((b.DG[1] - b.DG[0]) + (long)T * 4 * H), st) != hipSuccess) { set_error("%s: memset failed", who); return -5; }
+        std::vector<SstGrp> groups;
+        sst_groups(x, T, groups);
+        ProfScope prof(PROF_SST, 2.0 * T * 3.0 * 4 * H * H, 4.0 * (groups.size() * 3.0 * 4 * H * H + (double)T * (2 * (4.0 * H + 2.0 * H) + H + 2 * 4.0 * H)), st);
+        for (size_t gi = 0; gi < groups.size(); ++gi) {
+            SstPBB B;
+            B.p = sst_pb(a, w, b, dc, groups[gi].len[0]);
+            B.p.stamps = (gi == 0 && config().persist_stamps == 4) ? persist_stamp_buffer(B.p.T + 1, st) : nullptr;
+            B.g = groups[gi];
+            if (one) RC(sst_persist_launch(sst_persist_bwd_kernel, B.p, "sst_persist_bwd", st, sizeof(float) * (2 + 8) * 4 * SP_H));
+            else RC(sst_persist_launch(sst_persist_bwd_batch_kernel, B, "sst_persist_bwd_batch", st, sizeof(float) * SPB_NV * 2 * 4 * SP_H));
+        }
     } else {
-    {
-            const TransposeJob tj[3] = {{a->w_hh[0], H, b.WT[0], 4 * H, 4 * H, H}, {a->w_hh[1], H, b.WT[1], 4 * H, 4 * H, H},
-                                        {a->w_ih[1], H, b.WT_IH1, 4 * H, 4 * H, H}};
-            RC(transpose_multi(tj, 3, st));
-            float* zp[2] = {b.DC[0], b.DC[1]};
-            const long zn[2] = {H, H};
-            RC(fill_zero_multi(zp, zn, 2, st));
+        const TransposeJob tj[3] = {{a->w_hh[0], H, b.WT[0], 4 * H, 4 * H, H}, {a->w_hh[1], H, b.WT[1], 4 * H, 4 * H, H},
+                                    {a->w_ih[1], H, b.WT_IH1, 4 * H, 4 * H, H}};
+        RC(transpose_multi(tj, 3, st));
+        // wavefront: launch k = layer 1 at step T_v-1-k  ||  layer 0 at step T_v-k (its upstream gradient is W_ih1^T . dG1 of the same step,
+        // through the inter-layer dropout mask), per video.  The carried d c of both layers starts at zero: one fill over their span
+        const int nwg = (H + UPW - 1) / UPW, Tmax = sst_tmax(x, T);
+        SstWaveBB p;
+        p.WT0 = b.WT[0]; p.WT1 = b.WT[1]; p.WT_IH1 = b.WT_IH1; p.ACT0 = w.ACT[0]; p.ACT1 = w.ACT[1]; p.CS0 = w.CS[0]; p.CS1 = w.CS[1]; p.DHO = b.DHO;
+        p.DG0 = b.DG[0]; p.DG1 = b.DG[1]; p.row_offset = one ? nullptr : x->row_offset; p.H = H; p.T1 = T;
+        p.DC0 = one ? b.DC[0] : bb.DCV; p.DC1 = one ? b.DC[1] : bb.DCV + H; p.dc_stride = one ? 0 : 2 * H;
+        RC(fill_zero(p.DC0, (p.DC1 - p.DC0) + H + (V - 1) * p.dc_stride, st));
+        for (int k = 0; k <= Tmax; ++k) {
+            p.k = k;
+            hipLaunchKernelGGL(one ? sst_wave_bwd_batch_kernel<true> : sst_wave_bwd_batch_kernel<false>, dim3(nwg, 2, V), dim3(256), (8 * H + 2 * UPW) * sizeof(float), st, p, dc);
         }
-        // wavefront: launch k = layer 1 at step T-1-k  ||  layer 0 at step T-k (its upstream gradient is W_ih1^T . dG1 of the same step,
-        // through the inter-layer dropout mask)
-        for (int k = 0; k <= T; ++k) {
-            SstBwdRole r1{}, r0{};
-            if (k < T) {
-                const int t = T - 1 - k;
-                r1.active = 1; r1.t = t;
-                r1.WT[0] = b.WT[1]; r1.vec[0] = t + 1 < T ? b.DG[1] + (long)(t + 1) * 4 * H : nullptr;
-                r1.dh_base = b.DHO + (long)t * H;
-                r1.act = w.ACT[1] + (long)t * 4 * H; r1.c = w.CS[1] + (long)t * H; r1.cprev = t ? w.CS[1] + (long)(t - 1) * H : nullptr;
-                r1.dc = b.DC[1]; r1.dg = b.DG[1] + (long)t * 4 * H;
-            }
-            if (k >= 1) {
-                const int t = T - k;
-                r0.active = 1; r0.t = t; r0.drop_first = 1;
-                r0.WT[0] = b.WT_IH1; r0.vec[0] = b.DG[1] + (long)t * 4 * H;
-                r0.WT[1] = b.WT[0]; r0.vec[1] = t + 1 < T ? b.DG[0] + (long)(t + 1) * 4 * H : nullptr;
-                r0.act = w.ACT[0] + (long)t * 4 * H; r0.c = w.CS[0] + (long)t * H; r0.cprev = t ? w.CS[0] + (long)(t - 1) * H : nullptr;
-                r0.dc = b.DC[0]; r0.dg = b.DG[0] + (long)t * 4 * H;
-            }
-            hipLaunchKernelGGL(sst_wave_bwd_kernel, dim3(nwg, 2), dim3(256), (8 * H + 2 * UPW) * sizeof(float), st, r1, r0, H, dc);
-        }
-        RC(check_launch("sst_wave_bwd"));
+        RC(check_launch(one ? "sst_wave_bwd" : "sst_wave_bwd_batch"));
     }
-    // parameter gradients (sums over the T rows); h(t-1) pairs with dG(t): rows 1..T-1.  The two layers' products are independent small
-    // GEMMs (20-25 us each, half a chip): layer 0's run on the library's helper stream beside layer 1's
+    // parameter gradients (sums over the T rows).  The recurrent ones pair dG(t) with h(t-1): one video pairs rows 1..T-1 with the states
+    // themselves, a batch all T_tot rows with the shifted states (zero rows at video starts: no pair crosses a boundary).  The two layers'
+    // products are independent small GEMMs (20-25 us each, half a chip): layer 0's run on the library's helper stream beside layer 1's
+    const float* hprev[2] = {one ? w.HS[0] : bb.HP[0], one ? a->tap_feats : bb.HP[1]};
+    const long dg0 = one ? 4 * H : 0;
+    const int hrows = one ? T - 1 : T;
     hipStream_t s0 = aux_fork(st);
     const bool fork = s0 != nullptr;
     if (!fork) s0 = st;
-    if (z && T > 1 && fork) {
+    if (one && z && T > 1 && fork) {
         // zeroed gradient buffers (the arena path): the two recurrent products share their shape (4H x H over T - 1 rows) -> one grouped launch
         // on this stream beside the two input products on the helper stream, and ONE column-sum launch for both layers' biases
-        // (four GEMM + two column-sum launches on two streams before)
+        // (four GEMM + two column-sum launches on two streams before).  One video only: a batch keeps its per-product summation
         echr_gemm_desc gh[2];
         for (int l = 0; l < 2; ++l) {
-            gh[l] = desc_tn(b.DG[l] + 4 * H, 4 * H, l == 0 ? w.HS[0] : a->tap_feats, H, g->g_w_hh[l], H, 4 * H, H, T - 1);
+            gh[l] = desc_tn(b.DG[l] + dg0, 4 * H, hprev[l], H, g->g_w_hh[l], H, 4 * H, H, hrows);
             gh[l].split_k = -1; gh[l].beta = 1.f;
         }
         RC(gemm_grouped(gh, 2, st));
@@ -1367,13 +1422,12 @@ extern "C" int echr_sst_bwd(const echr_sst_args* a, const echr_sst_grads* g, con
     }
     for (int l = 1; l >= 0; --l) {
         hipStream_t sl = l == 0 ? s0 : st;
-        const float* hs = l == 0 ? w.HS[0] : a->tap_feats;
         const float* xin = l == 0 ? a->x : w.H0D;
         const int din = l == 0 ? D : H;
         d = desc_tn(b.DG[l], 4 * H, xin, din, g->g_w_ih[l], din, 4 * H, din, T); d.split_k = -1; d.beta = zb;
         RC(gemm(d, sl));
-        if (T > 1) {
-            d = desc_tn(b.DG[l] + 4 * H, 4 * H, hs, H, g->g_w_hh[l], H, 4 * H, H, T - 1); d.split_k = -1; d.beta = zb;
+        if (hrows > 0) {
+            d = desc_tn(b.DG[l] + dg0, 4 * H, hprev[l], H, g->g_w_hh[l], H, 4 * H, H, hrows); d.split_k = -1; d.beta = zb;
             RC(gemm(d, sl));
         } else if (!z) {
             RC(fill_zero(g->g_w_hh[l], (long)4 * H * H, sl));
@@ -1384,182 +1438,31 @@ extern "C" int echr_sst_bwd(const echr_sst_args* a, const echr_sst_grads* g, con
     return 0;
 }
 
-// =====================================================================================================================
-// Multi-video batches (echr_sst_batch): V videos concatenated row-wise, every video from the zero state.  Products over rows (layer 0's
-// input product, the head, the input-side weight gradients, the bias sums) are the single-video launches over T_tot rows; the recurrences
-// carry a video axis (persistent form: groups of SPB_NV videos per launch; wavefront form: blockIdx.z).
-// =====================================================================================================================
-namespace echr {
-struct SstWsBB { SstWsB b; float *HP[2], *DCV; long total; };
-static SstWsBB carve_bb(int T, int D, int H, int K, int V, float* base) {
-    SstWsBB w;
-    w.b = carve_b(T, D, H, K, base);
-    long off = w.b.total;
-    auto take = [&](long n) { float* p = base ? base + off : nullptr; off += rup(n, 64); return p; };
-    w.HP[0] = take((long)T * H); w.HP[1] = take((long)T * H);        // h(t-1) per row, zero at video starts (recurrent weight gradients)
-    w.DCV = take((long)V * 2 * H);                                   // wavefront form: d c carried per video and layer
-    w.total = off;
-    return w;
+extern "C" int echr_sst_fwd(const echr_sst_args* a, const echr_dropout* drop, void* stream) {
+    RC(sst_check(a, "sst_fwd"));
+    return sst_forward(a, nullptr, drop, (hipStream_t)stream, true, "sst_fwd");
 }
-// groups of the persistent form: videos ordered by length (longest first, ties by index) and cut into runs of SPB_NV -- a group runs
-// len[0] + 1 steps, so neighbours in length share a launch
-static void sst_groups(const echr_sst_batch* x, std::vector<SstGrp>& out) {
-    const int V = x->n_videos;
-    std::vector<int> order(V);
-    for (int v = 0; v < V; ++v) order[v] = v;
-    const int32_t* ro = x->row_offset_host;
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return ro[a + 1] - ro[a] > ro[b + 1] - ro[b]; });
-    for (int s = 0; s < V; s += SPB_NV) {
-        SstGrp g{};
-        g.nv = std::min(SPB_NV, V - s);
-        for (int i = 0; i < g.nv; ++i) { g.base[i] = ro[order[s + i]]; g.len[i] = ro[order[s + i] + 1] - ro[order[s + i]]; }
-        out.push_back(g);
-    }
+// the two halves of echr_sst_fwd on their own (joint iteration: the caption side waits for tap_feats alone, so its caller queues the proposal
+// head BEHIND the caption call instead of in front of it)
+extern "C" int echr_sst_fwd_states(const echr_sst_args* a, const echr_dropout* drop, void* stream) {
+    RC(sst_check(a, "sst_fwd"));
+    return sst_forward(a, nullptr, drop, (hipStream_t)stream, false, "sst_fwd");
 }
-}  // namespace echr
-
-extern "C" int echr_sst_batch_group(void) { return SPB_NV; }
-extern "C" int64_t echr_sst_batch_ws_floats(int32_t T, int32_t D, int32_t H, int32_t K, int32_t V) { (void)V; return carve(T, D, H, K, nullptr).total; }
-extern "C" int64_t echr_sst_batch_ws_bwd_floats(int32_t T, int32_t D, int32_t H, int32_t K, int32_t V) {
-    return carve_bb(T, D, H, K, V > 0 ? V : 1, nullptr).total;
+extern "C" int echr_sst_head_fwd(const echr_sst_args* a, void* stream) {
+    RC(sst_check(a, "sst_head_fwd"));
+    return sst_head(a, (hipStream_t)stream);
 }
-
-static int sst_batch_check(const echr_sst_args* a, const echr_sst_batch* x, const char* who) {
-    RC(sst_check(a, who));
-    ECHR_REQUIRE(x && x->n_videos >= 1 && x->n_videos <= 65535 && x->row_offset && x->row_offset_host, "%s: missing batch description (1..65535 videos)", who);
-    ECHR_REQUIRE(x->row_offset_host[0] == 0 && x->row_offset_host[x->n_videos] == a->T, "%s: row_offset must run from 0 to T_tot = %d", who, a->T);
-    for (int v = 0; v < x->n_videos; ++v)
-        ECHR_REQUIRE(x->row_offset_host[v + 1] > x->row_offset_host[v], "%s: video %d has no row", who, v);
-    ECHR_REQUIRE((long)a->T * a->H < (1l << 31), "%s: T_tot * H must stay below 2^31 (dropout keys)", who);
-    return 0;
+extern "C" int echr_sst_bwd(const echr_sst_args* a, const echr_sst_grads* g, const echr_dropout* drop, void* stream) {
+    RC(sst_check(a, "sst_bwd"));
+    return sst_backward(a, nullptr, g, drop, (hipStream_t)stream, "sst_bwd");
 }
-static int sst_tmax(const echr_sst_batch* x) {
-    int m = 0;
-    for (int v = 0; v < x->n_videos; ++v) m = std::max(m, (int)(x->row_offset_host[v + 1] - x->row_offset_host[v]));
-    return m;
-}
-
 extern "C" int echr_sst_fwd_batch(const echr_sst_args* a, const echr_sst_batch* x, const echr_dropout* drop, void* stream) {
     RC(sst_batch_check(a, x, "sst_fwd_batch"));
-    if (x->n_videos == 1) return sst_fwd_impl(a, drop, stream, true);          // one video: today's call, today's dropout keys
-    hipStream_t st = (hipStream_t)stream;
-    const int T = a->T, D = a->D, H = a->H, K = a->K, V = x->n_videos;
-    SstWs w = carve(T, D, H, K, a->ws);
-    const DropCfg dc = make_drop(drop, a->p_drop);
-    echr_gemm_desc d0 = desc_nt(a->x, D, a->w_ih[0], D, w.GIN0, 4 * H, T, 4 * H, D);
-    d0.bias = a->b_ih[0]; d0.bias2 = a->b_hh[0]; d0.split_k = T >= 128 ? 1 : -1;
-    RC(gemm(d0, st));
-    if (sst_persist_ok(H)) {
-        RC(persist_check_async());
-        if (hipMemsetAsync(w.HS[0], 0xFF, sizeof(float) * (size_t)((w.H0D - w.HS[0]) + (long)T * H), st) != hipSuccess ||
-            hipMemsetAsync(a->tap_feats, 0xFF, sizeof(float) * (size_t)T * H, st) != hipSuccess) { set_error("sst_fwd_batch: memset failed"); return -5; }
-        std::vector<SstGrp> groups;
-        sst_groups(x, groups);
-        ProfScope prof(PROF_SST, 2.0 * T * 3.0 * 4 * H * H, 4.0 * (groups.size() * 3.0 * 4 * H * H + (double)T * (4.0 * H + 2 * (4.0 * H + 2.0 * H) + H)), st);
-        for (size_t gi = 0; gi < groups.size(); ++gi) {
-            SstPFB B;
-            SstPF& P = B.p;
-            P.T = groups[gi].len[0]; P.w_hh0 = a->w_hh[0]; P.w_ih1 = a->w_ih[1]; P.w_hh1 = a->w_hh[1]; P.b_ih1 = a->b_ih[1]; P.b_hh1 = a->b_hh[1]; P.GIN0 = w.GIN0;
-            P.HS0 = w.HS[0]; P.H0D = w.H0D; P.TAP = a->tap_feats; P.ACT0 = w.ACT[0]; P.ACT1 = w.ACT[1]; P.CS0 = w.CS[0]; P.CS1 = w.CS[1];
-            P.y = sst_sync(); P.dc = dc;
-            P.stamps = (gi == 0 && config().persist_stamps == 3) ? persist_stamp_buffer(P.T + 1, st) : nullptr;
-            B.g = groups[gi];
-            RC(sst_persist_launch(sst_persist_fwd_batch_kernel, B, "sst_persist_fwd_batch", st, sizeof(float) * SPB_NV * 3 * SP_H));
-        }
-    } else {
-        const int nwg = (H + UPW - 1) / UPW, Tmax = sst_tmax(x);
-        SstWaveFB p;
-        p.w_hh0 = a->w_hh[0]; p.w_ih1 = a->w_ih[1]; p.w_hh1 = a->w_hh[1]; p.b_ih1 = a->b_ih[1]; p.b_hh1 = a->b_hh[1]; p.GIN0 = w.GIN0;
-        p.HS0 = w.HS[0]; p.H0D = w.H0D; p.TAP = a->tap_feats; p.ACT0 = w.ACT[0]; p.ACT1 = w.ACT[1]; p.CS0 = w.CS[0]; p.CS1 = w.CS[1];
-        p.row_offset = x->row_offset; p.H = H;
-        for (int k = 0; k <= Tmax; ++k) {
-            p.k = k;
-            hipLaunchKernelGGL(sst_wave_fwd_batch_kernel, dim3(nwg, 2, V), dim3(256), (2 * H + 4 * UPW) * sizeof(float), st, p, dc);
-        }
-        RC(check_launch("sst_wave_fwd_batch"));
-    }
-    return sst_head_impl(a, st);
+    return sst_forward(a, x, drop, (hipStream_t)stream, true, sst_one(x) ? "sst_fwd" : "sst_fwd_batch");
 }
-
 extern "C" int echr_sst_bwd_batch(const echr_sst_args* a, const echr_sst_batch* x, const echr_sst_grads* g, const echr_dropout* drop, void* stream) {
     RC(sst_batch_check(a, x, "sst_bwd_batch"));
-    if (x->n_videos == 1) return echr_sst_bwd(a, g, drop, stream);
-    ECHR_REQUIRE(g && g->ws_bwd && (g->g_tap || g->g_scores), "sst_bwd_batch: missing buffers");
-    hipStream_t st = (hipStream_t)stream;
-    const int T = a->T, D = a->D, H = a->H, K = a->K, V = x->n_videos;
-    SstWs w = carve(T, D, H, K, a->ws);
-    SstWsBB bb = carve_bb(T, D, H, K, V, g->ws_bwd);
-    SstWsB& b = bb.b;
-    const DropCfg dc = make_drop(drop, a->p_drop);
-    const bool z = g->zeroed != 0;
-    const float zb = z ? 1.f : 0.f;
-    echr_gemm_desc d;
-    if (g->g_tap) RC(hipMemcpyAsync(b.DHO, g->g_tap, sizeof(float) * T * H, hipMemcpyDeviceToDevice, st) == hipSuccess ? 0 : -5);
-    else RC(fill_zero(b.DHO, (long)T * H, st));
-    if (g->g_scores) {
-        const long n = (long)T * K;
-        hipLaunchKernelGGL(sigmoid_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a->scores, g->g_scores, b.DZ, n);
-        RC(check_launch("sigmoid_bwd"));
-        d = desc_nn(b.DZ, K, a->w_sc, H, b.DHO, H, T, H, K); d.beta = 1.f; d.split_k = -1;
-        RC(gemm(d, st));
-        d = desc_tn(b.DZ, K, a->tap_feats, H, g->g_w_sc, H, K, H, T); d.split_k = -1; d.beta = zb;
-        RC(gemm(d, st));
-        RC(colsum(b.DZ, K, T, K, g->g_b_sc, z, st));
-    } else if (!z) {
-        RC(fill_zero(g->g_w_sc, (long)K * H, st));
-        RC(fill_zero(g->g_b_sc, K, st));
-    }
-    // previous-state rows for the recurrent weight gradients (reads the forward's states only: ahead of the recurrence, off its tail)
-    hipLaunchKernelGGL(sst_shift_rows_kernel, dim3(T), dim3(128), 0, st, w.HS[0], a->tap_feats, bb.HP[0], bb.HP[1], x->row_offset, V, H);
-    RC(check_launch("sst_shift_rows"));
-    if (sst_persist_ok(H)) {
-        RC(persist_check_async());
-        if (hipMemsetAsync(b.DG[0], 0xFF, sizeof(float) * (size_t)((b.DG[1] - b.DG[0]) + (long)T * 4 * H), st) != hipSuccess) { set_error("sst_bwd_batch: memset failed"); return -5; }
-        std::vector<SstGrp> groups;
-        sst_groups(x, groups);
-        ProfScope prof(PROF_SST, 2.0 * T * 3.0 * 4 * H * H, 4.0 * (groups.size() * 3.0 * 4 * H * H + (double)T * (2 * (4.0 * H + 2.0 * H) + H + 2 * 4.0 * H)), st);
-        for (size_t gi = 0; gi < groups.size(); ++gi) {
-            SstPBB B;
-            SstPB& P = B.p;
-            P.T = groups[gi].len[0]; P.w_hh0 = a->w_hh[0]; P.w_ih1 = a->w_ih[1]; P.w_hh1 = a->w_hh[1];
-            P.ACT0 = w.ACT[0]; P.ACT1 = w.ACT[1]; P.CS0 = w.CS[0]; P.CS1 = w.CS[1]; P.DHO = b.DHO; P.DG0 = b.DG[0]; P.DG1 = b.DG[1];
-            P.y = sst_sync(); P.dc = dc;
-            P.stamps = (gi == 0 && config().persist_stamps == 4) ? persist_stamp_buffer(P.T + 1, st) : nullptr;
-            B.g = groups[gi];
-            RC(sst_persist_launch(sst_persist_bwd_batch_kernel, B, "sst_persist_bwd_batch", st, sizeof(float) * SPB_NV * 2 * 4 * SP_H));
-        }
-    } else {
-        const TransposeJob tj[3] = {{a->w_hh[0], H, b.WT[0], 4 * H, 4 * H, H}, {a->w_hh[1], H, b.WT[1], 4 * H, 4 * H, H},
-                                    {a->w_ih[1], H, b.WT_IH1, 4 * H, 4 * H, H}};
-        RC(transpose_multi(tj, 3, st));
-        RC(fill_zero(bb.DCV, (long)V * 2 * H, st));
-        const int nwg = (H + UPW - 1) / UPW, Tmax = sst_tmax(x);
-        SstWaveBB p;
-        p.WT0 = b.WT[0]; p.WT1 = b.WT[1]; p.WT_IH1 = b.WT_IH1; p.ACT0 = w.ACT[0]; p.ACT1 = w.ACT[1]; p.CS0 = w.CS[0]; p.CS1 = w.CS[1]; p.DHO = b.DHO;
-        p.DG0 = b.DG[0]; p.DG1 = b.DG[1]; p.DC = bb.DCV; p.row_offset = x->row_offset; p.H = H;
-        for (int k = 0; k <= Tmax; ++k) {
-            p.k = k;
-            hipLaunchKernelGGL(sst_wave_bwd_batch_kernel, dim3(nwg, 2, V), dim3(256), (8 * H + 2 * UPW) * sizeof(float), st, p, dc);
-        }
-        RC(check_launch("sst_wave_bwd_batch"));
-    }
-    // parameter gradients: sums over all T_tot rows; the recurrent ones against the shifted states (zero rows at video starts: no pair
-    // crosses a boundary).  Layer 0's products run on the helper stream beside layer 1's, as in echr_sst_bwd
-    hipStream_t s0 = aux_fork(st);
-    const bool fork = s0 != nullptr;
-    if (!fork) s0 = st;
-    for (int l = 1; l >= 0; --l) {
-        hipStream_t sl = l == 0 ? s0 : st;
-        const float* xin = l == 0 ? a->x : w.H0D;
-        const int din = l == 0 ? D : H;
-        d = desc_tn(b.DG[l], 4 * H, xin, din, g->g_w_ih[l], din, 4 * H, din, T); d.split_k = -1; d.beta = zb;
-        RC(gemm(d, sl));
-        d = desc_tn(b.DG[l], 4 * H, bb.HP[l], H, g->g_w_hh[l], H, 4 * H, H, T); d.split_k = -1; d.beta = zb;
-        RC(gemm(d, sl));
-        RC(colsum2(b.DG[l], 4 * H, T, 4 * H, g->g_b_ih[l], g->g_b_hh[l], z, sl));
-    }
-    if (fork) RC(aux_join(st));
-    return 0;
+    return sst_backward(a, x, g, drop, (hipStream_t)stream, sst_one(x) ? "sst_bwd" : "sst_bwd_batch");
 }
 
 extern "C" int echr_tap_bce_fwd(const float* scores, const float* masks, const float* labels, const float* w1, float* loss, int32_t T,

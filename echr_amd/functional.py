@@ -1017,25 +1017,23 @@ def gemm(A, B, trans_b=True, bias=None, algo=0):
 
 # --------------------------------------------------------------------------------------------------
 class SSTFunction(torch.autograd.Function):
-    """SST.forward (models/sst_model.py:31-40): 2-layer LSTM over one video + sigmoid proposal head, native."""
+    """SST.forward (models/sst_model.py:31-40): 2-layer LSTM + sigmoid proposal head, native.  Without offsets (`ro_host` None) x is one video
+    [T, D] (echr_sst_fwd / echr_sst_bwd); with them it is the concatenated [T_tot, D] matrix of a multi-video batch (echr_sst_fwd_batch /
+    echr_sst_bwd_batch): `ro_host` the validated int32 offsets (sst_row_offsets), `ro_dev` their device copy, and the parameter gradients are
+    the sum over the videos."""
 
     @staticmethod
-    def forward(ctx, x, p_drop, drop, sink, *params):
-        lib = L.load()
+    def forward(ctx, x, ro_host, ro_dev, p_drop, drop, sink, *params):
         ctx.sink = sink
         x = _f32c(x)
         ps = [_f32c(p) for p in params]           # w_ih0, w_hh0, b_ih0, b_hh0, w_ih1, w_hh1, b_ih1, b_hh1, w_sc, b_sc
-        T, D = x.shape
-        H, K = ps[1].shape[1], ps[8].shape[0]
-        dev = x.device
-        ws = torch.empty(lib.echr_sst_ws_floats(T, D, H, K), device=dev, dtype=torch.float32)
-        tap = torch.empty(T, H, device=dev, dtype=torch.float32)
-        scores = torch.empty(T, K, device=dev, dtype=torch.float32)
-        a = SSTFunction._args(ps, x, p_drop, ws, tap, scores)
-        d = drop.c()
-        L.check(lib.echr_sst_fwd(C.byref(a), C.byref(d), L.stream_ptr()), 'sst_fwd')
-        ctx.save_for_backward(x, ws, tap, scores, *ps)
-        ctx.meta = (p_drop, drop)
+        T, H, K = x.shape[0], ps[1].shape[1], ps[8].shape[0]
+        ws = SSTFunction._workspace(x, ps, ro_host, 'ws')
+        tap = torch.empty(T, H, device=x.device, dtype=torch.float32)
+        scores = torch.empty(T, K, device=x.device, dtype=torch.float32)
+        SSTFunction._call('fwd', ro_host, ro_dev, drop, SSTFunction._args(ps, x, p_drop, ws, tap, scores))
+        ctx.save_for_backward(x, ws, tap, scores, *([] if ro_host is None else [ro_dev]), *ps)
+        ctx.meta = (p_drop, drop, ro_host)
         return tap, scores
 
     @staticmethod
@@ -1047,25 +1045,41 @@ class SSTFunction(torch.autograd.Function):
                          L.ptr(ps[8]), L.ptr(ps[9]), L.ptr(x), L.ptr(ws), L.ptr(tap), L.ptr(scores))
 
     @staticmethod
-    def backward(ctx, g_tap, g_scores):
+    def _workspace(x, ps, ro_host, which):
+        """The forward ('ws') or backward ('ws_bwd') workspace of the call: the batch entries size their own."""
         lib = L.load()
+        dims = (x.shape[0], x.shape[1], ps[1].shape[1], ps[8].shape[0])
+        n = getattr(lib, 'echr_sst_%s_floats' % which)(*dims) if ro_host is None else \
+            getattr(lib, 'echr_sst_batch_%s_floats' % which)(*dims, len(ro_host) - 1)
+        return torch.empty(n, device=x.device, dtype=torch.float32)
+
+    @staticmethod
+    def _call(direction, ro_host, ro_dev, drop, a, *grads):
+        """echr_sst_<direction> on the argument struct `a` (and the gradient struct), or its _batch form when the call has offsets."""
+        lib = L.load()
+        rest = [C.byref(g) for g in grads] + [C.byref(drop.c()), L.stream_ptr()]
+        if ro_host is None:
+            L.check(getattr(lib, 'echr_sst_' + direction)(C.byref(a), *rest), 'sst_' + direction)
+        else:
+            bx = L.SstBatch(len(ro_host) - 1, L.ptr(ro_dev, torch.int32), ro_host.ctypes.data)
+            L.check(getattr(lib, 'echr_sst_%s_batch' % direction)(C.byref(a), C.byref(bx), *rest), 'sst_%s_batch' % direction)
+
+    @staticmethod
+    def backward(ctx, g_tap, g_scores):
+        p_drop, drop, ro_host = ctx.meta
         x, ws, tap, scores, *ps = ctx.saved_tensors
-        p_drop, drop = ctx.meta
-        T, D = x.shape
-        H, K = ps[1].shape[1], ps[8].shape[0]
+        ro_dev = ps.pop(0) if ro_host is not None else None
         # flat arena (no gradient live yet): ONE zero fill of the span, then every product accumulates (`zeroed`): the split-K weight-gradient
         # products would otherwise zero-fill their own outputs, one launch each
         use_arena = ctx.sink is not None and ctx.sink.usable()
         grads = ctx.sink.take() if use_arena else [torch.empty_like(p) for p in ps]
-        wsb = torch.empty(lib.echr_sst_ws_bwd_floats(T, D, H, K), device=x.device, dtype=torch.float32)
-        a = SSTFunction._args(ps, x, p_drop, ws, tap, scores)
+        wsb = SSTFunction._workspace(x, ps, ro_host, 'ws_bwd')
+        g_tap, g_scores = (_f32c(t) if t is not None else None for t in (g_tap, g_scores))          # (held: the call reads the fp32 copies)
         two = lambda a_, b_: (L.c_f * 2)(L.ptr(a_), L.ptr(b_))
         g = L.SstGrads(two(grads[0], grads[4]), two(grads[1], grads[5]), two(grads[2], grads[6]), two(grads[3], grads[7]),
-                       L.ptr(grads[8]), L.ptr(grads[9]), L.ptr(_f32c(g_tap)) if g_tap is not None else None,
-                       L.ptr(_f32c(g_scores)) if g_scores is not None else None, L.ptr(wsb), 1 if use_arena else 0)
-        d = drop.c()
-        L.check(lib.echr_sst_bwd(C.byref(a), C.byref(g), C.byref(d), L.stream_ptr()), 'sst_bwd')
-        return (None, None, None, None) + tuple(grads)
+                       L.ptr(grads[8]), L.ptr(grads[9]), L.ptr(g_tap), L.ptr(g_scores), L.ptr(wsb), 1 if use_arena else 0)
+        SSTFunction._call('bwd', ro_host, ro_dev, drop, SSTFunction._args(ps, x, p_drop, ws, tap, scores), g)
+        return (None,) * 6 + tuple(grads)
 
 
 def sst_row_offsets(row_offset, rows):
@@ -1081,53 +1095,6 @@ def sst_row_offsets(row_offset, rows):
     if int(ro[-1]) != int(rows):
         raise ValueError('row_offset ends at %d but the features have %d rows' % (ro[-1], rows))
     return np.ascontiguousarray(ro.astype(np.int32))
-
-
-class SSTBatchFunction(torch.autograd.Function):
-    """SST.forward over a multi-video batch (echr_sst_fwd_batch / echr_sst_bwd_batch): x is the concatenated [T_tot, D] matrix, `ro_host` the
-    validated int32 offsets (sst_row_offsets), `ro_dev` their device copy.  Parameter gradients are the sum over the videos."""
-
-    @staticmethod
-    def forward(ctx, x, ro_host, ro_dev, p_drop, drop, sink, *params):
-        lib = L.load()
-        ctx.sink = sink
-        x = _f32c(x)
-        ps = [_f32c(p) for p in params]
-        T, D = x.shape
-        H, K = ps[1].shape[1], ps[8].shape[0]
-        V = len(ro_host) - 1
-        dev = x.device
-        ws = torch.empty(lib.echr_sst_batch_ws_floats(T, D, H, K, V), device=dev, dtype=torch.float32)
-        tap = torch.empty(T, H, device=dev, dtype=torch.float32)
-        scores = torch.empty(T, K, device=dev, dtype=torch.float32)
-        a = SSTFunction._args(ps, x, p_drop, ws, tap, scores)
-        bx = L.SstBatch(V, L.ptr(ro_dev, torch.int32), ro_host.ctypes.data)
-        d = drop.c()
-        L.check(lib.echr_sst_fwd_batch(C.byref(a), C.byref(bx), C.byref(d), L.stream_ptr()), 'sst_fwd_batch')
-        ctx.save_for_backward(x, ws, tap, scores, ro_dev, *ps)
-        ctx.meta = (p_drop, drop, ro_host)
-        return tap, scores
-
-    @staticmethod
-    def backward(ctx, g_tap, g_scores):
-        lib = L.load()
-        x, ws, tap, scores, ro_dev, *ps = ctx.saved_tensors
-        p_drop, drop, ro_host = ctx.meta
-        T, D = x.shape
-        H, K = ps[1].shape[1], ps[8].shape[0]
-        V = len(ro_host) - 1
-        use_arena = ctx.sink is not None and ctx.sink.usable()
-        grads = ctx.sink.take() if use_arena else [torch.empty_like(p) for p in ps]
-        wsb = torch.empty(lib.echr_sst_batch_ws_bwd_floats(T, D, H, K, V), device=x.device, dtype=torch.float32)
-        a = SSTFunction._args(ps, x, p_drop, ws, tap, scores)
-        bx = L.SstBatch(V, L.ptr(ro_dev, torch.int32), ro_host.ctypes.data)
-        two = lambda a_, b_: (L.c_f * 2)(L.ptr(a_), L.ptr(b_))
-        g = L.SstGrads(two(grads[0], grads[4]), two(grads[1], grads[5]), two(grads[2], grads[6]), two(grads[3], grads[7]),
-                       L.ptr(grads[8]), L.ptr(grads[9]), L.ptr(_f32c(g_tap)) if g_tap is not None else None,
-                       L.ptr(_f32c(g_scores)) if g_scores is not None else None, L.ptr(wsb), 1 if use_arena else 0)
-        d = drop.c()
-        L.check(lib.echr_sst_bwd_batch(C.byref(a), C.byref(bx), C.byref(g), C.byref(d), L.stream_ptr()), 'sst_bwd_batch')
-        return (None, None, None, None, None, None) + tuple(grads)
 
 
 class TapBCE(torch.autograd.Function):

@@ -738,18 +738,6 @@ class _JointStep(object):
         ar.deferred_clamp = None
         ar.end_backward_pass()
 
-    def _tap_drop(self):
-        """(p, DropState) of the proposal encoder for this call: ONE counter per call, over a batch too (the mask is keyed by the batch-global
-        row, models.SST.forward_batch)."""
-        tm = self.tap_model
-        p_drop = float(tm.rnn.dropout)
-        if tm._drop_seed is None:
-            tm._drop_seed = (int(torch.initial_seed()) ^ 0x55AA) & 0xFFFFFFFFFFFFFFFF
-        drop = EF.DropState(tm._drop_seed, tm._drop_calls, p_drop > 0.0)
-        if p_drop > 0.0:
-            tm._drop_calls += 1
-        return p_drop, drop
-
     def _sst_grads(self, B):
         """echr_sst_grads: the proposal encoder's gradient slots in its arena, d tap_feats and d scores from the buffers `B`."""
         ar, nps = self.tap_arena, self.tap_model.native_params()
@@ -819,7 +807,7 @@ class JointTrainStep(_JointStep):
             # the gradient span of the proposal encoder and d tap_feats: zero-filled HERE, off the chain that later leads to its backward
             ar.flat_g.zero_()
             B['g_tap'].zero_()
-            p_drop, drop = self._tap_drop()
+            p_drop, drop = tm._next_drop()
             sa = EF.SSTFunction._args(ps, c3d, p_drop, B['ws'], B['tap'], B['scores'])
             dc = drop.c()
             L.check(lib.echr_sst_fwd_states(C.byref(sa), C.byref(dc), L.stream_ptr()), 'sst_fwd_states')           # models/sst_model.py:31-37
@@ -871,7 +859,6 @@ class JointBatchStep(_JointStep):
         self._init_joint(fused, tap_model, tap_optim, lambda1, lambda2, tap_grad_clip)
         self.lam = torch.full((2,), self.lambda1, device=self.dev, dtype=torch.float32)
         self.lam[1] = self.lambda2
-        self._ro_cache = {}
         self.tap_loss = self.cg_loss = self.last_tap_losses = self.last_video_losses = None
         self.last_batch = None
 
@@ -891,13 +878,7 @@ class JointBatchStep(_JointStep):
 
     def _row_offsets(self, rows, T):
         ro = EF.sst_row_offsets(rows, T)
-        key = ro.tobytes()
-        ro_dev = self._ro_cache.get(key)
-        if ro_dev is None:          # (kept for the batches a loop repeats: a pageable host-to-device copy synchronises the stream)
-            if len(self._ro_cache) >= 64:
-                self._ro_cache.clear()
-            ro_dev = self._ro_cache[key] = torch.from_numpy(ro).to(self.dev)
-        return ro, ro_dev
+        return ro, self.tap_model.row_offsets_dev(ro, self.dev)
 
     def _sst_forward(self, c3d, rows):
         """The proposal encoder over the concatenated c3d rows into this object's buffers (echr_sst_fwd_batch; no graph): returns tap [T_tot, H]."""
@@ -913,7 +894,7 @@ class JointBatchStep(_JointStep):
         ro, ro_dev = self._row_offsets(rows, T)
         V = len(ro) - 1
         B = self._buffers(T, V, D, H, K)
-        p_drop, drop = self._tap_drop()
+        p_drop, drop = tm._next_drop()
         sa = EF.SSTFunction._args(ps, c3d, p_drop, B['ws'], B['tap'], B['scores'])
         bx = L.SstBatch(V, L.ptr(ro_dev, torch.int32), ro.ctypes.data)
         dc = drop.c()

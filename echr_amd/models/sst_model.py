@@ -51,19 +51,41 @@ class SST(nn.Module):
         return (r.weight_ih_l0, r.weight_hh_l0, r.bias_ih_l0, r.bias_hh_l0, r.weight_ih_l1, r.weight_hh_l1, r.bias_ih_l1, r.bias_hh_l1,
                 self.scores.weight, self.scores.bias)
 
-    def forward(self, features):
-        """features [T, video_dim] -> (tap_feats [T, hidden_dim], proposal scores [T, K] in (0,1))."""
-        if not features.is_cuda:
-            raise EF.L.EchrHipError('SST runs on the GPU only: move the module and its inputs with .cuda()')
+    def _next_drop(self):
+        """(p, DropState) of the inter-layer dropout for this call, and the counter moves on: ONE counter per call, over a batch too (the mask
+        is keyed by the batch-global row)."""
         p = float(self.rnn.dropout)
         if self._drop_seed is None:
             self._drop_seed = (int(torch.initial_seed()) ^ 0x55AA) & 0xFFFFFFFFFFFFFFFF
         drop = EF.DropState(self._drop_seed, self._drop_calls, p > 0.0)
         if p > 0.0:
             self._drop_calls += 1
+        return p, drop
+
+    def row_offsets_dev(self, ro, device):
+        """Device copy of validated offsets (EF.sst_row_offsets), kept for the batches a training loop repeats: a pageable host-to-device copy
+        synchronises the stream."""
+        key = (ro.tobytes(), str(device))
+        ro_dev = self._ro_cache.get(key)
+        if ro_dev is None:
+            if len(self._ro_cache) >= 64:
+                self._ro_cache.clear()
+            ro_dev = self._ro_cache[key] = torch.from_numpy(ro).to(device)
+        return ro_dev
+
+    def _run(self, features, ro=None):
+        """SSTFunction on one video (ro None) or on a batch with its validated offsets."""
+        p, drop = self._next_drop()
         arena = getattr(self, '_echr_arena', None)
         sink = EF.GradSink(arena, self.native_params()) if arena is not None else None
-        return EF.SSTFunction.apply(features, p, drop, sink, *self.native_params())
+        ro_dev = self.row_offsets_dev(ro, features.device) if ro is not None else None
+        return EF.SSTFunction.apply(features, ro, ro_dev, p, drop, sink, *self.native_params())
+
+    def forward(self, features):
+        """features [T, video_dim] -> (tap_feats [T, hidden_dim], proposal scores [T, K] in (0,1))."""
+        if not features.is_cuda:
+            raise EF.L.EchrHipError('SST runs on the GPU only: move the module and its inputs with .cuda()')
+        return self._run(features)
 
     def forward_batch(self, features, row_offset=None):
         """The encoder over V videos in one call.  `features`: the concatenated [T_tot, video_dim] matrix with `row_offset` [V+1] (video v owns
@@ -95,22 +117,7 @@ class SST(nn.Module):
                 raise EF.L.EchrHipError('SST runs on the GPU only: move the module and its inputs with .cuda()')
         if len(ro) == 2:
             return self.forward(features)          # one video: today's call (the library's batch entries reduce to it as well)
-        p = float(self.rnn.dropout)
-        if self._drop_seed is None:
-            self._drop_seed = (int(torch.initial_seed()) ^ 0x55AA) & 0xFFFFFFFFFFFFFFFF
-        drop = EF.DropState(self._drop_seed, self._drop_calls, p > 0.0)
-        if p > 0.0:
-            self._drop_calls += 1
-        arena = getattr(self, '_echr_arena', None)
-        sink = EF.GradSink(arena, self.native_params()) if arena is not None else None
-        # device copy of the offsets, kept for the batches a training loop repeats (a pageable host-to-device copy synchronises the stream)
-        key = (ro.tobytes(), str(features.device))
-        ro_dev = self._ro_cache.get(key)
-        if ro_dev is None:
-            if len(self._ro_cache) >= 64:
-                self._ro_cache.clear()
-            ro_dev = self._ro_cache[key] = torch.from_numpy(ro).to(features.device)
-        return EF.SSTBatchFunction.apply(features, ro, ro_dev, p, drop, sink, *self.native_params())
+        return self._run(features, ro)
 
     def build_arena(self):
         """Pack parameters and gradients into flat device buffers (echr_amd/arena.py): ClampAdam(..., arena=...) then updates the whole

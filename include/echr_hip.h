@@ -540,11 +540,13 @@ int echr_sst_bwd(const echr_sst_args* a, const echr_sst_grads* g, const echr_dro
  * of m_batch videos, train.py:281-283,313-317).  a->T is T_tot; x, tap_feats, scores and every saved activation use the concatenated
  * [T_tot, .] layout of the caption path's batches: video v owns rows [row_offset[v], row_offset[v+1]).  Every video starts from the zero
  * state.  The rows of video v equal what echr_sst_fwd gives for that video alone; parameter gradients are the SUM over the videos.  One
- * dropout counter per call: the inter-layer mask is keyed by the batch-global element (row_offset[v] + t) * H + u at site 5, so one video
- * reduces to echr_sst_fwd / echr_sst_bwd exactly.  Products over rows run once over T_tot rows; the recurrences carry a video axis:
- * the persistent form (H = 512) runs up to echr_sst_batch_group() videos through the register-resident weight slices per launch and
- * splits a larger batch into ceil(V / group) launches, the launch-per-step wavefront (any H) puts the videos on the grid.  Gradient
- * buffers, `zeroed` and the deterministic switch behave as in echr_sst_bwd. */
+ * dropout counter per call: the inter-layer mask is keyed by the batch-global element (row_offset[v] + t) * H + u at site 5.  These entries
+ * and the single-video ones above are wrappers around one forward and one backward: a batch of ONE video is echr_sst_fwd / echr_sst_bwd
+ * -- the same launches, the same bits, the device row_offset is not read, and a refusal behind the argument checks names "sst_fwd" /
+ * "sst_bwd".  Products over rows run once over T_tot rows; the recurrences carry a video axis: the persistent form (H = 512) runs up to
+ * echr_sst_batch_group() videos through the register-resident weight slices per launch and splits a larger batch into ceil(V / group)
+ * launches, the launch-per-step wavefront (any H) puts the videos on the grid.  Gradient buffers, `zeroed` and the deterministic switch
+ * behave as in echr_sst_bwd. */
 typedef struct {
     int32_t n_videos;                   /* V >= 1 */
     const int32_t* row_offset;          /* device [V+1], row_offset[0] = 0, strictly increasing, row_offset[V] = a->T */

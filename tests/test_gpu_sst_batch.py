@@ -92,14 +92,16 @@ def test_more_videos_than_one_launch_carries():
     _check(R.gpu_pass(R.module(params, D, H, K, True), x, wt, ws, ro), ref)
 
 
-def test_one_video_batch_equals_forward_bit_for_bit():
+@pytest.mark.parametrize('D,H,K,persist', [(500, 512, 16, 1), (500, 512, 16, 0), (20, 24, 8, 1)])
+def test_one_video_batch_equals_forward_bit_for_bit(D, H, K, persist):
     """V = 1 takes today's keys: outputs and gradients of forward_batch equal SST.forward on that video exactly.  Run in the fixed-order mode:
-    by default the split-K products of a short video add with atomics, so two runs of SST.forward itself differ in the last bit."""
+    by default the split-K products of a short video add with atomics, so two runs of SST.forward itself differ in the last bit.
+    On the persistent route, with sst_persist = 0 and on the small-H model: the wavefront kernels serve one video and a batch alike."""
     import echr_amd
-    D, H, K = 500, 512, 16
     params, (x, wt, ws, ro), _ = _case((9,), D, H, K, True)
     dev = torch.device('cuda')
     try:
+        _config(b'sst_persist', persist)
         echr_amd.set_deterministic(True)
         got = R.gpu_pass(R.module(params, D, H, K, True), x, wt, ws, ro)
         m = R.module(params, D, H, K, True)
@@ -111,12 +113,13 @@ def test_one_video_batch_equals_forward_bit_for_bit():
         from echr_amd import functional as EF
         m3 = R.module(params, D, H, K, True)
         ro3 = EF.sst_row_offsets(ro, x.shape[0])
-        t3, s3 = EF.SSTBatchFunction.apply(torch.from_numpy(x).to(dev), ro3, torch.from_numpy(ro3).to(dev), 0.5, EF.DropState(U.SEED, U.OFFSET, True), None,
-                                           *m3.native_params())
+        t3, s3 = EF.SSTFunction.apply(torch.from_numpy(x).to(dev), ro3, torch.from_numpy(ro3).to(dev), 0.5, EF.DropState(U.SEED, U.OFFSET, True), None,
+                                      *m3.native_params())
         ((t3 * torch.from_numpy(wt).to(dev)).sum() + (s3 * torch.from_numpy(ws).to(dev)).sum()).backward()
         torch.cuda.synchronize()
     finally:
         echr_amd.set_deterministic(False)
+        _config(b'sst_persist', 1)
     assert torch.equal(tap.detach().cpu(), torch.from_numpy(got['tap'])) and torch.equal(sc.detach().cpu(), torch.from_numpy(got['scores']))
     for k, p in m.named_parameters():
         assert np.array_equal(p.grad.cpu().numpy(), got['grads'][k]), k

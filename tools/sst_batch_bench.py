@@ -115,12 +115,15 @@ def main(argv=None):
     ap.add_argument('--iters', type=int, default=10)
     ap.add_argument('--out', type=str, default='')
     ap.add_argument('--stamps', action='store_true', help='also record per-step stamps of workgroup 0 (V = 1 / 8, T = 256)')
+    ap.add_argument('--cases', type=str, default='', help='comma-separated subset of V1,V4,V8,V16,mixed8 (default: all)')
     a = ap.parse_args(argv)
     lib = _lib.load()
     torch.manual_seed(0)
     m = models.setup_tap(synth.default_opt(video_dim=D, hidden_dim=H, K=K)).cuda()
     m.eval()          # timing only: no dropout (the mask costs one hash per element either way)
     cases = [('V1', [256]), ('V4', [256] * 4), ('V8', [256] * 8), ('V16', [256] * 16), ('mixed8', [32, 64, 96, 128, 160, 192, 224, 256])]
+    if a.cases:
+        cases = [c for c in cases if c[0] in a.cases.split(',')]
     res = dict(tool='sst_batch_bench', D=D, H=H, K=K, iters=a.iters, group=int(lib.echr_sst_batch_group()), device=torch.cuda.get_device_name(0))
     try:
         for persist, name in ((1, 'persistent'), (0, 'wavefront')):
