@@ -15,7 +15,7 @@ from torch import nn
 
 from . import functional as EF
 from . import models
-from .models.OldModel_NEW import ClipView
+from .models.OldModel_NEW import ClipView, caption_labels
 
 
 class CaptionGenerator(nn.Module):
@@ -235,26 +235,37 @@ class CaptionGenerator(nn.Module):
             raise NotImplementedError('scheduled sampling (ss_prob > 0) is never enabled by the reference and is not on the HIP path')
         # (the initial state once, with its graph: the two decodes read its values, the teacher-forced recompute carries the gradient)
         h0 = self._batch_initial_state(batch, video, event, ev_start, ev_len, vid)
-        h0_d = None if h0 is None else h0.detach()
-        if gen_result is None:
-            seed = lm._sample_seed() if seed is None else int(seed)
-            with torch.no_grad():
-                gen, _, video_words = EF.sample_train_batch(video, event.detach(), batch.clip_rows(), ev_start, ev_len, vid, A, lm.seq_length,
-                                                            lm.native_params(), drop, seed=seed, h0=h0_d)
-        else:
-            video_words = batch.caption_widths(gen_result)
-            gen = torch.as_tensor(gen_result)[:, :int(video_words.max())].to(device=batch.device, dtype=torch.int64).contiguous()
+        rows, ps = batch.clip_rows(), lm.native_params()
+
+        def sample(ev, h0_d):
+            gen, _, video_words = EF.sample_train_batch(video, ev, rows, ev_start, ev_len, vid, A, lm.seq_length, ps, drop,
+                                                        seed=lm._sample_seed() if seed is None else int(seed), h0=h0_d)
+            return gen, video_words
+        greedy = lambda ev, h0_d: EF.greedy_sample(video, ev, rows, ev_start, ev_len, A, lm.seq_length, ps, table_cache=lm.sample_tables(), vid=vid,
+                                                   h0=h0_d)[0]
+        logprobs = lambda gen: self._batch_decoder(batch, video, event, ev_start, ev_len, lm._tokens(caption_labels(gen), batch.device), A,
+                                                   EF.rows_disjoint(batch.soi), drop, h0, vid)
+        return self._self_critical(event, h0, gen_result, sample, greedy, logprobs, batch.caption_widths)
+
+    def _self_critical(self, event, h0, gen_result, sample, greedy, logprobs, widths=None):
+        """The one body of forward(mode='train_rl') and train_rl_batch.  `event` (and `h0`, or None) carry their graphs; the two decodes read
+        their values only: `sample(event, h0)` -> (gen or [], video_words or None) and `greedy(event, h0)` -> greedy_res get them detached
+        and run without a graph.  `gen_result` pins the sample instead (`widths(gen_result)`: its video_words, the batched form's cut).
+        `logprobs(gen)`: the teacher-forced log-probs of [0 | gen | 0] under the call's dropout state WITH the graph; they are gathered at
+        the tokens here.  Returns (gen, sample_logprobs, greedy_res), then video_words if there are any."""
+        ev_d, h0_d = event.detach(), None if h0 is None else h0.detach()
         with torch.no_grad():
-            greedy_res, _ = EF.greedy_sample(video, event.detach(), batch.clip_rows(), ev_start, ev_len, A, lm.seq_length, lm.native_params(),
-                                             table_cache=lm.sample_tables(), vid=vid, h0=h0_d)
+            if gen_result is None:
+                gen, video_words = sample(ev_d, h0_d)
+            else:
+                video_words = None if widths is None else widths(gen_result)
+                gen = torch.as_tensor(gen_result)
+                gen = (gen if widths is None else gen[:, :int(video_words.max())]).to(device=event.device, dtype=torch.int64).contiguous()
+            greedy_res = greedy(ev_d, h0_d)
+        tail = () if video_words is None else (video_words,)
         if isinstance(gen, list) or gen.numel() == 0:
-            return [], [], greedy_res, video_words          # every row drew <eos> first (OldModel.sample returns [] then, :186-187)
-        N, T = gen.shape
-        labels = torch.zeros(N, T + 2, dtype=torch.int64, device=gen.device)
-        labels[:, 1:T + 1] = gen
-        logp = self._batch_decoder(batch, video, event, ev_start, ev_len, lm._tokens(labels, batch.device), A, EF.rows_disjoint(batch.soi), drop,
-                                   h0, vid)
-        return gen, EF.GatherTokens.apply(logp, gen), greedy_res, video_words
+            return ([], [], greedy_res) + tail          # every row drew <eos> first (OldModel.sample returns [] then, :186-187)
+        return (gen, EF.GatherTokens.apply(logprobs(gen), gen), greedy_res) + tail
 
     def _event_context_groups(self, batch, groups, ech, ev_start, ev_len, vid, drop, params):
         """The event encoder of an inference batch, one call per run of videos (VideoBatch.event_groups), into one [N_tot, d_o] matrix.  The
@@ -319,20 +330,17 @@ class CaptionGenerator(nn.Module):
         eval mode without a graph, both on the same event context; `sample_logprobs` is the teacher-forced recompute of the sample under the
         SAME dropout state gathered at its tokens, so the gradient reaches the decoder, `event` and the encoder as mode='train' does."""
         lm = self.lm_model
-        if gen_result is None:
-            gen_result, _ = lm.sample_train(video, event.detach(), clip, clip_mask, drop)
-        else:
-            gen_result = torch.as_tensor(gen_result).to(device=event.device, dtype=torch.int64)
-        was_training = lm.training
-        lm.eval()
-        try:
-            with torch.no_grad():
-                greedy_res, _ = lm.sample(video, event.detach(), clip, clip_mask)
-        finally:
-            lm.train(was_training)
-        if isinstance(gen_result, list) or gen_result.numel() == 0:
-            return [], [], greedy_res                  # every row drew <eos> first (OldModel.sample returns [] then, :186-187)
-        return gen_result, lm.sequence_logprobs(video, event, clip, clip_mask, gen_result, drop=drop), greedy_res
+
+        def greedy(ev, _h0):
+            was_training = lm.training
+            lm.eval()
+            try:
+                return lm.sample(video, ev, clip, clip_mask)[0]
+            finally:
+                lm.train(was_training)
+        # (the initial state of CG_init_feats_type is made inside the decoder's own calls, from the event context each is given)
+        return self._self_critical(event, None, gen_result, lambda ev, _h0: (lm.sample_train(video, ev, clip, clip_mask, drop)[0], None), greedy,
+                                   lambda gen: lm(video, event, clip, clip_mask, caption_labels(gen), drop=drop))
 
     def change_context_dim(self):
         opt = self.opt

@@ -20,7 +20,7 @@ its own video's padded clip length.
 import numpy as np
 import torch
 
-from .models.OldModel_NEW import n_decoder_steps
+from .models.OldModel_NEW import caption_labels, n_decoder_steps
 
 _KEYS = ('c3d', 'tap', 'lda', 'ind', 'soi')
 
@@ -29,6 +29,47 @@ def _np(x, dtype):
     if isinstance(x, torch.Tensor):
         x = x.detach().cpu().numpy()
     return np.asarray(x, dtype=dtype)
+
+
+# whose reward: (it may be wider than T, its refusal) -- a batch's, a single video's, one video's of a batch from reward_fn
+_REWARD_FORMS = {'batch': (True, 'reward must be [N_tot, T] or [N_tot] (got %s for gen_result %s)'),
+                 'single': (False, 'reward must be [N, T] or [N] (got %s for gen_result %s)'),
+                 'video': (False, 'reward_fn must return [N_v, T_v] or [N_v] (got %s for a video of %s)')}
+
+
+def reward_matrix(reward, N, T, form='batch'):
+    """A reward [N] (one value per caption, broadcast over its steps) or [N, T] ('batch': [N, >= T]) as float32 [N, T]; any other shape
+    is the ValueError of `form` (_REWARD_FORMS)."""
+    wider, msg = _REWARD_FORMS[form]
+    r = _np(reward, np.float32)
+    if r.ndim == 1:
+        r = np.repeat(r[:, None], T, 1)
+    if (r.shape[0] != N or r.ndim != 2 or r.shape[1] < T) if wider else (r.shape != (N, T)):
+        raise ValueError(msg % (r.shape, (N, T)))
+    return r[:, :T]
+
+
+def sampled_criterion(gen, reward, widths, slices, form='batch'):
+    """RewardCriterion (misc/utils.py:48-59) of sampled captions as the reward-weighted one-call steps take it (host arrays).  gen
+    [N, >= T], reward [N] or [N, >= T] (reward_matrix, in `form`), and groups of rows `slices` with their own widths
+    `widths`, T = max(widths): the videos of a batch at their video_words, or one group at the width of the tensor it was given.  Returns
+    labels int64 [N, T+2] = [0 | gen | 0] (T+1 teacher-forced steps), mask float32 [N, T+1] -- [1 | gen > 0][:, :-1] over a group's own
+    width and zero from there on (at the batch's width the longest row of a narrower video would otherwise gain its <eos> position; the
+    step behind the last token, whose target is the trailing 0, always has mask 0) -- and reward * mask [N, T+1], undivided."""
+    g = _np(gen, np.int64)
+    T = int(max(widths)) if len(widths) else 0
+    if g.ndim != 2 or T > g.shape[1]:
+        raise ValueError('video_words %s exceed gen_result %s' % (list(map(int, widths)), g.shape))
+    g = g[:, :T]
+    r = reward_matrix(reward, len(g), T, form)
+    mask = np.zeros((len(g), T + 1), np.float32)
+    w = np.zeros_like(mask)
+    for s, wv in zip(slices, map(int, widths)):
+        if wv:
+            mask[s, 0] = 1.0
+            mask[s, 1:wv] = g[s, :wv - 1] > 0
+            w[s, :wv] = r[s, :wv] * mask[s, :wv]
+    return caption_labels(g), mask, w
 
 
 class VideoBatch(object):
@@ -326,14 +367,6 @@ class VideoBatch(object):
         words = (g != 0).sum(1)
         return np.asarray([int(words[s].max()) for s in self.event_slices], dtype=np.int64)
 
-    def _reward_matrix(self, reward, N, T):
-        r = _np(reward, np.float32)
-        if r.ndim == 1:
-            r = np.repeat(r[:, None], T, 1)
-        if r.shape[0] != N or r.ndim != 2 or r.shape[1] < T:
-            raise ValueError('reward must be [N_tot, T] or [N_tot] (got %s for gen_result %s)' % (r.shape, (N, T)))
-        return r[:, :T]
-
     def reward_criterion(self, crit, sample_logprobs, gen_result, reward, video_words):
         """RewardCriterion per video: `crit` on the rows of video v and its first video_words[v] columns -- the tensors that video's own
         call returns, so its longest row's <eos> position stays outside the criterion -- each video with its own normaliser sum(mask_v), no
@@ -346,7 +379,7 @@ class VideoBatch(object):
         N, T = gen.shape
         if int(vw.max()) > T or sample_logprobs.shape[0] != N or sample_logprobs.shape[1] < int(vw.max()):
             raise ValueError('video_words %s exceed gen_result %s / sample_logprobs %s' % (vw.tolist(), (N, T), tuple(sample_logprobs.shape)))
-        r = torch.from_numpy(np.ascontiguousarray(self._reward_matrix(reward, N, T)))
+        r = torch.from_numpy(np.ascontiguousarray(reward_matrix(reward, N, T)))
         per = []
         for s, w in zip(self.event_slices, vw.tolist()):
             if w == 0:
@@ -357,28 +390,16 @@ class VideoBatch(object):
         return per.sum(), per
 
     def reward_weights(self, gen_result, reward, video_words):
-        """The criterion of reward_criterion as the one-call step takes it (host arrays): labels int64 [N_tot, T+2] = [0 | gen | 0] (T+1
-        teacher-forced steps), mask float32 [N_tot, T+1] -- RewardCriterion's [1 | gen > 0][:, :-1], zero from the row's video's own width
-        on (at the batch's width the longest row of a narrower video would otherwise gain its <eos> position) -- and
+        """The criterion of reward_criterion as the one-call step takes it (host arrays): labels, mask and reward * mask of
+        `sampled_criterion` over the batch's videos, the weights divided by each video's own sum(mask) --
         w[n, t] = reward[n, t] * mask[n, t] / sum(mask of video vid[n]): the loss is sum(-logp[target] * w) with denominator 1."""
         g = _np(gen_result, np.int64)
         vw = np.asarray(video_words, dtype=np.int64).reshape(-1)
         if g.ndim != 2 or g.shape[0] != self.n_events or len(vw) != self.n_videos:
             raise ValueError('gen_result must be [%d events, T] and video_words [%d]' % (self.n_events, self.n_videos))
-        T = int(vw.max()) if len(vw) else 0
-        if T > g.shape[1]:
-            raise ValueError('video_words %s exceed gen_result %s' % (vw.tolist(), g.shape))
-        g = g[:, :T]
-        N = g.shape[0]
-        r = self._reward_matrix(reward, N, T)
-        labels = np.zeros((N, T + 2), np.int64)
-        labels[:, 1:T + 1] = g
-        mask = np.zeros((N, T + 1), np.float32)
-        w = np.zeros((N, T + 1), np.float32)
-        for s, wv in zip(self.event_slices, vw.tolist()):
-            if wv == 0:
-                continue
-            mask[s, 0] = 1.0
-            mask[s, 1:wv] = g[s, :wv - 1] > 0
-            w[s, :wv] = r[s, :wv] * mask[s, :wv] / mask[s, :wv].sum(dtype=np.float32)
+        slices = self.event_slices
+        labels, mask, w = sampled_criterion(g, reward, vw, slices)
+        for s, wv in zip(slices, vw.tolist()):
+            if wv:
+                w[s, :wv] /= mask[s, :wv].sum(dtype=np.float32)
         return labels, mask, w

@@ -12,11 +12,13 @@ accumulation, other consumers of the log-probs, joint training of the proposal e
 import ctypes as C
 import math
 import os
+from types import SimpleNamespace
 
 import numpy as np
 import torch
 
 from . import _lib as L
+from . import batch as VB
 from . import functional as EF
 from . import reward as RW
 from .models.OldModel_NEW import n_decoder_steps
@@ -507,23 +509,71 @@ class FusedTrainStep(object):
         return slot[0]
 
 
-class SelfCriticalStep(object):
-    """One self-critical training iteration (CaptionGenerator.py:32-37 + RewardCriterion, misc/utils.py:48-59; train.py:241-245, 303-308
-    past --self_critical_after) on the one-call path of `fused` (a FusedTrainStep):
+class _SelfCriticalIteration(object):
+    """What SelfCriticalStep and SelfCriticalBatchStep share: ONE self-critical training iteration (CaptionGenerator.py:32-37 +
+    RewardCriterion, misc/utils.py:48-59; train.py:241-245, 303-308 past --self_critical_after) on the one-call path of `fused` (a
+    FusedTrainStep):
 
-      event context in training mode under the iteration's dropout state -> sampled decode with the decoder's dropout active under the
-      same state (echr_decoder_sample_train) -> greedy baseline (eval mode, persistent decoder) -> ONE host sync -> reward_fn on the host
-      -> echr_train_step_rw on the teacher-forced tokens [0 | gen_result | 0] with the same dropout state: the encoder is recomputed, the
-      criterion weight is reward * mask, then clamp + Adam as FusedTrainStep does (applied-update counting included).
+      the event context in training mode under the iteration's dropout state -> the sampled decode with the decoder's dropout active under
+      the same state (or a pinned gen_result) -> the greedy baseline in eval mode -> the device reward, if any, queued behind both -> the
+      host reads -> the reward (device CiderDReward, host callable or an explicit `reward`) -> batch.sampled_criterion -> the
+      reward-weighted step on the teacher-forced tokens [0 | gen_result | 0] with the same dropout state: the encoder is recomputed, then
+      clamp + Adam as FusedTrainStep does (applied-update counting included).
 
-    `reward_fn(gen_result, greedy_res)` receives int64 host tensors [N,T] / [N,T'] and returns the reward [N,T] or [N] (one value per
-    caption, broadcast over its steps), e.g. CIDEr(gen) - CIDEr(greedy) on the decoded strings.  The recomputed event context equals the
-    sampling one within fp32 rounding (bitwise under echr_amd.set_deterministic(True)): the same kernels on the same inputs and masks."""
+    A class supplies what differs: its checks ahead of the reference rules and FusedTrainStep._begin, `_contexts`,
+    `_sample` / `_greedy` / `_device_reward` (how the decodes and the device reward are queued), `_read`, `_host_reward`, `_criterion` and
+    `_step`.  The recomputed event context equals the sampling one within fp32 rounding (bitwise under echr_amd.set_deterministic(True)):
+    the same kernels on the same inputs and masks."""
+    REWARD_FORM = 'batch'          # batch.reward_matrix's form of a whole reward; BEGIN: the arguments of FusedTrainStep._begin
 
     def __init__(self, fused, reward_fn=None):
         if not isinstance(fused, FusedTrainStep):
-            raise TypeError('SelfCriticalStep wraps a FusedTrainStep')
+            raise TypeError('%s wraps a FusedTrainStep' % type(self).__name__)
         self.fused, self.reward_fn = fused, reward_fn
+
+    def _iterate(self, x, gen_result, reward, step, refs, **launch):
+        """(loss 0-d device tensor, gen_result [N,T] int64 host, greedy_res [N,T'] int64 host, reward [N,T] fp32 host, the groups' widths)."""
+        on_device = RW.check_reward_refs(self.reward_fn, refs, reward)
+        self.fused._begin(*self.BEGIN)
+        if on_device:          # (uploads ahead of everything the iteration queues: a host-to-device copy waits for the stream)
+            refs = self.reward_fn.scorer.to(self.fused.dev).device_refs(refs)
+        with torch.no_grad():
+            c = self._contexts(x, gen_result, on_device)
+            self.last_event = c.event          # the event context the decodes read (inspection: the step recomputes it)
+            # both decodes and the device reward are queued ahead of the batched form's first read (the single-video sampled decode reads
+            # its own counts); the reward is read behind the drain the decodes pay anyway
+            sampled = self._sample(c) if gen_result is None else None
+            greedy_f = self._greedy(c)
+            r_dev = self._device_reward(c, sampled, greedy_f, refs) if on_device else None
+            gen_h, greedy, widths, slices = self._read(x, c, sampled, gen_result, greedy_f)
+        greedy_h = greedy.cpu() if isinstance(greedy, torch.Tensor) else torch.zeros(c.N, 0, dtype=torch.int64)
+        N, T = gen_h.shape[0], int(max(widths))          # (the rows of a pinned gen_result: _setup refuses a wrong count)
+        if T == 0:
+            raise ValueError('every caption drew <eos> at its first step: nothing to train on (OldModel.sample returns [] then)')
+        if r_dev is not None:
+            r = VB.reward_matrix(r_dev.cpu(), N, T, self.REWARD_FORM)          # (the stream is drained: a copy of N floats)
+            for s, wv in zip(slices, widths):          # one value per caption over its group's own width, zero behind it
+                r[s, wv:] = 0.0
+        elif reward is None:
+            if self.reward_fn is None:
+                raise ValueError('%s needs reward_fn or an explicit reward' % type(self).__name__)
+            r = self._host_reward(x, gen_h, greedy_h, widths, slices)
+        else:
+            r = np.ascontiguousarray(VB.reward_matrix(reward, N, T, self.REWARD_FORM))
+        labels, mask, w = self._criterion(x, gen_h, r, widths, slices)
+        return self._step(x, c, labels, mask, w, step, **launch), gen_h, greedy_h, torch.from_numpy(r), widths
+
+    def _criterion(self, x, gen_h, r, widths, slices):
+        return VB.sampled_criterion(gen_h, r, widths, slices, self.REWARD_FORM)
+
+
+class SelfCriticalStep(_SelfCriticalIteration):
+    """The self-critical iteration of ONE video: echr_decoder_sample_train (the slab-sum + draw pair), the persistent greedy decoder,
+    echr_train_step_rw with the criterion weight reward * mask (the step normalises with the mask).
+
+    `reward_fn(gen_result, greedy_res)` receives int64 host tensors [N,T] / [N,T'] and returns the reward [N,T] or [N] (one value per
+    caption, broadcast over its steps), e.g. CIDEr(gen) - CIDEr(greedy) on the decoded strings."""
+    BEGIN, REWARD_FORM = ('self_critical_step',), 'single'
 
     def batch(self, *args, **kwargs):
         """Multi-video batches (FusedTrainStep.batch) are not part of this step yet: the sampled and greedy decodes and the reward take one video per call."""
@@ -532,93 +582,71 @@ class SelfCriticalStep(object):
 
     def __call__(self, tap_feats, c3d_feats, lda_feats, ind_select_list, soi_select_list, gen_result=None, reward=None, step=True, refs=None):
         """Returns (loss 0-d device tensor, gen_result [N,T] int64 host, greedy_res [N,T'] int64 host, reward [N,T] fp32 host).
-        `gen_result` (optional): score these captions instead of drawing them (tests pin the sample this way); `reward` (optional): use
-        it instead of calling reward_fn.  step=False stops after the backward pass (gradients as `.grad` views, as FusedTrainStep).
-        `refs` (with an echr_amd.reward.CiderDReward as reward_fn): the packed references of the events in row order -- the reward is
-        then scored on the device behind the greedy decode and read behind the greedy decode's own stream drain."""
-        f = self.fused
-        m = f.model
-        lm = m.lm_model
-        on_device = RW.check_reward_refs(self.reward_fn, refs, reward)
-        f._begin('self_critical_step')
-        if on_device:          # (uploads, if any, ahead of everything the iteration queues)
-            refs = self.reward_fn.scorer.to(c3d_feats.device).device_refs(refs)
-        drop = lm.next_drop_state(m.fusion_model.enc_attn.dropout.p)
+        `gen_result` (optional): score these captions instead of drawing them (tests pin the sample this way), at the width they come
+        with; `reward` (optional): use it instead of calling reward_fn.  step=False stops after the backward pass (gradients as `.grad`
+        views, as FusedTrainStep).  `refs` (with an echr_amd.reward.CiderDReward as reward_fn): the packed references of the events in row
+        order -- the reward is then scored on the device behind the greedy decode and read behind the greedy decode's own stream drain."""
+        return self._iterate((tap_feats, c3d_feats, lda_feats, ind_select_list, soi_select_list), gen_result, reward, step, refs)[:4]
+
+    def _contexts(self, x, gen_result, on_device):
+        tap, c3d, lda, ind, soi = x
+        m = self.fused.model
+        drop = m.lm_model.next_drop_state(m.fusion_model.enc_attn.dropout.p)
         drop.training = m.training
-        with torch.no_grad():
-            ev = EF.event_index_tensors(soi_select_list, ind_select_list, c3d_feats.device, min(c3d_feats.shape[0], tap_feats.shape[0]))
-            video = m.get_video_context(tap_feats, c3d_feats, lda_feats, ind_select_list, soi_select_list)
-            clip, clip_mask = m.get_clip_context(tap_feats, c3d_feats, lda_feats, ind_select_list, soi_select_list, _ev=ev)
-            event = m.get_event_context(tap_feats, c3d_feats, lda_feats, ind_select_list, soi_select_list, _ev=ev, _drop=drop)
-            self.last_event = event          # the event context the decodes read (inspection: the step recomputes it)
-            if gen_result is None:
-                gen, _ = lm.sample_train(video, event, clip, clip_mask, drop)
-            else:
-                gen = torch.as_tensor(gen_result).to(dtype=torch.int64)
-            gen_d = gen.to(c3d_feats.device) if on_device and isinstance(gen, torch.Tensor) else None
-            was_training = lm.training
-            lm.eval()
-            try:
-                if on_device:
-                    greedy_f = lm.sample(video, event, clip, clip_mask, {'defer': True})
-                    if gen_d is not None and gen_d.shape[1] > 0:          # gen at its own width, the greedy decode at its device counts
-                        reward = self.reward_fn(gen_d, greedy_f.seq, refs, greedy_counts=greedy_f.counts)
-                    greedy, _ = greedy_f()
-                else:
-                    greedy, _ = lm.sample(video, event, clip, clip_mask)
-            finally:
-                lm.train(was_training)
-        # the one host sync of the iteration (the greedy decode's own counter read has already drained the stream)
-        gen_h = gen.cpu() if isinstance(gen, torch.Tensor) else torch.zeros(len(soi_select_list), 0, dtype=torch.int64)
-        greedy_h = greedy.cpu() if isinstance(greedy, torch.Tensor) else torch.zeros(len(soi_select_list), 0, dtype=torch.int64)
-        N, T = gen_h.shape
-        if T == 0:
-            raise ValueError('every caption drew <eos> at its first step: nothing to train on (OldModel.sample returns [] then)')
-        if reward is None:
-            if self.reward_fn is None:
-                raise ValueError('SelfCriticalStep needs reward_fn or an explicit reward')
-            reward = self.reward_fn(gen_h, greedy_h)
-        r = np.asarray(reward.cpu() if isinstance(reward, torch.Tensor) else reward, dtype=np.float32)
-        if r.ndim == 1:
-            r = np.repeat(r[:, None], T, 1)
-        if r.shape != (N, T):
-            raise ValueError('reward must be [N, T] or [N] (got %s for gen_result %s)' % (r.shape, (N, T)))
-        g = gen_h.numpy()
-        labels = np.zeros((N, T + 2), dtype=np.int64)
-        labels[:, 1:T + 1] = g
-        # RewardCriterion's mask [1 | seq > 0][:, :-1] over the T sampled positions; the teacher-forced pass has one step more (its target is
-        # the trailing 0), which gets mask and weight 0
-        mask = np.zeros((N, T + 1), dtype=np.float32)
-        mask[:, 0] = 1.0
-        mask[:, 1:T] = g[:, :T - 1] > 0
-        w = np.zeros((N, T + 1), dtype=np.float32)
-        w[:, :T] = r * mask[:, :T]
-        slot, st = f._setup(tap_feats, c3d_feats, lda_feats, labels, ind_select_list, soi_select_list, labels[:, 1:], mask, step, False, None,
-                            False, drop=drop, weights=w)
-        return f._launch(slot, st, False, rw=True), gen_h, greedy_h, torch.from_numpy(r)
+        ev = EF.event_index_tensors(soi, ind, c3d.device, min(c3d.shape[0], tap.shape[0]))
+        video = m.get_video_context(*x)
+        clip, clip_mask = m.get_clip_context(*x, _ev=ev)
+        event = m.get_event_context(*x, _ev=ev, _drop=drop)
+        # (a pinned gen_result goes to the device behind the contexts; the device reward scores it at its own width)
+        gen = None if gen_result is None else torch.as_tensor(gen_result).to(dtype=torch.int64)
+        return SimpleNamespace(N=len(soi), lm=m.lm_model, drop=drop, event=event, decode=(video, event, clip, clip_mask), gen=gen,
+                               gen_d=gen.to(c3d.device) if on_device and gen is not None else None)
+
+    def _sample(self, c):
+        return c.lm.sample_train(*c.decode, c.drop)[0]
+
+    def _greedy(self, c):
+        was_training = c.lm.training
+        c.lm.eval()
+        try:
+            return c.lm.sample(*c.decode, {'defer': True})
+        finally:
+            c.lm.train(was_training)
+
+    def _device_reward(self, c, sampled, greedy_f, refs):
+        gen_d = c.gen_d if sampled is None else sampled
+        if isinstance(gen_d, torch.Tensor) and gen_d.shape[1] > 0:          # gen at its own width, the greedy decode at its device counts
+            return self.reward_fn(gen_d, greedy_f.seq, refs, greedy_counts=greedy_f.counts)
+
+    def _read(self, x, c, sampled, gen_result, greedy_f):
+        greedy, _ = greedy_f()          # (the greedy decode's own counter read drains the stream)
+        gen = c.gen if sampled is None else sampled
+        gen_h = gen.cpu() if isinstance(gen, torch.Tensor) else torch.zeros(c.N, 0, dtype=torch.int64)
+        return gen_h, greedy, [gen_h.shape[1]], [slice(0, gen_h.shape[0])]          # one group: the tensor as it came
+
+    def _host_reward(self, x, gen_h, greedy_h, widths, slices):
+        return VB.reward_matrix(self.reward_fn(gen_h, greedy_h), gen_h.shape[0], widths[0], 'single')
+
+    def _step(self, x, c, labels, mask, w, step):
+        tap, c3d, lda, ind, soi = x
+        f = self.fused
+        slot, st = f._setup(tap, c3d, lda, labels, ind, soi, labels[:, 1:], mask, step, False, None, False, drop=c.drop, weights=w)
+        return f._launch(slot, st, False, rw=True)
 
 
-class SelfCriticalBatchStep(object):
-    """One self-critical training iteration over a multi-video batch (echr_amd.batch.VideoBatch) on the one-call path of `fused`: the
-    reference's m_batch = V protocol past --self_critical_after (train.py:241-245, 281-283, 303-308) without V sequential calls.
-
-      ONE training-mode event context over the batch under the iteration's dropout state -> the sampled decode of all N_tot rows with the
-      decoder's dropout active under that state (echr_decoder_sample_train_batch) -> the greedy baseline of all rows (eval mode) -> ONE
-      host sync (both decodes are queued before either is read) -> reward_fn per video on the host -> echr_train_step_batch on the
-      teacher-forced tokens [0 | gen_result | 0] with the same dropout state and the weights of VideoBatch.reward_weights: the loss is
-      the SUM over the videos of RewardCriterion, each video at its own width and with its own normaliser; gradients are summed over the
-      videos, then one clamp + Adam (applied-update counting as SelfCriticalStep).
+class SelfCriticalBatchStep(_SelfCriticalIteration):
+    """The self-critical iteration over a multi-video batch (echr_amd.batch.VideoBatch): the reference's m_batch = V protocol past
+    --self_critical_after (train.py:241-245, 281-283, 303-308) without V sequential calls.  ONE event context over the batch, the sampled
+    decode of all N_tot rows (echr_decoder_sample_train_batch, the one-launch multinomial step) and their greedy baseline, ONE host sync
+    (both decodes are queued before either is read), echr_train_step_batch with the weights of VideoBatch.reward_weights: the loss is the
+    SUM over the videos of RewardCriterion, each video at its own width and with its own normaliser; gradients are summed over the
+    videos, then one clamp + Adam.
 
     `reward_fn(gen_v, greedy_v)` is called once per video, in order, with that video's rows cut to its own widths -- the arguments a
     single-video SelfCriticalStep passes -- and returns [N_v, T_v] or [N_v]; it is not called for a video whose sample has width 0 (that
     video contributes loss 0 and no gradient); `current_video` names the video of the call in progress.  `last_video_losses` holds the
     per-video losses as a device vector [V]."""
-
-    def __init__(self, fused, reward_fn=None):
-        if not isinstance(fused, FusedTrainStep):
-            raise TypeError('SelfCriticalBatchStep wraps a FusedTrainStep')
-        self.fused, self.reward_fn = fused, reward_fn
-        self.last_video_losses, self.current_video = None, None
+    BEGIN, last_video_losses, current_video = ('self_critical_batch_step', 'a batch step'), None, None
 
     def __call__(self, batch, gen_result=None, reward=None, step=True):
         """Returns (loss 0-d device tensor, gen_result [N_tot,T] int64 host, greedy_res [N_tot,T'] int64 host, reward [N_tot,T] fp32 host,
@@ -630,87 +658,70 @@ class SelfCriticalBatchStep(object):
         counts) ahead of the iteration's one host read, and the [N_tot] reward is read behind the same stream drain; a video whose sample
         has width 0 gets reward 0, as with a callable.  A CiderDReward without batch.refs is a ValueError, batch.refs with a plain
         callable a TypeError."""
-        return self._run(batch, gen_result, reward, step, False, None, batch.refs)
+        return self._iterate(batch, gen_result, reward, step, batch.refs)
 
     def handover(self, batch, handover_cb=None, gen_result=None, reward=None, refs=None):
         """__call__(step=False) with the data-parallel hand-over points recorded, as FusedTrainStep.batch_handover (DataParallelBatchStep).
         `refs`: instead of batch.refs."""
-        return self._run(batch, gen_result, reward, False, True, handover_cb, batch.refs if refs is None else refs)
+        return self._iterate(batch, gen_result, reward, False, batch.refs if refs is None else refs, handover=True, handover_cb=handover_cb)
 
-    def _run(self, batch, gen_result, reward, step, handover, handover_cb, refs=None):
-        f = self.fused
-        m = f.model
-        lm = m.lm_model
-        m._check_batch_options(batch)          # (ahead of everything that touches the device)
-        on_device = RW.check_reward_refs(self.reward_fn, refs, reward)
-        f._begin('self_critical_batch_step', 'a batch step')
-        N, V = batch.n_events, batch.n_videos
-        gen_d = r_dev = None
-        if on_device:          # (uploads ahead of everything the iteration queues: a host-to-device copy waits for the stream)
-            refs = self.reward_fn.scorer.to(f.dev).device_refs(refs)
-            if gen_result is not None:
-                gen_d = torch.as_tensor(gen_result).to(f.dev)
-        with torch.no_grad():
-            video, event, ev_start, ev_len, A, vid, drop = m._batch_contexts(batch, None)
-            video = EF._f32c(video)
-            self.last_event = event          # the event context the decodes read (inspection: the step recomputes it)
-            ps = lm.native_params()
-            # (CG_init_feats_type: both decodes start from the batch's initial state; the step below recomputes it inside the call)
-            h0 = m._batch_initial_state(batch, video, event, ev_start, ev_len, vid)
-            sampled = None
-            if gen_result is None:
-                sampled = EF.sample_train_batch(video, event, batch.clip_rows(), ev_start, ev_len, vid, A, lm.seq_length, ps, drop,
-                                                seed=lm._sample_seed(), defer=True, h0=h0)
-            greedy_f = EF.greedy_sample(video, event, batch.clip_rows(), ev_start, ev_len, A, lm.seq_length, ps, table_cache=lm.sample_tables(),
-                                        vid=vid, defer=True, h0=h0)
-            if on_device:          # queued behind both decodes, ahead of the read; a pinned gen_result is scored at its own width
-                if sampled is not None:
-                    r_dev = self.reward_fn(sampled.seq, greedy_f.seq, refs, gen_counts=sampled.counts, greedy_counts=greedy_f.counts)
-                else:
-                    r_dev = self.reward_fn(gen_d, greedy_f.seq, refs, gen_width=min(gen_d.shape[1], lm.seq_length), greedy_counts=greedy_f.counts)
-            # the one host sync of the iteration: the first read drains the stream, both decodes included
-            if sampled is not None:
-                gen, _, vw = sampled()
-                gen_h = gen.cpu() if isinstance(gen, torch.Tensor) else torch.zeros(N, 0, dtype=torch.int64)
-            else:
-                vw = batch.caption_widths(gen_result)
-                gen_h = torch.as_tensor(np.asarray(gen_result.cpu() if isinstance(gen_result, torch.Tensor) else gen_result,
-                                                   dtype=np.int64))[:, :int(vw.max())].contiguous()
-            greedy, _ = greedy_f()
-        greedy_h = greedy.cpu() if isinstance(greedy, torch.Tensor) else torch.zeros(N, 0, dtype=torch.int64)
-        T = int(vw.max())
-        if T == 0:
-            raise ValueError('every caption drew <eos> at its first step: nothing to train on (OldModel.sample returns [] then)')
-        if r_dev is not None:
-            r1 = r_dev.cpu().numpy()          # (the stream is drained: a copy of N_tot floats)
-            r = np.zeros((N, T), dtype=np.float32)
-            for s, wv in zip(batch.event_slices, vw.tolist()):
-                r[s, :wv] = r1[s, None]
-        elif reward is None:
-            if self.reward_fn is None:
-                raise ValueError('SelfCriticalBatchStep needs reward_fn or an explicit reward')
-            gw = batch.caption_widths(greedy_h)
-            r = np.zeros((N, T), dtype=np.float32)
-            for v, (s, wv, wg) in enumerate(zip(batch.event_slices, vw.tolist(), gw.tolist())):
-                if wv == 0:
-                    continue
-                self.current_video = v
-                rv = self.reward_fn(gen_h[s, :wv], greedy_h[s, :wg])
-                rv = np.asarray(rv.cpu() if isinstance(rv, torch.Tensor) else rv, dtype=np.float32)
-                if rv.ndim == 1:
-                    rv = np.repeat(rv[:, None], wv, 1)
-                if rv.shape != (s.stop - s.start, wv):
-                    raise ValueError('reward_fn must return [N_v, T_v] or [N_v] (got %s for a video of %s)' % (rv.shape, (s.stop - s.start, wv)))
-                r[s, :wv] = rv
+    def _iterate(self, batch, *args, **launch):
+        self.fused.model._check_batch_options(batch)          # (ahead of the reference rules and of everything that touches the device)
+        return _SelfCriticalIteration._iterate(self, batch, *args, **launch)
+
+    def _contexts(self, batch, gen_result, on_device):
+        m = self.fused.model
+        # (a pinned gen_result goes to the device ahead of everything the iteration queues)
+        gen_d = torch.as_tensor(gen_result).to(self.fused.dev) if on_device and gen_result is not None else None
+        video, event, ev_start, ev_len, A, vid, drop = m._batch_contexts(batch, None)
+        video = EF._f32c(video)
+        # (CG_init_feats_type: both decodes start from the batch's initial state; the step recomputes it inside the call)
+        h0 = m._batch_initial_state(batch, video, event, ev_start, ev_len, vid)
+        return SimpleNamespace(N=batch.n_events, lm=m.lm_model, drop=drop, event=event, video=video, gen_d=gen_d, A=A, vid=vid, h0=h0,
+                               decode=(video, event, batch.clip_rows(), ev_start, ev_len))
+
+    def _sample(self, c):
+        return EF.sample_train_batch(*c.decode, c.vid, c.A, c.lm.seq_length, c.lm.native_params(), c.drop, seed=c.lm._sample_seed(), defer=True,
+                                     h0=c.h0)
+
+    def _greedy(self, c):
+        return EF.greedy_sample(*c.decode, c.A, c.lm.seq_length, c.lm.native_params(), table_cache=c.lm.sample_tables(), vid=c.vid, defer=True,
+                                h0=c.h0)
+
+    def _device_reward(self, c, sampled, greedy_f, refs):
+        if sampled is not None:          # the uncut sequences at their device counts; a pinned gen_result at its own width
+            return self.reward_fn(sampled.seq, greedy_f.seq, refs, gen_counts=sampled.counts, greedy_counts=greedy_f.counts)
+        width = min(c.gen_d.shape[1], c.lm.seq_length)
+        return self.reward_fn(c.gen_d, greedy_f.seq, refs, gen_width=width, greedy_counts=greedy_f.counts)
+
+    def _read(self, batch, c, sampled, gen_result, greedy_f):
+        # the one host sync of the iteration: the first read drains the stream, both decodes included
+        if sampled is not None:
+            gen, _, vw = sampled()
+            gen_h = gen.cpu() if isinstance(gen, torch.Tensor) else torch.zeros(c.N, 0, dtype=torch.int64)
         else:
-            r = np.ascontiguousarray(batch._reward_matrix(reward, N, T))
-        labels, mask, w = batch.reward_weights(gen_h, r, vw)
-        slot, st = f._setup(batch.tap, batch.c3d, video, labels, batch.ind, batch.soi, labels[:, 1:], mask, step, False, None, False,
-                            drop=drop, weights=w, batch=batch)
-        self.last_video_losses = f.last_video_losses = torch.empty(V, device=f.dev, dtype=torch.float32)
-        loss = f._launch(slot, st, False, rw=True, video_loss=self.last_video_losses, handover=handover and not step, handover_cb=handover_cb,
-                         keep=(video,))
-        return loss, gen_h, greedy_h, torch.from_numpy(r), vw
+            vw = batch.caption_widths(gen_result)
+            gen_h = torch.from_numpy(VB._np(gen_result, np.int64)[:, :int(vw.max())]).contiguous()
+        return gen_h, greedy_f()[0], vw, batch.event_slices
+
+    def _host_reward(self, batch, gen_h, greedy_h, vw, slices):
+        r = np.zeros(tuple(gen_h.shape), dtype=np.float32)
+        for v, (s, wv, wg) in enumerate(zip(slices, vw.tolist(), batch.caption_widths(greedy_h).tolist())):
+            if wv:
+                self.current_video = v
+                r[s, :wv] = VB.reward_matrix(self.reward_fn(gen_h[s, :wv], greedy_h[s, :wg]), s.stop - s.start, wv, 'video')
+        return r
+
+    def _criterion(self, batch, gen_h, r, vw, slices):
+        return batch.reward_weights(gen_h, r, vw)
+
+    def _step(self, batch, c, labels, mask, w, step, handover=False, handover_cb=None):
+        f = self.fused
+        slot, st = f._setup(batch.tap, batch.c3d, c.video, labels, batch.ind, batch.soi, labels[:, 1:], mask, step, False, None, False,
+                            drop=c.drop, weights=w, batch=batch)
+        self.last_video_losses = f.last_video_losses = torch.empty(batch.n_videos, device=f.dev, dtype=torch.float32)
+        return f._launch(slot, st, False, rw=True, video_loss=self.last_video_losses, handover=handover and not step, handover_cb=handover_cb,
+                         keep=(c.video,))
 
 
 class _JointStep(object):

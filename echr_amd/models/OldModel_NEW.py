@@ -64,6 +64,15 @@ def n_decoder_steps(seq):
     return S
 
 
+def caption_labels(gen):
+    """[0 | gen | 0]: the teacher-forced tokens of captions gen [N, T] as int64 [N, T+2] -- a torch tensor on gen's device or a numpy
+    array, as gen is."""
+    N, T = gen.shape
+    labels = torch.zeros(N, T + 2, dtype=torch.int64, device=gen.device) if isinstance(gen, torch.Tensor) else np.zeros((N, T + 2), np.int64)
+    labels[:, 1:T + 1] = gen
+    return labels
+
+
 class OldModel(nn.Module):
     def __init__(self, opt):
         super(OldModel, self).__init__()
@@ -291,10 +300,7 @@ class OldModel(nn.Module):
         `drop`, gathered at seq -- with the drop state of the sampled pass these are its `sampleLogprobs` up to each row's <eos>, and the
         gradient flows through the decoder into `event` like forward()'s (the sampling loop keeps no graph)."""
         seq = torch.as_tensor(seq)
-        N, T = seq.shape
-        labels = torch.zeros(N, T + 2, dtype=torch.int64, device=seq.device)
-        labels[:, 1:T + 1] = seq
-        logp = self.forward(video, event, clip, clip_mask, labels, drop=drop)
+        logp = self.forward(video, event, clip, clip_mask, caption_labels(seq), drop=drop)
         return EF.GatherTokens.apply(logp, seq)
 
 

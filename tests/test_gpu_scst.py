@@ -21,11 +21,7 @@ CASES = [('case_scst.npz', 'tiny'), ('case_scst_eos.npz', 'tiny_eos')]
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _rl_mask(gen):
-    mask = np.zeros(gen.shape, dtype=bool)
-    mask[:, 0] = True
-    mask[:, 1:] = gen[:, :-1] > 0
-    return mask
+_rl_mask = U.rl_mask
 
 
 def _check_grads(named, ref):

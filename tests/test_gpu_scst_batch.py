@@ -38,14 +38,7 @@ def _batch(videos):
     return VideoBatch.from_videos([{k: v[k] for k in ('c3d', 'tap', 'lda', 'ind', 'soi')} for v in videos], device=torch.device('cuda'))
 
 
-def _rl_mask(gen, widths=None, vid=None):
-    """RewardCriterion's mask; with widths / vid cut to each row's video's own width."""
-    mask = np.zeros(gen.shape, dtype=bool)
-    mask[:, 0] = True
-    mask[:, 1:] = gen[:, :-1] > 0
-    if widths is not None:
-        mask &= np.arange(gen.shape[1])[None, :] < np.asarray(widths)[np.asarray(vid)][:, None]
-    return mask
+_rl_mask = U.rl_mask
 
 
 def _check_grads(named, ref, tol=TOL_GRAD):

@@ -92,6 +92,17 @@ def run_gpu(opt, params, vid, train_mode, backward=True):
     return pred.detach().cpu().numpy(), float(loss.detach()), grads, m
 
 
+def rl_mask(gen, widths=None, vid=None):
+    """RewardCriterion's mask [1 | gen > 0][:, :-1] of captions gen [N, T] (bool); with widths [V] / vid [N] cut to each row's video's own
+    width.  An independent statement of the formula, not a call of echr_amd.batch.sampled_criterion."""
+    mask = np.zeros(gen.shape, dtype=bool)
+    mask[:, 0] = True
+    mask[:, 1:] = gen[:, :-1] > 0
+    if widths is not None:
+        mask &= np.arange(gen.shape[1])[None, :] < np.asarray(widths)[np.asarray(vid)][:, None]
+    return mask
+
+
 def relerr(a, b, floor=0.0):
     """max|a-b| relative to the reference tensor's max-norm (`floor` = scale below which a tensor counts as numerical zero)."""
     a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
