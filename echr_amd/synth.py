@@ -347,6 +347,106 @@ def make_attsat(name, clip_context_type='CC'):
     return opt, params, vid
 
 
+# The decoder's three LSTM streams at TRAINED-WEIGHT scales.  make_params draws layer{0,1,2}.weight_* in +-1/sqrt(512) and the embedding in +-0.1:
+# gate pre-activations stay below 1.1, cell states below 0.7, and the attended context (rows from N(0, 1)) below 4.  The variants below leave
+# that regime by SCALING only (no stored weights), at the ECHR widths (H = Ha = 512, D = 500: the persistent kernels' shape), vocabulary 300,
+# greedy decoding over seq_length 19:
+#   embed / ih / hh   scale of embed.weight and of weight_ih / weight_hh of all three layers
+#   forget / igate    added to bias_ih[H:2H] / bias_ih[0:H] of all three layers
+#   steps             teacher-forced decoder steps (default 6)
+#   feat              (lo, hi): C3D row r is multiplied by 2^e_r, e_r a uniform integer in [lo, hi] (RandomState(video seed + 1000)): the bound on
+#                     |context| of the persistent kernels' fp32 -> fp16-pair conversion differs from event to event by up to 14 binades
+#   c2a_w             scale of ctx2att.weight (keeps |p| inside the factored tanh's domain under `feat`)
+#   plant 'events'    event 0 becomes rows [0, 3) and those rows are zeroed (context bound 0); one element of event 1 becomes the power of two
+#                     just above every other |element| of that event (the exponent boundary of the bound); event 2 becomes the ONE row that
+#                     holds the video's largest |element|: its attended context IS that row (|context| = 216, where the average over a longer
+#                     event stays far below its bound), so a conversion factor formed for the usual |context| < 8 overflows fp16 there
+#   plant 'big'       events 0..3 are laid out back to back -- 130 rows, 258 rows, 100 rows, one row that belongs to none of the four, 173 rows.
+#                     Events 0, 1, 3 are quiet (row exponents lo .. lo + 3: |element| < 0.3) but for ONE element of 4096: in slot 129 of event 0
+#                     (its last, the first of the second slot set), in the last slot of event 1, in slot 129 of event 3.  Spread over the event
+#                     by the near-uniform attention it leaves |context| ~ 4096 / length = 16 .. 32, a hundred times the other rows' bound: a
+#                     maximum that misses that slot gives a conversion factor under which the context overflows fp16.  The row just PAST
+#                     event 2's end holds 16384 and must not enter event 2's bound
+#   vbatch            a multi-video batch (make_vbatch_videos) instead of one video
+# Video seeds of the decoded variants: the first of 91, 191, ... (92, 192, ...; 93, ...; 94, ...; 95, ...) whose float64-oracle greedy decode keeps a
+# top-1 / top-2 margin above 1e-4 at every step of every unfinished row (91 .. 94 hold it; 95 and 195 miss it: 4.0e-5, 4.9e-5) -- and, for
+# gates_sat70, whose float32-oracle log-prob error stays below a third of the 1e-4 contract: over 70 events the float32 reference itself costs
+# 3.1e-5 .. 5.1e-5 in train mode (log-probs of -50 have an ulp of 3.8e-6), so 4 e_ref leaves the contract at every seed and the gate there is the
+# contract itself (295 holds the margin with e_ref 5.1e-5; 395: 3.1e-5).  tests/test_decoder_regime_host.py asserts all of it.
+_GATES_SAT = dict(embed=10.0, ih=16.0, hh=12.0, forget=1.0)
+_FEAT_WIDE = dict(feat=(-8, 6), c2a_w=2.0 ** -6)
+DECSAT = {
+    'gates_sat': dict(_GATES_SAT, video=dict(N=12, A=40, seed=91)),
+    'drift': dict(embed=10.0, ih=4.0, hh=2.0, forget=8.0, igate=3.0, steps=20, video=dict(N=12, A=40, seed=92)),
+    'feat_wide': dict(_FEAT_WIDE, plant='events', video=dict(N=12, A=40, seed=93)),
+    # events of up to 258 segments: the BIG instantiation of the persistent kernels (129 < A <= 258)
+    'feat_wide_big': dict(_FEAT_WIDE, plant='big', video=dict(N=10, A=258, seed=94, T_v=700, min_len=100)),
+    # more than 64 rows: the launch-per-phase recurrences in training, the chain sampler in decoding
+    'gates_sat70': dict(_GATES_SAT, video=dict(N=70, A=40, seed=395)),
+    'gates_sat_vb': dict(_GATES_SAT, vbatch=dict(V=3, events=(3, 6), max_events=16, seg=(3, 40), T=(40, 80), L=(6, 8), seed=96)),
+}
+DECSAT_BIG_LENS = (130, 258, 100, 173)
+DECSAT_BIG_TOP = np.float32(4096.0)
+
+
+def decsat_event_max(vid, n):
+    """(largest |C3D| element of event n, its slot)."""
+    s, e = (int(x) for x in vid['soi'][n])
+    a = np.abs(vid['c3d'][s:e])
+    return float(a.max()), int(np.unravel_index(int(a.argmax()), a.shape)[0])
+
+
+def _pow2_above(x):
+    return float(2.0 ** (math.floor(math.log2(x)) + 1))
+
+
+def make_decsat(name):
+    """(opt, params, video) of a trained-decoder-regime case (see DECSAT); 'gates_sat_vb': (opt, params, [videos])."""
+    c = DECSAT[name]
+    f32 = np.float32
+    opt = default_opt(vocab_size=300, seq_length=19)
+    H = opt.CG_rnn_size
+    params = make_params(opt, 0)
+    params['lm_model.embed.weight'] = (params['lm_model.embed.weight'] * f32(c.get('embed', 1.0))).astype(f32)
+    for k in range(3):
+        pre = 'lm_model.core.layer%d.' % k
+        params[pre + 'weight_ih'] = (params[pre + 'weight_ih'] * f32(c.get('ih', 1.0))).astype(f32)
+        params[pre + 'weight_hh'] = (params[pre + 'weight_hh'] * f32(c.get('hh', 1.0))).astype(f32)
+        params[pre + 'bias_ih'][:H] += f32(c.get('igate', 0.0))
+        params[pre + 'bias_ih'][H:2 * H] += f32(c.get('forget', 0.0))
+    att = 'lm_model.core.attention.'
+    params[att + 'ctx2att.weight'] = (params[att + 'ctx2att.weight'] * f32(c.get('c2a_w', 1.0))).astype(f32)
+    V1 = opt.CG_vocab_size + 1
+    if 'vbatch' in c:
+        return opt, params, make_vbatch_videos(V1=V1, **c['vbatch'])
+    vid = make_video(L=c.get('steps', 6) + 1, V1=V1, **c['video'])
+    c3d, soi = vid['c3d'], vid['soi']
+    if 'feat' in c:
+        lo, hi = c['feat']
+        e = np.random.RandomState(c['video']['seed'] + 1000).randint(lo, hi + 1, size=c3d.shape[0])
+        if c.get('plant') == 'big':
+            starts = (0, 130, 388, 489)          # row 488: just past event 2's end, inside none of the four
+            for n, (s, l) in enumerate(zip(starts, DECSAT_BIG_LENS)):
+                soi[n] = (s, s + l)
+                if n != 2:
+                    e[s:s + l] = lo + (e[s:s + l] - lo) % 4          # the quiet events: exponents lo .. lo + 3
+        c3d *= np.ldexp(f32(1.0), e).astype(f32)[:, None]
+    if c.get('plant') == 'events':
+        soi[0] = (0, 3)
+        c3d[0:3] = 0.0
+        r = int(np.abs(c3d).max(1).argmax())
+        soi[2] = (r, r + 1)
+        s, e = (int(x) for x in soi[1])
+        c3d[s + (e - s) // 2, 7] = -f32(_pow2_above(np.abs(c3d[s:e]).max()))
+    elif c.get('plant') == 'big':
+        c3d[0 + 129, 3] = DECSAT_BIG_TOP
+        c3d[130 + 257, 499] = -DECSAT_BIG_TOP
+        c3d[488, 11] = f32(4.0) * DECSAT_BIG_TOP
+        c3d[489 + 129, 250] = DECSAT_BIG_TOP
+    vid['ind'] = (soi[:, 1] - 1).astype(np.int64)
+    return opt, params, vid
+
+
 # Multi-video batches (echr_amd/batch.py): V videos of a few events each, as caption pre-training on ground-truth events sees them
 # (train.py:268-271), with ragged event counts, event lengths, video lengths and label widths.  Video v of a case is
 # make_video(seed = case seed + v); the per-video shapes come from one RandomState(case seed).

@@ -213,6 +213,31 @@ def do_attsat():
     print('  wrote case_attsat.npz (%d arrays)' % len(out))
 
 
+def do_decsat():
+    """The decoder recurrences at trained-weight scales (synth.make_decsat): the reference's own CPU passes on 'gates_sat' (a sixth of the gate
+    pre-activations beyond +-8) and 'drift' (cell states up to 19, 20 steps), eval and train mode, in the summary format of the other cases ->
+    tests/golden/case_decsat.npz (keys '<variant>|...')."""
+    out = {}
+    for name in ('gates_sat', 'drift'):
+        opt, params, vid = synth.make_decsat(name)
+        m = build_ref(opt, params)
+        for mode in ('eval', 'train'):
+            pred, loss, grads = run_ref(m, vid, mode == 'train', opt)
+            opred, oloss, ograds = run_oracle(opt, params, vid, mode == 'train')
+            dev = max(rel(ograds[k], grads[k]) for k in grads if grads[k] is not None)
+            print('[decsat %s/%s] loss %.6f | oracle-vs-ref: max|dlogp| %.2e  dloss %.2e  max rel grad %.2e'
+                  % (name, mode, loss, np.abs(opred - pred).max(), abs(oloss - loss), dev))
+            assert np.abs(opred - pred).max() < 2e-5 and abs(oloss - loss) < 1e-5 and dev < 1e-4
+            tag = name + '|' + mode
+            out[tag + '|loss'] = np.float64(loss)
+            for k, v in SM.summarize_logp(pred).items():
+                out[tag + '|logp|' + k] = v
+            for k, v in SM.summarize_grads(grads).items():
+                out[tag + '|grad|' + k] = v
+    np.savez_compressed(os.path.join(GOLD, 'case_decsat.npz'), **out)
+    print('  wrote case_decsat.npz (%d arrays)' % len(out))
+
+
 def do_c5():
     """BASELINE config 5 as ONE unit: the reference's SST (eval: no inter-layer dropout, sst_model.py:25-26) over a 256-segment video
     -> tap_feats -> reference CaptionGenerator on 64 proposals of 4..256 segments -> lambda1 * tap_loss + lambda2 * cg_loss
@@ -575,12 +600,12 @@ if __name__ == '__main__':
     ap = argparse.ArgumentParser()
     ap.add_argument('--cases', nargs='*', default=['tiny', 'c1', 'c2', 'c2full', 'c3bench'])
     ap.add_argument('--skip-aux', action='store_true')
-    ap.add_argument('--only', choices=['position', 'adam', 'proposals', 'checkpoint', 'sst', 'c5', 'eosmix', 'peaked', 'attsat'], help='regenerate one auxiliary fixture only')
+    ap.add_argument('--only', choices=['position', 'adam', 'proposals', 'checkpoint', 'sst', 'c5', 'eosmix', 'peaked', 'attsat', 'decsat'], help='regenerate one auxiliary fixture only')
     a = ap.parse_args()
     os.makedirs(GOLD, exist_ok=True)
     torch.manual_seed(0)
     if a.only:
-        {'position': do_position, 'adam': do_adam, 'proposals': do_proposals, 'checkpoint': do_checkpoint, 'sst': do_sst, 'c5': do_c5, 'eosmix': do_eosmix, 'peaked': do_peaked, 'attsat': do_attsat}[a.only]()
+        {'position': do_position, 'adam': do_adam, 'proposals': do_proposals, 'checkpoint': do_checkpoint, 'sst': do_sst, 'c5': do_c5, 'eosmix': do_eosmix, 'peaked': do_peaked, 'attsat': do_attsat, 'decsat': do_decsat}[a.only]()
         sys.exit(0)
     if not a.skip_aux:
         do_position()
@@ -592,5 +617,6 @@ if __name__ == '__main__':
         do_eosmix()
         do_peaked()
         do_attsat()
+        do_decsat()
     for c in a.cases:
         do_case(c)

@@ -8,7 +8,12 @@ present, the HIP path's errors beside them.
 
 --sst: the proposal encoder's trained-regime variants (tests/proposal_regime_ref.py) -- e_ref per variant, mode and one video / batch (the E_REF table
 of tests/test_gpu_proposal_regime.py holds the largest of each column) and, when a GPU is present, the HIP path against the same float64 oracle beside
-it, persistent and wavefront."""
+it, persistent and wavefront.
+
+--decsat: the decoder recurrences' trained-regime variants (synth.make_decsat, tests/decoder_regime_ref.py) -- e_ref per variant and mode (log-probs,
+loss, worst gradient tensor, worst LSTM gate slice; the E_REF table of tests/test_gpu_decoder_regime.py holds the larger of eval and train) and, when a
+GPU is present, the HIP path against the same float64 oracle beside it per route: persistent on fp16 pairs, persistent in exact fp32,
+launch-per-phase (70 events: the launch form alone; the batch: forward_batch)."""
 import sys, os; sys.path.insert(0, os.environ.get('GRAFT_REPO_ROOT', '/root/repo')); sys.path.insert(0, os.path.join(os.environ.get('GRAFT_REPO_ROOT', '/root/repo'), 'tests'))
 import numpy as np, torch
 import util as U
@@ -76,6 +81,34 @@ def sst_report():
                 print(line, flush=True)
 
 
+def decsat_report():
+    from tests import decoder_regime_ref as D
+    gpu = torch.cuda.is_available()
+    if gpu:
+        from tests import test_gpu_decoder_regime as T
+    fmt = 'logp %.1e loss %.1e grad %.1e slice %.1e'
+    pick = lambda e: (e[0], e[1], e[2], e[4])
+    for name in synth.DECSAT:
+        for train in (False, True):
+            line = '%-14s %s  e_ref: ' % (name, 'train' if train else 'eval ') + fmt % pick(D.e_ref(name, train))
+            if gpu:
+                ref = D.oracle(name, train)
+                if name == 'gates_sat_vb':
+                    runs = [('forward_batch', T.batch_module_pass(train))]
+                else:
+                    runs = [(r, T._module_pass(name, train, r)) for r in (T.ROUTES if name in T.PERSISTENT else ('launch',))]
+                for route, got in runs:
+                    line += ' | HIP %s: ' % route + fmt % pick(D.errors(got, ref))
+            print(line, flush=True)
+    line = 'drift, one step from the state of largest |c|  e_ref: logp %.1e h %.1e c %.1e' % D.drift_step_e_ref()
+    if gpu:
+        line += ' | HIP: logp %.1e h %.1e c %.1e' % tuple(T.drift_step_errors())
+    print(line, flush=True)
+
+
+if '--decsat' in sys.argv:
+    decsat_report()
+    sys.exit(0)
 if '--sst' in sys.argv:
     sst_report()
     sys.exit(0)
