@@ -3,7 +3,8 @@
 Same constructor side effects on `opt` (video/event/clip_context_dim, :56-84), same `forward`
 signature and live modes ('train' -> log-probs [N,S,V+1]; 'eval' -> (seq, logp); 'train_rl' -> (gen_result, sample_logprobs,
 greedy_res), self-critical training), same sub-module
-names (`fusion_model`, `lm_model`) and state_dict keys.  The three context levels are built without
+names (`fusion_model`, `lm_model`) and state_dict keys (event_context_type 'EC' / 'EH' builds no
+`fusion_model`, as in the reference).  The three context levels are built without
 python loops over events: index lists are uploaded once as int32 (start, length, anchor) vectors and
 every kernel addresses the video features through them.
 """
@@ -19,17 +20,29 @@ from .models.OldModel_NEW import ClipView, caption_labels
 
 
 class CaptionGenerator(nn.Module):
+    # event_context_type (CaptionGenerator.py:106-137), exact values: through the TSRM event encoder -> which of (pooled C3D rows, anchor state)
+    # it reads; EVENT_DIRECT: the same pieces AS the event vector, no encoder (the "captioner without event relations" ablation)
+    EVENT_ENCODED = {'ER1': 1, 'ER2': 2, 'ER3': 3}
+    EVENT_DIRECT = {'EC': 1, 'EH': 2}
+
     def __init__(self, opt):
         super(CaptionGenerator, self).__init__()
         self.opt = opt
+        et = opt.event_context_type
+        if et not in self.EVENT_ENCODED and et not in self.EVENT_DIRECT:
+            raise NotImplementedError("event_context_type=%r: the live values are ER1 / ER2 / ER3 (through the TSRM event encoder) and EC / EH (the "
+                                      "event vector itself, no encoder).  The reference runs no other: 'EC' and 'EH' together ('ECEH', 'EC+EH') fail in "
+                                      "get_event_context, where torch.cat(event_feats, 0) joins a video_dim-wide and a hidden_dim-wide tensor along dim 0 "
+                                      "(CaptionGenerator.py:132-133), and a value with neither ('') returns None (:134-135), which the decoder's "
+                                      "torch.cat((xt, None)) refuses" % (et,))
         self.change_context_dim()
-        if 'TSRM' in opt.fusion_model and 'ER' in opt.event_context_type:
+        if 'TSRM' in opt.fusion_model and et in self.EVENT_ENCODED:          # ('EC' / 'EH': no fusion_model attribute, no fusion_model.* keys)
             self.fusion_model = models.setup_fusion(opt)
         self.lm_model = models.setup_lm(opt)
         self.overlap_encoder = os.environ.get('ECHR_OVERLAP_ENCODER', '1') != '0'        # 'train' mode: run the decoder's event-independent precompute concurrently with the event encoder
-        if not any(k in opt.video_context_type for k in ('VL', 'VC', 'VH')) or opt.event_context_type not in ('ER1', 'ER2', 'ER3') or not self.clip_parts():
+        if not any(k in opt.video_context_type for k in ('VL', 'VC', 'VH')) or not self.clip_parts():
             raise NotImplementedError('the HIP path implements the ECHR recipe: video_context_type from VL / VC / VH (any combination), '
-                                      'event_context_type ER1 / ER2 / ER3, clip_context_type CC / CH / CC+CH (experiments/train_ECHR.sh, opts.py:130)')
+                                      'event_context_type ER1 / ER2 / ER3 / EC / EH, clip_context_type CC / CH / CC+CH (experiments/train_ECHR.sh, opts.py:130)')
         if self.clip_parts() & 2 and 'C' in opt.CG_init_feats_type:
             raise NotImplementedError("clip_context_type with 'CH' and a CG_init_feats_type that reads the clip: the initial state's clip mean has "
                                       "no gradient into tap_feats on the HIP path")
@@ -39,6 +52,15 @@ class CaptionGenerator(nn.Module):
         proposal encoder's states), 3 = both, C3D first ('CC+CH', also spelt 'CCCH'); 0 = neither."""
         ct = self.opt.clip_context_type
         return (1 if 'CC' in ct else 0) | (2 if 'CH' in ct else 0)
+
+    def event_direct(self):
+        """0: the event context goes through the event encoder ('ER1' / 'ER2' / 'ER3'); 1 = 'EC' (the mean of the event's C3D rows), 2 = 'EH' (the
+        proposal encoder's state at the event's anchor): the event vector itself, no `fusion_model` (echr_train_step_args.event_direct)."""
+        return self.EVENT_DIRECT.get(self.opt.event_context_type, 0)
+
+    def encoder_dropout_p(self):
+        """The dropout probability of the event encoder's one site; 0.0 without an encoder ('EC' / 'EH': no site is drawn)."""
+        return self.fusion_model.enc_attn.dropout.p if hasattr(self, 'fusion_model') else 0.0
 
     def _require_live_decoder(self):
         if type(self.lm_model).__name__ != 'ThreestreamModel':
@@ -76,7 +98,7 @@ class CaptionGenerator(nn.Module):
         if not c3d_feats.is_cuda:
             raise EF.L.EchrHipError('CaptionGenerator runs on the GPU only: move the module and its inputs with .cuda()')
         ev = EF.event_index_tensors(soi_select_list, ind_select_list, c3d_feats.device, min(c3d_feats.shape[0], tap_feats.shape[0]))
-        drop = self.lm_model.next_drop_state(self.fusion_model.enc_attn.dropout.p if hasattr(self, 'fusion_model') else 0.0)
+        drop = self.lm_model.next_drop_state(self.encoder_dropout_p())
         drop.training = self.training
         video = self.get_video_context(tap_feats, c3d_feats, lda_feats, ind_select_list, soi_select_list)
         clip, clip_mask = self.get_clip_context(tap_feats, c3d_feats, lda_feats, ind_select_list, soi_select_list, _ev=ev)
@@ -108,6 +130,8 @@ class CaptionGenerator(nn.Module):
         run of `batch.event_groups(G)` -- consecutive videos with at most G events together -- so that the pair work and the workspace are bounded
         by G * N_tot instead of N_tot^2; a run of one video takes the single-video encoder with that video's own inference bounds (the tabulated
         pair MLP of large inference calls).  The greedy decode stays ONE call over all rows.  The training backward is not grouped.
+        With event_context_type 'EC' / 'EH' there is no event encoder: `event_group_rows` is accepted and has no effect (it only bounds the
+        encoder's pair work), here and in beam_batch.
         `beam_size` stays 1 here: beam search over a batch is `beam_batch`."""
         if mode == 'train_rl':
             raise NotImplementedError("mode='train_rl' takes one video per call: self-critical training over a batch is "
@@ -164,11 +188,17 @@ class CaptionGenerator(nn.Module):
             raise ValueError("mode='train' needs a batch with labels")
         ev_start, ev_len, ind, A = EF.event_index_tensors(batch.soi, batch.ind, batch.device, batch.c3d.shape[0])
         vid = batch.dev('vid')
-        lm, fm = self.lm_model, self.fusion_model
-        drop = lm.next_drop_state(fm.enc_attn.dropout.p)
+        lm = self.lm_model
+        drop = lm.next_drop_state(self.encoder_dropout_p())
         drop.training = self.training
         video = self.get_video_context_batch(batch)
-        parts = {'ER1': 1, 'ER2': 2, 'ER3': 3}[self.opt.event_context_type]
+        if self.event_direct():
+            # 'EC' / 'EH': ev_start / ind are batch-absolute, so the pooled rows / the anchors' states of all videos ARE the event vectors;
+            # there is no pair work for `groups` to bound
+            event = EF.EventPoolGather.apply(batch.c3d, batch.tap, ev_start, ev_len, ind, self.event_direct())
+            return video, event, ev_start, ev_len, A, vid, drop
+        fm = self.fusion_model
+        parts = self.EVENT_ENCODED[self.opt.event_context_type]
         ech = EF.EventPoolGather.apply(batch.c3d, batch.tap, ev_start, ev_len, ind, parts)
         params = fm.native_params()
         infer = not (torch.is_grad_enabled() and (ech.requires_grad or any(p.requires_grad for p in params)))
@@ -370,9 +400,12 @@ class CaptionGenerator(nn.Module):
 
     def get_event_context(self, tap_feats, c3d_feats, lda_feats, ind_select_list, soi_select_list, _ev=None, _drop=None):
         """TSRM over the per-event features (CaptionGenerator.py:106-130): 'ER1' the mean-pooled C3D rows, 'ER2' the SST state at the anchor,
-        'ER3' (the recipe) both, concatenated."""
+        'ER3' (the recipe) both, concatenated.  'EC' / 'EH': those features as they are, [N, video_dim] / [N, hidden_dim], without the encoder;
+        'EH' carries EventPoolGather's autograd edge into tap_feats."""
         ev_start, ev_len, ind, _ = _ev if _ev is not None else EF.event_index_tensors(soi_select_list, ind_select_list, c3d_feats.device)
-        parts = {'ER1': 1, 'ER2': 2, 'ER3': 3}[self.opt.event_context_type]
+        if self.event_direct():          # 'EC' / 'EH' (:131-137): the pooled rows / the anchors' states themselves
+            return EF.EventPoolGather.apply(c3d_feats, tap_feats, ev_start, ev_len, ind, self.event_direct())
+        parts = self.EVENT_ENCODED[self.opt.event_context_type]
         ech = EF.EventPoolGather.apply(c3d_feats, tap_feats, ev_start, ev_len, ind, parts)
         return self.fusion_model(ech, soi_select_list, ev_tensors=(ev_start, ev_len), drop=_drop)
 

@@ -112,7 +112,7 @@ class TrainStepArgs(C.Structure):
                 ('handover', i32), ('handover_cb', C.c_void_p), ('handover_user', C.c_void_p), ('adam_applied', c_f),
                 ('event_parts', i32), ('w_init', c_f), ('b_init', c_f), ('g_w_init', c_f), ('g_b_init', c_f),
                 ('init_use_v', i32), ('init_use_e', i32), ('init_use_c', i32), ('vh_offset', i32), ('tap_rows', i32),
-                ('mid_cb', C.c_void_p), ('mid_user', C.c_void_p)]
+                ('mid_cb', C.c_void_p), ('mid_user', C.c_void_p), ('event_direct', i32)]
 
 
 class ClipStepArgs(C.Structure):

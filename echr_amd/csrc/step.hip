@@ -46,15 +46,17 @@ static StepWs carve_step(const StepCall& c) {
     const echr_dec_args& d = a->dec;
     w.idx = take((long)(3 + (rw ? 5 : 4) * d.S) * d.N + (bx ? (long)d.N : 0));  // int32: ev_start | ev_len | ind | tokens [S,N] | active rows [<= S*N] | targets [N,S] | mask fp32 [N,S]
                                                           // (| weights fp32 [N,S] with rw)
-    w.ech = take((long)t.N * t.Din);
-    w.tsrm_ws = take(echr_tsrm_ws_floats(t.N, t.Din, t.Df, t.Do, t.G));
-    w.event = take((long)t.N * t.Do);
+    // (event_direct: 'EC' / 'EH' -- the pooled / gathered rows ARE the event vectors; no encoder input, workspace or gradients; tsrm is not read)
+    const bool direct = a->event_direct != 0;
+    w.ech = direct ? -1 : take((long)t.N * t.Din);
+    w.tsrm_ws = direct ? -1 : take(echr_tsrm_ws_floats(t.N, t.Din, t.Df, t.Do, t.G));
+    w.event = direct ? take((long)d.N * d.De) : take((long)t.N * t.Do);
     w.logp = take((long)d.N * d.S * d.V1);
     w.dec_ws = take(echr_decoder_ws_floats(&d));
     w.dec_ws_bwd = take(echr_decoder_ws_bwd_floats(&d));
     w.g_event = take((long)d.N * d.De);
-    w.g_ech = take((long)t.N * t.Din);
-    w.tsrm_ws_bwd = take(echr_tsrm_ws_bwd_floats(t.N, t.Din, t.Df, t.Do, t.G));
+    w.g_ech = direct ? -1 : take((long)t.N * t.Din);
+    w.tsrm_ws_bwd = direct ? -1 : take(echr_tsrm_ws_bwd_floats(t.N, t.Din, t.Df, t.Do, t.G));
     // non-recipe options: initial state (h0, its gradient, init_linear's input rows and their gradient), d video
     w.h0 = w.g_h0 = w.init_feats = w.init_dfeats = -1;
     if (a->w_init) {
@@ -292,6 +294,7 @@ static size_t step_index_count(const StepCall& c) { return step_vid_offset(c) + 
 extern "C" int echr_train_step_prepare(const echr_train_step_args* a, void* stream) {
     ECHR_REQUIRE(a && a->ws && a->host_index && a->flat_g, "train_step_prepare: missing buffers");
     ECHR_REQUIRE(a->overlap_encoder, "train_step_prepare: needs overlap_encoder = 1");
+    ECHR_REQUIRE(!a->event_direct, "train_step_prepare: event_direct = %d ('EC' / 'EH') runs without the prepare half (call echr_train_step with prepared = 0)", a->event_direct);
     hipStream_t st = (hipStream_t)stream;
     RC(join_tail(st));
     const StepCall c = plain_call(a);
@@ -364,14 +367,24 @@ static int train_step_impl(const StepCall& c, void* stream) {
     RC(validate_step(c));
     const echr_train_step_args* a = c.a; const echr_clip_step_args* x = c.x; const echr_batch_ext* bx = c.bx; const bool rw = c.rw;
     float* video_loss = c.video_loss; const int32_t* row_offset = c.row_offset;
-    ECHR_REQUIRE(a && a->ws && a->host_index && a->loss && a->g_loss && a->flat_g && (a->tap || a->event_parts == 1), "train_step: missing buffers");
+    // event_direct ('EC' / 'EH', include/echr_hip.h): the event vectors without the event encoder; its own rules first, each with its own message
+    const int direct = a ? a->event_direct : 0;
+    if (direct) {
+        ECHR_REQUIRE(direct >= 1 && direct <= 2, "train_step: event_direct = %d: 0 (through the event encoder), 1 ('EC') or 2 ('EH')", direct);
+        ECHR_REQUIRE(direct != 2 || (a->tap && a->Ht > 0), "train_step: event_direct = 2 ('EH') reads the anchors' rows of tap: tap / Ht missing");
+        const int want = direct == 1 ? (x ? x->Dc : a->dec.D) : a->Ht;
+        ECHR_REQUIRE(a->dec.De == want, "train_step: event_direct = %d: dec.De = %d is not the width of the %s (%d)", direct, a->dec.De,
+                     direct == 1 ? "C3D rows" : "proposal encoder's states", want);
+        ECHR_REQUIRE(!a->prepared, "train_step: event_direct = %d runs without echr_train_step_prepare (prepared must be 0)", direct);
+    }
+    ECHR_REQUIRE(a && a->ws && a->host_index && a->loss && a->g_loss && a->flat_g && (a->tap || a->event_parts == 1 || direct == 1), "train_step: missing buffers");
     ECHR_REQUIRE(!a->prepared || a->overlap_encoder, "train_step: prepared = 1 needs overlap_encoder = 1");
-    const int parts = a->event_parts ? a->event_parts : 3;
+    const int parts = direct ? direct : a->event_parts ? a->event_parts : 3;
     ECHR_REQUIRE(parts >= 1 && parts <= 3, "train_step: event_parts must be 0..3");
     const int Dc = x ? x->Dc : a->dec.D;          // (the C3D features' width: the row source's one with 'CC')
     const float* c3d = x ? x->c3d : a->dec.c3d;
     const int De_c3d = (parts & 1) ? Dc : 0, De_tap = (parts & 2) ? a->Ht : 0;          // the two halves of the event encoder's input rows
-    ECHR_REQUIRE(a->tsrm.N == a->dec.N && a->tsrm.Do == a->dec.De && a->tsrm.Din == De_c3d + De_tap, "train_step: encoder / decoder shapes disagree");
+    ECHR_REQUIRE(direct || (a->tsrm.N == a->dec.N && a->tsrm.Do == a->dec.De && a->tsrm.Din == De_c3d + De_tap), "train_step: encoder / decoder shapes disagree");
     const bool vh = a->g_tap && a->vh_offset >= 0;
     ECHR_REQUIRE(!vh || (a->vh_offset + a->Ht <= a->dec.Dv && a->tap_rows > 0), "train_step: vh_offset / tap_rows do not describe a span of dec.video");
     ECHR_REQUIRE(!a->w_init || (a->b_init && (a->forward_only || (a->g_w_init && a->g_b_init)) && init_feats_width(a) > 0), "train_step: init_linear pointers incomplete");
@@ -429,14 +442,14 @@ static int train_step_impl(const StepCall& c, void* stream) {
 
     echr_dec_args d = step_dec_args(a, L, idx);
     if (x) d.c3d = x->clip_parts == 3 ? ws + L.rows : a->tap;
-    echr_tsrm_args t = a->tsrm;
-    t.ech = ws + L.ech; t.ev_start = ev_start; t.ev_len = ev_len; t.ws = ws + L.tsrm_ws; t.out = ws + L.event;
+    echr_tsrm_args t = a->tsrm;          // (event_direct: described, never launched)
+    t.ech = direct ? nullptr : ws + L.ech; t.ev_start = ev_start; t.ev_len = ev_len; t.ws = direct ? nullptr : ws + L.tsrm_ws; t.out = ws + L.event;
     t.inference = 0; t.max_len = 0; t.max_span = 0;
     // the event encoder's position branch (pair embedding -> fc1 -> fc2 gates: indices and parameters only) starts right behind the staging
     // CaptionGenerator.forward (:23-30): the decoder's event-independent part starts on the library's second stream and overlaps the event encoder
     if (a->overlap_encoder && !a->prepared) {
         fork_event(ring_last());          // both forks hang off the staging copy's event: no further record in front of event pooling
-        int rc2 = tsrm_position_early(&t, st);
+        int rc2 = direct ? 0 : tsrm_position_early(&t, st);          // (no encoder, no position branch)
         if (!rc2) rc2 = echr_decoder_fwd_prepare(&d, stream);
         fork_event(nullptr);
         if (rc2) {
@@ -449,8 +462,9 @@ static int train_step_impl(const StepCall& c, void* stream) {
             return rc2;
         }
     }
-    int rc = echr_event_pool_gather_fwd(c3d, a->tap, ev_start, ev_len, ind, ws + L.ech, N, De_c3d, De_tap, stream);       // :106-128
-    if (!rc) rc = echr_tsrm_fwd(&t, &a->drop, stream);                                                                       // :129
+    // (event_direct: the pooled rows / the anchors' states are the event vectors themselves, :131-137)
+    int rc = echr_event_pool_gather_fwd(c3d, a->tap, ev_start, ev_len, ind, ws + (direct ? L.event : L.ech), N, De_c3d, De_tap, stream);       // :106-128
+    if (!rc && !direct) rc = echr_tsrm_fwd(&t, &a->drop, stream);                                                            // :129
     if (rc) { (void)tsrm_position_early(nullptr, nullptr); if (a->overlap_encoder) (void)echr_decoder_fwd_prepare_cancel(stream); return rc; }
     d.event = ws + L.event; d.prepared = a->overlap_encoder ? 1 : 0;
     // OldModel.init_hidden with CG_init_feats_type (OldModel_NEW.py:72-96): h(-1) = c(-1) = init_linear(cat(selected contexts))
@@ -496,7 +510,7 @@ static int train_step_impl(const StepCall& c, void* stream) {
     // backward (train.py:313): criterion gradient in fused form
     g.zero_extra = nullptr; g.zero_extra_count = 0;
     handover_request(false);          // (hand-over points of an earlier call are void from here on)
-    if (a->defer_update && a->g_tap && a->do_step && g.async_tail == 2 && fused_nll && config().gemm_h2 && helpers_available() && !vh && !a->w_init && !x) {
+    if (a->defer_update && a->g_tap && a->do_step && g.async_tail == 2 && fused_nll && config().gemm_h2 && helpers_available() && !vh && !a->w_init && !x && !direct) {
         // Joint 'tap_cg' iteration (train.py:300-313): the proposal encoder's backward -- a 64-workgroup persistent launch that leaves three
         // quarters of the chip idle -- waits for d tap_feats alone.  The chain that leads to it (late fusion, reverse recurrence, d event,
         // the event encoder's attention backward, d ech) runs first and alone on the caller's stream; every parameter gradient and the
@@ -537,11 +551,16 @@ static int train_step_impl(const StepCall& c, void* stream) {
         } else
         RC(echr_init_state_bwd(&ia, &ig, stream));
     }
-    echr_tsrm_grads tg = a->tsrm_g;
-    // d ech (the gradient of the event encoder's INPUT rows) only matters when d tap_feats is asked for: c3d features are data
-    tg.g_ech = (a->g_tap && De_tap > 0) ? ws + L.g_ech : nullptr; tg.g_out = ws + L.g_event; tg.ws_bwd = ws + L.tsrm_ws_bwd; tg.zeroed = 1;
-    RC(echr_tsrm_bwd(&t, &tg, &a->drop, stream));
-    if (a->g_tap && De_tap > 0) RC(echr_event_pool_gather_bwd(ws + L.g_ech, ind, a->g_tap, N, De_c3d, De_tap, stream));
+    if (direct) {
+        // d event IS the gradient of the pooled / gathered rows: 'EH' scatters it onto the anchors' rows of g_tap, 'EC' reaches data only
+        if (a->g_tap && De_tap > 0) RC(echr_event_pool_gather_bwd(ws + L.g_event, ind, a->g_tap, N, 0, De_tap, stream));
+    } else {
+        echr_tsrm_grads tg = a->tsrm_g;
+        // d ech (the gradient of the event encoder's INPUT rows) only matters when d tap_feats is asked for: c3d features are data
+        tg.g_ech = (a->g_tap && De_tap > 0) ? ws + L.g_ech : nullptr; tg.g_out = ws + L.g_event; tg.ws_bwd = ws + L.tsrm_ws_bwd; tg.zeroed = 1;
+        RC(echr_tsrm_bwd(&t, &tg, &a->drop, stream));
+        if (a->g_tap && De_tap > 0) RC(echr_event_pool_gather_bwd(ws + L.g_ech, ind, a->g_tap, N, De_c3d, De_tap, stream));
+    }
     if (fused_nll) RC(decoder_fused_loss(&d, &g, a->loss, st, crit_w != nullptr));
     if (fused_nll && bx && video_loss) RC(decoder_fused_video_loss(&d, &g, bxl.vid, bxl.n_videos, video_loss, st));
     step_mark(3, st);

@@ -126,7 +126,8 @@ class GradSink(object):
 # --------------------------------------------------------------------------------------------------
 class EventPoolGather(torch.autograd.Function):
     """ech = [mean-pooled C3D rows | tap[ind]]  (CaptionGenerator.py:111-114,121,128); `parts`: 3 = both ('ER3'), 1 = the pooled rows only
-    ('ER1'), 2 = the anchors' SST states only ('ER2')."""
+    ('ER1'), 2 = the anchors' SST states only ('ER2').  With event_context_type 'EC' / 'EH' the result of parts 1 / 2 IS the event context
+    (CaptionGenerator.py:131-137: no event encoder behind it)."""
 
     @staticmethod
     def forward(ctx, c3d, tap, ev_start, ev_len, ind, parts=3):

@@ -44,8 +44,11 @@ class FusedTrainStep(object):
         arena = optimizer.arena
         if getattr(model, '_echr_arena', None) is not arena or not arena.params_in_arena():
             raise ValueError('the optimiser\'s arena is not the model\'s (call model.build_arena() after .cuda(), pass it to ClampAdam)')
-        if not hasattr(model, 'fusion_model') or model.opt.event_context_type not in ('ER1', 'ER2', 'ER3'):
-            raise NotImplementedError('the fused step needs the TSRM event encoder (event_context_type ER1 / ER2 / ER3)')
+        # ('EC' / 'EH': no event encoder -- echr_train_step_args.event_direct; anything else was refused by the model's constructor)
+        self.direct = model.event_direct()
+        if not self.direct and (not hasattr(model, 'fusion_model') or model.opt.event_context_type not in model.EVENT_ENCODED):
+            raise NotImplementedError('the fused step needs the TSRM event encoder (event_context_type ER1 / ER2 / ER3) or a direct event '
+                                      'context (EC / EH)')
         if len(optimizer.param_groups) != 1 or {id(p) for p in optimizer.param_groups[0]['params']} != {id(p) for p in arena.params}:
             raise ValueError('the optimiser must hold exactly the model\'s parameters in one group')
         self.model, self.optim, self.arena = model, optimizer, arena
@@ -139,16 +142,18 @@ class FusedTrainStep(object):
     def _fill_static(self):
         a, m, ar = self.a, self.model, self.arena
         gp = lambda p: ar.flat_g.data_ptr() + 4 * ar.offsets[ar.slot(p)]
-        lm, fm = m.lm_model, m.fusion_model
-        tp = fm.native_params()
-        tsrm_params = (fm.event_emb.weight, fm.event_emb.bias, fm.enc_attn.pair_pos_fc1.weight, fm.enc_attn.pair_pos_fc1.bias,
-                       fm.enc_attn.pair_pos_fc2.weight, fm.enc_attn.pair_pos_fc2.bias, fm.enc_attn.query_1.weight, fm.enc_attn.query_1.bias,
-                       fm.enc_attn.key_1.weight, fm.enc_attn.key_1.bias, fm.enc_attn.linear_out_1.weight, fm.enc_attn.linear_out_1.bias)
-        for name, p, v in zip(EF.TSRM_PARAMS, tsrm_params, tp):
-            setattr(a.tsrm, name, L.ptr(v))
-            setattr(a.tsrm_g, 'g_' + name, gp(p))
-        a.tsrm.Din, a.tsrm.Df, a.tsrm.Do, a.tsrm.G = tp[0].shape[1], tp[0].shape[0], tp[10].shape[0], fm.enc_attn.group
-        a.tsrm.fst_mode = fm.fst_mode()
+        lm, tp = m.lm_model, ()
+        if not self.direct:          # (a direct event context leaves tsrm / tsrm_g zeroed: the library does not read them)
+            fm = m.fusion_model
+            tp = fm.native_params()
+            tsrm_params = (fm.event_emb.weight, fm.event_emb.bias, fm.enc_attn.pair_pos_fc1.weight, fm.enc_attn.pair_pos_fc1.bias,
+                           fm.enc_attn.pair_pos_fc2.weight, fm.enc_attn.pair_pos_fc2.bias, fm.enc_attn.query_1.weight, fm.enc_attn.query_1.bias,
+                           fm.enc_attn.key_1.weight, fm.enc_attn.key_1.bias, fm.enc_attn.linear_out_1.weight, fm.enc_attn.linear_out_1.bias)
+            for name, p, v in zip(EF.TSRM_PARAMS, tsrm_params, tp):
+                setattr(a.tsrm, name, L.ptr(v))
+                setattr(a.tsrm_g, 'g_' + name, gp(p))
+            a.tsrm.Din, a.tsrm.Df, a.tsrm.Do, a.tsrm.G = tp[0].shape[1], tp[0].shape[0], tp[10].shape[0], fm.enc_attn.group
+            a.tsrm.fst_mode = fm.fst_mode()
         ps = lm.native_params()
         (embed, w_logit, b_logit, wi0, wi1, wi2, wh0, wh1, wh2, bi0, bi1, bi2, bh0, bh1, bh2, w_c2a, b_c2a, w_h2a, b_h2a, w_alpha, b_alpha) = ps
         d, g = a.dec, a.dec_g
@@ -165,12 +170,15 @@ class FusedTrainStep(object):
         d.H, d.E, d.Ha, d.V1 = wh0.shape[1], embed.shape[1], w_c2a.shape[0], embed.shape[0]
         d.D = w_c2a.shape[1]
         d.De, d.Dv = wi0.shape[1] - d.E, wi2.shape[1] - d.E
-        if wi1.shape[1] != d.E + d.D or a.tsrm.Do != d.De:
+        # (the width check wi0.shape[1] - E == De: against the encoder's output, or the C3D rows' / the proposal encoder's states' width)
+        want_de = a.tsrm.Do if not self.direct else (m.opt.video_dim if self.direct == 1 else m.opt.hidden_dim)
+        if wi1.shape[1] != d.E + d.D or want_de != d.De:
             raise ValueError('LSTM input widths do not match the contexts')
         a.flat_g, a.n_flat, a.flat_p = ar.flat_g.data_ptr(), ar.total, ar.flat_p.data_ptr()
         a.g_loss = self.one.data_ptr()
         # the reference's non-recipe options (CaptionGenerator.py:106-130 event_context_type; OldModel_NEW.py:72-96 CG_init_feats_type)
-        a.event_parts = {'ER1': 1, 'ER2': 2, 'ER3': 3}[m.opt.event_context_type]
+        a.event_parts = m.EVENT_ENCODED.get(m.opt.event_context_type, 0)
+        a.event_direct = self.direct          # 1 = 'EC', 2 = 'EH': event_parts is not read then
         if getattr(lm, 'CG_init_feats_dim', 0):
             t = lm.CG_init_feats_type
             a.w_init, a.b_init = L.ptr(lm.init_linear.weight), L.ptr(lm.init_linear.bias)
@@ -201,6 +209,9 @@ class FusedTrainStep(object):
         if self.clip != 1:
             raise NotImplementedError("clip_context_type with 'CH': the attended rows are tap_feats and their attention projection is part of the "
                                       "event-independent half, prepare() runs ahead of them (call without prepare(); JointTrainStep(early_prepare=False))")
+        if self.direct:
+            raise NotImplementedError("event_context_type 'EC' / 'EH': the library refuses prepared = 1 with a direct event context "
+                                      "(echr_train_step_args.event_direct) -- call without prepare(); JointTrainStep does so by itself")
         self._setup(None, c3d_feats, lda_feats, lm_labels, ind_select_list, soi_select_list, targets, masks, True, False, None, False)
         L.check(self.lib.echr_train_step_prepare(C.byref(self.a), L.stream_ptr()), 'train_step_prepare')
         self._prepared = True
@@ -313,7 +324,8 @@ class FusedTrainStep(object):
 
     def _set_tap(self, tap, tap_grad, defer_update, step, forward_only):
         a, d = self.a, self.a.dec
-        if (tap.shape[1] if a.event_parts & 2 else 0) + (self._dc if a.event_parts & 1 else 0) != a.tsrm.Din or tap.shape[0] < self._tv_needed:
+        parts, want = (self.direct, a.dec.De) if self.direct else (a.event_parts, a.tsrm.Din)
+        if (tap.shape[1] if parts & 2 else 0) + (self._dc if parts & 1 else 0) != want or tap.shape[0] < self._tv_needed:
             raise L.EchrHipError('tap_feats %s do not match the model / the event anchors' % (tuple(tap.shape),))
         a.tap, a.Ht = tap.data_ptr(), tap.shape[1]
         self._tap_keep = tap
@@ -447,7 +459,7 @@ class FusedTrainStep(object):
             a.nll_target, a.nll_target_i64, a.nll_mask = tgt.data_ptr(), 1 if tgt.dtype == torch.int64 else 0, msk.data_ptr()
         self.last_active_rows = n_act
         if drop is None:
-            drop = m.lm_model.next_drop_state(m.fusion_model.enc_attn.dropout.p)
+            drop = m.lm_model.next_drop_state(m.encoder_dropout_p())
             drop.training = m.training
         a.drop = drop.c()
         self._batched = batch is not None
@@ -501,7 +513,8 @@ class FusedTrainStep(object):
             # parameters keep .grad None (their slots are zero)
             unused = self._unused
             if unused is None:
-                unused = self._unused = {id(p) for p in list(m.lm_model.core.fusion_layer.parameters()) + list(m.fusion_model.h2a_layer.parameters())}
+                unused = self._unused = {id(p) for p in list(m.lm_model.core.fusion_layer.parameters()) +
+                                         (list(m.fusion_model.h2a_layer.parameters()) if hasattr(m, 'fusion_model') else [])}
             for i, p in enumerate(ar.params):
                 if id(p) not in unused:
                     p.grad = ar.grad_view(i)
@@ -591,7 +604,7 @@ class SelfCriticalStep(_SelfCriticalIteration):
     def _contexts(self, x, gen_result, on_device):
         tap, c3d, lda, ind, soi = x
         m = self.fused.model
-        drop = m.lm_model.next_drop_state(m.fusion_model.enc_attn.dropout.p)
+        drop = m.lm_model.next_drop_state(m.encoder_dropout_p())
         drop.training = m.training
         ev = EF.event_index_tensors(soi, ind, c3d.device, min(c3d.shape[0], tap.shape[0]))
         video = m.get_video_context(*x)
@@ -773,7 +786,9 @@ class JointTrainStep(_JointStep):
 
     def __init__(self, fused, tap_model, tap_optim, lambda1=1.0, tap_grad_clip=None, early_prepare=True, order=None, lambda2=1.0):
         self._init_joint(fused, tap_model, tap_optim, lambda1, lambda2, tap_grad_clip)
-        self.early = bool(early_prepare)
+        # (a direct event context 'EC' / 'EH' runs without the prepare half: the library refuses prepared = 1 there and ignores defer_update --
+        # the plain form runs and the proposal encoder's backward follows the call, as with 'VH', an initial state or 'CH' rows)
+        self.early = bool(early_prepare) and not fused.direct
         # 'after' (default): the proposal encoder's backward is queued when the caption call has returned -- on the caller's stream right behind
         # d tap_feats, BESIDE the caption side's tail on the library's streams; 'hook': from inside the call, the tail forked behind it
         # (serialised: measured 3.19 vs 3.00 ms per config-5 iteration)

@@ -44,7 +44,10 @@ def state_dict_shapes(opt):
     vt = opt.video_context_type
     vi = (opt.lda_dim if 'VL' in vt else 0) + (opt.video_dim if 'VC' in vt else 0) + (opt.hidden_dim if 'VH' in vt else 0)
     ct = getattr(opt, 'clip_context_type', 'CC')      # frame-level rows: 'CC' C3D, 'CH' the SST states, 'CC+CH' both (CaptionGenerator.py:80-84)
-    ev, cl = opt.d_o, (opt.video_dim if 'CC' in ct else 0) + (opt.hidden_dim if 'CH' in ct else 0)      # context widths; vi: VL / VC / VH (:56-64)
+    # event context width (:66-74): d_o behind the event encoder; 'EC' the pooled C3D rows, 'EH' the anchor's SST state -- no fusion_model.* keys
+    direct = 'ER' not in et
+    ev_w = opt.d_o if not direct else (opt.video_dim if 'EC' in et else 0) + (opt.hidden_dim if 'EH' in et else 0)
+    ev, cl = ev_w, (opt.video_dim if 'CC' in ct else 0) + (opt.hidden_dim if 'CH' in ct else 0)      # context widths; vi: VL / VC / VH (:56-64)
     s = {
         'fusion_model.h2a_layer.weight': (10, 10), 'fusion_model.h2a_layer.bias': (10,),
         'fusion_model.event_emb.weight': (Df, tsrm_in), 'fusion_model.event_emb.bias': (Df,),
@@ -56,6 +59,8 @@ def state_dict_shapes(opt):
         'lm_model.embed.weight': (V1, E),
         'lm_model.logit.weight': (V1, 3 * H), 'lm_model.logit.bias': (V1,),
     }
+    if direct:
+        s = {k: v for k, v in s.items() if not k.startswith('fusion_model.')}
     it = getattr(opt, 'CG_init_feats_type', '')       # non-zero initial state (OldModel_NEW.py:38-39,55-63): Linear(selected context widths -> 3H)
     init_in = (vi if 'V' in it else 0) + (ev if 'E' in it else 0) + (cl if 'C' in it else 0)
     if init_in:
@@ -179,6 +184,10 @@ CASES = {
     'ch': dict(opt=dict(clip_context_type='CH', CG_vocab_size=300, CG_seq_length=7), video=dict(N=12, A=40, L=9, seed=71)),
     'cch': dict(opt=dict(clip_context_type='CC+CH', CG_vocab_size=300, CG_seq_length=7), video=dict(N=12, A=40, L=9, seed=72)),
     'ch64': dict(opt=dict(clip_context_type='CH', CG_vocab_size=5000, CG_seq_length=19), video=dict(N=64, A=128, L=21, seed=73)),
+    # the event vector without the event encoder (CaptionGenerator.py:131-137): 'EC' the mean of the event's C3D rows (layer0.weight_ih is
+    # [4H, E + 500]), 'EH' the proposal encoder's state at the anchor ([4H, E + 512]); no fusion_model.* parameters
+    'ec': dict(opt=dict(event_context_type='EC', CG_vocab_size=300, CG_seq_length=7), video=dict(N=12, A=40, L=9, seed=74)),
+    'eh': dict(opt=dict(event_context_type='EH', CG_vocab_size=300, CG_seq_length=7), video=dict(N=12, A=40, L=9, seed=75)),
     # EXACTLY the layout bench.py times (BASELINE config 3): 64 disjoint 128-segment events on a T_v = 8192 video
     'c3bench': dict(opt=dict(CG_vocab_size=5000, CG_seq_length=19), video=dict(N=64, A=128, L=21, seed=1234, disjoint=True)),
 }

@@ -712,6 +712,17 @@ typedef struct {
                                       gains).  Called exactly once per call that takes the deferred form, never otherwise; may call other entry
                                       points of this library on `stream`; must not block on the device */
     void* mid_user;
+    int32_t event_direct;          /* event_context_type 'EC' / 'EH' (CaptionGenerator.py:106-137): the event vector without the event encoder.
+                                      0 = through the encoder (event_parts; everything above).  1 = 'EC': the mean of the event's C3D rows
+                                      (dec.De = the C3D width), 2 = 'EH': the proposal encoder's state at the event's anchor, tap[ind]
+                                      (dec.De = Ht; tap must be given).  echr_event_pool_gather_fwd writes the [N, De] vectors straight into the
+                                      decoder's event input; tsrm / tsrm_g / event_parts are not read, the workspace has no encoder regions, no
+                                      position branch is forked.  Backward: the decoder's d event (plus init_linear's with init_use_e) goes,
+                                      with g_tap and value 2, to echr_event_pool_gather_bwd(g_event, ind, g_tap, N, 0, Ht); with value 1 it
+                                      reaches nothing.  defer_update is ignored (the plain form runs, mid_cb is not called); prepared = 1 is
+                                      refused -- echr_train_step_prepare's work ahead of tap_feats is the decoder's event-independent part
+                                      plus the encoder's position branch, and the callers of a direct context run without it.  Everything else
+                                      (hand-over points, stage-ahead, n_active, host_nll, weights, per-video losses, 'VH', clip rows) is unchanged */
 } echr_train_step_args;
 int64_t echr_train_step_ws_floats(const echr_train_step_args* a);
 /* Back-to-back calls (round 6, "stage-ahead"): a call that ends with its own update (do_step = 1, not deferred) lets the NEXT call on the same

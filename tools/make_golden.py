@@ -61,10 +61,11 @@ SEED, OFFSET = 0x5EED0123456789, 7
 
 class MaskFeeder:
     """Replaces F.dropout: hands out Philox masks in the reference's call order:
-    TSRM [N,G,N] once, then per step h0, h1, h2 [N,H] and out [N,3H]."""
+    TSRM [N,G,N] once, then per step h0, h1, h2 [N,H] and out [N,3H].  encoder=False (event_context_type 'EC' / 'EH': the reference
+    builds no fusion_model): the first call is already step 0's h0."""
 
-    def __init__(self, p_out):
-        self.calls = 0
+    def __init__(self, p_out, encoder=True):
+        self.calls = 0 if encoder else 1
         self.p_out = p_out
 
     def __call__(self, x, p=0.5, training=True, inplace=False):
@@ -109,7 +110,7 @@ def run_ref(m, vid, train_mode, opt):
     orig = F.dropout
     if train_mode:
         m.train()
-        F.dropout = MaskFeeder(opt.CG_drop_prob)
+        F.dropout = MaskFeeder(opt.CG_drop_prob, encoder=hasattr(m, 'fusion_model'))
     else:
         m.eval()
     try:
@@ -123,6 +124,9 @@ def run_ref(m, vid, train_mode, opt):
 
 
 def run_oracle(opt, params, vid, train_mode):
+    if opt.event_context_type in ('EC', 'EH'):          # O.caption_forward knows 'ER*' only: the oracle's pieces composed (tests/plain_event_ref.py)
+        from tests import plain_event_ref
+        return plain_event_ref.run(opt, params, vid, train_mode)[:3]
     P = {k: torch.from_numpy(v.copy()).requires_grad_(True) for k, v in params.items()}
     tap, c3d, lda = (torch.from_numpy(vid[k]) for k in ('tap', 'c3d', 'lda'))
     labels = torch.from_numpy(vid['labels'])
@@ -175,8 +179,12 @@ def do_case(name):
         seq, slp = m(tap, c3d, lda, [], vid['ind'], vid['soi'].tolist(), mode='eval')
     P = {k: torch.from_numpy(v) for k, v in params.items()}
     with torch.no_grad():
-        oseq, oslp = O.caption_forward(P, tap, c3d, lda, None, vid['ind'], vid['soi'], 'eval', None, opt.n_head,
-                                       opt.CG_seq_length, video_context_type=opt.video_context_type, event_context_type=opt.event_context_type, fST_type=getattr(opt, 'fST_type', 'fST0'), use_posit=opt.use_posit, init_feats_type=opt.CG_init_feats_type)
+        if opt.event_context_type in ('EC', 'EH'):
+            from tests import plain_event_ref
+            oseq, oslp = plain_event_ref.sample(opt, params, vid)
+        else:
+            oseq, oslp = O.caption_forward(P, tap, c3d, lda, None, vid['ind'], vid['soi'], 'eval', None, opt.n_head,
+                                           opt.CG_seq_length, video_context_type=opt.video_context_type, event_context_type=opt.event_context_type, fST_type=getattr(opt, 'fST_type', 'fST0'), use_posit=opt.use_posit, init_feats_type=opt.CG_init_feats_type)
     assert torch.equal(seq, oseq), 'oracle greedy seq differs'
     print('[%s/sample] seq %s  oracle max|dlogp| %.2e' % (name, tuple(seq.shape), float((slp - oslp).abs().max())))
     out['sample|seq'] = seq.numpy().astype(np.int64)

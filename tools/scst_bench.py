@@ -57,7 +57,7 @@ def main():
     lm = m.lm_model
     with torch.no_grad():
         ev = EF.event_index_tensors(soi, ind, c3d.device, min(c3d.shape[0], tap.shape[0]))
-        drop = lm.next_drop_state(m.fusion_model.enc_attn.dropout.p)
+        drop = lm.next_drop_state(m.encoder_dropout_p())
         drop.training = True
         video = m.get_video_context(tap, c3d, lda, ind, soi)
         clip, cm = m.get_clip_context(tap, c3d, lda, ind, soi, _ev=ev)
