@@ -62,9 +62,24 @@ class CaptionGenerator(nn.Module):
         """The dropout probability of the event encoder's one site; 0.0 without an encoder ('EC' / 'EH': no site is drawn)."""
         return self.fusion_model.enc_attn.dropout.p if hasattr(self, 'fusion_model') else 0.0
 
+    def one_stream(self):
+        """True with caption_model='show_attend_tell' (models.ShowAttendTellModel): the one-stream decoder of echr_amd.sat."""
+        return type(self.lm_model).__name__ == 'ShowAttendTellModel'
+
     def _require_live_decoder(self):
-        if type(self.lm_model).__name__ != 'ThreestreamModel':
-            self.lm_model.forward()          # raises: parameter-container decoders (show_attend_tell) never run
+        """The configuration check of forward(), ahead of every argument: the one-stream decoder runs with one LSTM layer, a non-empty
+        CG_input_feats_type and 'CC' rows (ShowAttendTellModel._require_live names the option otherwise)."""
+        if self.one_stream():
+            self.lm_model._require_live()
+            if self.clip_parts() & 2:
+                self.lm_model._refuse("clip_context_type=%r -- the one-stream decoder attends over the C3D rows ('CC'); 'CH' rows (the gradient into "
+                                      "tap_feats through the clip context) are a follow-up" % (self.opt.clip_context_type,))
+
+    def _require_three_stream(self, what):
+        """Entries that only the three-stream decoder has (batches, beam search, self-critical training, the fused steps)."""
+        if self.one_stream():
+            self.lm_model._refuse('%s runs on the three_stream decoder; the one-stream decoder takes one video per call through '
+                                  "forward(mode='train' / 'eval')" % what)
 
     def build_arena(self):
         """Pack parameters and gradients into flat device buffers (echr_amd/arena.py).  Call after .cuda(); enables the
@@ -95,6 +110,12 @@ class CaptionGenerator(nn.Module):
         if return_score and (mode != 'eval' or beam_size == 1):
             raise ValueError("return_score is taken by mode='eval' with beam_size > 1 only")
         self._require_live_decoder()
+        if mode == 'train_rl':
+            self._require_three_stream("mode='train_rl' (self-critical training)")
+        if beam_size != 1:
+            self._require_three_stream('beam_size=%r (beam search)' % (beam_size,))
+        if self.one_stream() and self.lm_model.training and self.lm_model.ss_prob > 0.0:
+            self.lm_model._refuse('ss_prob > 0 -- scheduled sampling is never enabled by the reference and is not on the HIP path')
         if not c3d_feats.is_cuda:
             raise EF.L.EchrHipError('CaptionGenerator runs on the GPU only: move the module and its inputs with .cuda()')
         ev = EF.event_index_tensors(soi_select_list, ind_select_list, c3d_feats.device, min(c3d_feats.shape[0], tap_feats.shape[0]))
@@ -103,7 +124,7 @@ class CaptionGenerator(nn.Module):
         video = self.get_video_context(tap_feats, c3d_feats, lda_feats, ind_select_list, soi_select_list)
         clip, clip_mask = self.get_clip_context(tap_feats, c3d_feats, lda_feats, ind_select_list, soi_select_list, _ev=ev)
         prepared = None
-        if mode == 'train' and self.overlap_encoder:
+        if mode == 'train' and self.overlap_encoder and not self.one_stream():
             # the decoder's event-independent precompute starts on a second stream and overlaps the event encoder launched next
             prepared = self.lm_model.prepare(video, clip, clip_mask, lm_labels)
         try:
@@ -133,6 +154,7 @@ class CaptionGenerator(nn.Module):
         With event_context_type 'EC' / 'EH' there is no event encoder: `event_group_rows` is accepted and has no effect (it only bounds the
         encoder's pair work), here and in beam_batch.
         `beam_size` stays 1 here: beam search over a batch is `beam_batch`."""
+        self._require_three_stream('forward_batch (a multi-video batch)')
         if mode == 'train_rl':
             raise NotImplementedError("mode='train_rl' takes one video per call: self-critical training over a batch is "
                                       "train_rl_batch(batch) (one call: fused.SelfCriticalBatchStep)")
@@ -180,6 +202,7 @@ class CaptionGenerator(nn.Module):
     def _batch_contexts(self, batch, groups, need_labels=False):
         """What forward_batch and beam_batch hand to the decoder: the checks of a batched call, then (video [V, Dv], event [N_tot, d_o],
         ev_start, ev_len, A, vid, drop) -- the scene vectors, and the event encoder as one block-diagonal call or once per run of `groups`."""
+        self._require_three_stream('a multi-video batch (VideoBatch)')
         self._check_batch_options(batch)
         self._require_live_decoder()
         if not batch.c3d.is_cuda:
@@ -219,6 +242,7 @@ class CaptionGenerator(nn.Module):
         `max_rows`: the decode keeps seq_length + 1 states of every one of its events * beam_size rows, so it runs once per run of
         `batch.beam_groups(beam_size, max_rows)` -- consecutive videos with at most max_rows rows together; a video above the budget runs
         alone, None is one decode over the batch.  Each run is one echr_decoder_beam_batch call and one host read (its video_words)."""
+        self._require_three_stream('beam_batch (beam search over a multi-video batch)')
         B = EF._check_beam_size(beam_size, self.lm_model.vocab_size + 1)
         if self.training or self.lm_model.training:
             raise ValueError('beam search is an evaluation decode: call eval() first')
@@ -259,6 +283,7 @@ class CaptionGenerator(nn.Module):
         are what forward(mode='train_rl') returns for that video.  Apply the criterion with `batch.reward_criterion(crit, sample_logprobs,
         gen_result, reward, video_words)`.  gen_result and sample_logprobs are [] when T == 0.
         `gen_result` [N_tot, >= T]: score these captions instead of drawing them.  The batch need not carry labels."""
+        self._require_three_stream('train_rl_batch (self-critical training over a multi-video batch)')
         video, event, ev_start, ev_len, A, vid, drop = self._batch_contexts(batch, None)
         lm = self.lm_model
         if lm.training and lm.ss_prob > 0.0:

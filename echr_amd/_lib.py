@@ -133,6 +133,25 @@ class CiderdArgs(C.Structure):        # echr_ciderd_args
                 ('idf_unseen', C.c_double), ('base', c_f), ('weight', f32), ('out', c_f)]
 
 
+class SatArgs(C.Structure):          # echr_sat_args: the one-stream (show_attend_tell) decoder
+    _fields_ = [('N', i32), ('A', i32), ('Tv', i32), ('D', i32), ('H', i32), ('E', i32), ('Ha', i32), ('De', i32),
+                ('Dv', i32), ('V1', i32), ('S', i32), ('feats', i32), ('rows_disjoint', i32),
+                ('embed', c_f), ('w_logit', c_f), ('b_logit', c_f), ('w_ih', c_f), ('w_hh', c_f),
+                ('w_c2a', c_f), ('b_c2a', c_f), ('w_h2a', c_f), ('b_h2a', c_f), ('w_alpha', c_f), ('b_alpha', c_f),
+                ('c3d', c_f), ('ev_start', c_f), ('ev_len', c_f), ('event', c_f), ('video', c_f), ('tokens', c_f), ('h0', c_f),
+                ('ws', c_f), ('logp', c_f), ('train', i32)]
+
+
+class SatGrads(C.Structure):         # echr_sat_grads
+    _fields_ = [('g_embed', c_f), ('g_w_logit', c_f), ('g_b_logit', c_f), ('g_w_ih', c_f), ('g_w_hh', c_f),
+                ('g_w_c2a', c_f), ('g_b_c2a', c_f), ('g_w_h2a', c_f), ('g_b_h2a', c_f), ('g_w_alpha', c_f), ('g_b_alpha', c_f),
+                ('g_event', c_f), ('g_video', c_f), ('g_h0', c_f), ('g_logp', c_f), ('ws_bwd', c_f), ('zeroed', i32)]
+
+
+class SatSampleArgs(C.Structure):    # echr_sat_sample_args
+    _fields_ = [('dec', SatArgs), ('seq_len', i32), ('seq', c_f), ('seq_logp', c_f), ('n_unfinished', c_f), ('ws_sample', c_f)]
+
+
 # every symbol include/echr_hip.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ('echr_version', i32, []),
@@ -241,13 +260,20 @@ SYMBOLS = [
     ('echr_clamp_adam', i32, [c_f, c_f, c_f, c_f, i64, i32, C.c_double, C.c_double, C.c_double, C.c_double, f32, C.c_void_p]),
     ('echr_clamp_adam_counted', i32, [c_f, c_f, c_f, c_f, i64, i32, C.c_double, C.c_double, C.c_double, C.c_double, f32, c_f, C.c_void_p]),
     ('echr_ciderd_score', i32, [C.POINTER(CiderdArgs), C.c_void_p]),
+    ('echr_sat_ws_floats', i64, [C.POINTER(SatArgs)]),
+    ('echr_sat_ws_bwd_floats', i64, [C.POINTER(SatArgs)]),
+    ('echr_sat_fwd', i32, [C.POINTER(SatArgs), C.POINTER(Dropout), C.c_void_p]),
+    ('echr_sat_bwd', i32, [C.POINTER(SatArgs), C.POINTER(SatGrads), C.POINTER(Dropout), C.c_void_p]),
+    ('echr_sat_step', i32, [C.POINTER(SatArgs), c_f, c_f, c_f, c_f, C.POINTER(Dropout), C.c_void_p]),
+    ('echr_sat_sampler_ws_floats', i64, [C.POINTER(SatArgs)]),
+    ('echr_sat_sample', i32, [C.POINTER(SatSampleArgs), C.c_void_p]),
 ]
 
 ABI_STRUCTS = {'echr_gemm_desc': GemmDesc, 'echr_dropout': Dropout, 'echr_tsrm_args': TsrmArgs, 'echr_tsrm_grads': TsrmGrads,
                'echr_dec_args': DecArgs, 'echr_dec_grads': DecGrads, 'echr_sample_args': SampleArgs, 'echr_sst_args': SstArgs,
                'echr_sst_grads': SstGrads, 'echr_train_step_args': TrainStepArgs, 'echr_init_state_args': InitStateArgs, 'echr_init_state_grads': InitStateGrads,
                'echr_beam_args': BeamArgs, 'echr_row_grad_args': RowGradArgs, 'echr_clip_step_args': ClipStepArgs, 'echr_batch_ext': BatchExt, 'echr_sst_batch': SstBatch,
-               'echr_ciderd_args': CiderdArgs}
+               'echr_ciderd_args': CiderdArgs, 'echr_sat_args': SatArgs, 'echr_sat_grads': SatGrads, 'echr_sat_sample_args': SatSampleArgs}
 
 ABI_VERSION = 3          # include/echr_hip.h ECHR_ABI_VERSION
 _lib = None

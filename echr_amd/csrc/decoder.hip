@@ -1187,6 +1187,56 @@ static int input_gates(const echr_dec_args* a, const DecWs& w, const float* xt, 
     return gemm_grouped(d, 3, st);       // the three streams' token-side products in one launch
 }
 
+// ---- the frame-level attention launches as the one-stream decoder (sat.hip) calls them: q arrives as ONE finished [N, Ha] product
+// (without its bias), d ATT as one [N, D] buffer ----
+int att_score_launch(const AttShape& s, const float* PALL, const float* Q1, const float* b_q, float* QS, const float* alpha, const float* b_alpha,
+                     const int* ev_start, const int* ev_len, float* SC, hipStream_t st) {
+    const AttDims ad{s.N, s.A, s.Ha, s.D};
+    return launch_att_score(ad, PALL, Q1, 1, (long)s.N * s.Ha, b_q, QS, alpha, b_alpha, ev_start, ev_len, SC, st);
+}
+int att_context_launch(const AttShape& s, const float* C3D, const float* SC, const int* ev_start, const int* ev_len, float* WT, float* ATT, hipStream_t st) {
+    hipLaunchKernelGGL(att_context_kernel, dim3(s.N, (s.D + 127) / 128), dim3(256), (((s.A + 31) & ~31) + 8 * 128) * sizeof(float), st, C3D, SC, ev_start, ev_len,
+                       WT, ATT, s.A, s.D);
+    return check_launch("att_context");
+}
+int att_bwd_launch(const AttShape& s, const float* PALL, const float* C3D, const float* Q, const float* alpha, const float* WT, const float* ATT,
+                   const float* DATT, const int* ev_start, const int* ev_len, float* DSC, float* DQ, hipStream_t st) {
+    const AttDims ad{s.N, s.A, s.Ha, s.D};
+    return launch_att_bwd(ad, PALL, C3D, Q, alpha, WT, ATT, DATT, 1, (long)s.N * s.D, ev_start, ev_len, DSC, DQ, st);
+}
+// d P_all (into the zero-filled DPALL [Tv, Ha]) and d alpha / d b_alpha (ADDED to g_alpha / g_balpha) over all S steps; GAREP / GBREP: the
+// zero-filled replica scratch [ALPHA_REP, Ha] / [ALPHA_REP] of the atomic form (att_post_replicas())
+int att_post_replicas() { return ALPHA_REP; }
+int att_post_launch(const AttShape& s, int Tv, int S, int rows_disjoint, const float* PALL, const float* QS, const float* alpha, const float* DSC,
+                    const int* ev_start, const int* ev_len, float* DPALL, float* GAREP, float* GBREP, float* g_alpha, float* g_balpha, hipStream_t st) {
+    const AttDims ad{s.N, s.A, s.Ha, s.D};
+    const int Ha = s.Ha;
+    if (det_mode()) {          // fixed-order form, as in the three-stream backward's part B
+        const long nblk = (long)s.N * ((s.A + 7) / 8);
+        float* ga = det_scratch(DET_ALPHA, (size_t)nblk * (Ha + 1));
+        if (!ga) return -12;
+        float* gb = ga + nblk * Ha;
+        RC(fill_zero(ga, nblk * (Ha + 1), st));
+        float* dps = nullptr;
+        if (!rows_disjoint) { dps = det_scratch(DET_DPALL, (size_t)s.N * s.A * Ha); if (!dps) return -12; }
+        RC(launch_att_post(ad, PALL, QS, alpha, DSC, ev_start, ev_len, dps ? dps : DPALL, ga, gb, S, dps ? 2 : 1, st, 1));
+        if (dps) {
+            hipLaunchKernelGGL(dpall_fold_kernel, dim3(Tv), dim3(256), 0, st, dps, ev_start, ev_len, DPALL, s.N, s.A, Ha);
+            RC(check_launch("dpall_fold"));
+        }
+        RC(colsum(ga, Ha, (int)nblk, Ha, g_alpha, true, st));
+        return colsum(gb, 1, (int)nblk, 1, g_balpha, true, st);
+    }
+    RC(launch_att_post(ad, PALL, QS, alpha, DSC, ev_start, ev_len, DPALL, GAREP, GBREP, S, rows_disjoint ? 1 : 0, st));
+    RC(colsum(GAREP, Ha, ALPHA_REP, Ha, g_alpha, true, st));
+    return colsum(GBREP, 1, ALPHA_REP, 1, g_balpha, true, st);
+}
+int att_check_dims(const AttShape& s, const char* who) {
+    ECHR_REQUIRE(s.D % 4 == 0 && s.Ha % 4 == 0 && s.Ha <= 256 * MAXR && s.D <= 256 * MAXR && s.D >= 4 && s.Ha >= 4,
+                 "%s: need D%%4==0, Ha%%4==0, 4 <= D,Ha <= %d (D=%d Ha=%d)", who, 256 * MAXR, s.D, s.Ha);
+    return 0;
+}
+
 }  // namespace echr
 
 using namespace echr;

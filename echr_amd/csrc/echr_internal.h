@@ -116,6 +116,19 @@ void handover_request(bool on, echr_handover_fn cb = nullptr, void* user = nullp
 void decoder_bwd_views(const echr_dec_args* a, const echr_dec_grads* g, const float** dg1, const float** dpall);
 const float* decoder_fwd_wt(const echr_dec_args* a);
 int check_dims_public(const echr_dec_args* a, const char* who);
+// the frame-level attention launches of decoder.hip for the one-stream decoder (sat.hip): q as one finished [N, Ha] product without its bias,
+// d ATT as one [N, D] buffer; att_post_launch zero-expects DPALL / GAREP / GBREP and ADDS d alpha / d b_alpha to g_alpha / g_balpha
+struct AttShape { int N, A, Ha, D; };
+DropCfg make_drop(const echr_dropout* d, float p);
+int att_check_dims(const AttShape& s, const char* who);
+int att_score_launch(const AttShape& s, const float* PALL, const float* Q1, const float* b_q, float* QS, const float* alpha, const float* b_alpha,
+                     const int* ev_start, const int* ev_len, float* SC, hipStream_t st);
+int att_context_launch(const AttShape& s, const float* C3D, const float* SC, const int* ev_start, const int* ev_len, float* WT, float* ATT, hipStream_t st);
+int att_bwd_launch(const AttShape& s, const float* PALL, const float* C3D, const float* Q, const float* alpha, const float* WT, const float* ATT,
+                   const float* DATT, const int* ev_start, const int* ev_len, float* DSC, float* DQ, hipStream_t st);
+int att_post_replicas();
+int att_post_launch(const AttShape& s, int Tv, int S, int rows_disjoint, const float* PALL, const float* QS, const float* alpha, const float* DSC,
+                    const int* ev_start, const int* ev_len, float* DPALL, float* GAREP, float* GBREP, float* g_alpha, float* g_balpha, hipStream_t st);
 // list_form: the context-term scatter reads the compacted active_rows list itself (echr_train_step_batch_clip; "row_grad_list" = 0 or a step count
 // beyond its LDS flags: the flag form every other entry launches)
 int row_grad(const echr_dec_args* a, const echr_dec_grads* g, const echr_row_grad_args* r, hipStream_t st, bool list_form = false);

@@ -42,6 +42,8 @@ class FusedTrainStep(object):
         if not isinstance(optimizer, ClampAdam) or optimizer.arena is None:
             raise ValueError('FusedTrainStep needs echr_amd.optim.ClampAdam built with the flat arena (model.build_arena())')
         arena = optimizer.arena
+        if hasattr(model, '_require_three_stream'):          # (the one-stream decoder trains on the autograd path: forward, backward, ClampAdam.step)
+            model._require_three_stream('fused.%s (the one-call training steps)' % type(self).__name__)
         if getattr(model, '_echr_arena', None) is not arena or not arena.params_in_arena():
             raise ValueError('the optimiser\'s arena is not the model\'s (call model.build_arena() after .cuda(), pass it to ClampAdam)')
         # ('EC' / 'EH': no event encoder -- echr_train_step_args.event_direct; anything else was refused by the model's constructor)

@@ -2,6 +2,9 @@
 (the `three_stream` branch that models.setup_lm can return: OldModel :18-187, Attention :366-401,
 ThreeStream_Core :762-823, ThreestreamModel :1040-1043).
 
+Also the one-stream decoder of the reference's default options: ShowAttendTellCore :190-274, ShowAttendTellModel :1009-1012, live with one
+LSTM layer through echr_amd.sat (echr_sat_fwd / _bwd / _step / _sample).
+
 Module/parameter names and shapes match the reference so `state_dict()`s are interchangeable.  The
 sub-modules (nn.Embedding, nn.Linear, nn.LSTMCell) are parameter containers only: `forward` and
 `sample` run the whole sequence through libechr_hip.so (echr_decoder_fwd/bwd, echr_decoder_sample).
@@ -92,9 +95,10 @@ class OldModel(nn.Module):
             # `embed` like the reference does
             self.init_linear = nn.Linear(self.CG_init_feats_dim, self.num_layers * self.rnn_size)
         self.embed = nn.Embedding(self.vocab_size + 1, self.input_encoding_size)
-        if 'three_stream' not in opt.caption_model or 'three_stream_2stream' in opt.caption_model:
-            raise NotImplementedError('caption_model=%r: only the three_stream decoder is on the HIP path' % (opt.caption_model,))
-        self.logit = nn.Linear(3 * self.rnn_size, self.vocab_size + 1)
+        one_stream = opt.caption_model == 'show_attend_tell'
+        if not one_stream and ('three_stream' not in opt.caption_model or 'three_stream_2stream' in opt.caption_model):
+            raise NotImplementedError('caption_model=%r: the three_stream and show_attend_tell decoders are on the HIP path' % (opt.caption_model,))
+        self.logit = nn.Linear((1 if one_stream else 3) * self.rnn_size, self.vocab_size + 1)          # OldModel_NEW.py:41-51
         self.dropout = nn.Dropout(self.drop_prob_lm)
         self.init_weights()
         self._drop_seed = None
@@ -122,11 +126,14 @@ class OldModel(nn.Module):
                 # of the reference), so the rank is mixed into the seed
                 seed ^= ((torch.distributed.get_rank() + 1) * 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF
             self._drop_seed = seed & 0xFFFFFFFFFFFFFFFF
-        c = self.core
-        st = EF.DropState(self._drop_seed, self._drop_calls, self.training, p_tsrm, c.dropout0.p, self.dropout.p)
+        st = EF.DropState(self._drop_seed, self._drop_calls, self.training, p_tsrm, self._stream_dropout_p(), self.dropout.p)
         if self.training:
             self._drop_calls += 1
         return st
+
+    def _stream_dropout_p(self):
+        """p of the per-stream dropout sites (echr_dropout.p_h): the three-stream core's; a core without such sites returns 0."""
+        return self.core.dropout0.p
 
     def native_params(self):
         cached = self.__dict__.get('_native_params')
@@ -363,7 +370,7 @@ class ShowAttendTellCore(nn.Module):
         self.CG_input_dim = (opt.video_context_dim if 'V' in t else 0) + (opt.event_context_dim if 'E' in t else 0) + \
                             (opt.clip_context_dim if 'C' in t else 0)                                        # :219-227
         self.rnn = getattr(nn, opt.CG_rnn_type.upper())(opt.CG_input_encoding_size + self.CG_input_dim, opt.CG_rnn_size, opt.CG_num_layers,
-                                                        bias=False, dropout=opt.CG_drop_prob)
+                                                        bias=False, dropout=opt.CG_drop_prob if opt.CG_num_layers > 1 else 0.0)          # (one layer: nn.LSTM's own dropout has no site)
         if opt.CG_att_hid_size > 0:
             self.ctx2att = nn.Linear(opt.clip_context_dim, opt.CG_att_hid_size)
             self.h2att = nn.Linear(opt.CG_rnn_size, opt.CG_att_hid_size)
@@ -373,36 +380,113 @@ class ShowAttendTellCore(nn.Module):
             self.h2att = nn.Linear(opt.CG_rnn_size, 1)
 
 
-class ShowAttendTellModel(nn.Module):
-    """`caption_model='show_attend_tell'` (models/__init__.py:7-8, OldModel_NEW.py:1009-1012) as a PARAMETER CONTAINER: constructible,
-    state_dict-compatible with the reference (embed, logit [V+1, H], core.rnn.*, core.ctx2att / h2att / alpha_net), movable, savable.
-    experiments/train_SST.sh selects it while it trains the proposal encoder with the captioner idle (train.py:291-295), so that recipe
-    can build its cg_model through this package and write / read the reference's checkpoints.  Its arithmetic is an ablation outside the
-    ECHR hot path: forward / sample raise."""
+class ShowAttendTellModel(OldModel):
+    """`caption_model='show_attend_tell'` (models/__init__.py:7-8, OldModel_NEW.py:1009-1012), the reference's default decoder: ONE attention
+    LSTM stream whose input is [token | video if 'V' | event if 'E' | attended clip if 'C'] (CG_input_feats_type), one dropout site on its
+    output, logit [V+1, H].  state_dict-compatible with the reference (embed, logit, core.rnn.*, core.ctx2att / h2att / alpha_net).
+
+    Live on the HIP path (echr_amd.sat over echr_sat_fwd / _bwd / _step / _sample) with CG_num_layers == 1, an LSTM, CG_att_hid_size > 0 and
+    a non-empty CG_input_feats_type: forward (teacher forcing, with its autograd graph), get_logprobs_state, init_hidden and the greedy
+    sample.  Every other configuration CONSTRUCTS -- experiments/train_SST.sh builds the three-layer one while the captioner stays idle
+    (train.py:291-295) and reads / writes its checkpoints -- and refuses at call time, before any argument is touched.  The state handed from
+    step to step is the UNDROPPED (h, c), each [1, N, H]."""
 
     def __init__(self, opt):
-        super(ShowAttendTellModel, self).__init__()
-        self.opt = opt
-        self.vocab_size, self.seq_length, self.ss_prob = opt.CG_vocab_size, opt.CG_seq_length, 0.0
-        self.rnn_size, self.num_layers = opt.CG_rnn_size, opt.CG_num_layers
-        t = opt.CG_init_feats_type
-        init_dim = (opt.video_context_dim if 'V' in t else 0) + (opt.event_context_dim if 'E' in t else 0) + (opt.clip_context_dim if 'C' in t else 0)
-        if init_dim:
-            self.init_linear = nn.Linear(init_dim, self.num_layers * self.rnn_size)                          # :36-37
-        self.embed = nn.Embedding(self.vocab_size + 1, opt.CG_input_encoding_size)
-        self.logit = nn.Linear(self.rnn_size, self.vocab_size + 1)                                           # :49-51
-        self.dropout = nn.Dropout(opt.CG_drop_prob)
-        with torch.no_grad():                                                                                # init_weights :66-70
-            self.embed.weight.uniform_(-0.1, 0.1)
-            self.logit.bias.zero_()
-            self.logit.weight.uniform_(-0.1, 0.1)
+        super(ShowAttendTellModel, self).__init__(opt)
         self.core = ShowAttendTellCore(opt)
 
-    def _idle(self, *a, **k):
-        raise NotImplementedError("caption_model='show_attend_tell' is a parameter container here (the recipe that selects it, "
-                                  "experiments/train_SST.sh, never runs the captioner); the HIP path implements 'three_stream'")
+    def _refuse(self, what):
+        raise NotImplementedError("caption_model='show_attend_tell': %s" % what)
 
-    forward = sample = get_logprobs_state = _idle
+    def _require_live(self):
+        """The configuration check of every entry: NotImplementedError naming the option, or the echr_sat_args.feats bits."""
+        o = self.opt
+        if o.CG_num_layers != 1:
+            self._refuse('CG_num_layers=%r -- one LSTM layer runs on the HIP path; a deeper stack is a parameter container (the recipe that '
+                         'builds it, experiments/train_SST.sh, never runs the captioner)' % (o.CG_num_layers,))
+        if o.CG_rnn_type.lower() != 'lstm':
+            self._refuse("CG_rnn_type=%r -- the HIP path runs the 'lstm' cell" % (o.CG_rnn_type,))
+        if not o.CG_att_hid_size > 0:
+            self._refuse('CG_att_hid_size=%r -- the HIP path runs the attention with a hidden layer (CG_att_hid_size > 0)' % (o.CG_att_hid_size,))
+        from ..sat import feats_bits
+        feats = feats_bits(o.CG_input_feats_type)
+        if not feats:
+            self._refuse("CG_input_feats_type=%r selects none of 'V', 'E', 'C' -- the reference fails there too (torch.cat of an empty list in "
+                         "get_input_feats, OldModel_NEW.py:241)" % (o.CG_input_feats_type,))
+        return feats
+
+    def _clip(self, clip, clip_mask):
+        cv = self._clip_view(clip, clip_mask)
+        if cv.grad_src is not None:
+            self._refuse("clip_context_type with 'CH' -- the one-stream decoder attends over the C3D rows ('CC'); the gradient into tap_feats "
+                         "through the clip rows is a follow-up")
+        return cv
+
+    def next_drop_state(self, p_tsrm=0.3):
+        """Dropout configuration for the next forward: the decoder's one site is on its output (p_h is not drawn)."""
+        self._require_live()
+        return super(ShowAttendTellModel, self).next_drop_state(p_tsrm)
+
+    def _stream_dropout_p(self):
+        return 0.0
+
+    def _native_params_now(self):
+        c = self.core
+        return (self.embed.weight, self.logit.weight, self.logit.bias, c.rnn.weight_ih_l0, c.rnn.weight_hh_l0,
+                c.ctx2att.weight, c.ctx2att.bias, c.h2att.weight, c.h2att.bias, c.alpha_net.weight, c.alpha_net.bias)
+
+    def prepare(self, *a, **k):
+        self._refuse('prepare() -- the overlap-encoder pre-compute belongs to the three_stream decoder')
+
+    def forward(self, video=None, event=None, clip=None, clip_mask=None, seq=None, drop=None, prepared=None):
+        """Teacher-forced log-probs [N,S,V+1] (OldModel_NEW.py:98-130)."""
+        from .. import sat
+        feats = self._require_live()
+        if prepared is not None:
+            self.prepare()
+        if self.training and self.ss_prob > 0.0:
+            self._refuse('ss_prob > 0 -- scheduled sampling is never enabled by the reference and is not on the HIP path')
+        cv = self._clip(clip, clip_mask)
+        tokens = self._tokens(seq, cv.feats.device)
+        if drop is None:
+            drop = self.next_drop_state()
+        ps = self.native_params()
+        return sat.SatFunction.apply(video, event, cv.feats, cv.ev_start, cv.ev_len, tokens, cv.max_len, cv.rows_disjoint, drop,
+                                     self._grad_sink(ps), self._initial_state(video, event, cv), feats, *ps)
+
+    def init_hidden(self, video=None, event=None, clip=None, clip_mask=None):
+        """Initial state (h, c), each [1,N,H] (OldModel_NEW.py:72-96)."""
+        self._require_live()
+        return super(ShowAttendTellModel, self).init_hidden(video, event, clip, clip_mask)
+
+    def get_logprobs_state(self, it=None, video=None, event=None, clip=None, clip_mask=None, state=None):
+        """One decoder timestep (OldModel_NEW.py:133-137): (log-probs [N,V+1], (h', c')), the state undropped and [1,N,H].  Forward only; in
+        training mode each call draws a fresh dropout stream."""
+        from .. import sat
+        feats = self._require_live()
+        cv = self._clip(clip, clip_mask)
+        drop = self.next_drop_state()
+        with torch.no_grad():
+            return sat.sat_step(it, video, event, cv.feats, cv.ev_start, cv.ev_len, cv.max_len, state, self.native_params(), feats, drop)
+
+    def sample(self, video=None, event=None, clip=None, clip_mask=None, opt={}):
+        """The greedy branch of OldModel.sample (OldModel_NEW.py:139-187): (seq, logp), or ([], [])."""
+        from .. import sat
+        feats = self._require_live()
+        if int(opt.get('beam_size', 1)) != 1:
+            self._refuse('beam_size=%r -- beam search runs on the three_stream decoder; this one decodes greedily' % (opt.get('beam_size'),))
+        if opt.get('sample_max', 1) != 1:
+            self._refuse('sample_max=0 -- the multinomial decode runs on the three_stream decoder; this one decodes greedily')
+        cv = self._clip(clip, clip_mask)
+        with torch.no_grad():
+            return sat.sat_greedy_sample(video, event, cv.feats, cv.ev_start, cv.ev_len, cv.max_len, self.seq_length, self.native_params(), feats,
+                                         h0=self._initial_state(video, event, cv))
+
+    def sample_train(self, *a, **k):
+        self._refuse("mode='train_rl' -- self-critical training (the sampled pass) runs on the three_stream decoder")
+
+    def sequence_logprobs(self, *a, **k):
+        self._refuse("mode='train_rl' -- self-critical training (the sample's log-probs) runs on the three_stream decoder")
 
 
 def _ablation(name):

@@ -5,7 +5,7 @@ from . import OldModel_NEW as _decoder
 from .MA_attention_8_NEW import MA_Attention8
 from .sst_model import SST
 
-# decoder classes the reference's package namespace exposes; only ThreestreamModel is live on the HIP path
+# decoder classes the reference's package namespace exposes; ThreestreamModel and (with one LSTM layer) ShowAttendTellModel are live on the HIP path
 _DECODER_NAMES = ('ShowAttendTellModel', 'AllImgModel', 'H3Model', 'TwostreamModel', 'Twostream_jump_Model', 'ThreestreamModel',
                   'TwostreamModel_3LSTM', 'H3denseModel', 'H3denaddModel', 'ThreestreamModel_2stream',
                   'ThreestreamModel_2stream_LDA', 'ThreestreamModel_2stream_CC')

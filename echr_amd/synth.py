@@ -193,6 +193,75 @@ CASES = {
 }
 
 
+# The one-stream decoder (caption_model='show_attend_tell', one LSTM layer: echr_amd.sat).  `opt` = overrides of default_opt; the context
+# widths follow CaptionGenerator.change_context_dim.
+#   sat_tiny   the 'tiny' widths and video, input [token | video | event | attended clip]
+#   the others at N = 12, A = 40, V1 = 301, seq_length 7 (tests/golden/case_sat.npz): 'C' alone; 'E' alone (the attention is computed by the
+#   reference and never read: its parameters get no gradient); 'VE'; 'VEC' from a non-zero initial state; 'VEC' with the event vector and the
+#   scene context reading the proposal encoder's states (gradients into tap_feats)
+_SAT = dict(caption_model='show_attend_tell', CG_num_layers=1)
+SAT_CASES = {
+    'sat_tiny': dict(opt=dict(_SAT, CG_input_feats_type='VEC', video_dim=20, hidden_dim=24, lda_dim=12, d_feats=32, d_o=32, n_head=4, CG_rnn_size=32,
+                              CG_input_encoding_size=16, CG_att_hid_size=24, CG_vocab_size=30, CG_seq_length=5),
+                     video=dict(N=3, A=7, L=7, seed=11)),
+    'sat_c': dict(opt=dict(_SAT, CG_input_feats_type='C', CG_vocab_size=300, CG_seq_length=7), video=dict(N=12, A=40, L=9, seed=101)),
+    'sat_e': dict(opt=dict(_SAT, CG_input_feats_type='E', CG_vocab_size=300, CG_seq_length=7), video=dict(N=12, A=40, L=9, seed=102)),
+    'sat_ve': dict(opt=dict(_SAT, CG_input_feats_type='VE', CG_vocab_size=300, CG_seq_length=7), video=dict(N=12, A=40, L=9, seed=103)),
+    'sat_vec_init': dict(opt=dict(_SAT, CG_input_feats_type='VEC', CG_init_feats_type='VEC', CG_vocab_size=300, CG_seq_length=7),
+                         video=dict(N=12, A=40, L=9, seed=104)),
+    'sat_vec_eh': dict(opt=dict(_SAT, CG_input_feats_type='VEC', event_context_type='EH', video_context_type='VLVCVH', CG_vocab_size=300,
+                                CG_seq_length=7), video=dict(N=12, A=40, L=9, seed=105)),
+}
+
+
+def sat_state_dict_shapes(opt):
+    """Name -> shape of CaptionGenerator.state_dict() with caption_model='show_attend_tell' (printed from the reference: models/OldModel_NEW.py
+    :36-51, :190-216): the event encoder's keys as in state_dict_shapes, then embed, logit [V1, H], init_linear [L*H, .], core.rnn.* (no
+    biases) and the three attention projections directly under core."""
+    s = {k: v for k, v in state_dict_shapes(opt).items() if k.startswith('fusion_model.')}
+    V1, H, E, Ha, nl = opt.CG_vocab_size + 1, opt.CG_rnn_size, opt.CG_input_encoding_size, opt.CG_att_hid_size, opt.CG_num_layers
+    vt, et, ct = opt.video_context_type, opt.event_context_type, getattr(opt, 'clip_context_type', 'CC')
+    vi = (opt.lda_dim if 'VL' in vt else 0) + (opt.video_dim if 'VC' in vt else 0) + (opt.hidden_dim if 'VH' in vt else 0)
+    ev = opt.d_o if 'ER' in et else (opt.video_dim if 'EC' in et else 0) + (opt.hidden_dim if 'EH' in et else 0)
+    cl = (opt.video_dim if 'CC' in ct else 0) + (opt.hidden_dim if 'CH' in ct else 0)
+    width = lambda t: (vi if 'V' in t else 0) + (ev if 'E' in t else 0) + (cl if 'C' in t else 0)
+    s.update({'lm_model.embed.weight': (V1, E), 'lm_model.logit.weight': (V1, H), 'lm_model.logit.bias': (V1,)})
+    if width(getattr(opt, 'CG_init_feats_type', '')):
+        s['lm_model.init_linear.weight'] = (nl * H, width(opt.CG_init_feats_type))
+        s['lm_model.init_linear.bias'] = (nl * H,)
+    for l in range(nl):
+        s['lm_model.core.rnn.weight_ih_l%d' % l] = (4 * H, E + width(opt.CG_input_feats_type) if l == 0 else H)
+        s['lm_model.core.rnn.weight_hh_l%d' % l] = (4 * H, H)
+    s.update({'lm_model.core.ctx2att.weight': (Ha, cl), 'lm_model.core.ctx2att.bias': (Ha,),
+              'lm_model.core.h2att.weight': (Ha, H), 'lm_model.core.h2att.bias': (Ha,),
+              'lm_model.core.alpha_net.weight': (1, Ha), 'lm_model.core.alpha_net.bias': (1,)})
+    return s
+
+
+def make_sat_params(opt, seed=0):
+    """make_params for the one-stream decoder: sorted-name order from one RandomState, the reference's initial ranges (embed / logit +-0.1,
+    nn.LSTM and nn.Linear +-1/sqrt(fan))."""
+    rs = np.random.RandomState(seed)
+    shapes = sat_state_dict_shapes(opt)
+    out = {}
+    for name in sorted(shapes):
+        shp = shapes[name]
+        r = 1.0 / math.sqrt(opt.CG_rnn_size) if '.core.rnn.' in name else _init_range(name, shapes, opt.CG_rnn_size)
+        out[name] = rs.uniform(-r, r, size=shp).astype(np.float32) if r > 0 else np.zeros(shp, np.float32)
+    return out
+
+
+def make_sat_case(name, param_seed=0, video_seed=None):
+    """(opt, params, video) of a named one-stream case; `video_seed` replaces the case's own (tools/make_golden_sat.py picks it)."""
+    c = SAT_CASES[name]
+    opt = default_opt(**c['opt'])
+    vd = dict(c['video'])
+    if video_seed is not None:
+        vd['seed'] = video_seed
+    vid = make_video(V1=opt.CG_vocab_size + 1, video_dim=opt.video_dim, hidden_dim=opt.hidden_dim, lda_dim=opt.lda_dim, **vd)
+    return opt, make_sat_params(opt, param_seed), vid
+
+
 def sst_param_shapes(opt):
     """Name -> shape of SST.state_dict() (models/sst_model.py:12,22-23: nn.LSTM(video_dim, hidden_dim, 2 layers) + Linear(hidden_dim, K))."""
     H, D, K = opt.hidden_dim, opt.video_dim, opt.K

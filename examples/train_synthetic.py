@@ -33,6 +33,9 @@ batch form, JointBatchStep with `--joint`, SelfCriticalBatchStep with `--self_cr
 ranks, one clamp + Adam per model, identical on every rank.  `--dist_backend gloo` with fewer devices than ranks is the one-GPU rehearsal:
 every rank on cuda:0, launch-per-phase recurrences.  Without a process group nothing changes.
 
+`--caption_model show_attend_tell --CG_input_feats_type VEC` trains the reference's default one-stream decoder (one LSTM layer, echr_amd.sat)
+on the plain autograd path -- forward, criterion, backward, clip_gradient, ClampAdam.step over the flat arena -- and decodes greedily.
+
 usage: python examples/train_synthetic.py [--iters 20] [--m_batch 2] [--joint] [--pre_tap] [--self_critical [--reward ciderd]] [--save /tmp/echr_ckpt.pth]
                                           [--resume /tmp/echr_ckpt.pth]
 """
@@ -268,6 +271,11 @@ def main(argv=None):
                                                                         "--m_batch V are built for it")
     ap.add_argument('--CG_init_feats_type', type=str, default='', help="non-zero initial decoder state from 'V', 'E', 'C' (opts.py); the batches "
                                                                        "of --m_batch V are built for it")
+    ap.add_argument('--caption_model', type=str, default='three_stream', help="'three_stream' (the ECHR recipe) or 'show_attend_tell' (the "
+                                                                                "reference's default one-stream decoder, one LSTM layer: trains "
+                                                                                "on the plain autograd path, one video per call)")
+    ap.add_argument('--CG_input_feats_type', type=str, default='', help="show_attend_tell: the contexts its LSTM reads beside the token, from "
+                                                                        "'V', 'E', 'C' (e.g. VEC)")
     ap.add_argument('--dist_backend', type=str, default='nccl', help="under torchrun: 'nccl' (RCCL, one device per rank) or 'gloo' (also the "
                                                                      "rehearsal with every rank on one device)")
     ap.add_argument('--save', type=str, default='')
@@ -285,6 +293,14 @@ def main(argv=None):
     opt = synth.default_opt(vocab_size=a.vocab, seq_length=10, K=32, lr=a.lr)
     opt.clip_context_type = a.clip_context_type
     opt.CG_init_feats_type = a.CG_init_feats_type
+    if a.caption_model == 'show_attend_tell':
+        # the one-stream decoder has no one-call step, batch or self-critical entry yet: forward, criterion, backward, clip, ClampAdam.step
+        if a.self_critical or 'RANK' in os.environ or (a.joint and a.m_batch > 1 and not a.no_fused):
+            raise SystemExit('--caption_model show_attend_tell trains on the autograd path: not with --self_critical, torchrun or the batched --joint')
+        opt.caption_model, opt.CG_num_layers, opt.CG_input_feats_type = 'show_attend_tell', 1, a.CG_input_feats_type
+        a.no_fused = True
+    elif a.caption_model != 'three_stream':
+        raise SystemExit("--caption_model is 'three_stream' or 'show_attend_tell'")
     torch.manual_seed(0)
     tap_model = models.setup_tap(opt).to(dev)
     cg_model = echr_amd.CaptionGenerator(opt).to(dev)

@@ -963,6 +963,75 @@ int echr_persist_read_stamps(uint64_t* dst, int32_t max_entries);
 /* stand-alone element-wise clamp (misc/utils.py:107-111) for optimisers other than the fused one */
 int echr_clamp(float* g, int64_t n, float clip, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * One-stream attention decoder: caption_model 'show_attend_tell' with CG_num_layers = 1 (the default of the reference's opts.py).
+ * Replaces ShowAttendTellCore.forward (models/OldModel_NEW.py:190-274) under OldModel.forward / get_logprobs_state / the greedy branch of
+ * OldModel.sample (:98-187).  Per event n and step t, from h(-1) = c(-1) = 0 or h0:
+ *   q = h2att(h(t-1))  (the UNDROPPED state);  w = softmax over the event's own rows of alpha_net(tanh(ctx2att(clip) + q));  att = sum_a w_a clip_a;
+ *   x = [embed(it) | video if V | event if E | att if C];  gates = x . W_ih^T + h(t-1) . W_hh^T (no bias; i, f, g, o);  LSTM cell;
+ *   logp = log_softmax(logit(dropout(h(t))))     -- ONE dropout site (echr_dropout.p_out, the counter's site 4, element n * H + u, step t).
+ * The state handed from step to step (and in / out of echr_sat_step) is the undropped (h, c).
+ * Per step the recurrence is the attention launches of the three-stream decoder and ONE fused kernel (csrc/sat.hip): [att | h(t-1)] .
+ * [W_ih[:, C columns] | W_hh]^T on the f32-input matrix cores (K = D + H, or H without 'C'), the pre-computed token / video / event rows and
+ * the cell in its epilogue; the reverse pass is one kernel per step as well (d gates from the saved activations, then d [att | h(t-1)]
+ * against the same panel).  Every sum has a fixed order except where the three-stream decoder's attention backward and the split-K weight
+ * gradients add atomically; echr_config_set("deterministic", 1) replaces those too.  H, D, E, Ha multiples of 4; any N >= 1.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct {
+    int32_t N, A, Tv, D, H, E, Ha, De, Dv, V1, S;
+    int32_t feats;                             /* CG_input_feats_type: bit 0 'V', bit 1 'E', bit 2 'C' (non-zero).  Fixes the columns of w_ih
+                                                  behind the E token columns: [video Dv if V | event De if E | attended clip D if C] */
+    int32_t rows_disjoint;                     /* 1: no two events share a video row */
+    const float* embed;                        /* embed.weight [V1,E] */
+    const float *w_logit, *b_logit;            /* logit [V1,H],[V1] */
+    const float* w_ih;                         /* core.rnn.weight_ih_l0 [4H, E + X], X = the widths `feats` selects */
+    const float* w_hh;                         /* core.rnn.weight_hh_l0 [4H, H] */
+    const float *w_c2a, *b_c2a;                /* core.ctx2att [Ha,D],[Ha] */
+    const float *w_h2a, *b_h2a;                /* core.h2att [Ha,H],[Ha] */
+    const float *w_alpha, *b_alpha;            /* core.alpha_net [1,Ha],[1] */
+    const float* c3d;                          /* [Tv,D] */
+    const int32_t *ev_start, *ev_len;          /* [N] */
+    const float* event;                        /* [N,De]; read with 'E' only */
+    const float* video;                        /* [Dv];   read with 'V' only */
+    const int32_t* tokens;                     /* [S,N] time-major input tokens */
+    const float* h0;                           /* optional [N,H]: h(-1) = c(-1) = init_linear(...) (one layer); NULL = zeros */
+    float* ws;                                 /* echr_sat_ws_floats; saved for echr_sat_bwd */
+    float* logp;                               /* out [N,S,V1] */
+    int32_t train;                             /* 1 = echr_sat_bwd will follow on this workspace (informative: the forward saves the same either way) */
+} echr_sat_args;
+
+typedef struct {
+    /* parameter gradients: written, or accumulated into when `zeroed` */
+    float *g_embed, *g_w_logit, *g_b_logit, *g_w_ih, *g_w_hh;
+    float *g_w_c2a, *g_b_c2a, *g_w_h2a, *g_b_h2a, *g_w_alpha, *g_b_alpha;      /* bit 2 of `feats` clear: exactly zero, no attention launch */
+    float* g_event;                            /* [N,De] written with 'E' only (never touched otherwise); may be NULL */
+    float* g_video;                            /* [Dv] written with 'V' only; may be NULL */
+    float* g_h0;                               /* [N,H] written when echr_sat_args.h0 is given; may be NULL */
+    const float* g_logp;                       /* [N,S,V1] upstream gradient */
+    float* ws_bwd;                             /* scratch, echr_sat_ws_bwd_floats */
+    int32_t zeroed;                            /* 1: every parameter-gradient buffer arrives zero-filled (flat arena) */
+} echr_sat_grads;
+
+int64_t echr_sat_ws_floats(const echr_sat_args* a);
+int64_t echr_sat_ws_bwd_floats(const echr_sat_args* a);
+int echr_sat_fwd(const echr_sat_args* a, const echr_dropout* drop, void* stream);
+int echr_sat_bwd(const echr_sat_args* a, const echr_sat_grads* g, const echr_dropout* drop, void* stream);
+/* ONE get_logprobs_state: a->S is ignored (1), tokens = it [N], logp = out [N,V1], ws from echr_sat_ws_floats with S = 1; h / c are [1,N,H],
+ * the undropped state.  drop->offset selects the dropout stream of the call (step 0 of it).  Forward only; bitwise reproducible. */
+int echr_sat_step(const echr_sat_args* a, const float* h_in, const float* c_in, float* h_out, float* c_out, const echr_dropout* drop, void* stream);
+/* Greedy decode: seq_len steps on device without host syncs, eval mode; seq / seq_logp / n_unfinished as the three-stream sampler's argument struct
+ * defines them; ties go to the lowest index.  dec: S, tokens, logp unused; ws from echr_sat_ws_floats with S = seq_len. */
+typedef struct {
+    echr_sat_args dec;
+    int32_t seq_len;
+    int64_t* seq;            /* [N, seq_len] */
+    float* seq_logp;         /* [N, seq_len] */
+    int32_t* n_unfinished;   /* [seq_len + 1] */
+    float* ws_sample;        /* echr_sat_sampler_ws_floats */
+} echr_sat_sample_args;
+int64_t echr_sat_sampler_ws_floats(const echr_sat_args* a);
+int echr_sat_sample(const echr_sat_sample_args* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

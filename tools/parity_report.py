@@ -13,7 +13,10 @@ it, persistent and wavefront.
 --decsat: the decoder recurrences' trained-regime variants (synth.make_decsat, tests/decoder_regime_ref.py) -- e_ref per variant and mode (log-probs,
 loss, worst gradient tensor, worst LSTM gate slice; the E_REF table of tests/test_gpu_decoder_regime.py holds the larger of eval and train) and, when a
 GPU is present, the HIP path against the same float64 oracle beside it per route: persistent on fp16 pairs, persistent in exact fp32,
-launch-per-phase (70 events: the launch form alone; the batch: forward_batch)."""
+launch-per-phase (70 events: the launch form alone; the batch: forward_batch).
+
+--sat: the one-stream decoder's cases (synth.SAT_CASES, tests/sat_ref.py) -- e_ref per variant and mode and, when a GPU is present, the HIP path
+against the same float64 run beside it."""
 import sys, os; sys.path.insert(0, os.environ.get('GRAFT_REPO_ROOT', '/root/repo')); sys.path.insert(0, os.path.join(os.environ.get('GRAFT_REPO_ROOT', '/root/repo'), 'tests'))
 import numpy as np, torch
 import util as U
@@ -106,6 +109,32 @@ def decsat_report():
     print(line, flush=True)
 
 
+def sat_report():
+    """The one-stream decoder (synth.SAT_CASES, tests/sat_ref.py): e_ref per variant and mode (log-probs and loss relative, worst gradient tensor
+    and d tap_feats of their max-norms) and, when a GPU is present, the HIP path against the same float64 run beside it (the gates of
+    tests/test_gpu_sat.py are ten times the largest of those columns)."""
+    from tests import sat_ref as R
+    gpu = torch.cuda.is_available()
+    if gpu:
+        from tests import test_gpu_sat as T
+
+    def errs(got, ref):
+        worst = max((U.relerr(got[2][k], g, U.GRAD_FLOOR), k) for k, g in ref[2].items() if g is not None and k not in R.NOISE_ONLY)
+        return U.relerr(got[0], ref[0]), abs(got[1] - ref[1]) / abs(ref[1]), worst[0], U.relerr(got[3], ref[3], U.GRAD_FLOOR), worst[1]
+    fmt = 'logp %.1e loss %.1e grad %.1e d tap %.1e (%s)'
+    for name in synth.SAT_CASES:
+        opt, params, vid = synth.make_sat_case(name)
+        for train in (False, True):
+            ref = R.run(opt, params, vid, train, dtype=torch.float64)
+            line = '%-13s %s  e_ref: ' % (name, 'train' if train else 'eval ') + fmt % errs(R.run(opt, params, vid, train), ref)
+            if gpu:
+                line += ' | HIP: ' + fmt % errs(T._run(opt, params, vid, train), ref)
+            print(line, flush=True)
+
+
+if '--sat' in sys.argv:
+    sat_report()
+    sys.exit(0)
 if '--decsat' in sys.argv:
     decsat_report()
     sys.exit(0)
