@@ -1207,25 +1207,33 @@ int att_bwd_launch(const AttShape& s, const float* PALL, const float* C3D, const
 // d P_all (into the zero-filled DPALL [Tv, Ha]) and d alpha / d b_alpha (ADDED to g_alpha / g_balpha) over all S steps; GAREP / GBREP: the
 // zero-filled replica scratch [ALPHA_REP, Ha] / [ALPHA_REP] of the atomic form (att_post_replicas())
 int att_post_replicas() { return ALPHA_REP; }
+// att_post in fixed-order form (deterministic mode), no atomics: one d alpha / d b_alpha row per workgroup (*ga [*nblk, Ha], *gb [*nblk] in det_scratch;
+// their column sums stay with the caller) and, for events that share video rows, one d P_all slab row per (event, position), folded into DPALL in order
+static int att_post_fixed_order(const AttDims& ad, int Tv, int S, int rows_disjoint, const float* PALL, const float* QS, const float* alpha, const float* DSC,
+                                const int* ev_start, const int* ev_len, float* DPALL, float** ga, float** gb, int* nblk, hipStream_t st) {
+    const long nb = (long)ad.N * ((ad.A + 7) / 8);
+    *ga = det_scratch(DET_ALPHA, (size_t)nb * (ad.Ha + 1));
+    if (!*ga) return -12;
+    *gb = *ga + nb * ad.Ha; *nblk = (int)nb;
+    RC(fill_zero(*ga, nb * (ad.Ha + 1), st));          // workgroups behind an event's end return early: their rows stay zero
+    float* dps = nullptr;
+    if (!rows_disjoint) { dps = det_scratch(DET_DPALL, (size_t)ad.N * ad.A * ad.Ha); if (!dps) return -12; }
+    RC(launch_att_post(ad, PALL, QS, alpha, DSC, ev_start, ev_len, dps ? dps : DPALL, *ga, *gb, S, dps ? 2 : 1, st, 1));
+    if (dps) {
+        hipLaunchKernelGGL(dpall_fold_kernel, dim3(Tv), dim3(256), 0, st, dps, ev_start, ev_len, DPALL, ad.N, ad.A, ad.Ha);
+        RC(check_launch("dpall_fold"));
+    }
+    return 0;
+}
 int att_post_launch(const AttShape& s, int Tv, int S, int rows_disjoint, const float* PALL, const float* QS, const float* alpha, const float* DSC,
                     const int* ev_start, const int* ev_len, float* DPALL, float* GAREP, float* GBREP, float* g_alpha, float* g_balpha, hipStream_t st) {
     const AttDims ad{s.N, s.A, s.Ha, s.D};
     const int Ha = s.Ha;
-    if (det_mode()) {          // fixed-order form, as in the three-stream backward's part B
-        const long nblk = (long)s.N * ((s.A + 7) / 8);
-        float* ga = det_scratch(DET_ALPHA, (size_t)nblk * (Ha + 1));
-        if (!ga) return -12;
-        float* gb = ga + nblk * Ha;
-        RC(fill_zero(ga, nblk * (Ha + 1), st));
-        float* dps = nullptr;
-        if (!rows_disjoint) { dps = det_scratch(DET_DPALL, (size_t)s.N * s.A * Ha); if (!dps) return -12; }
-        RC(launch_att_post(ad, PALL, QS, alpha, DSC, ev_start, ev_len, dps ? dps : DPALL, ga, gb, S, dps ? 2 : 1, st, 1));
-        if (dps) {
-            hipLaunchKernelGGL(dpall_fold_kernel, dim3(Tv), dim3(256), 0, st, dps, ev_start, ev_len, DPALL, s.N, s.A, Ha);
-            RC(check_launch("dpall_fold"));
-        }
-        RC(colsum(ga, Ha, (int)nblk, Ha, g_alpha, true, st));
-        return colsum(gb, 1, (int)nblk, 1, g_balpha, true, st);
+    if (det_mode()) {
+        float *ga, *gb; int nblk;
+        RC(att_post_fixed_order(ad, Tv, S, rows_disjoint, PALL, QS, alpha, DSC, ev_start, ev_len, DPALL, &ga, &gb, &nblk, st));
+        RC(colsum(ga, Ha, nblk, Ha, g_alpha, true, st));
+        return colsum(gb, 1, nblk, 1, g_balpha, true, st);
     }
     RC(launch_att_post(ad, PALL, QS, alpha, DSC, ev_start, ev_len, DPALL, GAREP, GBREP, S, rows_disjoint ? 1 : 0, st));
     RC(colsum(GAREP, Ha, ALPHA_REP, Ha, g_alpha, true, st));
@@ -1529,17 +1537,6 @@ static int decoder_fwd_impl(const echr_dec_args* a, const echr_dropout* drop, vo
     return logits(st);
 }
 
-// d W_logit = DLG^T . OUTD (plain overwrite) and d b_logit on packed operands that the caller has prepared
-// bias_too = false: the caller folds the column sum of DLG (d b_logit) into a later multi-problem column-sum launch
-static int logit_grads(const echr_dec_args* a, const echr_dec_grads* g, const DecWs& w, const DecWsBwd& b, bool z, hipStream_t st, bool bias_too = true) {
-    (void)w;
-    const int SN = (g->dlg_ready && g->active_rows && g->n_active > 0) ? g->n_active : a->S * a->N;          // (compacted rows: see echr_decoder_bwd)
-    echr_gemm_desc d = desc_h2(b.PK_DLGT, b.PK_OUTDT, g->g_w_logit, 3 * a->H, a->V1, 3 * a->H, SN);
-    d.split_k = 1;                         // one k slice per tile: a plain overwrite, no read of the (zeroed or stale) 30 MB buffer
-    RC(gemm(d, st));
-    return bias_too ? colsum(b.DLG, b.ldg, SN, a->V1, g->g_b_logit, z, st) : 0;
-}
-
 extern "C" int echr_decoder_bwd(const echr_dec_args* a, const echr_dec_grads* g, const echr_dropout* drop, void* stream) {
     return echr::decoder_bwd_checked(a, g, drop, stream, nullptr);
 }
@@ -1575,435 +1572,377 @@ int echr::decoder_bwd_checked(const echr_dec_args* a, const echr_dec_grads* g, c
     return decoder_bwd_parts(a, g, drop, stream, 0, rw);
 }
 
-// part 0: the whole call.  echr_train_step's joint mode (d tap_feats wanted early, step.hip) issues it in two pieces: 1 = what runs on the
-// caller's stream (late fusion, reverse recurrence, d event), 2 = what runs on the library's helper streams (every other gradient) -- forked
-// from the caller's stream where the second call is made, i.e. behind the event encoder's backward.  Pieces need async_tail = 2.
-int echr::decoder_bwd_parts(const echr_dec_args* a, const echr_dec_grads* g, const echr_dropout* drop, void* stream, int part, const float* rw) {
-    if (prep().fill_pending) {
-        prep().fill_pending = false;
-        if (hipStreamWaitEvent((hipStream_t)stream, prep().fill_done, 0) != hipSuccess) { set_error("decoder_bwd: stream wait failed"); return -5; }
-    }
+// ---- decoder backward: one plan (BwdPlan, made at entry, before the first launch), stages as functions of (plan, stream), two schedulers
+// (bwd_lstm_stage, bwd_tail_stage).  No stage reassigns its stream; what one scheduler leaves for the other travels in BwdSched.
+// Which stage runs on which stream.  C = the caller's stream, T = the tail stream, P = the prepare stream (idle during a backward pass); head =
+// d logits + scratch + late fusion, rec = reverse recurrence (+ d h0), lstm = weight gradients, bias sums, d W_ih0[:, E:], scene gradients, wl =
+// logit-layer gradients, att = attention parameters, emb = embedding chain:
+//   schedule                     head          rec    d event  lstm   wl               att    emb    forks / joins
+//   synchronous (also phase 2)   C (with wl)   C      C        C      C, inside head   C      C      none
+//   async_tail 1                 C             C      C        C      T                T      T      T forks behind lstm (tail().fork); tail().done
+//   async_tail 2 (zeroed)        C             C      C        P      T                T      P      P and T fork behind rec off ONE event (prep().fork), P sums
+//                                                                                                   d gates0 per event itself; tail().done3 / tail().done
+//   staged phases 1 / 3 / 4      C, phase 1    C, 3   C, 3     C, 3   C, inside head   C, 4   C, 4   none
+//   two-piece parts 1 / 2        C, part 1     C, 1   C, 1     P, 2   T, 2             T, 2   P, 2   part 2 forks P and T where it is called; done3 / done
+// async_tail needs phase 0 and the tail stream, else the call is synchronous; async_tail 2 without zeroed gradients runs as async_tail 1; without the
+// prepare stream (a prepare is pending) lstm follows d event on C and emb moves to T.  Deferred wl on the native product path needs part 0.  A
+// data-parallel hand-over point is marked behind wl (on T) and behind lstm (on P).  part 0 is the whole call; the two pieces are echr_train_step's
+// joint mode (d tap_feats wanted early, step.hip): part 2 is called, and forks, behind the event encoder's backward.  Pieces need async_tail = 2.
+enum { BWD_HEAD = 1, BWD_REC = 2, BWD_LSTM = 4, BWD_TAIL = 8 };          // the stage mask of a call
+enum { EV_SUMS = 1, EV_D_WEIGHT = 2, EV_D_EVENT = 4 };                      // what bwd_event_grads forms, in this order
+struct BwdPlan {
+    const echr_dec_args* a; const echr_dec_grads* g; const float* rw;
+    int part, N, S, H, E, Ha, A, D, V1, SN, cin[3];
+    DecWs w; DecWsBwd b; DropCfg dh, dout;
+    bool z, h2; float zb;          // z: gradient buffers pre-zeroed by the caller: accumulate (beta zb = 1), no fills; h2: products on h2-packed operands
+    // echr_train_step's compacted late-fusion stage: d logits exist for the SNc rows with a non-zero criterion mask only (rows act[i]);
+    // crec: the recurrent weight gradients / d XT on the active rows too (the k gather rides in the h2 packs: the native products keep all rows)
+    bool compact, crec; int SNc, SNr; const int *act, *actr;
+    bool bwd_persist;              // the reverse recurrence runs as the persistent launch (same test as the recurrence stage applies)
+    int stages;                    // BWD_*: late fusion | reverse recurrence | its batched parameter gradients | attention + embedding gradients
+    bool defer_wl;                 // the logit-layer gradients, which nothing in the backward pass reads, are formed on the tail stream
+    bool lstm_on_helper;           // async_tail = 2: only d event on the caller's stream, the rest of the LSTM-layer stage on the prepare stream
+    bool async_tail;               // the tail stage runs on the tail stream, joined by the caller
+    const float* outd_rows;        // native + compact: the forward's gathered [n_active, 3H] operand
+};
+struct BwdSched { bool embed_queued = false, bias_owed = false; };          // embedding chain already queued (prepare stream) | d b_logit still owed (tail)
+// Every check that needs no launch result, before the first launch: a refused call queues nothing.
+static int bwd_plan(const echr_dec_args* a, const echr_dec_grads* g, const echr_dropout* drop, int part, const float* rw, BwdPlan& p) {
     ECHR_REQUIRE(part == 0 || (g->phase == 0 && g->async_tail == 2 && g->zeroed && config().gemm_h2 && tail().ok),
                  "decoder_bwd: the two-piece form needs phase 0, async_tail 2, zeroed gradients, the h2 path and the helper streams");
-    hipStream_t st = (hipStream_t)stream;
-    const int N = a->N, S = a->S, H = a->H, E = a->E, Ha = a->Ha, A = a->A, D = a->D, V1 = a->V1;
-    const int SN = S * N;
-    DecWs w = carve_ws(a, a->ws);
-    DecWsBwd b = carve_ws_bwd(a, g->ws_bwd);
-    const DropCfg dh = make_drop(drop, drop ? drop->p_h : 0.f), dout = make_drop(drop, drop ? drop->p_out : 0.f);
-    const int cin[3] = {E + a->De, E + D, E + a->Dv};
-    const bool z = g->zeroed != 0;             // gradient buffers pre-zeroed by the caller: accumulate, no fills
-    const float zb = z ? 1.f : 0.f;
-    // echr_train_step's compacted late-fusion stage: d logits exist for the SNc rows with a non-zero criterion mask only (rows act[i])
-    const bool compact = g->dlg_ready && g->active_rows && g->n_active > 0;
-    const int SNc = compact ? g->n_active : SN;
-    const int* act = compact ? g->active_rows : nullptr;
-    // the recurrent weight gradients / d XT on the active rows too
-    const bool crec = compact && config().gemm_h2;          // (the k gather rides in the h2 packs: the native products keep all rows there)
-    const int SNr = crec ? SNc : SN;
-    const int* actr = crec ? act : nullptr;
-    ECHR_REQUIRE(!compact || (g->phase == 0 && g->async_tail != 0), "decoder_bwd: active_rows needs the asynchronous tail");
-
+    p.a = a; p.g = g; p.rw = rw; p.part = part;
+    p.N = a->N; p.S = a->S; p.H = a->H; p.E = a->E; p.Ha = a->Ha; p.A = a->A; p.D = a->D; p.V1 = a->V1; p.SN = a->S * a->N;
+    p.cin[0] = a->E + a->De; p.cin[1] = a->E + a->D; p.cin[2] = a->E + a->Dv;
+    p.w = carve_ws(a, a->ws); p.b = carve_ws_bwd(a, g->ws_bwd);
+    p.dh = make_drop(drop, drop ? drop->p_h : 0.f); p.dout = make_drop(drop, drop ? drop->p_out : 0.f);
+    p.z = g->zeroed != 0; p.zb = p.z ? 1.f : 0.f; p.h2 = config().gemm_h2 != 0;
+    p.compact = g->dlg_ready && g->active_rows && g->n_active > 0; p.crec = p.compact && p.h2;
+    p.SNc = p.compact ? g->n_active : p.SN; p.act = p.compact ? g->active_rows : nullptr;
+    p.SNr = p.crec ? p.SNc : p.SN; p.actr = p.crec ? p.act : nullptr;
+    ECHR_REQUIRE(!p.compact || (g->phase == 0 && g->async_tail != 0), "decoder_bwd: active_rows needs the asynchronous tail");
     ECHR_REQUIRE(g->phase >= 0 && g->phase <= 4, "decoder_bwd: phase must be 0..4");
-    // stages: late fusion | reverse recurrence + LSTM-layer gradients (part A) | attention + embedding gradients (part B)
-    const bool do_a = (g->phase == 0 || g->phase == 1) && part != 2;
-    const bool do_rec_main = (g->phase == 0 || g->phase == 2 || g->phase == 3) && part != 2;          // the reverse recurrence itself
-    const bool do_rec = g->phase == 0 || g->phase == 2 || g->phase == 3;                                // ... and its batched parameter gradients
-    const bool do_pb = (g->phase == 0 || g->phase == 2 || g->phase == 4) && part != 1;
-    // the reverse recurrence of this call runs as the persistent launch (same test as stage 3 applies)
-    const bool bwd_persist = persist_bwd_eligible(a);
-    // 1. d logits (time-major, padded leading dimension)
-    if (do_a) {
+    const int all = BWD_HEAD | BWD_REC | BWD_LSTM | BWD_TAIL;
+    const int by_phase[5] = {all, BWD_HEAD, BWD_REC | BWD_LSTM | BWD_TAIL, BWD_REC | BWD_LSTM, BWD_TAIL};
+    p.stages = by_phase[g->phase] & (part == 1 ? BWD_HEAD | BWD_REC | BWD_LSTM : part == 2 ? BWD_LSTM | BWD_TAIL : all);
+    const bool tail_ok = g->phase == 0 && g->async_tail != 0 && tail().ok;
+    p.defer_wl = tail_ok && (p.h2 || part == 0);
+    p.lstm_on_helper = p.defer_wl && g->async_tail == 2 && p.z;
+    p.async_tail = tail_ok && (p.stages & BWD_TAIL);
+    ECHR_REQUIRE(p.h2 || !p.compact || p.defer_wl, "decoder_bwd: active_rows on the native product path needs the deferred logit-layer gradients");
+    ECHR_REQUIRE(!(p.stages & BWD_HEAD) || !p.h2 || !p.compact || p.defer_wl, "decoder_bwd: active_rows needs the deferred logit-layer gradients");
+    p.bwd_persist = persist_bwd_eligible(a); p.outd_rows = (p.compact && !p.h2) ? p.w.PK_OUTD : p.w.OUTD;
+    return 0;
+}
+// 1. d logits (time-major, padded leading dimension), the transposed recurrent weights and the zero-filled scratch
+static int bwd_dlogits_and_scratch(const BwdPlan& p, hipStream_t st) {
+    const echr_dec_args* a = p.a; const echr_dec_grads* g = p.g; const DecWsBwd& b = p.b; const int N = p.N, S = p.S, H = p.H, E = p.E, V1 = p.V1;
     if (!g->dlg_ready) {          // (echr_train_step formed d logits in the pass that read the logits)
         if (!g->g_logp && !g->nll_msum) RC(colsum(g->nll_mask, 1, N * S, 1, b.MSUM, false, st));
         RC(logsoftmax_bwd(a->logp, g->g_logp, g->nll_target, g->nll_target_i64, g->nll_mask, g->g_loss, g->nll_msum ? g->nll_msum : b.MSUM, b.DLG, b.ldg, N, S, V1, st,
-                           rw));
+                           p.rw));
     }
     // scratch that is accumulated into, and the transposed recurrent weights (every d h / d ATT product of the reverse recurrence
     // then has the same NT form as forward): two launches, independent of everything above
     // (the persistent reverse launch builds its weight images from the untransposed matrices: nothing to transpose then)
-    if (!bwd_persist) {
+    if (!p.bwd_persist) {
         const TransposeJob tj[5] = {{a->w_hh[0], H, b.WT_HH[0], 4 * H, 4 * H, H}, {a->w_hh[1], H, b.WT_HH[1], 4 * H, 4 * H, H},
-                                    {a->w_hh[2], H, b.WT_HH[2], 4 * H, 4 * H, H}, {a->w_ih[1] + E, cin[1], b.WT_ATT, 4 * H, 4 * H, D},
-                                    {a->w_h2a, H, b.WT_H2A, Ha, Ha, H}};
+                                    {a->w_hh[2], H, b.WT_HH[2], 4 * H, 4 * H, H}, {a->w_ih[1] + E, p.cin[1], b.WT_ATT, 4 * H, 4 * H, p.D},
+                                    {a->w_h2a, H, b.WT_H2A, p.Ha, p.Ha, H}};
         RC(transpose_multi(tj, 5, st));
     }
     if (scratch_ahead() == g->ws_bwd && g->dlg_ready) {
         // echr_train_step queued this fill behind the decoder's prepare (decoder_bwd_scratch_ahead); this stream waited for it on entry
         if (g->zero_extra && g->zero_extra_count > 0) RC(fill_zero(g->zero_extra, (long)g->zero_extra_count, st));
     } else {
-        float* zp[FILL_MAX_JOBS];
-        long zn[FILL_MAX_JOBS];
-        const int nz = bwd_scratch_ranges(a, g, b, bwd_persist, zp, zn);
-        RC(fill_zero_multi(zp, zn, nz, st));
+        float* zp[FILL_MAX_JOBS]; long zn[FILL_MAX_JOBS];
+        RC(fill_zero_multi(zp, zn, bwd_scratch_ranges(a, g, b, p.bwd_persist, zp, zn), st));
     }
     scratch_ahead() = nullptr;
-    }
-    // 2. late fusion gradients.  Both late-fusion products run as NT problems on k-contiguous (transposed) operands so that they qualify for the
-    // bf16-split matrix-core path: d W_logit = DLG^T . OUTD  and  d OUTD = DLG . W_logit.
+    return 0;
+}
+// d W_logit = DLG^T . OUTD and d b_logit over the SNc rows of d logits: on h2-packed operands that the caller has prepared (a plain overwrite), or
+// on the native path through transposes.  bias_too = false: the caller folds the column sum of DLG into a later multi-problem column-sum launch
+static int bwd_logit_grads(const BwdPlan& p, hipStream_t st, bool bias_too = true) {
+    const echr_dec_grads* g = p.g; const DecWsBwd& b = p.b; const int H = p.H, V1 = p.V1, SNc = p.SNc;
     echr_gemm_desc d;
-    const bool h2 = config().gemm_h2 != 0;
-    const bool native_defer_wl = !h2 && part == 0 && g->phase == 0 && g->async_tail != 0 && tail().ok;
-    ECHR_REQUIRE(h2 || !compact || native_defer_wl, "decoder_bwd: active_rows on the native product path needs the deferred logit-layer gradients");
-    const float* outd_rows = (compact && !h2) ? w.PK_OUTD : w.OUTD;          // native + compact: the forward's gathered [n_active, 3H] operand
-    if (!do_a) {
-    } else if (h2) {
+    if (p.h2) {
+        d = desc_h2(b.PK_DLGT, b.PK_OUTDT, g->g_w_logit, 3 * H, V1, 3 * H, SNc);
+        d.split_k = 1;                         // one k slice per tile: a plain overwrite, no read of the (zeroed or stale) 30 MB buffer
+    } else {
+        // (compact: SNc rows of d logits against the gathered OUTD rows; the transposes zero-pad the contraction to its padded length)
+        const int kp = (SNc + 3) / 4 * 4;
+        RC(transpose(b.DLG, b.ldg, b.DLGT, b.snp, SNc, V1, kp, st));
+        RC(transpose(p.outd_rows, 3 * H, b.OUTDT, b.snp, SNc, 3 * H, kp, st));
+        d = desc_nt(b.DLGT, b.snp, b.OUTDT, b.snp, g->g_w_logit, 3 * H, V1, 3 * H, kp);
+        d.beta = p.zb; d.split_k = -1; d.algo = ECHR_GEMM_BF16X3;
+    }
+    RC(gemm(d, st));
+    return bias_too ? colsum(b.DLG, b.ldg, SNc, V1, g->g_b_logit, p.z, st) : 0;
+}
+// 2. late fusion gradients.  Both late-fusion products run as NT problems on k-contiguous (transposed) operands so that they qualify for the
+// bf16-split matrix-core path: d W_logit = DLG^T . OUTD  and  d OUTD = DLG . W_logit.
+static int bwd_late_fusion(const BwdPlan& p, hipStream_t st) {
+    const echr_dec_args* a = p.a; const DecWs& w = p.w; const DecWsBwd& b = p.b; const int H = p.H, V1 = p.V1, SN = p.SN, SNc = p.SNc;
+    echr_gemm_desc d;
+    if (p.h2) {
         // d W_logit = DLG^T . OUTD and d OUTD = DLG . W_logit on h2-packed operands; the four packs (two of them transposing) are one launch
         // with an asynchronous tail (phase 0) the logit-layer gradients, which nothing in the backward pass reads, are formed on the tail
         // stream beside the launch-bound rest of the backward instead of in front of the reverse recurrence
-        const bool defer_wl = g->phase == 0 && g->async_tail != 0 && tail().ok;
         // (a->train: W_logit^T was packed with the forward operands; otherwise here)
         const float* pk_wlt = a->train ? w.PK_WLT : b.PK_WLT;
-        if (defer_wl) {
+        if (p.defer_wl) {
             H2PackJob pj[2] = {pack_rows(b.DLG, b.ldg, SNc, V1, b.PK_DLG), pack_cols(a->w_logit, 3 * H, 3 * H, V1, b.PK_WLT)};
             RC(h2_pack_multi(pj, a->train ? 1 : 2, st));
         } else {
-            ECHR_REQUIRE(!compact, "decoder_bwd: active_rows needs the deferred logit-layer gradients");
             H2PackJob pj[4] = {pack_cols(b.DLG, b.ldg, V1, SN, b.PK_DLGT), pack_cols(w.OUTD, 3 * H, 3 * H, SN, b.PK_OUTDT),
                                pack_rows(b.DLG, b.ldg, SN, V1, b.PK_DLG), pack_cols(a->w_logit, 3 * H, 3 * H, V1, b.PK_WLT)};
             RC(h2_pack_multi(pj, a->train ? 3 : 4, st));
-            RC(logit_grads(a, g, w, b, z, st));
+            RC(bwd_logit_grads(p, st));
         }
         d = desc_h2(b.PK_DLG, pk_wlt, b.DOUT, 3 * H, SNc, 3 * H, V1);
-        d.beta = 1.f;                          // DOUT was zeroed above: the k slices add atomically, no fill launch
-        if (compact) { d.row_index = act; d.row_index_max = SN - 1; }          // compacted row i is row act[i] of d OUTD (the others stay zero)
-        RC(gemm(d, st));
     } else {
-    // (native fp32 / bf16x3 products.  With an asynchronous tail the logit-layer gradients -- which nothing in the backward pass reads -- are formed
-    // on the tail stream behind the reverse recurrence, as on the h2 path, instead of in front of it: 0.2 ms off the caller's stream)
-    if (!native_defer_wl) {
-    RC(transpose(b.DLG, b.ldg, b.DLGT, b.snp, SN, V1, (int)b.snp, st));
-    RC(transpose(w.OUTD, 3 * H, b.OUTDT, b.snp, SN, 3 * H, (int)b.snp, st));
-    d = desc_nt(b.DLGT, b.snp, b.OUTDT, b.snp, g->g_w_logit, 3 * H, V1, 3 * H, (int)b.snp);
-    d.beta = zb; d.split_k = -1; d.algo = ECHR_GEMM_BF16X3;
-    RC(gemm(d, st));
-    RC(colsum(b.DLG, b.ldg, SN, V1, g->g_b_logit, z, st));
+        // (native fp32 / bf16x3 products.  With an asynchronous tail the logit-layer gradients -- which nothing in the backward pass reads -- are formed
+        // on the tail stream behind the reverse recurrence, as on the h2 path, instead of in front of it: 0.2 ms off the caller's stream)
+        if (!p.defer_wl) RC(bwd_logit_grads(p, st));          // (not compact then: all SN rows, the contraction padded to b.snp)
+        RC(transpose(a->w_logit, 3 * H, b.WLT, b.ldg, V1, 3 * H, (int)b.ldg, st));
+        d = desc_nt(b.DLG, b.ldg, b.WLT, b.ldg, b.DOUT, 3 * H, SNc, 3 * H, (int)b.ldg);
+        d.split_k = -1; d.algo = p.compact ? ECHR_GEMM_F32 : ECHR_GEMM_BF16X3;
     }
-    RC(transpose(a->w_logit, 3 * H, b.WLT, b.ldg, V1, 3 * H, (int)b.ldg, st));
-    d = desc_nt(b.DLG, b.ldg, b.WLT, b.ldg, b.DOUT, 3 * H, SNc, 3 * H, (int)b.ldg);
-    d.split_k = -1; d.algo = ECHR_GEMM_BF16X3; d.beta = 1.f;
-    if (compact) { d.row_index = act; d.row_index_max = SN - 1; d.algo = ECHR_GEMM_F32; }          // compacted row i adds into row act[i] of d OUTD
-    RC(gemm(d, st));
+    d.beta = 1.f;                          // DOUT was zeroed with the scratch: the k slices add atomically, no fill launch
+    if (p.compact) { d.row_index = p.act; d.row_index_max = SN - 1; }          // compacted row i adds into row act[i] of d OUTD (the others stay zero)
+    return gemm(d, st);
+}
+// the logit-layer gradients that bwd_late_fusion deferred, on the tail stream `st`
+static int bwd_logit_grads_on_tail(const BwdPlan& p, hipStream_t st, BwdSched& s) {
+    const DecWsBwd& b = p.b; const int H = p.H, V1 = p.V1, SNc = p.SNc;
+    if (p.h2) {
+        H2PackJob pj[2] = {pack_cols(b.DLG, b.ldg, V1, SNc, b.PK_DLGT), pack_cols(p.w.OUTD, 3 * H, 3 * H, SNc, b.PK_OUTDT)};
+        pj[1].gather = p.act;          // (compact: the contraction runs over the active rows of OUTD)
+        RC(h2_pack_multi(pj, 2, st));
     }
-    // 3. reverse recurrence
+    // h2 + z: d b_logit rides in the multi-problem column-sum launch behind att_post -- unless the logit layer's range is handed over to a
+    // data-parallel collective right here (then the bias sum is formed with the product, so the whole range is final)
+    s.bias_owed = p.h2 && p.z && !handover().want;
+    RC(bwd_logit_grads(p, st, !s.bias_owed));
+    return handover_mark(ECHR_HANDOVER_LOGIT, st);
+}
+// one reverse timestep
+static int bwd_step(const BwdPlan& p, int t, hipStream_t q) {
+    const echr_dec_args* a = p.a; const echr_dec_grads* g = p.g; const DecWs& w = p.w; const DecWsBwd& b = p.b; const int N = p.N, H = p.H, Ha = p.Ha, D = p.D;
     const long hs = (long)N * H, as = (long)N * D;
-    // weight gradients that are sums over the S timesteps: W_hh_k, W_ih_k[:, :E], W_ih1[:, E:], W_h2a.
-    // beta = 0 writes, beta = 1 accumulates.  HS[t] holds h(t-1), so rows t*N.. pair with DG[t].
-    auto wgrad = [&](float beta, hipStream_t q) -> int {
-        echr_gemm_desc e, ghh[3], gih[3];
-        if (h2) {
-            // all S*N rows at once: DG_k^T, h(t-1)_k^T, XT^T, ATT^T, DQ^T packed (transposing) by one launch; DG_k^T is shared by the
-            // W_hh, W_ih[:, :E] and W_ih1[:, E:] gradients, h1^T by the W_hh1 and W_h2a gradients
-            H2PackJob pj[9];
-            for (int k = 0; k < 3; ++k) {
-                pj[k] = pack_cols(b.DG[k], 4 * H, 4 * H, SN, b.PK_DGT[k]);
-                pj[3 + k] = pack_cols(w.HS + k * H, 3 * H, H, SN, b.PK_HT[k]);
-            }
-            pj[6] = pack_cols(w.XT, E, E, SN, b.PK_XTT);
-            pj[7] = pack_cols(w.ATT, D, D, SN, b.PK_ATTT);
-            pj[8] = pack_cols(b.DQ, Ha, Ha, SN, b.PK_DQT);
-            if (crec)          // rows behind a caption's end carry d G = d q = 0 exactly: the contraction runs over the active rows only
-                for (int i = 0; i < 9; ++i) { pj[i].K = SNr; pj[i].gather = actr; }
-            RC(h2_pack_multi(pj, 9, q));
-            // the seven products that contract d G_k^T over the S*N rows (W_hh x3, W_ih[:, :E] x3, W_ih1[:, E:]) share M = 4H and K, the W_h2a
-            // gradient shares K: ONE grouped launch of 8 x 64 tile slots fills the chip in a single round (they were five launches)
-            echr_gemm_desc g7[8];
-            for (int k = 0; k < 3; ++k) {
-                g7[k] = desc_h2(b.PK_DGT[k], b.PK_HT[k], g->g_w_hh[k], H, 4 * H, H, SNr);
-                g7[3 + k] = desc_h2(b.PK_DGT[k], b.PK_XTT, g->g_w_ih[k], cin[k], 4 * H, E, SNr);
-            }
-            g7[6] = desc_h2(b.PK_DGT[1], b.PK_ATTT, g->g_w_ih[1] + E, cin[1], 4 * H, D, SNr);
-            g7[7] = desc_h2(b.PK_DQT, b.PK_HT[1], g->g_w_h2a, H, Ha, H, SNr);      // d q^T . h1 (M = Ha): same K, rides along
-            for (int i = 0; i < 8; ++i) g7[i].beta = beta;
-            return gemm_grouped(g7, 8, q);
-        }
-        for (int k = 0; k < 3; ++k) {
-            ghh[k] = desc_tn(b.DG[k], 4 * H, w.HS + k * H, 3 * H, g->g_w_hh[k], H, 4 * H, H, SN);
-            ghh[k].beta = beta; ghh[k].split_k = -1;
-            gih[k] = desc_tn(b.DG[k], 4 * H, w.XT, E, g->g_w_ih[k], cin[k], 4 * H, E, SN);
-            gih[k].beta = beta; gih[k].split_k = -1;
-        }
-        RC(gemm_grouped(ghh, 3, q));        // three W_hh gradients in one launch
-        RC(gemm_grouped(gih, 3, q));        // three W_ih[:, :E] gradients in one launch
-        e = desc_tn(b.DG[1], 4 * H, w.ATT, D, g->g_w_ih[1] + E, cin[1], 4 * H, D, SN);
-        e.beta = beta; e.split_k = -1;
-        RC(gemm(e, q));
-        e = desc_tn(b.DQ, Ha, w.HS + H, 3 * H, g->g_w_h2a, H, Ha, H, SN);
-        e.beta = beta; e.split_k = -1;
-        return gemm(e, q);
-    };
-    // one reverse timestep
-    auto bwd_step = [&](int t, hipStream_t q) -> int {
-        LstmBwdPtrs P;
-        for (int k = 0; k < 3; ++k) {
-            P.gates[k] = w.GATES[k] + (long)t * N * 4 * H;
-            P.c_prev[k] = w.CS[k] + (long)t * N * H;
-            P.c_new[k] = w.CS[k] + (long)(t + 1) * N * H;
-            P.dgates[k] = b.DG[k] + (long)t * N * 4 * H;
-            P.dh_slab[k] = nullptr;
-            P.dh_acc[k] = b.DHACC[k];                           // d h(t), added atomically while processing step t+1 (zero at t = S-1)
-            P.nslab[k] = 0;
-            P.kmap[k] = k;
-        }
-        P.slab_stride = hs;
-        hipLaunchKernelGGL(lstm_pointwise_bwd_kernel, dim3((N * H + 255) / 256, 3), dim3(256), 0, q, P,
-                           b.DOUT + (long)t * N * 3 * H, b.DC, N, H, t, dh, dout);
-        RC(check_launch("lstm_pointwise_bwd"));
-        // d h(t-1) = dG_k(t) . W_hh_k  (skipped at t = 0 when h(-1) is the constant zero state; with echr_dec_args.h0 it is d h0);  d ATT = dG_1(t) . W_ih1[:,E:]
-        const bool rec0 = t > 0 || (a->h0 && g->g_h0);
-        RecArgs ra;
-        ra.M = N; ra.njobs = 0;
-        float* datt = b.DASL + (long)t * N * D;     // re-read by every attention workgroup of an event: one atomically summed buffer
-        ra.job[ra.njobs++] = mkjob(P.dgates[1], 4 * H, 4 * H, b.WT_ATT, 4 * H, D, datt, as, D, 1);
-        if (rec0)
-            for (int k = 0; k < 3; ++k) ra.job[ra.njobs++] = mkjob(P.dgates[k], 4 * H, 4 * H, b.WT_HH[k], 4 * H, H, b.DHACC[k], hs, H, 1);
+    LstmBwdPtrs P;
+    for (int k = 0; k < 3; ++k) {
+        P.gates[k] = w.GATES[k] + (long)t * N * 4 * H;
+        P.c_prev[k] = w.CS[k] + (long)t * N * H;
+        P.c_new[k] = w.CS[k] + (long)(t + 1) * N * H;
+        P.dgates[k] = b.DG[k] + (long)t * N * 4 * H;
+        P.dh_acc[k] = b.DHACC[k];                           // d h(t), added atomically while processing step t+1 (zero at t = S-1)
+        P.dh_slab[k] = nullptr; P.nslab[k] = 0; P.kmap[k] = k;
+    }
+    P.slab_stride = hs;
+    hipLaunchKernelGGL(lstm_pointwise_bwd_kernel, dim3((N * H + 255) / 256, 3), dim3(256), 0, q, P,
+                       b.DOUT + (long)t * N * 3 * H, b.DC, N, H, t, p.dh, p.dout);
+    RC(check_launch("lstm_pointwise_bwd"));
+    // d h(t-1) = dG_k(t) . W_hh_k  (skipped at t = 0 when h(-1) is the constant zero state; with echr_dec_args.h0 it is d h0);  d ATT = dG_1(t) . W_ih1[:,E:]
+    const bool rec0 = t > 0 || (a->h0 && g->g_h0);
+    RecArgs ra; ra.M = N; ra.njobs = 0;
+    float* datt = b.DASL + (long)t * N * D;     // re-read by every attention workgroup of an event: one atomically summed buffer
+    ra.job[ra.njobs++] = mkjob(P.dgates[1], 4 * H, 4 * H, b.WT_ATT, 4 * H, D, datt, as, D, 1);
+    if (rec0)
+        for (int k = 0; k < 3; ++k) ra.job[ra.njobs++] = mkjob(P.dgates[k], 4 * H, 4 * H, b.WT_HH[k], 4 * H, H, b.DHACC[k], hs, H, 1);
+    RC(rec_gemm(ra, q));
+    // attention backward (needed at every t: feeds d P_all, d alpha, d W_h)
+    float* dq = b.DQ + (long)t * N * Ha;
+    {
+        ProfScope prof(PROF_ATT_BWD, 4.0 * N * p.A * (Ha + D), 4.0 * ((double)N * p.A * (Ha + D + 2) + (double)N * (2 * Ha + 2 * D)), q);
+        const AttDims ad{N, p.A, Ha, D};
+        RC(launch_att_bwd(ad, w.PALL, a->c3d, w.QS + (long)t * N * Ha, a->w_alpha, w.WT + (long)t * N * p.A, w.ATT + (long)t * N * D,
+                          datt, 1, as, a->ev_start, a->ev_len, b.DSC + (long)t * N * p.A, dq, q));
+    }
+    if (rec0) {   // d h1(t-1) += dq . W_h : extra slabs behind stream 1's W_hh slabs
+        ra.njobs = 1;
+        ra.job[0] = mkjob(dq, Ha, Ha, b.WT_H2A, Ha, H, b.DHACC[1], hs, H, 1);
         RC(rec_gemm(ra, q));
-        // attention backward (needed at every t: feeds d P_all, d alpha, d W_h)
-        float* dq = b.DQ + (long)t * N * Ha;
-        {
-        ProfScope prof(PROF_ATT_BWD, 4.0 * N * A * (Ha + D), 4.0 * ((double)N * A * (Ha + D + 2) + (double)N * (2 * Ha + 2 * D)), q);
-        const AttDims ad{N, A, Ha, D};
-        RC(launch_att_bwd(ad, w.PALL, a->c3d, w.QS + (long)t * N * Ha, a->w_alpha, w.WT + (long)t * N * A, w.ATT + (long)t * N * D,
-                          datt, 1, as, a->ev_start, a->ev_len, b.DSC + (long)t * N * A, dq, q));
-        }
-        if (rec0) {   // d h1(t-1) += dq . W_h : extra slabs behind stream 1's W_hh slabs
-            ra.njobs = 1;
-            ra.job[0] = mkjob(dq, Ha, Ha, b.WT_H2A, Ha, H, b.DHACC[1], hs, H, 1);
-            RC(rec_gemm(ra, q));
-        }
-        return 0;
-    };
-    if (!do_rec_main) {
-    } else if (bwd_persist) {
+    }
+    return 0;
+}
+// 3. reverse recurrence
+static int bwd_recurrence(const BwdPlan& p, hipStream_t st) {
+    const echr_dec_args* a = p.a; const echr_dec_grads* g = p.g; const DecWs& w = p.w; const DecWsBwd& b = p.b;
+    if (p.bwd_persist) {
         // the whole reverse recurrence in two concurrent persistent launches (csrc/persist.hip)
         PersistBwdBufs pb;
         for (int k = 0; k < 3; ++k) { pb.GATES[k] = w.GATES[k]; pb.CS[k] = w.CS[k]; pb.DG[k] = b.DG[k]; }
         pb.QS = w.QS; pb.WT = w.WT; pb.ATT = w.ATT; pb.PALL = w.PALL; pb.DOUT = b.DOUT; pb.DQ = b.DQ; pb.DSC = b.DSC; pb.xws = b.XWSB;
-        pb.prezeroed = do_a;                    // stage 1 of this call zeroed the exchange workspace with the backward scratch
-        RC(persist_bwd(a, pb, dh, dout, st));
+        pb.prezeroed = (p.stages & BWD_HEAD) != 0;          // stage 1 of this call zeroed the exchange workspace with the backward scratch
+        RC(persist_bwd(a, pb, p.dh, p.dout, st));
     } else {
-        for (int t = S - 1; t >= 0; --t) RC(bwd_step(t, st));
+        for (int t = p.S - 1; t >= 0; --t) RC(bwd_step(p, t, st));
     }
-    if (do_rec_main && a->h0 && g->g_h0) {          // d loss / d (initial state): what step 0 left in the d h accumulators + the carried d c
-        const long n = (long)N * 3 * H;
-        hipLaunchKernelGGL(init_state_grad_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, b.DHACC[0], b.DHACC[1], b.DHACC[2], b.DC, g->g_h0, N, H);
+    if (a->h0 && g->g_h0) {          // d loss / d (initial state): what step 0 left in the d h accumulators + the carried d c
+        const long n = (long)p.N * 3 * p.H;
+        hipLaunchKernelGGL(init_state_grad_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, b.DHACC[0], b.DHACC[1], b.DHACC[2], b.DC, g->g_h0, p.N, p.H);
         RC(check_launch("init_state_grad"));
     }
-    // 4. batched parameter gradients, part A: everything of the three LSTM layers (core.layer0..2) -- final after this block, so a
-    //    data-parallel caller can start reducing them (phase 3) while part B runs
-    // async_tail = 2: only d event (what the caller's next backward kernels, the event encoder's, wait for) is formed on the caller's stream,
-    // first; the rest of part A -- nine transposing packs, the grouped weight-gradient product, bias sums, the context halves of W_ih: ~0.13 ms
-    // -- moves to the prepare stream (idle during a backward pass) and is joined by echr_stream_join like the tail
-    bool dxt_done = false;
-    //    token embedding: dXT = sum_k DG_k . W_ih_k[:, :E], scatter-added into the (caller-zeroed) table gradient.  Reads what the recurrence
-    //    left (DG) and parameters only, so the chain rides on the prepare stream behind the LSTM-layer stage, which leaves the three streams of
-    //    the backward tail ending together
-    auto dxt_chain = [&](hipStream_t q) -> int {
-        dxt_done = true;
-        echr_gemm_desc gx[3];
-        if (h2) {
-            H2PackJob pj[6];
-            for (int k = 0; k < 3; ++k) {
-                pj[k] = pack_rows(b.DG[k], 4 * H, SNr, 4 * H, b.PK_DG[k]);
-                pj[k].gather = actr;          // (compact: d XT is formed for the active rows only, row i of it belongs to position act[i])
-                pj[3 + k] = pack_cols(a->w_ih[k], cin[k], E, 4 * H, b.PK_WIHT[k]);
-            }
-            RC(h2_pack_multi(pj, 6, q));
-        }
-        // dXT is materialised, not added by the products' epilogues straight into the table gradient row of its token (echr_gemm_desc.row_index):
-        // measured on one box, alternating runs, 1.74 ms per iteration against 1.94 -- every k-slice of every product would send its atomics to the
-        // table, and the 64 <bos> rows of a batch (plus frequent words) serialise on the same addresses; the dense d XT buffer takes the k-slice
-        // atomics without contention and the scatter pass meets each duplicate once (20 us, `tools/skip_bounds.py`)
-        for (int k = 0; k < 3; ++k) {
-            gx[k] = h2 ? desc_h2(b.PK_DG[k], b.PK_WIHT[k], b.DXT, E, SNr, E, 4 * H) : desc_nn(b.DG[k], 4 * H, a->w_ih[k], cin[k], b.DXT, E, SN, E, 4 * H);
-            gx[k].split_k = -1; gx[k].beta = 1.f;                // shared, pre-zeroed output: everything adds atomically
-        }
-        RC(gemm_grouped(gx, 3, q));
-        RC(embed_scatter_add(b.DXT, a->tokens, g->g_embed, h2 ? SNr : SN, E, V1, q, h2 ? actr : nullptr));
-        return 0;
-    };
-    // scene half of W_ih2 and d video.  One video: DGCOL[2] (column sum of d gates2) x the scene vector.  Multi-video batch: what stream 0's
-    // per-event context already does -- d gates2 summed over time per event (DGSUM[2]; have_sum: the caller has formed it), a segmented row
-    // sum by video in a fixed order (DGSEG [V, 4H]), then d W_ih2[:, E:] = DGSEG^T . video (K = V) and d video = DGSEG . W_ih2[:, E:], each
-    // one fixed-order k loop per tile
-    auto scene_grads = [&](hipStream_t q, bool have_sum) -> int {
-        const echr_batch_ext* bx = batch_ext();
-        if (!bx) {
-            RC(rank1_update(b.DGCOL[2], a->video, g->g_w_ih[2] + E, cin[2], 4 * H, a->Dv, false, q));          // K = 1: no GEMM launch
-            if (g->g_video) RC(vec_mat(b.DGCOL[2], a->w_ih[2] + E, cin[2], g->g_video, 4 * H, a->Dv, q));
-            return 0;
-        }
-        const int V = bx->n_videos;
-        if (!have_sum) RC(sum_over_time(b.DG[2], 4 * H, S, N, 4 * H, b.DGSUM[2], 4 * H, q));
-        float* dgseg = carve_batch(N, V, H, bx->ws).DGSEG;
-        RC(seg_rowsum(b.DGSUM[2], bx->vid, N, V, 4 * H, 4 * H, dgseg, q));
-        echr_gemm_desc ds = desc_tn(dgseg, 4 * H, bx->video, a->Dv, g->g_w_ih[2] + E, cin[2], 4 * H, a->Dv, V);
-        ds.split_k = 1;
-        RC(gemm(ds, q));
-        if (bx->g_video) {
-            ds = desc_nn(dgseg, 4 * H, a->w_ih[2] + E, cin[2], bx->g_video, a->Dv, V, a->Dv, 4 * H);
-            ds.split_k = 1;
-            RC(gemm(ds, q));
-        }
-        return 0;
-    };
-    hipStream_t sa2 = nullptr;
-    auto part_a = [&]() -> int {
-    if (!do_rec) return 0;
-    if (g->phase == 0 && g->async_tail == 2 && z && (h2 || part == 0) && tail().ok) {
-        // Both helper streams fork RIGHT BEHIND the reverse recurrence, off ONE recorded event, not behind d event with one record each: the
-        // two records used to sit between the d event product and everything that follows on all three streams (~15 us of an idle chip).
-        // The prepare stream then forms its own copy of the per-event gate-gradient sums (6 us) instead of waiting for this stream's
-        const bool ff = part == 0;
-        if (ff) {
-            sa2 = aux2_fork(st);
-            if (sa2) fork_event(prep().fork);          // part B's fork waits for the same event
-        }
-        if (part != 2) {
-        RC(sum_over_time(b.DG[0], 4 * H, S, N, 4 * H, b.DGSUM[0], 4 * H, st));
-        d = desc_nn(b.DGSUM[0], 4 * H, a->w_ih[0] + E, cin[0], g->g_event, a->De, N, a->De, 4 * H);
-        d.split_k = -1; d.beta = 1.f;
-        RC(gemm(d, st));
-        }
-        if (part == 1) return 0;
-        if (!ff) sa2 = aux2_fork(st);
-        const float* dgsum0 = b.DGSUM[0];
-        if (sa2 && ff) { RC(sum_over_time(b.DG[0], 4 * H, S, N, 4 * H, b.DGSUM[1], 4 * H, sa2)); dgsum0 = b.DGSUM[1]; }
-        if (sa2) {
-            RC(wgrad(1.f, sa2));
-            const ColsumJob cj[4] = {{b.DQ, Ha, SN, Ha, g->g_b_h2a, nullptr, nullptr},
-                                     {b.DG[0], 4 * H, SN, 4 * H, g->g_b_ih[0], g->g_b_hh[0], nullptr},
-                                     {b.DG[1], 4 * H, SN, 4 * H, g->g_b_ih[1], g->g_b_hh[1], nullptr},
-                                     {b.DG[2], 4 * H, SN, 4 * H, g->g_b_ih[2], g->g_b_hh[2], b.DGCOL[2]}};
-            RC(colsum_multi(cj, 4, sa2));
-            d = desc_tn(dgsum0, 4 * H, a->event, a->De, g->g_w_ih[0] + E, cin[0], 4 * H, a->De, N);
-            d.beta = zb; d.split_k = -1;
-            RC(gemm(d, sa2));
-            RC(scene_grads(sa2, false));
-            RC(handover_mark(ECHR_HANDOVER_LSTM, sa2));          // every gradient of core.layer0..2 is final here
-            if (do_pb && !dxt_done) RC(dxt_chain(sa2));
-            if (hipEventRecord(tail().done3, sa2) != hipSuccess) { set_error("decoder_bwd: event record failed"); return -5; }
-            tail().pending3 = true;
-            return 0;
-        }
-        // (no second helper stream: the rest follows on the caller's stream; d event is already there)
-        RC(wgrad(1.f, st));
-        const ColsumJob cj[4] = {{b.DQ, Ha, SN, Ha, g->g_b_h2a, nullptr, nullptr},
-                                 {b.DG[0], 4 * H, SN, 4 * H, g->g_b_ih[0], g->g_b_hh[0], nullptr},
-                                 {b.DG[1], 4 * H, SN, 4 * H, g->g_b_ih[1], g->g_b_hh[1], nullptr},
-                                 {b.DG[2], 4 * H, SN, 4 * H, g->g_b_ih[2], g->g_b_hh[2], b.DGCOL[2]}};
-        RC(colsum_multi(cj, 4, st));
-        d = desc_tn(b.DGSUM[0], 4 * H, a->event, a->De, g->g_w_ih[0] + E, cin[0], 4 * H, a->De, N);
-        d.beta = zb; d.split_k = -1;
-        RC(gemm(d, st));
-        RC(scene_grads(st, false));
-        return 0;
-    }
-    RC(wgrad(zb, st));          // W_hh_k, W_ih_k[:, :E], W_ih1[:, E:], W_h2a: sums over timesteps
-    //    bias gradients b_h2a and per stream b_ih = b_hh = column sums of DG_k over all S*N rows (stream 2's also as the plain vector
-    //    DGCOL that the scene projection below consumes).  One launch when the gradient buffers accumulate.
-    if (z) {
-        const ColsumJob cj[4] = {{b.DQ, Ha, SN, Ha, g->g_b_h2a, nullptr, nullptr},
-                                 {b.DG[0], 4 * H, SN, 4 * H, g->g_b_ih[0], g->g_b_hh[0], nullptr},
-                                 {b.DG[1], 4 * H, SN, 4 * H, g->g_b_ih[1], g->g_b_hh[1], nullptr},
-                                 {b.DG[2], 4 * H, SN, 4 * H, g->g_b_ih[2], g->g_b_hh[2], b.DGCOL[2]}};
-        RC(colsum_multi(cj, 4, st));
-        RC(sum_over_time(b.DG[0], 4 * H, S, N, 4 * H, b.DGSUM[0], 4 * H, st));     // per-event sums feed the event-context products
-    } else {
-        RC(colsum(b.DQ, Ha, SN, Ha, g->g_b_h2a, z, st));
-        for (int k = 0; k < 3; ++k) {
-            RC(sum_over_time(b.DG[k], 4 * H, S, N, 4 * H, b.DGSUM[k], 4 * H, st));
-            RC(colsum2(b.DGSUM[k], 4 * H, N, 4 * H, g->g_b_ih[k], g->g_b_hh[k], z, st));       // b_ih and b_hh share their gradient
-            if (k == 2) RC(colsum(b.DGSUM[k], 4 * H, N, 4 * H, b.DGCOL[k], false, st));          // also needed as a vector below
-        }
-    }
-    //    context halves of W_ih: event (stream 0), video (stream 2)
-    d = desc_tn(b.DGSUM[0], 4 * H, a->event, a->De, g->g_w_ih[0] + E, cin[0], 4 * H, a->De, N);
-    d.beta = zb; d.split_k = -1;
-    RC(gemm(d, st));
-    d = desc_nn(b.DGSUM[0], 4 * H, a->w_ih[0] + E, cin[0], g->g_event, a->De, N, a->De, 4 * H);
-    d.split_k = -1; d.beta = 1.f;                                // zeroed with the backward scratch above
-    RC(gemm(d, st));
-    RC(scene_grads(st, !z));          // (the non-accumulating form has formed every stream's per-event sums above)
     return 0;
-    };
-    // phase 0 + async_tail: nothing downstream in the backward pass needs part B's outputs -> second stream, joined by the caller.  Its three
-    // chains (logit-layer gradients, attention parameters, token embedding) read only what the recurrence left (DLG, OUTD, DG, DQ, DSC); the
-    // tail forks behind part A, not ahead of it: measured on one box, alternating runs, 1.726 vs 1.731 ms per iteration -- this phase is bound
-    // by its chip-filling GEMMs, packs and att_post (~0.4 ms), not by stream order
-    const bool async_tail = g->phase == 0 && g->async_tail != 0 && tail().ok && do_pb;
-    hipStream_t sm = st;              // the caller's stream
-    bool bias_pending = false;
-    auto part_b = [&]() -> int {
-    if (!do_pb) return 0;
-    if (async_tail) {
-        st = tail().s;
-        if (hipEvent_t fe = fork_event_slot()) {          // (forked with the prepare stream, right behind the reverse recurrence)
-            if (hipStreamWaitEvent(st, fe, 0) != hipSuccess) { set_error("decoder_bwd: stream fork failed"); return -5; }
-        } else RC(hop(sm, tail().fork, st));
-        if (h2) {          // the logit-layer gradients deferred above
-            H2PackJob pj[2] = {pack_cols(b.DLG, b.ldg, V1, SNc, b.PK_DLGT), pack_cols(w.OUTD, 3 * H, 3 * H, SNc, b.PK_OUTDT)};
-            pj[1].gather = act;          // (compact: the contraction runs over the active rows of OUTD)
-            RC(h2_pack_multi(pj, 2, st));
-            // z: d b_logit rides in the multi-problem column-sum launch behind att_post -- unless the logit layer's range is handed over to a
-            // data-parallel collective right here (then the bias sum is formed with the product, so the whole range is final)
-            const bool ho = handover().want;
-            RC(logit_grads(a, g, w, b, z, st, !z || ho));
-            bias_pending = z && !ho;
-            RC(handover_mark(ECHR_HANDOVER_LOGIT, st));
-        } else if (native_defer_wl) {
-            // (compact: SNc rows of d logits against the gathered OUTD rows; the transposes zero-pad the contraction to its padded length)
-            const int kp = (SNc + 3) / 4 * 4;
-            RC(transpose(b.DLG, b.ldg, b.DLGT, b.snp, SNc, V1, kp, st));
-            RC(transpose(outd_rows, 3 * H, b.OUTDT, b.snp, SNc, 3 * H, kp, st));
-            d = desc_nt(b.DLGT, b.snp, b.OUTDT, b.snp, g->g_w_logit, 3 * H, V1, 3 * H, kp);
-            d.beta = zb; d.split_k = -1; d.algo = ECHR_GEMM_BF16X3;
-            RC(gemm(d, st));
-            RC(colsum(b.DLG, b.ldg, SNc, V1, g->g_b_logit, z, st));
-            RC(handover_mark(ECHR_HANDOVER_LOGIT, st));
+}
+// weight gradients that are sums over the S timesteps: W_hh_k, W_ih_k[:, :E], W_ih1[:, E:], W_h2a.
+// beta = 0 writes, beta = 1 accumulates (p.zb).  HS[t] holds h(t-1), so rows t*N.. pair with DG[t].
+static int bwd_weight_grads(const BwdPlan& p, hipStream_t q) {
+    const echr_dec_grads* g = p.g; const DecWs& w = p.w; const DecWsBwd& b = p.b; const int H = p.H, E = p.E, Ha = p.Ha, D = p.D, SN = p.SN, SNr = p.SNr;
+    if (p.h2) {
+        // all S*N rows at once: DG_k^T, h(t-1)_k^T, XT^T, ATT^T, DQ^T packed (transposing) by one launch; DG_k^T is shared by the
+        // W_hh, W_ih[:, :E] and W_ih1[:, E:] gradients, h1^T by the W_hh1 and W_h2a gradients
+        H2PackJob pj[9];
+        for (int k = 0; k < 3; ++k) {
+            pj[k] = pack_cols(b.DG[k], 4 * H, 4 * H, SN, b.PK_DGT[k]);
+            pj[3 + k] = pack_cols(w.HS + k * H, 3 * H, H, SN, b.PK_HT[k]);
         }
+        pj[6] = pack_cols(w.XT, E, E, SN, b.PK_XTT);
+        pj[7] = pack_cols(w.ATT, D, D, SN, b.PK_ATTT);
+        pj[8] = pack_cols(b.DQ, Ha, Ha, SN, b.PK_DQT);
+        if (p.crec)          // rows behind a caption's end carry d G = d q = 0 exactly: the contraction runs over the active rows only
+            for (int i = 0; i < 9; ++i) { pj[i].K = SNr; pj[i].gather = p.actr; }
+        RC(h2_pack_multi(pj, 9, q));
+        // the seven products that contract d G_k^T over the S*N rows (W_hh x3, W_ih[:, :E] x3, W_ih1[:, E:]) share M = 4H and K, the W_h2a
+        // gradient shares K: ONE grouped launch of 8 x 64 tile slots fills the chip in a single round (they were five launches)
+        echr_gemm_desc g7[8];
+        for (int k = 0; k < 3; ++k) {
+            g7[k] = desc_h2(b.PK_DGT[k], b.PK_HT[k], g->g_w_hh[k], H, 4 * H, H, SNr);
+            g7[3 + k] = desc_h2(b.PK_DGT[k], b.PK_XTT, g->g_w_ih[k], p.cin[k], 4 * H, E, SNr);
+        }
+        g7[6] = desc_h2(b.PK_DGT[1], b.PK_ATTT, g->g_w_ih[1] + E, p.cin[1], 4 * H, D, SNr);
+        g7[7] = desc_h2(b.PK_DQT, b.PK_HT[1], g->g_w_h2a, H, Ha, H, SNr);      // d q^T . h1 (M = Ha): same K, rides along
+        for (int i = 0; i < 8; ++i) g7[i].beta = p.zb;
+        return gemm_grouped(g7, 8, q);
     }
-    // 5. part B: attention parameters (d P_all / d alpha over all timesteps, then ctx2att) and the token embedding
-    {
-    ProfScope prof(PROF_ATT_POST, 6.0 * N * A * Ha * S, 4.0 * ((double)N * A * Ha * 2 + (double)S * N * (Ha + A)), st);
-    const AttDims ad{N, A, Ha, D};
-    if (det_mode()) {
-        // fixed-order mode: one d alpha / d b_alpha row per workgroup and (for events that share video rows) one d P_all slab row per (event,
-        // position), folded by fixed-order launches -- no atomics
-        const long nblk = (long)N * ((A + 7) / 8);
-        float* ga = det_scratch(DET_ALPHA, (size_t)nblk * (Ha + 1));
-        if (!ga) return -12;
-        float* gb = ga + nblk * Ha;
-        RC(fill_zero(ga, nblk * (Ha + 1), st));          // workgroups behind an event's end return early: their rows stay zero
-        float* dps = nullptr;
-        if (!a->rows_disjoint) { dps = det_scratch(DET_DPALL, (size_t)N * A * Ha); if (!dps) return -12; }
-        RC(launch_att_post(ad, w.PALL, w.QS, a->w_alpha, b.DSC, a->ev_start, a->ev_len, dps ? dps : b.DPALL, ga, gb, S, dps ? 2 : 1, st, 1));
-        if (dps) {
-            hipLaunchKernelGGL(dpall_fold_kernel, dim3(a->Tv), dim3(256), 0, st, dps, a->ev_start, a->ev_len, b.DPALL, N, A, Ha);
-            RC(check_launch("dpall_fold"));
+    echr_gemm_desc e, ghh[3], gih[3];
+    for (int k = 0; k < 3; ++k) {
+        ghh[k] = desc_tn(b.DG[k], 4 * H, w.HS + k * H, 3 * H, g->g_w_hh[k], H, 4 * H, H, SN);
+        ghh[k].beta = p.zb; ghh[k].split_k = -1;
+        gih[k] = desc_tn(b.DG[k], 4 * H, w.XT, E, g->g_w_ih[k], p.cin[k], 4 * H, E, SN);
+        gih[k].beta = p.zb; gih[k].split_k = -1;
+    }
+    RC(gemm_grouped(ghh, 3, q));        // three W_hh gradients in one launch
+    RC(gemm_grouped(gih, 3, q));        // three W_ih[:, :E] gradients in one launch
+    e = desc_tn(b.DG[1], 4 * H, w.ATT, D, g->g_w_ih[1] + E, p.cin[1], 4 * H, D, SN);
+    e.beta = p.zb; e.split_k = -1;
+    RC(gemm(e, q));
+    e = desc_tn(b.DQ, Ha, w.HS + H, 3 * H, g->g_w_h2a, H, Ha, H, SN);
+    e.beta = p.zb; e.split_k = -1;
+    return gemm(e, q);
+}
+// bias gradients b_h2a and per stream b_ih = b_hh = column sums of DG_k over all S*N rows (stream 2's also as the plain vector DGCOL that the scene
+// projection consumes).  One launch when the gradient buffers accumulate; the other form goes through the per-event sums DGSUM[0..2] and leaves them
+static int bwd_bias_sums(const BwdPlan& p, hipStream_t q) {
+    const echr_dec_grads* g = p.g; const DecWsBwd& b = p.b; const int N = p.N, S = p.S, H = p.H, Ha = p.Ha, SN = p.SN;
+    if (p.z) {
+        const ColsumJob cj[4] = {{b.DQ, Ha, SN, Ha, g->g_b_h2a, nullptr, nullptr},
+                                 {b.DG[0], 4 * H, SN, 4 * H, g->g_b_ih[0], g->g_b_hh[0], nullptr},
+                                 {b.DG[1], 4 * H, SN, 4 * H, g->g_b_ih[1], g->g_b_hh[1], nullptr},
+                                 {b.DG[2], 4 * H, SN, 4 * H, g->g_b_ih[2], g->g_b_hh[2], b.DGCOL[2]}};
+        return colsum_multi(cj, 4, q);
+    }
+    RC(colsum(b.DQ, Ha, SN, Ha, g->g_b_h2a, p.z, q));
+    for (int k = 0; k < 3; ++k) {
+        RC(sum_over_time(b.DG[k], 4 * H, S, N, 4 * H, b.DGSUM[k], 4 * H, q));
+        RC(colsum2(b.DGSUM[k], 4 * H, N, 4 * H, g->g_b_ih[k], g->g_b_hh[k], p.z, q));       // b_ih and b_hh share their gradient
+        if (k == 2) RC(colsum(b.DGSUM[k], 4 * H, N, 4 * H, b.DGCOL[k], false, q));          // also needed as a vector below
+    }
+    return 0;
+}
+// event context of stream 0, from d gates0 summed over time per event (`dgsum` [N, 4H]; EV_SUMS: formed here): the context half of W_ih0,
+// d W_ih0[:, E:] = dgsum^T . event, and d event = dgsum . W_ih0[:, E:] (what the caller's next backward kernels, the event encoder's, wait for)
+static int bwd_event_grads(const BwdPlan& p, int what, float* dgsum, hipStream_t q) {
+    const echr_dec_args* a = p.a; const echr_dec_grads* g = p.g; const int N = p.N, H = p.H, E = p.E;
+    if (what & EV_SUMS) RC(sum_over_time(p.b.DG[0], 4 * H, p.S, N, 4 * H, dgsum, 4 * H, q));
+    echr_gemm_desc dw = desc_tn(dgsum, 4 * H, a->event, a->De, g->g_w_ih[0] + E, p.cin[0], 4 * H, a->De, N);
+    dw.beta = p.zb; dw.split_k = -1;
+    if (what & EV_D_WEIGHT) RC(gemm(dw, q));
+    echr_gemm_desc de = desc_nn(dgsum, 4 * H, a->w_ih[0] + E, p.cin[0], g->g_event, a->De, N, a->De, 4 * H);
+    de.split_k = -1; de.beta = 1.f;                                // zeroed with the backward scratch
+    return (what & EV_D_EVENT) ? gemm(de, q) : 0;
+}
+// scene half of W_ih2 and d video.  One video: DGCOL[2] (column sum of d gates2) x the scene vector.  Multi-video batch: what stream 0's per-event
+// context already does -- d gates2 summed over time per event (DGSUM[2]; have_sum: the caller has formed it), a segmented row sum by video in a fixed
+// order (DGSEG [V, 4H]), then d W_ih2[:, E:] = DGSEG^T . video (K = V) and d video = DGSEG . W_ih2[:, E:], each one fixed-order k loop per tile
+static int bwd_scene_grads(const BwdPlan& p, hipStream_t q, bool have_sum) {
+    const echr_dec_args* a = p.a; const echr_dec_grads* g = p.g; const DecWsBwd& b = p.b; const int N = p.N, H = p.H, E = p.E;
+    const echr_batch_ext* bx = batch_ext();
+    if (!bx) {
+        RC(rank1_update(b.DGCOL[2], a->video, g->g_w_ih[2] + E, p.cin[2], 4 * H, a->Dv, false, q));          // K = 1: no GEMM launch
+        if (g->g_video) RC(vec_mat(b.DGCOL[2], a->w_ih[2] + E, p.cin[2], g->g_video, 4 * H, a->Dv, q));
+        return 0;
+    }
+    const int V = bx->n_videos;
+    if (!have_sum) RC(sum_over_time(b.DG[2], 4 * H, p.S, N, 4 * H, b.DGSUM[2], 4 * H, q));
+    float* dgseg = carve_batch(N, V, H, bx->ws).DGSEG;
+    RC(seg_rowsum(b.DGSUM[2], bx->vid, N, V, 4 * H, 4 * H, dgseg, q));
+    echr_gemm_desc ds = desc_tn(dgseg, 4 * H, bx->video, a->Dv, g->g_w_ih[2] + E, p.cin[2], 4 * H, a->Dv, V);
+    ds.split_k = 1;
+    RC(gemm(ds, q));
+    if (!bx->g_video) return 0;
+    ds = desc_nn(dgseg, 4 * H, a->w_ih[2] + E, p.cin[2], bx->g_video, a->Dv, V, a->Dv, 4 * H);
+    ds.split_k = 1;
+    return gemm(ds, q);
+}
+// token embedding: dXT = sum_k DG_k . W_ih_k[:, :E], scatter-added into the (caller-zeroed) table gradient.  Reads what the recurrence left (DG) and
+// parameters only, so the chain rides on the prepare stream behind the LSTM-layer stage: the three streams of the backward tail end together
+static int bwd_embed_grads(const BwdPlan& p, hipStream_t q) {
+    const echr_dec_args* a = p.a; const DecWsBwd& b = p.b; const int H = p.H, E = p.E, SN = p.SN, SNr = p.SNr;
+    echr_gemm_desc gx[3];
+    if (p.h2) {
+        H2PackJob pj[6];
+        for (int k = 0; k < 3; ++k) {
+            pj[k] = pack_rows(b.DG[k], 4 * H, SNr, 4 * H, b.PK_DG[k]);
+            pj[k].gather = p.actr;          // (compact: d XT is formed for the active rows only, row i of it belongs to position act[i])
+            pj[3 + k] = pack_cols(a->w_ih[k], p.cin[k], E, 4 * H, b.PK_WIHT[k]);
         }
-        RC(colsum(ga, Ha, (int)nblk, Ha, g->g_w_alpha, z, st));
-        RC(colsum(gb, 1, (int)nblk, 1, g->g_b_alpha, z, st));
+        RC(h2_pack_multi(pj, 6, q));
+    }
+    // dXT is materialised, not added by the products' epilogues straight into the table gradient row of its token (echr_gemm_desc.row_index):
+    // measured on one box, alternating runs, 1.74 ms per iteration against 1.94 -- every k-slice of every product would send its atomics to the
+    // table, and the 64 <bos> rows of a batch (plus frequent words) serialise on the same addresses; the dense d XT buffer takes the k-slice
+    // atomics without contention and the scatter pass meets each duplicate once (20 us, `tools/skip_bounds.py`)
+    for (int k = 0; k < 3; ++k) {
+        gx[k] = p.h2 ? desc_h2(b.PK_DG[k], b.PK_WIHT[k], b.DXT, E, SNr, E, 4 * H) : desc_nn(b.DG[k], 4 * H, a->w_ih[k], p.cin[k], b.DXT, E, SN, E, 4 * H);
+        gx[k].split_k = -1; gx[k].beta = 1.f;                // shared, pre-zeroed output: everything adds atomically
+    }
+    RC(gemm_grouped(gx, 3, q));
+    return embed_scatter_add(b.DXT, a->tokens, p.g->g_embed, p.h2 ? SNr : SN, E, p.V1, q, p.h2 ? p.actr : nullptr);
+}
+// 5. attention parameters: d P_all / d alpha over all timesteps (att_post), the column sums behind it (bias_owed: with d b_logit) and ctx2att
+static int bwd_attention_params(const BwdPlan& p, bool bias_owed, hipStream_t st) {
+    const echr_dec_args* a = p.a; const echr_dec_grads* g = p.g; const DecWs& w = p.w; const DecWsBwd& b = p.b; const int N = p.N, S = p.S, Ha = p.Ha, A = p.A, D = p.D;
+    const bool z = p.z;
+    const double fl = 6.0 * N * A * Ha * S, by = 4.0 * ((double)N * A * Ha * 2 + (double)S * N * (Ha + A));
+    const AttDims ad{N, A, Ha, D};
+    if (det_mode()) {          // fixed-order mode: the profile scope spans the fixed-order column sums too
+        ProfScope prof(PROF_ATT_POST, fl, by, st);
+        float *ga, *gb; int nblk;
+        RC(att_post_fixed_order(ad, a->Tv, S, a->rows_disjoint, w.PALL, w.QS, a->w_alpha, b.DSC, a->ev_start, a->ev_len, b.DPALL, &ga, &gb, &nblk, st));
+        RC(colsum(ga, Ha, nblk, Ha, g->g_w_alpha, z, st));
+        RC(colsum(gb, 1, nblk, 1, g->g_b_alpha, z, st));
         if (z) {
             RC(colsum(b.DPALL, Ha, a->Tv, Ha, g->g_b_c2a, z, st));
-            if (bias_pending) RC(colsum(b.DLG, b.ldg, SNc, V1, g->g_b_logit, z, st));
+            if (bias_owed) RC(colsum(b.DLG, b.ldg, p.SNc, p.V1, g->g_b_logit, z, st));
         }
     } else {
-    RC(launch_att_post(ad, w.PALL, w.QS, a->w_alpha, b.DSC, a->ev_start, a->ev_len, b.DPALL, b.GAREP, b.GBREP, S, a->rows_disjoint ? 1 : 0, st));
+        { ProfScope prof(PROF_ATT_POST, fl, by, st);
+          RC(launch_att_post(ad, w.PALL, w.QS, a->w_alpha, b.DSC, a->ev_start, a->ev_len, b.DPALL, b.GAREP, b.GBREP, S, a->rows_disjoint ? 1 : 0, st)); }
+        if (z) {
+            // accumulate mode: the replicas -> d alpha, d b_alpha, the ctx2att bias gradient (column sums of d P_all) and -- when the logit-layer
+            // gradients were formed on this stream just before -- d b_logit: ONE multi-problem launch instead of four
+            ColsumJob sums[4] = {{b.GAREP, Ha, ALPHA_REP, Ha, g->g_w_alpha, nullptr, nullptr}, {b.GBREP, 1, ALPHA_REP, 1, g->g_b_alpha, nullptr, nullptr},
+                                 {b.DPALL, Ha, a->Tv, Ha, g->g_b_c2a, nullptr, nullptr}, {b.DLG, b.ldg, p.SNc, p.V1, g->g_b_logit, nullptr, nullptr}};
+            RC(colsum_multi(sums, bias_owed ? 4 : 3, st));
+        } else {
+            RC(colsum(b.GAREP, Ha, ALPHA_REP, Ha, g->g_w_alpha, z, st));        // replicas -> d alpha, d b_alpha (overwrite or accumulate like every
+            RC(colsum(b.GBREP, 1, ALPHA_REP, 1, g->g_b_alpha, z, st));          // other parameter gradient)
+        }
     }
-    }
-    if (det_mode()) {
-    } else if (z) {
-        // accumulate mode: the replicas -> d alpha, d b_alpha, the ctx2att bias gradient (column sums of d P_all) and -- when the logit-layer
-        // gradients were formed on this stream just before -- d b_logit: ONE multi-problem launch instead of four
-        ColsumJob cj[4] = {{b.GAREP, Ha, ALPHA_REP, Ha, g->g_w_alpha, nullptr, nullptr}, {b.GBREP, 1, ALPHA_REP, 1, g->g_b_alpha, nullptr, nullptr},
-                           {b.DPALL, Ha, a->Tv, Ha, g->g_b_c2a, nullptr, nullptr}, {b.DLG, b.ldg, SNc, V1, g->g_b_logit, nullptr, nullptr}};
-        RC(colsum_multi(cj, bias_pending ? 4 : 3, st));
-    } else {
-    RC(colsum(b.GAREP, Ha, ALPHA_REP, Ha, g->g_w_alpha, z, st));        // replicas -> d alpha, d b_alpha (overwrite or accumulate like every
-    RC(colsum(b.GBREP, 1, ALPHA_REP, 1, g->g_b_alpha, z, st));          // other parameter gradient)
-    }
-    if (h2) {
+    echr_gemm_desc d;
+    if (p.h2) {
         H2PackJob pj[2] = {pack_cols(b.DPALL, Ha, Ha, a->Tv, b.PK_DPT), pack_cols(a->c3d, D, D, a->Tv, b.PK_C3DT)};
         RC(h2_pack_multi(pj, 2, st));
         d = desc_h2(b.PK_DPT, b.PK_C3DT, g->g_w_c2a, D, Ha, D, a->Tv);
@@ -2011,21 +1950,82 @@ int echr::decoder_bwd_parts(const echr_dec_args* a, const echr_dec_grads* g, con
         d = desc_tn(b.DPALL, Ha, a->c3d, D, g->g_w_c2a, D, Ha, D, a->Tv);
         d.split_k = -1;
     }
-    d.beta = zb;
+    d.beta = p.zb;
     RC(gemm(d, st));
-    if (!z) RC(colsum(b.DPALL, Ha, a->Tv, Ha, g->g_b_c2a, z, st));
-    if (!dxt_done) RC(dxt_chain(st));
-    if (async_tail) {
+    return z ? 0 : colsum(b.DPALL, Ha, a->Tv, Ha, g->g_b_c2a, z, st);
+}
+// the LSTM-layer gradients behind the recurrence on one stream: weight gradients, bias sums, event context (`ev`: EV_*), scene gradients
+static int bwd_lstm_grads(const BwdPlan& p, int ev, float* dgsum0, hipStream_t q) {
+    RC(bwd_weight_grads(p, q));
+    RC(bwd_bias_sums(p, q));
+    RC(bwd_event_grads(p, ev, dgsum0, q));
+    return bwd_scene_grads(p, q, !p.z);          // (the non-accumulating bias form has formed every stream's per-event sums)
+}
+// 4. batched parameter gradients of the three LSTM layers (core.layer0..2) -- final after this stage, so a data-parallel caller can start reducing
+//    them (phase 3) while the tail stage runs.  Three schedules: the caller's stream, accumulating (the per-event sums of stream 0 feed the
+//    event-context products) or not, and async_tail = 2: only d event (what the caller's next backward kernels, the event encoder's, wait for) is
+//    formed on the caller's stream, first; the rest -- nine transposing packs, the grouped weight-gradient product, bias sums, the context halves
+//    of W_ih: ~0.13 ms -- moves to the prepare stream (idle during a backward pass) and is joined by echr_stream_join like the tail
+static int bwd_lstm_stage(const BwdPlan& p, hipStream_t st, BwdSched& s) {
+    float* const* dgsum = p.b.DGSUM;
+    if (!(p.stages & BWD_LSTM)) return 0;
+    if (!p.lstm_on_helper) return bwd_lstm_grads(p, (p.z ? EV_SUMS : 0) | EV_D_WEIGHT | EV_D_EVENT, dgsum[0], st);
+    // Both helper streams fork RIGHT BEHIND the reverse recurrence, off ONE recorded event, not behind d event with one record each: the
+    // two records used to sit between the d event product and everything that follows on all three streams (~15 us of an idle chip).
+    // The prepare stream then forms its own copy of the per-event gate-gradient sums (6 us) instead of waiting for this stream's
+    const bool whole = p.part == 0;
+    const hipStream_t early = whole ? aux2_fork(st) : nullptr;
+    if (early) fork_event(prep().fork);          // the tail stage's fork waits for the same event
+    if (p.part != 2) RC(bwd_event_grads(p, EV_SUMS | EV_D_EVENT, dgsum[0], st));
+    if (p.part == 1) return 0;
+    const hipStream_t q = whole ? early : aux2_fork(st);
+    if (!q) return bwd_lstm_grads(p, EV_D_WEIGHT, dgsum[0], st);          // (no second helper stream: the rest follows d event on the caller's stream)
+    if (whole) RC(bwd_event_grads(p, EV_SUMS, dgsum[1], q));
+    RC(bwd_lstm_grads(p, EV_D_WEIGHT, dgsum[whole ? 1 : 0], q));
+    RC(handover_mark(ECHR_HANDOVER_LSTM, q));          // every gradient of core.layer0..2 is final here
+    if (p.stages & BWD_TAIL) { RC(bwd_embed_grads(p, q)); s.embed_queued = true; }
+    if (hipEventRecord(tail().done3, q) != hipSuccess) { set_error("decoder_bwd: event record failed"); return -5; }
+    tail().pending3 = true;
+    return 0;
+}
+// the tail: deferred logit-layer gradients, attention parameters, token embedding (unless the prepare stream took it).  phase 0 + async_tail: nothing
+// downstream in the backward pass needs its outputs -> the tail stream, joined by the caller.  Its three chains read only what the recurrence left
+// (DLG, OUTD, DG, DQ, DSC); the tail forks behind the LSTM-layer stage, not ahead of it: measured on one box, alternating runs, 1.726 vs 1.731 ms
+// per iteration -- this phase is bound by its chip-filling GEMMs, packs and att_post (~0.4 ms), not by stream order
+static int bwd_tail_stage(const BwdPlan& p, hipStream_t sm, BwdSched& s) {
+    if (!(p.stages & BWD_TAIL)) return 0;
+    const hipStream_t st = p.async_tail ? tail().s : sm;
+    if (p.async_tail) {
+        if (hipEvent_t fe = fork_event_slot()) {          // (forked with the prepare stream, right behind the reverse recurrence)
+            if (hipStreamWaitEvent(st, fe, 0) != hipSuccess) { set_error("decoder_bwd: stream fork failed"); return -5; }
+        } else RC(hop(sm, tail().fork, st));
+        RC(bwd_logit_grads_on_tail(p, st, s));
+    }
+    RC(bwd_attention_params(p, s.bias_owed, st));
+    if (!s.embed_queued) RC(bwd_embed_grads(p, st));
+    if (p.async_tail) {
         if (hipEventRecord(tail().done, st) != hipSuccess) { set_error("decoder_bwd: event record failed"); return -5; }
         tail().pending = true;
-        st = sm;
     }
     return 0;
-    };
-    int rcp = part_a();
-    if (!rcp) rcp = part_b();
+}
+static int bwd_stages(const BwdPlan& p, hipStream_t st) {
+    BwdSched s;
+    if (p.stages & BWD_HEAD) { RC(bwd_dlogits_and_scratch(p, st)); RC(bwd_late_fusion(p, st)); }
+    if (p.stages & BWD_REC) RC(bwd_recurrence(p, st));
+    RC(bwd_lstm_stage(p, st, s));
+    return bwd_tail_stage(p, st, s);
+}
+int echr::decoder_bwd_parts(const echr_dec_args* a, const echr_dec_grads* g, const echr_dropout* drop, void* stream, int part, const float* rw) {
+    if (prep().fill_pending) {          // (a stream wait, not a launch: the caller's arena fill is ordered in front of whatever follows, refused or not)
+        prep().fill_pending = false;
+        if (hipStreamWaitEvent((hipStream_t)stream, prep().fill_done, 0) != hipSuccess) { set_error("decoder_bwd: stream wait failed"); return -5; }
+    }
+    BwdPlan p;
+    RC(bwd_plan(a, g, drop, part, rw, p));
+    const int rc = bwd_stages(p, (hipStream_t)stream);
     fork_event(nullptr);
-    return rcp;
+    return rc;
 }
 
 // ------------------------------------------------------------------------------------------------------
