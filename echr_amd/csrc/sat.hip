@@ -240,6 +240,10 @@ __global__ __launch_bounds__(256) void sat_add2_kernel(const float* __restrict__
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i < n) out[i] = a[i] + b[i];
 }
+__global__ __launch_bounds__(256) void sat_acc_kernel(float* __restrict__ dst, const float* __restrict__ src, long n) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) dst[i] += src[i];
+}
 
 // ------------------------------------------------------------------------------------------------------
 // workspaces
@@ -282,7 +286,7 @@ static SatWs sat_carve(const echr_sat_args* a, float* base) {
     w.total = off;
     return w;
 }
-struct SatWsB { float *DLG, *DOUT, *DG, *DGSUM, *DGCOL, *DATT, *DSC, *DXT, *DHB[2], *DCB[2], *DQ, *GAREP, *GBREP, *DPALL; long ldg, zero_floats, total; };
+struct SatWsB { float *DLG, *DOUT, *DG, *DGSUM, *DGCOL, *DATT, *DSC, *DXT, *DHB[2], *DCB[2], *DQ, *GAREP, *GBREP, *DPALL, *GEMB; long ldg, zero_floats, total; };
 static SatWsB sat_carve_bwd(const echr_sat_args* a, float* base) {
     SatWsB w;
     long off = 0;
@@ -306,6 +310,9 @@ static SatWsB sat_carve_bwd(const echr_sat_args* a, float* base) {
     w.GBREP = take(att_post_replicas());
     w.DPALL = take((long)a->Tv * a->Ha);
     w.zero_floats = off - z0;
+    // the table gradient of one call, summed from zero and added to g_embed ONCE (`zeroed` = 1 only): the scatter adds a row per occurrence of
+    // its token, which rounds at the magnitude of whatever the caller's buffer already holds
+    w.GEMB = take((long)a->V1 * a->E);
     w.total = off;
     return w;
 }
@@ -604,5 +611,10 @@ extern "C" int echr_sat_bwd(const echr_sat_args* a, const echr_sat_grads* g, con
     // 4. token embedding: d XT = DG . W_ih[:, :E], scatter-added into the table gradient
     d = desc_nn(b.DG, H4, a->w_ih, dm.ldw, b.DXT, E, SN, E, H4);
     SRC(gemm(d, st));
-    return embed_scatter_add(b.DXT, a->tokens, g->g_embed, SN, E, V1, st);
+    if (!g->zeroed) return embed_scatter_add(b.DXT, a->tokens, g->g_embed, SN, E, V1, st);          // (zero-filled above)
+    const long ne = (long)V1 * E;
+    SRC(fill_zero(b.GEMB, ne, st));
+    SRC(embed_scatter_add(b.DXT, a->tokens, b.GEMB, SN, E, V1, st));
+    hipLaunchKernelGGL(sat_acc_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, st, g->g_embed, b.GEMB, ne);
+    return check_launch("sat_acc");
 }

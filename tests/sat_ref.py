@@ -23,6 +23,7 @@ PRE = 'lm_model.'
 # d loss / d alpha_net.bias is exactly zero in real arithmetic (the slot softmax is shift invariant): every side holds rounding noise
 # (tests/util.NOISE_ONLY names the three-stream decoder's)
 NOISE_ONLY = (PRE + 'core.alpha_net.bias',)
+PROBE = None          # a list here receives what core_step saw
 
 
 def attention(P, h, clip, mask):
@@ -50,6 +51,8 @@ def core_step(P, xt, video, event, clip, mask, state, feats_type):
     g = F.linear(torch.cat(parts, 1), P[PRE + 'core.rnn.weight_ih_l0']) + F.linear(h, P[PRE + 'core.rnn.weight_hh_l0'])
     i, f, gg, o = g.chunk(4, 1)
     c2 = torch.sigmoid(f) * c + torch.sigmoid(i) * torch.tanh(gg)
+    if PROBE is not None:          # (tests/sat_regime_ref.probe: the gate pre-activations [N, 4H] and the new cell state [N, H] of every step)
+        PROBE.append((g.detach().numpy().copy(), c2.detach().numpy().copy()))
     h2 = torch.sigmoid(o) * torch.tanh(c2)
     return h2, (h2.unsqueeze(0), c2.unsqueeze(0))
 
