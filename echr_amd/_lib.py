@@ -133,6 +133,13 @@ class CiderdArgs(C.Structure):        # echr_ciderd_args
                 ('idf_unseen', C.c_double), ('base', c_f), ('weight', f32), ('out', c_f)]
 
 
+class DensecapArgs(C.Structure):      # echr_densecap_args: one struct for the four dense-caption scoring entries
+    _fields_ = [('V', i32), ('n_tau', i32), ('N_tot', i32), ('G_tot', i32), ('pred_stamps', c_f), ('pred_offset', c_f), ('gt_stamps', c_f),
+                ('gt_offset', c_f), ('tau', c_f), ('count', c_f), ('pred_flag', c_f), ('gt_hit', c_f), ('start', c_f), ('P_tot', i64),
+                ('pair_pred', c_f), ('pair_gt', c_f), ('L', i32), ('T', i32), ('cand', c_f), ('cand_i32', i32), ('ld', i64), ('cs', i64),
+                ('refs', c_f), ('stats', c_f), ('rouge', c_f), ('cider', c_f), ('video', c_f), ('mean', c_f)]
+
+
 class SatArgs(C.Structure):          # echr_sat_args: the one-stream (show_attend_tell) decoder
     _fields_ = [('N', i32), ('A', i32), ('Tv', i32), ('D', i32), ('H', i32), ('E', i32), ('Ha', i32), ('De', i32),
                 ('Dv', i32), ('V1', i32), ('S', i32), ('feats', i32), ('rows_disjoint', i32),
@@ -260,6 +267,10 @@ SYMBOLS = [
     ('echr_clamp_adam', i32, [c_f, c_f, c_f, c_f, i64, i32, C.c_double, C.c_double, C.c_double, C.c_double, f32, C.c_void_p]),
     ('echr_clamp_adam_counted', i32, [c_f, c_f, c_f, c_f, i64, i32, C.c_double, C.c_double, C.c_double, C.c_double, f32, c_f, C.c_void_p]),
     ('echr_ciderd_score', i32, [C.POINTER(CiderdArgs), C.c_void_p]),
+    ('echr_densecap_match', i32, [C.POINTER(DensecapArgs), C.c_void_p]),
+    ('echr_densecap_fill', i32, [C.POINTER(DensecapArgs), C.c_void_p]),
+    ('echr_densecap_pair_stats', i32, [C.POINTER(DensecapArgs), C.c_void_p]),
+    ('echr_densecap_reduce', i32, [C.POINTER(DensecapArgs), C.c_void_p]),
     ('echr_sat_ws_floats', i64, [C.POINTER(SatArgs)]),
     ('echr_sat_ws_bwd_floats', i64, [C.POINTER(SatArgs)]),
     ('echr_sat_fwd', i32, [C.POINTER(SatArgs), C.POINTER(Dropout), C.c_void_p]),
@@ -273,7 +284,8 @@ ABI_STRUCTS = {'echr_gemm_desc': GemmDesc, 'echr_dropout': Dropout, 'echr_tsrm_a
                'echr_dec_args': DecArgs, 'echr_dec_grads': DecGrads, 'echr_sample_args': SampleArgs, 'echr_sst_args': SstArgs,
                'echr_sst_grads': SstGrads, 'echr_train_step_args': TrainStepArgs, 'echr_init_state_args': InitStateArgs, 'echr_init_state_grads': InitStateGrads,
                'echr_beam_args': BeamArgs, 'echr_row_grad_args': RowGradArgs, 'echr_clip_step_args': ClipStepArgs, 'echr_batch_ext': BatchExt, 'echr_sst_batch': SstBatch,
-               'echr_ciderd_args': CiderdArgs, 'echr_sat_args': SatArgs, 'echr_sat_grads': SatGrads, 'echr_sat_sample_args': SatSampleArgs}
+               'echr_ciderd_args': CiderdArgs, 'echr_sat_args': SatArgs, 'echr_sat_grads': SatGrads, 'echr_sat_sample_args': SatSampleArgs,
+               'echr_densecap_args': DensecapArgs}
 
 ABI_VERSION = 3          # include/echr_hip.h ECHR_ABI_VERSION
 _lib = None

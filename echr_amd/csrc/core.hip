@@ -1281,6 +1281,7 @@ extern "C" int64_t echr_abi_sizeof(const char* name) {
     ECHR_SZ(echr_init_state_args); ECHR_SZ(echr_init_state_grads); ECHR_SZ(echr_beam_args);
     ECHR_SZ(echr_row_grad_args); ECHR_SZ(echr_clip_step_args); ECHR_SZ(echr_batch_ext); ECHR_SZ(echr_sst_batch);
     ECHR_SZ(echr_ciderd_args); ECHR_SZ(echr_sat_args); ECHR_SZ(echr_sat_grads); ECHR_SZ(echr_sat_sample_args);
+    ECHR_SZ(echr_densecap_args);
 #undef ECHR_SZ
     return -1;
 }

@@ -395,3 +395,33 @@ def ciderd_of(extras_or_seq, scorer, refs):
         scorer.cuda()
         seq, width = torch.zeros(n, 1, dtype=torch.int64, device=scorer.device), 0
     return float(scorer.score(seq, refs, width=width).mean().cpu())
+
+
+def dense_scores(vid_infos, extras, gt, tious=None, scorer=None):
+    """The dense-captioning scores (echr_amd.densecap.evaluate) of what caption_videos / caption_videos_beam /
+    caption_video returned: tIoU matching of the records' 'timestamp' against `gt` (densecap.pack_ground_truth(...).cuda(), the videos in
+    the call's order), Recall / Precision / f1() and BLEU-1..4, ROUGE-L and -- with a reward.CiderD `scorer` -- CIDEr-D over the matched
+    pairs.  The caption rows are those of extras['batch'].event_slices over extras['kept']; a video that was not kept, or that has no
+    record, counts as a video without predictions.  A flag_eval_what='tap' result (no captions) gives detection only."""
+    from . import densecap
+    single = isinstance(extras, dict) and 'per_video' not in extras          # caption_video: one flat list of records
+    infos = [vid_infos] if single else list(vid_infos)
+    V = gt.offset.numel() - 1
+    if len(infos) != V:
+        raise ValueError('%d videos were captioned, the ground truth has %d' % (len(infos), V))
+    dev = gt.stamps.device
+    stamps = [r['timestamp'] for info in infos for r in info]
+    off = np.concatenate([[0], np.cumsum([len(info) for info in infos])]).astype(np.int32)
+    pst = torch.from_numpy(np.asarray(stamps, dtype=np.float64).reshape(-1, 2)).to(dev)
+    seq = extras.get('seq')
+    if not isinstance(seq, torch.Tensor) or seq.numel() == 0:
+        seq = None
+    elif not single:
+        slices = dict(zip(extras['kept'], extras['batch'].event_slices))
+        rows = [np.arange(slices[v].start, slices[v].stop) for v in range(V) if len(infos[v])]
+        rows = np.concatenate(rows) if rows else np.zeros(0, np.int64)
+        if rows.size != seq.shape[0] or (rows != np.arange(rows.size)).any():
+            seq = seq.index_select(0, torch.from_numpy(rows).to(seq.device))
+    if seq is not None and seq.shape[0] != int(off[-1]):
+        raise ValueError('%d records, %d caption rows' % (int(off[-1]), seq.shape[0]))
+    return densecap.evaluate(pst, off, seq, gt, densecap.TIOUS if tious is None else tious, scorer=scorer)

@@ -495,6 +495,62 @@ typedef struct {
 } echr_ciderd_args;
 int echr_ciderd_score(const echr_ciderd_args* a, void* stream);
 
+/* Dense-caption scoring over token ids: the ANETcaptions protocol of the reference's
+ * external_tool/densevid_eval/evaluate.py without METEOR -- tIoU matching at n_tau thresholds, Recall / Precision, and BLEU-1..4,
+ * ROUGE-L and (optionally) CIDEr-D over the matched (prediction, ground truth) pairs.  Video v owns predictions
+ * pred_offset[v] .. pred_offset[v + 1] - 1 (possibly none) and ground truths gt_offset[v] .. gt_offset[v + 1] - 1 (at least one).
+ *   iou = max(0, min(e1, e2) - max(s1, s2)) / (min(max(e1, e2) - min(s1, s2), (e2 - s2) + (e1 - s1)) + 1e-8), fp64 in this order.
+ * One struct serves the four entries; each reads the fields its stage names and validates them on the host before any launch.
+ *  echr_densecap_match: count[k, i] = number of ground truths of prediction i's video with iou >= tau[k], 1 when there is none (the
+ *    unmatched pair); pred_flag[k, i] = (any iou > tau[k]) | 2 * (no iou >= tau[k]); gt_hit[k, j] = any prediction of j's video with
+ *    iou > tau[k].  No atomics: a thread owns a prediction or a ground truth.
+ *  echr_densecap_fill: with start the exclusive scan of count (flattened [n_tau, N_tot], one entry more for the total), the pair list
+ *    (pair_pred, pair_gt) ordered by threshold, video, prediction, ground truth; an unmatched pair has pair_gt = -1.
+ *  echr_densecap_pair_stats: one wave per pair.  A caption's words are the tokens before its first 0 among its columns (< T for a
+ *    candidate, < L for a reference row), all of them when there is none.  stats[p] = {match_1..4, len_c, len_r, lcs}: match_n the clipped
+ *    count sum over the candidate's distinct order-n n-grams of min(tf_cand, tf_ref), lcs the longest common subsequence; an unmatched
+ *    pair has zero matches, len_r = 1 and lcs 0.  rouge[p] = (1 + b^2) P R / (R + b^2 P), P = lcs / len_c, R = lcs / len_r, b = 1.2, 0
+ *    unless both are positive.
+ *  echr_densecap_reduce: video[k, v, :] = {recall, precision, Bleu_1..4, ROUGE_L, CIDErD, pairs, unmatched pairs} of video v at tau[k]
+ *    (integer sums; BLEU in fp64 with p_n = (match_n + 1e-15) / (guess_n + 1e-9) and the brevity penalty of (c + 1e-15) / (r + 1e-9); the
+ *    ROUGE-L and CIDEr-D means summed in pair order), and mean[k, :] the first eight averaged over the V videos in video order.  With
+ *    stats == NULL (no captions) the language columns are 0.  Bitwise reproducible; a video's numbers do not depend on the others. */
+#define ECHR_DENSECAP_MAX_TAU 8
+#define ECHR_DENSECAP_VIDEO_COLS 10
+#define ECHR_DENSECAP_MEAN_COLS 8
+#define ECHR_DENSECAP_STATS 7
+typedef struct {
+    int32_t V, n_tau;            /* videos; thresholds, 1 .. ECHR_DENSECAP_MAX_TAU */
+    int32_t N_tot, G_tot;        /* predictions and ground truths of the call */
+    const double* pred_stamps;   /* [N_tot, 2] seconds */
+    const int32_t* pred_offset;  /* [V + 1] */
+    const double* gt_stamps;     /* [G_tot, 2] */
+    const int32_t* gt_offset;    /* [V + 1] */
+    const double* tau;           /* [n_tau], device memory */
+    int32_t* count;              /* match out [n_tau, N_tot] */
+    int32_t* pred_flag;          /* match out [n_tau, N_tot] */
+    int32_t* gt_hit;             /* match out [n_tau, G_tot] */
+    const int64_t* start;        /* [n_tau * N_tot + 1] exclusive scan of count */
+    int64_t P_tot;               /* start's last entry: pairs over all thresholds, < 2^31 */
+    int32_t* pair_pred;          /* fill out [P_tot] prediction row */
+    int32_t* pair_gt;            /* fill out [P_tot] ground-truth row or -1 */
+    int32_t L;                   /* seq_length, 1 .. 63: the width of refs */
+    int32_t T;                   /* columns of cand, 0 .. 63 */
+    const void* cand;            /* [N_tot, T] token ids, int64 (cand_i32 = 0) or int32 (1): element (n, t) at n * ld + t * cs */
+    int32_t cand_i32;
+    int64_t ld, cs;
+    const int32_t* refs;         /* [G_tot, L] one reference per ground truth, zero-padded */
+    int32_t* stats;              /* pair_stats out [P_tot, ECHR_DENSECAP_STATS] */
+    double* rouge;               /* pair_stats out [P_tot] */
+    const float* cider;          /* optional [P_tot]: the pairs' CIDEr-D (0 at unmatched pairs) */
+    double* video;               /* reduce out [n_tau, V, ECHR_DENSECAP_VIDEO_COLS] */
+    double* mean;                /* reduce out [n_tau, ECHR_DENSECAP_MEAN_COLS] */
+} echr_densecap_args;
+int echr_densecap_match(const echr_densecap_args* a, void* stream);
+int echr_densecap_fill(const echr_densecap_args* a, void* stream);
+int echr_densecap_pair_stats(const echr_densecap_args* a, void* stream);
+int echr_densecap_reduce(const echr_densecap_args* a, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * SST proposal encoder.  Replaces models/sst_model.py:31-40 (nn.LSTM over one video + Linear + sigmoid)
  * and TAPModelCriterion (misc/utils.py:78-99).  Parameters use nn.LSTM's layout: w_ih[l] [4H, D or H], w_hh[l] [4H,H],
