@@ -578,10 +578,10 @@ __global__ __launch_bounds__(256) void logsoftmax_bwd_reg_kernel(const float* __
     }
 }
 int logsoftmax_bwd(const float* logp, const float* G, const void* target, int tgt64, const float* mask, const float* g_loss,
-                   const float* mask_sum, float* out, long ldo, int N, int S, int V1, hipStream_t st, const float* rw) {
+                   const float* mask_sum, float* out, long ldo, int N, int S, int V1, hipStream_t st, const float* rw, bool unit_den) {
     if (G && ldo <= 256 * 20 && ldo > 256 * 8) hipLaunchKernelGGL(logsoftmax_bwd_reg_kernel<20>, dim3(N * S), dim3(256), 0, st, logp, G, out, ldo, N, S, V1);
     else if (G && ldo <= 256 * 8) hipLaunchKernelGGL(logsoftmax_bwd_reg_kernel<8>, dim3(N * S), dim3(256), 0, st, logp, G, out, ldo, N, S, V1);
-    else if (rw && !G) hipLaunchKernelGGL(logsoftmax_bwd_kernel<true>, dim3(N * S), dim3(256), 0, st, logp, G, target, tgt64, mask, g_loss, mask_sum, out, ldo, N, S, V1, rw, crit_unit_den());
+    else if (rw && !G) hipLaunchKernelGGL(logsoftmax_bwd_kernel<true>, dim3(N * S), dim3(256), 0, st, logp, G, target, tgt64, mask, g_loss, mask_sum, out, ldo, N, S, V1, rw, unit_den ? 1 : 0);
     else hipLaunchKernelGGL(logsoftmax_bwd_kernel<false>, dim3(N * S), dim3(256), 0, st, logp, G, target, tgt64, mask, g_loss, mask_sum, out, ldo, N, S, V1, nullptr, 0);
     return check_launch("logsoftmax_bwd");
 }
@@ -647,10 +647,10 @@ __global__ __launch_bounds__(256) void nll_rows_sum_kernel(const float* __restri
 }
 bool logsoftmax_nll_dlg_ok(int V1, long ldo) { return ldo <= 256 * 40; }
 int logsoftmax_nll_dlg(const float* X, long ld, const void* target, int tgt64, const float* mask, const float* g_loss, float* out, long ldo,
-                       float* row_loss, float* msum_out, int N, int S, int V1, hipStream_t st, const int* act, int n_active, const float* rw) {
+                       float* row_loss, float* msum_out, int N, int S, int V1, hipStream_t st, const int* act, int n_active, const float* rw, bool unit_den) {
     const int rows = act ? n_active : N * S;
 #define ECHR_NLL_DLG(EPT) \
-    if (rw) hipLaunchKernelGGL((logsoftmax_nll_dlg_kernel<EPT, true>), dim3(rows), dim3(256), 0, st, X, ld, target, tgt64, mask, g_loss, out, ldo, row_loss, msum_out, N, S, V1, act, rw, crit_unit_den()); \
+    if (rw) hipLaunchKernelGGL((logsoftmax_nll_dlg_kernel<EPT, true>), dim3(rows), dim3(256), 0, st, X, ld, target, tgt64, mask, g_loss, out, ldo, row_loss, msum_out, N, S, V1, act, rw, unit_den ? 1 : 0); \
     else hipLaunchKernelGGL((logsoftmax_nll_dlg_kernel<EPT, false>), dim3(rows), dim3(256), 0, st, X, ld, target, tgt64, mask, g_loss, out, ldo, row_loss, msum_out, N, S, V1, act, nullptr, 0)
     if (ldo <= 256 * 8) { ECHR_NLL_DLG(8); }
     else if (ldo <= 256 * 20) { ECHR_NLL_DLG(20); }
@@ -658,8 +658,8 @@ int logsoftmax_nll_dlg(const float* X, long ld, const void* target, int tgt64, c
 #undef ECHR_NLL_DLG
     return check_launch("logsoftmax_nll_dlg");
 }
-int nll_rows_sum(const float* row_loss, int NS, const float* msum, float* loss, hipStream_t st, bool rw) {
-    if (rw) hipLaunchKernelGGL(nll_rows_sum_kernel<true>, dim3(1), dim3(256), 0, st, row_loss, NS, msum, loss, crit_unit_den());
+int nll_rows_sum(const float* row_loss, int NS, const float* msum, float* loss, hipStream_t st, bool rw, bool unit_den) {
+    if (rw) hipLaunchKernelGGL(nll_rows_sum_kernel<true>, dim3(1), dim3(256), 0, st, row_loss, NS, msum, loss, unit_den ? 1 : 0);
     else hipLaunchKernelGGL(nll_rows_sum_kernel<false>, dim3(1), dim3(256), 0, st, row_loss, NS, msum, loss, 0);
     return check_launch("nll_rows_sum");
 }
@@ -1490,21 +1490,13 @@ static int nll_fwd(const float* logp, const void* target, int tgt64, const float
     return check_launch("nll_loss_fwd");
 }
 namespace echr {
-int nll_loss_rw(const float* logp, const void* target, int tgt64, const float* mask, const float* rw, float* loss, int N, int S, int V1, hipStream_t st) {
+int nll_loss_rw(const float* logp, const void* target, int tgt64, const float* mask, const float* rw, float* loss, int N, int S, int V1, hipStream_t st, bool unit_den) {
     ECHR_REQUIRE(logp && target && mask && rw && loss && N > 0 && S > 0 && V1 > 0, "nll_loss_rw: bad arguments");
-    hipLaunchKernelGGL(nll_loss_kernel<true>, dim3(1), dim3(256), 0, st, logp, target, tgt64, mask, loss, N * S, V1, rw, crit_unit_den());
+    hipLaunchKernelGGL(nll_loss_kernel<true>, dim3(1), dim3(256), 0, st, logp, target, tgt64, mask, loss, N * S, V1, rw, unit_den ? 1 : 0);
     return check_launch("nll_loss_rw");
 }
 }  // namespace echr
 // ---- multi-video batches (echr_batch_ext) ----
-namespace echr {
-static thread_local const echr_batch_ext* g_batch_ext = nullptr;
-const echr_batch_ext* batch_ext() { return g_batch_ext; }
-static thread_local bool g_batch_scene_rows = false;
-bool batch_scene_rows() { return g_batch_scene_rows; }
-BatchScope::BatchScope(const echr_batch_ext* x, bool scene_rows) : prev(g_batch_ext), prev_rows(g_batch_scene_rows) { g_batch_ext = x; g_batch_scene_rows = scene_rows; }
-BatchScope::~BatchScope() { g_batch_ext = prev; g_batch_scene_rows = prev_rows; }
-}  // namespace echr
 
 // column means over row segments: block = (segment v, 64 columns); thread = (column, one of four row lanes); the four partial sums are added
 // in lane order (fixed order: bit-reproducible)

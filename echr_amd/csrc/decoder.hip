@@ -90,8 +90,10 @@ int join_tail(hipStream_t st) {
 
 // Data-parallel hand-over points (echr_train_step_args.handover, echr_handover_wait): events recorded where a contiguous range of the
 // gradient arena becomes final long before the backward pass ends -- the logit layer's gradients on the tail stream right behind their
-// product, the three LSTM layers' gradients on the prepare stream behind the grouped weight-gradient product.
-struct Handover { hipEvent_t ev[2] = {nullptr, nullptr}; bool valid[2] = {false, false}; bool want = false, init = false, ok = false; echr_handover_fn cb = nullptr; void* user = nullptr; };
+// product, the three LSTM layers' gradients on the prepare stream behind the grouped weight-gradient product.  What persists here is what
+// echr_handover_wait reads after the call: the events and which of them hold a point.  The request belongs to ONE backward pass and travels
+// with it (DecCall.handover, copied into BwdPlan, where it is in force only when the events exist).
+struct Handover { hipEvent_t ev[2] = {nullptr, nullptr}; bool valid[2] = {false, false}; bool init = false, ok = false; };
 static Handover& handover() {
     static Handover h;
     if (!h.init) {
@@ -103,19 +105,13 @@ static Handover& handover() {
     }
     return h;
 }
-void handover_request(bool on, echr_handover_fn cb, void* user) {
+void handover_clear() { Handover& h = handover(); h.valid[0] = h.valid[1] = false; }
+static int handover_mark(const DecCall& c, int which, hipStream_t on) {
+    if (!c.handover) return 0;
     Handover& h = handover();
-    h.want = on && h.ok;
-    h.cb = on ? cb : nullptr; h.user = user;
-    h.valid[0] = h.valid[1] = false;
-}
-void handover_close() { handover().want = false; handover().cb = nullptr; }
-static int handover_mark(int which, hipStream_t on) {
-    Handover& h = handover();
-    if (!h.want) return 0;
     if (hipEventRecord(h.ev[which], on) != hipSuccess) { set_error("decoder_bwd: hand-over event record failed"); return -5; }
     h.valid[which] = true;
-    if (h.cb) h.cb(which, on, h.user);          // (host callback: the caller queues its collective behind this point of `on`)
+    if (c.handover_cb) c.handover_cb(which, on, c.handover_user);          // (host callback: the caller queues its collective behind this point of `on`)
     return 0;
 }
 extern "C" int echr_handover_wait(int which, void* stream) {
@@ -851,6 +847,17 @@ __global__ __launch_bounds__(256) void lstm_pointwise_bwd_kernel(LstmBwdPtrs P, 
 // ------------------------------------------------------------------------------------------------------
 static inline long rup(long x, long a) { return (x + a - 1) / a * a; }
 
+// Multi-video batches: the caller's scratch echr_batch_ext.ws = VIDB [N, 4H] (scene part of stream 2's gates per EVENT) | VIDV [V, 4H] (per
+// video) | DGSEG [V, 4H] (d gates2 summed over time and over the events of a video).  The workspaces below are those of a single video.
+struct BatchWs { float *VIDB, *VIDV, *DGSEG; long total; };
+static BatchWs carve_batch(long N, long V, long H, float* base) {
+    BatchWs w;
+    long off = 0;
+    auto take = [&](long n) { float* p = base ? base + off : nullptr; off += rup(n, 64); return p; };
+    w.VIDB = take(N * 4 * H); w.VIDV = take(V * 4 * H); w.DGSEG = take(V * 4 * H);
+    w.total = off;
+    return w;
+}
 struct DecWs {
     float *XT, *GATES[3], *CS[3], *HS, *OUTD, *PALL, *QS, *SC, *WT, *ATT, *EVB0, *VIDB;
     float *QSL, *GSL[3];         // split-K slabs of the current timestep (q and the three gate blocks)
@@ -860,8 +867,11 @@ struct DecWs {
     float *PK_WLT;               // W_logit^T packed for the backward's d OUTD product (echr_dec_args.train: packed with the forward operands)
     int nq, ng[3];
     long total;
+    // the scene part of stream 2's gate pre-activations: one [4H] vector (VIDB, pitch 0) or, for a multi-video batch (bx, nullptr otherwise), one
+    // row per event in the caller's batch scratch (pitch 4H), consumed like stream 0's per-event EVB0; scene_rows: see DecCall
+    const echr_batch_ext* bx; float* scene; long scene_ld; bool scene_rows;
 };
-static DecWs carve_ws(const echr_dec_args* a, float* base) {
+static DecWs carve_ws(const echr_dec_args* a, float* base, const echr_batch_ext* bx = nullptr, bool scene_rows = false) {
     DecWs w;
     long off = 0;
     const long N = a->N, S = a->S, H = a->H;
@@ -894,6 +904,9 @@ static DecWs carve_ws(const echr_dec_args* a, float* base) {
     w.XWS = take(persist_fwd_ws_floats((int)S));
     w.PK_WLT = take(h2_floats(3 * a->H, a->V1));
     w.total = off;
+    w.bx = bx; w.scene_rows = bx && scene_rows;
+    w.scene = bx ? carve_batch(N, bx->n_videos, H, bx->ws).VIDB : w.VIDB;
+    w.scene_ld = bx ? 4 * H : 0;
     return w;
 }
 
@@ -954,22 +967,6 @@ static DecWsBwd carve_ws_bwd(const echr_dec_args* a, float* base) {
     return w;
 }
 
-// Multi-video batches: the caller's scratch echr_batch_ext.ws = VIDB [N, 4H] (scene part of stream 2's gates per EVENT) | VIDV [V, 4H] (per
-// video) | DGSEG [V, 4H] (d gates2 summed over time and over the events of a video).  The workspaces above are those of a single video.
-struct BatchWs { float *VIDB, *VIDV, *DGSEG; long total; };
-static BatchWs carve_batch(long N, long V, long H, float* base) {
-    BatchWs w;
-    long off = 0;
-    auto take = [&](long n) { float* p = base ? base + off : nullptr; off += rup(n, 64); return p; };
-    w.VIDB = take(N * 4 * H); w.VIDV = take(V * 4 * H); w.DGSEG = take(V * 4 * H);
-    w.total = off;
-    return w;
-}
-// the scene part of stream 2's gate pre-activations and its row pitch: one [4H] vector of the workspace, or one row per event of a batch
-static inline float* scene_base(const echr_dec_args* a, const DecWs& w) {
-    const echr_batch_ext* bx = batch_ext();
-    return bx ? carve_batch(a->N, bx->n_videos, a->H, bx->ws).VIDB : w.VIDB;
-}
 static int check_dims(const echr_dec_args* a, const char* who) {
     ECHR_REQUIRE(a, "%s: null args", who);
     ECHR_REQUIRE(a->N > 0 && a->A > 0 && a->Tv > 0 && a->S >= 0, "%s: bad N/A/Tv/S", who);
@@ -1027,11 +1024,11 @@ static int precompute_static(const echr_dec_args* a, const DecWs& w, hipStream_t
     }
     d.bias = a->b_c2a;
     RC(gemm(d, st));
-    if (const echr_batch_ext* bx = batch_ext()) {
+    if (const echr_batch_ext* bx = w.bx) {
         // multi-video batch: one scene vector per video -> VIDV [V, 4H] (one fixed-order k loop per tile), gathered by vid into the per-event
         // VIDB [N, 4H] that the gate products / kernels consume exactly as they consume stream 0's per-event EVB0
         const BatchWs bw = carve_batch(a->N, bx->n_videos, H, bx->ws);
-        if (batch_scene_rows()) {          // every video's vector exactly as its own call forms it (BatchScope)
+        if (w.scene_rows) {          // every video's vector exactly as its own call forms it (DecCall.scene_rows)
             RC(rows_matvec(bx->video, a->Dv, a->w_ih[2] + E, E + a->Dv, a->b_ih[2], a->b_hh[2], bw.VIDV, 4 * H, bx->n_videos, 4 * H, a->Dv, st));
         } else {
             d = desc_nt(bx->video, a->Dv, a->w_ih[2] + E, E + a->Dv, bw.VIDV, 4 * H, bx->n_videos, 4 * H, a->Dv);
@@ -1149,7 +1146,7 @@ static int step_fwd(const echr_dec_args* a, const DecWs& w, int t, const DropCfg
         if (tok) {
             if (k == 0) { P.base[k] = w.EVB0; P.bmod[k] = N; }
             else if (k == 1) { P.base[k] = a->b_ih[1]; P.base2[k] = a->b_hh[1]; }
-            else { P.base[k] = scene_base(a, w); if (batch_ext()) P.bmod[k] = N; }          // (multi-video batch: per-event scene part)
+            else { P.base[k] = w.scene; if (w.bx) P.bmod[k] = N; }          // (multi-video batch: per-event scene part)
         }
         P.c_prev[k] = w.CS[k] + (long)t * N * H;
         P.c_new[k] = w.CS[k] + (long)(t + 1) * N * H;
@@ -1180,7 +1177,7 @@ static int input_gates(const echr_dec_args* a, const DecWs& w, const float* xt, 
         d[k].add_mod = N; d[k].ld_add = 4 * H;
         if (k == 0) { if (!no_evb0) d[k].addend = w.EVB0; }
         else if (k == 1) { d[k].bias = a->b_ih[1]; d[k].bias2 = a->b_hh[1]; }
-        else if (batch_ext()) d[k].addend = scene_base(a, w);          // multi-video batch: the scene part is per event, like EVB0
+        else if (w.bx) d[k].addend = w.scene;          // multi-video batch: the scene part is per event, like EVB0
         else d[k].bias = w.VIDB;
         d[k].split_k = force_h2 ? 1 : -1;          // sampler: one fixed-order k loop per tile (bitwise reproducible)
     }
@@ -1376,7 +1373,8 @@ int decoder_bwd_scratch_ahead(const echr_dec_args* a, const echr_dec_grads* g) {
     return 0;
 }
 }  // namespace echr
-extern "C" int echr_decoder_fwd_prepare(const echr_dec_args* a, void* stream) {
+extern "C" int echr_decoder_fwd_prepare(const echr_dec_args* a, void* stream) { return decoder_fwd_prepare(a, DecCall{}, stream); }
+int echr::decoder_fwd_prepare(const echr_dec_args* a, const DecCall& c, void* stream) {
     RC(persist_check_async());
     RC(check_dims(a, "decoder_fwd_prepare"));
     ECHR_REQUIRE(a->S > 0 && a->ws && a->tokens, "decoder_fwd_prepare: missing buffers");
@@ -1389,7 +1387,7 @@ extern "C" int echr_decoder_fwd_prepare(const echr_dec_args* a, void* stream) {
     if (hipEvent_t fe = fork_event_slot()) {
         if (hipStreamWaitEvent(st, fe, 0) != hipSuccess) { set_error("decoder_fwd_prepare: stream fork failed"); return -5; }
     } else RC(hop(sm, pr.fork, st));
-    DecWs w = carve_ws(a, a->ws);
+    DecWs w = carve_ws(a, a->ws, c.bx, c.scene_rows);
     // the persistent forward chain's weight images (parameters only) are built now, on the CALLER's stream -- it idles ~20 us waiting for the
     // position branch's gates -- so that the launch copies them instead of converting them in front of its first step (set-up 24.7 -> ~14 us)
     if (fwd_uses_persist(a)) RC(persist_fwd_prebuild(a, w.XWS, sm));
@@ -1426,22 +1424,23 @@ extern "C" int echr_decoder_fwd_prepare_cancel(void* stream) {
 }
 
 static int decoder_fwd_impl(const echr_dec_args* a, const echr_dropout* drop, void* stream, const echr_dec_grads* fz, bool* fused_out, bool* compact_out,
-                            const float* rw);
-extern "C" int echr_decoder_fwd(const echr_dec_args* a, const echr_dropout* drop, void* stream) { return decoder_fwd_impl(a, drop, stream, nullptr, nullptr, nullptr, nullptr); }
+                            const DecCall& c);
+extern "C" int echr_decoder_fwd(const echr_dec_args* a, const echr_dropout* drop, void* stream) { return decoder_fwd_impl(a, drop, stream, nullptr, nullptr, nullptr, DecCall{}); }
 namespace echr {
-int decoder_fwd_fused(const echr_dec_args* a, const echr_dec_grads* g, const echr_dropout* drop, void* stream, bool* fused, bool* compact, const float* rw) {
-    return decoder_fwd_impl(a, drop, stream, g, fused, compact, rw);
+int decoder_fwd_fused(const echr_dec_args* a, const echr_dec_grads* g, const echr_dropout* drop, void* stream, bool* fused, bool* compact, const DecCall& c) {
+    return decoder_fwd_impl(a, drop, stream, g, fused, compact, c);
 }
-int decoder_fused_loss(const echr_dec_args* a, const echr_dec_grads* g, float* loss, hipStream_t st, bool rw) {
+int decoder_fused_loss(const echr_dec_args* a, const echr_dec_grads* g, float* loss, hipStream_t st, bool rw, bool unit_den) {
     const DecWsBwd b = carve_ws_bwd(a, g->ws_bwd);
-    return nll_rows_sum(b.ROWL, (g->active_rows && g->n_active > 0) ? g->n_active : a->S * a->N, b.MSUM, loss, st, rw);
+    return nll_rows_sum(b.ROWL, (g->active_rows && g->n_active > 0) ? g->n_active : a->S * a->N, b.MSUM, loss, st, rw, unit_den);
 }
 }  // namespace echr
 // fz != nullptr: the criterion is fused behind the logits product (echr_train_step) -- the logits are turned into d logits in ws_bwd and
 // per-row loss terms by ONE pass instead of log-softmax, NLL and log-softmax backward passes; the log-probs are never materialised
-// rw (with fz): RewardCriterion's signed weight [N,S] (echr_train_step_rw) in place of the NLL's mask in the fused criterion pass
+// c.rw (with fz): RewardCriterion's signed weight [N,S] (echr_train_step_rw) in place of the NLL's mask in the fused criterion pass, over the
+// denominator 1 when the call is a batch (c.bx)
 static int decoder_fwd_impl(const echr_dec_args* a, const echr_dropout* drop, void* stream, const echr_dec_grads* fz, bool* fused_out, bool* compact_out,
-                            const float* rw) {
+                            const DecCall& c) {
     if (fused_out) *fused_out = false;
     if (compact_out) *compact_out = false;
     RC(persist_check_async());
@@ -1450,7 +1449,7 @@ static int decoder_fwd_impl(const echr_dec_args* a, const echr_dropout* drop, vo
     ECHR_REQUIRE(a->S > 0 && a->ws && a->logp && a->tokens, "decoder_fwd: missing buffers");
     hipStream_t st = (hipStream_t)stream;
     const int N = a->N, S = a->S, H = a->H, E = a->E;
-    DecWs w = carve_ws(a, a->ws);
+    DecWs w = carve_ws(a, a->ws, c.bx, c.scene_rows);
     const DropCfg dh = make_drop(drop, drop ? drop->p_h : 0.f), dout = make_drop(drop, drop ? drop->p_out : 0.f);
     bool evb0_pending = false;
     if (a->prepared) {
@@ -1500,7 +1499,7 @@ static int decoder_fwd_impl(const echr_dec_args* a, const echr_dropout* drop, vo
                 if (fused_out) *fused_out = true;
                 if (compact_out) *compact_out = true;
                 return logsoftmax_nll_dlg(a->logp, a->V1, fz->nll_target, fz->nll_target_i64, fz->nll_mask, fz->g_loss, b.DLG, b.ldg, b.ROWL, b.MSUM, N, S, a->V1, q,
-                                          fz->active_rows, fz->n_active, rw);
+                                          fz->active_rows, fz->n_active, c.rw, c.bx != nullptr);
             }
         }
         echr_gemm_desc d = desc_nt(w.OUTD, 3 * H, a->w_logit, 3 * H, a->logp, a->V1, S * N, a->V1, 3 * H);
@@ -1518,7 +1517,7 @@ static int decoder_fwd_impl(const echr_dec_args* a, const echr_dropout* drop, vo
             if (logsoftmax_nll_dlg_ok(a->V1, b.ldg)) {
                 if (fused_out) *fused_out = true;
                 return logsoftmax_nll_dlg(a->logp, a->V1, fz->nll_target, fz->nll_target_i64, fz->nll_mask, fz->g_loss, b.DLG, b.ldg, b.ROWL, b.MSUM, N, S, a->V1, q,
-                                          nullptr, 0, rw);
+                                          nullptr, 0, c.rw, c.bx != nullptr);
             }
         }
         return logsoftmax_rows(a->logp, a->V1, N, S, 0, S, a->V1, q);
@@ -1538,9 +1537,10 @@ static int decoder_fwd_impl(const echr_dec_args* a, const echr_dropout* drop, vo
 }
 
 extern "C" int echr_decoder_bwd(const echr_dec_args* a, const echr_dec_grads* g, const echr_dropout* drop, void* stream) {
-    return echr::decoder_bwd_checked(a, g, drop, stream, nullptr);
+    return echr::decoder_bwd_checked(a, g, drop, stream, DecCall{});
 }
-// ---- multi-video batches: the single-video entries with the extension published for the duration of the call ----
+// ---- multi-video batches: the single-video code, called with the extension (DecCall.bx) ----
+static DecCall dec_batch_call(const echr_batch_ext* x, bool scene_rows = false) { DecCall c; c.bx = x; c.scene_rows = scene_rows; return c; }
 static int check_batch(const echr_dec_args* a, const echr_batch_ext* x, const char* who) {
     ECHR_REQUIRE(a && x && x->n_videos > 0 && x->n_videos <= a->N && x->vid && x->video && x->ws, "%s: the batch extension needs 0 < n_videos <= N, vid, video and ws", who);
     return 0;
@@ -1548,13 +1548,11 @@ static int check_batch(const echr_dec_args* a, const echr_batch_ext* x, const ch
 extern "C" int echr_decoder_fwd_batch(const echr_dec_args* a, const echr_dropout* drop, const echr_batch_ext* x, void* stream) {
     RC(check_batch(a, x, "decoder_fwd_batch"));
     ECHR_REQUIRE(!a->prepared, "decoder_fwd_batch: prepared must be 0");
-    BatchScope scope(x);
-    return echr_decoder_fwd(a, drop, stream);
+    return decoder_fwd_impl(a, drop, stream, nullptr, nullptr, nullptr, dec_batch_call(x));
 }
 extern "C" int echr_decoder_bwd_batch(const echr_dec_args* a, const echr_dec_grads* g, const echr_dropout* drop, const echr_batch_ext* x, void* stream) {
     RC(check_batch(a, x, "decoder_bwd_batch"));
-    BatchScope scope(x);
-    return echr_decoder_bwd(a, g, drop, stream);
+    return echr::decoder_bwd_checked(a, g, drop, stream, dec_batch_call(x));
 }
 namespace echr {
 int decoder_fused_video_loss(const echr_dec_args* a, const echr_dec_grads* g, const int* vid, int V, float* vloss, hipStream_t st) {
@@ -1563,13 +1561,13 @@ int decoder_fused_video_loss(const echr_dec_args* a, const echr_dec_grads* g, co
     return video_loss_rows(b.ROWL, compact ? g->active_rows : nullptr, compact ? g->n_active : a->S * a->N, a->N, vid, V, vloss, st);
 }
 }  // namespace echr
-int echr::decoder_bwd_checked(const echr_dec_args* a, const echr_dec_grads* g, const echr_dropout* drop, void* stream, const float* rw) {
+int echr::decoder_bwd_checked(const echr_dec_args* a, const echr_dec_grads* g, const echr_dropout* drop, void* stream, const DecCall& c) {
     RC(persist_check_async());
     RC(join_tail((hipStream_t)stream));
     RC(check_dims(a, "decoder_bwd"));
     ECHR_REQUIRE(g && a->ws && g->ws_bwd && a->logp, "decoder_bwd: missing buffers");
     ECHR_REQUIRE(g->dlg_ready || g->g_logp || (g->nll_target && g->nll_mask && g->g_loss), "decoder_bwd: need g_logp or the fused NLL inputs");
-    return decoder_bwd_parts(a, g, drop, stream, 0, rw);
+    return decoder_bwd_parts(a, g, drop, stream, 0, c);
 }
 
 // ---- decoder backward: one plan (BwdPlan, made at entry, before the first launch), stages as functions of (plan, stream), two schedulers
@@ -1591,7 +1589,8 @@ int echr::decoder_bwd_checked(const echr_dec_args* a, const echr_dec_grads* g, c
 enum { BWD_HEAD = 1, BWD_REC = 2, BWD_LSTM = 4, BWD_TAIL = 8 };          // the stage mask of a call
 enum { EV_SUMS = 1, EV_D_WEIGHT = 2, EV_D_EVENT = 4 };                      // what bwd_event_grads forms, in this order
 struct BwdPlan {
-    const echr_dec_args* a; const echr_dec_grads* g; const float* rw;
+    const echr_dec_args* a; const echr_dec_grads* g;
+    DecCall c;          // the call: criterion weight, batch extension (also in w), hand-over request (in force only when the events exist)
     int part, N, S, H, E, Ha, A, D, V1, SN, cin[3];
     DecWs w; DecWsBwd b; DropCfg dh, dout;
     bool z, h2; float zb;          // z: gradient buffers pre-zeroed by the caller: accumulate (beta zb = 1), no fills; h2: products on h2-packed operands
@@ -1607,13 +1606,14 @@ struct BwdPlan {
 };
 struct BwdSched { bool embed_queued = false, bias_owed = false; };          // embedding chain already queued (prepare stream) | d b_logit still owed (tail)
 // Every check that needs no launch result, before the first launch: a refused call queues nothing.
-static int bwd_plan(const echr_dec_args* a, const echr_dec_grads* g, const echr_dropout* drop, int part, const float* rw, BwdPlan& p) {
+static int bwd_plan(const echr_dec_args* a, const echr_dec_grads* g, const echr_dropout* drop, int part, const DecCall& c, BwdPlan& p) {
     ECHR_REQUIRE(part == 0 || (g->phase == 0 && g->async_tail == 2 && g->zeroed && config().gemm_h2 && tail().ok),
                  "decoder_bwd: the two-piece form needs phase 0, async_tail 2, zeroed gradients, the h2 path and the helper streams");
-    p.a = a; p.g = g; p.rw = rw; p.part = part;
+    p.a = a; p.g = g; p.part = part;
+    p.c = c; p.c.handover = c.handover && handover().ok;
     p.N = a->N; p.S = a->S; p.H = a->H; p.E = a->E; p.Ha = a->Ha; p.A = a->A; p.D = a->D; p.V1 = a->V1; p.SN = a->S * a->N;
     p.cin[0] = a->E + a->De; p.cin[1] = a->E + a->D; p.cin[2] = a->E + a->Dv;
-    p.w = carve_ws(a, a->ws); p.b = carve_ws_bwd(a, g->ws_bwd);
+    p.w = carve_ws(a, a->ws, c.bx, c.scene_rows); p.b = carve_ws_bwd(a, g->ws_bwd);
     p.dh = make_drop(drop, drop ? drop->p_h : 0.f); p.dout = make_drop(drop, drop ? drop->p_out : 0.f);
     p.z = g->zeroed != 0; p.zb = p.z ? 1.f : 0.f; p.h2 = config().gemm_h2 != 0;
     p.compact = g->dlg_ready && g->active_rows && g->n_active > 0; p.crec = p.compact && p.h2;
@@ -1639,7 +1639,7 @@ static int bwd_dlogits_and_scratch(const BwdPlan& p, hipStream_t st) {
     if (!g->dlg_ready) {          // (echr_train_step formed d logits in the pass that read the logits)
         if (!g->g_logp && !g->nll_msum) RC(colsum(g->nll_mask, 1, N * S, 1, b.MSUM, false, st));
         RC(logsoftmax_bwd(a->logp, g->g_logp, g->nll_target, g->nll_target_i64, g->nll_mask, g->g_loss, g->nll_msum ? g->nll_msum : b.MSUM, b.DLG, b.ldg, N, S, V1, st,
-                           p.rw));
+                           p.c.rw, p.c.bx != nullptr));
     }
     // scratch that is accumulated into, and the transposed recurrent weights (every d h / d ATT product of the reverse recurrence
     // then has the same NT form as forward): two launches, independent of everything above
@@ -1722,9 +1722,9 @@ static int bwd_logit_grads_on_tail(const BwdPlan& p, hipStream_t st, BwdSched& s
     }
     // h2 + z: d b_logit rides in the multi-problem column-sum launch behind att_post -- unless the logit layer's range is handed over to a
     // data-parallel collective right here (then the bias sum is formed with the product, so the whole range is final)
-    s.bias_owed = p.h2 && p.z && !handover().want;
+    s.bias_owed = p.h2 && p.z && !p.c.handover;
     RC(bwd_logit_grads(p, st, !s.bias_owed));
-    return handover_mark(ECHR_HANDOVER_LOGIT, st);
+    return handover_mark(p.c, ECHR_HANDOVER_LOGIT, st);
 }
 // one reverse timestep
 static int bwd_step(const BwdPlan& p, int t, hipStream_t q) {
@@ -1868,7 +1868,7 @@ static int bwd_event_grads(const BwdPlan& p, int what, float* dgsum, hipStream_t
 // order (DGSEG [V, 4H]), then d W_ih2[:, E:] = DGSEG^T . video (K = V) and d video = DGSEG . W_ih2[:, E:], each one fixed-order k loop per tile
 static int bwd_scene_grads(const BwdPlan& p, hipStream_t q, bool have_sum) {
     const echr_dec_args* a = p.a; const echr_dec_grads* g = p.g; const DecWsBwd& b = p.b; const int N = p.N, H = p.H, E = p.E;
-    const echr_batch_ext* bx = batch_ext();
+    const echr_batch_ext* bx = p.c.bx;
     if (!bx) {
         RC(rank1_update(b.DGCOL[2], a->video, g->g_w_ih[2] + E, p.cin[2], 4 * H, a->Dv, false, q));          // K = 1: no GEMM launch
         if (g->g_video) RC(vec_mat(b.DGCOL[2], a->w_ih[2] + E, p.cin[2], g->g_video, 4 * H, a->Dv, q));
@@ -1982,7 +1982,7 @@ static int bwd_lstm_stage(const BwdPlan& p, hipStream_t st, BwdSched& s) {
     if (!q) return bwd_lstm_grads(p, EV_D_WEIGHT, dgsum[0], st);          // (no second helper stream: the rest follows d event on the caller's stream)
     if (whole) RC(bwd_event_grads(p, EV_SUMS, dgsum[1], q));
     RC(bwd_lstm_grads(p, EV_D_WEIGHT, dgsum[whole ? 1 : 0], q));
-    RC(handover_mark(ECHR_HANDOVER_LSTM, q));          // every gradient of core.layer0..2 is final here
+    RC(handover_mark(p.c, ECHR_HANDOVER_LSTM, q));          // every gradient of core.layer0..2 is final here
     if (p.stages & BWD_TAIL) { RC(bwd_embed_grads(p, q)); s.embed_queued = true; }
     if (hipEventRecord(tail().done3, q) != hipSuccess) { set_error("decoder_bwd: event record failed"); return -5; }
     tail().pending3 = true;
@@ -2016,13 +2016,13 @@ static int bwd_stages(const BwdPlan& p, hipStream_t st) {
     RC(bwd_lstm_stage(p, st, s));
     return bwd_tail_stage(p, st, s);
 }
-int echr::decoder_bwd_parts(const echr_dec_args* a, const echr_dec_grads* g, const echr_dropout* drop, void* stream, int part, const float* rw) {
+int echr::decoder_bwd_parts(const echr_dec_args* a, const echr_dec_grads* g, const echr_dropout* drop, void* stream, int part, const DecCall& c) {
     if (prep().fill_pending) {          // (a stream wait, not a launch: the caller's arena fill is ordered in front of whatever follows, refused or not)
         prep().fill_pending = false;
         if (hipStreamWaitEvent((hipStream_t)stream, prep().fill_done, 0) != hipSuccess) { set_error("decoder_bwd: stream wait failed"); return -5; }
     }
     BwdPlan p;
-    RC(bwd_plan(a, g, drop, part, rw, p));
+    RC(bwd_plan(a, g, drop, part, c, p));
     const int rc = bwd_stages(p, (hipStream_t)stream);
     fork_event(nullptr);
     return rc;
@@ -2229,35 +2229,32 @@ static int chain_step(const echr_dec_args& a, const DecWs& w, const SampWs& s, i
 // drop != nullptr: echr_decoder_sample_train -- the launch-per-step chain with the caller's training-mode dropout masks, keyed like
 // echr_decoder_fwd's step t: (element, t, site, drop->offset)
 // row_step: the multinomial step as ONE launch that forms the row from the slabs and draws (sample_row_step; the batched training decode)
-static int decoder_sample_impl(const echr_sample_args* sa, const echr_dropout* drop, void* stream, bool row_step = false);
-extern "C" int echr_decoder_sample(const echr_sample_args* sa, void* stream) { return decoder_sample_impl(sa, nullptr, stream); }
+// c: the call's batch extension and scene_rows (DecCall; the criterion weight and the hand-over are not read here)
+static int decoder_sample_impl(const echr_sample_args* sa, const echr_dropout* drop, void* stream, const DecCall& c, bool row_step = false);
+extern "C" int echr_decoder_sample(const echr_sample_args* sa, void* stream) { return decoder_sample_impl(sa, nullptr, stream, DecCall{}); }
 extern "C" int echr_decoder_sample_train(const echr_sample_args* sa, const echr_dropout* drop, void* stream) {
     ECHR_REQUIRE(sa && drop, "decoder_sample_train: null args");
     ECHR_REQUIRE(sa->multinomial, "decoder_sample_train: the training-mode decode is the multinomial one (multinomial = 1)");
-    return decoder_sample_impl(sa, drop, stream);
+    return decoder_sample_impl(sa, drop, stream, DecCall{});
 }
 extern "C" int echr_decoder_sample_batch(const echr_sample_args* sa, const echr_batch_ext* x, void* stream) {
     ECHR_REQUIRE(sa && !sa->multinomial, "decoder_sample_batch: the batched decode is the greedy one (multinomial = 0)");
     RC(check_batch(&sa->dec, x, "decoder_sample_batch"));
-    BatchScope scope(x);
-    return decoder_sample_impl(sa, nullptr, stream);
+    return decoder_sample_impl(sa, nullptr, stream, dec_batch_call(x));
 }
-// The sampled pass of self-critical training over a multi-video batch: echr_decoder_sample_train with the per-row scene part published for
-// the call, the multinomial step as one launch per step, and the per-video widths behind the last step on the same stream
+// The sampled pass of self-critical training over a multi-video batch: echr_decoder_sample_train with the per-row scene part formed as each
+// video's own call forms it (scene_rows), the multinomial step as one launch per step, and the per-video widths behind the last step on the same stream
 extern "C" int echr_decoder_sample_train_batch(const echr_sample_args* sa, const echr_dropout* drop, const echr_batch_ext* x, int32_t* video_words,
                                                void* stream) {
     ECHR_REQUIRE(sa && drop && video_words, "decoder_sample_train_batch: null args / video_words");
     ECHR_REQUIRE(sa->multinomial, "decoder_sample_train_batch: the training-mode decode is the multinomial one (multinomial = 1)");
     RC(check_batch(&sa->dec, x, "decoder_sample_train_batch"));
     ECHR_REQUIRE(x->n_videos <= 65535, "decoder_sample_train_batch: at most 65535 videos per call (got %d)", x->n_videos);
-    {
-        BatchScope scope(x, true);
-        RC(decoder_sample_impl(sa, drop, stream, true));
-    }
+    RC(decoder_sample_impl(sa, drop, stream, dec_batch_call(x, true), true));
     return sample_video_words(reinterpret_cast<const long long*>(sa->seq), x->vid, sa->dec.N, sa->seq_len, x->n_videos, video_words,
                               (hipStream_t)stream);
 }
-static int decoder_sample_impl(const echr_sample_args* sa, const echr_dropout* drop, void* stream, bool row_step) {
+static int decoder_sample_impl(const echr_sample_args* sa, const echr_dropout* drop, void* stream, const DecCall& c, bool row_step) {
     ECHR_REQUIRE(sa, "decoder_sample: null args");
     RC(persist_check_async());
     DeterministicScope det;                    // `seq` is an index output: bitwise reproducible logits (no atomic split-K anywhere below)
@@ -2268,7 +2265,7 @@ static int decoder_sample_impl(const echr_sample_args* sa, const echr_dropout* d
     RC(check_dims(&a, "decoder_sample"));
     hipStream_t st = (hipStream_t)stream;
     const int N = a.N, H = a.H, E = a.E;
-    DecWs w = carve_ws(&a, a.ws);
+    DecWs w = carve_ws(&a, a.ws, c.bx, c.scene_rows);
     SampWs s = carve_samp(&a, sa->ws_sample);
     const DropCfg dh = make_drop(drop, drop ? drop->p_h : 0.f), dout = make_drop(drop, drop ? drop->p_out : 0.f);          // (nullptr: identity)
     const bool persistent = !sa->multinomial && !drop && sample_uses_persistent(&a);
@@ -2305,8 +2302,8 @@ static int decoder_sample_impl(const echr_sample_args* sa, const echr_dropout* d
             RC(persist_logit_image(a.w_logit, a.V1, tb.LIMG, st));
         }
         PersistSampleBufs B;
-        B.PALL = w.PALL; B.EVB0 = w.EVB0; B.VIDB = scene_base(&a, w); B.xws = s.PSX;
-        B.vidb_ld = batch_ext() ? 4L * H : 0;          // multi-video batch: the scene part of stream 2 is per event
+        B.PALL = w.PALL; B.EVB0 = w.EVB0; B.VIDB = w.scene; B.xws = s.PSX;
+        B.vidb_ld = w.scene_ld;          // multi-video batch: the scene part of stream 2 is per event
         for (int k = 0; k < 3; ++k) B.TG[k] = tb.TG[k];
         B.limg = tb.LIMG; B.sws = s.PSWS;
         B.seq = reinterpret_cast<long long*>(sa->seq); B.seq_logp = sa->seq_logp; B.n_unfinished = sa->n_unfinished;
@@ -2359,7 +2356,8 @@ extern "C" int64_t echr_beam_ws_floats(const echr_beam_args* ba) {
     a.S = ba->seq_len;
     return carve_beam(&a, ba->beam_size, nullptr).total;
 }
-extern "C" int echr_decoder_beam(const echr_beam_args* ba, void* stream) {
+// bx: the batch extension of echr_decoder_beam_batch (nullptr: one video) -- chain_step's gate products then read the per-row scene part (DecWs)
+static int decoder_beam_impl(const echr_beam_args* ba, const echr_batch_ext* bx, void* stream) {
     ECHR_REQUIRE(ba, "decoder_beam: null args");
     RC(persist_check_async());
     DeterministicScope det;                    // `seq` is an index output: bitwise reproducible logits, as the sampler's
@@ -2373,7 +2371,7 @@ extern "C" int echr_decoder_beam(const echr_beam_args* ba, void* stream) {
     RC(check_dims(&a, "decoder_beam"));
     hipStream_t st = (hipStream_t)stream;
     const int N = a.N, H = a.H, E = N / B;
-    DecWs w = carve_ws(&a, a.ws);
+    DecWs w = carve_ws(&a, a.ws, bx);
     const BeamWs bw = carve_beam(&a, B, ba->ws_beam);
     const DropCfg none = make_drop(nullptr, 0.f);
     {
@@ -2393,15 +2391,12 @@ extern "C" int echr_decoder_beam(const echr_beam_args* ba, void* stream) {
     }
     return beam_finalize(bw.b, E, L, reinterpret_cast<long long*>(ba->seq), ba->seq_logp, ba->score, ba->words, st);
 }
-// multi-video batch: the same chain with the per-row scene part published for the call (chain_step's gate products read it through
-// scene_base / batch_ext), then the per-video result widths behind beam_finalize on the same stream
+extern "C" int echr_decoder_beam(const echr_beam_args* ba, void* stream) { return decoder_beam_impl(ba, nullptr, stream); }
+// multi-video batch: the same chain called with the extension, then the per-video result widths behind beam_finalize on the same stream
 extern "C" int echr_decoder_beam_batch(const echr_beam_args* ba, const echr_batch_ext* x, int32_t* video_words, void* stream) {
     ECHR_REQUIRE(ba && video_words, "decoder_beam_batch: null args / video_words");
     RC(check_batch(&ba->dec, x, "decoder_beam_batch"));
-    {
-        BatchScope scope(x);
-        RC(echr_decoder_beam(ba, stream));
-    }
+    RC(decoder_beam_impl(ba, x, stream));
     return beam_video_words(ba->words, x->vid, ba->dec.N / ba->beam_size, ba->beam_size, x->n_videos, video_words, (hipStream_t)stream);
 }
 

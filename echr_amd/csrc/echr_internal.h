@@ -106,12 +106,24 @@ int tail_publish();
 int tsrm_position_early(const echr_tsrm_args* a, hipStream_t from);          // echr_train_step: start the event encoder's position branch right behind the index staging
 int tsrm_bwd_parts(const echr_tsrm_args* a, const echr_tsrm_grads* g, const echr_dropout* drop, void* stream, int part);
 int decoder_bwd_scratch_ahead(const echr_dec_args* a, const echr_dec_grads* g);
-// rw (optional): RewardCriterion's signed weight [N,S] for the criterion gradient formed here (the non-fused d logits; echr_train_step_rw)
-int decoder_bwd_parts(const echr_dec_args* a, const echr_dec_grads* g, const echr_dropout* drop, void* stream, int part, const float* rw = nullptr);
-// echr_decoder_bwd with that weight: the entry checks, then the whole backward pass
-int decoder_bwd_checked(const echr_dec_args* a, const echr_dec_grads* g, const echr_dropout* drop, void* stream, const float* rw);
-void handover_close();                   // stop recording; the recorded events stay valid for echr_handover_wait
-void handover_request(bool on, echr_handover_fn cb = nullptr, void* user = nullptr);          // the next decoder backward records the data-parallel hand-over events (decoder.hip)
+// What a decoder call carries beside its argument structs.  A default-constructed value is a single video, the plain criterion and no hand-over.
+//   bx: the multi-video batch extension (echr_batch_ext, below); scene_rows: the per-video scene part of stream 2's gates is formed with the
+//   single-video entry's own arithmetic (row_matvec per video) instead of one product over the V scene vectors, so a row decodes as it does alone
+//   to the bit (echr_decoder_sample_train_batch: a last-bit difference in a logit can flip a draw)
+//   rw: RewardCriterion's signed weight [N,S] in place of the NLL's mask in the criterion's numerator (echr_train_step_rw)
+//   handover (+ cb, user): this backward pass records the data-parallel hand-over events (echr_train_step_args.handover, decoder.hip)
+struct DecCall {
+    const echr_batch_ext* bx = nullptr; bool scene_rows = false;
+    const float* rw = nullptr;
+    bool handover = false; echr_handover_fn handover_cb = nullptr; void* handover_user = nullptr;
+};
+int decoder_bwd_parts(const echr_dec_args* a, const echr_dec_grads* g, const echr_dropout* drop, void* stream, int part, const DecCall& c);
+// echr_decoder_bwd as that call: the entry checks, then the whole backward pass
+int decoder_bwd_checked(const echr_dec_args* a, const echr_dec_grads* g, const echr_dropout* drop, void* stream, const DecCall& c);
+void handover_clear();                   // the hand-over points an earlier backward pass recorded are void from here on (echr_handover_wait returns 1)
+// echr_decoder_fwd_prepare / echr_tsrm_fwd as echr_train_step calls them: vid (optional) makes the event encoder's softmax block-diagonal
+int decoder_fwd_prepare(const echr_dec_args* a, const DecCall& c, void* stream);
+int tsrm_fwd_checked(const echr_tsrm_args* a, const echr_dropout* drop, void* stream, const int* vid);
 // clip contexts 'CH' / 'CC+CH' (clipctx.hip): the decoder backward's d gates1 and d P_all, the forward's attention weights WT [S,N,A]
 void decoder_bwd_views(const echr_dec_args* a, const echr_dec_grads* g, const float** dg1, const float** dpall);
 const float* decoder_fwd_wt(const echr_dec_args* a);
@@ -213,32 +225,21 @@ int vec_mat(const float* x, const float* W, long ldw, float* out, int M, int N, 
 int embed_scatter_add(const float* dX, const int* tok, float* gW, int rows, int E, int V1, hipStream_t st, const int* rowmap = nullptr);
 int logsoftmax_rows(float* X, long ld, int N, int S, int t0, int nt, int cols, hipStream_t st);
 int logsoftmax_bwd(const float* logp, const float* G, const void* target, int tgt64, const float* mask, const float* g_loss,
-                   const float* mask_sum, float* out, long ldo, int N, int S, int V1, hipStream_t st, const float* rw = nullptr);
+                   const float* mask_sum, float* out, long ldo, int N, int S, int V1, hipStream_t st, const float* rw = nullptr, bool unit_den = false);
 // log-softmax + masked NLL + d logits in one pass over the logits (echr_train_step); rows_sum turns the per-row terms into (loss, sum(mask))
 bool logsoftmax_nll_dlg_ok(int V1, long ldo);
 int logsoftmax_nll_dlg(const float* X, long ld, const void* target, int tgt64, const float* mask, const float* g_loss, float* out, long ldo,
                        float* row_loss, float* msum_out, int N, int S, int V1, hipStream_t st, const int* act = nullptr, int n_active = 0,
-                       const float* rw = nullptr);
-int nll_rows_sum(const float* row_loss, int NS, const float* msum, float* loss, hipStream_t st, bool rw = false);
+                       const float* rw = nullptr, bool unit_den = false);
+int nll_rows_sum(const float* row_loss, int NS, const float* msum, float* loss, hipStream_t st, bool rw = false, bool unit_den = false);
 // RewardCriterion's loss from log-probs [N,S,V1]: out = (sum(-logp[target] * rw) / sum(mask), sum(mask))
-int nll_loss_rw(const float* logp, const void* target, int tgt64, const float* mask, const float* rw, float* loss, int N, int S, int V1, hipStream_t st);
+int nll_loss_rw(const float* logp, const void* target, int tgt64, const float* mask, const float* rw, float* loss, int N, int S, int V1, hipStream_t st, bool unit_den);
 
-// Multi-video batches (echr_batch_ext, include/echr_hip.h).  The *_batch entry points publish their extension for the duration of the call;
-// the shared code paths read it here -- nullptr on every single-video entry, which then runs exactly what it ran before:
+// Multi-video batches (echr_batch_ext, include/echr_hip.h).  The extension is an argument of every internal function that needs it -- the
+// *_batch entry points and echr_train_step_batch* hand it down (DecCall.bx, `vid`, `unit_den`), every single-video entry passes nullptr -- so
+// what a function does is decided by what it is called with:
 //   event encoder: block-diagonal softmax by vid; decoder: per-row scene part of stream 2's gates and its segmented gradients;
-//   criterion: the weighted (rw) form with denominator 1 -- the per-video normalisers sum(mask_v) + 1e-6 arrive inside the weights
-const echr_batch_ext* batch_ext();
-struct BatchScope {
-    const echr_batch_ext* prev;
-    bool prev_rows;
-    // scene_rows: the per-video scene part of stream 2's gates is formed with the single-video entry's own arithmetic (row_matvec per video)
-    // instead of one product over the V scene vectors, so a row decodes as it does alone to the bit (echr_decoder_sample_train_batch: a
-    // last-bit difference in a logit can flip a draw)
-    explicit BatchScope(const echr_batch_ext* x, bool scene_rows = false);
-    ~BatchScope();
-};
-bool batch_scene_rows();
-inline int crit_unit_den() { return batch_ext() ? 1 : 0; }
+//   criterion: the weighted (rw) form with denominator 1 (unit_den) -- the per-video normalisers sum(mask_v) + 1e-6 arrive inside the weights
 // out[v*ld + c] = sum over the rows n with vid[n] == v of X[n*ld + c], rows added in ascending n (fixed order: bit-reproducible)
 int seg_rowsum(const float* X, const int* vid, int N, int V, int cols, long ld, float* out, hipStream_t st);
 // per-video losses of a batch: vloss[v] = sum of row_loss over the rows of video v (row i is the time-major row act[i], or i itself) ...
@@ -249,10 +250,10 @@ int decoder_fused_video_loss(const echr_dec_args* a, const echr_dec_grads* g, co
 
 // echr_decoder_fwd with the criterion fused behind the logits product: g carries nll_target / nll_mask / g_loss / ws_bwd; d logits land in ws_bwd
 // (echr_dec_grads.dlg_ready = 1 for the echr_decoder_bwd that follows); returns through *fused whether the fused form applied
-// rw (optional): echr_train_step_rw's signed criterion weight [N,S] (RewardCriterion) in place of the NLL's mask in the numerator
+// (g = fused = compact = nullptr: echr_decoder_fwd itself, as the call `c`)
 int decoder_fwd_fused(const echr_dec_args* a, const echr_dec_grads* g, const echr_dropout* drop, void* stream, bool* fused, bool* compact,
-                      const float* rw = nullptr);
-int decoder_fused_loss(const echr_dec_args* a, const echr_dec_grads* g, float* loss, hipStream_t st, bool rw = false);
+                      const DecCall& c);
+int decoder_fused_loss(const echr_dec_args* a, const echr_dec_grads* g, float* loss, hipStream_t st, bool rw, bool unit_den);
 int sample_step(const float* logits, long ld, int N, int V1, int t, int seq_len, int* it_next, int* unfinished, long long* seq,
                 float* seq_logp, int* n_unfinished, float temperature, unsigned long long seed, hipStream_t st);
 // the multinomial step with the row on chip (echr_decoder_sample_train_batch): sample_step's draw, bit for bit, with the slab sum folded in

@@ -251,11 +251,11 @@ static void step_timing_end() {
 
 // joint mode: the helper streams' work of one call
 struct JointPending { echr_dec_args d; echr_dec_grads g; echr_tsrm_args t; echr_tsrm_grads tg; echr_dropout drop; echr_train_step_args args;
-                      const float* crit_w; };          // (crit_w: echr_train_step_rw's criterion weight, nullptr for the NLL)
+                      DecCall call; };          // (call: the decoder call of the first piece -- echr_train_step_rw's criterion weight; one video, no hand-over)
 // every parameter gradient (decoder: helper streams forked from `src`; event encoder: behind them on the prepare stream), then clamp + Adam on
 // the tail stream, published for echr_stream_join
 static int joint_finish(JointPending& jp, hipStream_t src) {
-    RC(decoder_bwd_parts(&jp.d, &jp.g, &jp.drop, src, 2, jp.crit_w));
+    RC(decoder_bwd_parts(&jp.d, &jp.g, &jp.drop, src, 2, jp.call));
     hipStream_t s2 = aux2_stream();
     RC(tsrm_bwd_parts(&jp.t, &jp.tg, &jp.drop, s2, 2));
     hipStream_t ts = helpers_merge_to_tail();
@@ -333,8 +333,8 @@ extern "C" int64_t echr_train_step_rw_ws_floats(const echr_train_step_args* a) {
 extern "C" int echr_train_step_rw(const echr_train_step_args* a, const float* weight, void* stream) { return train_step_impl(rw_call(a, weight), stream); }
 // Multi-video batch (include/echr_hip.h): the same iteration over the events of V videos.  What differs sits in the pieces the call sequences --
 // per-video scene vectors and their segmented gradients (decoder.hip), the block-diagonal event encoder (tsrm.hip), the criterion's
-// per-video normalisers inside the weights (core.hip) -- which read the extension published here; this file stages vid with
-// the other index vectors and adds the per-video losses.  Stage-ahead, the applied-update count and the asynchronous failure reports are
+// per-video normalisers inside the weights (core.hip) -- which are handed the extension as an argument (DecCall.bx, vid, unit_den); this file
+// stages vid with the other index vectors and adds the per-video losses.  Stage-ahead, the applied-update count and the asynchronous failure reports are
 // those of echr_train_step: the same code runs.
 extern "C" int64_t echr_train_step_batch_ws_floats(const echr_train_step_args* a, const echr_batch_ext* x) {
     return (a && x && x->n_videos > 0) ? carve_step(batch_call(a, x)).total : -1;
@@ -417,8 +417,8 @@ static int train_step_impl(const StepCall& c, void* stream) {
         RC(prep_stream_wait(sa.post));
         if (hipStreamWaitEvent(st, ring_last(), 0) != hipSuccess) { set_error("train_step: stream wait failed"); return -5; }
     } else if (!a->prepared) RC(stage_indices(a->host_index, idx, sizeof(int32_t) * step_index_count(c), st));
-    // multi-video batch: vid is the tail of the staged index region, the batch scratch a piece of `ws`; everything below reads the extension
-    // through batch_ext()
+    // multi-video batch: vid is the tail of the staged index region, the batch scratch a piece of `ws`; everything below that needs the
+    // extension is called with it (dc.bx, bxl.vid, unit_den)
     echr_batch_ext bxl;
     if (bx) {
         bxl = *bx;
@@ -426,7 +426,6 @@ static int train_step_impl(const StepCall& c, void* stream) {
         bxl.ws = ws + L.batch;
         if (vh) bxl.g_video = ws + L.g_video;          // [V, Dv]: the batched decoder backward writes d video per video (its spans go into g_tap)
     }
-    BatchScope scope(bx ? &bxl : nullptr);
     const int32_t *ev_start = idx, *ev_len = idx + N, *ind = idx + 2 * N, *active = idx + (3 + S) * N;          // (tokens at idx + 3 N: step_dec_args)
     const void* nll_target = a->nll_target;
     const float* nll_mask = a->nll_mask;
@@ -439,6 +438,9 @@ static int train_step_impl(const StepCall& c, void* stream) {
         if (rw) crit_w = reinterpret_cast<const float*>(active + a->n_active + 2 * (size_t)S * N);
     }
     ECHR_REQUIRE(nll_target && nll_mask, "train_step: criterion targets / mask missing");
+    DecCall dc;          // the decoder call of this iteration; the backward adds the hand-over request
+    dc.bx = bx ? &bxl : nullptr; dc.rw = crit_w;
+    const bool unit_den = bx != nullptr;          // a batch: the per-video normalisers arrive inside the criterion weights
 
     echr_dec_args d = step_dec_args(a, L, idx);
     if (x) d.c3d = x->clip_parts == 3 ? ws + L.rows : a->tap;
@@ -450,7 +452,7 @@ static int train_step_impl(const StepCall& c, void* stream) {
     if (a->overlap_encoder && !a->prepared) {
         fork_event(ring_last());          // both forks hang off the staging copy's event: no further record in front of event pooling
         int rc2 = direct ? 0 : tsrm_position_early(&t, st);          // (no encoder, no position branch)
-        if (!rc2) rc2 = echr_decoder_fwd_prepare(&d, stream);
+        if (!rc2) rc2 = decoder_fwd_prepare(&d, dc, stream);
         fork_event(nullptr);
         if (rc2) {
             // the position branch may already be queued on the tail stream: forget it (a later echr_tsrm_fwd on this workspace must not take the
@@ -464,7 +466,7 @@ static int train_step_impl(const StepCall& c, void* stream) {
     }
     // (event_direct: the pooled rows / the anchors' states are the event vectors themselves, :131-137)
     int rc = echr_event_pool_gather_fwd(c3d, a->tap, ev_start, ev_len, ind, ws + (direct ? L.event : L.ech), N, De_c3d, De_tap, stream);       // :106-128
-    if (!rc && !direct) rc = echr_tsrm_fwd(&t, &a->drop, stream);                                                            // :129
+    if (!rc && !direct) rc = tsrm_fwd_checked(&t, &a->drop, stream, bx ? bxl.vid : nullptr);          // :129
     if (rc) { (void)tsrm_position_early(nullptr, nullptr); if (a->overlap_encoder) (void)echr_decoder_fwd_prepare_cancel(stream); return rc; }
     d.event = ws + L.event; d.prepared = a->overlap_encoder ? 1 : 0;
     // OldModel.init_hidden with CG_init_feats_type (OldModel_NEW.py:72-96): h(-1) = c(-1) = init_linear(cat(selected contexts))
@@ -492,9 +494,9 @@ static int train_step_impl(const StepCall& c, void* stream) {
     // logits (d logits land in the backward workspace, the log-probs are never written; the loss is summed behind the backward pass, where
     // this stream waits for the helper stream anyway).  forward_only: the plain log-softmax + criterion, loss[0] = loss, loss[1] = sum(mask)
     bool fused_nll = false, compact = false;
-    if (a->forward_only) RC(echr_decoder_fwd(&d, &a->drop, stream));
-    else RC(decoder_fwd_fused(&d, &g, &a->drop, stream, &fused_nll, &compact, crit_w));          // (crit_w nullptr: LanguageModelCriterion)
-    if (!fused_nll && crit_w) RC(nll_loss_rw(d.logp, nll_target, nll_i64, nll_mask, crit_w, a->loss, N, S, d.V1, st));
+    if (a->forward_only) RC(decoder_fwd_fused(&d, nullptr, &a->drop, stream, nullptr, nullptr, dc));
+    else RC(decoder_fwd_fused(&d, &g, &a->drop, stream, &fused_nll, &compact, dc));          // (dc.rw nullptr: LanguageModelCriterion)
+    if (!fused_nll && crit_w) RC(nll_loss_rw(d.logp, nll_target, nll_i64, nll_mask, crit_w, a->loss, N, S, d.V1, st, unit_den));
     else if (!fused_nll) {
         if (nll_i64) RC(echr_nll_loss_fwd_i64(d.logp, static_cast<const int64_t*>(nll_target), nll_mask, a->loss, N, S, d.V1, stream));
         else RC(echr_nll_loss_fwd(d.logp, static_cast<const int32_t*>(nll_target), nll_mask, a->loss, N, S, d.V1, stream));
@@ -509,33 +511,33 @@ static int train_step_impl(const StepCall& c, void* stream) {
 
     // backward (train.py:313): criterion gradient in fused form
     g.zero_extra = nullptr; g.zero_extra_count = 0;
-    handover_request(false);          // (hand-over points of an earlier call are void from here on)
+    handover_clear();          // (hand-over points of an earlier call are void from here on)
     if (a->defer_update && a->g_tap && a->do_step && g.async_tail == 2 && fused_nll && config().gemm_h2 && helpers_available() && !vh && !a->w_init && !x && !direct) {
         // Joint 'tap_cg' iteration (train.py:300-313): the proposal encoder's backward -- a 64-workgroup persistent launch that leaves three
         // quarters of the chip idle -- waits for d tap_feats alone.  The chain that leads to it (late fusion, reverse recurrence, d event,
         // the event encoder's attention backward, d ech) runs first and alone on the caller's stream; every parameter gradient and the
         // clamp + Adam update follow on the helper streams, forked behind it, and are NOT joined here: they overlap whatever the caller
         // queues next.  echr_stream_join (and the next echr_train_step / decoder call) waits for them.
+        ECHR_REQUIRE(!bx, "train_step: the deferred update is not part of the batched step");          // (R_BATCHED refuses defer_update: one video from here on)
         echr_tsrm_grads tg = a->tsrm_g;
         tg.g_ech = ws + L.g_ech; tg.g_out = ws + L.g_event; tg.ws_bwd = ws + L.tsrm_ws_bwd; tg.zeroed = 1;
-        RC(decoder_bwd_parts(&d, &g, &a->drop, stream, 1, crit_w));
+        RC(decoder_bwd_parts(&d, &g, &a->drop, stream, 1, dc));
         RC(tsrm_bwd_parts(&t, &tg, &a->drop, stream, 1));
         if (De_tap > 0) RC(echr_event_pool_gather_bwd(ws + L.g_ech, ind, a->g_tap, N, De_c3d, De_tap, stream));
-        RC(decoder_fused_loss(&d, &g, a->loss, st, crit_w != nullptr));
+        RC(decoder_fused_loss(&d, &g, a->loss, st, crit_w != nullptr, unit_den));
         // the caller's hook: the proposal encoder's backward (+ update) goes onto `stream` HERE, right behind g_tap; the helper streams fork
         // behind it (joint_finish), so the chip-filling tail never shares CUs with that 64-workgroup latency chain
         if (a->mid_cb) a->mid_cb(stream, a->mid_user);
         JointPending jp;
-        jp.d = d; jp.g = g; jp.t = t; jp.tg = tg; jp.drop = a->drop; jp.args = *a; jp.crit_w = crit_w;
+        jp.d = d; jp.g = g; jp.t = t; jp.tg = tg; jp.drop = a->drop; jp.args = *a; jp.call = dc;
         // (issuing the helper work only after the caller has queued the proposal encoder's backward -- a second entry point, tried -- is worse:
         // 3.21 vs 3.00 ms on c5.  The host needs ~0.5 ms to get from here to that launch anyway, the helpers fill exactly that gap, and a
         // persistent recurrence that shares its CUs with GEMM workgroups from its first step on loses more than the gap is worth)
         return joint_finish(jp, st);
     }
-    handover_request(a->handover && !a->do_step, a->handover_cb, a->handover_user);
-    rc = decoder_bwd_checked(&d, &g, &a->drop, stream, crit_w);
-    handover_close();          // (the events stay valid for echr_handover_wait; later backward passes do not re-record them)
-    RC(rc);
+    // (the hand-over request is part of THIS backward pass: its events stay valid for echr_handover_wait, later backward passes record none)
+    dc.handover = a->handover && !a->do_step; dc.handover_cb = a->handover_cb; dc.handover_user = a->handover_user;
+    RC(decoder_bwd_checked(&d, &g, &a->drop, stream, dc));
     step_mark(2, st);
     if (a->w_init) {
         // d h0 -> init_linear's gradients, d event (ADDED to what the decoder left there, ahead of the event encoder's backward), d video
@@ -561,7 +563,7 @@ static int train_step_impl(const StepCall& c, void* stream) {
         RC(echr_tsrm_bwd(&t, &tg, &a->drop, stream));
         if (a->g_tap && De_tap > 0) RC(echr_event_pool_gather_bwd(ws + L.g_ech, ind, a->g_tap, N, De_c3d, De_tap, stream));
     }
-    if (fused_nll) RC(decoder_fused_loss(&d, &g, a->loss, st, crit_w != nullptr));
+    if (fused_nll) RC(decoder_fused_loss(&d, &g, a->loss, st, crit_w != nullptr, unit_den));
     if (fused_nll && bx && video_loss) RC(decoder_fused_video_loss(&d, &g, bxl.vid, bxl.n_videos, video_loss, st));
     step_mark(3, st);
     RC(echr_stream_join(stream));          // the decoder backward's asynchronous tail: every gradient is final in `stream` order now

@@ -662,24 +662,24 @@ extern "C" int echr_tsrm_posemb(const int32_t* ev_start, const int32_t* ev_len, 
     return posemb(ev_start, ev_len, pos, N, Df, (hipStream_t)stream);
 }
 
-static int tsrm_fwd_impl(const echr_tsrm_args* a, const echr_dropout* drop, void* stream, const float* x_given, const float* pos_given);
+// vid (optional, [N]): a multi-video batch -- the softmax is block-diagonal by video; nullptr is one video
+static int tsrm_fwd_impl(const echr_tsrm_args* a, const echr_dropout* drop, void* stream, const float* x_given, const float* pos_given, const int* vid);
 
-extern "C" int echr_tsrm_fwd(const echr_tsrm_args* a, const echr_dropout* drop, void* stream) {
+int echr::tsrm_fwd_checked(const echr_tsrm_args* a, const echr_dropout* drop, void* stream, const int* vid) {
     RC(check(a, "tsrm_fwd"));
-    return tsrm_fwd_impl(a, drop, stream, nullptr, nullptr);
+    return tsrm_fwd_impl(a, drop, stream, nullptr, nullptr, vid);
 }
+extern "C" int echr_tsrm_fwd(const echr_tsrm_args* a, const echr_dropout* drop, void* stream) { return tsrm_fwd_checked(a, drop, stream, nullptr); }
 static int check_batch_ext(const echr_batch_ext* x, const char* who) {
     ECHR_REQUIRE(x && x->n_videos > 0 && x->vid, "%s: the batch extension needs n_videos > 0 and vid", who);
     return 0;
 }
 extern "C" int echr_tsrm_fwd_batch(const echr_tsrm_args* a, const echr_dropout* drop, const echr_batch_ext* x, void* stream) {
     RC(check_batch_ext(x, "tsrm_fwd_batch"));
-    BatchScope scope(x);
-    return echr_tsrm_fwd(a, drop, stream);
+    return tsrm_fwd_checked(a, drop, stream, x->vid);
 }
 extern "C" int echr_tsrm_bwd_batch(const echr_tsrm_args* a, const echr_tsrm_grads* g, const echr_dropout* drop, const echr_batch_ext* x, void* stream) {
-    RC(check_batch_ext(x, "tsrm_bwd_batch"));
-    BatchScope scope(x);          // (nothing in the backward reads it: the saved weights of cross-video pairs are 0, see tsrm_softmax_fwd_kernel)
+    RC(check_batch_ext(x, "tsrm_bwd_batch"));          // (nothing in the backward reads it: the saved weights of cross-video pairs are 0, see tsrm_softmax_fwd_kernel)
     return echr_tsrm_bwd(a, g, drop, stream);
 }
 
@@ -689,7 +689,7 @@ extern "C" int echr_tsrm_attn_fwd(const echr_tsrm_args* a, const float* roi_feat
     ECHR_REQUIRE(a && roi_feat && pos_emb, "tsrm_attn_fwd: null arguments");
     ECHR_REQUIRE(a->N > 0 && a->Df > 0 && a->Do > 0 && a->G > 0 && a->Df % a->G == 0 && a->Do % a->G == 0 && a->Df % 4 == 0, "tsrm_attn_fwd: bad dims");
     ECHR_REQUIRE(a->ws && a->out, "tsrm_attn_fwd: missing buffers");
-    return tsrm_fwd_impl(a, drop, stream, roi_feat, pos_emb);
+    return tsrm_fwd_impl(a, drop, stream, roi_feat, pos_emb, nullptr);
 }
 
 // the dense position branch (:39-41, :108-116): pair embedding -> fc1 (+ tanh) -> fc2 gates, on stream sp.  Independent of the event features.
@@ -760,7 +760,7 @@ int echr::tsrm_position_early(const echr_tsrm_args* a, hipStream_t from) {
     return 0;
 }
 
-static int tsrm_fwd_impl(const echr_tsrm_args* a, const echr_dropout* drop, void* stream, const float* x_given, const float* pos_given) {
+static int tsrm_fwd_impl(const echr_tsrm_args* a, const echr_dropout* drop, void* stream, const float* x_given, const float* pos_given, const int* vid) {
     hipStream_t st = (hipStream_t)stream;
     const int N = a->N, Din = a->Din, Df = a->Df, Do = a->Do, G = a->G;
     const int NN = N * N, dgq = Df / G, dgo = Do / G;
@@ -841,7 +841,6 @@ static int tsrm_fwd_impl(const echr_tsrm_args* a, const echr_dropout* drop, void
         else for (int i = 0; i < 3; ++i) RC(gemm(q3[i], st));
     }
     const DropCfg dc = make_drop(drop, drop ? drop->p_tsrm : 0.f);
-    const int* vid = batch_ext() ? batch_ext()->vid : nullptr;          // multi-video batch: block-diagonal softmax
     if (head_fused_ok(N, Df, Do, G)) {
         // few events: affinities, gated softmax, dropout and the weighted sum in one launch, one wave per (event, head) (:138-160)
         if (fork) RC(aux_join(st));

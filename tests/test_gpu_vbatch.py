@@ -402,3 +402,59 @@ def test_cross_video_isolation_is_bitwise():
             assert not np.array_equal(a[s], c[s])
         else:
             assert np.array_equal(a[s], c[s]), v
+
+
+def test_call_order_does_not_matter():
+    """Nothing of one call survives into the next: six calls on 'vbctx' (5 videos incl. a one-event video, 'VLVCVH' scene vectors), computed
+    once and then again in another order, every result bit-equal to its first value -- a single-video call behind a batched one runs as a
+    single-video call, a batched one behind the per-row scene form (sample_train_batch) as the plain batched one, and so on.
+    (a) eval forward of video 0, single-video entry; (b) eval forward of the batch; (c) greedy decode of the batch; (d) sample_train_batch,
+    fixed seed and dropout state; (e) greedy decode of video 0; (f) the gradient arena of FusedTrainStep.batch(step=False).
+    The decode chains are bitwise reproducible by construction, but the event encoder in front of them, the teacher-forced forward and the
+    backward sum with atomics in the default mode: the whole test runs in the fixed-order mode, where two runs on the same inputs agree bit for
+    bit (the rule of test_cross_video_isolation_is_bitwise; the greedy decodes take the same persistent launches in either mode)."""
+    import echr_amd
+    from echr_amd import functional as EF
+    opt, params, vids = synth.make_vbatch('vbctx')
+    m, o, f = _fused(opt, params, False)
+    b, _ = _batch(vids)
+    dev = torch.device('cuda')
+    v0 = vids[0]
+    tap, c3d, lda = (torch.from_numpy(v0[k]).to(dev) for k in ('tap', 'c3d', 'lda'))
+    one = (tap, c3d, lda, torch.from_numpy(v0['labels']), v0['ind'], v0['soi'])
+    lm = m.lm_model
+
+    def host(xs):
+        torch.cuda.synchronize()
+        xs = xs if isinstance(xs, (tuple, list)) else (xs,)
+        return tuple(x.detach().cpu().numpy().copy() if isinstance(x, torch.Tensor) else np.asarray(x).copy() for x in xs)
+
+    def no_grad(fn):
+        with torch.no_grad():
+            return host(fn())
+
+    def grad_arena():
+        loss = f.batch(b, step=False)
+        return host((loss, f.last_video_losses, m._echr_arena.flat_g))
+
+    echr_amd.set_deterministic(True)
+    try:
+        with torch.no_grad():
+            video, event, ev_start, ev_len, A, vid, drop = m._batch_contexts(b, None)
+        drop.training = True          # (the sampled pass of training: the decoder's dropout under this one state, every time)
+        sample_args = (video, event, b.clip_rows(), ev_start, ev_len, vid, A, lm.seq_length, lm.native_params(), drop)
+        calls = {'a': lambda: no_grad(lambda: m(*one, mode='train')),
+                 'b': lambda: no_grad(lambda: m.forward_batch(b, mode='train')),
+                 'c': lambda: no_grad(lambda: m.forward_batch(b, mode='eval')),
+                 'd': lambda: no_grad(lambda: EF.sample_train_batch(*sample_args, seed=1234)),
+                 'e': lambda: no_grad(lambda: m(*one, mode='eval')),
+                 'f': grad_arena}
+        first = {k: calls[k]() for k in 'abcdef'}
+        assert first['c'][0].any() and first['d'][0].any() and first['e'][0].any() and first['f'][2].any()
+        for k in 'dafecba':
+            again = calls[k]()
+            assert len(again) == len(first[k])
+            for i, (x, y) in enumerate(zip(first[k], again)):
+                assert x.shape == y.shape and x.dtype == y.dtype and np.array_equal(x, y), (k, i)
+    finally:
+        echr_amd.set_deterministic(False)
