@@ -76,10 +76,20 @@ class CaptionGenerator(nn.Module):
                                       "tap_feats through the clip context) are a follow-up" % (self.opt.clip_context_type,))
 
     def _require_three_stream(self, what):
-        """Entries that only the three-stream decoder has (batches, beam search, self-critical training, the fused steps)."""
+        """Entries that only the three-stream decoder has (beam search, self-critical training, the fused steps)."""
         if self.one_stream():
-            self.lm_model._refuse('%s runs on the three_stream decoder; the one-stream decoder takes one video per call through '
-                                  "forward(mode='train' / 'eval')" % what)
+            self.lm_model._refuse("%s runs on the three_stream decoder; the one-stream decoder runs forward(mode='train' / 'eval') and "
+                                  "forward_batch(mode='train' / 'eval')" % what)
+
+    def _check_batch_decoder(self, batch, what):
+        """A batch is built for one decoder (VideoBatch(..., caption_model=)): a one-stream model refuses a plain (or missing) batch with a
+        NotImplementedError that names the keyword, a three-stream model refuses a one-stream batch with a ValueError."""
+        built = bool(getattr(batch, 'one_stream', False))
+        if self.one_stream() and not built:
+            self.lm_model._refuse("%s takes a batch built for this decoder -- VideoBatch.from_videos(..., caption_model='show_attend_tell'): a "
+                                  "plain batch is the three_stream decoder's" % what)
+        if built and not self.one_stream():
+            raise ValueError("the batch was built for caption_model='show_attend_tell', the model has %r" % (self.opt.caption_model,))
 
     def build_arena(self):
         """Pack parameters and gradients into flat device buffers (echr_amd/arena.py).  Call after .cuda(); enables the
@@ -153,8 +163,11 @@ class CaptionGenerator(nn.Module):
         pair MLP of large inference calls).  The greedy decode stays ONE call over all rows.  The training backward is not grouped.
         With event_context_type 'EC' / 'EH' there is no event encoder: `event_group_rows` is accepted and has no effect (it only bounds the
         encoder's pair work), here and in beam_batch.
-        `beam_size` stays 1 here: beam search over a batch is `beam_batch`."""
-        self._require_three_stream('forward_batch (a multi-video batch)')
+        `beam_size` stays 1 here: beam search over a batch is `beam_batch`.
+        With caption_model='show_attend_tell' the batch must have been built for the one-stream decoder (VideoBatch.from_videos(...,
+        caption_model='show_attend_tell')): both modes then run echr_amd.sat's batched entries (SatBatchFunction, sat_greedy_sample(vid=))
+        with the same contexts, edges and `event_group_rows`; beam_batch, train_rl_batch and the fused steps stay the three-stream decoder's."""
+        self._check_batch_decoder(batch, 'forward_batch (a multi-video batch)')
         if mode == 'train_rl':
             raise NotImplementedError("mode='train_rl' takes one video per call: self-critical training over a batch is "
                                       "train_rl_batch(batch) (one call: fused.SelfCriticalBatchStep)")
@@ -171,6 +184,11 @@ class CaptionGenerator(nn.Module):
         disjoint = EF.rows_disjoint(batch.soi)
         if mode == 'eval':
             with torch.no_grad():
+                if self.one_stream():
+                    from . import sat
+                    return sat.sat_greedy_sample(video, event, batch.c3d, ev_start, ev_len, A, lm.seq_length, lm.native_params(), lm._require_live(),
+                                                 h0=self._batch_initial_state(batch, video, event, ev_start, ev_len, vid),
+                                                 vid=sat.BatchVid(batch.vid, batch.n_videos, dev=vid))
                 return EF.greedy_sample(video, event, batch.clip_rows(), ev_start, ev_len, A, lm.seq_length, lm.native_params(),
                                         table_cache=lm.sample_tables(), vid=vid,
                                         h0=self._batch_initial_state(batch, video, event, ev_start, ev_len, vid))
@@ -185,11 +203,15 @@ class CaptionGenerator(nn.Module):
         first column in the row source: the row source carries no graph, the decoder's backward returns d tap itself (as ClipView.grad_src /
         grad_col0 arrange for one video)."""
         ps = self.lm_model.native_params()
+        if self.one_stream():          # (sat.SatBatchFunction: 'CC' rows only, the batch was refused otherwise when it was built)
+            from . import sat
+            return sat.SatBatchFunction.apply(video, event, batch.c3d, ev_start, ev_len, tokens, A, disjoint, drop, self.lm_model._grad_sink(ps),
+                                              h0, self.lm_model._require_live(), sat.BatchVid(batch.vid, batch.n_videos, dev=vid), *ps)
         return EF.DecoderFunction.apply(video, event, batch.clip_rows(), ev_start, ev_len, tokens, A, disjoint, drop, self.lm_model._grad_sink(ps),
                                         None, h0, batch.tap if batch.clip_parts > 1 else None, int(batch.clip_col0), vid, *ps)
 
     def _batch_initial_state(self, batch, video, event, ev_start, ev_len, vid):
-        """None (the recipe: zero state) or h0 [N_tot, 3H] of CG_init_feats_type over a batch (functional.InitState with vid): every event from
+        """None (the recipe: zero state) or h0 [N_tot, 3H] ([N_tot, H] for the one-stream decoder) of CG_init_feats_type over a batch (functional.InitState with vid): every event from
         its own video's scene vector, its event context and its clip mean over its own video's padded clip length.  The clip mean reads
         C3D rows only (the constructor refuses 'C' with 'CH' rows)."""
         lm = self.lm_model
@@ -202,7 +224,7 @@ class CaptionGenerator(nn.Module):
     def _batch_contexts(self, batch, groups, need_labels=False):
         """What forward_batch and beam_batch hand to the decoder: the checks of a batched call, then (video [V, Dv], event [N_tot, d_o],
         ev_start, ev_len, A, vid, drop) -- the scene vectors, and the event encoder as one block-diagonal call or once per run of `groups`."""
-        self._require_three_stream('a multi-video batch (VideoBatch)')
+        self._check_batch_decoder(batch, 'a multi-video batch (VideoBatch)')
         self._check_batch_options(batch)
         self._require_live_decoder()
         if not batch.c3d.is_cuda:

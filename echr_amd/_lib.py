@@ -278,6 +278,10 @@ SYMBOLS = [
     ('echr_sat_step', i32, [C.POINTER(SatArgs), c_f, c_f, c_f, c_f, C.POINTER(Dropout), C.c_void_p]),
     ('echr_sat_sampler_ws_floats', i64, [C.POINTER(SatArgs)]),
     ('echr_sat_sample', i32, [C.POINTER(SatSampleArgs), C.c_void_p]),
+    ('echr_sat_batch_ws_floats', i64, [i32, i32, i32]),
+    ('echr_sat_fwd_batch', i32, [C.POINTER(SatArgs), C.POINTER(Dropout), C.POINTER(BatchExt), C.c_void_p]),
+    ('echr_sat_bwd_batch', i32, [C.POINTER(SatArgs), C.POINTER(SatGrads), C.POINTER(Dropout), C.POINTER(BatchExt), C.c_void_p]),
+    ('echr_sat_sample_batch', i32, [C.POINTER(SatSampleArgs), C.POINTER(BatchExt), C.c_void_p]),
 ]
 
 ABI_STRUCTS = {'echr_gemm_desc': GemmDesc, 'echr_dropout': Dropout, 'echr_tsrm_args': TsrmArgs, 'echr_tsrm_grads': TsrmGrads,

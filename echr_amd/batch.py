@@ -15,7 +15,9 @@ A batch is built for ONE frame-level context (`clip_context_type`, default 'CC')
 `clip_rows()` -- tap, or [c3d | tap] -- and d tap gains the attended rows' gradient; the entry points refuse a batch built for another
 context than the model's.  Likewise a batch is built for the model's initial decoder state (`CG_init_feats_type`, default '': zeros):
 with 'V' / 'E' / 'C' every event starts from init_linear over its OWN video's scene vector, its event context and its clip mean over
-its own video's padded clip length.
+its own video's padded clip length.  And a batch is built for ONE decoder (`caption_model`, default the three-stream recipe's):
+`caption_model='show_attend_tell'` is the one-stream decoder of echr_amd.sat, which attends over the C3D rows only -- such a batch
+refuses 'CH' rows when it is built, a three-stream model refuses it, and a one-stream model refuses a batch built without the keyword.
 """
 import numpy as np
 import torch
@@ -72,6 +74,18 @@ def sampled_criterion(gen, reward, widths, slices, form='batch'):
     return caption_labels(g), mask, w
 
 
+def _check_decoder(caption_model, clip_context_type):
+    """True for a batch of the one-stream decoder (caption_model='show_attend_tell'), False for the three-stream one (None or a
+    'three_stream' name); refuses what the named decoder cannot take."""
+    one_stream = caption_model == 'show_attend_tell'
+    if caption_model is not None and not one_stream and 'three_stream' not in caption_model:
+        raise ValueError("caption_model=%r: a batch is built for the three_stream decoder (the default) or 'show_attend_tell'" % (caption_model,))
+    if one_stream and 'CH' in clip_context_type:
+        raise NotImplementedError("caption_model='show_attend_tell' with clip_context_type=%r: the one-stream decoder attends over the C3D rows "
+                                  "('CC'); 'CH' rows (the gradient into tap_feats through the clip context) are a follow-up" % (clip_context_type,))
+    return one_stream
+
+
 class VideoBatch(object):
     """V >= 1 videos as one batch.  Build it with `from_videos`.
 
@@ -89,13 +103,17 @@ class VideoBatch(object):
       clip_context_type, clip_parts     the frame-level context the batch was built for: 1 = 'CC' (default), 2 = 'CH', 3 = 'CC+CH';
                                         clip_rows() is the decoder's row source -- c3d, tap or [c3d | tap]
       CG_init_feats_type                the initial decoder state the batch was built for ('' = zeros, else from 'V', 'E', 'C')
+      caption_model, one_stream         the decoder the batch was built for: None (the three-stream recipe) or 'show_attend_tell'
       refs                              optional, set by the caller: the packed references of the N_tot events in row order
                                         (echr_amd.reward.pack_refs) -- what fused.SelfCriticalBatchStep scores a CiderDReward against
     """
 
-    def __init__(self, c3d, tap, lda, row_offset, event_offset, soi, ind, labels=None, masks=None, *, CG_init_feats_type='', clip_context_type='CC'):
+    def __init__(self, c3d, tap, lda, row_offset, event_offset, soi, ind, labels=None, masks=None, *, caption_model=None, CG_init_feats_type='',
+                 clip_context_type='CC'):
         self.c3d, self.tap, self.lda = c3d, tap, lda
         self.refs = None
+        self.caption_model = caption_model
+        self.one_stream = _check_decoder(caption_model, clip_context_type)
         self.CG_init_feats_type = str(CG_init_feats_type or '')
         if set(self.CG_init_feats_type) - set('VEC') or len(set(self.CG_init_feats_type)) != len(self.CG_init_feats_type):
             raise ValueError("CG_init_feats_type=%r: the initial state reads 'V', 'E' and / or 'C', each at most once" % (CG_init_feats_type,))
@@ -121,7 +139,7 @@ class VideoBatch(object):
 
     # ---- construction -------------------------------------------------------------------------------------------------------
     @classmethod
-    def from_videos(cls, videos, device=None, tap_model=None, tap_fn=None, *, CG_init_feats_type='', clip_context_type='CC'):
+    def from_videos(cls, videos, device=None, tap_model=None, tap_fn=None, *, caption_model=None, CG_init_feats_type='', clip_context_type='CC'):
         """`videos`: a list of dicts with the arguments of a single-video call -- 'c3d' [T, D], 'tap' [T', Ht], 'lda' [lda_dim], 'ind' [N_v],
         'soi' [N_v, 2] (indices local to the video) and, for training, 'labels' / 'masks' [N_v, L_v] -- or a dict of parallel lists under
         the same keys.  Features may be numpy arrays or tensors on any device; they are concatenated on `device` (default: the device of
@@ -132,8 +150,10 @@ class VideoBatch(object):
         offsets (fused.JointBatchStep runs the encoder into its own buffers, without a graph).
         `clip_context_type`: the model's frame-level context ('CC', 'CH', 'CC+CH'); the batched entry points refuse a batch built for
         another one.
-        `CG_init_feats_type`: the model's initial decoder state ('' = zeros; else from 'V', 'E', 'C'), under the same rule.  Both
-        options are keyword-only."""
+        `CG_init_feats_type`: the model's initial decoder state ('' = zeros; else from 'V', 'E', 'C'), under the same rule.
+        `caption_model`: the model's decoder -- None / a 'three_stream' name (the default) or 'show_attend_tell' (the one-stream decoder,
+        'CC' rows only), under the same rule.  The three options are keyword-only."""
+        _check_decoder(caption_model, clip_context_type)          # (ahead of any tensor work)
         if isinstance(videos, dict):
             n = len(videos['c3d'])
             videos = [{k: v[i] for k, v in videos.items()} for i in range(n)]
@@ -193,7 +213,7 @@ class VideoBatch(object):
         else:
             tap_all = torch.cat(taps, 0) if tap_model is None else tap_model.forward_batch(c3d_all, rows)[0]
         return cls(c3d_all, tap_all, torch.stack(ldas, 0), rows, counts, np.concatenate(sois, 0), np.concatenate(inds, 0),
-                   labels, masks, clip_context_type=clip_context_type, CG_init_feats_type=CG_init_feats_type)
+                   labels, masks, clip_context_type=clip_context_type, CG_init_feats_type=CG_init_feats_type, caption_model=caption_model)
 
     @staticmethod
     def _stack_labels(videos, counts):

@@ -317,18 +317,43 @@ static SatWsB sat_carve_bwd(const echr_sat_args* a, float* base) {
     return w;
 }
 
-static int sat_check(const echr_sat_args* a, const char* who) {
+// Multi-video batches: the caller's scratch echr_batch_ext.ws = VIDV [V, 4H] (scene part of the gates per video) | VIDB [N, 4H] (gathered by vid:
+// per event) | DGSEG [V, 4H] (d gates summed over time and over the events of a video)
+struct SatBatchWs { float *VIDV, *VIDB, *DGSEG; long total; };
+static SatBatchWs sat_carve_batch(long N, long V, long H, float* base) {
+    SatBatchWs w;
+    long off = 0;
+    auto take = [&](long n) { float* p = base ? base + off : nullptr; off += srup(n, 64); return p; };
+    w.VIDV = take(V * 4 * H); w.VIDB = take(N * 4 * H); w.DGSEG = take(V * 4 * H);
+    w.total = off;
+    return w;
+}
+
+// bx: a multi-video batch -- a->video is not read then ('V' needs bx->video [V, Dv])
+static int sat_check(const echr_sat_args* a, const char* who, const echr_batch_ext* bx = nullptr) {
     ECHR_REQUIRE(a, "%s: null args", who);
     ECHR_REQUIRE(a->N > 0 && a->A > 0 && a->Tv > 0 && a->S >= 0, "%s: bad N/A/Tv/S", who);
     ECHR_REQUIRE((a->feats & 7) != 0 && (a->feats & ~7) == 0, "%s: feats must select at least one of V (1), E (2), C (4): got %d (the reference fails on "
                  "an empty CG_input_feats_type too)", who, a->feats);
     SRC(att_check_dims(AttShape{a->N, a->A, a->Ha, a->D}, who));
     ECHR_REQUIRE(a->H > 0 && a->E > 0 && a->V1 > 1 && a->H % 4 == 0 && a->E % 4 == 0, "%s: need H%%4==0 and E%%4==0, V1 > 1 (H=%d E=%d V1=%d)", who, a->H, a->E, a->V1);
-    ECHR_REQUIRE(!(a->feats & 1) || (a->Dv > 0 && a->video), "%s: 'V' needs video [Dv]", who);
+    ECHR_REQUIRE(bx || !(a->feats & 1) || (a->Dv > 0 && a->video), "%s: 'V' needs video [Dv]", who);
     ECHR_REQUIRE(!(a->feats & 2) || (a->De > 0 && a->event), "%s: 'E' needs event [N,De]", who);
     ECHR_REQUIRE(a->embed && a->w_logit && a->b_logit && a->w_ih && a->w_hh && a->w_c2a && a->b_c2a && a->w_h2a && a->b_h2a && a->w_alpha && a->b_alpha &&
                  a->c3d && a->ev_start && a->ev_len, "%s: missing parameters / inputs", who);
     ECHR_REQUIRE((uintptr_t)a->w_hh % 16 == 0, "%s: w_hh must be 16-byte aligned", who);
+    return 0;
+}
+// the batch extension, ahead of every other check and of the first launch.  (vid lives on the device: that it does not decrease is the caller's contract, which
+// echr_amd.sat checks on the host copy it builds the device vector from)
+static int sat_check_batch(const echr_sat_args* a, const echr_batch_ext* x, const char* who) {
+    ECHR_REQUIRE(a && x, "%s: null args / batch extension", who);
+    ECHR_REQUIRE(x->n_videos >= 1 && x->n_videos <= a->N, "%s: the batch extension needs 1 <= n_videos <= N (n_videos=%d N=%d)", who, x->n_videos, a->N);
+    ECHR_REQUIRE(x->vid, "%s: the batch extension needs vid [N]", who);
+    if (a->feats & 1) {
+        ECHR_REQUIRE(a->Dv > 0 && x->video, "%s: 'V' needs the batch's video [n_videos, Dv]", who);
+        ECHR_REQUIRE(x->ws, "%s: 'V' needs the batch scratch ws (echr_sat_batch_ws_floats)", who);
+    }
     return 0;
 }
 static SatPanel sat_panel(const echr_sat_args* a, const SatDims& d) {
@@ -340,7 +365,11 @@ static SatPanel sat_panel(const echr_sat_args* a, const SatDims& d) {
 
 // P_all = ctx2att over the video rows ('C'), and the per-event constant part of the pre-activations: EVC [N, 4H] = [video | event] .
 // W_ih[:, V / E columns]^T ('E'), or the one row VB [4H] ('V' alone)
-static int sat_static(const echr_sat_args* a, const SatDims& dm, const SatWs& w, hipStream_t st) {
+//
+// Multi-video batch (bx): the scene product once per video, VIDV [V, 4H], each row with row_matvec's arithmetic (rows_matvec), gathered by
+// vid into VIDB [N, 4H]; that per-row addend stands where the one-video call has the bias VB -- the same add at the same place, so a
+// one-video batch forms the one-video call's values.  Returns in *rowadd what sat_token_rows adds per event (nullptr: VB, or nothing).
+static int sat_static(const echr_sat_args* a, const SatDims& dm, const SatWs& w, const echr_batch_ext* bx, const float** rowadd, hipStream_t st) {
     const int H = a->H;
     echr_gemm_desc d;
     if (dm.c) {
@@ -348,19 +377,28 @@ static int sat_static(const echr_sat_args* a, const SatDims& dm, const SatWs& w,
         d.bias = a->b_c2a; d.algo = ECHR_GEMM_BF16X3;          // (three exact bf16 planes, fp32-accurate: the three-stream decoder's choice for this product)
         SRC(gemm(d, st));
     }
-    if (dm.v) SRC(row_matvec(a->video, a->w_ih + dm.cv, dm.ldw, nullptr, nullptr, w.VB, 4 * H, a->Dv, st));
+    const float* vidb = nullptr;
+    if (dm.v && bx) {
+        const SatBatchWs bw = sat_carve_batch(a->N, bx->n_videos, H, bx->ws);
+        SRC(rows_matvec(bx->video, a->Dv, a->w_ih + dm.cv, dm.ldw, nullptr, nullptr, bw.VIDV, 4 * H, bx->n_videos, 4 * H, a->Dv, st));
+        SRC(embed_gather(bw.VIDV, bx->vid, bw.VIDB, a->N, 4 * H, bx->n_videos, st));
+        vidb = bw.VIDB;
+    } else if (dm.v) SRC(row_matvec(a->video, a->w_ih + dm.cv, dm.ldw, nullptr, nullptr, w.VB, 4 * H, a->Dv, st));
     if (dm.e) {
         d = desc_nt(a->event, a->De, a->w_ih + dm.ce, dm.ldw, w.EVC, 4 * H, a->N, 4 * H, a->De);
-        if (dm.v) d.bias = w.VB;
+        if (vidb) { d.addend = vidb; d.add_mod = a->N; d.ld_add = 4 * H; }
+        else if (dm.v) d.bias = w.VB;
         SRC(gemm(d, st));
     }
+    *rowadd = dm.e ? w.EVC : vidb;
     return 0;
 }
 // token-side gate rows of `rows` = nt * N token rows (embedded in xt) into PRE rows [row0, row0 + rows), plus the constant part
-static int sat_token_rows(const echr_sat_args* a, const SatDims& dm, const SatWs& w, const float* xt, long row0, int rows, hipStream_t st) {
+static int sat_token_rows(const echr_sat_args* a, const SatDims& dm, const SatWs& w, const float* rowadd, const float* xt, long row0, int rows,
+                          hipStream_t st) {
     const int H = a->H;
     echr_gemm_desc d = desc_nt(xt, a->E, a->w_ih, dm.ldw, w.PRE + row0 * 4 * H, 4 * H, rows, 4 * H, a->E);
-    if (dm.e) { d.addend = w.EVC; d.add_mod = a->N; d.ld_add = 4 * H; }
+    if (rowadd) { d.addend = rowadd; d.add_mod = a->N; d.ld_add = 4 * H; }
     else if (dm.v) d.bias = w.VB;
     return gemm(d, st);
 }
@@ -408,9 +446,15 @@ using namespace echr;
 extern "C" int64_t echr_sat_ws_floats(const echr_sat_args* a) { return a ? sat_carve(a, nullptr).total : -1; }
 extern "C" int64_t echr_sat_ws_bwd_floats(const echr_sat_args* a) { return a ? sat_carve_bwd(a, nullptr).total : -1; }
 
-extern "C" int echr_sat_fwd(const echr_sat_args* a, const echr_dropout* drop, void* stream) {
-    SRC(sat_check(a, "sat_fwd"));
-    ECHR_REQUIRE(a->S > 0 && a->ws && a->logp && a->tokens, "sat_fwd: missing buffers");
+extern "C" int64_t echr_sat_batch_ws_floats(int32_t N, int32_t n_videos, int32_t H) {
+    return (N > 0 && n_videos > 0 && H > 0) ? sat_carve_batch(N, n_videos, H, nullptr).total : -1;
+}
+
+// echr_sat_fwd (bx = nullptr) and echr_sat_fwd_batch
+static int sat_fwd(const echr_sat_args* a, const echr_dropout* drop, const echr_batch_ext* bx, const char* who, void* stream) {
+    if (bx) SRC(sat_check_batch(a, bx, who));
+    SRC(sat_check(a, who, bx));
+    ECHR_REQUIRE(a->S > 0 && a->ws && a->logp && a->tokens, "%s: missing buffers", who);
     SRC(persist_check_async());
     SRC(join_tail((hipStream_t)stream));
     hipStream_t st = (hipStream_t)stream;
@@ -418,15 +462,21 @@ extern "C" int echr_sat_fwd(const echr_sat_args* a, const echr_dropout* drop, vo
     const SatWs w = sat_carve(a, a->ws);
     const int N = a->N, S = a->S, H = a->H;
     const DropCfg dout = make_drop(drop, drop ? drop->p_out : 0.f);
+    const float* rowadd = nullptr;
     SRC(sat_initial_state(a, w, a->h0, a->h0, st));
-    SRC(sat_static(a, dm, w, st));
+    SRC(sat_static(a, dm, w, bx, &rowadd, st));
     SRC(embed_gather(a->embed, a->tokens, w.XT, S * N, a->E, a->V1, st));
-    SRC(sat_token_rows(a, dm, w, w.XT, 0, S * N, st));
+    SRC(sat_token_rows(a, dm, w, rowadd, w.XT, 0, S * N, st));
     for (int t = 0; t < S; ++t) SRC(sat_step(a, dm, w, t, dout, st));
     echr_gemm_desc d = desc_nt(w.OUTD, H, a->w_logit, H, a->logp, a->V1, S * N, a->V1, H);
     d.bias = a->b_logit; d.rowmap_mod = N; d.rowmap_mul = S; d.algo = ECHR_GEMM_BF16X3;
     SRC(gemm(d, st));
     return logsoftmax_rows(a->logp, a->V1, N, S, 0, S, a->V1, st);
+}
+extern "C" int echr_sat_fwd(const echr_sat_args* a, const echr_dropout* drop, void* stream) { return sat_fwd(a, drop, nullptr, "sat_fwd", stream); }
+extern "C" int echr_sat_fwd_batch(const echr_sat_args* a, const echr_dropout* drop, const echr_batch_ext* x, void* stream) {
+    ECHR_REQUIRE(x, "sat_fwd_batch: null batch extension");
+    return sat_fwd(a, drop, x, "sat_fwd_batch", stream);
 }
 
 extern "C" int echr_sat_step(const echr_sat_args* a0, const float* h_in, const float* c_in, float* h_out, float* c_out, const echr_dropout* drop,
@@ -443,10 +493,11 @@ extern "C" int echr_sat_step(const echr_sat_args* a0, const float* h_in, const f
     const SatWs w = sat_carve(&a, a.ws);
     const int N = a.N, H = a.H;
     const long hs = (long)N * H;
+    const float* rowadd = nullptr;
     SRC(sat_initial_state(&a, w, h_in, c_in, st));
-    SRC(sat_static(&a, dm, w, st));
+    SRC(sat_static(&a, dm, w, nullptr, &rowadd, st));
     SRC(embed_gather(a.embed, a.tokens, w.XT, N, a.E, a.V1, st));
-    SRC(sat_token_rows(&a, dm, w, w.XT, 0, N, st));
+    SRC(sat_token_rows(&a, dm, w, rowadd, w.XT, 0, N, st));
     SRC(sat_step(&a, dm, w, 0, make_drop(drop, drop ? drop->p_out : 0.f), st));
     echr_gemm_desc d = desc_nt(w.OUTD, H, a.w_logit, H, a.logp, a.V1, N, a.V1, H);
     d.bias = a.b_logit;
@@ -471,11 +522,13 @@ static SatSampWs sat_carve_samp(const echr_sat_args* a, float* base) {
 }
 extern "C" int64_t echr_sat_sampler_ws_floats(const echr_sat_args* a) { return a ? sat_carve_samp(a, nullptr).total : -1; }
 
-extern "C" int echr_sat_sample(const echr_sat_sample_args* sa, void* stream) {
-    ECHR_REQUIRE(sa, "sat_sample: null args");
-    SRC(sat_check(&sa->dec, "sat_sample"));
+// echr_sat_sample (bx = nullptr) and echr_sat_sample_batch: every row stops on its own <eos>, the chain runs seq_len steps either way
+static int sat_sample(const echr_sat_sample_args* sa, const echr_batch_ext* bx, const char* who, void* stream) {
+    ECHR_REQUIRE(sa, "%s: null args", who);
+    if (bx) SRC(sat_check_batch(&sa->dec, bx, who));
+    SRC(sat_check(&sa->dec, who, bx));
     const int L = sa->seq_len;
-    ECHR_REQUIRE(L > 0 && sa->seq && sa->seq_logp && sa->n_unfinished && sa->ws_sample && sa->dec.ws, "sat_sample: missing buffers");
+    ECHR_REQUIRE(L > 0 && sa->seq && sa->seq_logp && sa->n_unfinished && sa->ws_sample && sa->dec.ws, "%s: missing buffers", who);
     SRC(persist_check_async());
     SRC(join_tail((hipStream_t)stream));
     DeterministicScope det;                    // `seq` is an index output: one fixed-order k loop per tile everywhere
@@ -491,12 +544,13 @@ extern "C" int echr_sat_sample(const echr_sat_sample_args* sa, void* stream) {
         long zn[4] = {L + 1, 2L * srup(N, 64), 2L * N * L, (long)N * L};          // (IT | UNF are adjacent)
         SRC(fill_zero_multi(zp, zn, 4, st));
     }
+    const float* rowadd = nullptr;
     SRC(sat_initial_state(&a, w, a.h0, a.h0, st));
-    SRC(sat_static(&a, dm, w, st));
+    SRC(sat_static(&a, dm, w, bx, &rowadd, st));
     const DropCfg none = make_drop(nullptr, 0.f);
     for (int t = 0; t < L; ++t) {
         SRC(embed_gather(a.embed, s.IT, w.XT, N, a.E, a.V1, st));
-        SRC(sat_token_rows(&a, dm, w, w.XT, (long)t * N, N, st));
+        SRC(sat_token_rows(&a, dm, w, rowadd, w.XT, (long)t * N, N, st));
         SRC(sat_step(&a, dm, w, t, none, st));
         echr_gemm_desc d = desc_nt(w.OUTD + (long)t * N * H, H, a.w_logit, H, s.LOGITS, a.V1, N, a.V1, H);
         d.bias = a.b_logit;
@@ -505,12 +559,19 @@ extern "C" int echr_sat_sample(const echr_sat_sample_args* sa, void* stream) {
     }
     return 0;
 }
+extern "C" int echr_sat_sample(const echr_sat_sample_args* sa, void* stream) { return sat_sample(sa, nullptr, "sat_sample", stream); }
+extern "C" int echr_sat_sample_batch(const echr_sat_sample_args* sa, const echr_batch_ext* x, void* stream) {
+    ECHR_REQUIRE(x, "sat_sample_batch: null batch extension");
+    return sat_sample(sa, x, "sat_sample_batch", stream);
+}
 
-extern "C" int echr_sat_bwd(const echr_sat_args* a, const echr_sat_grads* g, const echr_dropout* drop, void* stream) {
-    SRC(sat_check(a, "sat_bwd"));
-    ECHR_REQUIRE(g && a->S > 0 && a->ws && a->logp && a->tokens && g->g_logp && g->ws_bwd, "sat_bwd: missing buffers");
+// echr_sat_bwd (bx = nullptr) and echr_sat_bwd_batch
+static int sat_bwd(const echr_sat_args* a, const echr_sat_grads* g, const echr_dropout* drop, const echr_batch_ext* bx, const char* who, void* stream) {
+    if (bx) SRC(sat_check_batch(a, bx, who));
+    SRC(sat_check(a, who, bx));
+    ECHR_REQUIRE(g && a->S > 0 && a->ws && a->logp && a->tokens && g->g_logp && g->ws_bwd, "%s: missing buffers", who);
     ECHR_REQUIRE(g->g_embed && g->g_w_logit && g->g_b_logit && g->g_w_ih && g->g_w_hh && g->g_w_c2a && g->g_b_c2a && g->g_w_h2a && g->g_b_h2a &&
-                 g->g_w_alpha && g->g_b_alpha, "sat_bwd: missing parameter-gradient buffers");
+                 g->g_w_alpha && g->g_b_alpha, "%s: missing parameter-gradient buffers", who);
     SRC(persist_check_async());
     SRC(join_tail((hipStream_t)stream));
     hipStream_t st = (hipStream_t)stream;
@@ -591,7 +652,21 @@ extern "C" int echr_sat_bwd(const echr_sat_args* a, const echr_sat_grads* g, con
             SRC(gemm(d, st));
         }
     }
-    if (dm.v) {
+    if (dm.v && bx) {
+        // the rows of a video are one contiguous run of vid: summed in ascending row order (no atomics), then two products with K = V / 4H,
+        // each one fixed-order k loop per tile
+        const int V = bx->n_videos;
+        float* dgseg = sat_carve_batch(N, V, H, bx->ws).DGSEG;
+        SRC(seg_rowsum(b.DGSUM, bx->vid, N, V, H4, H4, dgseg, st));
+        d = desc_tn(dgseg, H4, bx->video, a->Dv, g->g_w_ih + dm.cv, dm.ldw, H4, a->Dv, V);
+        d.beta = 1.f; d.split_k = 1;
+        SRC(gemm(d, st));
+        if (bx->g_video) {
+            d = desc_nn(dgseg, H4, a->w_ih + dm.cv, dm.ldw, bx->g_video, a->Dv, V, a->Dv, H4);
+            d.split_k = 1;
+            SRC(gemm(d, st));
+        }
+    } else if (dm.v) {
         SRC(colsum(b.DGSUM, H4, N, H4, b.DGCOL, false, st));
         SRC(rank1_update(b.DGCOL, a->video, g->g_w_ih + dm.cv, dm.ldw, H4, a->Dv, true, st));
         if (g->g_video) SRC(vec_mat(b.DGCOL, a->w_ih + dm.cv, dm.ldw, g->g_video, H4, a->Dv, st));
@@ -617,4 +692,11 @@ extern "C" int echr_sat_bwd(const echr_sat_args* a, const echr_sat_grads* g, con
     SRC(embed_scatter_add(b.DXT, a->tokens, b.GEMB, SN, E, V1, st));
     hipLaunchKernelGGL(sat_acc_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, st, g->g_embed, b.GEMB, ne);
     return check_launch("sat_acc");
+}
+extern "C" int echr_sat_bwd(const echr_sat_args* a, const echr_sat_grads* g, const echr_dropout* drop, void* stream) {
+    return sat_bwd(a, g, drop, nullptr, "sat_bwd", stream);
+}
+extern "C" int echr_sat_bwd_batch(const echr_sat_args* a, const echr_sat_grads* g, const echr_dropout* drop, const echr_batch_ext* x, void* stream) {
+    ECHR_REQUIRE(x, "sat_bwd_batch: null batch extension");
+    return sat_bwd(a, g, drop, x, "sat_bwd_batch", stream);
 }

@@ -197,6 +197,8 @@ def caption_videos(tap_model, cg_model, videos, featstamp_to_time, vocab=None, t
 
     Host reads per call, whatever V is: the selection counts, the selected lists (one packed copy), the decoder's step counts, and the
     sequences / log-probs of the batch.  Beam search over the batch is caption_videos_beam.
+    The batch is built for the model's decoder (opt.caption_model): a one-stream model ('show_attend_tell') gets the same one-pass
+    evaluation through its batched greedy decode; caption_videos_beam refuses it, as beam_batch does.
 
     The validation loss of the same batch (eval_split's get_eval_loss), with labels stacked into the batch:
         logp = cg_model.forward_batch(extras['batch'], mode='train')
@@ -309,7 +311,8 @@ def _caption_videos(tap_model, cg_model, videos, featstamp_to_time, vocab, topN,
     batch = extras['batch'] = VideoBatch(c3d_b, tap_b, lda_b, rows_b, eo_b, np.concatenate([sois[v] + rows_b[i] for i, v in enumerate(kept)], 0),
                                          np.concatenate([inds[v] + rows_b[i] for i, v in enumerate(kept)], 0),
                                          clip_context_type=cg_model.opt.clip_context_type,
-                                         CG_init_feats_type=getattr(cg_model.opt, 'CG_init_feats_type', ''))
+                                         CG_init_feats_type=getattr(cg_model.opt, 'CG_init_feats_type', ''),
+                                         caption_model=getattr(cg_model.opt, 'caption_model', None))
     if flag_eval_what == 'tap':
         for v in kept:
             n = len(sois[v])

@@ -35,6 +35,8 @@ every rank on cuda:0, launch-per-phase recurrences.  Without a process group not
 
 `--caption_model show_attend_tell --CG_input_feats_type VEC` trains the reference's default one-stream decoder (one LSTM layer, echr_amd.sat)
 on the plain autograd path -- forward, criterion, backward, clip_gradient, ClampAdam.step over the flat arena -- and decodes greedily.
+With `--m_batch V` (V > 1, without --joint) the V videos of an update are ONE VideoBatch built for that decoder: forward_batch,
+batch.criterion, backward, clip_gradient, ClampAdam.step -- the launch chain of the decoder once per update instead of once per video.
 
 usage: python examples/train_synthetic.py [--iters 20] [--m_batch 2] [--joint] [--pre_tap] [--self_critical [--reward ciderd]] [--save /tmp/echr_ckpt.pth]
                                           [--resume /tmp/echr_ckpt.pth]
@@ -252,6 +254,30 @@ def self_critical(a, opt, dev, loader, tap_model, cg_model, cg_opt, start):
     return history
 
 
+def one_stream_batch(a, opt, dev, loader, tap_model, cg_model, cg_opt, cg_crit, start):
+    """--caption_model show_attend_tell --m_batch V ('pre_cg' mode: the proposal encoder idle, its states without a graph): the V videos of an
+    update as one VideoBatch through forward_batch + batch.criterion + backward + clip_gradient + ClampAdam.step."""
+    from echr_amd.batch import VideoBatch
+    history = []
+    for it in range(start, start + a.iters):
+        vids = [loader[(it * a.m_batch + j) % len(loader)] for j in range(a.m_batch)]
+        set_lr_for_epoch(cg_opt, opt.lr, it * a.m_batch // len(loader))
+        cg_opt.zero_grad()
+        with torch.no_grad():
+            batch = VideoBatch.from_videos([{k: v[k] for k in ('c3d', 'lda', 'ind', 'soi', 'labels', 'masks')} for v in vids], device=dev,
+                                             tap_model=tap_model, clip_context_type=opt.clip_context_type,
+                                             CG_init_feats_type=opt.CG_init_feats_type, caption_model=opt.caption_model)
+        pred = cg_model.forward_batch(batch, mode='train')
+        loss, _ = batch.criterion(cg_crit, pred)
+        loss.backward()
+        utils.clip_gradient(cg_opt, opt.grad_clip)
+        cg_opt.step()
+        history.append(float(loss.detach()) / a.m_batch)
+        if not a.quiet and (it % 5 == 0 or it == start + a.iters - 1):
+            print('iter %3d  cg_loss %.4f  (mean of %d videos, one forward_batch call)' % (it, history[-1], a.m_batch), flush=True)
+    return history
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--iters', type=int, default=20)
@@ -294,7 +320,7 @@ def main(argv=None):
     opt.clip_context_type = a.clip_context_type
     opt.CG_init_feats_type = a.CG_init_feats_type
     if a.caption_model == 'show_attend_tell':
-        # the one-stream decoder has no one-call step, batch or self-critical entry yet: forward, criterion, backward, clip, ClampAdam.step
+        # the one-stream decoder has no one-call step or self-critical entry yet: forward / forward_batch, criterion, backward, clip, ClampAdam.step
         if a.self_critical or 'RANK' in os.environ or (a.joint and a.m_batch > 1 and not a.no_fused):
             raise SystemExit('--caption_model show_attend_tell trains on the autograd path: not with --self_critical, torchrun or the batched --joint')
         opt.caption_model, opt.CG_num_layers, opt.CG_input_feats_type = 'show_attend_tell', 1, a.CG_input_feats_type
@@ -346,6 +372,8 @@ def main(argv=None):
         history, iters = data_parallel_batch(a, opt, dev, loader, tap_model, cg_model, cg_opt, tap_opt, start, *ranks), ()
     elif batch_joint:
         history, iters = joint_batch(a, opt, dev, loader, tap_model, cg_model, cg_opt, tap_opt, start), ()
+    elif a.caption_model == 'show_attend_tell' and a.m_batch > 1 and not a.joint:
+        history, iters = one_stream_batch(a, opt, dev, loader, tap_model, cg_model, cg_opt, cg_crit, start), ()
     for it in iters:
         v = loader[it % len(loader)]
         set_lr_for_epoch(cg_opt, opt.lr, it // len(loader))

@@ -1087,6 +1087,29 @@ typedef struct {
 } echr_sat_sample_args;
 int64_t echr_sat_sampler_ws_floats(const echr_sat_args* a);
 int echr_sat_sample(const echr_sat_sample_args* a, void* stream);
+/* The one-stream decoder over a multi-video batch, under the rules of "Multi-video batches" above: feature rows concatenated (Tv = the total
+ * row count, A = the widest event of the batch), ev_start batch-absolute, vid non-decreasing, one scene vector per video, gradients the SUM
+ * over the videos.  Each entry takes the arguments of its single-video sibling plus the extension:
+ *   - echr_sat_args.video is ignored: row n reads x->video[vid[n], :].  The scene product is formed once per video ([V, 4H], each row with
+ *     the single-video entry's arithmetic), gathered by vid on the device and added to the pre-activations per row, where the single-video
+ *     entry adds its one [4H] row.  With n_videos = 1 the arithmetic and its order are the single-video entry's: a one-video batch equals
+ *     echr_sat_fwd / echr_sat_sample bit for bit in eval mode;
+ *   - h0 (optional): the rows echr_init_state_fwd_batch forms with H3 = H;
+ *   - dropout: one counter per call; the one site is keyed by element n * H + u with n the BATCH-GLOBAL row (and step t), so row n of a
+ *     batch draws what a single-video call draws for its row n only when the video is the batch's first;
+ *   - backward: d W_ih[:, V columns] = sum over v of (sum over t and the rows of v of d gates)^T . video[v]; x->g_video [V, Dv] (optional;
+ *     echr_sat_grads.g_video is ignored) is WRITTEN with the matching data gradient -- the rows of a video are one contiguous run of vid,
+ *     added in ascending row order, no atomics.  d event, g_h0 and the other parameter gradients are per row, as for one video;
+ *     "deterministic" = 1 keeps its meaning;
+ *   - greedy decode: every row stops on its own <eos>; the chain runs seq_len steps and n_unfinished counts over the batch, so the caller
+ *     cuts at the width of the batch's longest caption and finds each video's own width on the host from seq.
+ * x->ws: echr_sat_batch_ws_floats(N, n_videos, H) floats (read with 'V' only; may be NULL otherwise), only read and written inside the
+ * call.  Checked before the first launch: n_videos in [1, N], vid, and x->video with 'V'.  vid is device memory: that it does not decrease
+ * is the caller's contract (echr_amd.sat checks it on the host vector it uploads). */
+int64_t echr_sat_batch_ws_floats(int32_t N, int32_t n_videos, int32_t H);
+int echr_sat_fwd_batch(const echr_sat_args* a, const echr_dropout* drop, const echr_batch_ext* x, void* stream);
+int echr_sat_bwd_batch(const echr_sat_args* a, const echr_sat_grads* g, const echr_dropout* drop, const echr_batch_ext* x, void* stream);
+int echr_sat_sample_batch(const echr_sat_sample_args* a, const echr_batch_ext* x, void* stream);
 
 #ifdef __cplusplus
 }
