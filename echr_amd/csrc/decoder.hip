@@ -1908,7 +1908,10 @@ static int bwd_embed_grads(const BwdPlan& p, hipStream_t q) {
         gx[k] = p.h2 ? desc_h2(b.PK_DG[k], b.PK_WIHT[k], b.DXT, E, SNr, E, 4 * H) : desc_nn(b.DG[k], 4 * H, a->w_ih[k], p.cin[k], b.DXT, E, SN, E, 4 * H);
         gx[k].split_k = -1; gx[k].beta = 1.f;                // shared, pre-zeroed output: everything adds atomically
     }
-    RC(gemm_grouped(gx, 3, q));
+    // (a grouped launch whose problems share C adds its k-slices atomically and needs two of them: K = 4H <= 32, i.e. H = 4 or 8, runs the
+    // three accumulating products one behind the other instead, as tsrm.hip does for d X)
+    if (4 * H > 32) RC(gemm_grouped(gx, 3, q));
+    else for (int k = 0; k < 3; ++k) RC(gemm(gx[k], q));
     return embed_scatter_add(b.DXT, a->tokens, p.g->g_embed, p.h2 ? SNr : SN, E, p.V1, q, p.h2 ? p.actr : nullptr);
 }
 // 5. attention parameters: d P_all / d alpha over all timesteps (att_post), the column sums behind it (bias_owed: with d b_logit) and ctx2att

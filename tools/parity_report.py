@@ -16,7 +16,10 @@ GPU is present, the HIP path against the same float64 oracle beside it per route
 launch-per-phase (70 events: the launch form alone; the batch: forward_batch).
 
 --sat: the one-stream decoder's cases (synth.SAT_CASES, tests/sat_ref.py) -- e_ref per variant and mode and, when a GPU is present, the HIP path
-against the same float64 run beside it."""
+against the same float64 run beside it.
+
+--widths: the decoder-width cases (tests/width_ref.py) -- e_ref per case (log-probs, loss, worst gradient tensor, worst slice of the varied axis),
+what the two mutants move, and, when a GPU is present, the HIP path against the same float64 oracle beside it."""
 import sys, os; sys.path.insert(0, os.environ.get('GRAFT_REPO_ROOT', '/root/repo')); sys.path.insert(0, os.path.join(os.environ.get('GRAFT_REPO_ROOT', '/root/repo'), 'tests'))
 import numpy as np, torch
 import util as U
@@ -132,6 +135,32 @@ def sat_report():
             print(line, flush=True)
 
 
+def widths_report():
+    """The decoder-width cases (tests/width_ref.py): e_ref per case in train mode (log-probs, loss, worst gradient tensor, worst width slice --
+    the table in the docstring of tests/test_gpu_decoder_widths.py and E_REF of tests/width_ref.py), the movement of the two mutants, and, when
+    a GPU is present, the HIP path against the same float64 oracle beside it on the default route."""
+    from tests import width_ref as W
+    gpu = torch.cuda.is_available()
+    if gpu:
+        from tests import test_gpu_decoder_widths as T
+    fmt = 'logp %.1e loss %.1e grad %.1e slice %.1e'
+    pick = lambda e: (e[0], e[1], e[2], e[4])
+    for name, c in W.CASES.items():
+        e = W.e_ref(name)
+        line = '%-20s R %d RD %d  e_ref: ' % ((name,) + W.dispatch(c)) + fmt % pick(e) + ' (%s)' % e[5].replace('lm_model.core.', '')
+        if name in W.MUTATED:
+            opt, ref = W.case(name)[0], W.oracle(name)
+            for which in ('alpha', 'c3d'):
+                m = W.errors(W.mutant(name, which), ref, opt)
+                line += ' | %s: logp %.1e grad %.1e' % (which, m[0], m[2])
+        if gpu:
+            line += ' | HIP: ' + fmt % pick(W.errors(T.module_pass(name, ()), W.oracle(name), W.case(name)[0]))
+        print(line, flush=True)
+
+
+if '--widths' in sys.argv:
+    widths_report()
+    sys.exit(0)
 if '--sat' in sys.argv:
     sat_report()
     sys.exit(0)
