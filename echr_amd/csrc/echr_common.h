@@ -64,6 +64,9 @@ __device__ __forceinline__ unsigned philox_word(unsigned elem, unsigned step, un
     return sel == 0 ? c0 : (sel == 1 ? c1 : (sel == 2 ? c2 : c3));
 }
 
+// site 7 (echr_amd/philox.py SITE_PROP) is no dropout site: the sampling key of a good proposal cell (targets.hip), step = the video's draw id
+constexpr unsigned SITE_PROP = 7u;
+
 // multiplicative dropout factor (0 or scale; 1 when inactive) for flat element `elem` of a site/step
 __device__ __forceinline__ float drop_mult(const DropCfg& d, unsigned elem, unsigned step, unsigned site) {
     if (!d.active) return 1.0f;

@@ -24,6 +24,8 @@ SITE_H2 = 3
 SITE_OUT = 4       # [N, 3H]    p = CG_drop_prob
 SITE_SST = 5       # [T, H]     p = rnn_dropout (SST inter-layer dropout; step counter 0, element t*H + j)
 SITE_SAMPLE = 6    # [N]        the multinomial draw of (row, step): element = row (batch-global in a multi-video batch), offset 0
+SITE_PROP = 7      # [T_v * K]  the sampling key of a good proposal cell (csrc/targets.hip): element = t * K + k local to the video, step = the
+                   # video's draw id, offset 0, the call's seed as the key; the cells with the smallest (word, element) are the sample
 
 _M0 = np.uint64(0xD2511F53)
 _M1 = np.uint64(0xCD9E8D57)

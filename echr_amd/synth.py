@@ -145,6 +145,33 @@ def make_video(N, A, L, V1, seed=1234, T_v=None, full_len=False, min_len=4, vide
                 ind=ind.astype(np.int64), soi=soi.astype(np.int64), T_v=T_v)
 
 
+def make_gt_video(T_v, G, L, V1, seed=1234, min_len=2, max_len=None, video_dim=500, hidden_dim=512, lda_dim=100):
+    """One synthetic ANNOTATED video, as a dataset gives it: features and G ground-truth segments with one caption each -- no proposal
+    labels and no event lists; echr_amd.targets.build makes those.  'featstamps' int64 [G, 2]: integer (start, end) rows with
+    0 <= start < end <= T_v - 1 and end - start in [min_len, max_len] (default: up to T_v - 1; segment 0 is the longest allowed);
+    'gt_labels' int64 [G, L] / 'gt_masks' float32 [G, L] in make_video's caption layout (column 0 = BOS, `nonzeros + 2` ones);
+    'c3d', 'tap', 'lda', 'T_v' as make_video.  L >= 3; T_v >= 2 when G > 0 (a one-row video admits no segment)."""
+    rs = np.random.RandomState(seed)
+    max_len = T_v - 1 if max_len is None else min(int(max_len), T_v - 1)
+    min_len = max(1, min(int(min_len), max_len))
+    lens = rs.randint(min_len, max_len + 1, size=G)
+    if G:
+        lens[0] = max_len
+    starts = np.array([rs.randint(0, T_v - l) for l in lens], dtype=np.int64).reshape(-1)
+    stamps = np.stack([starts, starts + lens], 1).astype(np.int64).reshape(-1, 2)
+    c3d = rs.standard_normal((T_v, video_dim)).astype(np.float32)
+    tap = (0.5 * rs.standard_normal((T_v, hidden_dim))).astype(np.float32)
+    lda = np.abs(rs.standard_normal(lda_dim)).astype(np.float32)
+    lda /= lda.sum()
+    labels = np.zeros((G, L), dtype=np.int64)
+    masks = np.zeros((G, L), dtype=np.float32)
+    for i in range(G):
+        n = int(rs.randint(1, L - 1)) if i else L - 2          # caption 0 uses all L - 2 token slots
+        labels[i, 1:1 + n] = rs.randint(1, V1, size=n)
+        masks[i, :n + 2] = 1.0
+    return dict(c3d=c3d, tap=tap, lda=lda, featstamps=stamps, gt_labels=labels, gt_masks=masks, T_v=T_v)
+
+
 # Named parity / bench cases (BASELINE.json `configs`; SURVEY 8-d).  `opt` = overrides of default_opt.
 CASES = {
     # every width shrunk (all multiples of 4) so that full tensors fit in a fixture

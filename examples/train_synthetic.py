@@ -38,6 +38,12 @@ on the plain autograd path -- forward, criterion, backward, clip_gradient, Clamp
 With `--m_batch V` (V > 1, without --joint) the V videos of an update are ONE VideoBatch built for that decoder: forward_batch,
 batch.criterion, backward, clip_gradient, ClampAdam.step -- the launch chain of the decoder once per update instead of once per video.
 
+`--gt_targets` (with `--joint --m_batch V` or `--pre_tap`) trains from ground-truth SEGMENTS instead of ready-made supervision: the loader's
+videos carry featstamps and one caption per segment (synth.make_gt_video), and every batch's proposal labels, masks and caption events are
+built on the device by echr_amd.targets.build (dataloader.get_vid_data / get_shuffle_list: IoU of every anchor against every segment, the
+thresholded maps, a sample of `--events` good proposals per video, a new draw every iteration).  Videos without a good proposal are skipped
+as train.py:261 does.
+
 usage: python examples/train_synthetic.py [--iters 20] [--m_batch 2] [--joint] [--pre_tap] [--self_critical [--reward ciderd]] [--save /tmp/echr_ckpt.pth]
                                           [--resume /tmp/echr_ckpt.pth]
 """
@@ -68,6 +74,25 @@ def make_loader(opt, n_videos, N, A, L, seed=0):
     return vids
 
 
+def make_gt_loader(opt, n_videos, G, A, L, seed=0):
+    """--gt_targets: annotated videos as a dataset gives them -- G ground-truth segments of up to min(A, K) - 2 rows with one caption each
+    on a video of A + max(8, A // 4) rows (make_video's default length), and the class weights of the SST head."""
+    V1 = opt.CG_vocab_size + 1
+    vids = [synth.make_gt_video(A + max(8, A // 4), G, L, V1, seed=seed + i, max_len=max(2, min(A, opt.K) - 2), video_dim=opt.video_dim,
+                                hidden_dim=opt.hidden_dim, lda_dim=opt.lda_dim) for i in range(n_videos)]
+    rs = np.random.RandomState(seed)
+    for v in vids:
+        v['w1'] = rs.uniform(0.05, 0.3, size=(opt.K,)).astype(np.float32)
+    return vids
+
+
+def build_targets(a, opt, dev, vids, it):
+    """The batch's supervision from its segments (echr_amd.targets.build): a new sample per iteration through the draw ids."""
+    from echr_amd import targets
+    return targets.build(vids, opt.K, prop_sample_num=a.events, seed=a.target_seed, device=dev,
+                         draw=[(it * a.m_batch + j) % (1 << 31) for j in range(len(vids))])
+
+
 def set_lr_for_epoch(optimizer, base_lr, epoch, start=8, every=3, rate=0.5):
     """Step decay as train.py:232-240."""
     lr = base_lr if epoch <= start or start < 0 else base_lr * rate ** ((epoch - start) // every)
@@ -90,7 +115,12 @@ def pre_tap(a, opt, dev, loader, tap_model, cg_model, cg_opt, tap_opt, tap_crit,
         row_offset = np.concatenate([[0], np.cumsum([len(v['c3d']) for v in vids])])
         tap_opt.zero_grad()
         _, pred_proposals = tap_model.forward_batch(as_dev(vids, 'c3d'), row_offset)
-        tap_loss, per_video = utils.tap_criterion_batch(tap_crit, pred_proposals, as_dev(vids, 'tap_masks'), as_dev(vids, 'tap_labels'),
+        if a.gt_targets:          # labels and masks built on the device from the videos' segments
+            t = build_targets(a, opt, dev, vids, it)
+            masks, labels = t.tap_masks, t.tap_labels
+        else:
+            masks, labels = as_dev(vids, 'tap_masks'), as_dev(vids, 'tap_labels')
+        tap_loss, per_video = utils.tap_criterion_batch(tap_crit, pred_proposals, masks, labels,
                                                         [torch.from_numpy(v['w1']).to(dev) for v in vids], row_offset)
         tap_loss.backward()
         utils.clip_gradient(tap_opt, opt.grad_clip)
@@ -181,8 +211,15 @@ def joint_batch(a, opt, dev, loader, tap_model, cg_model, cg_opt, tap_opt, start
         epoch = it * a.m_batch // len(loader)
         set_lr_for_epoch(cg_opt, opt.lr, epoch)
         set_lr_for_epoch(tap_opt, opt.lr, epoch)
-        loss = step([{k: v[k] for k in keys} for v in vids], [torch.from_numpy(v['tap_masks']) for v in vids],
-                    [torch.from_numpy(v['tap_labels']) for v in vids], [torch.from_numpy(v['w1']) for v in vids])
+        if a.gt_targets:          # proposal labels, masks and the sampled caption events built on the device from the videos' segments
+            t = build_targets(a, opt, dev, vids, it)
+            videos = t.videos([{k: v[k] for k in keys[:2]} for v in vids], [v['gt_labels'] for v in vids], [v['gt_masks'] for v in vids])
+            if not videos:          # no video of the batch has a good proposal (train.py:261)
+                continue
+            loss = step(videos, t.kept(t.tap_masks), t.kept(t.tap_labels), [torch.from_numpy(vids[v]['w1']) for v in t.keep])
+        else:
+            loss = step([{k: v[k] for k in keys} for v in vids], [torch.from_numpy(v['tap_masks']) for v in vids],
+                        [torch.from_numpy(v['tap_labels']) for v in vids], [torch.from_numpy(v['w1']) for v in vids])
         history.append(float(step.cg_loss) / a.m_batch)
         if not a.quiet and (it % 5 == 0 or it == start + a.iters - 1):
             print('iter %3d  JointBatchStep over %d videos: joint_loss %.4f  cg_loss %.4f  tap_loss %.4f  (means over the videos)'
@@ -290,6 +327,11 @@ def main(argv=None):
                                                                                        "CIDEr-D scored on the device (echr_amd.reward) against "
                                                                                        "each event's own label")
     ap.add_argument('--events', type=int, default=16)
+    ap.add_argument('--gt_targets', action='store_true', help='with --joint --m_batch V or --pre_tap: the loader gives ground-truth segments '
+                                                              'with one caption each, and every batch\'s proposal labels, masks and '
+                                                              '--events sampled caption events are built on the device (echr_amd.targets)')
+    ap.add_argument('--gt_segments', type=int, default=4, help='--gt_targets: ground-truth segments per synthetic video')
+    ap.add_argument('--target_seed', type=int, default=0, help='--gt_targets: the key of the proposal sampling')
     ap.add_argument('--segments', type=int, default=32)
     ap.add_argument('--vocab', type=int, default=500)
     ap.add_argument('--lr', type=float, default=5e-4)
@@ -357,7 +399,12 @@ def main(argv=None):
     if a.m_batch == 1 and not a.no_fused:
         from echr_amd.fused import FusedTrainStep
         fused = FusedTrainStep(cg_model, cg_opt, grad_clip=opt.grad_clip)
-    loader = make_loader(opt, 8, a.events, a.segments, opt.CG_seq_length + 2)
+    if a.gt_targets and not (a.pre_tap or (batch_joint and not dp_batch)):
+        raise SystemExit('--gt_targets builds the targets of a batch: it goes with --joint --m_batch V (V > 1) or --pre_tap in one process')
+    if a.gt_targets:
+        loader = make_gt_loader(opt, 8, a.gt_segments, a.segments, opt.CG_seq_length + 2)
+    else:
+        loader = make_loader(opt, 8, a.events, a.segments, opt.CG_seq_length + 2)
     history = []
     if a.pre_tap:
         return pre_tap(a, opt, dev, loader, tap_model, cg_model, cg_opt, tap_opt, tap_crit, start)
@@ -433,6 +480,9 @@ def main(argv=None):
         c3d, lda = torch.from_numpy(v['c3d']).to(dev), torch.from_numpy(v['lda']).to(dev)
         tap_model.eval()
         tap_feats, _ = tap_model(c3d)
+        if a.gt_targets:          # caption the ground-truth events (the reference's gts_*_select_list)
+            from echr_amd import targets
+            v = dict(v, **targets.gt_events(v['featstamps']))
         seq, logp = cg_model(tap_feats, c3d, lda, [], v['ind'], v['soi'], mode='eval')
     if not a.quiet:
         print('greedy captions (token ids) of video 0:', seq[:3].tolist() if len(seq) else seq)

@@ -551,6 +551,38 @@ int echr_densecap_fill(const echr_densecap_args* a, void* stream);
 int echr_densecap_pair_stats(const echr_densecap_args* a, void* stream);
 int echr_densecap_reduce(const echr_densecap_args* a, void* stream);
 
+/* Proposal targets and caption-event samples from ground-truth segments: what dataloader.get_vid_data / get_data /
+ * get_shuffle_list build per video on the host (dataloader.py:266-281, 339-357, 107-109, 124, 615-639), over a multi-video batch in the
+ * concatenated [T_tot, K] layout.  Video v owns rows row_offset[v] .. row_offset[v + 1] - 1 (at least one) and the ground-truth featstamps
+ * gt[gt_offset[v] .. gt_offset[v + 1] - 1] = (start, end), local to the video, possibly none, at most ECHR_TARGETS_MAX_GT.  All vectors are
+ * device memory; that the offsets grow and that 0 <= start < end <= T_v - 1 is the caller's contract (echr_amd.targets checks its host
+ * copies) -- offsets outside the buffers select nothing and no access leaves the buffers.  G_max is the caller's statement of the largest
+ * per-video segment count: what the library can refuse before the launch.
+ *  echr_tap_targets_batch, for local row t and column k:
+ *    valid = t >= k + 1;  tap_masks = valid;  iou = 0 and gts_index = 0 where not valid.  Where valid the anchor is [a, t], a = t - k - 1, and
+ *    for each ground truth i in order, with s = start - 0.01, e = end + 0.01:
+ *      inter = max(0, min(e, t) - max(s, a));  uni = min(max(e, t) - min(s, a), ((e - s) + t) - a);  ov = inter / (uni + 1e-8)
+ *    in fp64 in this order; the running maximum is replaced when ov >= best, from best = 0.0, index = -1: ties go to the later ground truth,
+ *    an anchor that overlaps nothing gets G_v - 1, a video without segments -1.  iou = (float)best;  tap_labels = iou >= (float)iou_threshold;
+ *    good = iou >= (float)iou_threshold_good (fp32 compares);  good_gt = gts_index where good, else -1;  n_good[v] = the number of good cells.
+ *    Both thresholds must be positive.  Every operation is a correctly rounded fp64 add, subtract, compare or divide, with no product: the
+ *    outputs equal the host's bit for bit.
+ *  echr_prop_events_batch: events[v, i, :] = (t, k, gt) of video v's i-th listed proposal, -1 behind the list; cap = prop_sample_num.
+ *    sampled = 0: every good cell in row-major (t, k) order, cut at cap; n_events[v] = the uncut count (`*_select_list_eval`).
+ *    sampled = 1: cell p = t * K + k draws word p & 3 of Philox-4x32-10 with counter (p >> 2, draw[v], 7, 0) and key (seed lo, seed hi) -- site 7
+ *    of echr_amd/philox.py; the min(n_good, cap) cells with the smallest (word, p) are listed in ascending (word, p) order: a uniform subset
+ *    in uniform order up to ties of words, which position breaks; n_events[v] = the listed count.  A video's list depends on its own cells,
+ *    seed and draw[v] alone.  Bitwise reproducible. */
+#define ECHR_TARGETS_MAX_GT 1024
+#define ECHR_TARGETS_MAX_VIDEOS 65535
+#define ECHR_TARGETS_MAX_K 65536
+#define ECHR_PROP_MAX_SAMPLE 1024
+int echr_tap_targets_batch(const int32_t* row_offset, const int32_t* gt_offset, const int32_t* gt, int32_t V, int32_t T_tot, int32_t G_tot,
+                           int32_t G_max, int32_t K, double iou_threshold, double iou_threshold_good, float* iou, int32_t* gts_index,
+                           float* tap_masks, float* tap_labels, int32_t* good_gt, int32_t* n_good, void* stream);
+int echr_prop_events_batch(const int32_t* good_gt, const int32_t* row_offset, int32_t V, int32_t T_tot, int32_t K, int32_t cap, int32_t sampled,
+                           uint64_t seed, const int32_t* draw, int32_t* events, int32_t* n_events, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * SST proposal encoder.  Replaces models/sst_model.py:31-40 (nn.LSTM over one video + Linear + sigmoid)
  * and TAPModelCriterion (misc/utils.py:78-99).  Parameters use nn.LSTM's layout: w_ih[l] [4H, D or H], w_hh[l] [4H,H],
