@@ -273,6 +273,9 @@ SYMBOLS = [
     ('echr_densecap_reduce', i32, [C.POINTER(DensecapArgs), C.c_void_p]),
     ('echr_tap_targets_batch', i32, [c_f, c_f, c_f, i32, i32, i32, i32, i32, C.c_double, C.c_double, c_f, c_f, c_f, c_f, c_f, c_f, C.c_void_p]),
     ('echr_prop_events_batch', i32, [c_f, c_f, i32, i32, i32, i32, i32, C.c_uint64, c_f, c_f, c_f, C.c_void_p]),
+    ('echr_nms_segments_batch', i32, [c_f, c_f, c_f, c_f, i32, i32, i32, C.c_double, i32, c_f, c_f, C.c_void_p]),
+    ('echr_ext_proposals_batch', i32, [c_f, c_f, c_f, c_f, c_f, c_f, c_f, i32, i32, i32, i32, i32, i32, C.c_double, i32, C.c_uint64, c_f, c_f, i32,
+                                       c_f, c_f, c_f, c_f, c_f, C.c_void_p]),
     ('echr_sat_ws_floats', i64, [C.POINTER(SatArgs)]),
     ('echr_sat_ws_bwd_floats', i64, [C.POINTER(SatArgs)]),
     ('echr_sat_fwd', i32, [C.POINTER(SatArgs), C.POINTER(Dropout), C.c_void_p]),

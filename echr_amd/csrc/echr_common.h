@@ -66,6 +66,9 @@ __device__ __forceinline__ unsigned philox_word(unsigned elem, unsigned step, un
 
 // site 7 (echr_amd/philox.py SITE_PROP) is no dropout site: the sampling key of a good proposal cell (targets.hip), step = the video's draw id
 constexpr unsigned SITE_PROP = 7u;
+// site 8 (echr_amd/philox.py SITE_CROP): the crop offset of an over-long external proposal (extprops.hip), element = its video-local index,
+// step = the video's draw id
+constexpr unsigned SITE_CROP = 8u;
 
 // multiplicative dropout factor (0 or scale; 1 when inactive) for flat element `elem` of a site/step
 __device__ __forceinline__ float drop_mult(const DropCfg& d, unsigned elem, unsigned step, unsigned site) {

@@ -7,7 +7,8 @@ round trip through python lists.
 
 `caption_videos` is the same flow over V videos in one pass: one batched SST call, one batched selection launch
 (echr_top_proposals_batch / _nms_batch, a workgroup per video), one caption pass over a VideoBatch.  `caption_videos_beam` is that flow
-with the captions decoded by beam search (CaptionGenerator.beam_batch).
+with the captions decoded by beam search (CaptionGenerator.beam_batch).  With flag_eval_what='SOTA_TEP' the events of both come from an
+external proposal list instead of the score grid (echr_amd.extprops.select).
 """
 import ctypes as C
 
@@ -80,7 +81,7 @@ def gettop1000_nms(pred_proposals, tap_masks, cg_gts, duration, featstamp_to_tim
 
 
 def caption_video(tap_model, cg_model, c3d_feats, lda_feats, duration, featstamp_to_time, vocab=None, tap_masks=None, cg_gts=(),
-                  topN=1000, nms_threshold=0.0, val_score_thres=0.0, flag_eval_what='tap_cg', beam_size=1):
+                  topN=1000, nms_threshold=0.0, val_score_thres=0.0, flag_eval_what='tap_cg', beam_size=1, *, ext_proposals=None, ext_seed=0):
     """One video through the reference's evaluation flow (eval_utils.py:51-53,106-167 for flag_eval_what 'tap_cg' / 'tap'):
     SST -> proposal selection (greedy NMS when nms_threshold != 0, else score threshold) -> greedy captions -> the per-proposal
     records of result.json.  Everything between the two host reads (proposal count, caption lengths) stays on the GPU.
@@ -88,7 +89,13 @@ def caption_video(tap_model, cg_model, c3d_feats, lda_feats, duration, featstamp
     Returns (vid_info, extras): vid_info is the reference's list of dicts (sentence, timestamp, sentence_confidence, proposal_score,
     re_score, num); extras carries the tensors (tap_feats, pred_proposals, seq, ind_select_list, soi_select_list).
     beam_size > 1 captions by beam search (the reference's --beam_size); sentence_confidence is then each caption's beam score (the sum
-    of its token log-probs, <eos> included)."""
+    of its token log-probs, <eos> included).
+
+    flag_eval_what='SOTA_TEP' with ext_proposals=(timestamps [P, 2] in seconds, scores [P]) captions external proposals instead
+    (extprops.select on this one video, draw id 0, the crop keyed by `ext_seed`; see caption_videos): 'timestamp' is the external segment,
+    proposal_score the external score, cg_select_list = cg_gts[e, e - s - 1].  scores None: the reference skips the video ([])."""
+    if (flag_eval_what == 'SOTA_TEP') != (ext_proposals is not None):
+        raise ValueError("flag_eval_what='SOTA_TEP' and ext_proposals=(timestamps, scores) go together")
     if not c3d_feats.is_cuda:
         raise L.EchrHipError('caption_video runs on the GPU: move the models and features with .cuda()')
     nfeats = c3d_feats.shape[0]
@@ -97,7 +104,14 @@ def caption_video(tap_model, cg_model, c3d_feats, lda_feats, duration, featstamp
         if tap_masks is None:
             K = pred_proposals.shape[1]
             tap_masks = (np.arange(nfeats)[:, None] >= np.arange(K)[None, :]).astype(np.float32)
-        if nms_threshold != 0:
+        if ext_proposals is not None:
+            from . import extprops
+            sel = extprops.select([dict(SOTA_timestamps=ext_proposals[0], SOTA_Prop_score=ext_proposals[1], duration=duration, nfeats=nfeats)],
+                                  int(pred_proposals.shape[1]), topN, nms_threshold, val_score_thres, seed=ext_seed, device=c3d_feats.device)
+            ind_select_list, soi_select_list = sel.ind[0].tolist(), sel.soi[0].tolist()
+            cg_select_list = [cg_gts[e, e - s - 1] for e, (s, _) in zip(ind_select_list, soi_select_list)] if len(cg_gts) else []
+            good_time_stamps, tap_prob = sel.timestamps[0].tolist(), sel.scores[0].tolist()
+        elif nms_threshold != 0:
             ind_select_list, soi_select_list, cg_select_list, good_time_stamps, tap_prob = gettop1000_nms(
                 pred_proposals, tap_masks, cg_gts, duration, featstamp_to_time, overlap=nms_threshold, topN=topN)
         else:
@@ -178,7 +192,7 @@ def _to_dev(x, dev):
 
 
 def caption_videos(tap_model, cg_model, videos, featstamp_to_time, vocab=None, topN=1000, nms_threshold=0.0, val_score_thres=0.0,
-                   flag_eval_what='tap_cg', event_group_rows=EVENT_GROUP_ROWS):
+                   flag_eval_what='tap_cg', event_group_rows=EVENT_GROUP_ROWS, *, ext_seed=0):
     """`caption_video` over V videos in ONE evaluation pass: SST.forward_batch over the concatenated features -> batched proposal selection
     (a workgroup per video; greedy NMS when nms_threshold != 0, else score threshold) -> one greedy caption pass over a VideoBatch
     (forward_batch(mode='eval', event_group_rows=...)).  Runs under no_grad with both models switched to eval mode for the call.
@@ -187,6 +201,15 @@ def caption_videos(tap_model, cg_model, videos, featstamp_to_time, vocab=None, t
     and 'cg_gts'.  flag_eval_what='cg' captions given events instead of selected ones: every video then carries 'ind', 'soi' and
     'timestamps' (the reference's gts_ind_select_list / gts_soi_select_list / gt_timestamps; proposal_score is 1).  'tap' skips the
     caption pass (sentence 0).
+
+    flag_eval_what='SOTA_TEP' captions EXTERNAL proposals (eval_utils.py:76-104): every video carries 'SOTA_timestamps'
+    [P_v, 2] in seconds and 'SOTA_Prop_score' [P_v], optionally 'SOTA_draw' (its crop stream id, default its position).  The SST still runs
+    (its states feed the VH / EH / CH contexts); the events come from extprops.select with K the encoder's anchor count and topN,
+    nms_threshold, val_score_thres passed through (greedy cluster NMS over the timestamps when nms_threshold > 0, score threshold, topN,
+    featstamps, crop of over-long proposals keyed by `ext_seed`).  'timestamp' is the external segment, proposal_score the external score.
+    cg_select_list = cg_gts[e, e - s - 1] for rows (s, e): the reference's own off-by-one against the anchor convention cg_gts[n, n - s] of
+    the other modes (dataloader.py:522 indexes k = e - s - 1 where anchor k of row e starts at e - k), reproduced as it is.  A video whose
+    score list is None or missing, or with at most one row, is skipped as in the reference: [] and listed in extras['bad'].
 
     Returns (vid_infos, extras).  vid_infos[v] is the list caption_video returns for video v alone (sentence, timestamp,
     sentence_confidence, proposal_score, re_score, num); a video without a pick, or whose rows all emit <eos> first, gets [].  The batched
@@ -205,14 +228,15 @@ def caption_videos(tap_model, cg_model, videos, featstamp_to_time, vocab=None, t
         cg_loss, _ = extras['batch'].criterion(cg_crit, logp)
         tap_loss, _ = utils.tap_criterion_batch(tap_crit, extras['pred_proposals'], tap_masks, tap_labels, w1, extras['row_offset'])"""
     return _caption_videos_checked(tap_model, cg_model, videos, featstamp_to_time, vocab, topN, nms_threshold, val_score_thres, flag_eval_what,
-                                   event_group_rows)
+                                   event_group_rows, ext_seed=ext_seed)
 
 
 def caption_videos_beam(tap_model, cg_model, videos, featstamp_to_time, beam_size, vocab=None, topN=1000, nms_threshold=0.0, val_score_thres=0.0,
-                        flag_eval_what='tap_cg', event_group_rows=EVENT_GROUP_ROWS, max_rows=8192):
+                        flag_eval_what='tap_cg', event_group_rows=EVENT_GROUP_ROWS, max_rows=8192, *, ext_seed=0):
     """`caption_videos` with the captions decoded by beam search (the reference's eval.py --beam_size): the same SST call, selection call
     and VideoBatch, then CaptionGenerator.beam_batch(batch, beam_size, event_group_rows, max_rows) instead of the greedy pass.  `max_rows`
     bounds the decode's workspace: it runs once per run of consecutive videos with at most that many events * beam_size rows (None: once).
+    flag_eval_what='SOTA_TEP' runs the same external-proposal selection as caption_videos (`ext_seed` keys its crop).
 
     vid_infos[v] is what caption_video(beam_size=) returns for video v alone: seq / cg_prob cut to the video's own width
     video_words[v], sentence_confidence the beam score (the sum of the caption's token log-probs, <eos> included).  A video whose
@@ -222,14 +246,14 @@ def caption_videos_beam(tap_model, cg_model, videos, featstamp_to_time, beam_siz
     Host reads per call do not grow with V: the selection reads, one video_words read per run, the batch's sequences and scores."""
     B = EF._check_beam_size(beam_size, cg_model.lm_model.vocab_size + 1)
     return _caption_videos_checked(tap_model, cg_model, videos, featstamp_to_time, vocab, topN, nms_threshold, val_score_thres, flag_eval_what,
-                                   event_group_rows, B, max_rows)
+                                   event_group_rows, B, max_rows, ext_seed=ext_seed)
 
 
 def _caption_videos_checked(tap_model, cg_model, videos, featstamp_to_time, vocab, topN, nms_threshold, val_score_thres, flag_eval_what,
-                            event_group_rows, beam=None, max_rows=None):
+                            event_group_rows, beam=None, max_rows=None, ext_seed=0):
     """The argument checks of caption_videos / caption_videos_beam, then _caption_videos under no_grad with both models in eval mode."""
-    if flag_eval_what not in ('tap_cg', 'tap', 'cg'):
-        raise ValueError("flag_eval_what=%r: caption_videos runs 'tap_cg', 'tap' and 'cg'" % (flag_eval_what,))
+    if flag_eval_what not in ('tap_cg', 'tap', 'cg', 'SOTA_TEP'):
+        raise ValueError("flag_eval_what=%r: caption_videos runs 'tap_cg', 'tap', 'cg' and 'SOTA_TEP'" % (flag_eval_what,))
     videos = list(videos)
     if not videos:
         raise ValueError('a batch needs at least one video')
@@ -248,14 +272,14 @@ def _caption_videos_checked(tap_model, cg_model, videos, featstamp_to_time, voca
     try:
         with torch.no_grad():
             return _caption_videos(tap_model, cg_model, videos, featstamp_to_time, vocab, topN, nms_threshold, val_score_thres, flag_eval_what,
-                                   event_group_rows, V, dev, rows, beam, max_rows)
+                                   event_group_rows, V, dev, rows, beam, max_rows, ext_seed)
     finally:
         tap_model.rnn.dropout = sst_dropout
         cg_model.train(cg_training)
 
 
 def _caption_videos(tap_model, cg_model, videos, featstamp_to_time, vocab, topN, nms_threshold, val_score_thres, flag_eval_what, event_group_rows,
-                    V, dev, rows, beam=None, max_rows=None):
+                    V, dev, rows, beam=None, max_rows=None, ext_seed=0):
     c3d_all = torch.cat([_to_dev(v['c3d'], dev) for v in videos], 0)
     lda_all = torch.stack([_to_dev(v['lda'], dev).reshape(-1) for v in videos], 0)
     tap_all, scores = tap_model.forward_batch(c3d_all, rows)
@@ -268,6 +292,16 @@ def _caption_videos(tap_model, cg_model, videos, featstamp_to_time, vocab, topN,
         inds = [np.asarray(v['ind'], dtype=np.int64).reshape(-1) for v in videos]
         probs = [[1] * len(s) for s in sois]
         stamps = [list(v['timestamps']) for v in videos]
+    elif flag_eval_what == 'SOTA_TEP':
+        from . import extprops
+        ext = [dict(SOTA_timestamps=v.get('SOTA_timestamps'), SOTA_Prop_score=v.get('SOTA_Prop_score'), duration=v['duration'],
+                    nfeats=int(rows[i + 1] - rows[i])) for i, v in enumerate(videos)]
+        sel = extras['selection'] = extprops.select(ext, int(scores.shape[1]), topN, nms_threshold, val_score_thres, seed=ext_seed,
+                                                    draw=[int(v.get('SOTA_draw', i)) for i, v in enumerate(videos)], device=dev)
+        extras['bad'] = sel.bad
+        sois, inds = sel.soi, sel.ind
+        probs = [s.tolist() for s in sel.scores]
+        stamps = [t.tolist() for t in sel.timestamps]
     else:
         masks = [v.get('tap_masks') for v in videos]
         if any(m is not None for m in masks) and not all(m is not None for m in masks):
@@ -290,9 +324,10 @@ def _caption_videos(tap_model, cg_model, videos, featstamp_to_time, vocab, topN,
             probs = [conf[eo[v]:eo[v + 1]].tolist() for v in range(V)]
         stamps = [[featstamp_to_time(int(s), int(e), int(rows[v + 1] - rows[v]), videos[v]['duration']) for s, e in sois[v]] for v in range(V)]
     per_video = []
+    sota = 1 if flag_eval_what == 'SOTA_TEP' else 0          # dataloader.py:522 reads cg_gts[e, e - s - 1]
     for v in range(V):
         gts = videos[v].get('cg_gts', ())
-        cg_sel = [gts[n, n - s] for n, (s, _) in zip(inds[v].tolist(), sois[v].tolist())] if len(gts) else []
+        cg_sel = [gts[n, n - s - sota] for n, (s, _) in zip(inds[v].tolist(), sois[v].tolist())] if len(gts) else []
         per_video.append(dict(ind_select_list=inds[v].tolist(), soi_select_list=sois[v].tolist(), cg_select_list=cg_sel, seq=None, cg_prob=None))
     extras['per_video'] = per_video
     vid_infos = [[] for _ in range(V)]
@@ -367,7 +402,9 @@ def gettopN_nms(props, prop_scores, sent_score, nms_overlap=0.999, topN=1000):
     sent_score = np.asarray(sent_score)
     start, end = props[:, 0], props[:, 1]
     length = (end - start + 1e-3).astype(float)
-    alive = np.argsort(prop_scores)                 # ascending; the current best is the last entry (same sort call as the reference)
+    # ascending; the current best is the last entry.  The reference's np.argsort is its unstable default; a stable sort is one of that
+    # call's possible outcomes on tied scores, the only one on distinct scores, and the rule the device states (extprops.nms)
+    alive = np.argsort(prop_scores, kind='stable')
     pick = []
     while alive.size and len(pick) < topN:
         best = alive[-1]

@@ -26,6 +26,8 @@ SITE_SST = 5       # [T, H]     p = rnn_dropout (SST inter-layer dropout; step c
 SITE_SAMPLE = 6    # [N]        the multinomial draw of (row, step): element = row (batch-global in a multi-video batch), offset 0
 SITE_PROP = 7      # [T_v * K]  the sampling key of a good proposal cell (csrc/targets.hip): element = t * K + k local to the video, step = the
                    # video's draw id, offset 0, the call's seed as the key; the cells with the smallest (word, element) are the sample
+SITE_CROP = 8      # [P_v]      the crop offset of an over-long external proposal (csrc/extprops.hip): element = the proposal's video-local index,
+                   # step = the video's draw id, offset 0, the call's seed as the key; r = (word * n) >> 32 is uniform in [0, n)
 
 _M0 = np.uint64(0xD2511F53)
 _M1 = np.uint64(0xCD9E8D57)

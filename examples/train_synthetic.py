@@ -44,6 +44,10 @@ built on the device by echr_amd.targets.build (dataloader.get_vid_data / get_shu
 thresholded maps, a sample of `--events` good proposals per video, a new draw every iteration).  Videos without a good proposal are skipped
 as train.py:261 does.
 
+`--ext_proposals P` makes the evaluation leg caption P synthetic external proposals of video 0 -- (start s, end s) segments with a score each,
+as a temporal-event-proposal file gives them -- through eval_utils.caption_video(flag_eval_what='SOTA_TEP', ext_proposals=...): greedy cluster
+NMS over the timestamps, topN, featstamps and the crop of over-long proposals on the device (echr_amd.extprops).
+
 usage: python examples/train_synthetic.py [--iters 20] [--m_batch 2] [--joint] [--pre_tap] [--self_critical [--reward ciderd]] [--save /tmp/echr_ckpt.pth]
                                           [--resume /tmp/echr_ckpt.pth]
 """
@@ -332,6 +336,8 @@ def main(argv=None):
                                                               '--events sampled caption events are built on the device (echr_amd.targets)')
     ap.add_argument('--gt_segments', type=int, default=4, help='--gt_targets: ground-truth segments per synthetic video')
     ap.add_argument('--target_seed', type=int, default=0, help='--gt_targets: the key of the proposal sampling')
+    ap.add_argument('--ext_proposals', type=int, default=0, metavar='P', help="the evaluation leg captions P synthetic EXTERNAL proposals of "
+                                                                              "video 0 (seconds + scores; flag_eval_what='SOTA_TEP') instead of its ready-made events")
     ap.add_argument('--segments', type=int, default=32)
     ap.add_argument('--vocab', type=int, default=500)
     ap.add_argument('--lr', type=float, default=5e-4)
@@ -483,7 +489,20 @@ def main(argv=None):
         if a.gt_targets:          # caption the ground-truth events (the reference's gts_*_select_list)
             from echr_amd import targets
             v = dict(v, **targets.gt_events(v['featstamps']))
-        seq, logp = cg_model(tap_feats, c3d, lda, [], v['ind'], v['soi'], mode='eval')
+        if a.ext_proposals:          # somebody else's proposals: NMS over the timestamps, score threshold, topN, featstamps, crop (extprops.select)
+            from echr_amd import eval_utils
+            rs = np.random.RandomState(a.target_seed)
+            start_s = rs.uniform(0.0, 50.0, size=a.ext_proposals)
+            stamps = np.stack([start_s, start_s + rs.uniform(1.0, 30.0, size=a.ext_proposals)], 1)
+            info, extras = eval_utils.caption_video(tap_model, cg_model, c3d, lda, 60.0, None, flag_eval_what='SOTA_TEP', topN=8, nms_threshold=0.7,
+                                                    ext_proposals=(stamps, rs.permutation(a.ext_proposals) / float(a.ext_proposals)),
+                                                    ext_seed=a.target_seed)
+            seq = extras['seq'] if extras['seq'] is not None else []
+            if not a.quiet:
+                print('external proposals: %d of %d selected, rows' % (len(extras['soi_select_list']), a.ext_proposals), extras['soi_select_list'][:3])
+                print('captioned (seconds, score):', [(r['timestamp'], round(r['proposal_score'], 3)) for r in info[:3]])
+        else:
+            seq, logp = cg_model(tap_feats, c3d, lda, [], v['ind'], v['soi'], mode='eval')
     if not a.quiet:
         print('greedy captions (token ids) of video 0:', seq[:3].tolist() if len(seq) else seq)
     if a.save and (ranks is None or ranks[0] == 0):

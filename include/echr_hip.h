@@ -583,6 +583,42 @@ int echr_tap_targets_batch(const int32_t* row_offset, const int32_t* gt_offset, 
 int echr_prop_events_batch(const int32_t* good_gt, const int32_t* row_offset, int32_t V, int32_t T_tot, int32_t K, int32_t cap, int32_t sampled,
                            uint64_t seed, const int32_t* draw, int32_t* events, int32_t* n_events, void* stream);
 
+/* Captioning external temporal-event proposals (the reference's flag_eval_what = 'SOTA_TEP') over a multi-video batch.
+ * Video v owns the proposals prop_offset[v] .. prop_offset[v + 1] - 1 (possibly none, at most ECHR_EXTPROPS_MAX_P) of stamps [P_tot, 2]
+ * (start, end in seconds) and prop_scores [P_tot], both fp64.  All vectors are device memory; that the offsets grow, that every value is
+ * finite and that end >= start is the caller's contract (echr_amd.extprops checks its host copies) -- offsets outside the buffers select
+ * nothing and no access leaves the buffers.  P_max is the caller's statement of the largest per-video count: what the library can refuse
+ * before the launch.
+ *  echr_nms_segments_batch: eval_utils.gettopN_nms (eval_utils.py:230-256) per video, a workgroup each.  area_i = (t2_i - t1_i) + 1e-3; the
+ *    alive set starts as everything; a round takes the alive proposal i with the largest prop_score (ties: the largest index -- the last
+ *    element of a stable ascending sort) and forms for every alive j, i included,
+ *      wh = max(0, (min(t2_i, t2_j) - max(t1_i, t1_j)) + 1e-3);  o = wh / ((area_i + area_j) - wh)
+ *    in fp64 in this order (no product: the comparison bits are numpy's).  The cluster is the alive j with o >= nms_overlap; the round's pick
+ *    is its member with the largest sent_score (null: prop_scores), ties to the member that comes first in ascending (prop_score, index)
+ *    order; alive becomes the alive j with o <= nms_overlap -- a proposal whose o equals the threshold is clustered AND stays alive, as in
+ *    the reference.  Rounds end when nothing is alive or `rounds` picks are made.  pick[v, 0 .. count[v] - 1] (row stride `rounds`) are the
+ *    picks in round order, video-local indices, duplicates as they occur, -1 behind the list.  0 <= nms_overlap < 1: at 1 the best never
+ *    leaves the alive set.
+ *  echr_ext_proposals_batch: the selection of eval_utils.py:88-104, then dataloader.timestamp_to_featstamp and the crop of
+ *    dataloader.py:515-520.  A video's proposals are walked in file order; i is kept if it occurs in pick[v, 0 .. pick_count[v] - 1] (pick
+ *    null: every proposal is picked, the nms_threshold <= 0 branch) and prop_scores[i] >= val_score_thres (fp64); the walk ends after topN
+ *    kept.  Per kept proposal, with T = rows[v] (a video with T < 2 selects nothing) and duration[v] > 0, in fp64:
+ *      s = clamp(round((start / duration) * T), 0, T - 2);  e = clamp(round((end / duration) * T), s + 1, T - 1)      (round: half away from zero)
+ *    and, with crop = 1, where e - s >= K + 1:  r = (w * (e - s - K + 1)) >> 32,  s = s + r,  e = s + K,  w = word i & 3 of Philox-4x32-10
+ *    with counter (i >> 2, draw[v], 8, 0) and key (seed lo, seed hi) -- site 8 of echr_amd/philox.py.  A video's list depends on its own
+ *    proposals, seed and draw[v] alone.  Outputs, compacted over the batch in video order: index (the kept video-local i, ascending per
+ *    video), ind = e, soi = (s, e + 1), each of capacity `cap` entries (at least the sum of min(P_v, topN)); count[v] and event_offset[v],
+ *    with the total in count[V] and event_offset[V].  stage is a scratch of 3 * P_tot int32. */
+#define ECHR_EXTPROPS_MAX_P 4096
+#define ECHR_EXTPROPS_MAX_VIDEOS 65535
+int echr_nms_segments_batch(const double* stamps, const double* prop_scores, const double* sent_score, const int32_t* prop_offset, int32_t V,
+                            int32_t P_tot, int32_t P_max, double nms_overlap, int32_t rounds, int32_t* pick, int32_t* count, void* stream);
+int echr_ext_proposals_batch(const double* stamps, const double* prop_scores, const int32_t* prop_offset, const int32_t* rows,
+                             const double* duration, const int32_t* pick, const int32_t* pick_count, int32_t rounds, int32_t V, int32_t P_tot,
+                             int32_t P_max, int32_t K, int32_t topN, double val_score_thres, int32_t crop, uint64_t seed, const int32_t* draw,
+                             int32_t* stage, int32_t cap, int32_t* count, int32_t* event_offset, int32_t* index, int32_t* ind, int32_t* soi,
+                             void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * SST proposal encoder.  Replaces models/sst_model.py:31-40 (nn.LSTM over one video + Linear + sigmoid)
  * and TAPModelCriterion (misc/utils.py:78-99).  Parameters use nn.LSTM's layout: w_ih[l] [4H, D or H], w_hh[l] [4H,H],
